@@ -2,6 +2,7 @@
 """bench.py -- blind-bid Bulletproofs hot path on MI355X (one process per GPU).
 
     python bench.py --gpus N --steps K --warmup W [--workload prove|verify|verify_aggregated|msm|stream] [--batch B] [--items N_ITEMS]
+                    [--dump-outputs DIR]
 
 A "step" is one pass of the hot path over one batch of B synthetic bids whose inputs are already resident in HBM.
   workload prove (default): BASELINE.json configs[2] -- full R1CS prove of B = 1024 bids (gadget witness, Merlin, commitment
@@ -21,15 +22,11 @@ Launch: `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environme
 RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, backend nccl = RCCL) before this process has touched the GPU, relays rank 0's JSON
 line and fails if any rank fails or the line does not say n_gpus == N.  Under torchrun (WORLD_SIZE set) it is one of the ranks;
 --gpus must then equal WORLD_SIZE.
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed its caller as DIR/<name>.npy (float32, one
+value per byte of a proof record / MSM point, one per verification status); the inputs are seeded, so two builds run with the same
+arguments can be compared output for output.
 """
 import os
-
-# The engine keeps four HIP streams busy per GPU (the caller's, the opening stage's, two more heavy-stage slices) -- HIP's default
-# number of hardware queues.  Any other stream used before it (torch.distributed's RCCL stream in the multi-rank run) makes
-# two of them share a queue and serialise: measured 84.5 vs 61.6 ms per batch (tools/hwq_probe.py).  Must be set before the HIP
-# runtime initialises, i.e. before the first torch.cuda call.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
-
 import argparse
 import json
 import subprocess
@@ -173,6 +170,55 @@ def exclusive_pass(wl, bbp, torch, device, dev_index, alu_peak, steps=3, ctx2=No
             ctx2.close()
 
 
+DUMP_CAP_BYTES = 64 * 1000 * 1000
+
+
+def last_step_outputs(wl):
+    """What the workload's last step handed its caller, as named host arrays with one row per proof.  Read here from the buffers
+    the workloads of bench_workloads.py write, so that this script dumps any build of the project whose workloads have them."""
+    import numpy as np
+    import bench_workloads as bw
+    if isinstance(wl, bw.ProveWorkload):
+        out_dev = wl.sets[(wl.k - 1) % len(wl.sets)][2]  # the input set the last step proved into
+        return {"proof_records": out_dev.view(wl.B, wl.rec).cpu().numpy()}
+    if isinstance(wl, bw.VerifyWorkload):  # (and the aggregated form) the statuses of the last step's lane
+        return {"verify_status": wl.status.cpu().numpy()}
+    if isinstance(wl, bw.MsmWorkload):
+        return {"msm_" + name: o.cpu().numpy() for name, o in zip(("A_I1", "A_O1", "S1"), wl.out)}
+    if isinstance(wl, bw.StreamWorkload):
+        sl = wl.slots[(wl.k - 1) % wl.depth]  # the last chunk's records and flags, on the host after drain()
+        return {"proof_records": sl["h_rec"].numpy().reshape(wl.B, wl.rec).copy(), "verify_status": sl["h_st"].numpy().copy()}
+    if isinstance(wl, bw.StubWorkload):
+        # steps run so far (warmup + timed), and 4 KiB of seeded bytes per unit: enough rows to exercise the size cap
+        return {"steps_run": np.array([getattr(wl, "k", -1)], dtype=np.int64),
+                "records": np.random.default_rng(wl.units_per_step).integers(0, 256, (wl.units_per_step, 4096), dtype=np.uint8)}
+    raise SystemExit("bench.py --dump-outputs: no outputs known for workload %s" % type(wl).__name__)
+
+
+def dump_outputs(wl, out_dir, cap=DUMP_CAP_BYTES):
+    """last_step_outputs(wl) as float32 .npy files under out_dir, at most `cap` bytes in all.  Arrays have one row per proof; if they
+    do not fit, every array keeps the same share of its rows, picked with a fixed seed and saved beside it as <name>_rows.npy."""
+    import numpy as np
+    arrays = {name: np.asarray(a) for name, a in last_step_outputs(wl).items()}
+    room = cap - 4096 * len(arrays)  # .npy headers, two files per array at most
+    full = sum(4 * a.size for a in arrays.values())
+    share = 1.0
+    if full > room:
+        share = room / sum(a.shape[0] * (4 * (a.size // max(a.shape[0], 1)) + 8) for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = 0
+    for name, a in sorted(arrays.items()):
+        if share < 1.0 and a.ndim and a.shape[0] > 1:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, int(a.shape[0] * share)), replace=False))
+            a = a[rows]
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+            written += rows.nbytes
+        a = a.astype(np.float32)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written += a.nbytes
+    return written
+
+
 def launch_ranks(args, argv):
     """--gpus N > 1 without a launcher: start N fresh ranks (this process has not touched the GPU), relay rank 0's JSON line."""
     import socket
@@ -222,13 +268,14 @@ def launch_ranks(args, argv):
 def build_all(check_only=False):
     """Compile (or, with check_only, insist on up-to-date) native artefacts.  Runs BEFORE the first torch.cuda / HIP call of this
     process, under a file lock so that concurrently started ranks build once: a profiler's preloaded library must never see this
-    process spawn a compiler after the GPU is initialised (tools/profile_round.sh passes --no-build)."""
+    process spawn a compiler after the GPU is initialised (tools/profile_round.sh passes --no-build).  Up-to-date artefacts need
+    neither a compiler nor the lock: nothing is written then, and a built tree may be read-only."""
     import fcntl
     import __graft_entry__ as ge
-    if check_only:
-        stale = ge.stale_artefacts()
-        if stale:
-            raise SystemExit("bench.py --no-build: stale or missing artefacts %r (run `python __graft_entry__.py` first)" % stale)
+    stale = ge.stale_artefacts()
+    if check_only and stale:
+        raise SystemExit("bench.py --no-build: stale or missing artefacts %r (run `python __graft_entry__.py` first)" % stale)
+    if not stale:
         return
     with open(os.path.join(ROOT, ".build.lock"), "w") as lk:
         fcntl.flock(lk, fcntl.LOCK_EX)
@@ -258,7 +305,10 @@ def main():
     ap.add_argument("--no-also", action="store_true", help="skip the secondary verify / msm-stage measurements")
     ap.add_argument("--no-build", action="store_true", help="do not compile anything: fail if the native artefacts are stale")
     ap.add_argument("--no-exclusive", action="store_true", help="skip the exclusive (one-slice) pass behind roofline.exclusive")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args, sys.argv[1:]))
@@ -340,6 +390,10 @@ def main():
         per_rank_s = [float(t.item()) for t in allt]
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     dt = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # before anything else runs on the workload: the gather and the secondary workloads below reuse its buffers
+        n = dump_outputs(wl, args.dump_outputs)
+        sys.stderr.write("bench.py: %.1f MB of outputs of the last timed step in %s\n" % (n / 1e6, args.dump_outputs))
     # The path's one collective: every rank's proof records / flags to rank 0 in global proof order, after the timed
     # region.  Timed on its own between barriers -- the first call also builds the point-to-point connections, the second is the
     # steady-state cost -- and the tensor rank 0 received is CHECKED: a sample from every rank's block against the oracle.

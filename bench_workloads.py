@@ -152,11 +152,13 @@ class StubWorkload(_Base):
     metric, unit, data = "stub (launcher plumbing test, not a measurement)", "steps/s", "stub"
 
     def __init__(self, batch):
+        self.k = 0  # steps run (bench.py --dump-outputs reports it)
         self.units_per_step = batch
         self.config = {"workload": "stub: sleeps 1 ms per step", "batch_per_gpu": batch}
 
     def step(self, stream):
         time.sleep(0.001)
+        self.k += 1
 
     def check(self):
         pass

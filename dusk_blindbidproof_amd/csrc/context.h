@@ -175,7 +175,7 @@ struct bbp_ctx {
 #ifndef BBP_VLANES
 #define BBP_VLANES 4
 #endif
-    static constexpr int VLANES = BBP_VLANES;    // four lanes -- with enough hardware queues (GPU_MAX_HW_QUEUES >= 16), see below
+    static constexpr int VLANES = BBP_VLANES;    // four lanes -- each with a hardware queue of its own at best, see below
     static constexpr int FAMILIES = 1 + VLANES;  // prover | one per verifier lane
     hipStream_t last_stream[FAMILIES] = {};
     hipEvent_t ev_last[FAMILIES] = {};
@@ -186,7 +186,7 @@ struct bbp_ctx {
     // device-API callers pick a lane by passing that lane's stream (bbp_context_verify_stream), any other stream is lane 0.
     // FOUR lanes (round 3; two before).  A 1024-proof call is a chain of ~10 ms of kernels of which only the 4 ms MSM accumulate fills
     // the machine, so several chains must be in flight.  A third lane first measured 8-10 % SLOWER than two -- because its stream
-    // shared a HARDWARE QUEUE with another lane's (GPU_MAX_HW_QUEUES was 8, the context creates 9+ streams): with 16 queues, 1024
+    // shared a HARDWARE QUEUE with another lane's (fewer queues than the context's 9+ streams): with a queue per stream, 1024
     // verifications per call take 6.3 ms on two lanes, 5.45 on three, 5.17 on four, 5.45 / 5.25 on five / six.
     struct VLane {
         hipStream_t stream = nullptr;

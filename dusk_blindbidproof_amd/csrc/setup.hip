@@ -109,14 +109,14 @@ static void mimc_constants_host(std::vector<uint8_t>& out) {
 namespace bbp {
 // ---- the library owns its hardware-queue configuration (round 4) ------------------------------------------------------------------
 // A context keeps up to eleven streams (prover: caller's, two opening, three slices, copy; verifier: four lanes); HIP hands hardware
-// queues out in stream-creation order and lets later streams SHARE once GPU_MAX_HW_QUEUES (default 4) are taken -- two busy streams on
-// one queue serialise (prover up to 30 % slower at 4, a verifier lane on a shared queue costs 1024 verifications 7.2 instead of 5.2 ms).
-// The variable is read ONCE, when the HIP runtime initialises in the process.  A host program bound per INTEGRATION.md (Rust, Go, C)
-// would have to know; so bbp_init / bbp_init_all / bbp_pool_init look BEFORE their first HIP call: if the caller's environment has
-// the variable it is left alone; else if HIP / HSA is not up yet in this process (no descriptor on /dev/kfd) the library exports
-// BBP_HWQ_DEFAULT itself; else it is too late, and bbp_describe says so in a WARNING line.
+// queues out in stream-creation order and lets later streams SHARE once the queues the runtime was allowed are taken.  The count is
+// read ONCE, when the HIP runtime initialises in the process.  A host program bound per INTEGRATION.md (Rust, Go, C) would have to
+// know; so bbp_init / bbp_init_all / bbp_pool_init look BEFORE their first HIP call: if the caller's environment has the variable it
+// is left alone; else if HIP / HSA is not up yet in this process (no descriptor on /dev/kfd) the library exports BBP_HWQ_DEFAULT
+// itself; else it is too late, and bbp_describe says so in a WARNING line.  The default is two queues per process: a GPU's queue
+// slots are shared by every process on it, and more queues than slots is a state a shared machine must not be driven into.
 #ifndef BBP_HWQ_DEFAULT
-#define BBP_HWQ_DEFAULT "16"
+#define BBP_HWQ_DEFAULT "2"
 #endif
 static std::atomic<int> g_hwq_state{0};  // 1 caller's environment, 2 set by the library, 3 too late (HIP already initialised, variable unset)
 static bool hsa_is_up() {
@@ -476,22 +476,19 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                           total_b / 1073741824.0, ctx->slices, ctx->tail_round, ctx->rng_coop_below, (int)bbp_ctx::VLANES,
                                           ctx->verify_serial_acc ? "chained" : "free-running", ctx->verify_group, ctx->verify_group ? "" : " (off)");
         // The engine keeps four streams busy during a prove call (caller's, opening stage, two more slices) and four more for
-        // verification (one per lane), out of eleven it creates: HIP's default of four hardware queues makes them share and serialise
-        // (measured 84.5 vs 61.6 ms per prove batch).  How many are best depends on the mix: 8 for prove-dominated host-pointer use
-        // (the UDS server: the seven prover streams are created first and have a queue each; a few percent better than 16 at saturation), 16 for verification on all four lanes through the device API
-        // (1024 per call: 5.2 ms against 7.2 with 8): INTEGRATION.md section 5.  The variable is read when the HIP runtime
-        // initialises, i.e. possibly long before bbp_init.
+        // verification (one per lane), out of eleven it creates; how many hardware queues they get is read when the HIP runtime
+        // initialises, i.e. possibly long before bbp_init (INTEGRATION.md section 5).
         const int hst = hw_queues_state();
         if (off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "hardware queues: GPU_MAX_HW_QUEUES=%s (%s); scratch: %.2f GiB in %llu allocation(s) since bbp_init\n",
                                       hwq ? hwq : "unset",
                                       hst == 2 ? "exported by the library before HIP initialised" : hst == 1 ? "from the caller's environment" : hst == 3 ? "unset and HIP was already initialised" : "?",
                                       ctx->scratch_bytes / 1073741824.0, (unsigned long long)ctx->scratch_allocs);
-        if ((hst == 3 || !hwq || atoi(hwq) < 8) && off + 1 < cap)
+        if ((hst == 3 || !hwq || atoi(hwq) < atoi(BBP_HWQ_DEFAULT)) && off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off,
-                                      "WARNING: GPU_MAX_HW_QUEUES is %s%s: the HIP runtime reads it once, when it initialises; export GPU_MAX_HW_QUEUES=" BBP_HWQ_DEFAULT
+                                      "WARNING: GPU_MAX_HW_QUEUES is %s%s: the HIP runtime reads it once, when it initialises; export the library's default"
                                       " before the process first touches HIP (or call bbp_init first: it does so itself), or streams of this context share "
-                                      "hardware queues and serialise (prover up to ~30 %% slower with the default of 4)\n",
+                                      "fewer hardware queues and serialise\n",
                                       hwq ? hwq : "not set", hst == 3 ? " and HIP was initialised before bbp_init could set it" : "");
         if (free_b < ((size_t)6 << 30) && off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "WARNING: less than 6 GiB of device memory free: a 1024-proof batch needs ~14 GiB of scratch\n");

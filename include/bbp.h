@@ -236,9 +236,10 @@ int32_t bbp_debug_compile_circuit(uint32_t N, uint32_t* n_mul, uint32_t* n_cons)
 
 /* Diagnostics: a short text report of what the context (every member of a pool) runs on and how it is configured -- device, free
  * memory, scheduling knobs -- into buf (NUL-terminated, truncated to cap).  Conditions known to cost throughput silently are
- * reported as lines starting with "WARNING:" (today: GPU_MAX_HW_QUEUES below 8, or unset while HIP was already initialised when
- * the engine was created; little free device memory).  The report also says where the hardware-queue setting came from -- bbp_init
- * exports GPU_MAX_HW_QUEUES=16 itself when the variable is unset and the process has not initialised HIP yet -- and how much
+ * reported as lines starting with "WARNING:" (today: GPU_MAX_HW_QUEUES below the library's default, or unset while HIP was already
+ * initialised when the engine was created; little free device memory).  The report also says where the hardware-queue setting came
+ * from -- bbp_init exports the library's default (two queues) itself when the variable is unset and the process has not initialised
+ * HIP yet -- and how much
  * scratch the context holds in how many allocations (after bbp_reserve that count stands still).
  * Environment, read once per process: BBP_DEBUG_DEVICE_CHECK=1 asserts before every HIP call made for a context that the calling
  * thread's current device is the context's (first multi-GPU bring-up); BBP_TRACE_ALLOC=1 names every scratch buffer that grows. */

@@ -40,3 +40,31 @@ def test_world_size_mismatch_is_refused():
 def test_failing_rank_fails_the_launch():
     p = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--workload", "stream"], {"BBP_BENCH_STUB_FAIL_RANK": "1"})
     assert p.returncode != 0
+
+
+def test_dump_outputs_writes_the_last_step_under_the_cap(tmp_path):
+    """--dump-outputs: float32 .npy files of what the last timed step returned, the same from run to run, at most 64 MB in all
+    (the stub's 4 KiB per unit at --batch 5000 is 82 MB as float32: a seeded sample of its rows is kept, with their indices)."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("run%d" % run)
+        p = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--batch", "5000", "--dump-outputs", str(d)])
+        assert p.returncode == 0, p.stderr[-2000:]
+        files = sorted(os.listdir(d))
+        assert files == ["records.npy", "records_rows.npy", "steps_run.npy"], files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 1000 * 1000
+        got = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+        assert got["steps_run.npy"].tolist() == [7.0]  # --warmup 2 + --steps 5: --steps is the number of timed steps
+        rows = got["records_rows.npy"].astype(np.int64)
+        assert len(rows) == len(got["records.npy"]) and 3000 < len(rows) < 5000 and (np.diff(rows) > 0).all()
+        full = np.random.default_rng(5000).integers(0, 256, (5000, 4096), dtype=np.uint8)
+        assert (got["records.npy"] == full[rows].astype(np.float32)).all()
+        dumps.append(got)
+    assert all((dumps[0][f] == dumps[1][f]).all() for f in dumps[0])
+
+
+def test_steps_must_be_positive():
+    p = _run(["--gpus", "1", "--steps", "0", "--warmup", "0"])
+    assert p.returncode != 0 and "--steps" in p.stderr

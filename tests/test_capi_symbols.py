@@ -73,7 +73,7 @@ def test_init_exports_the_hardware_queue_setting_before_touching_hip(bbp):
         "libc = ctypes.CDLL(None)\n"
         "libc.getenv.restype = ctypes.c_char_p\n"
         "print('RC', rc, 'ENV', libc.getenv(b'GPU_MAX_HW_QUEUES'))\n")
-    for preset, expect in ((None, b"16"), ("8", b"8")):
+    for preset, expect in ((None, b"2"), ("1", b"1")):
         env = {k: v for k, v in os.environ.items() if k != "GPU_MAX_HW_QUEUES"}
         if preset:
             env["GPU_MAX_HW_QUEUES"] = preset

@@ -215,7 +215,17 @@ def test_combiner_under_thread_sanitizer(built):
     """csrc/submit.cpp compiled with -fsanitize=thread behind a stand-in engine: 48 threads, three request classes, prove and
     verify mixed, a batching window and a stagger -- every answer right, one class per batch, max_batch respected, at most two
     batches in flight, and no data race reported by the sanitizer."""
-    p = subprocess.run([built.build_combiner_tsan()], capture_output=True, text=True, timeout=300)
+    import platform
+    import shutil
+    exe = built.build_combiner_tsan()
+    # ThreadSanitizer keeps its shadow memory at fixed addresses; on kernels that randomise mmap with more bits than its runtime
+    # expects it aborts before main ("unexpected memory mapping").  The binary runs with address randomisation off for its own
+    # process (setarch -R, a personality flag of the child only) wherever setarch is there and allowed to set it.
+    cmd = [exe]
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        cmd = [setarch, platform.machine(), "-R", exe]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stdout + p.stderr[-3000:]
     assert "WARNING: ThreadSanitizer" not in p.stderr, p.stderr[-3000:]
     assert "wrong 0, bad batches 0" in p.stdout, p.stdout
@@ -238,8 +248,10 @@ def test_combiner_waits_out_a_lopsided_pair_of_batches(built):
             res[rule] = (int(m.group(1)), int(m.group(2)))
         return res
     # the harness is 600 real threads timed in hundreds of microseconds: on a loaded 8-core box one run in a few dozen lands a batch
-    # boundary elsewhere.  Correctness (wrong 0, live 0) is asserted in every attempt; the batch-size pattern in one of three.
-    for attempt in range(3):
+    # boundary elsewhere, and on a shared host under a CPU quota (16 of 256 cores, load ~30) the rule's run came out 167 / 433,
+    # 202 / 398 and 300 / 300 in three runs.  Correctness (wrong 0, live 0) is asserted in every attempt; the batch-size pattern in
+    # one of six.
+    for attempt in range(6):
         res = once()
         if res[1][0] >= 200 and res[1][1] <= 400 and res[0][0] * 2 < res[0][1]:
             break

@@ -5,7 +5,7 @@
                        [--steps 20 --warmup 4] [--exclusive] [--tag NAME] [--commit SHA] [--out gpurun_out/ab/NAME.jsonl]
     python tools/ab.py --knob variant --values - coop            # "-" = the product library, others = tools/build_variant.py builds
     python tools/ab.py --knob "BBP_A,BBP_B" --values 1,0 0,1      # several environment knobs moved together
-    python tools/ab.py --harness uds --knob hwq --values 8 16 --bench "--connections 3072 --no-verify --ops 110592"   # through the UDS server
+    python tools/ab.py --harness uds --knob hwq --values 1 2 --bench "--connections 3072 --no-verify --ops 110592"   # through the UDS server
     python tools/ab.py --harness script --script tools/midsize.py --knob BBP_RNG_DPP --values 1 0 --bench "256"         # any other tool
 
 Arms alternate inside every repeat (a b a b ...), so box drift and clock state hit both alike.  Every run is one child process

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Does an extra stream used before the engine (as RCCL's is in multi-rank runs) cost throughput?  EXTRA_STREAMS=n [GPU_MAX_HW_QUEUES=8] python tools/hwq_probe.py"""
+"""Does an extra stream used before the engine (as RCCL's is in multi-rank runs) cost throughput?  EXTRA_STREAMS=n [GPU_MAX_HW_QUEUES=1|2] python tools/hwq_probe.py"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch

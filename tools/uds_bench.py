@@ -30,7 +30,7 @@ def main():
     ap.add_argument("--gen-threads", type=int, default=2)
     ap.add_argument("--preconnect", type=int, default=0, help="open loop: connections opened before the clock starts")
     ap.add_argument("--verify-aggregate", type=int, default=0, help="server --verify-aggregate G (0 = one MSM per proof like the reference)")
-    ap.add_argument("--hwq", type=int, default=int(os.environ.get("BBP_SERVER_HWQ", "8")), help="GPU_MAX_HW_QUEUES of the server process")
+    ap.add_argument("--hwq", type=int, default=int(os.environ.get("BBP_SERVER_HWQ", "2")), choices=(1, 2), help="GPU_MAX_HW_QUEUES of the server process")
     ap.add_argument("--devices", default="0", help="server --devices list (a,b,..: device pool)")
     ap.add_argument("--stub", action="store_true", help="CPU box: the tests' stub engine (plumbing check, not a measurement)")
     a = ap.parse_args()

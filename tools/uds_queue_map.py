@@ -5,8 +5,8 @@ bbp-uds-loadgen, stops it, and prints from the trace: Stream_Id -> Queue_Id, lau
 stream (k_open_serial = an opening stream, k_msm_acc = a heavy-stage stream, k_vtranscript = a verifier lane ...), then per queue
 the streams that share it.
 
-    python tools/uds_queue_map.py --hwq 8  [--connections 3072] [--ops 49152] [--verify]
-    python tools/uds_queue_map.py --hwq 16
+    python tools/uds_queue_map.py --hwq 2  [--connections 3072] [--ops 49152] [--verify]
+    python tools/uds_queue_map.py --hwq 1
 """
 import argparse, collections, csv, glob, json, os, signal, struct, subprocess, sys, tempfile, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -17,7 +17,7 @@ from tests import uds_client as uc
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--hwq", type=int, default=8)
+    ap.add_argument("--hwq", type=int, default=2, choices=(1, 2))
     ap.add_argument("--connections", type=int, default=3072)
     ap.add_argument("--ops", type=int, default=49152)
     ap.add_argument("--verify", action="store_true", help="prove then verify per connection (default: prove only)")
