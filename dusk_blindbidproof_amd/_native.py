@@ -56,6 +56,10 @@ SIGNATURES = {
     "bbp_check_health": (_i32, [_vp, ctypes.POINTER(_u32)]),
     "bbp_debug_corrupt_scratch": (_i32, [_vp]),
     "bbp_describe": (_i32, [_vp, _vp, _u32]),
+    "bbp_set_prove_check": (_i32, [_vp, _i32]),
+    "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_corrupt_next_proof": (_i32, [_vp, _u32]),
     "bbp_debug_challenges": (_i32, [_vp, _u32, _u32, _u32, _vp]),
     "bbp_ubench": (_i32, [_vp, _i32, _u32, _u32, ctypes.POINTER(ctypes.c_double)]),
     "bbp_set_profiling": (_i32, [_vp, _i32]),
@@ -295,6 +299,26 @@ class Context:
     def debug_corrupt_scratch(self):
         """Test hook: the next MSM launch finds an out-of-range entry in its sorted scratch (bbp_debug_corrupt_scratch)."""
         self._check(lib.bbp_debug_corrupt_scratch(self._h))
+
+    def set_prove_check(self, on):
+        """Checked proving (bbp_set_prove_check): every record of the host-pointer prove calls is verified on the device before it is
+        returned; rows whose witness the circuit rejects get status BAD_ARG and a zeroed record.  Off by default; a pool: every member."""
+        self._check(lib.bbp_set_prove_check(self._h, 1 if on else 0))
+
+    def prove_check_stats(self):
+        """(n_checked, n_unsatisfied, n_reproved, n_failed) since the context was created (a pool: summed over its members)."""
+        v = [ctypes.c_uint64() for _ in range(4)]
+        self._check(lib.bbp_prove_check_stats(self._h, *[ctypes.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def prove_batch_checked_dev(self, B, N, in_ptr, ent_ptr, check_ent_ptr, out_ptr, status_ptr, stream=None):
+        """bbp_prove_batch_checked_dev: prove + verify on the device, one int32 status per proof (OK / FORMAT / BAD_ARG / VERIFY),
+        records of non-OK rows zeroed; stream-ordered like prove_batch_dev, no synchronisation."""
+        self._check(lib.bbp_prove_batch_checked_dev(self._h, B, N, in_ptr, ent_ptr, check_ent_ptr, out_ptr, status_ptr, _stream(stream)))
+
+    def debug_corrupt_next_proof(self, index):
+        """Test hook: the next prove call adds 1 mod l to t_x of its record `index` on the device (bbp_debug_corrupt_next_proof)."""
+        self._check(lib.bbp_debug_corrupt_next_proof(self._h, index))
 
     def debug_challenges(self, B, N, proof):
         out = (ctypes.c_uint8 * (32 * 32))()

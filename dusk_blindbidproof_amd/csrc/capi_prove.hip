@@ -3,14 +3,18 @@
 #include <string.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <chrono>
+#include <functional>
 #include <thread>
 
 #include "batch.h"
 #include "submit.h"
+#include "witness_check.h"
 
 namespace bbp {
-int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s);
+int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s,
+                        const std::function<int32_t(hipStream_t)>* open_hook = nullptr);
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
 int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
@@ -85,6 +89,62 @@ __global__ void k_prepare_bids(u32 B, u32 N, const u8* __restrict__ bids, const 
             o[56 + 8 * i + w] = word;
             if (v) v[24 + 8 * i + w] = word;
         }
+}
+
+// ---- checked proving (bbp_set_prove_check, bbp_prove_batch_checked_dev) -------------------------------------------------------
+// Witness check: one lane per proof, the relations of witness_check.h on the input row; reads inputs only, so it runs on the
+// opening stream beside the draw chain (prove_batch_dev's open_hook).  mask[p] = failed-relation bits (0 = satisfied).
+__global__ void k_witness_check(u32 B, u32 N, const u8* __restrict__ in, const sc* __restrict__ mimc, u32* __restrict__ mask) {
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    const size_t in_words = 7 * 8 + (size_t)N * 8 + 2;
+    mask[p] = witness_check_row(N, reinterpret_cast<const u32*>(in) + in_words * p, mimc);
+}
+
+// Verify-row assembly: record || q || z_img || seed || pub_list (bbp_verify_batch's row) from the output records and the input rows
+// (scalars 4, 5, 6 and the list).  Records are 1121 + 32 m bytes -- odd -- so the copy goes byte by byte, one byte per lane.
+__global__ void k_check_rows(u32 B, u32 N, const u8* __restrict__ in, const u8* __restrict__ recs, u8* __restrict__ rows) {
+    const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (4 + (size_t)N), in_stride = 7 * 32 + 32 * (size_t)N + 8, row = rec + 96 + 32 * (size_t)N;
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= row * B) return;
+    const size_t p = i / row, o = i - p * row;
+    rows[i] = o < rec ? recs[rec * p + o] : in[in_stride * p + 4 * 32 + (o - rec)];  // o - rec < 96: q, z_img, seed; beyond: the list at 7*32
+}
+
+// Status merge (caller's stream, after the check has joined): per proof, in the host path's screening order,
+//   toggle >= N -> BBP_ERR_BAD_ARG, non-canonical scalar -> BBP_ERR_FORMAT, witness not satisfied -> BBP_ERR_BAD_ARG,
+//   record rejected -> BBP_ERR_VERIFY, else BBP_OK.
+// Records of non-OK rows are zeroed.  counts[0] / counts[1] (context-wide) count refused rows / rejected records; with fail_idx,
+// the rejected rows (idx_base + p) are compacted there behind the counter *fail_n (host path: the rows it proves once more).
+__global__ void k_check_merge(u32 B, u32 N, const u32* __restrict__ mask, const int32_t* __restrict__ vstatus, u8* __restrict__ recs,
+                              int32_t* __restrict__ status, unsigned long long* __restrict__ counts, u32* __restrict__ fail_n,
+                              u32* __restrict__ fail_idx, u32 idx_base) {
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    const u32 f = mask[p];
+    const int32_t st = (f & WC_TOGGLE) ? BBP_ERR_BAD_ARG : (f & WC_FORMAT) ? BBP_ERR_FORMAT : f ? BBP_ERR_BAD_ARG
+                     : vstatus[p] != BBP_OK ? BBP_ERR_VERIFY : BBP_OK;
+    status[p] = st;
+    if (st == BBP_OK) return;
+    const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (4 + (size_t)N);
+    for (size_t o = 0; o < rec; o++) recs[rec * p + o] = 0;
+    atomicAdd(&counts[st == BBP_ERR_VERIFY ? 1 : 0], 1ull);
+    if (st == BBP_ERR_VERIFY && fail_idx) fail_idx[atomicAdd(fail_n, 1u)] = idx_base + p;
+}
+
+// bbp_debug_corrupt_next_proof: t_x (record bytes 257..288: version, eight points, then t_x) += 1 mod l, still canonical
+__global__ void k_corrupt_tx(u8* __restrict__ rec) {
+    if (threadIdx.x != 0) return;
+    u8* t = rec + 1 + 8 * 32;
+    u32 w[8];
+    for (int i = 0; i < 8; i++) w[i] = (u32)t[4 * i] | (u32)t[4 * i + 1] << 8 | (u32)t[4 * i + 2] << 16 | (u32)t[4 * i + 3] << 24;
+    const sc v = sc_add(sc_reduce256(w), sc_one());
+    for (int i = 0; i < 8; i++)
+        for (int b = 0; b < 4; b++) t[4 * i + b] = (u8)(v.v[i] >> (8 * b));
+}
+
+__global__ void k_health_or(u32* __restrict__ health, u32 bits) {
+    if (threadIdx.x == 0) atomicOr(health, bits);
 }
 
 // proofs per engine call when a host-pointer batch API is handed more (BBP_HOST_CHUNK_PROVE / BBP_HOST_CHUNK_VERIFY)
@@ -301,8 +361,9 @@ static int32_t fetch_results(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, size_t bytes) {
         const u32 flags = *sl.h_flag;
         api_guard(ctx, [&]() -> int32_t {
             char buf[200];
-            snprintf(buf, sizeof buf, "engine health flags %#x: an MSM table gather was out of range and had to be clamped (corrupted engine scratch); "
-                                      "results since then are not trustworthy -- free this context and create a new one", flags);
+            snprintf(buf, sizeof buf, "engine health flags %#x: %s; results since then are not trustworthy -- free this context and create a new one", flags,
+                     (flags & 1u) ? "an MSM table gather was out of range and had to be clamped (corrupted engine scratch)"
+                                  : "a proof with a satisfied witness failed its check twice (checked proving)");
             return ctx->err = buf, BBP_ERR_DEVICE;
         });
         return BBP_ERR_DEVICE;
@@ -311,13 +372,107 @@ static int32_t fetch_results(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, size_t bytes) {
 }
 }  // namespace bbp
 
+// bbp_debug_corrupt_next_proof: the armed record index, relative to this launch's first proof, is corrupted on `s` right after the
+// prover wrote it (before any check reads it); the hook fires once
+static int32_t corrupt_hook(bbp_ctx* ctx, u32 first, u32 nb, u32 N, u8* out_dev, hipStream_t s) {
+    const int64_t i = ctx->debug_corrupt_proof - (int64_t)first;
+    if (ctx->debug_corrupt_proof < 0 || i < 0 || i >= (int64_t)nb) return BBP_OK;
+    ctx->debug_corrupt_proof = -1;
+    hipLaunchKernelGGL(k_corrupt_tx, dim3(1), dim3(64), 0, s, out_dev + (size_t)bbp_proof_record_size(N) * (size_t)i);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+static size_t check_row_bytes(u32 N) { return bbp_proof_record_size(N) + 96 + 32 * (size_t)N; }
+static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
+// scratch of one checked call of B proofs: verify rows, then verifier statuses
+static size_t check_scratch_bytes(u32 B, u32 N) { return align256(check_row_bytes(N) * B) + 4 * (size_t)B; }
+
+// One checked prove launch (context lock held): witness check on the opening stream, the prover, the verify rows and the aggregated
+// verifier on a verifier lane's stream -- forked from the records' completion on `s`, joined back before the status merge on `s`.
+// Everything this call writes is complete for work enqueued on `s` afterwards.  `scratch` holds check_scratch_bytes(B, N);
+// `reuse` (optional) is the event after which `scratch` and `mask` may be overwritten.
+static int32_t prove_checked_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* in, const u8* ent, const u8* cent, u8* out, int32_t* status,
+                                     u32* mask, u8* scratch, u32* fail_n, u32* fail_idx, u32 idx_base, hipStream_t s, hipEvent_t reuse) {
+    int32_t rc;
+    if (!ctx->chk_counts) {
+        BBP_HIP_TRY(ctx, hipMalloc(&ctx->chk_counts, 2 * sizeof(unsigned long long)));
+        BBP_HIP_TRY(ctx, hipMemsetAsync(ctx->chk_counts, 0, 2 * sizeof(unsigned long long), s));
+    }
+    if (!ctx->ev_chk_fork) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_chk_fork, hipEventDisableTiming));
+    if (!ctx->ev_chk_join) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_chk_join, hipEventDisableTiming));
+    u32 hog = 0;  // a serial wave of four MiMC chains beside other calls' heavy stages: fenced onto CUs of its own, as k_prepare_bids
+    if ((rc = serial_lds_bytes(ctx, (const void*)k_witness_check, &hog))) return rc;
+    const std::function<int32_t(hipStream_t)> open_hook = [&](hipStream_t os) -> int32_t {
+        if (reuse) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, reuse, 0));
+        ScopedEvent ev(ctx, TAG_WITNESS, os);
+        hipLaunchKernelGGL(k_witness_check, dim3((B + 63) / 64), dim3(64), hog, os, B, N, in, ctx->mimc_c, mask);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        return BBP_OK;
+    };
+    if ((rc = prove_batch_dev(ctx, B, N, in, ent, out, s, &open_hook))) return rc;
+    if ((rc = corrupt_hook(ctx, 0, B, N, out, s))) return rc;
+    bbp_ctx::VLane& L = ctx->vl[ctx->chk_lane++ % (u32)bbp_ctx::VLANES];
+    u8* rows = scratch;
+    int32_t* vstatus = reinterpret_cast<int32_t*>(scratch + align256(check_row_bytes(N) * B));
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_chk_fork, s));
+    BBP_HIP_TRY(ctx, hipStreamWaitEvent(L.stream, ctx->ev_chk_fork, 0));
+    if (reuse) BBP_HIP_TRY(ctx, hipStreamWaitEvent(L.stream, reuse, 0));
+    {
+        ScopedEvent ev(ctx, TAG_VERIFY_SCALARS, L.stream);
+        const size_t n = check_row_bytes(N) * B;
+        hipLaunchKernelGGL(k_check_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L.stream, B, N, in, (const u8*)out, rows);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+    }
+    const int last_par = ctx->last_par;  // (the verifier takes it over; bbp_debug_challenges means the prove call)
+    rc = verify_batch_agg_dev(ctx, B, N, BBP_AGG_GROUP_DEFAULT, rows, cent, vstatus, L.stream, nullptr);
+    ctx->last_par = last_par;
+    if (rc) return rc;
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_chk_join, L.stream));
+    BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_chk_join, 0));
+    {
+        ScopedEvent ev(ctx, TAG_VERIFY_SCALARS, s);
+        hipLaunchKernelGGL(k_check_merge, dim3((B + 63) / 64), dim3(64), 0, s, B, N, (const u32*)mask, (const int32_t*)vstatus, out, status,
+                           ctx->chk_counts, fail_n, fail_idx, idx_base);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+    }
+    return BBP_OK;
+}
+
+// a proof with a satisfied witness failed its check twice: health bit 1, sticky like bit 0 (every later host-pointer call fails)
+static int32_t raise_check_failure(bbp_ctx* ctx, u32 row) {
+    return api_guard(ctx, [&]() -> int32_t {
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipLaunchKernelGGL(k_health_or, dim3(1), dim3(64), 0, ctx->stream, ctx->health, 2u);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        ctx->err = "checked proving: the record of row " + std::to_string(row) +
+                   " (a satisfied witness) failed verification twice -- health bit 1; free this context and create a new one";
+        return BBP_ERR_DEVICE;
+    });
+}
+
+// last-error text of a row the witness check refused (host evaluation of the same relations: failure paths only)
+static std::string refused_row_text(const bbp_ctx* ctx, const uint8_t* row, uint32_t N) {
+    const bbp_ctx* c = is_pool(ctx) ? ctx->members[0] : ctx;
+    std::vector<sc> mc(BBP_MIMC_ROUNDS);
+    if (c->mimc_host.size() < sizeof(sc) * BBP_MIMC_ROUNDS) return "toggle >= N";
+    memcpy(mc.data(), c->mimc_host.data(), sizeof(sc) * BBP_MIMC_ROUNDS);
+    std::vector<u32> w(7 * 8 + (size_t)N * 8 + 2);
+    memcpy(w.data(), row, 4 * w.size());
+    return witness_check_text(witness_check_row(N, w.data(), mc.data()));
+}
+
+enum CheckMode { CHECK_AUTO, CHECK_OFF, CHECK_REPROVE };  // context's setting / never (bbp_reserve) / checked, no second prove
+
 // body of bbp_prove_batch.  Takes the context lock itself, for the enqueue phase only.
 static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out,
-                                int32_t* status) {
+                                int32_t* status, CheckMode mode = CHECK_AUTO) {
     int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
     if (rc) return rc;
     if (B == 0) return BBP_OK;
     fault_injected("prove_batch");
+    const bool check = mode == CHECK_REPROVE || (mode == CHECK_AUTO && ctx->prove_check.load());
     const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, ent_stride = bbp_entropy_size(N), out_stride = bbp_proof_record_size(N);
     // host-side argument screening (the reference's typed API cannot express these states: SURVEY.md 8b)
     std::vector<uint8_t> fixed;
@@ -360,9 +515,28 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         }
         entropy = ent_host.data();
     }
+    // checked: the verifier's weights come from the OS like bbp_verify_batch's; they travel behind the prover's entropy.  The results
+    // come back behind the records: statuses, witness masks, the count and the rows of rejected records (k_check_merge)
+    std::vector<uint8_t> ent_all;
+    const uint8_t* up_ent = entropy;
+    size_t up_ent_bytes = ent_stride * B;
+    if (check) {
+        ent_all.resize(ent_stride * B + 32 * (size_t)B);
+        memcpy(ent_all.data(), entropy, ent_stride * B);
+        if (!os_random(ent_all.data() + ent_stride * B, 32 * (size_t)B)) {
+            api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
+            return BBP_ERR_DEVICE;
+        }
+        up_ent = ent_all.data();
+        up_ent_bytes = ent_all.size();
+    }
+    const size_t info_off = check ? align256(out_stride * B) : out_stride * B, out_bytes = info_off + (check ? 4 * (3 * (size_t)B + 1) : 0);
+    std::vector<int32_t> dstatus;
+    std::vector<u32> dmask, fail_rows;
     static const bool trace = getenv("BBP_TRACE") != nullptr;
     auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double t_enter = now_ms();
+  {  // the staging slot is held for this block only: a second prove of rejected rows below takes a slot of its own
     SlotLease lease(ctx);  // may wait for the call two back to collect its results; the context lock is NOT held here
     bbp_ctx::IoSlot& sl = *lease.sl;
     const double t_slot = now_ms();
@@ -371,32 +545,86 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         int32_t rc;
         t_lock = now_ms();
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = dev_reserve(ctx, sl.out, out_stride * B)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, out_stride * B)) ||
-            (rc = upload_inputs(ctx, sl, src, in_stride * B, entropy, ent_stride * B)))
+        if ((rc = dev_reserve(ctx, sl.out, out_bytes)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, out_bytes)) ||
+            (check && (rc = dev_reserve(ctx, sl.chk, check_scratch_bytes(B, N)))) ||
+            (rc = upload_inputs(ctx, sl, src, in_stride * B, up_ent, up_ent_bytes)))
             return rc;
         t_h2d = now_ms();
+        u8* info = (u8*)sl.out.p + info_off;
+        int32_t* st_dev = (int32_t*)info;
+        u32 *mask_dev = (u32*)(info + 4 * (size_t)B), *fail_n = mask_dev + B, *fail_idx = fail_n + 1;
+        if (check) BBP_HIP_TRY(ctx, hipMemsetAsync(fail_n, 0, sizeof(u32), ctx->stream));
         // Very large host batches go through the engine in equal chunks of at most host_chunk_prove proofs so that scratch stays
         // bounded (~1.3 MB per proof of the largest call, three buffers); consecutive calls pipeline -- chunk k+1's opening stage
         // under chunk k's MSMs.  One 16384-proof call was measured 5 % faster than four of 4096, hence the large default.
         const uint32_t n_chunks = (B + host_chunk_prove() - 1) / host_chunk_prove(), chunk = (B + n_chunks - 1) / n_chunks;
         for (uint32_t first = 0; first < B; first += chunk) {
             const uint32_t nb = B - first < chunk ? B - first : chunk;
-            if ((rc = prove_batch_dev(ctx, nb, N, (const u8*)sl.in.p + in_stride * first, (const u8*)sl.ent.p + ent_stride * first,
-                                      (u8*)sl.out.p + out_stride * first, ctx->stream)))
-                return rc;
+            const u8 *cin = (const u8*)sl.in.p + in_stride * first, *cent = (const u8*)sl.ent.p + ent_stride * first;
+            u8* cout = (u8*)sl.out.p + out_stride * first;
+            if (check) {
+                u8* scratch = (u8*)sl.chk.p;  // chunks are stream-ordered on ctx->stream; each chunk's check joins back before the next starts
+                if ((rc = prove_checked_enqueue(ctx, nb, N, cin, cent, (const u8*)sl.ent.p + ent_stride * B + 32 * (size_t)first, cout,
+                                                st_dev + first, mask_dev + first, scratch, fail_n, fail_idx, first, ctx->stream, nullptr)))
+                    return rc;
+            } else {
+                if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream))) return rc;
+                if ((rc = corrupt_hook(ctx, first, nb, N, cout, ctx->stream))) return rc;
+            }
         }
+        ctx->debug_corrupt_proof = -1;  // armed for an index beyond this call: consumed all the same
         BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, ctx->stream));
         return BBP_OK;
     });
     if (rc) return rc;
     const double t_enq = now_ms();
-    if ((rc = fetch_results(ctx, sl, out_stride * B))) return rc;  // lock released: another thread may be enqueueing the next batch now
+    if ((rc = fetch_results(ctx, sl, out_bytes))) return rc;  // lock released: another thread may be enqueueing the next batch now
     memcpy(out, sl.h_out, out_stride * B);
+    if (check) {
+        const u8* info = (const u8*)sl.h_out + info_off;
+        dstatus.resize(B);
+        dmask.resize(B);
+        memcpy(dstatus.data(), info, 4 * (size_t)B);
+        memcpy(dmask.data(), info + 4 * (size_t)B, 4 * (size_t)B);
+        u32 n_fail = 0;
+        memcpy(&n_fail, info + 8 * (size_t)B, 4);
+        fail_rows.resize(std::min<u32>(n_fail, B));
+        memcpy(fail_rows.data(), info + 8 * (size_t)B + 4, 4 * fail_rows.size());
+    }
     if (trace)
         fprintf(stderr, "[bbp trace] prove_batch B=%u slot=%d: enter %.1f, slot +%.1f, lock +%.1f, h2d +%.1f, enqueued +%.1f, done +%.1f\n", B,
                 (int)(&sl - ctx->io), t_enter, t_slot - t_enter, t_lock - t_enter, t_h2d - t_enter, t_enq - t_enter, now_ms() - t_enter);
+  }
     for (uint32_t i = 0; i < B; i++)
         if (status[i] != BBP_OK) memset(out + out_stride * i, 0, out_stride);
+    if (!check) return BBP_OK;
+    if (mode == CHECK_AUTO) ctx->chk_checked += B;
+    // rows the host screening let through take the device's verdict (their records are already zeroed unless OK)
+    int64_t first_refused = -1;
+    for (uint32_t i = 0; i < B; i++) {
+        if (status[i] != BBP_OK) continue;
+        status[i] = dstatus[i];
+        if (dstatus[i] != BBP_OK && dstatus[i] != BBP_ERR_VERIFY && first_refused < 0) first_refused = i;
+    }
+    if (first_refused >= 0) set_tls_error(ctx, std::string("row ") + std::to_string(first_refused) + ": " + witness_check_text(dmask[first_refused]));
+    if (mode == CHECK_REPROVE || fail_rows.empty()) return BBP_OK;
+    // a record that failed its check is proved once more with the same inputs and the same entropy (the drawn entropy when the
+    // caller gave none), and checked again; a second failure is a device fault: the whole call fails and health bit 1 is raised
+    std::sort(fail_rows.begin(), fail_rows.end());
+    const uint32_t nr = (uint32_t)fail_rows.size();
+    std::vector<uint8_t> rin(in_stride * nr), rent(ent_stride * nr), rout(out_stride * nr);
+    std::vector<int32_t> rst(nr);
+    for (uint32_t j = 0; j < nr; j++) {
+        memcpy(&rin[in_stride * j], src + in_stride * fail_rows[j], in_stride);
+        memcpy(&rent[ent_stride * j], entropy + ent_stride * fail_rows[j], ent_stride);
+    }
+    ctx->chk_reproved += nr;
+    if ((rc = prove_batch_host(ctx, nr, N, rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE))) return rc;
+    for (uint32_t j = 0; j < nr; j++) {
+        if (rst[j] != BBP_OK) return raise_check_failure(ctx, fail_rows[j]);
+        memcpy(out + out_stride * fail_rows[j], &rout[out_stride * j], out_stride);
+        status[fail_rows[j]] = BBP_OK;
+    }
     return BBP_OK;
 }
 
@@ -438,7 +666,81 @@ extern "C" int32_t bbp_prove_batch_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, con
         if (rc) return rc;
         if (B == 0) return BBP_OK;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return prove_batch_dev(ctx, B, N, (const u8*)in_dev, (const u8*)entropy_dev, (u8*)out_dev, pick_stream(ctx, stream));
+        hipStream_t s = pick_stream(ctx, stream);
+        if ((rc = prove_batch_dev(ctx, B, N, (const u8*)in_dev, (const u8*)entropy_dev, (u8*)out_dev, s))) return rc;
+        rc = corrupt_hook(ctx, 0, B, N, (u8*)out_dev, s);
+        ctx->debug_corrupt_proof = -1;
+        return rc;
+    });
+}
+
+extern "C" int32_t bbp_prove_batch_checked_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
+                                               const void* check_entropy_dev, void* out_dev, void* status_dev, void* stream) {
+    if (!ctx || !in_dev || !entropy_dev || !check_entropy_dev || !out_dev || !status_dev) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_prove_batch_checked_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc = check_n(ctx, N);
+        if (rc) return rc;
+        if (B == 0) return BBP_OK;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = pick_stream(ctx, stream);
+        // scratch in rotation: verify rows + verifier statuses, then the witness masks; a ring entry waits for the status kernel of
+        // the call that used it last (several calls in flight, no host synchronisation)
+        bbp_ctx::CheckBuf& cb = ctx->chk[ctx->chk_next++ % (u32)bbp_ctx::CHECK_RING];
+        const size_t mask_off = align256(check_scratch_bytes(B, N));
+        if ((rc = dev_reserve(ctx, cb.buf, mask_off + 4 * (size_t)B))) return rc;
+        if (!cb.ev) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&cb.ev, hipEventDisableTiming));
+        u8* base = (u8*)cb.buf.p;
+        rc = prove_checked_enqueue(ctx, B, N, (const u8*)in_dev, (const u8*)entropy_dev, (const u8*)check_entropy_dev, (u8*)out_dev,
+                                   (int32_t*)status_dev, (u32*)(base + mask_off), base, nullptr, nullptr, 0, s, cb.ev_valid ? cb.ev : nullptr);
+        ctx->debug_corrupt_proof = -1;
+        if (rc) return rc;
+        BBP_HIP_TRY(ctx, hipEventRecord(cb.ev, s));
+        cb.ev_valid = true;
+        ctx->chk_checked += B;
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_set_prove_check(bbp_ctx* ctx, int32_t on) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    for (bbp_ctx* m : ctx->members) bbp_set_prove_check(m, on);
+    ctx->prove_check = on != 0;
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_prove_check_stats(bbp_ctx* ctx, uint64_t* n_checked, uint64_t* n_unsatisfied, uint64_t* n_reproved, uint64_t* n_failed) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    uint64_t v[4] = {0, 0, 0, 0};
+    std::vector<bbp_ctx*> ctxs = is_pool(ctx) ? ctx->members : std::vector<bbp_ctx*>{ctx};
+    for (bbp_ctx* c : ctxs) {
+        unsigned long long dc[2] = {0, 0};
+        const int32_t rc = api_guard(c, [&]() -> int32_t {  // the device counters are final once the device is idle
+            if (!c->chk_counts) return BBP_OK;
+            BBP_HIP_TRY(c, hipSetDevice(c->device));
+            BBP_HIP_TRY(c, hipDeviceSynchronize());
+            BBP_HIP_TRY(c, hipMemcpy(dc, c->chk_counts, sizeof dc, hipMemcpyDeviceToHost));
+            return BBP_OK;
+        });
+        if (rc) return rc;
+        v[0] += c->chk_checked.load();
+        v[1] += dc[0];
+        v[2] += c->chk_reproved.load();
+        v[3] += dc[1];
+    }
+    if (n_checked) *n_checked = v[0];
+    if (n_unsatisfied) *n_unsatisfied = v[1];
+    if (n_reproved) *n_reproved = v[2];
+    if (n_failed) *n_failed = v[3];
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_debug_corrupt_next_proof(bbp_ctx* ctx, uint32_t index) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_corrupt_next_proof");
+    return api_guard(ctx, [&]() -> int32_t {
+        ctx->debug_corrupt_proof = index;
+        return BBP_OK;
     });
 }
 
@@ -454,7 +756,9 @@ int32_t bbp::prove_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
 // bbp_last_error text for the duration of the callback, then the request is gone
 static void async_done(Request* r) {
     try {
-        set_tls_error(r->origin, r->status == BBP_OK ? std::string() : !r->err.empty() ? r->err : r->status == BBP_ERR_BAD_ARG ? "toggle >= N"
+        set_tls_error(r->origin, r->status == BBP_OK ? std::string() : !r->err.empty() ? r->err
+                                 : r->status == BBP_ERR_BAD_ARG ? (r->kind == 0 && static_cast<const bbp_ctx*>(r->origin)->prove_check
+                                                                      ? refused_row_text(static_cast<const bbp_ctx*>(r->origin), r->in, r->N) : "toggle >= N")
                                      : r->status == BBP_ERR_FORMAT && r->kind == 0 ? "non-canonical scalar input"
                                                                                     : status_text(r->status));
     } catch (...) {
@@ -491,7 +795,8 @@ extern "C" int32_t bbp_prove(bbp_ctx* ctx, const uint8_t scalars7[7 * 32], const
         r.out = proof_out;
         const int32_t st = static_cast<Combiner*>(ctx->combiner)->submit(ctx, r);
         if (st != BBP_OK) {
-            set_tls_error(ctx, !r.err.empty() ? r.err : st == BBP_ERR_BAD_ARG ? "toggle >= N" : "non-canonical scalar input");
+            set_tls_error(ctx, !r.err.empty() ? r.err : st == BBP_ERR_BAD_ARG ? (ctx->prove_check ? refused_row_text(ctx, in.data(), N) : "toggle >= N")
+                                                                             : "non-canonical scalar input");
             return st;
         }
         if (proof_len) *proof_len = BBP_R1CS_PROOF_BYTES;
@@ -759,19 +1064,37 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
         std::vector<int32_t> st(B);
         int32_t rc = BBP_OK;
         // batches below 1024 proofs rotate three buffers and two opening streams, larger ones two buffers: both shapes, every slot
-        for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data());
+        for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data(), CHECK_OFF);
         // the small-batch path rotates over ALL five batch buffers (buffer = call % PROVE_BUFS): five more calls whatever B is -- with
         // max_batch < 1024 the loop above IS that path but touches only three of them, and the first 4th / 5th call under load would
         // grow its buffer with hipFree + hipMalloc: the stall this function exists to prevent
         const uint32_t small = B < 1023 ? B : 1023;
-        for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, small, N, in.data(), ent.data(), out.data(), st.data());
+        for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, small, N, in.data(), ent.data(), out.data(), st.data(), CHECK_OFF);
         // ... and the shape a caller with several calls in flight gets (prover.hip "deep"): whole calls of B in rotation, five buffers
         if (B >= 1024 && ctx->slices > 1 && ctx->rotate_deep_max > 0 && B <= (uint32_t)ctx->rotate_deep_max) {
             struct Reset { bool& b; ~Reset() { b = false; } } reset{ctx->force_deep};
             ctx->force_deep = true;
-            for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data());
+            for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data(), CHECK_OFF);
         }
         for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++) rc = verify_batch_host(ctx, B, N, 0, vin.data(), st.data());
+        // checked proving (only when it is on, and without running a check): the staging slots' and the device ring's check
+        // scratch, and the aggregated verifier's buffers of every lane (the check's verifier)
+        if (rc == BBP_OK && ctx->prove_check) {
+            for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++)
+                rc = verify_batch_host(ctx, B, N, 0, vin.data(), st.data(), BBP_AGG_GROUP_DEFAULT);
+            if (rc == BBP_OK)
+                rc = api_guard(ctx, [&]() -> int32_t {
+                    int32_t rc = BBP_OK;
+                    BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+                    const size_t out_bytes = align256(rec * B) + 4 * (3 * (size_t)B + 1);
+                    for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++)
+                        if (!(rc = dev_reserve(ctx, ctx->io[k].chk, check_scratch_bytes(B, N))) && !(rc = dev_reserve(ctx, ctx->io[k].out, out_bytes)))
+                            rc = pinned_reserve(ctx, ctx->io[k].h_out, ctx->io[k].h_cap, out_bytes);
+                    for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++)
+                        rc = dev_reserve(ctx, ctx->chk[k].buf, align256(check_scratch_bytes(B, N)) + 4 * (size_t)B);
+                    return rc;
+                });
+        }
         return rc;
     });
 }

@@ -6,6 +6,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include <atomic>
 #include <condition_variable>
 #include <map>
 #include <mutex>
@@ -198,7 +199,25 @@ struct bbp_ctx {
     };
     VLane vl[VLANES];
     std::string err;
-    bbp::u32* health = nullptr;  // device word, bit 0: an MSM table gather had to be clamped (corrupted scratch) -- bbp_check_health
+    bbp::u32* health = nullptr;  // device word, bit 0: an MSM table gather had to be clamped (corrupted scratch); bit 1: a proof with a
+                                 // satisfied witness failed its check twice (checked proving) -- bbp_check_health
+    // Checked proving (bbp_set_prove_check, capi_prove.hip): every record is verified on the device before it is handed out.
+    std::atomic<int> prove_check{0};
+    std::atomic<uint64_t> chk_checked{0}, chk_reproved{0};  // rows handed to checked calls / records proved a second time
+    unsigned long long* chk_counts = nullptr;  // device [2]: rows refused by the witness check / records that failed verification
+    int64_t debug_corrupt_proof = -1;          // bbp_debug_corrupt_next_proof: record index of the next prove call to corrupt (tests)
+    uint32_t chk_lane = 0;                     // verifier lane of the next check (rotation)
+    hipEvent_t ev_chk_fork = nullptr, ev_chk_join = nullptr;  // records complete -> check on a lane stream -> back on the caller's
+    // Scratch of bbp_prove_batch_checked_dev calls (verify rows, verifier statuses, witness masks), in rotation: a ring entry is
+    // reused only after the status kernel of the call that used it last (ev); host-pointer calls use their staging slot's `chk`.
+    static constexpr int CHECK_RING = PROVE_BUFS;
+    struct CheckBuf {
+        bbp::DevBuf buf;
+        hipEvent_t ev = nullptr;
+        bool ev_valid = false;
+    };
+    CheckBuf chk[CHECK_RING];
+    uint32_t chk_next = 0;
     // resident tables
     bbp::ge* gens = nullptr;           // [TAB_BASES] extended points: B_blinding, G[2048], H[2048], B, then the PAD_BASES range sums and the MRG_BASES merged bases
     bbp::niels_row* ptable = nullptr;      // [TAB_BASES * MSM_POS] affine cached 2^b * P_i, 128-byte limb rows (275 MB)
@@ -216,7 +235,7 @@ struct bbp_ctx {
     // so other host threads can enqueue the next batches meanwhile and the engine's cross-call pipeline (opening stage of call
     // k+1 under the MSM stage of call k) also works for bbp_prove_batch / bbp_prove / the UDS server (capi_prove.hip).
     struct IoSlot {
-        bbp::DevBuf in, ent, out;
+        bbp::DevBuf in, ent, out, chk;               // chk: verify rows + verifier statuses of a checked prove call
         uint32_t* h_flag = nullptr;              // pinned: the context's health word as read back with this slot's results
         void *h_out = nullptr, *h_in = nullptr;  // pinned mirrors: results / inputs (a copy from PAGEABLE memory waits for the whole
         size_t h_cap = 0, h_in_cap = 0;          // device to go idle -- measured 87 ms behind a running batch -- a pinned one does not)

@@ -27,6 +27,8 @@
 #define BBP_KECCAK_WAVE 1
 #include <string.h>
 
+#include <functional>
+
 #include "batch.h"
 #include "hosthash.h"
 #include "keccak_wave.h"
@@ -1639,7 +1641,10 @@ static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd
                            hipEvent_t stagger, hipEvent_t out_guard);
 
 // in_dev: B * (7*32 + N*32 + 8) ; ent_dev: B * (32 m + 32) ; out_dev: B * (1121 + 32 m).  All device pointers.
-int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s) {
+// open_hook (optional): called once with the opening stream after its waits, before the opening kernels -- work that reads the
+// inputs only and should run beside the draw chain rather than on the caller's stream (checked proving's witness check)
+int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s,
+                        const std::function<int32_t(hipStream_t)>* open_hook) {
     const CircuitDev* cp;
     int32_t rc = circuit_get(ctx, N, &cp);
     if (rc) return rc;
@@ -1703,6 +1708,7 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
             BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_prep, 0));
             ctx->ev_prep_valid = false;
         }
+        if (open_hook && (rc = (*open_hook)(s))) return rc;
         LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);
         // every launch asks for what serial_lds_bytes set the kernel's limit to (reservation minus the kernel's static LDS): the two
         // cannot diverge when a kernel gains a __shared__ array

@@ -381,7 +381,7 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
     }
     ctx->circuits.clear();
     for (auto& sl : ctx->io) {
-        for (void* p : {sl.in.p, sl.ent.p, sl.out.p})
+        for (void* p : {sl.in.p, sl.ent.p, sl.out.p, sl.chk.p})
             if (p) (void)hipFree(p);
         if (sl.h_flag) (void)hipHostFree(sl.h_flag);
         if (sl.h_out) (void)hipHostFree(sl.h_out);
@@ -390,6 +390,13 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
     }
     if (ctx->health) (void)hipFree(ctx->health);
+    if (ctx->chk_counts) (void)hipFree(ctx->chk_counts);
+    for (auto& cb : ctx->chk) {
+        if (cb.buf.p) (void)hipFree(cb.buf.p);
+        if (cb.ev) (void)hipEventDestroy(cb.ev);
+    }
+    for (hipEvent_t e : {ctx->ev_chk_fork, ctx->ev_chk_join})
+        if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_vacc)
         if (e) (void)hipEventDestroy(e);
     for (auto& L : ctx->vl) {
@@ -490,6 +497,9 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                       " before the process first touches HIP (or call bbp_init first: it does so itself), or streams of this context share "
                                       "fewer hardware queues and serialise\n",
                                       hwq ? hwq : "not set", hst == 3 ? " and HIP was initialised before bbp_init could set it" : "");
+        if (off + 1 < cap)
+            off += (uint32_t)snprintf(buf + off, cap - off, "checked proving: %s\n",
+                                      ctx->prove_check ? "on (every record is verified on the device before it is returned)" : "off");
         if (free_b < ((size_t)6 << 30) && off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "WARNING: less than 6 GiB of device memory free: a 1024-proof batch needs ~14 GiB of scratch\n");
         return BBP_OK;

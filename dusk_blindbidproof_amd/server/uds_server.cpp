@@ -530,7 +530,8 @@ static void on_signal(int) {
 static void usage(const char* argv0) {
     fprintf(stderr,
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
-            "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n",
+            "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
+            "          [--check-proofs]\n",
             argv0);
 }
 
@@ -541,6 +542,7 @@ int main(int argc, char** argv) {
     std::vector<int32_t> devices, reserve_items;  // --reserve: bid-list lengths whose buffers are sized for --max-batch before the first request
     uint32_t window_us = 200, max_batch = 4096;
     int io_threads = 2;
+    bool check_proofs = false;  // --check-proofs: every proof is verified on the device before it is answered (bbp_set_prove_check)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -573,6 +575,7 @@ int main(int argc, char** argv) {
         else if (a == "--io-threads") io_threads = atoi(val());
         else if (a == "--verify-aggregate") setenv("BBP_VERIFY_AGGREGATE", val(), 1);  // opcode-2 batches of >= 2 G proofs are checked in groups of G with
                                                                                          // per-proof fallback: same verdicts, 2-3x the rate (include/bbp.h)
+        else if (a == "--check-proofs") check_proofs = true;
         else if (a == "--reserve") {
             for (const char* p = val(); *p;) {
                 reserve_items.push_back(atoi(p));
@@ -622,6 +625,15 @@ int main(int argc, char** argv) {
             for (size_t i = 0; i < devices.size(); i++) devices[i] = (int32_t)i;
         }
         g_eng.set_batching(g_eng.ctx, window_us, max_batch);
+        if (check_proofs) {  // an engine without checked proving cannot honour the flag: refuse to serve rather than serve unchecked
+            auto set_check = (decltype(&bbp_set_prove_check))dlsym(g_eng.so, "bbp_set_prove_check");
+            if (!set_check || set_check(g_eng.ctx, 1) != BBP_OK) {
+                logf(0, "--check-proofs: the engine %s does not provide checked proving (bbp_set_prove_check)", engine_path.c_str());
+                g_eng.free_(g_eng.ctx);
+                return 2;
+            }
+            logf(2, "checked proving on: every proof is verified on the device before it is answered");
+        }
         if (g_eng.describe) {  // what the engine runs on; its WARNING lines (hardware queues, memory) at warn level
             static char report[8192];
             if (g_eng.describe(g_eng.ctx, report, sizeof report) == BBP_OK)

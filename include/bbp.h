@@ -251,11 +251,48 @@ int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap);
 int32_t bbp_debug_corrupt_scratch(bbp_ctx* ctx);
 
 /* Engine self-check (synchronises the device).  *flags bit 0: an MSM table gather was out of range since bbp_init and had to be
- * clamped, i.e. engine scratch was corrupted (the one GPU fault of round 1 was such a state); 0 = healthy.  The flag is
+ * clamped, i.e. engine scratch was corrupted (the one GPU fault of round 1 was such a state); bit 1: with checked proving
+ * on, a proof whose witness is satisfied failed its check twice (bbp_set_prove_check); 0 = healthy.  Both flags are
  * sticky.  Every host-pointer call (bbp_prove[_batch], bbp_verify[_batch][_aggregated], bbp_msm_batch, the asynchronous forms)
  * reads it back with its results and returns BBP_ERR_DEVICE for the whole call once it is set -- never BBP_OK with results computed
  * from corrupted scratch; callers of the stream-ordered *_dev entry points poll this function at their own synchronisation points. */
 int32_t bbp_check_health(bbp_ctx* ctx, uint32_t* flags);
+
+/* ---- Checked proving ------------------------------------------------------------------------------------------------------------
+ * Proof::prove does not check its witness (src/blindbid/proof.rs:36-91): inputs that do not satisfy the circuit prove to a record
+ * every verifier rejects, and a record the device computed wrongly would go out as BBP_OK too.  With checking on, every record is
+ * verified on the device before it is handed out.  OFF by default; set through this call only (no environment variable).  On a
+ * pool it applies to every member.
+ * A witness is satisfied when the blind-bid circuit accepts it (src/gadgets.rs): m = mimc(k, 0), x = mimc(d, m); toggle < N and
+ * pub_list[toggle] = x mod l (Scalar::from_bits items: an encoding of x + l passes); z_img = mimc(seed, m); mimc(seed, x) * y_inv = 1;
+ * q = d * y_inv.  y is committed but not constrained: a wrong y with the right y_inv passes.
+ * Host-pointer calls with checking on (bbp_prove, bbp_prove_async, bbp_prove_batch, on a context or a pool, combined or not):
+ *   rows whose witness is not satisfied   BBP_ERR_BAD_ARG and a zeroed record; bbp_last_error names the first relation that failed
+ *   every other record                    verified on the device (the aggregated verifier, on a verifier lane's stream)
+ *   a record that fails                   proved once more with the same inputs and the same entropy (the entropy the call drew when
+ *                                         none was given) and checked again: OK then, with the bytes an unchecked call with that
+ *                                         entropy returns; a second failure returns BBP_ERR_DEVICE for the whole call and raises
+ *                                         health bit 1 (the rule bbp_check_health's bit 0 follows)
+ * Costs: one aggregated verification per proof (DESIGN.md section 10 has the measured share). */
+int32_t bbp_set_prove_check(bbp_ctx* ctx, int32_t on);
+/* Counts since bbp_init (a pool: the sum over its members; any pointer may be NULL; synchronises the device): rows handed to checked
+ * calls, rows refused by the witness check (toggle >= N and non-canonical rows included), records proved a second time, and checks
+ * that failed (on the host path each is followed by one re-prove, whose check counts again). */
+int32_t bbp_prove_check_stats(bbp_ctx* ctx, uint64_t* n_checked, uint64_t* n_unsatisfied, uint64_t* n_reproved, uint64_t* n_failed);
+/* The device form, whatever bbp_set_prove_check says: same input contract and stream ordering as bbp_prove_batch_dev (no host
+ * screening, no synchronisation); check_entropy_dev holds B * 32 bytes that seed the verifier's weights (bbp_verify_batch_dev's
+ * entropy_dev).  status_dev: B int32, per proof
+ *   BBP_OK            the record verified
+ *   BBP_ERR_FORMAT    one of the seven scalars is non-canonical
+ *   BBP_ERR_BAD_ARG   toggle >= N, or the witness is not satisfied
+ *   BBP_ERR_VERIFY    the record failed its check
+ * Records of non-OK rows are zeroed; nothing is proved twice (the caller decides).  A pool refuses it, like every *_dev call. */
+int32_t bbp_prove_batch_checked_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
+                                    const void* check_entropy_dev, void* out_dev, void* status_dev, void* stream);
+/* Test hook: the next prove call on the context (any of the prove entry points) adds 1 mod l to the t_x scalar of its record `index`,
+ * on the device, after the prover wrote it and before any check reads it: the record still parses and fails verification (no write
+ * out of bounds; an index beyond the call's batch corrupts nothing and is consumed all the same).  A pool refuses it. */
+int32_t bbp_debug_corrupt_next_proof(bbp_ctx* ctx, uint32_t index);
 
 /* Parity hook: the 32-scalar challenge block of proof `proof` of the LAST batch call of geometry (B, N):
  * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch.h), 32 x 32 bytes. */
