@@ -16,6 +16,8 @@ STREAM_CONTEXT = ctypes.c_void_p(-1).value  # BBP_STREAM_CONTEXT: the context's 
 LAYOUT_BLIND_G_H, LAYOUT_BLIND_G = 0, 1
 BASE_BBLIND, BASE_G0, BASE_H0, BASE_B, NUM_BASES = 0, 1, 2049, 4097, 4098
 R1CS_PROOF_BYTES = 1121
+ENTROPY_PROVE, ENTROPY_VERIFY = 0, 1            # bbp_draw_entropy_dev kinds
+ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE = 0, 1  # bbp_set_entropy_source
 
 # every symbol include/bbp.h declares: (restype, argtypes)
 _vp, _u32, _i32, _u64, _cp = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_char_p
@@ -60,6 +62,9 @@ SIGNATURES = {
     "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_corrupt_next_proof": (_i32, [_vp, _u32]),
+    "bbp_draw_entropy_dev": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "bbp_set_entropy_source": (_i32, [_vp, _i32]),
+    "bbp_debug_next_entropy_key": (_i32, [_vp, _vp]),
     "bbp_debug_challenges": (_i32, [_vp, _u32, _u32, _u32, _vp]),
     "bbp_ubench": (_i32, [_vp, _i32, _u32, _u32, ctypes.POINTER(ctypes.c_double)]),
     "bbp_set_profiling": (_i32, [_vp, _i32]),
@@ -320,6 +325,26 @@ class Context:
         """Test hook: the next prove call adds 1 mod l to t_x of its record `index` on the device (bbp_debug_corrupt_next_proof)."""
         self._check(lib.bbp_debug_corrupt_next_proof(self._h, index))
 
+    def draw_entropy_dev(self, B, N, kind, out_ptr, key=None, stream=None):
+        """bbp_draw_entropy_dev: B rows of on-device ChaCha20 entropy into device memory at out_ptr -- kind ENTROPY_PROVE (rows of
+        entropy_size(N) bytes, the next prove_batch_dev waits for them by itself) or ENTROPY_VERIFY (rows of 32 bytes).  key: 32 bytes,
+        or None for 32 fresh OS bytes (a key used twice reuses every blinding).  Stream-ordered, no synchronisation."""
+        if key is not None and len(key) != 32:
+            raise ValueError("key must be 32 bytes")
+        self._check(lib.bbp_draw_entropy_dev(self._h, B, N, kind, None if key is None else _buf(key), out_ptr, _stream(stream)))
+
+    def set_entropy_source(self, source):
+        """Where host-pointer calls without caller entropy get theirs (bbp_set_entropy_source): "os" / ENTROPY_SOURCE_OS (default) or
+        "device" / ENTROPY_SOURCE_DEVICE (one OS key per call, expanded on the device).  A pool: every member."""
+        src = {"os": ENTROPY_SOURCE_OS, "device": ENTROPY_SOURCE_DEVICE}.get(source, source)
+        self._check(lib.bbp_set_entropy_source(self._h, src))
+
+    def debug_next_entropy_key(self, key):
+        """Test hook: the key of the next host-pointer call that draws on the device (bbp_debug_next_entropy_key)."""
+        if len(key) != 32:
+            raise ValueError("key must be 32 bytes")
+        self._check(lib.bbp_debug_next_entropy_key(self._h, _buf(key)))
+
     def debug_challenges(self, B, N, proof):
         out = (ctypes.c_uint8 * (32 * 32))()
         self._check(lib.bbp_debug_challenges(self._h, B, N, proof, out))
@@ -368,6 +393,10 @@ class Pool(Context):
         if not h:
             raise IndexError(i)
         return Context(_borrowed=h)
+
+    def set_entropy_source(self, source):
+        """bbp_set_entropy_source on the pool: every member takes the setting."""
+        super().set_entropy_source(source)
 
     def member_stats(self, i):
         """(combined prove / verify device calls dealt to member i, requests they carried)"""

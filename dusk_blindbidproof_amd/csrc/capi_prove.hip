@@ -9,6 +9,7 @@
 #include <thread>
 
 #include "batch.h"
+#include "chacha.h"
 #include "submit.h"
 #include "witness_check.h"
 
@@ -143,6 +144,24 @@ __global__ void k_corrupt_tx(u8* __restrict__ rec) {
         for (int b = 0; b < 4; b++) t[4 * i + b] = (u8)(v.v[i] >> (8 * b));
 }
 
+// On-device entropy (bbp_draw_entropy_dev, bbp_set_entropy_source; the expansion is csrc/chacha.h): one lane per 32-byte slot, i.e.
+// one ChaCha20 block, consecutive lanes on consecutive slots of a row (prove rows: 5 + N slots, verify rows: one), so a wavefront's
+// stores cover 2 KB without a gap.  Rows row_base.. of the key's streams; no LDS, no atomics.
+__global__ void __launch_bounds__(64) k_draw_entropy(u32 n_slots, u32 N, u32 kind, u32 row_base, ChachaKey key, u32* __restrict__ out) {
+    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_slots) return;
+    u32 w[8];
+    if (kind == BBP_ENTROPY_PROVE) {
+        const u32 per = 5 + N, r = g / per;
+        entropy_prove_slot(key, N, row_base + r, g - r * per, w);
+    } else {
+        entropy_verify_row(key, row_base + g, w);
+    }
+    u32* o = out + 8 * (size_t)g;
+#pragma unroll
+    for (int i = 0; i < 8; i++) o[i] = w[i];
+}
+
 __global__ void k_health_or(u32* __restrict__ health, u32 bits) {
     if (threadIdx.x == 0) atomicOr(health, bits);
 }
@@ -162,6 +181,19 @@ static bool os_random(uint8_t* buf, size_t n) {
     size_t got = fread(buf, 1, n, f);
     fclose(f);
     return got == n;
+}
+
+// B rows of `kind` (rows row_base.. of the key's streams) into out on s
+static int32_t draw_enqueue(bbp_ctx* ctx, u32 B, u32 N, u32 kind, const ChachaKey& key, u32 row_base, void* out, hipStream_t s) {
+    const u64 n = kind == BBP_ENTROPY_PROVE ? (u64)B * (5 + N) : (u64)B;
+    if (n > 0x7fffffffull || (u64)row_base + B > 0x100000000ull) {
+        ctx->err = "entropy draw: too many rows for one call";
+        return BBP_ERR_BAD_ARG;
+    }
+    ScopedEvent ev(ctx, TAG_RNG, s);
+    hipLaunchKernelGGL(k_draw_entropy, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (u32)n, N, kind, row_base, key, (u32*)out);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
 }
 
 }  // namespace bbp
@@ -328,13 +360,15 @@ static int32_t pinned_reserve(bbp_ctx* ctx, void*& p, size_t& cap, size_t bytes)
 // inputs of a host-pointer call: caller's (pageable) memory -> the slot's pinned mirror -> device, on the context's copy stream.
 // The main stream may still be busy with the previous call's MSM stage, and the opening stage of THIS call is meant to run under
 // it; it only needs complete inputs (include/bbp.h), hence the wait -- on the copy's own event, polled.
-static int32_t upload_inputs(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, const uint8_t* a, size_t na, const uint8_t* b, size_t nb) {
+// `b` lands at byte ent_off of the slot's entropy buffer, which holds at least ent_off + nb bytes afterwards (a device draw fills
+// what lies below ent_off).
+static int32_t upload_inputs(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, size_t ent_off = 0) {
     int32_t rc;
-    if ((rc = dev_reserve(ctx, sl.in, na)) || (rc = dev_reserve(ctx, sl.ent, nb)) || (rc = pinned_reserve(ctx, sl.h_in, sl.h_in_cap, na + nb))) return rc;
+    if ((rc = dev_reserve(ctx, sl.in, na)) || (rc = dev_reserve(ctx, sl.ent, ent_off + nb)) || (rc = pinned_reserve(ctx, sl.h_in, sl.h_in_cap, na + nb))) return rc;
     memcpy(sl.h_in, a, na);
-    memcpy((uint8_t*)sl.h_in + na, b, nb);
+    if (nb) memcpy((uint8_t*)sl.h_in + na, b, nb);
     BBP_HIP_TRY(ctx, hipMemcpyAsync(sl.in.p, sl.h_in, na, hipMemcpyHostToDevice, ctx->copy));
-    BBP_HIP_TRY(ctx, hipMemcpyAsync(sl.ent.p, (uint8_t*)sl.h_in + na, nb, hipMemcpyHostToDevice, ctx->copy));
+    if (nb) BBP_HIP_TRY(ctx, hipMemcpyAsync((uint8_t*)sl.ent.p + ent_off, (uint8_t*)sl.h_in + na, nb, hipMemcpyHostToDevice, ctx->copy));
     BBP_HIP_TRY(ctx, hipEventRecord(sl.ev_in, ctx->copy));
     BBP_HIP_TRY(ctx, wait_event_polling(sl.ev_in));
     return BBP_OK;
@@ -372,6 +406,23 @@ static int32_t fetch_results(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, size_t bytes) {
 }
 }  // namespace bbp
 
+// key of a host-pointer call that draws on the device: the armed test key (bbp_debug_next_entropy_key), else 32 OS bytes
+static int32_t next_device_key(bbp_ctx* ctx, ChachaKey* key) {
+    uint8_t k[32];
+    bool armed = false;
+    api_guard(ctx, [&]() -> int32_t {
+        if ((armed = ctx->debug_key_armed)) memcpy(k, ctx->debug_key, 32);
+        ctx->debug_key_armed = false;
+        return BBP_OK;
+    });
+    if (!armed && !os_random(k, sizeof k)) {
+        api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
+        return BBP_ERR_DEVICE;
+    }
+    *key = chacha_key_from_bytes(k);
+    return BBP_OK;
+}
+
 // bbp_debug_corrupt_next_proof: the armed record index, relative to this launch's first proof, is corrupted on `s` right after the
 // prover wrote it (before any check reads it); the hook fires once
 static int32_t corrupt_hook(bbp_ctx* ctx, u32 first, u32 nb, u32 N, u8* out_dev, hipStream_t s) {
@@ -391,9 +442,10 @@ static size_t check_scratch_bytes(u32 B, u32 N) { return align256(check_row_byte
 // One checked prove launch (context lock held): witness check on the opening stream, the prover, the verify rows and the aggregated
 // verifier on a verifier lane's stream -- forked from the records' completion on `s`, joined back before the status merge on `s`.
 // Everything this call writes is complete for work enqueued on `s` afterwards.  `scratch` holds check_scratch_bytes(B, N);
-// `reuse` (optional) is the event after which `scratch` and `mask` may be overwritten.
+// `reuse` (optional) is the event after which `scratch` and `mask` may be overwritten; `draw` (optional) writes `ent` on the opening stream.
 static int32_t prove_checked_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* in, const u8* ent, const u8* cent, u8* out, int32_t* status,
-                                     u32* mask, u8* scratch, u32* fail_n, u32* fail_idx, u32 idx_base, hipStream_t s, hipEvent_t reuse) {
+                                     u32* mask, u8* scratch, u32* fail_n, u32* fail_idx, u32 idx_base, hipStream_t s, hipEvent_t reuse,
+                                     const std::function<int32_t(hipStream_t)>* draw = nullptr) {
     int32_t rc;
     if (!ctx->chk_counts) {
         BBP_HIP_TRY(ctx, hipMalloc(&ctx->chk_counts, 2 * sizeof(unsigned long long)));
@@ -405,6 +457,10 @@ static int32_t prove_checked_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* in, c
     if ((rc = serial_lds_bytes(ctx, (const void*)k_witness_check, &hog))) return rc;
     const std::function<int32_t(hipStream_t)> open_hook = [&](hipStream_t os) -> int32_t {
         if (reuse) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, reuse, 0));
+        if (draw) {  // the call's entropy, drawn on the device before the opening stage reads it
+            const int32_t rc = (*draw)(os);
+            if (rc) return rc;
+        }
         ScopedEvent ev(ctx, TAG_WITNESS, os);
         hipLaunchKernelGGL(k_witness_check, dim3((B + 63) / 64), dim3(64), hog, os, B, N, in, ctx->mimc_c, mask);
         BBP_HIP_TRY(ctx, hipGetLastError());
@@ -493,8 +549,12 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         }
     }
     const uint8_t* src = fixed.empty() ? in : fixed.data();
+    // source DEVICE: one key for the call, each chunk's rows drawn on its opening stream (k_draw_entropy); only the key leaves the OS
+    const bool dev_draw = !entropy && ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
+    ChachaKey key{};
+    if (dev_draw && (rc = next_device_key(ctx, &key))) return rc;
     std::vector<uint8_t> ent_host;
-    if (!entropy) {
+    if (!entropy && !dev_draw) {
         // thread_rng replacement: 64 OS bytes per blinding, wide-reduced like Scalar::random; 32 OS bytes for the rng seed
         const uint32_t m = 4 + N;
         std::vector<uint8_t> raw((size_t)B * (64 * m + 32));
@@ -519,11 +579,13 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
     // come back behind the records: statuses, witness masks, the count and the rows of rejected records (k_check_merge)
     std::vector<uint8_t> ent_all;
     const uint8_t* up_ent = entropy;
-    size_t up_ent_bytes = ent_stride * B;
+    size_t up_ent_bytes = dev_draw ? 0 : ent_stride * B;
+    const size_t up_ent_off = dev_draw ? ent_stride * B : 0;  // (drawn rows below it)
     if (check) {
-        ent_all.resize(ent_stride * B + 32 * (size_t)B);
-        memcpy(ent_all.data(), entropy, ent_stride * B);
-        if (!os_random(ent_all.data() + ent_stride * B, 32 * (size_t)B)) {
+        const size_t own = dev_draw ? 0 : ent_stride * B;
+        ent_all.resize(own + 32 * (size_t)B);
+        if (own) memcpy(ent_all.data(), entropy, own);
+        if (!os_random(ent_all.data() + own, 32 * (size_t)B)) {
             api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
             return BBP_ERR_DEVICE;
         }
@@ -547,7 +609,7 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = dev_reserve(ctx, sl.out, out_bytes)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, out_bytes)) ||
             (check && (rc = dev_reserve(ctx, sl.chk, check_scratch_bytes(B, N)))) ||
-            (rc = upload_inputs(ctx, sl, src, in_stride * B, up_ent, up_ent_bytes)))
+            (rc = upload_inputs(ctx, sl, src, in_stride * B, up_ent, up_ent_bytes, up_ent_off)))
             return rc;
         t_h2d = now_ms();
         u8* info = (u8*)sl.out.p + info_off;
@@ -562,13 +624,18 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
             const uint32_t nb = B - first < chunk ? B - first : chunk;
             const u8 *cin = (const u8*)sl.in.p + in_stride * first, *cent = (const u8*)sl.ent.p + ent_stride * first;
             u8* cout = (u8*)sl.out.p + out_stride * first;
+            // (source DEVICE) this chunk's own rows of the call's key: no two chunks draw equal rows
+            const std::function<int32_t(hipStream_t)> draw = [&](hipStream_t os) -> int32_t {
+                return draw_enqueue(ctx, nb, N, BBP_ENTROPY_PROVE, key, first, (void*)cent, os);
+            };
             if (check) {
                 u8* scratch = (u8*)sl.chk.p;  // chunks are stream-ordered on ctx->stream; each chunk's check joins back before the next starts
                 if ((rc = prove_checked_enqueue(ctx, nb, N, cin, cent, (const u8*)sl.ent.p + ent_stride * B + 32 * (size_t)first, cout,
-                                                st_dev + first, mask_dev + first, scratch, fail_n, fail_idx, first, ctx->stream, nullptr)))
+                                                st_dev + first, mask_dev + first, scratch, fail_n, fail_idx, first, ctx->stream, nullptr,
+                                                dev_draw ? &draw : nullptr)))
                     return rc;
             } else {
-                if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream))) return rc;
+                if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream, dev_draw ? &draw : nullptr))) return rc;
                 if ((rc = corrupt_hook(ctx, first, nb, N, cout, ctx->stream))) return rc;
             }
         }
@@ -609,14 +676,18 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
     if (first_refused >= 0) set_tls_error(ctx, std::string("row ") + std::to_string(first_refused) + ": " + witness_check_text(dmask[first_refused]));
     if (mode == CHECK_REPROVE || fail_rows.empty()) return BBP_OK;
     // a record that failed its check is proved once more with the same inputs and the same entropy (the drawn entropy when the
-    // caller gave none), and checked again; a second failure is a device fault: the whole call fails and health bit 1 is raised
+    // caller gave none; source DEVICE: the row re-derived from the call's key), and checked again; a second failure is a device
+    // fault: the whole call fails and health bit 1 is raised
     std::sort(fail_rows.begin(), fail_rows.end());
     const uint32_t nr = (uint32_t)fail_rows.size();
     std::vector<uint8_t> rin(in_stride * nr), rent(ent_stride * nr), rout(out_stride * nr);
     std::vector<int32_t> rst(nr);
     for (uint32_t j = 0; j < nr; j++) {
         memcpy(&rin[in_stride * j], src + in_stride * fail_rows[j], in_stride);
-        memcpy(&rent[ent_stride * j], entropy + ent_stride * fail_rows[j], ent_stride);
+        if (dev_draw)
+            entropy_prove_row_bytes(key, N, fail_rows[j], &rent[ent_stride * j]);
+        else
+            memcpy(&rent[ent_stride * j], entropy + ent_stride * fail_rows[j], ent_stride);
     }
     ctx->chk_reproved += nr;
     if ((rc = prove_batch_host(ctx, nr, N, rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE))) return rc;
@@ -744,6 +815,46 @@ extern "C" int32_t bbp_debug_corrupt_next_proof(bbp_ctx* ctx, uint32_t index) {
     });
 }
 
+extern "C" int32_t bbp_draw_entropy_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t kind, const uint8_t* key32, void* out_dev, void* stream) {
+    if (!ctx || !out_dev || (kind != BBP_ENTROPY_PROVE && kind != BBP_ENTROPY_VERIFY)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_draw_entropy_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc;
+        if (kind == BBP_ENTROPY_PROVE && (rc = check_n(ctx, N))) return rc;
+        if (B == 0) return BBP_OK;
+        uint8_t k[32];
+        if (key32)
+            memcpy(k, key32, sizeof k);
+        else if (!os_random(k, sizeof k))
+            return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = pick_stream(ctx, stream);
+        if ((rc = draw_enqueue(ctx, B, N, kind, chacha_key_from_bytes(k), 0, out_dev, s))) return rc;
+        if (kind == BBP_ENTROPY_PROVE) {  // the next prove call's opening stage waits for these rows (not ev_prep: see context.h)
+            BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_draw, s));
+            ctx->ev_draw_valid = true;
+        }
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_set_entropy_source(bbp_ctx* ctx, int32_t source) {
+    if (!ctx || (source != BBP_ENTROPY_SOURCE_OS && source != BBP_ENTROPY_SOURCE_DEVICE)) return BBP_ERR_BAD_ARG;
+    for (bbp_ctx* m : ctx->members) bbp_set_entropy_source(m, source);
+    ctx->entropy_source = source;
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]) {
+    if (!ctx || !key32) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_next_entropy_key");
+    return api_guard(ctx, [&]() -> int32_t {
+        memcpy(ctx->debug_key, key32, sizeof ctx->debug_key);
+        ctx->debug_key_armed = true;
+        return BBP_OK;
+    });
+}
+
 // what the call combiner runs for a group of concurrent bbp_prove callers (submit.cpp)
 int32_t bbp::prove_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out,
                                 int32_t* status, std::string* err) {
@@ -841,8 +952,13 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
                                  uint32_t group = 0, uint32_t* n_fallback = nullptr) {
     const size_t stride = (size_t)(rec_ver ? 1217u : 1121u) + 32 * (4 + (size_t)N) + 96 + (size_t)N * 32;
     if (group == 0 && rec_ver == 0 && ctx->verify_group > 1 && B >= 2 * ctx->verify_group) group = ctx->verify_group;  // BBP_VERIFY_AGGREGATE
-    std::vector<uint8_t> ent((size_t)B * 32);
-    if (!os_random(ent.data(), ent.size())) {  // Verifier::verify mixes thread_rng into its TranscriptRng (A.7)
+    // Verifier::verify mixes thread_rng into its TranscriptRng (A.7): 32 OS bytes per proof, or (source DEVICE) rows of one key
+    const bool dev_draw = ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
+    ChachaKey key{};
+    std::vector<uint8_t> ent(dev_draw ? 0 : (size_t)B * 32);
+    if (dev_draw) {
+        if (int32_t rc = next_device_key(ctx, &key)) return rc;
+    } else if (!os_random(ent.data(), ent.size())) {
         api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
         return BBP_ERR_DEVICE;
     }
@@ -853,8 +969,9 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
         int32_t rc;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = dev_reserve(ctx, sl.out, 4 * ((size_t)B + 1))) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, 4 * ((size_t)B + 1))) ||
-            (rc = upload_inputs(ctx, sl, in, stride * B, ent.data(), ent.size())))
+            (rc = upload_inputs(ctx, sl, in, stride * B, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0)))
             return rc;
+        if (dev_draw && (rc = draw_enqueue(ctx, B, N, BBP_ENTROPY_VERIFY, key, 0, sl.ent.p, L.stream))) return rc;  // ahead of every chunk on the lane
         const uint32_t n_chunks = (B + host_chunk_verify() - 1) / host_chunk_verify(), chunk = (B + n_chunks - 1) / n_chunks;
         for (uint32_t first = 0; first < B; first += chunk) {  // bounded scratch for any B (see bbp_prove_batch)
             const uint32_t nb = B - first < chunk ? B - first : chunk;

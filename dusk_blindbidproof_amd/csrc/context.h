@@ -166,6 +166,12 @@ struct bbp_ctx {
     uint32_t seq_at_last_verify = 0;                     // prover call counter seen by the last verification (interleaving test)
     hipEvent_t ev_prep = nullptr;  // end of the last bbp_prepare_bids_dev: the next prove call's opening stage waits for it
     bool ev_prep_valid = false;
+    hipEvent_t ev_draw = nullptr;  // end of the last prove-kind bbp_draw_entropy_dev: the same rule as ev_prep, an event of its own
+    bool ev_draw_valid = false;
+    // On-device entropy (bbp_set_entropy_source, capi_prove.hip): where host-pointer calls without caller entropy get theirs
+    std::atomic<int> entropy_source{BBP_ENTROPY_SOURCE_OS};
+    bool debug_key_armed = false;  // bbp_debug_next_entropy_key: the next device draw of a host-pointer call uses debug_key
+    uint8_t debug_key[32] = {};
     uint32_t seq = 0;
     int last_par = 0;
     // calls on one context share scratch buffers: a call issued on a different caller stream than the previous one is ordered

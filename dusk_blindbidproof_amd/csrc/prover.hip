@@ -1642,7 +1642,8 @@ static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd
 
 // in_dev: B * (7*32 + N*32 + 8) ; ent_dev: B * (32 m + 32) ; out_dev: B * (1121 + 32 m).  All device pointers.
 // open_hook (optional): called once with the opening stream after its waits, before the opening kernels -- work that reads the
-// inputs only and should run beside the draw chain rather than on the caller's stream (checked proving's witness check)
+// inputs only and should run beside the draw chain rather than on the caller's stream (checked proving's witness check), or that
+// writes ent_dev for this call (the host path's on-device entropy, bbp_set_entropy_source)
 int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s,
                         const std::function<int32_t(hipStream_t)>* open_hook) {
     const CircuitDev* cp;
@@ -1707,6 +1708,10 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
         if (ctx->ev_prep_valid) {  // rows written by bbp_prepare_bids_dev since the last prove call
             BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_prep, 0));
             ctx->ev_prep_valid = false;
+        }
+        if (ctx->ev_draw_valid) {  // prove rows drawn by bbp_draw_entropy_dev since the last prove call
+            BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_draw, 0));
+            ctx->ev_draw_valid = false;
         }
         if (open_hook && (rc = (*open_hook)(s))) return rc;
         LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);

@@ -260,6 +260,7 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&sl.ev_in, hipEventDisableTiming));
     }
     BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
+    BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_draw, hipEventDisableTiming));
     if (const char* e = getenv("BBP_VERIFY_OVERLAP")) ctx->verify_overlap = atoi(e) != 0;
     if (const char* e = getenv("BBP_VERIFY_SERIAL_ACC")) ctx->verify_serial_acc = atoi(e) != 0;
     for (auto& e : ctx->ev_vacc) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
@@ -424,6 +425,7 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
     for (int f = 0; f < bbp_ctx::FAMILIES; f++)
         if (ctx->ev_last[f]) (void)hipEventDestroy(ctx->ev_last[f]);
     if (ctx->ev_prep) (void)hipEventDestroy(ctx->ev_prep);
+    if (ctx->ev_draw) (void)hipEventDestroy(ctx->ev_draw);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->copy) (void)hipStreamDestroy(ctx->copy);
     if (ctx->side2) (void)hipStreamDestroy(ctx->side2);
@@ -500,6 +502,11 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
         if (off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "checked proving: %s\n",
                                       ctx->prove_check ? "on (every record is verified on the device before it is returned)" : "off");
+        if (off + 1 < cap)
+            off += (uint32_t)snprintf(buf + off, cap - off, "entropy source: %s\n",
+                                      ctx->entropy_source == BBP_ENTROPY_SOURCE_DEVICE
+                                          ? "device (one 32-byte OS key per call, expanded with ChaCha20 on the device)"
+                                          : "os (the calling thread reads /dev/urandom and reduces the blindings on the host)");
         if (free_b < ((size_t)6 << 30) && off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "WARNING: less than 6 GiB of device memory free: a 1024-proof batch needs ~14 GiB of scratch\n");
         return BBP_OK;

@@ -531,7 +531,7 @@ static void usage(const char* argv0) {
     fprintf(stderr,
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
-            "          [--check-proofs]\n",
+            "          [--check-proofs] [--entropy os|device]\n",
             argv0);
 }
 
@@ -543,6 +543,7 @@ int main(int argc, char** argv) {
     uint32_t window_us = 200, max_batch = 4096;
     int io_threads = 2;
     bool check_proofs = false;  // --check-proofs: every proof is verified on the device before it is answered (bbp_set_prove_check)
+    bool device_entropy = false;  // --entropy device: one OS key per engine call, expanded on the device (bbp_set_entropy_source)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -576,6 +577,14 @@ int main(int argc, char** argv) {
         else if (a == "--verify-aggregate") setenv("BBP_VERIFY_AGGREGATE", val(), 1);  // opcode-2 batches of >= 2 G proofs are checked in groups of G with
                                                                                          // per-proof fallback: same verdicts, 2-3x the rate (include/bbp.h)
         else if (a == "--check-proofs") check_proofs = true;
+        else if (a == "--entropy") {
+            const std::string v = val();
+            if (v != "os" && v != "device") {
+                usage(argv[0]);
+                return 2;
+            }
+            device_entropy = v == "device";
+        }
         else if (a == "--reserve") {
             for (const char* p = val(); *p;) {
                 reserve_items.push_back(atoi(p));
@@ -633,6 +642,15 @@ int main(int argc, char** argv) {
                 return 2;
             }
             logf(2, "checked proving on: every proof is verified on the device before it is answered");
+        }
+        if (device_entropy) {  // resolved only when asked for: an engine without it cannot honour the flag, so the server does not start
+            auto set_source = (decltype(&bbp_set_entropy_source))dlsym(g_eng.so, "bbp_set_entropy_source");
+            if (!set_source || set_source(g_eng.ctx, BBP_ENTROPY_SOURCE_DEVICE) != BBP_OK) {
+                logf(0, "--entropy device: the engine %s does not provide on-device entropy (bbp_set_entropy_source)", engine_path.c_str());
+                g_eng.free_(g_eng.ctx);
+                return 2;
+            }
+            logf(2, "entropy source: device (one OS key per engine call, expanded with ChaCha20 on the device)");
         }
         if (g_eng.describe) {  // what the engine runs on; its WARNING lines (hardware queues, memory) at warn level
             static char report[8192];

@@ -294,6 +294,41 @@ int32_t bbp_prove_batch_checked_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const 
  * out of bounds; an index beyond the call's batch corrupts nothing and is consumed all the same).  A pool refuses it. */
 int32_t bbp_debug_corrupt_next_proof(bbp_ctx* ctx, uint32_t index);
 
+/* ---- On-device entropy ----------------------------------------------------------------------------------------------------------
+ * Every proof needs (4+N) commitment blindings and a 32-byte TranscriptRng seed (thread_rng, src/blindbid/proof.rs:53-64); every
+ * verification a 32-byte seed for its weights.  These calls expand ONE 32-byte key on the device with ChaCha20 (RFC 8439 2.3:
+ * 256-bit key, 32-bit block counter, 96-bit nonce, 64-byte blocks) into exactly the layouts the prove / verify entry points take,
+ * one ChaCha20 stream per row (rows are re-derivable one by one):
+ *   prove row i, list length N, m = 4+N   nonce = "BBPE" || u32le(N) || u32le(i); blinding k < m = the 64-byte block(key, k, nonce)
+ *                                         read as a little-endian integer, mod l (from_bytes_mod_order_wide), 32 canonical bytes at 32k;
+ *                                         the rng seed = the first 32 bytes of block(key, m, nonce), at 32m -- bbp_entropy_size(N) bytes
+ *   verify row i                          nonce = "BBPV" || u32le(0) || u32le(i); the row = the first 32 bytes of block(key, 0, nonce)
+ * A KEY USED FOR TWO CALLS REUSES EVERY BLINDING: two proofs with equal blindings reveal their witness (d, k), exactly as reusing
+ * explicit `entropy` does.  Pass key32 = NULL (32 fresh OS bytes per call) unless the rows must be reproducible (tests). */
+#define BBP_ENTROPY_PROVE 0u  /* rows of bbp_entropy_size(N) bytes */
+#define BBP_ENTROPY_VERIFY 1u /* rows of 32 bytes (N ignored)      */
+/* B rows of `kind` into out_dev (device memory, B * bbp_entropy_size(N) or B * 32 bytes) under key32 (host memory; NULL = 32 fresh
+ * OS bytes).  Stream-ordered on `stream` (a hipStream_t or BBP_STREAM_CONTEXT), no synchronisation.  Prove rows follow the exception of
+ * bbp_prepare_bids_dev: the next bbp_prove_batch_dev / bbp_prove_batch_checked_dev on this context waits for them by itself (an event of
+ * their own: a prepare and a draw on two different streams are both waited for); verify rows are ordered by the caller, like any other
+ * _dev input.  A pool refuses it, like every *_dev call. */
+int32_t bbp_draw_entropy_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t kind, const uint8_t* key32, void* out_dev, void* stream);
+/* Where the host-pointer calls get their randomness when the caller gives none (bbp_prove / bbp_prove_async / bbp_prove_batch with
+ * entropy == NULL, combined or not; bbp_verify[_async] / bbp_verify_batch[_aggregated], which never take any):
+ *   BBP_ENTROPY_SOURCE_OS       (default) the calling thread reads 64 bytes per blinding and 32 per seed from /dev/urandom and reduces
+ *                               the blindings on the host, then uploads them with the inputs
+ *   BBP_ENTROPY_SOURCE_DEVICE   one 32-byte OS key per engine call (per member of a pool), expanded on the device as above, ordered
+ *                               before the prover's opening stage / the verifier; the host reads 32 bytes per call
+ * Rows with caller entropy are untouched; a host batch cut into chunks (BBP_HOST_CHUNK_PROVE) draws each chunk's own row range of the
+ * call's key; checked proving re-proves a failed record with its row re-derived from the same key (the bytes an unchecked call returns
+ * under that key).  The *_dev entry points still require entropy_dev.  On a pool: every member.  bbp_describe reports the source. */
+#define BBP_ENTROPY_SOURCE_OS 0
+#define BBP_ENTROPY_SOURCE_DEVICE 1
+int32_t bbp_set_entropy_source(bbp_ctx* ctx, int32_t source);
+/* Test hook: the key of the next host-pointer call that draws on the device (source DEVICE, no caller entropy) instead of 32 OS bytes,
+ * so that its records can be compared with an explicit-entropy call; consumed by that call.  A pool refuses it (take a member). */
+int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]);
+
 /* Parity hook: the 32-scalar challenge block of proof `proof` of the LAST batch call of geometry (B, N):
  * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch.h), 32 x 32 bytes. */
 int32_t bbp_debug_challenges(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t proof, uint8_t* out32x32);
