@@ -13,7 +13,11 @@ namespace bbp {
 // 64-bit rotate left.  On the device a rotation by a constant is two v_alignbit_b32 (the compiler's own lowering of the shift /
 // or form costs three instructions: 64-bit shift, 32-bit shift, or) -- 27 of the ~300 instructions of a Keccak round, and the
 // prover's 2935-permutation rng chain runs at exactly the single-wave issue limit.
+// n is taken mod 64 and a rotation by 0 returns x: v_alignbit_b32 reads its shift mod 32, so s = 32 would select b and swap the
+// halves, and the host's x >> 64 is undefined.  For the literal amounts of keccak_f1600_body both checks fold away.
 BBP_HD u64 rotl64(u64 x, int n) {
+    n &= 63;
+    if (n == 0) return x;
 #if defined(__HIP_DEVICE_COMPILE__)
     const u32 lo = (u32)x, hi = (u32)(x >> 32);
     if (n == 32) return ((u64)lo << 32) | hi;

@@ -59,6 +59,29 @@ void hc_fe_op(int op, const uint8_t* a32, const uint8_t* b32, uint8_t* out32) {
     fe_tobytes(out32, r);
 }
 
+// raw signed limbs in, raw limbs and canonical bytes out; op codes as device_check.hip dc_fe_limbs: 0 mul(a, b), 1 sq(a), 2 sq2(a),
+// 3 mul_small(a, b[0]), 4 mul(a + b, a - b), 5 towords(a), 6 iszero(a), 7 isneg(a), 8 eq(a, b) (ops 5..8: bytes of a, predicate in limb 0)
+void hc_fe_limbs(int op, const int32_t* a10, const int32_t* b10, int32_t* out10, uint8_t* out32) {
+    fe a, b, r = fe_zero();
+    for (int i = 0; i < 10; i++) {
+        a.v[i] = a10[i];
+        b.v[i] = b10[i];
+    }
+    switch (op) {
+        case 0: r = fe_mul(a, b); break;
+        case 1: r = fe_sq(a); break;
+        case 2: r = fe_sq2(a); break;
+        case 3: r = fe_mul_small(a, (u32)b.v[0] & 0x3ffffffu); break;
+        case 4: r = fe_mul(fe_add(a, b), fe_sub(a, b)); break;
+        case 6: r.v[0] = fe_iszero(a) ? 1 : 0; break;
+        case 7: r.v[0] = fe_isneg(a) ? 1 : 0; break;
+        case 8: r.v[0] = fe_eq(a, b) ? 1 : 0; break;
+        default: break;
+    }
+    for (int i = 0; i < 10; i++) out10[i] = r.v[i];
+    fe_tobytes(out32, op >= 5 ? a : r);
+}
+
 // NAF recoding used by the MSM kernels: writes (position, signed digit) pairs, returns the count (width 12 or 9)
 int hc_sc_naf(int width, const uint8_t* a32, int32_t* pos_out, int32_t* digit_out) {
     u32 w[8];
@@ -291,6 +314,8 @@ void hc_kw_keccak_f(uint8_t* st200) {
         if (c[L].live) st[c[L].word] = kw_join(x.v[L] ^ k[L].v[24], x.v[L + 32] ^ k[L + 32].v[24]);
     memcpy(st200, st, 200);
 }
+
+uint64_t hc_rotl64(uint64_t x, int n) { return rotl64(x, n); }
 
 void hc_keccak_f(uint8_t* st200) {
     u64 s[25];

@@ -101,3 +101,19 @@ def test_exception_barrier_turns_a_throw_into_a_status(bbp, monkeypatch):
     assert compile_circuit(8)[0] == 6
     monkeypatch.delenv("BBP_FAULT_INJECT")
     assert compile_circuit(8)[0] == 0
+
+
+def test_device_check_libraries_export_every_entry_point(built, bbp):
+    """tests/device_check.hip (the gpu tier's view of the product headers) cross-compiles for gfx950 in both field variants, and both
+    libraries load and export every dc_* entry point the source defines, each one bound in tests/test_gpu_device_arith.py"""
+    from tests.test_gpu_device_arith import SIGNATURES, VARIANTS
+    src = open(os.path.join(ROOT, "tests", "device_check.hip")).read()
+    defined = sorted(set(re.findall(r"^int (dc_[a-z0-9_]+)\(", src, flags=re.M)))
+    assert len(defined) >= 13 and defined == sorted(SIGNATURES)
+    for v in VARIANTS:
+        path = built.build_devcheck(v)
+        blob = open(path, "rb").read()
+        assert b"gfx950" in blob, v
+        L = ctypes.CDLL(path)
+        for n in defined:
+            assert hasattr(L, n), (v, n)
