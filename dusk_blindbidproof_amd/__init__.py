@@ -5,8 +5,10 @@ The library has no CPU compute path: importing works anywhere (so the C-ABI surf
 """
 from ._native import (Context, Pool, BbpError, lib, lib_path, STATUS, SIGNATURES, record_size, entropy_size,
                       LAYOUT_BLIND_G_H, LAYOUT_BLIND_G, BASE_BBLIND, BASE_G0, BASE_H0, BASE_B, NUM_BASES, STREAM_CONTEXT,
-                      compile_circuit, ENTROPY_PROVE, ENTROPY_VERIFY, ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE)
+                      compile_circuit, ENTROPY_PROVE, ENTROPY_VERIFY, ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE, verify_row_size,
+                      mixed_row_offsets, pack_mixed_rows)
 
 __all__ = ["Context", "Pool", "BbpError", "lib", "lib_path", "STATUS", "SIGNATURES", "record_size", "entropy_size",
            "LAYOUT_BLIND_G_H", "LAYOUT_BLIND_G", "BASE_BBLIND", "BASE_G0", "BASE_H0", "BASE_B", "NUM_BASES", "STREAM_CONTEXT", "compile_circuit",
-           "ENTROPY_PROVE", "ENTROPY_VERIFY", "ENTROPY_SOURCE_OS", "ENTROPY_SOURCE_DEVICE"]
+           "ENTROPY_PROVE", "ENTROPY_VERIFY", "ENTROPY_SOURCE_OS", "ENTROPY_SOURCE_DEVICE", "verify_row_size", "mixed_row_offsets",
+           "pack_mixed_rows"]

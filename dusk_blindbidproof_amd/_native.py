@@ -51,6 +51,10 @@ SIGNATURES = {
     "bbp_prepare_bids_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_batch_aggregated": (_i32, [_vp, _u32, _u32, _vp, _vp, _u32, _vp]),
     "bbp_verify_batch_aggregated_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "bbp_verify_batch_mixed": (_i32, [_vp, _u32, _vp, _vp, _vp]),
+    "bbp_verify_batch_mixed_aggregated": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "bbp_verify_batch_mixed_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_batch_mixed_aggregated_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "bbp_reserve": (_i32, [_vp, _u32, _u32]),
     "bbp_set_batching": (_i32, [_vp, _u32, _u32]),
     "bbp_batching_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u32)]),
@@ -100,6 +104,32 @@ def record_size(n):
 
 def entropy_size(n):
     return 32 * (4 + n) + 32
+
+
+def verify_row_size(n):
+    """Bytes of one verify row for list length n: record || score || z_img || seed || pub_list."""
+    return record_size(n) + 96 + 32 * n
+
+
+def mixed_row_offsets(Ns):
+    """Byte offset of every row of a mixed-N verify input, and the total size last (len(Ns) + 1 entries)."""
+    off = [0]
+    for n in Ns:
+        off.append(off[-1] + verify_row_size(n))
+    return off
+
+
+def pack_mixed_rows(rows):
+    """[(record, score, z_img, seed, pub_list)] -> (Ns, input bytes) for verify_batch_mixed*: rows back to back in request order,
+    N of each row from its pub_list."""
+    Ns, parts = [], []
+    for record, score, z_img, seed, pub_list in rows:
+        n = len(pub_list) // 32
+        if len(pub_list) != 32 * n or len(record) != record_size(n) or not len(score) == len(z_img) == len(seed) == 32:
+            raise ValueError("row does not have the layout of list length %d" % n)
+        Ns.append(n)
+        parts += [record, score, z_img, seed, pub_list]
+    return Ns, b"".join(bytes(p) for p in parts)
 
 
 def _buf(b):
@@ -265,6 +295,34 @@ class Context:
                                                         ctypes.byref(nfb) if want_count else None, _stream(stream)))
         return nfb.value if want_count else None
 
+    def verify_batch_mixed(self, Ns, inputs):
+        """Rows of any mix of list lengths in one call (pack_mixed_rows): one status per row, as verify_batch with that row's N."""
+        B = len(Ns)
+        status = (ctypes.c_int32 * B)()
+        self._check(lib.bbp_verify_batch_mixed(self._h, B, (_u32 * B)(*Ns), _buf(inputs), status))
+        return list(status)
+
+    def verify_batch_mixed_aggregated(self, Ns, inputs, group=0):
+        """verify_batch_aggregated over mixed rows, groups cut by index: (statuses, proofs checked individually)."""
+        B = len(Ns)
+        status = (ctypes.c_int32 * B)()
+        nfb = ctypes.c_uint32()
+        self._check(lib.bbp_verify_batch_mixed_aggregated(self._h, B, (_u32 * B)(*Ns), _buf(inputs), status, group, ctypes.byref(nfb)))
+        return list(status), nfb.value
+
+    def verify_batch_mixed_dev(self, Ns, in_ptr, ent_ptr, status_ptr, stream=None):
+        """Stream-ordered; Ns is read during the call only."""
+        B = len(Ns)
+        self._check(lib.bbp_verify_batch_mixed_dev(self._h, B, (_u32 * B)(*Ns), in_ptr, ent_ptr, status_ptr, _stream(stream)))
+
+    def verify_batch_mixed_aggregated_dev(self, Ns, in_ptr, ent_ptr, status_ptr, group=0, stream=None, want_count=True):
+        """As verify_batch_aggregated_dev: want_count=False leaves the call asynchronous and returns None."""
+        B = len(Ns)
+        nfb = ctypes.c_uint32()
+        self._check(lib.bbp_verify_batch_mixed_aggregated_dev(self._h, B, (_u32 * B)(*Ns), in_ptr, ent_ptr, status_ptr, group,
+                                                              ctypes.byref(nfb) if want_count else None, _stream(stream)))
+        return nfb.value if want_count else None
+
     def prove_batch_dev(self, B, N, in_ptr, ent_ptr, out_ptr, stream=None):
         self._check(lib.bbp_prove_batch_dev(self._h, B, N, in_ptr, ent_ptr, out_ptr, _stream(stream)))
 
@@ -372,7 +430,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / msm_batch (block-split over the members, results in request order); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / msm_batch (block-split over the members, results in request order); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):

@@ -17,9 +17,10 @@ namespace bbp {
 int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s,
                         const std::function<int32_t(hipStream_t)>* open_hook = nullptr);
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
-int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
+int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
+                            const u32* ns = nullptr);
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                             u32* n_fallback, u32* total_out_dev = nullptr);
+                             u32* n_fallback, u32* total_out_dev = nullptr, const u32* ns = nullptr);
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out);
 
 // native (non-circuit) image of the gadget wiring: what the reference's Go caller computes before Proof::prove
@@ -948,9 +949,17 @@ extern "C" int32_t bbp_prove_async(bbp_ctx* ctx, const uint8_t scalars7[7 * 32],
 
 // rec_ver 0: compact 1121-byte proofs; 1: the 2-phase 1217-byte R1CSProof layout (both parse in the reference)
 // Takes the context lock itself, for the enqueue phase only (aggregated mode synchronises inside it: the host reads group verdicts).
+// Ns (B entries, screened): a mixed-N call, rows of bbp_verify_batch_mixed packed back to back; N is then unused.
 static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status,
-                                 uint32_t group = 0, uint32_t* n_fallback = nullptr) {
+                                 uint32_t group = 0, uint32_t* n_fallback = nullptr, const uint32_t* Ns = nullptr) {
     const size_t stride = (size_t)(rec_ver ? 1217u : 1121u) + 32 * (4 + (size_t)N) + 96 + (size_t)N * 32;
+    std::vector<size_t> row_off;  // mixed: byte offset of every row, and the total at [B]
+    if (Ns) {
+        row_off.resize((size_t)B + 1);
+        row_off[0] = 0;
+        for (uint32_t i = 0; i < B; i++) row_off[i + 1] = row_off[i] + verify_row_size(Ns[i]);
+    }
+    const size_t in_bytes = Ns ? row_off[B] : stride * B;
     if (group == 0 && rec_ver == 0 && ctx->verify_group > 1 && B >= 2 * ctx->verify_group) group = ctx->verify_group;  // BBP_VERIFY_AGGREGATE
     // Verifier::verify mixes thread_rng into its TranscriptRng (A.7): 32 OS bytes per proof, or (source DEVICE) rows of one key
     const bool dev_draw = ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
@@ -969,18 +978,19 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
         int32_t rc;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = dev_reserve(ctx, sl.out, 4 * ((size_t)B + 1))) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, 4 * ((size_t)B + 1))) ||
-            (rc = upload_inputs(ctx, sl, in, stride * B, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0)))
+            (rc = upload_inputs(ctx, sl, in, in_bytes, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0)))
             return rc;
         if (dev_draw && (rc = draw_enqueue(ctx, B, N, BBP_ENTROPY_VERIFY, key, 0, sl.ent.p, L.stream))) return rc;  // ahead of every chunk on the lane
         const uint32_t n_chunks = (B + host_chunk_verify() - 1) / host_chunk_verify(), chunk = (B + n_chunks - 1) / n_chunks;
         for (uint32_t first = 0; first < B; first += chunk) {  // bounded scratch for any B (see bbp_prove_batch)
             const uint32_t nb = B - first < chunk ? B - first : chunk;
-            const u8 *cin = (const u8*)sl.in.p + stride * first, *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
+            const u8 *cin = (const u8*)sl.in.p + (Ns ? row_off[first] : stride * first), *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
             int32_t* cst = (int32_t*)sl.out.p + first;
+            const u32* cns = Ns ? Ns + first : nullptr;
             if (group > 1) {  // stream-ordered: no synchronisation while the context lock is held
                 if (first == 0 && L.agg_count) BBP_HIP_TRY(ctx, hipMemsetAsync(L.agg_count + 1, 0, sizeof(u32), L.stream));
-                if ((rc = verify_batch_agg_dev(ctx, nb, N, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B))) return rc;
-            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream)))
+                if ((rc = verify_batch_agg_dev(ctx, nb, N, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B, cns))) return rc;
+            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream, cns)))
                 return rc;
         }
         BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, L.stream));
@@ -1044,6 +1054,62 @@ extern "C" int32_t bbp_verify_batch_aggregated_dev(bbp_ctx* ctx, uint32_t B, uin
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         return verify_batch_agg_dev(ctx, B, N, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)in_dev, (const u8*)entropy_dev,
                                     (int32_t*)status_dev, pick_stream(ctx, stream), n_fallback);
+    });
+}
+
+// ---- mixed-N verification: rows of any mix of bid-list lengths in one call (include/bbp.h) ------------------------------------
+// Every row's N is screened on the host before anything is verified: a 0 anywhere is BBP_ERR_BAD_ARG, else an N above
+// BBP_MAX_ITEMS anywhere is BBP_ERR_GENS_LEN -- what a uniform call with that N returns.
+static int32_t check_ns(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns) {
+    for (uint32_t i = 0; i < B; i++)
+        if (Ns[i] == 0) return check_n(ctx, 0);
+    for (uint32_t i = 0; i < B; i++)
+        if (Ns[i] > BBP_MAX_ITEMS) return check_n(ctx, Ns[i]);
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_verify_batch_mixed(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status) {
+    if (!ctx || !in || !status || (B && !Ns)) return BBP_ERR_BAD_ARG;
+    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_ns(ctx, B, Ns); });
+    if (rc || B == 0) return rc;
+    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_batch_mixed(ctx, B, Ns, in, status, false, 0, nullptr); });
+    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, in, status, 0, nullptr, Ns); });
+}
+
+extern "C" int32_t bbp_verify_batch_mixed_aggregated(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, uint32_t group,
+                                                     uint32_t* n_fallback) {
+    if (n_fallback) *n_fallback = 0;
+    if (!ctx || !in || !status || (B && !Ns)) return BBP_ERR_BAD_ARG;
+    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_ns(ctx, B, Ns); });
+    if (rc || B == 0) return rc;
+    const uint32_t g = group ? group : BBP_AGG_GROUP_DEFAULT;
+    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_batch_mixed(ctx, B, Ns, in, status, true, g, n_fallback); });
+    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, in, status, g, n_fallback, Ns); });
+}
+
+extern "C" int32_t bbp_verify_batch_mixed_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev,
+                                              void* status_dev, void* stream) {
+    if (!ctx || !in_dev || !entropy_dev || !status_dev || (B && !Ns)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_batch_mixed_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc = check_ns(ctx, B, Ns);
+        if (rc || B == 0) return rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return verify_batch_dev_ex(ctx, B, 0, 0, 0, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev, pick_stream(ctx, stream), Ns);
+    });
+}
+
+extern "C" int32_t bbp_verify_batch_mixed_aggregated_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev,
+                                                         void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream) {
+    if (n_fallback) *n_fallback = 0;
+    if (!ctx || !in_dev || !entropy_dev || !status_dev || (B && !Ns)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_batch_mixed_aggregated_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc = check_ns(ctx, B, Ns);
+        if (rc || B == 0) return rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return verify_batch_agg_dev(ctx, B, 0, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev,
+                                    pick_stream(ctx, stream), n_fallback, nullptr, Ns);
     });
 }
 

@@ -202,6 +202,15 @@ struct bbp_ctx {
         int32_t* agg_gstatus = nullptr;                 // per-group verdicts of that pass (inside agg)
         bbp::u32* agg_count = nullptr;                  // [2] device counters: proofs of the current call on the per-proof path / running total
         hipEvent_t ev_vfork = nullptr, ev_vjoin = nullptr;  // variable-base kernel on lane[1] beside the generator MSM (lane 0 only)
+        // mixed-N calls (verifier_mixed.inc): pinned staging of the per-row N upload.  An entry is reused only once its copy has run
+        // (its event), so a call queued behind others on the lane never has its Ns overwritten by a later call.
+        struct NsStage {
+            void* h = nullptr;
+            size_t cap = 0;
+            hipEvent_t ev = nullptr;
+        };
+        std::vector<NsStage> ns_ring;
+        uint32_t ns_oldest = 0;  // the entry waited for when every entry is still queued (NS_RING of them)
     };
     VLane vl[VLANES];
     std::string err;
@@ -255,6 +264,8 @@ struct bbp_ctx {
     std::condition_variable io_cv;
     uint32_t io_next = 0, io_vnext = 0;
     std::map<uint32_t, void*> circuits;  // N -> CircuitDev* (compiled blind-bid circuit tables on the device)
+    void* vctab = nullptr;               // mixed-N verification: device table [MAX_ITEMS + 1] of VCirc (verifier_mixed.inc), entry N
+    uint8_t vctab_has[256] = {};         // filled once circuit N is compiled
     std::map<uint64_t, bbp::u32*> layout_idx;  // (layout << 32 | n_terms) -> device base-index list of bbp_msm_batch (capi_msm.hip)
     std::vector<float> timings;
     uint64_t scratch_allocs = 0;  // dev_reserve: how many times a grow-only scratch buffer was (re)allocated since bbp_init ...
@@ -451,6 +462,10 @@ int hw_queues_state();
 // pool.cpp: the host-pointer batch calls on a pool handle (block split by index over the members, results in request order)
 int32_t pool_prove_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status);
 int32_t pool_verify_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group, uint32_t* n_fallback);
+int32_t pool_verify_batch_mixed(bbp_ctx* pool, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group,
+                                uint32_t* n_fallback);
+// bytes of one bbp_verify_batch row for list length N: record || score || z_img || seed || pub_list
+inline size_t verify_row_size(uint32_t N) { return (size_t)bbp_proof_record_size(N) + 96 + 32 * (size_t)N; }
 int32_t pool_msm_batch(bbp_ctx* pool, uint32_t B, uint32_t n_terms, const uint8_t* scalars, uint32_t layout, uint8_t* out32);
 int32_t pool_reject(bbp_ctx* pool, const char* what);  // BBP_ERR_BAD_ARG + message: entry points that need ONE device
 void pool_workers_start(bbp_ctx* pool);

@@ -266,6 +266,23 @@ int32_t pool_verify_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* 
     return rc;
 }
 
+// mixed-N rows: the same contiguous blocks by index, byte offsets from Ns
+int32_t pool_verify_batch_mixed(bbp_ctx* pool, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group,
+                                uint32_t* n_fallback) {
+    std::vector<size_t> off((size_t)B + 1, 0);
+    for (uint32_t i = 0; i < B; i++) off[i + 1] = off[i] + verify_row_size(Ns[i]);
+    std::vector<uint32_t> nfb(pool->members.size(), 0);
+    const int32_t rc = for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
+        if (!aggregated) return bbp_verify_batch_mixed(m, hi - lo, Ns + lo, in + off[lo], status + lo);
+        return bbp_verify_batch_mixed_aggregated(m, hi - lo, Ns + lo, in + off[lo], status + lo, group, &nfb[m->member_index]);
+    });
+    if (n_fallback) {
+        *n_fallback = 0;
+        for (uint32_t v : nfb) *n_fallback += v;
+    }
+    return rc;
+}
+
 int32_t pool_msm_batch(bbp_ctx* pool, uint32_t B, uint32_t n_terms, const uint8_t* scalars, uint32_t layout, uint8_t* out32) {
     return for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
         return bbp_msm_batch(m, hi - lo, n_terms, scalars + (size_t)32 * n_terms * lo, layout, out32 + (size_t)32 * lo);

@@ -390,6 +390,7 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
         if (sl.ev) (void)hipEventDestroy(sl.ev);
         if (sl.ev_in) (void)hipEventDestroy(sl.ev_in);
     }
+    if (ctx->vctab) (void)hipFree(ctx->vctab);
     if (ctx->health) (void)hipFree(ctx->health);
     if (ctx->chk_counts) (void)hipFree(ctx->chk_counts);
     for (auto& cb : ctx->chk) {
@@ -405,6 +406,11 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
             if (p) (void)hipFree(p);
         if (L.ev_vfork) (void)hipEventDestroy(L.ev_vfork);
         if (L.ev_vjoin) (void)hipEventDestroy(L.ev_vjoin);
+        for (auto& e : L.ns_ring) {
+            if (e.h) (void)hipHostFree(e.h);
+            if (e.ev) (void)hipEventDestroy(e.ev);
+        }
+        L.ns_ring.clear();
         if (L.stream) (void)hipStreamDestroy(L.stream);
     }
     for (auto& kv : ctx->layout_idx)

@@ -589,6 +589,10 @@ __global__ BBP_LANE_KERNEL void k_fallback_final(const u32* __restrict__ counter
 }
 
 
+}  // namespace bbp
+#include "verifier_mixed.inc"
+namespace bbp {
+
 // in_dev: B * (record || score || z_img || seed || pub_list); ent_dev: B * 32; status_dev: B * int32
 // G = 0: every proof gets its own mega-check MSM (the reference's semantics, one Verifier::verify per proof).
 // G > 0: groups of G proofs share one weighted check; status_dev then only carries the rejections found before the group
@@ -599,12 +603,21 @@ static int vlane_of(const bbp_ctx* ctx, hipStream_t s) {  // a lane's own stream
     return 0;
 }
 
-int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
+// ns (host, B entries): a mixed-N call (verifier_mixed.inc): row i is bbp_verify_batch's row for N = ns[i], rows packed back to back
+// (compact records only); N is then unused.  Strides are those of the largest N; the launches are the same in number.
+int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
+                            const u32* ns) {
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
     const CircuitDev* cp;
-    int32_t rc = circuit_get(ctx, N, &cp);
-    if (rc) return rc;
+    int32_t rc;
+    MixedCall mx;
+    if (ns) {
+        if ((rc = mixed_prepare(ctx, B, ns, mx))) return rc;
+        cp = &mx.cmax;
+        rec_ver = 0;
+    } else if ((rc = circuit_get(ctx, N, &cp)))
+        return rc;
     const CircuitDev& c = *cp;
     BatchDev bd;
     StreamGuard guard(ctx, s, 1 + lane);  // this verifier lane: own batch buffer, own misc scratch, own MSM scratch slot
@@ -623,6 +636,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     size_t o_vpts = take((size_t)B * np * 32), o_vchal = take((size_t)B * VC_COUNT * 32), o_vs = take((size_t)B * 4098 * 32),
            o_tab = take((size_t)B * np * 8 * sizeof(ge)), o_var = take((size_t)B * np * sizeof(ge)), o_fixed = take((size_t)B * sizeof(ge)),
            o_sp = take((size_t)B * np * 32);
+    const size_t o_rows = ns ? take((size_t)B * sizeof(VRow)) : 0, o_ns = ns ? take((size_t)B * 4) : 0;
     if ((rc = dev_reserve(ctx, L.misc, off))) return rc;
     u8* base = static_cast<u8*>(L.misc.p);
     u32* vpts = (u32*)(base + o_vpts);
@@ -632,6 +646,11 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     ge* var = (ge*)(base + o_var);
     ge* fixed = (ge*)(base + o_fixed);
     u32* sp = (u32*)(base + o_sp);
+    const VRow* rows = (const VRow*)(base + o_rows);
+    if (ns) {
+        if ((rc = stage_ns(ctx, L, ns, B, (u32*)(base + o_ns), s))) return rc;
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, 1, VROWS_BLK, s, B, (const u32*)(base + o_ns), (VRow*)(base + o_rows));
+    }
     const merlin_transcript prefix = prover_prefix();
     // lanes per proof in k_varbase: as few as still give the launch ctx->varbase_lanes lanes (fewer lanes = more points per lane
     // sharing one doubling chain)
@@ -645,7 +664,15 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     const bool vb2 = vb_force ? vb_force == 2 : B < 4096;
     if (vb2) Q = 1;
     auto launch_varbase = [&](hipStream_t st, u32 agg_flag) -> int32_t {
-        if (vb2) {
+        if (ns) {
+            if (vb2) {
+                LAUNCH(ctx, TAG_VARBASE, k_varprep_mx, cdiv(B * npa, 64), 64, st, B, npa, np, rows, vpts, vchal, bd.misc, bd.wv, m, tab, sp, status_dev,
+                       agg_flag);
+                LAUNCH(ctx, TAG_VARBASE, k_varsum_mx, cdiv(B, 2), 64, st, B, np, rows, (const ge*)tab, (const u32*)sp, var);
+            } else
+                LAUNCH(ctx, TAG_VARBASE, k_varbase_mx, cdiv(B * Q, 64), 64, st, B, Q, np, rows, vpts, vchal, bd.misc, bd.wv, m, tab, sp, var,
+                       status_dev, agg_flag);
+        } else if (vb2) {
             LAUNCH(ctx, TAG_VARBASE, k_varprep, cdiv(B * npa, 64), 64, st, B, m, vpts, vchal, bd.misc, bd.wv, tab, sp, status_dev, agg_flag, rec_ver ? 0u : 1u);
             LAUNCH(ctx, TAG_VARBASE, k_varsum, cdiv(B, 2), 64, st, B, m, (const ge*)tab, (const u32*)sp, var, rec_ver ? 0u : 1u);
         } else
@@ -665,12 +692,20 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     constexpr int ko = 0;
 #endif
     LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);
-    LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse, cdiv(B, 64), 64, s, B, N, c.n_cst, rec_ver, in_dev, vpts, vchal, bd.cst, status_dev);
+    if (ns)
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_mx, cdiv(B, 64), 64, s, B, rows, np * 8, c.n_cst, in_dev, vpts, vchal, bd.cst, status_dev);
+    else
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse, cdiv(B, 64), 64, s, B, N, c.n_cst, rec_ver, in_dev, vpts, vchal, bd.cst, status_dev);
     {
         // BBP_V_FENCE=1 (experiment): the transcript replay's serial waves get CUs of their own like the prover's opening kernels
         static const int fence = getenv("BBP_V_FENCE") ? atoi(getenv("BBP_V_FENCE")) : 0;
         const u32 vtw = B <= (u32)ctx->tr_wave_below ? 1u : 0u;  // the replay of a few proofs: a wavefront each (as the prover's transcript kernels)
         if (ko & 4) {
+        } else if (ns) {
+            u32 hog = lds_token(ctx);
+            if (fence && ctx->serial_lds > 0 && (rc = serial_lds_bytes(ctx, (const void*)k_vtranscript_mx, &hog))) return rc;
+            LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript_mx, vtw ? B : cdiv(B, 64), 64, hog, s, B, rows, np * 8, prefix, vpts, ent_dev, vchal, bd.misc,
+                       status_dev, vtw);
         } else if (fence && ctx->serial_lds > 0) {
             u32 hog = 0;
             if ((rc = serial_lds_bytes(ctx, (const void*)k_vtranscript, &hog))) return rc;
@@ -679,11 +714,18 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
             LAUNCH(ctx, TAG_TRANSCRIPT, k_vtranscript, vtw ? B : cdiv(B, 64), 64, s, B, m, prefix, vpts, ent_dev, vchal, bd.misc, status_dev, vtw);
     }
     if (!(ko & 32)) {
-        LAUNCH(ctx, TAG_POLY, k_powers, cdiv(B * cdiv(c.n_cons + 1, 32), 64), 64, s, B, c.n_cons + 1, bd.misc, (int)MS_Z, bd.zpow, c.n_cons + 1, 0u);
+        if (ns)
+            LAUNCH(ctx, TAG_POLY, k_powers_mx, cdiv(B * cdiv(c.n_cons + 1, 32), 64), 64, s, B, cdiv(c.n_cons + 1, 32), rows, mx.ctab, bd.misc, (int)MS_Z,
+                   bd.zpow, c.n_cons + 1);
+        else
+            LAUNCH(ctx, TAG_POLY, k_powers, cdiv(B * cdiv(c.n_cons + 1, 32), 64), 64, s, B, c.n_cons + 1, bd.misc, (int)MS_Z, bd.zpow, c.n_cons + 1, 0u);
         LAUNCH(ctx, TAG_POLY, k_powers, cdiv(B * cdiv(2048, 32), 64), 64, s, B, 2048u, bd.misc, (int)MS_YINV, bd.yipow, 2048u, 1u);  // y^-i R
     }
     const u32 n_tgt = 3 * n1 + m;
-    if (!(ko & 8))
+    if (ko & 8) {
+    } else if (ns)
+        LAUNCH(ctx, TAG_POLY, k_flatten_mx, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, rows, mx.ctab, bd.zpow, c.n_cons + 1, bd.wl, bd.wr, bd.wo, bd.wv, m);
+    else
         LAUNCH(ctx, TAG_POLY, k_flatten, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, c.n_cons + 1, bd.wl, bd.wr,
                bd.wo, bd.wv, 2048u);
     // The variable-base part needs only the challenges and wV: it runs on a second stream beside the generator scalars and the
@@ -699,7 +741,11 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
         if ((rc = launch_varbase(vs_stream, G ? 1u : 0u))) return rc;
         BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vjoin, vs_stream));
     }
-    if (!(ko & 16))
+    if (ko & 16) {
+    } else if (ns)
+        LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars_mx, B, VS_BLK, s, rows, mx.ctab, c.n_cst, c.n_cons + 1, bd.cst, bd.zpow, bd.yipow, bd.wl, bd.wr, bd.wo,
+               vchal, bd.misc, bd.a, vs, G ? 1u : 0u);
+    else
         LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars, B, VS_BLK, s, n1, c.n_cterms, c.n_cst, c.n_cons + 1, c.c_q, c.c_cst, bd.cst, bd.zpow, bd.yipow,
                bd.wl, bd.wr, bd.wo, vchal, bd.misc, bd.a, vs, G ? 1u : 0u);
     if (G == 0) {
@@ -742,7 +788,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
 }
 
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
-    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s);
+    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, nullptr);
 }
 
 // Aggregated verification with exact per-proof statuses: groups of G proofs are checked with one weighted MSM each; the members
@@ -751,9 +797,9 @@ int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8*
 // and the fallback kernels are launched for up to B proofs and size themselves from the device counter.  *n_fallback
 // (optional) receives the number of proofs that were checked individually -- asking for it synchronises `s`.
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                             u32* n_fallback, u32* total_out_dev) {
+                             u32* n_fallback, u32* total_out_dev, const u32* ns) {
     if (n_fallback) *n_fallback = 0;
-    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s);
+    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, ns);
     int32_t rc;
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
@@ -776,9 +822,9 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev
     };
     const size_t o_fx = take((size_t)B * sizeof(ge)), o_idx = take(4 * (size_t)B);
     if ((rc = dev_reserve(ctx, L.agg_io, off))) return rc;
-    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s))) return rc;
-    const CircuitDev* cp;
-    if ((rc = circuit_get(ctx, N, &cp))) return rc;
+    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s, ns))) return rc;
+    const CircuitDev* cp;  // idx_ver is the same list for every N: any compiled circuit of the call serves
+    if ((rc = circuit_get(ctx, ns ? ns[0] : N, &cp))) return rc;
     u8* base = static_cast<u8*>(L.agg_io.p);
     u32* idx_dev = (u32*)(base + o_idx);
     StreamGuard guard(ctx, s, 1 + lane);

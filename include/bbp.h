@@ -214,6 +214,25 @@ int32_t bbp_verify_batch_aggregated(bbp_ctx* ctx, uint32_t B, uint32_t N, const 
 int32_t bbp_verify_batch_aggregated_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
                                         void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream);
 
+/* Mixed-N verification: one call verifies rows whose bid lists have different lengths (a node catching up verifies many rounds'
+ * proofs, and the public list changes between rounds).  Ns: B host entries, read during the call only, in every form.  Rows are
+ * packed back to back in request order; row i is record(Ns[i]) || score || z_img || seed || pub_list(Ns[i]), i.e.
+ * bbp_proof_record_size(Ns[i]) + 96 + 32*Ns[i] bytes (bbp_verify_batch's row for that N).  status: B entries, each exactly what
+ * bbp_verify_batch with that row's N reports (BBP_OK / BBP_ERR_VERIFY / BBP_ERR_FORMAT).  Ns is screened first: a 0 in any row
+ * returns BBP_ERR_BAD_ARG, else an N above BBP_MAX_ITEMS in any row BBP_ERR_GENS_LEN, and nothing is verified; B == 0 returns
+ * BBP_OK.  The aggregated forms keep bbp_verify_batch_aggregated's contract; groups are cut by index across any mix of N.  The
+ * _dev forms are stream-ordered like bbp_verify_batch_dev (the aggregated one synchronises `stream` when n_fallback is non-NULL):
+ * the library uploads Ns and derives the row offsets on `stream`.  One call makes the same number of launches whatever its mix of
+ * N: one front end and one generator MSM (per group when aggregated).  A pool takes the host forms (rows split by index into
+ * contiguous blocks) and refuses the _dev forms. */
+int32_t bbp_verify_batch_mixed(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status);
+int32_t bbp_verify_batch_mixed_aggregated(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, uint32_t group,
+                                          uint32_t* n_fallback);
+int32_t bbp_verify_batch_mixed_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev, void* status_dev,
+                                   void* stream);
+int32_t bbp_verify_batch_mixed_aggregated_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev,
+                                              void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream);
+
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.
  * Without it the buffers grow on demand, and a call that finds them too small frees and reallocates gigabytes under load (the
