@@ -57,6 +57,7 @@ SIGNATURES = {
     "bbp_verify_batch_mixed_aggregated_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "bbp_reserve": (_i32, [_vp, _u32, _u32]),
     "bbp_set_batching": (_i32, [_vp, _u32, _u32]),
+    "bbp_set_verify_mixing": (_i32, [_vp, _i32]),
     "bbp_batching_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u32)]),
     "bbp_debug_compile_circuit": (_i32, [_u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "bbp_check_health": (_i32, [_vp, ctypes.POINTER(_u32)]),
@@ -341,6 +342,11 @@ class Context:
         """Micro-batching window / size bound of the call combiner (concurrent prove() / verify() callers share device batches)."""
         self._check(lib.bbp_set_batching(self._h, window_us, max_batch))
 
+    def set_verify_mixing(self, on):
+        """Verify mixing (bbp_set_verify_mixing, default on): concurrent verify() / verify_async() requests share a device call
+        whatever their bid-list length and record layout; off = one call per list length and layout.  Same verdicts either way."""
+        self._check(lib.bbp_set_verify_mixing(self._h, 1 if on else 0))
+
     def batching_stats(self):
         """(combined device calls, requests they carried, largest batch) since the context was created."""
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
@@ -455,6 +461,10 @@ class Pool(Context):
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""
         super().set_entropy_source(source)
+
+    def set_verify_mixing(self, on):
+        """bbp_set_verify_mixing on the pool: the pool's combiner, which deals the combined calls to the members."""
+        super().set_verify_mixing(on)
 
     def member_stats(self, i):
         """(combined prove / verify device calls dealt to member i, requests they carried)"""

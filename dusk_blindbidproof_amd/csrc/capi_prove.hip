@@ -18,7 +18,7 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
                         const std::function<int32_t(hipStream_t)>* open_hook = nullptr);
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
 int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                            const u32* ns = nullptr);
+                            const u32* ns = nullptr, const u8* vers = nullptr);
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
                              u32* n_fallback, u32* total_out_dev = nullptr, const u32* ns = nullptr);
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out);
@@ -949,15 +949,23 @@ extern "C" int32_t bbp_prove_async(bbp_ctx* ctx, const uint8_t scalars7[7 * 32],
 
 // rec_ver 0: compact 1121-byte proofs; 1: the 2-phase 1217-byte R1CSProof layout (both parse in the reference)
 // Takes the context lock itself, for the enqueue phase only (aggregated mode synchronises inside it: the host reads group verdicts).
-// Ns (B entries, screened): a mixed-N call, rows of bbp_verify_batch_mixed packed back to back; N is then unused.
+// Ns (B entries, screened): a mixed-N call, rows of bbp_verify_batch_mixed packed back to back; N and rec_ver are then unused.
+// vers (with Ns only, B bytes): the record layout of every row (0 / 1); null = compact rows, the public mixed calls' contract.
 static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status,
-                                 uint32_t group = 0, uint32_t* n_fallback = nullptr, const uint32_t* Ns = nullptr) {
+                                 uint32_t group = 0, uint32_t* n_fallback = nullptr, const uint32_t* Ns = nullptr, const uint8_t* vers = nullptr) {
     const size_t stride = (size_t)(rec_ver ? 1217u : 1121u) + 32 * (4 + (size_t)N) + 96 + (size_t)N * 32;
     std::vector<size_t> row_off;  // mixed: byte offset of every row, and the total at [B]
     if (Ns) {
         row_off.resize((size_t)B + 1);
         row_off[0] = 0;
-        for (uint32_t i = 0; i < B; i++) row_off[i + 1] = row_off[i] + verify_row_size(Ns[i]);
+        rec_ver = 0;
+        for (uint32_t i = 0; i < B; i++) {
+            const bool two_phase = vers && vers[i];
+            if (two_phase) rec_ver = 1;  // the aggregated path takes compact records only: one two-phase row and the call runs plain
+            row_off[i + 1] = row_off[i] + verify_row_size(Ns[i]) + (two_phase ? 96u : 0u);
+        }
+        if (rec_ver) group = 0;
+        else vers = nullptr;  // every row compact: the call the public mixed entry points make
     }
     const size_t in_bytes = Ns ? row_off[B] : stride * B;
     if (group == 0 && rec_ver == 0 && ctx->verify_group > 1 && B >= 2 * ctx->verify_group) group = ctx->verify_group;  // BBP_VERIFY_AGGREGATE
@@ -987,10 +995,11 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
             const u8 *cin = (const u8*)sl.in.p + (Ns ? row_off[first] : stride * first), *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
             int32_t* cst = (int32_t*)sl.out.p + first;
             const u32* cns = Ns ? Ns + first : nullptr;
+            const u8* cvers = vers ? vers + first : nullptr;
             if (group > 1) {  // stream-ordered: no synchronisation while the context lock is held
                 if (first == 0 && L.agg_count) BBP_HIP_TRY(ctx, hipMemsetAsync(L.agg_count + 1, 0, sizeof(u32), L.stream));
                 if ((rc = verify_batch_agg_dev(ctx, nb, N, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B, cns))) return rc;
-            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream, cns)))
+            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream, cns, cvers)))
                 return rc;
         }
         BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, L.stream));
@@ -1006,6 +1015,15 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
 int32_t bbp::verify_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status,
                                  std::string* err) {
     const int32_t rc = no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, N, rec_ver, in, status); });
+    if (rc && err) *err = tls_error();
+    return rc;
+}
+
+// what the call combiner runs for concurrent bbp_verify callers of different bid-list lengths or record layouts (submit.cpp: the
+// runner handed to Combiner::set_mixed_verify).  Ns and vers come from requests that bbp_verify has screened.
+int32_t bbp::verify_batch_mixed_locked(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* vers, const uint8_t* in, int32_t* status,
+                                       std::string* err) {
+    const int32_t rc = no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, in, status, 0, nullptr, Ns, vers); });
     if (rc && err) *err = tls_error();
     return rc;
 }
@@ -1286,6 +1304,14 @@ extern "C" int32_t bbp_set_batching(bbp_ctx* ctx, uint32_t window_us, uint32_t m
     if (!ctx || !ctx->combiner) return BBP_ERR_BAD_ARG;
     return no_throw([&]() -> int32_t {
         static_cast<Combiner*>(ctx->combiner)->configure(window_us, max_batch);
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_set_verify_mixing(bbp_ctx* ctx, int32_t on) {
+    if (!ctx || !ctx->combiner) return BBP_ERR_BAD_ARG;
+    return no_throw([&]() -> int32_t {
+        static_cast<Combiner*>(ctx->combiner)->set_verify_mixing(on != 0);
         return BBP_OK;
     });
 }

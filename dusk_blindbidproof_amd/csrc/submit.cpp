@@ -74,8 +74,26 @@ void Combiner::stats(uint64_t* n_calls, uint64_t* n_requests, uint32_t* max_seen
     if (max_seen) *max_seen = max_seen_;
 }
 
-static bool same_class(const Request* a, const Request* b) {
-    return a->kind == b->kind && a->N == b->N && a->rec_ver == b->rec_ver && a->in_len == b->in_len && (a->entropy == nullptr) == (b->entropy == nullptr);
+void Combiner::set_mixed_verify(MixedVerifyFn fn) {
+    std::lock_guard<std::mutex> lk(mu_);
+    mixed_fn_ = fn;
+}
+
+void Combiner::set_verify_mixing(bool on) {
+    std::lock_guard<std::mutex> lk(mu_);
+    mixing_ = on;
+}
+
+bool Combiner::verify_mixing() {
+    std::lock_guard<std::mutex> lk(mu_);
+    return mixing_ && mixed_fn_;
+}
+
+// verify requests are one class when the engine can run them in one call (a mixed-N runner is installed, mixing is on)
+bool Combiner::same_class_locked(const Request* a, const Request* b) const {
+    if (a->kind != b->kind) return false;
+    if (a->kind == 1 && mixing_ && mixed_fn_) return true;
+    return a->N == b->N && a->rec_ver == b->rec_ver && a->in_len == b->in_len && (a->entropy == nullptr) == (b->entropy == nullptr);
 }
 
 void Combiner::set_targets(const std::vector<bbp_ctx*>& targets) {
@@ -257,7 +275,7 @@ void Combiner::thread_main(int kind) {
         size_t limit = max_batch_;
         if (targets_.size() > 1 && idle_targets > 1) {
             size_t n_class = 0;
-            for (const Request* q : q_) n_class += same_class(q, head);
+            for (const Request* q : q_) n_class += same_class_locked(q, head);
             const size_t share = (n_class + idle_targets - 1) / idle_targets;
             limit = std::min<size_t>(limit, std::max<size_t>(share, MIN_SHARE));
         }
@@ -268,12 +286,12 @@ void Combiner::thread_main(int kind) {
             // runs under the first half's MSM stage, and the two halves' callers return out of phase from then on (the engine's
             // cross-call pipeline stays full: 3072 connections prove-only through the socket 13.3 k -> see DESIGN.md 6c).
             size_t n_class = 0;
-            for (const Request* q : q_) n_class += same_class(q, head);
+            for (const Request* q : q_) n_class += same_class_locked(q, head);
             if (n_class >= 2 * (size_t)split_min_) limit = std::min<size_t>(limit, std::max<size_t>((n_class + 1) / 2, split_min_));
         }
         std::vector<Request*> batch;
         for (auto it = q_.begin(); it != q_.end() && batch.size() < limit;) {
-            if (same_class(*it, head)) {
+            if (same_class_locked(*it, head)) {
                 batch.push_back(*it);
                 it = q_.erase(it);
             } else {
@@ -297,14 +315,17 @@ void Combiner::thread_main(int kind) {
         const auto t_batch = std::chrono::steady_clock::now();
         const size_t q_left = q_.size();
         const int inflight_before = proving ? targets_[ti].prove_inflight - 1 : 0;
+        const MixedVerifyFn mixed = mixing_ ? mixed_fn_ : nullptr;
+        uint32_t n_distinct = 1;
         lk.unlock();
-        run_batch(where, batch);
+        run_batch(where, batch, mixed, &n_distinct);
         lk.lock();
         if (log_) {  // BBP_BATCH_LOG: start (ms since the combiner was made), duration, kind, target, size, prove batches already in flight, queue left behind
             const auto t_end = std::chrono::steady_clock::now();
-            fprintf(log_, "%.2f %.2f %s %zu %zu %d %zu %.1f\n", std::chrono::duration<double, std::milli>(t_batch - t0_).count(),
+            fprintf(log_, "%.2f %.2f %s %zu %zu %d %zu %.1f %u\n", std::chrono::duration<double, std::milli>(t_batch - t0_).count(),
                     std::chrono::duration<double, std::milli>(t_end - t_batch).count(), proving ? "prove" : "verify", ti, batch.size(), inflight_before, q_left,
-                    per_proof_us_);  // (last column: the pacing estimate, microseconds per proof, as it stood when this batch ended)
+                    per_proof_us_, n_distinct);  // (per_proof_us_: the pacing estimate, microseconds per proof, as it stood when this batch ended;
+                                                 // last column: distinct list lengths in the batch, above 1 for a mixed verify batch only)
         }
         if (proving) {
             const auto t_end = std::chrono::steady_clock::now();
@@ -346,13 +367,40 @@ void Combiner::thread_main(int kind) {
     }
 }
 
-void Combiner::run_batch(bbp_ctx* ctx, std::vector<Request*>& batch) {
+void Combiner::run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerifyFn mixed, uint32_t* n_distinct) {
     const Request& h = *batch[0];
     const uint32_t B = (uint32_t)batch.size();
     int32_t rc;
     std::string err;
     std::vector<int32_t> status(B, 6);
     try {
+        // a verify batch formed as the merged class: uniform (every member of the head's list length, layout and row size: the call
+        // every single-N workload has always made) unless a member differs
+        bool uniform = true;
+        if (h.kind == 1 && mixed)
+            for (uint32_t i = 1; i < B && uniform; i++) uniform = batch[i]->N == h.N && batch[i]->rec_ver == h.rec_ver && batch[i]->in_len == h.in_len;
+        if (!uniform) {
+            size_t total = 0;
+            for (uint32_t i = 0; i < B; i++) total += batch[i]->in_len;
+            std::vector<uint8_t> in(total), vers(B);
+            std::vector<uint32_t> ns(B), seen;
+            size_t off = 0;
+            for (uint32_t i = 0; i < B; i++) {  // rows back to back in queue order
+                memcpy(&in[off], batch[i]->in, batch[i]->in_len);
+                off += batch[i]->in_len;
+                ns[i] = batch[i]->N;
+                vers[i] = batch[i]->rec_ver ? 1 : 0;
+            }
+            seen = ns;
+            std::sort(seen.begin(), seen.end());
+            *n_distinct = (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+            rc = mixed(ctx, B, ns.data(), vers.data(), in.data(), status.data(), &err);
+            for (uint32_t i = 0; i < B; i++) {
+                batch[i]->status = rc ? rc : status[i];
+                if (rc) batch[i]->err = err;
+            }
+            return;
+        }
         std::vector<uint8_t> in((size_t)B * h.in_len);
         for (uint32_t i = 0; i < B; i++) memcpy(&in[(size_t)i * h.in_len], batch[i]->in, h.in_len);
         if (h.kind == 0) {

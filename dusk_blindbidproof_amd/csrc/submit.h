@@ -3,9 +3,12 @@
 // The reference runs one Proof::prove / Verify::verify per dusk-uds worker thread (src/main.rs:55, src/futures/main.rs:46-56,
 // src/futures/prove.rs:21-26, verify.rs:21-26): N connections = N independent CPU proofs side by side.  On the GPU the unit of
 // efficiency is the batch, so bbp_prove / bbp_verify (and through them the UDS server under server/) hand their request to this
-// queue: the first caller to find the engine free becomes the leader, takes every queued request of its class (same kind, list
-// length, record layout, entropy mode), runs ONE bbp_prove_batch / bbp_verify_batch under the context lock and distributes the
-// results; requests that arrive while a batch is on the device form the next batch.  Up to TWO batches are in flight at a time
+// queue: the first caller to find the engine free becomes the leader, takes every queued request of its class, runs ONE batch call
+// under the context lock and distributes the results.  A prove class is one list length and one entropy mode (bbp_prove_batch).
+// Verify requests are ONE class whatever their list length or record layout once the engine's mixed-N runner is installed
+// (set_mixed_verify) and mixing is on: a batch whose members all agree runs bbp_verify_batch as before, any other is packed row
+// by row and runs the mixed call, each request getting its own row's status.  Without a runner, or with mixing off, a verify
+// class is one list length and one record layout; requests that arrive while a batch is on the device form the next batch.  Up to TWO batches are in flight at a time
 // per device: the host-pointer batch calls hold the context lock only while they enqueue, so the second batch's host work and
 // its opening stage on the device run under the first batch's MSM stage -- the engine's cross-call pipeline, kept full by the
 // queue.
@@ -55,6 +58,13 @@ struct Request {
 int32_t prove_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status,
                            std::string* err);
 int32_t verify_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status, std::string* err);
+// ... and what a verify batch of several list lengths or record layouts runs: rows packed back to back in queue order, Ns[i] / vers[i]
+// the list length and layout (0 compact, 1 two-phase) of row i.  The combiner does not link against it: it is handed over with
+// Combiner::set_mixed_verify by the library that has it.
+int32_t verify_batch_mixed_locked(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* vers, const uint8_t* in, int32_t* status,
+                                  std::string* err);
+using MixedVerifyFn = int32_t (*)(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* vers, const uint8_t* in, int32_t* status,
+                                  std::string* err);
 
 class Combiner {
   public:
@@ -97,9 +107,19 @@ class Combiner {
     // A prove burst that finds its device idle and holds at least 2 n requests is cut in two (each half >= n): 0 = never.
     void set_split_min(uint32_t n);
     void stats(uint64_t* n_calls, uint64_t* n_requests, uint32_t* max_seen);
+    // The runner of verify batches that mix list lengths / record layouts (nullptr, the default: there is none, and verify
+    // requests are batched per list length and layout).  set_verify_mixing(false) keeps that grouping with a runner installed.
+    void set_mixed_verify(MixedVerifyFn fn);
+    void set_verify_mixing(bool on);
+    bool verify_mixing();  // on AND a runner is installed
 
   private:
-    void run_batch(bbp_ctx* ctx, std::vector<Request*>& batch);
+    // mixed: the runner as it stood when the batch was formed (a batch formed as one merged class needs it whatever happens to the
+    // switch meanwhile); *n_distinct: the number of distinct list lengths the batch held (batch log)
+    void run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerifyFn mixed, uint32_t* n_distinct);
+    bool same_class_locked(const Request* a, const Request* b) const;
+    MixedVerifyFn mixed_fn_ = nullptr;
+    bool mixing_ = true;
     struct Target {
         bbp_ctx* ctx = nullptr;
         int running[2] = {0, 0};  // combined calls reserved / running on this target, per kind (0 = prove, 1 = verify)

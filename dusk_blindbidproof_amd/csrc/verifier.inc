@@ -603,10 +603,11 @@ static int vlane_of(const bbp_ctx* ctx, hipStream_t s) {  // a lane's own stream
     return 0;
 }
 
-// ns (host, B entries): a mixed-N call (verifier_mixed.inc): row i is bbp_verify_batch's row for N = ns[i], rows packed back to back
-// (compact records only); N is then unused.  Strides are those of the largest N; the launches are the same in number.
+// ns (host, B entries): a mixed-N call (verifier_mixed.inc): row i is bbp_verify_batch's row for N = ns[i], rows packed back to back;
+// N and rec_ver are then unused.  vers (host, B bytes, with ns only): the record layout of every row, 0 compact / 1 two-phase; null =
+// compact records only.  Strides are those of the largest N; the launches are the same in number.
 int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                            const u32* ns) {
+                            const u32* ns, const u8* vers) {
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
     const CircuitDev* cp;
@@ -615,7 +616,9 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     if (ns) {
         if ((rc = mixed_prepare(ctx, B, ns, mx))) return rc;
         cp = &mx.cmax;
-        rec_ver = 0;
+        rec_ver = 0;  // ... unless a row says otherwise: only the launch geometry below reads it (the largest count of active points)
+        if (vers)
+            for (u32 i = 0; i < B && !rec_ver; i++) rec_ver = vers[i] ? 1u : 0u;
     } else if ((rc = circuit_get(ctx, N, &cp)))
         return rc;
     const CircuitDev& c = *cp;
@@ -636,7 +639,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     size_t o_vpts = take((size_t)B * np * 32), o_vchal = take((size_t)B * VC_COUNT * 32), o_vs = take((size_t)B * 4098 * 32),
            o_tab = take((size_t)B * np * 8 * sizeof(ge)), o_var = take((size_t)B * np * sizeof(ge)), o_fixed = take((size_t)B * sizeof(ge)),
            o_sp = take((size_t)B * np * 32);
-    const size_t o_rows = ns ? take((size_t)B * sizeof(VRow)) : 0, o_ns = ns ? take((size_t)B * 4) : 0;
+    const size_t o_rows = ns ? take((size_t)B * sizeof(VRow)) : 0, o_ns = ns ? take((size_t)B * 5) : 0;  // Ns, then the version bytes
     if ((rc = dev_reserve(ctx, L.misc, off))) return rc;
     u8* base = static_cast<u8*>(L.misc.p);
     u32* vpts = (u32*)(base + o_vpts);
@@ -648,8 +651,9 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     u32* sp = (u32*)(base + o_sp);
     const VRow* rows = (const VRow*)(base + o_rows);
     if (ns) {
-        if ((rc = stage_ns(ctx, L, ns, B, (u32*)(base + o_ns), s))) return rc;
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, 1, VROWS_BLK, s, B, (const u32*)(base + o_ns), (VRow*)(base + o_rows));
+        if ((rc = stage_ns(ctx, L, ns, vers, B, (u32*)(base + o_ns), s))) return rc;
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, 1, VROWS_BLK, s, B, (const u32*)(base + o_ns), vers ? (const u8*)(base + o_ns + 4 * (size_t)B) : nullptr,
+               (VRow*)(base + o_rows));
     }
     const merlin_transcript prefix = prover_prefix();
     // lanes per proof in k_varbase: as few as still give the launch ctx->varbase_lanes lanes (fewer lanes = more points per lane
@@ -788,7 +792,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
 }
 
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
-    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, nullptr);
+    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, nullptr, nullptr);
 }
 
 // Aggregated verification with exact per-proof statuses: groups of G proofs are checked with one weighted MSM each; the members
@@ -799,7 +803,7 @@ int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8*
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
                              u32* n_fallback, u32* total_out_dev, const u32* ns) {
     if (n_fallback) *n_fallback = 0;
-    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, ns);
+    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, ns, nullptr);
     int32_t rc;
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
@@ -822,7 +826,7 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev
     };
     const size_t o_fx = take((size_t)B * sizeof(ge)), o_idx = take(4 * (size_t)B);
     if ((rc = dev_reserve(ctx, L.agg_io, off))) return rc;
-    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s, ns))) return rc;
+    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s, ns, nullptr))) return rc;  // aggregation: compact records only
     const CircuitDev* cp;  // idx_ver is the same list for every N: any compiled circuit of the call serves
     if ((rc = circuit_get(ctx, ns ? ns[0] : N, &cp))) return rc;
     u8* base = static_cast<u8*>(L.agg_io.p);

@@ -10,24 +10,27 @@
 
 namespace bbp {
 
-struct VRow {  // one row of a mixed call: byte offset of its input row, N, m = 4 + N
+struct VRow {  // one row of a mixed call: byte offset of its input row, N, m = 4 + N, record layout (0 compact, 1 two-phase)
     u64 off;
-    u32 n, m;
+    u32 n;
+    uint16_t m, ver;
 };
 struct VCirc {  // what the front end needs of circuit N (ctx->vctab[N], filled when circuit N is first used by a mixed call)
     u32 n_mul, n_cons, n_cst, n_cterms;
     const u32 *f_off, *f_ent, *c_q, *c_cst;
 };
-__host__ __device__ __forceinline__ u64 vrow_bytes(u32 n) { return 1121u + 32u * (4u + n) + 96u + 32u * n; }  // record || score || z_img || seed || list
+// record || score || z_img || seed || list
+__host__ __device__ __forceinline__ u64 vrow_bytes(u32 n, u32 ver) { return (ver ? 1217u : 1121u) + 32u * (4u + n) + 96u + 32u * n; }
 
-// row offsets: one workgroup, a contiguous run of rows per lane, a scan over the lanes' sums
+// row offsets: one workgroup, a contiguous run of rows per lane, a scan over the lanes' sums.  vers (one byte per row) may be
+// null: every row is then a compact record
 constexpr u32 VROWS_BLK = 1024;
-__global__ __launch_bounds__(VROWS_BLK) void k_vrows(u32 B, const u32* __restrict__ ns, VRow* __restrict__ rows) {
+__global__ __launch_bounds__(VROWS_BLK) void k_vrows(u32 B, const u32* __restrict__ ns, const u8* __restrict__ vers, VRow* __restrict__ rows) {
     __shared__ u64 part[VROWS_BLK];
     const u32 tid = threadIdx.x, per = (B + VROWS_BLK - 1) / VROWS_BLK;
     const u32 lo = min(B, tid * per), hi = min(B, lo + per);
     u64 sum = 0;
-    for (u32 i = lo; i < hi; i++) sum += vrow_bytes(ns[i]);
+    for (u32 i = lo; i < hi; i++) sum += vrow_bytes(ns[i], vers ? vers[i] : 0u);
     part[tid] = sum;
     __syncthreads();
     for (u32 d = 1; d < VROWS_BLK; d <<= 1) {
@@ -38,9 +41,9 @@ __global__ __launch_bounds__(VROWS_BLK) void k_vrows(u32 B, const u32* __restric
     }
     u64 off = part[tid] - sum;
     for (u32 i = lo; i < hi; i++) {
-        const u32 n = ns[i];
-        rows[i] = VRow{off, n, 4 + n};
-        off += vrow_bytes(n);
+        const u32 n = ns[i], ver = vers ? (vers[i] ? 1u : 0u) : 0u;
+        rows[i] = VRow{off, n, (uint16_t)(4 + n), (uint16_t)ver};
+        off += vrow_bytes(n, ver);
     }
 }
 
@@ -475,7 +478,7 @@ __global__ BBP_LANE_KERNEL void k_vparse_mx(u32 B, const VRow* __restrict__ rows
     const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= B) return;
     const VRow r = rows[p];
-    vparse_row(p, r.n, 0u, in + r.off, vpts + (size_t)p * vstride, vchal, cst_all + (size_t)p * cst_stride, status);
+    vparse_row(p, r.n, r.ver, in + r.off, vpts + (size_t)p * vstride, vchal, cst_all + (size_t)p * cst_stride, status);
 }
 
 // (held at one wave per SIMD like k_vtranscript, whose 256 + 12 registers it matches: left to itself the compiler aims at two waves
@@ -526,7 +529,9 @@ __global__ __launch_bounds__(VS_BLK) void k_vscalars_mx(const VRow* __restrict__
                    misc, s_all, vs_all, agg);
 }
 
-// compact (one-phase) records only: a mixed call takes bbp_verify_batch's rows
+// The record layout is the row's own: a compact row has no A_I2 / A_O2 / S2 and skips those three point slots, a two-phase row
+// weighs them, so the number of active points differs per row (npa_max: the call's largest).  The transcript replay needs no
+// version: it absorbs the three slots as they stand in vpts, and k_vparse_mx has zeroed them (the identity) for a compact row.
 __global__ __launch_bounds__(64) void k_varprep_mx(u32 B, u32 npa_max, u32 np_stride, const VRow* __restrict__ rows, const u32* __restrict__ vpts,
                                                     const sc* __restrict__ vchal, const sc* __restrict__ misc, const sc* __restrict__ wv, u32 wv_stride,
                                                     ge* __restrict__ tab_all, u32* __restrict__ sp_all, int32_t* __restrict__ status, u32 agg) {
@@ -534,9 +539,10 @@ __global__ __launch_bounds__(64) void k_varprep_mx(u32 B, u32 npa_max, u32 np_st
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x;  // one lane per (row, point slot)
     if (t >= B * npa_max) return;
     const u32 p = t / npa_max, a = t % npa_max;
-    const u32 m = rows[p].m;
-    if (a >= vnpts(m) - 3) return;
-    varprep_point(p, a, m, (size_t)p * np_stride, vpts, vchal, misc, wv + (size_t)p * wv_stride, tab_all, sp_all, status, agg, 1u);
+    const VRow r = rows[p];
+    const u32 m = r.m, one_phase = r.ver ? 0u : 1u;
+    if (a >= vnpts(m) - 3 * one_phase) return;
+    varprep_point(p, a, m, (size_t)p * np_stride, vpts, vchal, misc, wv + (size_t)p * wv_stride, tab_all, sp_all, status, agg, one_phase);
 }
 
 __global__ __launch_bounds__(64) void k_varsum_mx(u32 B, u32 np_stride, const VRow* __restrict__ rows, const ge* __restrict__ tab_all,
@@ -546,7 +552,7 @@ __global__ __launch_bounds__(64) void k_varsum_mx(u32 B, u32 np_stride, const VR
     const u32 p = blockIdx.x * 2 + (threadIdx.x >> 5);
     const bool live = p < B;
     ge acc = ge_identity();
-    if (live) acc = varsum_lane(lane, rows[p].m, (size_t)p * np_stride, tab_all, sp_all, 1u);
+    if (live) acc = varsum_lane(lane, rows[p].m, (size_t)p * np_stride, tab_all, sp_all, rows[p].ver ? 0u : 1u);
     acc = varsum_reduce(acc, lane);
     if (live && lane == 0) out[p] = acc;
 }
@@ -560,7 +566,7 @@ __global__ __launch_bounds__(64) void k_varbase_mx(u32 B, u32 Q, u32 np_stride, 
     if (t >= B * Q) return;
     const u32 p = t / Q, q = t % Q;
     out[(size_t)p * Q + q] = varbase_lane(p, q, Q, rows[p].m, (size_t)p * np_stride, vpts, vchal, misc, wv + (size_t)p * wv_stride, tab_all, sp_all,
-                                          status, agg, 1u);
+                                          status, agg, rows[p].ver ? 0u : 1u);
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
@@ -607,11 +613,12 @@ static int32_t mixed_prepare(bbp_ctx* ctx, u32 B, const u32* ns, MixedCall& mx) 
     return BBP_OK;
 }
 
-// Ns -> dst on s through the lane's pinned staging.  No synchronisation unless NS_RING mixed calls are still queued on the lane
-// ahead of this one: then the oldest upload is waited for before its staging is reused.
+// Ns (and, when given, the B version bytes right behind them) -> dst on s through the lane's pinned staging.  No synchronisation
+// unless NS_RING mixed calls are still queued on the lane ahead of this one: then the oldest upload is waited for before its
+// staging is reused.
 constexpr size_t NS_RING = 16;
-static int32_t stage_ns(bbp_ctx* ctx, bbp_ctx::VLane& L, const u32* ns, u32 B, u32* dst, hipStream_t s) {
-    const size_t bytes = 4 * (size_t)B;
+static int32_t stage_ns(bbp_ctx* ctx, bbp_ctx::VLane& L, const u32* ns, const u8* vers, u32 B, u32* dst, hipStream_t s) {
+    const size_t bytes = (vers ? 5 : 4) * (size_t)B;
     bbp_ctx::VLane::NsStage* st = nullptr;
     for (auto& e : L.ns_ring)
         if (hipEventQuery(e.ev) == hipSuccess) {  // its copy has run (or it was never used)
@@ -635,7 +642,8 @@ static int32_t stage_ns(bbp_ctx* ctx, bbp_ctx::VLane& L, const u32* ns, u32 B, u
         BBP_HIP_TRY(ctx, hipHostMalloc(&st->h, want, hipHostMallocDefault));
         st->cap = want;
     }
-    memcpy(st->h, ns, bytes);
+    memcpy(st->h, ns, 4 * (size_t)B);
+    if (vers) memcpy((u8*)st->h + 4 * (size_t)B, vers, B);
     BBP_HIP_TRY(ctx, hipMemcpyAsync(dst, st->h, bytes, hipMemcpyHostToDevice, s));
     BBP_HIP_TRY(ctx, hipEventRecord(st->ev, s));
     return BBP_OK;

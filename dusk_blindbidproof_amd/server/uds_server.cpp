@@ -531,7 +531,7 @@ static void usage(const char* argv0) {
     fprintf(stderr,
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
-            "          [--check-proofs] [--entropy os|device]\n",
+            "          [--check-proofs] [--entropy os|device] [--verify-mixing on|off]\n",
             argv0);
 }
 
@@ -544,6 +544,7 @@ int main(int argc, char** argv) {
     int io_threads = 2;
     bool check_proofs = false;  // --check-proofs: every proof is verified on the device before it is answered (bbp_set_prove_check)
     bool device_entropy = false;  // --entropy device: one OS key per engine call, expanded on the device (bbp_set_entropy_source)
+    int verify_mixing = -1;  // --verify-mixing on|off: opcode-2 requests share device calls across bid-list lengths (bbp_set_verify_mixing); -1 = not given, the engine's default (on)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -584,6 +585,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
             device_entropy = v == "device";
+        }
+        else if (a == "--verify-mixing") {
+            const std::string v = val();
+            if (v != "on" && v != "off") {
+                usage(argv[0]);
+                return 2;
+            }
+            verify_mixing = v == "on";
         }
         else if (a == "--reserve") {
             for (const char* p = val(); *p;) {
@@ -651,6 +660,18 @@ int main(int argc, char** argv) {
                 return 2;
             }
             logf(2, "entropy source: device (one OS key per engine call, expanded with ChaCha20 on the device)");
+        }
+        if (verify_mixing >= 0) {  // resolved only when asked for: an engine without the call batches per bid-list length, which is what "off" means
+            auto set_mixing = (decltype(&bbp_set_verify_mixing))dlsym(g_eng.so, "bbp_set_verify_mixing");
+            if (set_mixing ? set_mixing(g_eng.ctx, verify_mixing) != BBP_OK : verify_mixing == 0) {
+                logf(0, "--verify-mixing %s: the engine %s %s (bbp_set_verify_mixing)", verify_mixing ? "on" : "off", engine_path.c_str(),
+                     set_mixing ? "refused the setting" : "does not provide the switch");
+                g_eng.free_(g_eng.ctx);
+                return 2;
+            }
+            if (!set_mixing) logf(1, "--verify-mixing on: the engine %s has no such switch; its own grouping of verify requests applies", engine_path.c_str());
+            else logf(2, "verify mixing %s: opcode-2 requests %s", verify_mixing ? "on" : "off",
+                      verify_mixing ? "share device calls whatever their bid-list length" : "are batched per bid-list length and record layout");
         }
         if (g_eng.describe) {  // what the engine runs on; its WARNING lines (hardware queues, memory) at warn level
             static char report[8192];

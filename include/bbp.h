@@ -157,13 +157,17 @@ int32_t bbp_prove(bbp_ctx* ctx, const uint8_t scalars7[7 * 32], const uint8_t* p
 uint32_t bbp_proof_record_size(uint32_t N); /* 1121 + 32*(4+N) */
 uint32_t bbp_entropy_size(uint32_t N);      /* 32*(4+N) + 32 */
 
-/* Replaces Verify::new(..).verify() (src/blindbid/verify.rs:27-89). record layout as produced by bbp_prove. */
+/* Replaces Verify::new(..).verify() (src/blindbid/verify.rs:27-89). record layout as produced by bbp_prove.
+ * Concurrent callers (blocking or asynchronous, on a context or a pool) share device calls whatever their N and whichever of the
+ * two R1CSProof layouts (compact, two-phase) their records have: callers that agree on both run bbp_verify_batch, any other
+ * group runs one mixed-N call, and every caller receives the status of its own proof (bbp_set_verify_mixing, below). */
 int32_t bbp_verify(bbp_ctx* ctx, const uint8_t* record, uint32_t record_len, const uint8_t score[32],
                    const uint8_t z_img[32], const uint8_t seed[32], const uint8_t* pub_list, uint32_t N);
 
 /* Asynchronous forms of the two calls above, for hosts that cannot park a thread per request (an epoll server; a Rust Future --
  * the reference's ProveFuture / VerifyFuture, src/futures/prove.rs:21-26, verify.rs:21-26, can store its Waker in `user` and be
- * woken by `done`).  Same arguments, same screening, same combining into device batches.  Return value: BBP_OK = queued, and
+ * woken by `done`).  Same arguments, same screening, same combining into device batches (verify requests across bid-list lengths,
+ * see bbp_verify).  Return value: BBP_OK = queued, and
  * `done(user, status)` will be called exactly once, on an engine thread, with the status bbp_prove / bbp_verify would have
  * returned; anything else = decided at once (bad arguments, a record that fails the structural parse), `done` is NOT called.
  * The inputs are copied before the call returns; proof_out must stay valid until `done` runs (it is written before).  Inside
@@ -244,6 +248,13 @@ int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N);
  * window the leader of a batch waits that long for more concurrent bbp_prove / bbp_verify callers before it goes to the device --
  * what the UDS server (server/) uses to turn concurrent connections into GPU batches.  max_batch bounds one combined call. */
 int32_t bbp_set_batching(bbp_ctx* ctx, uint32_t window_us, uint32_t max_batch);
+/* Verify mixing (default on): concurrent bbp_verify / bbp_verify_async requests form ONE batch whatever their bid-list length and
+ * record layout; a batch that holds several runs the mixed-N verifier (bbp_verify_batch_mixed's kernels, with the layout read
+ * per row), one that holds a single N and layout runs bbp_verify_batch as before.  Off: one batch per bid-list length and record
+ * layout, as before mixing existed -- there to measure the old grouping in the same build, and the switch to reach for should
+ * mixing misbehave.  The verdicts are the same either way.  A mixed call sizes its per-row scratch by its largest N (see
+ * bbp_reserve: reserve for the largest N expected).  On a pool: the pool's combiner.  bbp_describe reports the setting. */
+int32_t bbp_set_verify_mixing(bbp_ctx* ctx, int32_t on);
 /* Combiner statistics since bbp_init: combined device calls issued / requests they carried / largest batch (any may be NULL). */
 int32_t bbp_batching_stats(bbp_ctx* ctx, uint64_t* n_calls, uint64_t* n_requests, uint32_t* max_seen);
 

@@ -1,9 +1,15 @@
 #!/usr/bin/env python3
 """Summary of a combiner batch log (BBP_BATCH_LOG=path; one line per batch: start ms, duration ms, kind, target, size, prove batches
-already in flight at its start, requests left queued): python tools/batch_log.py LOG [LOG ...]"""
+already in flight at its start, requests left queued, pacing estimate, distinct list lengths in the batch -- the last column is
+absent in logs of older builds): python tools/batch_log.py LOG [LOG ...]"""
 import sys
 for path in sys.argv[1:]:
     rows = [l.split() for l in open(path) if l.strip()]
+    vf = [(int(r[4]), int(r[8]) if len(r) > 8 else 1) for r in rows if r[2] == "verify"]
+    if vf:
+        mixed = [v for v in vf if v[1] > 1]
+        print("%s: %d verify batches, %d requests; %d mixed batches (several list lengths), %d requests in them, up to %d distinct N in one" %
+              (path, len(vf), sum(v[0] for v in vf), len(mixed), sum(v[0] for v in mixed), max([v[1] for v in vf])))
     pr = [(float(r[0]), float(r[1]), int(r[4]), int(r[5]), int(r[6])) for r in rows if r[2] == "prove"]
     if not pr:
         print(path, "no prove batches")
