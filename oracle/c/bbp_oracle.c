@@ -1075,6 +1075,9 @@ int oc_verify(const u8 *record, u32 record_len, const u8 *score32, const u8 *z_i
     p += 64 * lg_n;
     if (!sc_canonical(p) || !sc_canonical(p + 32)) return ST_FORMAT;
     sc a = sc_frombytes_raw(p), b = sc_frombytes_raw(p + 32);
+    /* score, z_img, seed reach Verify::new as serde-deserialised Scalars (verify.rs:100-102): canonical encodings only, anything
+     * else is an error before Verify::verify runs; the bid list goes through Scalar::from_bits instead (verify.rs:115) */
+    if (!sc_canonical(score32) || !sc_canonical(z_img32) || !sc_canonical(seed32)) return ST_FORMAT;
 
     cs_t cs;
     memset(&cs, 0, sizeof cs);

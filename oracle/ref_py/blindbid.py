@@ -1,6 +1,6 @@
 """ORACLE (test infrastructure, never shipped): restatement of the in-tree reference files
   src/gadgets.rs (entire), src/blindbid/mod.rs:7-40, src/blindbid/proof.rs:36-91,
-  src/blindbid/verify.rs:47-89, src/blindbid/bid.rs:20-29
+  src/blindbid/verify.rs:47-89 and 100-116 (the parse of the public inputs), src/blindbid/bid.rs:20-29
 on top of the oracle's r1cs / ristretto / merlin restatements.
 `rounds` / `cap` are parameters only so tests can run reduced circuits; the reference fixes
 MIMC_ROUNDS = 90 (src/gadgets.rs:4) and BulletproofGens::new(2048, 1) (src/blindbid/mod.rs:36).
@@ -138,6 +138,22 @@ class Proof:
         c = [buf[pl + 32 * i:pl + 32 * i + 32] for i in range(4)]
         t = [buf[pl + 128 + 32 * i:pl + 128 + 32 * i + 32] for i in range(n_items)]
         return Proof(pr, c, t)
+
+
+def parse_public_inputs(score32, z_img32, seed32, pub_list_bytes):
+    """src/blindbid/verify.rs:100-116 (Verify::try_from_reader_variables): score, z_img and seed are serde-deserialised
+    Scalars -- canonical encodings only, anything else is an error before Verify::verify runs (FormatError here) --, the bid list
+    goes through Scalar::from_bits (bit 255 cleared, never refused).  Returns (score, z_img, seed, [items]) as ints."""
+    three = []
+    for b in (score32, z_img32, seed32):
+        v = rs.sc_canonical(bytes(b)) if len(b) == 32 else None
+        if v is None:
+            raise FormatError("public scalar")
+        three.append(v)
+    if len(pub_list_bytes) % 32:
+        raise FormatError("bid list")
+    items = [int.from_bytes(pub_list_bytes[i:i + 32], "little") & (2 ** 255 - 1) for i in range(0, len(pub_list_bytes), 32)]
+    return three[0], three[1], three[2], items
 
 
 def prove(d, k, y, y_inv, q, z_img, seed, pub_list, toggle, entropy, rounds=MIMC_ROUNDS, cap=GENS_CAPACITY,

@@ -76,10 +76,14 @@ class OracleC:
         self.lib.oc_prove_many(self._b(inputs), self._b(entropy), B, N, rounds, cap, threads, out, stride, st)
         return bytes(out), list(st)
 
-    def verify_many(self, inputs, B, N, threads, rounds=90, cap=2048):
-        rec_len = 1121 + 32 * (4 + N)
+    def verify_many(self, inputs, B, N, threads, rounds=90, cap=2048, rec_len=None):
+        """rec_len: bytes of every record; default the compact layout's (the two-phase layout is 96 bytes longer)."""
+        if rec_len is None:
+            rec_len = 1121 + 32 * (4 + N)
+        assert len(inputs) == B * (rec_len + 96 + 32 * N)
         st = (ctypes.c_int * B)()
-        self.lib.oc_verify_many(self._b(inputs), B, N, rec_len, rounds, cap, threads, st)
+        rc = self.lib.oc_verify_many(self._b(inputs), B, N, rec_len, rounds, cap, threads, st)
+        assert rc == 0
         return list(st)
 
     def generator(self, i):

@@ -3,8 +3,8 @@ lengths, and every row's status is what bbp_verify_batch reports for it with its
 
 Anchors: the C oracle's verdicts (oracle/c, proving and verifying on the CPU under fixed entropy) and the per-N uniform calls
 on the same rows.  Tampered rows cover the transcript (t_x + 1), every public input (score, seed, one pub_list entry), the
-serde screening of the public scalars (score + l, a FormatError in the reference; the C oracle reduces it, so there the
-expected verdict is the uniform call's) and the structural parse (version byte)."""
+serde screening of the public scalars (score + l, a FormatError in the reference and in both oracles) and the structural parse
+(version byte)."""
 import hashlib
 import random
 
@@ -97,7 +97,7 @@ def anchor(oc, bbp):
         bad = [_tamper(good[k % 2], n, kind) for k, kind in enumerate(KINDS)]
         group = good + bad
         verdicts = oc.verify_many(b"".join(group), len(group), n, threads=8)
-        verdicts[2 + KINDS.index("noncanon")] = FORMAT  # serde screening: the oracle reduces the scalar (see the module doc)
+        assert verdicts[2 + KINDS.index("noncanon")] == FORMAT  # serde screening (see the module doc)
         rows += group
         ns += [n] * len(group)
         oracle += verdicts
@@ -150,8 +150,6 @@ def test_scale_random_n(ctx, scale, oc, bbp):
     rnd = random.Random(9)
     sample = sorted(set(rnd.sample(range(len(Ns)), 28)) | set(list(kinds)[:4]))
     for i in sample:
-        if kinds.get(i) == "noncanon":
-            continue  # the oracle reduces the scalar (module doc)
         assert oc.verify_many(blob[off[i]:off[i + 1]], 1, Ns[i], threads=8) == [st[i]], i
 
 
