@@ -55,6 +55,11 @@ SIGNATURES = {
     "bbp_verify_batch_mixed_aggregated": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "bbp_verify_batch_mixed_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_batch_mixed_aggregated_dev": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "bbp_round_row_size": (_u32, [_u32]),
+    "bbp_verify_rounds": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
+    "bbp_verify_rounds_aggregated": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
+    "bbp_verify_rounds_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_rounds_aggregated_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
     "bbp_reserve": (_i32, [_vp, _u32, _u32]),
     "bbp_set_batching": (_i32, [_vp, _u32, _u32]),
     "bbp_set_verify_mixing": (_i32, [_vp, _i32]),
@@ -131,6 +136,59 @@ def pack_mixed_rows(rows):
         Ns.append(n)
         parts += [record, score, z_img, seed, pub_list]
     return Ns, b"".join(bytes(p) for p in parts)
+
+
+def round_row_size(n):
+    """Bytes of one row of verify_rounds* for list length n: record || score || z_img."""
+    return record_size(n) + 64
+
+
+def pack_rounds(rounds):
+    """[(seed, pub_list)] -> (round_Ns, table bytes) for verify_rounds*: round r is seed || pub_list, packed back to back."""
+    Ns, parts = [], []
+    for seed, pub_list in rounds:
+        n = len(pub_list) // 32
+        if len(seed) != 32 or len(pub_list) != 32 * n:
+            raise ValueError("a round is a 32-byte seed and a bid list of 32-byte items")
+        Ns.append(n)
+        parts += [seed, pub_list]
+    return Ns, b"".join(bytes(p) for p in parts)
+
+
+def round_table_offsets(round_Ns):
+    """Byte offset of every round in a packed round table, and the total size last (len(round_Ns) + 1 entries)."""
+    off = [0]
+    for n in round_Ns:
+        off.append(off[-1] + 32 * (1 + n))
+    return off
+
+
+def expand_round_rows(round_Ns, table, round_of, rows):
+    """The (Ns, input bytes) that verify_batch_mixed* needs for the same proofs: every row of `rows` (record || score || z_img, packed)
+    followed by its round's seed || pub_list.  round_of=None: every row is of round 0."""
+    toff = round_table_offsets(round_Ns)
+    if len(table) != toff[-1]:
+        raise ValueError("round table does not have the size its list lengths give")
+    if round_of is None:
+        if len(round_Ns) != 1:
+            raise ValueError("round_of may be None with one round only")
+        n_rows, rem = divmod(len(rows), round_row_size(round_Ns[0]))
+        if rem:
+            raise ValueError("rows are not a whole number of rows of list length %d" % round_Ns[0])
+        round_of = [0] * n_rows
+    Ns, parts, at = [], [], 0
+    for r in round_of:
+        size = round_row_size(round_Ns[r])
+        parts += [rows[at:at + size], table[toff[r]:toff[r + 1]]]
+        Ns.append(round_Ns[r])
+        at += size
+    if at != len(rows):
+        raise ValueError("rows do not have the size their rounds give")
+    return Ns, b"".join(bytes(p) for p in parts)
+
+
+def _u32s(values):
+    return None if values is None else (_u32 * len(values))(*values)
 
 
 def _buf(b):
@@ -324,6 +382,52 @@ class Context:
                                                               ctypes.byref(nfb) if want_count else None, _stream(stream)))
         return nfb.value if want_count else None
 
+    def verify_rounds(self, round_Ns, table, round_of, rows, B=None):
+        """Rows of record || score || z_img against a table of rounds (pack_rounds); round_of[i] names row i's round, None = one round
+        (B, the number of rows, is then taken from the size of `rows` unless given).  One status per row, as verify_batch_mixed on
+        expand_round_rows(...)."""
+        B = self._rounds_B(round_Ns, round_of, rows, B)
+        status = (ctypes.c_int32 * B)()
+        self._check(lib.bbp_verify_rounds(self._h, len(round_Ns), _u32s(round_Ns), _buf(table), B, _u32s(round_of), _buf(rows), status))
+        return list(status)
+
+    def verify_rounds_aggregated(self, round_Ns, table, round_of, rows, group=0, B=None):
+        """verify_batch_aggregated over rows of rounds, groups cut by index across rounds: (statuses, proofs checked individually)."""
+        B = self._rounds_B(round_Ns, round_of, rows, B)
+        status = (ctypes.c_int32 * B)()
+        nfb = ctypes.c_uint32()
+        self._check(lib.bbp_verify_rounds_aggregated(self._h, len(round_Ns), _u32s(round_Ns), _buf(table), B, _u32s(round_of), _buf(rows), status,
+                                                     group, ctypes.byref(nfb)))
+        return list(status), nfb.value
+
+    def verify_round(self, N, seed, pub_list, rows):
+        """One round: every row of `rows` (record || score || z_img, packed) against the same seed and bid list."""
+        if len(seed) != 32 or len(pub_list) != 32 * N:
+            raise ValueError("a round is a 32-byte seed and a bid list of N 32-byte items")
+        return self.verify_rounds([N], bytes(seed) + bytes(pub_list), None, rows)
+
+    def verify_rounds_dev(self, round_Ns, table_ptr, round_of, B, rows_ptr, ent_ptr, status_ptr, stream=None):
+        """Stream-ordered; round_Ns and round_of (None = one round) are read during the call only."""
+        self._check(lib.bbp_verify_rounds_dev(self._h, len(round_Ns), _u32s(round_Ns), table_ptr, B, _u32s(round_of), rows_ptr, ent_ptr, status_ptr,
+                                              _stream(stream)))
+
+    def verify_rounds_aggregated_dev(self, round_Ns, table_ptr, round_of, B, rows_ptr, ent_ptr, status_ptr, group=0, stream=None, want_count=True):
+        """As verify_batch_aggregated_dev: want_count=False leaves the call asynchronous and returns None."""
+        nfb = ctypes.c_uint32()
+        self._check(lib.bbp_verify_rounds_aggregated_dev(self._h, len(round_Ns), _u32s(round_Ns), table_ptr, B, _u32s(round_of), rows_ptr, ent_ptr,
+                                                         status_ptr, group, ctypes.byref(nfb) if want_count else None, _stream(stream)))
+        return nfb.value if want_count else None
+
+    @staticmethod
+    def _rounds_B(round_Ns, round_of, rows, B):
+        if B is not None:
+            return B
+        if round_of is not None:
+            return len(round_of)
+        if len(round_Ns) != 1 or len(rows) % round_row_size(round_Ns[0]):
+            raise ValueError("without round_of the rows must be a whole number of rows of the one round")
+        return len(rows) // round_row_size(round_Ns[0])
+
     def prove_batch_dev(self, B, N, in_ptr, ent_ptr, out_ptr, stream=None):
         self._check(lib.bbp_prove_batch_dev(self._h, B, N, in_ptr, ent_ptr, out_ptr, _stream(stream)))
 
@@ -436,7 +540,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / msm_batch (block-split over the members, results in request order); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / msm_batch (block-split over the members, results in request order); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):

@@ -18,9 +18,9 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
                         const std::function<int32_t(hipStream_t)>* open_hook = nullptr);
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
 int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                            const u32* ns = nullptr, const u8* vers = nullptr);
+                            const u32* ns = nullptr, const u8* vers = nullptr, const VRounds* rd = nullptr);
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                             u32* n_fallback, u32* total_out_dev = nullptr, const u32* ns = nullptr);
+                             u32* n_fallback, u32* total_out_dev = nullptr, const u32* ns = nullptr, const VRounds* rd = nullptr);
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out);
 
 // native (non-circuit) image of the gadget wiring: what the reference's Go caller computes before Proof::prove
@@ -362,11 +362,16 @@ static int32_t pinned_reserve(bbp_ctx* ctx, void*& p, size_t& cap, size_t bytes)
 // The main stream may still be busy with the previous call's MSM stage, and the opening stage of THIS call is meant to run under
 // it; it only needs complete inputs (include/bbp.h), hence the wait -- on the copy's own event, polled.
 // `b` lands at byte ent_off of the slot's entropy buffer, which holds at least ent_off + nb bytes afterwards (a device draw fills
-// what lies below ent_off).
-static int32_t upload_inputs(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, size_t ent_off = 0) {
+// what lies below ent_off).  a2 (na2 bytes, optional): a second input that travels in the same copy and lands at byte a2_off >= na of the
+// slot's input buffer (the round table of bbp_verify_rounds behind its rows).
+static int32_t upload_inputs(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, const uint8_t* a, size_t na, const uint8_t* b, size_t nb, size_t ent_off = 0,
+                             const uint8_t* a2 = nullptr, size_t na2 = 0, size_t a2_off = 0) {
     int32_t rc;
+    const size_t na1 = na;
+    if (a2) na = a2_off + na2;
     if ((rc = dev_reserve(ctx, sl.in, na)) || (rc = dev_reserve(ctx, sl.ent, ent_off + nb)) || (rc = pinned_reserve(ctx, sl.h_in, sl.h_in_cap, na + nb))) return rc;
-    memcpy(sl.h_in, a, na);
+    memcpy(sl.h_in, a, na1);
+    if (a2) memcpy((uint8_t*)sl.h_in + a2_off, a2, na2);
     if (nb) memcpy((uint8_t*)sl.h_in + na, b, nb);
     BBP_HIP_TRY(ctx, hipMemcpyAsync(sl.in.p, sl.h_in, na, hipMemcpyHostToDevice, ctx->copy));
     if (nb) BBP_HIP_TRY(ctx, hipMemcpyAsync((uint8_t*)sl.ent.p + ent_off, (uint8_t*)sl.h_in + na, nb, hipMemcpyHostToDevice, ctx->copy));
@@ -951,11 +956,20 @@ extern "C" int32_t bbp_prove_async(bbp_ctx* ctx, const uint8_t scalars7[7 * 32],
 // Takes the context lock itself, for the enqueue phase only (aggregated mode synchronises inside it: the host reads group verdicts).
 // Ns (B entries, screened): a mixed-N call, rows of bbp_verify_batch_mixed packed back to back; N and rec_ver are then unused.
 // vers (with Ns only, B bytes): the record layout of every row (0 / 1); null = compact rows, the public mixed calls' contract.
+// rd (bbp_verify_rounds*, screened; without Ns): rows of record || score || z_img packed back to back, N of a row from its round; the
+// round table (host memory here) is uploaded behind the rows in the same staging slot, and every chunk receives the whole table.
 static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status,
-                                 uint32_t group = 0, uint32_t* n_fallback = nullptr, const uint32_t* Ns = nullptr, const uint8_t* vers = nullptr) {
+                                 uint32_t group = 0, uint32_t* n_fallback = nullptr, const uint32_t* Ns = nullptr, const uint8_t* vers = nullptr,
+                                 const VRounds* rd = nullptr) {
     const size_t stride = (size_t)(rec_ver ? 1217u : 1121u) + 32 * (4 + (size_t)N) + 96 + (size_t)N * 32;
-    std::vector<size_t> row_off;  // mixed: byte offset of every row, and the total at [B]
-    if (Ns) {
+    std::vector<size_t> row_off;  // mixed, rounds: byte offset of every row, and the total at [B]
+    size_t tab_bytes = 0;
+    if (rd) {
+        row_off.resize((size_t)B + 1);
+        row_off[0] = 0;
+        for (uint32_t i = 0; i < B; i++) row_off[i + 1] = row_off[i] + round_row_size(rd->n_of(i));
+        for (uint32_t r = 0; r < rd->R; r++) tab_bytes += 32 * (1 + (size_t)rd->round_ns[r]);
+    } else if (Ns) {
         row_off.resize((size_t)B + 1);
         row_off[0] = 0;
         rec_ver = 0;
@@ -967,7 +981,7 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
         if (rec_ver) group = 0;
         else vers = nullptr;  // every row compact: the call the public mixed entry points make
     }
-    const size_t in_bytes = Ns ? row_off[B] : stride * B;
+    const size_t in_bytes = Ns || rd ? row_off[B] : stride * B, tab_off = (in_bytes + 255) / 256 * 256;
     if (group == 0 && rec_ver == 0 && ctx->verify_group > 1 && B >= 2 * ctx->verify_group) group = ctx->verify_group;  // BBP_VERIFY_AGGREGATE
     // Verifier::verify mixes thread_rng into its TranscriptRng (A.7): 32 OS bytes per proof, or (source DEVICE) rows of one key
     const bool dev_draw = ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
@@ -986,20 +1000,23 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
         int32_t rc;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = dev_reserve(ctx, sl.out, 4 * ((size_t)B + 1))) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, 4 * ((size_t)B + 1))) ||
-            (rc = upload_inputs(ctx, sl, in, in_bytes, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0)))
+            (rc = upload_inputs(ctx, sl, in, in_bytes, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0, rd ? rd->rounds : nullptr, tab_bytes, tab_off)))
             return rc;
         if (dev_draw && (rc = draw_enqueue(ctx, B, N, BBP_ENTROPY_VERIFY, key, 0, sl.ent.p, L.stream))) return rc;  // ahead of every chunk on the lane
         const uint32_t n_chunks = (B + host_chunk_verify() - 1) / host_chunk_verify(), chunk = (B + n_chunks - 1) / n_chunks;
         for (uint32_t first = 0; first < B; first += chunk) {  // bounded scratch for any B (see bbp_prove_batch)
             const uint32_t nb = B - first < chunk ? B - first : chunk;
-            const u8 *cin = (const u8*)sl.in.p + (Ns ? row_off[first] : stride * first), *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
+            const u8 *cin = (const u8*)sl.in.p + (Ns || rd ? row_off[first] : stride * first), *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
             int32_t* cst = (int32_t*)sl.out.p + first;
             const u32* cns = Ns ? Ns + first : nullptr;
             const u8* cvers = vers ? vers + first : nullptr;
+            VRounds crd{};  // a chunk may begin and end inside a round: it takes its own slice of round_of and the whole table
+            if (rd) crd = VRounds{rd->R, rd->round_ns, (const u8*)sl.in.p + tab_off, rd->round_of ? rd->round_of + first : nullptr};
+            const VRounds* crdp = rd ? &crd : nullptr;
             if (group > 1) {  // stream-ordered: no synchronisation while the context lock is held
                 if (first == 0 && L.agg_count) BBP_HIP_TRY(ctx, hipMemsetAsync(L.agg_count + 1, 0, sizeof(u32), L.stream));
-                if ((rc = verify_batch_agg_dev(ctx, nb, N, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B, cns))) return rc;
-            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream, cns, cvers)))
+                if ((rc = verify_batch_agg_dev(ctx, nb, N, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B, cns, crdp))) return rc;
+            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream, cns, cvers, crdp)))
                 return rc;
         }
         BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, L.stream));
@@ -1129,6 +1146,74 @@ extern "C" int32_t bbp_verify_batch_mixed_aggregated_dev(bbp_ctx* ctx, uint32_t 
         return verify_batch_agg_dev(ctx, B, 0, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev,
                                     pick_stream(ctx, stream), n_fallback, nullptr, Ns);
     });
+}
+
+// ---- rounds: proofs that share a seed and a bid list, sent once per round (include/bbp.h) ------------------------------------------
+extern "C" uint32_t bbp_round_row_size(uint32_t N) { return bbp_proof_record_size(N) + 64; }
+
+// The screening every form shares, after the NULL checks and B == 0: R, then check_ns's order over all R entries, then round_of.
+static int32_t check_rounds(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, uint32_t B, const uint32_t* round_of) {
+    if (R == 0) return ctx->err = "bbp_verify_rounds: no rounds", BBP_ERR_BAD_ARG;
+    if (int32_t rc = check_ns(ctx, R, round_Ns)) return rc;
+    if (!round_of && R > 1) return ctx->err = "bbp_verify_rounds: round_of may be NULL with one round only", BBP_ERR_BAD_ARG;
+    if (round_of)
+        for (uint32_t i = 0; i < B; i++)
+            if (round_of[i] >= R) return ctx->err = "bbp_verify_rounds: round_of names a round beyond R", BBP_ERR_BAD_ARG;
+    return BBP_OK;
+}
+
+static int32_t verify_rounds_host(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                  const uint8_t* rows, int32_t* status, bool aggregated, uint32_t group, uint32_t* n_fallback) {
+    if (n_fallback) *n_fallback = 0;
+    if (!ctx || !round_Ns || !rounds || !rows || !status) return BBP_ERR_BAD_ARG;
+    if (B == 0) return BBP_OK;
+    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_rounds(ctx, R, round_Ns, B, round_of); });
+    if (rc) return rc;
+    const VRounds rd{R, round_Ns, rounds, round_of};
+    const uint32_t g = aggregated ? (group ? group : BBP_AGG_GROUP_DEFAULT) : 0;
+    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_rounds(ctx, rd, B, rows, status, aggregated, g, n_fallback); });
+    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, rows, status, g, n_fallback, nullptr, nullptr, &rd); });
+}
+
+static int32_t verify_rounds_dev(bbp_ctx* ctx, const char* what, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B,
+                                 const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, void* status_dev, bool aggregated,
+                                 uint32_t group, uint32_t* n_fallback, void* stream) {
+    if (n_fallback) *n_fallback = 0;
+    if (!ctx || !round_Ns || !rounds_dev || !rows_dev || !entropy_dev || !status_dev) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, what);
+    return api_guard(ctx, [&]() -> int32_t {
+        if (B == 0) return BBP_OK;
+        if (int32_t rc = check_rounds(ctx, R, round_Ns, B, round_of)) return rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const VRounds rd{R, round_Ns, (const u8*)rounds_dev, round_of};
+        if (aggregated)
+            return verify_batch_agg_dev(ctx, B, 0, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)rows_dev, (const u8*)entropy_dev, (int32_t*)status_dev,
+                                        pick_stream(ctx, stream), n_fallback, nullptr, nullptr, &rd);
+        return verify_batch_dev_ex(ctx, B, 0, 0, 0, (const u8*)rows_dev, (const u8*)entropy_dev, (int32_t*)status_dev, pick_stream(ctx, stream), nullptr,
+                                   nullptr, &rd);
+    });
+}
+
+extern "C" int32_t bbp_verify_rounds(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                     const uint8_t* rows, int32_t* status) {
+    return verify_rounds_host(ctx, R, round_Ns, rounds, B, round_of, rows, status, false, 0, nullptr);
+}
+
+extern "C" int32_t bbp_verify_rounds_aggregated(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B,
+                                                const uint32_t* round_of, const uint8_t* rows, int32_t* status, uint32_t group, uint32_t* n_fallback) {
+    return verify_rounds_host(ctx, R, round_Ns, rounds, B, round_of, rows, status, true, group, n_fallback);
+}
+
+extern "C" int32_t bbp_verify_rounds_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B, const uint32_t* round_of,
+                                         const void* rows_dev, const void* entropy_dev, void* status_dev, void* stream) {
+    return verify_rounds_dev(ctx, "bbp_verify_rounds_dev", R, round_Ns, rounds_dev, B, round_of, rows_dev, entropy_dev, status_dev, false, 0, nullptr, stream);
+}
+
+extern "C" int32_t bbp_verify_rounds_aggregated_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B,
+                                                    const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, void* status_dev,
+                                                    uint32_t group, uint32_t* n_fallback, void* stream) {
+    return verify_rounds_dev(ctx, "bbp_verify_rounds_aggregated_dev", R, round_Ns, rounds_dev, B, round_of, rows_dev, entropy_dev, status_dev, true, group,
+                             n_fallback, stream);
 }
 
 // Structural parse exactly as R1CSProof::from_bytes / InnerProductProof::from_bytes order their checks: a record of

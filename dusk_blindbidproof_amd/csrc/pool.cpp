@@ -283,6 +283,24 @@ int32_t pool_verify_batch_mixed(bbp_ctx* pool, uint32_t B, const uint32_t* Ns, c
     return rc;
 }
 
+// rows of rounds: the same contiguous blocks by index; every member receives the whole round table
+int32_t pool_verify_rounds(bbp_ctx* pool, const VRounds& rd, uint32_t B, const uint8_t* rows, int32_t* status, bool aggregated, uint32_t group,
+                           uint32_t* n_fallback) {
+    std::vector<size_t> off((size_t)B + 1, 0);
+    for (uint32_t i = 0; i < B; i++) off[i + 1] = off[i] + round_row_size(rd.n_of(i));
+    std::vector<uint32_t> nfb(pool->members.size(), 0);
+    const int32_t rc = for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
+        const uint32_t* of = rd.round_of ? rd.round_of + lo : nullptr;
+        if (!aggregated) return bbp_verify_rounds(m, rd.R, rd.round_ns, rd.rounds, hi - lo, of, rows + off[lo], status + lo);
+        return bbp_verify_rounds_aggregated(m, rd.R, rd.round_ns, rd.rounds, hi - lo, of, rows + off[lo], status + lo, group, &nfb[m->member_index]);
+    });
+    if (n_fallback) {
+        *n_fallback = 0;
+        for (uint32_t v : nfb) *n_fallback += v;
+    }
+    return rc;
+}
+
 int32_t pool_msm_batch(bbp_ctx* pool, uint32_t B, uint32_t n_terms, const uint8_t* scalars, uint32_t layout, uint8_t* out32) {
     return for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
         return bbp_msm_batch(m, hi - lo, n_terms, scalars + (size_t)32 * n_terms * lo, layout, out32 + (size_t)32 * lo);

@@ -606,13 +606,38 @@ static int vlane_of(const bbp_ctx* ctx, hipStream_t s) {  // a lane's own stream
 // ns (host, B entries): a mixed-N call (verifier_mixed.inc): row i is bbp_verify_batch's row for N = ns[i], rows packed back to back;
 // N and rec_ver are then unused.  vers (host, B bytes, with ns only): the record layout of every row, 0 compact / 1 two-phase; null =
 // compact records only.  Strides are those of the largest N; the launches are the same in number.
+// rd (bbp_verify_rounds*, with neither ns nor vers): in_dev holds rows of record || score || z_img, seed and bid list come from
+// rd->rounds (device memory).  One round runs the uniform front end behind k_vparse_round, several the mixed one behind
+// k_vparse_rounds_mx with every row's N taken from its round; N is unused either way.
 int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                            const u32* ns, const u8* vers) {
+                            const u32* ns, const u8* vers, const VRounds* rd) {
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
     const CircuitDev* cp;
     int32_t rc;
     MixedCall mx;
+    std::vector<u32> rd_ns, rd_off;  // rounds: N of every row (several rounds only), scalar offset of every round in the table
+    if (rd) {
+        rd_off.resize((size_t)rd->R + 1);
+        u64 total = 0;
+        for (u32 r = 0; r < rd->R; r++) {
+            rd_off[r] = (u32)total;
+            total += 1 + (u64)rd->round_ns[r];
+        }
+        if (total > 0x7fffffffu) {
+            ctx->err = "round table too large";
+            return BBP_ERR_BAD_ARG;
+        }
+        rd_off[rd->R] = (u32)total;
+        rec_ver = 0;
+        if (rd->R == 1)
+            N = rd->round_ns[0];
+        else {
+            rd_ns.resize(B);
+            for (u32 i = 0; i < B; i++) rd_ns[i] = rd->n_of(i);
+            ns = rd_ns.data();
+        }
+    }
     if (ns) {
         if ((rc = mixed_prepare(ctx, B, ns, mx))) return rc;
         cp = &mx.cmax;
@@ -639,7 +664,11 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     size_t o_vpts = take((size_t)B * np * 32), o_vchal = take((size_t)B * VC_COUNT * 32), o_vs = take((size_t)B * 4098 * 32),
            o_tab = take((size_t)B * np * 8 * sizeof(ge)), o_var = take((size_t)B * np * sizeof(ge)), o_fixed = take((size_t)B * sizeof(ge)),
            o_sp = take((size_t)B * np * 32);
-    const size_t o_rows = ns ? take((size_t)B * sizeof(VRow)) : 0, o_ns = ns ? take((size_t)B * 5) : 0;  // Ns, then the version bytes
+    const size_t o_rows = ns ? take((size_t)B * sizeof(VRow)) : 0, o_ns = ns && !rd ? take((size_t)B * 5) : 0;  // Ns, then the version bytes
+    // rounds: round_of (several rounds only) and the R + 1 round offsets behind it; the reduced round block; the per-round flags
+    const u32 rd_S = rd ? rd_off[rd->R] : 0, rd_nof = rd && ns ? B : 0;
+    const size_t o_rof = rd ? take(4 * ((size_t)rd_nof + rd->R + 1)) : 0, o_rblk = rd ? take((size_t)rd_S * sizeof(sc)) : 0,
+                 o_rflag = rd ? take(4 * (size_t)rd->R) : 0;
     if ((rc = dev_reserve(ctx, L.misc, off))) return rc;
     u8* base = static_cast<u8*>(L.misc.p);
     u32* vpts = (u32*)(base + o_vpts);
@@ -650,8 +679,15 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     ge* fixed = (ge*)(base + o_fixed);
     u32* sp = (u32*)(base + o_sp);
     const VRow* rows = (const VRow*)(base + o_rows);
-    if (ns) {
-        if ((rc = stage_ns(ctx, L, ns, vers, B, (u32*)(base + o_ns), s))) return rc;
+    const u32 *round_of_dev = (const u32*)(base + o_rof), *roff_dev = round_of_dev + rd_nof;
+    const sc* rblk = (const sc*)(base + o_rblk);
+    const int32_t* rflag = (const int32_t*)(base + o_rflag);
+    if (rd) {
+        if ((rc = stage_host(ctx, L, rd->round_of, 4 * (size_t)rd_nof, rd_off.data(), 4 * ((size_t)rd->R + 1), base + o_rof, s))) return rc;
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_round_consts, cdiv(rd_S, 64), 64, s, rd->R, roff_dev, rd->rounds, (sc*)(base + o_rblk), (int32_t*)(base + o_rflag));
+        if (ns) LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows_rounds, 1, VROWS_BLK, s, B, round_of_dev, roff_dev, (VRow*)(base + o_rows));
+    } else if (ns) {
+        if ((rc = stage_host(ctx, L, ns, 4 * (size_t)B, vers, vers ? (size_t)B : 0, base + o_ns, s))) return rc;
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, 1, VROWS_BLK, s, B, (const u32*)(base + o_ns), vers ? (const u8*)(base + o_ns + 4 * (size_t)B) : nullptr,
                (VRow*)(base + o_rows));
     }
@@ -696,7 +732,12 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     constexpr int ko = 0;
 #endif
     LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);
-    if (ns)
+    if (rd && ns)
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_rounds_mx, cdiv(B, 64), 64, s, B, rows, round_of_dev, roff_dev, np * 8, c.n_cst, in_dev, rblk, rflag, vpts,
+               vchal, bd.cst, status_dev);
+    else if (rd)
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_round, cdiv(B, 64), 64, s, B, N, c.n_cst, in_dev, rblk, rflag, vpts, vchal, bd.cst, status_dev);
+    else if (ns)
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_mx, cdiv(B, 64), 64, s, B, rows, np * 8, c.n_cst, in_dev, vpts, vchal, bd.cst, status_dev);
     else
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse, cdiv(B, 64), 64, s, B, N, c.n_cst, rec_ver, in_dev, vpts, vchal, bd.cst, status_dev);
@@ -792,7 +833,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
 }
 
 int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
-    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, nullptr, nullptr);
+    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, nullptr, nullptr, nullptr);
 }
 
 // Aggregated verification with exact per-proof statuses: groups of G proofs are checked with one weighted MSM each; the members
@@ -801,9 +842,9 @@ int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8*
 // and the fallback kernels are launched for up to B proofs and size themselves from the device counter.  *n_fallback
 // (optional) receives the number of proofs that were checked individually -- asking for it synchronises `s`.
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                             u32* n_fallback, u32* total_out_dev, const u32* ns) {
+                             u32* n_fallback, u32* total_out_dev, const u32* ns, const VRounds* rd) {
     if (n_fallback) *n_fallback = 0;
-    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, ns, nullptr);
+    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, ns, nullptr, rd);
     int32_t rc;
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
@@ -826,9 +867,9 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev
     };
     const size_t o_fx = take((size_t)B * sizeof(ge)), o_idx = take(4 * (size_t)B);
     if ((rc = dev_reserve(ctx, L.agg_io, off))) return rc;
-    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s, ns, nullptr))) return rc;  // aggregation: compact records only
+    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s, ns, nullptr, rd))) return rc;  // aggregation: compact records only
     const CircuitDev* cp;  // idx_ver is the same list for every N: any compiled circuit of the call serves
-    if ((rc = circuit_get(ctx, ns ? ns[0] : N, &cp))) return rc;
+    if ((rc = circuit_get(ctx, rd ? rd->n_of(0) : ns ? ns[0] : N, &cp))) return rc;
     u8* base = static_cast<u8*>(L.agg_io.p);
     u32* idx_dev = (u32*)(base + o_idx);
     StreamGuard guard(ctx, s, 1 + lane);

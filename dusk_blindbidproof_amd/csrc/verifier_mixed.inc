@@ -569,6 +569,137 @@ __global__ __launch_bounds__(64) void k_varbase_mx(u32 B, u32 Q, u32 np_stride, 
                                           status, agg, rows[p].ver ? 0u : 1u);
 }
 
+// ---- rounds (bbp_verify_rounds*): rows carry record || score || z_img; seed and bid list come once per round ---------------------
+// The caller's round table is round r = seed || pub_list(N_r), packed: scalar roff[r] of the table is round r's seed, the N_r
+// scalars behind it its items, roff[R] the total.  k_round_consts reduces the table ONCE per call into a block of the same layout
+// (what k_vparse does per row: canonicity of the seed, sc_reduce256, Scalar::from_bits for the items), the parse kernels below copy
+// a row's constants from it.  Only these read the short rows; everything from the transcript replay on is the existing front end.
+__host__ __device__ __forceinline__ u64 vround_row_bytes(u32 n) { return 1121u + 32u * (4u + n) + 64u; }  // record || score || z_img
+
+// one lane per scalar of the table; rflag[r]: BBP_ERR_FORMAT for a non-canonical seed (a serde-deserialised Scalar, as in k_vparse)
+__global__ BBP_LANE_KERNEL void k_round_consts(u32 R, const u32* __restrict__ roff, const u8* __restrict__ rounds, sc* __restrict__ rblk,
+                                               int32_t* __restrict__ rflag) {
+    BBP_THIN_PRIO();
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= roff[R]) return;
+    u32 lo = 0, hi = R;  // roff[lo] <= t < roff[hi]
+    while (hi - lo > 1) {
+        const u32 mid = (lo + hi) >> 1;
+        if (roff[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    const u8* b = rounds + 32 * (size_t)t;
+    u32 w[8];
+    for (int i = 0; i < 8; i++) w[i] = (u32)b[4 * i] | ((u32)b[4 * i + 1] << 8) | ((u32)b[4 * i + 2] << 16) | ((u32)b[4 * i + 3] << 24);
+    if (t == roff[lo]) {
+        rflag[lo] = sc_is_canonical(w) ? (int32_t)BBP_OK : (int32_t)BBP_ERR_FORMAT;
+        st_sc(&rblk[t], sc_reduce256(w));
+    } else
+        st_sc(&rblk[t], sc_from_bits(w));
+}
+
+// vparse_row for a compact record and a short row: rb is the row's round in the reduced block (seed, then the items), rfl its flag.
+// The outer loops stay rolled: unrolled, the byte loads of several fields are in flight at once and the two kernels below need
+// 78 / 84 VGPRs; rolled they need 64 each, below k_vparse (68) and k_vparse_mx (96).
+__device__ __forceinline__ void vparse_round_row(u32 p, u32 n_items, const u8* __restrict__ r, const sc* __restrict__ rb, int32_t rfl,
+                                                 u32* __restrict__ o, sc* __restrict__ vchal, sc* __restrict__ cst, int32_t* __restrict__ status) {
+    const u32 m = 4 + n_items;
+    int32_t st = rfl;
+    if (r[0] != 0) st = BBP_ERR_FORMAT;  // compact records only
+    auto ldw = [&](const u8* b, u32* w) {
+        for (int i = 0; i < 8; i++) w[i] = (u32)b[4 * i] | ((u32)b[4 * i + 1] << 8) | ((u32)b[4 * i + 2] << 16) | ((u32)b[4 * i + 3] << 24);
+    };
+    st_sc(&cst[circuit::CST_SEED], ld_sc(&rb[0]));
+#pragma unroll 1
+    for (u32 i = 0; i < n_items; i++) st_sc(&cst[circuit::CST_ITEM0 + i], ld_sc(&rb[1 + i]));
+    const u8* q = r + 1;
+#pragma unroll 1
+    for (u32 i = 0; i < 3; i++, q += 32) ldw(q, o + 8 * i);
+#pragma unroll 1
+    for (u32 i = 24; i < 48; i++) o[i] = 0;  // A_I2 = A_O2 = S2 = identity
+#pragma unroll 1
+    for (u32 i = 0; i < 5; i++, q += 32) ldw(q, o + 8 * (6 + m + i));
+    sc* vc = vchal + (size_t)p * VC_COUNT;
+    u32 w[8];
+#pragma unroll 1
+    for (u32 i = 0; i < 3; i++, q += 32) {
+        ldw(q, w);
+        if (!sc_is_canonical(w)) st = BBP_ERR_FORMAT;
+        st_sc(&vc[VC_TX + i], BBP_SC_LIT(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]));
+    }
+#pragma unroll 1
+    for (u32 j = 0; j < 11; j++, q += 64) {
+        ldw(q, o + 8 * (6 + m + 5 + j));
+        ldw(q + 32, o + 8 * (6 + m + 5 + 11 + j));
+    }
+#pragma unroll 1
+    for (u32 i = 0; i < 2; i++, q += 32) {
+        ldw(q, w);
+        if (!sc_is_canonical(w)) st = BBP_ERR_FORMAT;
+        st_sc(&vc[VC_A + i], BBP_SC_LIT(w[0], w[1], w[2], w[3], w[4], w[5], w[6], w[7]));
+    }
+#pragma unroll 1
+    for (u32 i = 0; i < m; i++, q += 32) ldw(q, o + 8 * (6 + i));
+    st_sc(&cst[circuit::CST_ONE], sc_one());
+    st_sc(&cst[circuit::CST_ZERO], sc_zero());
+    const u32 pub_slot[2] = {circuit::CST_Q, circuit::CST_ZIMG};  // score, z_img: the row's own, screened like k_vparse's
+#pragma unroll 1
+    for (u32 i = 0; i < 2; i++, q += 32) {
+        ldw(q, w);
+        if (!sc_is_canonical(w)) st = BBP_ERR_FORMAT;
+        st_sc(&cst[pub_slot[i]], sc_reduce256(w));
+    }
+    status[p] = st;
+}
+
+// one round: feeds the uniform front end (the reduced block is one round: the loads from it are the same for every lane)
+__global__ BBP_LANE_KERNEL void k_vparse_round(u32 B, u32 n_items, u32 n_cst, const u8* __restrict__ in, const sc* __restrict__ rblk,
+                                               const int32_t* __restrict__ rflag, u32* __restrict__ vpts, sc* __restrict__ vchal,
+                                               sc* __restrict__ cst_all, int32_t* __restrict__ status) {
+    BBP_THIN_PRIO();
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    vparse_round_row(p, n_items, in + vround_row_bytes(n_items) * p, rblk, rflag[0], vpts + (size_t)p * vnpts(4 + n_items) * 8, vchal,
+                     cst_all + (size_t)p * n_cst, status);
+}
+
+// several rounds: k_vrows for the short rows (N of a row from its round), and the parse that feeds the mixed front end
+__global__ __launch_bounds__(VROWS_BLK) void k_vrows_rounds(u32 B, const u32* __restrict__ round_of, const u32* __restrict__ roff,
+                                                             VRow* __restrict__ rows) {
+    __shared__ u64 part[VROWS_BLK];
+    const u32 tid = threadIdx.x, per = (B + VROWS_BLK - 1) / VROWS_BLK;
+    const u32 lo = min(B, tid * per), hi = min(B, lo + per);
+    auto n_of = [&](u32 i) { return roff[round_of[i] + 1] - roff[round_of[i]] - 1; };
+    u64 sum = 0;
+    for (u32 i = lo; i < hi; i++) sum += vround_row_bytes(n_of(i));
+    part[tid] = sum;
+    __syncthreads();
+    for (u32 d = 1; d < VROWS_BLK; d <<= 1) {
+        const u64 v = tid >= d ? part[tid - d] : 0;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    u64 off = part[tid] - sum;
+    for (u32 i = lo; i < hi; i++) {
+        const u32 n = n_of(i);
+        rows[i] = VRow{off, n, (uint16_t)(4 + n), (uint16_t)0};
+        off += vround_row_bytes(n);
+    }
+}
+
+__global__ BBP_LANE_KERNEL void k_vparse_rounds_mx(u32 B, const VRow* __restrict__ rows, const u32* __restrict__ round_of,
+                                                   const u32* __restrict__ roff, u32 vstride, u32 cst_stride, const u8* __restrict__ in,
+                                                   const sc* __restrict__ rblk, const int32_t* __restrict__ rflag, u32* __restrict__ vpts,
+                                                   sc* __restrict__ vchal, sc* __restrict__ cst_all, int32_t* __restrict__ status) {
+    BBP_THIN_PRIO();
+    const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= B) return;
+    const VRow r = rows[p];
+    const u32 rd = round_of[p];
+    vparse_round_row(p, r.n, in + r.off, rblk + roff[rd], rflag[rd], vpts + (size_t)p * vstride, vchal, cst_all + (size_t)p * cst_stride, status);
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 struct MixedCall {
     CircuitDev cmax;  // the call's strides: every size field the largest over its N; idx_ver (the same list for every N) of one of them
@@ -613,12 +744,13 @@ static int32_t mixed_prepare(bbp_ctx* ctx, u32 B, const u32* ns, MixedCall& mx) 
     return BBP_OK;
 }
 
-// Ns (and, when given, the B version bytes right behind them) -> dst on s through the lane's pinned staging.  No synchronisation
-// unless NS_RING mixed calls are still queued on the lane ahead of this one: then the oldest upload is waited for before its
-// staging is reused.
+// The host arrays of a call -- a (na bytes) and, when given, b (nb bytes) right behind it -> dst on s through the lane's pinned
+// staging: Ns and the version bytes of a mixed call, round_of and the round offsets of a rounds call.  No synchronisation unless
+// NS_RING such calls are still queued on the lane ahead of this one: then the oldest upload is waited for before its staging is
+// reused.  An entry grows to what the call needs.
 constexpr size_t NS_RING = 16;
-static int32_t stage_ns(bbp_ctx* ctx, bbp_ctx::VLane& L, const u32* ns, const u8* vers, u32 B, u32* dst, hipStream_t s) {
-    const size_t bytes = (vers ? 5 : 4) * (size_t)B;
+static int32_t stage_host(bbp_ctx* ctx, bbp_ctx::VLane& L, const void* a, size_t na, const void* b, size_t nb, void* dst, hipStream_t s) {
+    const size_t bytes = na + nb;
     bbp_ctx::VLane::NsStage* st = nullptr;
     for (auto& e : L.ns_ring)
         if (hipEventQuery(e.ev) == hipSuccess) {  // its copy has run (or it was never used)
@@ -642,8 +774,8 @@ static int32_t stage_ns(bbp_ctx* ctx, bbp_ctx::VLane& L, const u32* ns, const u8
         BBP_HIP_TRY(ctx, hipHostMalloc(&st->h, want, hipHostMallocDefault));
         st->cap = want;
     }
-    memcpy(st->h, ns, 4 * (size_t)B);
-    if (vers) memcpy((u8*)st->h + 4 * (size_t)B, vers, B);
+    if (na) memcpy(st->h, a, na);
+    if (nb) memcpy((u8*)st->h + na, b, nb);
     BBP_HIP_TRY(ctx, hipMemcpyAsync(dst, st->h, bytes, hipMemcpyHostToDevice, s));
     BBP_HIP_TRY(ctx, hipEventRecord(st->ev, s));
     return BBP_OK;

@@ -239,6 +239,37 @@ int32_t bbp_verify_batch_mixed_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns,
 int32_t bbp_verify_batch_mixed_aggregated_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev,
                                               void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream);
 
+/* Rounds: proofs that share a seed and a bid list, sent once.  In the blind-bid protocol seed and bid list are public and belong to a
+ * ROUND; only record, score and z_img belong to a proof (the reference sends both with every request because it verifies one proof per
+ * call, src/blindbid/verify.rs:27-47, :100-117).  These calls take a table of R rounds and rows that name their round:
+ *   round_Ns   R host entries, read during the call only, in every form
+ *   rounds     packed back to back: round r is seed(32) || pub_list(32 * round_Ns[r]), 32 * (1 + round_Ns[r]) bytes; host memory in the
+ *              host forms, device memory (rounds_dev) in the _dev forms
+ *   round_of   B host entries below R, read during the call only; may be NULL when R == 1 (every row belongs to round 0)
+ *   rows       packed back to back in request order: row i is record(N) || score || z_img, bbp_round_row_size(N) bytes, with
+ *              N = round_Ns[round_of[i]]; compact records only, as in the mixed calls
+ * status[i] is exactly what bbp_verify_batch_mixed reports for the expanded row record || score || z_img || seed_r || pub_list_r
+ * (BBP_OK / BBP_ERR_VERIFY / BBP_ERR_FORMAT): a non-canonical seed in round r gives every row of round r BBP_ERR_FORMAT and leaves
+ * the rows of other rounds alone; list items keep Scalar::from_bits semantics.  The table is reduced once per call on the device
+ * (1 + N scalars per round instead of per proof) and a batch of one round uploads 7 777 instead of 14 273 bytes per proof at N = 202.
+ * Screening, before anything is verified, the first failing check decides: a NULL among the required pointers BBP_ERR_BAD_ARG; B == 0
+ * BBP_OK; R == 0 BBP_ERR_BAD_ARG; a 0 anywhere in round_Ns BBP_ERR_BAD_ARG, else an entry above BBP_MAX_ITEMS BBP_ERR_GENS_LEN;
+ * round_of[i] >= R, or round_of == NULL with R > 1, BBP_ERR_BAD_ARG.  A round that no row names is allowed.
+ * The aggregated forms keep bbp_verify_batch_aggregated's contract, groups cut by index across rounds; *n_fallback and the stream
+ * ordering of the _dev forms are those of the mixed aggregated calls; entropy_dev holds B rows of 32 bytes under bbp_verify_batch_dev's
+ * contract (distinct, unpredictable rows).  The _dev forms do no host screening of device data.  A pool takes the host forms (rows split
+ * by index into contiguous blocks, every member receives the round table) and refuses the _dev forms. */
+uint32_t bbp_round_row_size(uint32_t N); /* bbp_proof_record_size(N) + 64 */
+int32_t bbp_verify_rounds(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                          const uint8_t* rows, int32_t* status);
+int32_t bbp_verify_rounds_aggregated(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                     const uint8_t* rows, int32_t* status, uint32_t group, uint32_t* n_fallback);
+int32_t bbp_verify_rounds_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B, const uint32_t* round_of,
+                              const void* rows_dev, const void* entropy_dev, void* status_dev, void* stream);
+int32_t bbp_verify_rounds_aggregated_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B,
+                                         const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, void* status_dev, uint32_t group,
+                                         uint32_t* n_fallback, void* stream);
+
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.
  * Without it the buffers grow on demand, and a call that finds them too small frees and reallocates gigabytes under load (the
