@@ -16,11 +16,10 @@
 namespace bbp {
 int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, u8* out_dev, hipStream_t s,
                         const std::function<int32_t(hipStream_t)>* open_hook = nullptr);
-int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
-int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                            const u32* ns = nullptr, const u8* vers = nullptr, const VRounds* rd = nullptr);
-int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                             u32* n_fallback, u32* total_out_dev = nullptr, const u32* ns = nullptr, const VRounds* rd = nullptr);
+// verifier.inc: the plain and the aggregated driver; what the rows are travels in the descriptor (verify_rows.h)
+int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s);
+int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
+                             u32* n_fallback, u32* total_out_dev = nullptr);
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out);
 
 // native (non-circuit) image of the gadget wiring: what the reference's Go caller computes before Proof::prove
@@ -234,7 +233,7 @@ static int32_t no_throw(F&& body, const void* ctx = nullptr) noexcept {
 }
 }  // namespace bbp
 
-extern "C" uint32_t bbp_proof_record_size(uint32_t N) { return BBP_R1CS_PROOF_BYTES + 32u * (4u + N); }
+extern "C" uint32_t bbp_proof_record_size(uint32_t N) { return (uint32_t)proof_record_bytes(N); }
 extern "C" uint32_t bbp_entropy_size(uint32_t N) { return 32u * (4u + N) + 32u; }
 
 extern "C" int32_t bbp_debug_compile_circuit(uint32_t N, uint32_t* n_mul, uint32_t* n_cons) {
@@ -440,10 +439,9 @@ static int32_t corrupt_hook(bbp_ctx* ctx, u32 first, u32 nb, u32 N, u8* out_dev,
     return BBP_OK;
 }
 
-static size_t check_row_bytes(u32 N) { return bbp_proof_record_size(N) + 96 + 32 * (size_t)N; }
 static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
 // scratch of one checked call of B proofs: verify rows, then verifier statuses
-static size_t check_scratch_bytes(u32 B, u32 N) { return align256(check_row_bytes(N) * B) + 4 * (size_t)B; }
+static size_t check_scratch_bytes(u32 B, u32 N) { return align256(verify_row_bytes(N) * B) + 4 * (size_t)B; }
 
 // One checked prove launch (context lock held): witness check on the opening stream, the prover, the verify rows and the aggregated
 // verifier on a verifier lane's stream -- forked from the records' completion on `s`, joined back before the status merge on `s`.
@@ -476,18 +474,18 @@ static int32_t prove_checked_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* in, c
     if ((rc = corrupt_hook(ctx, 0, B, N, out, s))) return rc;
     bbp_ctx::VLane& L = ctx->vl[ctx->chk_lane++ % (u32)bbp_ctx::VLANES];
     u8* rows = scratch;
-    int32_t* vstatus = reinterpret_cast<int32_t*>(scratch + align256(check_row_bytes(N) * B));
+    int32_t* vstatus = reinterpret_cast<int32_t*>(scratch + align256(verify_row_bytes(N) * B));
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_chk_fork, s));
     BBP_HIP_TRY(ctx, hipStreamWaitEvent(L.stream, ctx->ev_chk_fork, 0));
     if (reuse) BBP_HIP_TRY(ctx, hipStreamWaitEvent(L.stream, reuse, 0));
     {
         ScopedEvent ev(ctx, TAG_VERIFY_SCALARS, L.stream);
-        const size_t n = check_row_bytes(N) * B;
+        const size_t n = verify_row_bytes(N) * B;
         hipLaunchKernelGGL(k_check_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, L.stream, B, N, in, (const u8*)out, rows);
         BBP_HIP_TRY(ctx, hipGetLastError());
     }
     const int last_par = ctx->last_par;  // (the verifier takes it over; bbp_debug_challenges means the prove call)
-    rc = verify_batch_agg_dev(ctx, B, N, BBP_AGG_GROUP_DEFAULT, rows, cent, vstatus, L.stream, nullptr);
+    rc = verify_batch_agg_dev(ctx, VerifyRows::uniform(B, N), BBP_AGG_GROUP_DEFAULT, rows, cent, vstatus, L.stream, nullptr);
     ctx->last_par = last_par;
     if (rc) return rc;
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_chk_join, L.stream));
@@ -952,36 +950,14 @@ extern "C" int32_t bbp_prove_async(bbp_ctx* ctx, const uint8_t scalars7[7 * 32],
     }, ctx);
 }
 
-// rec_ver 0: compact 1121-byte proofs; 1: the 2-phase 1217-byte R1CSProof layout (both parse in the reference)
-// Takes the context lock itself, for the enqueue phase only (aggregated mode synchronises inside it: the host reads group verdicts).
-// Ns (B entries, screened): a mixed-N call, rows of bbp_verify_batch_mixed packed back to back; N and rec_ver are then unused.
-// vers (with Ns only, B bytes): the record layout of every row (0 / 1); null = compact rows, the public mixed calls' contract.
-// rd (bbp_verify_rounds*, screened; without Ns): rows of record || score || z_img packed back to back, N of a row from its round; the
-// round table (host memory here) is uploaded behind the rows in the same staging slot, and every chunk receives the whole table.
-static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status,
-                                 uint32_t group = 0, uint32_t* n_fallback = nullptr, const uint32_t* Ns = nullptr, const uint8_t* vers = nullptr,
-                                 const VRounds* rd = nullptr) {
-    const size_t stride = (size_t)(rec_ver ? 1217u : 1121u) + 32 * (4 + (size_t)N) + 96 + (size_t)N * 32;
-    std::vector<size_t> row_off;  // mixed, rounds: byte offset of every row, and the total at [B]
-    size_t tab_bytes = 0;
-    if (rd) {
-        row_off.resize((size_t)B + 1);
-        row_off[0] = 0;
-        for (uint32_t i = 0; i < B; i++) row_off[i + 1] = row_off[i] + round_row_size(rd->n_of(i));
-        for (uint32_t r = 0; r < rd->R; r++) tab_bytes += 32 * (1 + (size_t)rd->round_ns[r]);
-    } else if (Ns) {
-        row_off.resize((size_t)B + 1);
-        row_off[0] = 0;
-        rec_ver = 0;
-        for (uint32_t i = 0; i < B; i++) {
-            const bool two_phase = vers && vers[i];
-            if (two_phase) rec_ver = 1;  // the aggregated path takes compact records only: one two-phase row and the call runs plain
-            row_off[i + 1] = row_off[i] + verify_row_size(Ns[i]) + (two_phase ? 96u : 0u);
-        }
-        if (rec_ver) group = 0;
-        else vers = nullptr;  // every row compact: the call the public mixed entry points make
-    }
-    const size_t in_bytes = Ns || rd ? row_off[B] : stride * B, tab_off = (in_bytes + 255) / 256 * 256;
+// The host-pointer verify path of one context; `rows` says what `in` holds (verify_rows.h; a rounds call: its table in host memory,
+// uploaded behind the rows in the same staging slot).  Takes the context lock itself, for the enqueue phase only.
+static int32_t verify_batch_host(bbp_ctx* ctx, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group = 0,
+                                 uint32_t* n_fallback = nullptr) {
+    const uint32_t B = rows.B, rec_ver = rows.rec_ver, N = rows.kind == VerifyRows::UNIFORM ? rows.N : 0;
+    const std::vector<size_t> row_off = rows.offsets();
+    const size_t in_bytes = row_off[B], tab_bytes = rows.table_bytes(), tab_off = align256(in_bytes);
+    if (rec_ver) group = 0;  // the aggregated path takes compact records only: one two-phase row and the call runs plain
     if (group == 0 && rec_ver == 0 && ctx->verify_group > 1 && B >= 2 * ctx->verify_group) group = ctx->verify_group;  // BBP_VERIFY_AGGREGATE
     // Verifier::verify mixes thread_rng into its TranscriptRng (A.7): 32 OS bytes per proof, or (source DEVICE) rows of one key
     const bool dev_draw = ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
@@ -1000,23 +976,20 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
         int32_t rc;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         if ((rc = dev_reserve(ctx, sl.out, 4 * ((size_t)B + 1))) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, 4 * ((size_t)B + 1))) ||
-            (rc = upload_inputs(ctx, sl, in, in_bytes, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0, rd ? rd->rounds : nullptr, tab_bytes, tab_off)))
+            (rc = upload_inputs(ctx, sl, in, in_bytes, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0, rows.rounds, tab_bytes, tab_off)))
             return rc;
         if (dev_draw && (rc = draw_enqueue(ctx, B, N, BBP_ENTROPY_VERIFY, key, 0, sl.ent.p, L.stream))) return rc;  // ahead of every chunk on the lane
         const uint32_t n_chunks = (B + host_chunk_verify() - 1) / host_chunk_verify(), chunk = (B + n_chunks - 1) / n_chunks;
         for (uint32_t first = 0; first < B; first += chunk) {  // bounded scratch for any B (see bbp_prove_batch)
             const uint32_t nb = B - first < chunk ? B - first : chunk;
-            const u8 *cin = (const u8*)sl.in.p + (Ns || rd ? row_off[first] : stride * first), *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
+            const u8 *cin = (const u8*)sl.in.p + row_off[first], *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
             int32_t* cst = (int32_t*)sl.out.p + first;
-            const u32* cns = Ns ? Ns + first : nullptr;
-            const u8* cvers = vers ? vers + first : nullptr;
-            VRounds crd{};  // a chunk may begin and end inside a round: it takes its own slice of round_of and the whole table
-            if (rd) crd = VRounds{rd->R, rd->round_ns, (const u8*)sl.in.p + tab_off, rd->round_of ? rd->round_of + first : nullptr};
-            const VRounds* crdp = rd ? &crd : nullptr;
+            VerifyRows c = rows.slice(first, first + nb);  // a chunk may begin and end inside a round: it takes the whole table
+            if (c.rounds) c.rounds = (const u8*)sl.in.p + tab_off;
             if (group > 1) {  // stream-ordered: no synchronisation while the context lock is held
                 if (first == 0 && L.agg_count) BBP_HIP_TRY(ctx, hipMemsetAsync(L.agg_count + 1, 0, sizeof(u32), L.stream));
-                if ((rc = verify_batch_agg_dev(ctx, nb, N, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B, cns, crdp))) return rc;
-            } else if ((rc = verify_batch_dev_ex(ctx, nb, N, rec_ver, 0, cin, cent, cst, L.stream, cns, cvers, crdp)))
+                if ((rc = verify_batch_agg_dev(ctx, c, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B))) return rc;
+            } else if ((rc = verify_batch_dev(ctx, c, 0, cin, cent, cst, L.stream)))
                 return rc;
         }
         BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, L.stream));
@@ -1029,9 +1002,15 @@ static int32_t verify_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
     return BBP_OK;
 }
 
+int32_t bbp::verify_host(bbp_ctx* ctx, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback) {
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        return is_pool(ctx) ? pool_verify(ctx, rows, in, status, group, n_fallback) : verify_batch_host(ctx, rows, in, status, group, n_fallback);
+    });
+}
+
 int32_t bbp::verify_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status,
                                  std::string* err) {
-    const int32_t rc = no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, N, rec_ver, in, status); });
+    const int32_t rc = no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, VerifyRows::uniform(B, N, rec_ver), in, status); });
     if (rc && err) *err = tls_error();
     return rc;
 }
@@ -1040,59 +1019,12 @@ int32_t bbp::verify_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t 
 // runner handed to Combiner::set_mixed_verify).  Ns and vers come from requests that bbp_verify has screened.
 int32_t bbp::verify_batch_mixed_locked(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* vers, const uint8_t* in, int32_t* status,
                                        std::string* err) {
-    const int32_t rc = no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, in, status, 0, nullptr, Ns, vers); });
+    const int32_t rc = no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, VerifyRows::mixed(B, Ns, vers), in, status); });
     if (rc && err) *err = tls_error();
     return rc;
 }
 
-extern "C" int32_t bbp_verify_batch(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status) {
-    if (!ctx || !in || !status) return BBP_ERR_BAD_ARG;
-    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
-    if (rc || B == 0) return rc;
-    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_batch(ctx, B, N, in, status, false, 0, nullptr); });
-    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, N, 0, in, status); });
-}
-
-extern "C" int32_t bbp_verify_batch_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
-                                        void* status_dev, void* stream) {
-    if (!ctx || !in_dev || !entropy_dev || !status_dev) return BBP_ERR_BAD_ARG;
-    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_batch_dev");
-    return api_guard(ctx, [&]() -> int32_t {
-        int32_t rc = check_n(ctx, N);
-        if (rc) return rc;
-        if (B == 0) return BBP_OK;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return verify_batch_dev(ctx, B, N, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev, pick_stream(ctx, stream));
-    });
-}
-
-extern "C" int32_t bbp_verify_batch_aggregated(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status, uint32_t group,
-                                               uint32_t* n_fallback) {
-    if (n_fallback) *n_fallback = 0;
-    if (!ctx || !in || !status) return BBP_ERR_BAD_ARG;
-    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
-    if (rc || B == 0) return rc;
-    if (is_pool(ctx))
-        return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_batch(ctx, B, N, in, status, true, group ? group : BBP_AGG_GROUP_DEFAULT, n_fallback); });
-    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, N, 0, in, status, group ? group : BBP_AGG_GROUP_DEFAULT, n_fallback); });
-}
-
-extern "C" int32_t bbp_verify_batch_aggregated_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
-                                                   void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream) {
-    if (n_fallback) *n_fallback = 0;
-    if (!ctx || !in_dev || !entropy_dev || !status_dev) return BBP_ERR_BAD_ARG;
-    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_batch_aggregated_dev");
-    return api_guard(ctx, [&]() -> int32_t {
-        int32_t rc = check_n(ctx, N);
-        if (rc) return rc;
-        if (B == 0) return BBP_OK;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return verify_batch_agg_dev(ctx, B, N, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)in_dev, (const u8*)entropy_dev,
-                                    (int32_t*)status_dev, pick_stream(ctx, stream), n_fallback);
-    });
-}
-
-// ---- mixed-N verification: rows of any mix of bid-list lengths in one call (include/bbp.h) ------------------------------------
+// ---- the twelve verify entry points: uniform, mixed-N, rounds (include/bbp.h) x host / device pointers x plain / aggregated --------
 // Every row's N is screened on the host before anything is verified: a 0 anywhere is BBP_ERR_BAD_ARG, else an N above
 // BBP_MAX_ITEMS anywhere is BBP_ERR_GENS_LEN -- what a uniform call with that N returns.
 static int32_t check_ns(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns) {
@@ -1103,117 +1035,116 @@ static int32_t check_ns(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns) {
     return BBP_OK;
 }
 
+// Screening of a call's layout, under the context lock.  Rounds: R, then check_ns's order over all R entries, then round_of.
+static int32_t check_rows(bbp_ctx* ctx, const VerifyRows& v) {
+    if (v.kind == VerifyRows::UNIFORM) return check_n(ctx, v.N);
+    if (v.kind == VerifyRows::MIXED) return check_ns(ctx, v.B, v.ns);
+    if (v.R == 0) return ctx->err = "bbp_verify_rounds: no rounds", BBP_ERR_BAD_ARG;
+    if (int32_t rc = check_ns(ctx, v.R, v.round_ns)) return rc;
+    if (!v.round_of && v.R > 1) return ctx->err = "bbp_verify_rounds: round_of may be NULL with one round only", BBP_ERR_BAD_ARG;
+    if (v.round_of)
+        for (uint32_t i = 0; i < v.B; i++)
+            if (v.round_of[i] >= v.R) return ctx->err = "bbp_verify_rounds: round_of names a round beyond R", BBP_ERR_BAD_ARG;
+    return BBP_OK;
+}
+
+// The order is part of every form's behaviour: *n_fallback zeroed first; the NULL checks (layout_ok: the form's own array arguments);
+// device forms refuse a pool before any screening; uniform and mixed forms are screened BEFORE the B == 0 return, a rounds form
+// returns BBP_OK for B == 0 before its table is looked at.
+static int32_t verify_entry_host(bbp_ctx* ctx, bool layout_ok, const VerifyRows& rows, const uint8_t* in, int32_t* status, bool aggregated,
+                                 uint32_t group, uint32_t* n_fallback) {
+    if (n_fallback) *n_fallback = 0;
+    if (!ctx || !layout_ok || !in || !status) return BBP_ERR_BAD_ARG;
+    if (rows.kind == VerifyRows::ROUNDS && rows.B == 0) return BBP_OK;
+    const int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_rows(ctx, rows); });
+    if (rc || rows.B == 0) return rc;
+    return verify_host(ctx, rows, in, status, aggregated ? (group ? group : BBP_AGG_GROUP_DEFAULT) : 0, n_fallback);
+}
+
+static int32_t verify_entry_dev(bbp_ctx* ctx, const char* what, bool layout_ok, const VerifyRows& rows, const void* in_dev, const void* entropy_dev,
+                                void* status_dev, bool aggregated, uint32_t group, uint32_t* n_fallback, void* stream) {
+    if (n_fallback) *n_fallback = 0;
+    if (!ctx || !layout_ok || !in_dev || !entropy_dev || !status_dev) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, what);
+    return api_guard(ctx, [&]() -> int32_t {
+        if (rows.kind == VerifyRows::ROUNDS && rows.B == 0) return BBP_OK;
+        const int32_t rc = check_rows(ctx, rows);
+        if (rc || rows.B == 0) return rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (aggregated)
+            return verify_batch_agg_dev(ctx, rows, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev,
+                                        pick_stream(ctx, stream), n_fallback);
+        return verify_batch_dev(ctx, rows, 0, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev, pick_stream(ctx, stream));
+    });
+}
+
+extern "C" int32_t bbp_verify_batch(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status) {
+    return verify_entry_host(ctx, true, VerifyRows::uniform(B, N), in, status, false, 0, nullptr);
+}
+
+extern "C" int32_t bbp_verify_batch_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
+                                        void* status_dev, void* stream) {
+    return verify_entry_dev(ctx, "bbp_verify_batch_dev", true, VerifyRows::uniform(B, N), in_dev, entropy_dev, status_dev, false, 0, nullptr, stream);
+}
+
+extern "C" int32_t bbp_verify_batch_aggregated(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status, uint32_t group,
+                                               uint32_t* n_fallback) {
+    return verify_entry_host(ctx, true, VerifyRows::uniform(B, N), in, status, true, group, n_fallback);
+}
+
+extern "C" int32_t bbp_verify_batch_aggregated_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* in_dev, const void* entropy_dev,
+                                                   void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream) {
+    return verify_entry_dev(ctx, "bbp_verify_batch_aggregated_dev", true, VerifyRows::uniform(B, N), in_dev, entropy_dev, status_dev, true, group,
+                            n_fallback, stream);
+}
+
+// mixed-N verification: rows of any mix of bid-list lengths in one call
 extern "C" int32_t bbp_verify_batch_mixed(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status) {
-    if (!ctx || !in || !status || (B && !Ns)) return BBP_ERR_BAD_ARG;
-    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_ns(ctx, B, Ns); });
-    if (rc || B == 0) return rc;
-    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_batch_mixed(ctx, B, Ns, in, status, false, 0, nullptr); });
-    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, in, status, 0, nullptr, Ns); });
+    return verify_entry_host(ctx, !B || Ns, VerifyRows::mixed(B, Ns), in, status, false, 0, nullptr);
 }
 
 extern "C" int32_t bbp_verify_batch_mixed_aggregated(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, uint32_t group,
                                                      uint32_t* n_fallback) {
-    if (n_fallback) *n_fallback = 0;
-    if (!ctx || !in || !status || (B && !Ns)) return BBP_ERR_BAD_ARG;
-    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_ns(ctx, B, Ns); });
-    if (rc || B == 0) return rc;
-    const uint32_t g = group ? group : BBP_AGG_GROUP_DEFAULT;
-    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_batch_mixed(ctx, B, Ns, in, status, true, g, n_fallback); });
-    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, in, status, g, n_fallback, Ns); });
+    return verify_entry_host(ctx, !B || Ns, VerifyRows::mixed(B, Ns), in, status, true, group, n_fallback);
 }
 
 extern "C" int32_t bbp_verify_batch_mixed_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev,
                                               void* status_dev, void* stream) {
-    if (!ctx || !in_dev || !entropy_dev || !status_dev || (B && !Ns)) return BBP_ERR_BAD_ARG;
-    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_batch_mixed_dev");
-    return api_guard(ctx, [&]() -> int32_t {
-        int32_t rc = check_ns(ctx, B, Ns);
-        if (rc || B == 0) return rc;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return verify_batch_dev_ex(ctx, B, 0, 0, 0, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev, pick_stream(ctx, stream), Ns);
-    });
+    return verify_entry_dev(ctx, "bbp_verify_batch_mixed_dev", !B || Ns, VerifyRows::mixed(B, Ns), in_dev, entropy_dev, status_dev, false, 0, nullptr,
+                            stream);
 }
 
 extern "C" int32_t bbp_verify_batch_mixed_aggregated_dev(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const void* in_dev, const void* entropy_dev,
                                                          void* status_dev, uint32_t group, uint32_t* n_fallback, void* stream) {
-    if (n_fallback) *n_fallback = 0;
-    if (!ctx || !in_dev || !entropy_dev || !status_dev || (B && !Ns)) return BBP_ERR_BAD_ARG;
-    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_batch_mixed_aggregated_dev");
-    return api_guard(ctx, [&]() -> int32_t {
-        int32_t rc = check_ns(ctx, B, Ns);
-        if (rc || B == 0) return rc;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        return verify_batch_agg_dev(ctx, B, 0, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)in_dev, (const u8*)entropy_dev, (int32_t*)status_dev,
-                                    pick_stream(ctx, stream), n_fallback, nullptr, Ns);
-    });
+    return verify_entry_dev(ctx, "bbp_verify_batch_mixed_aggregated_dev", !B || Ns, VerifyRows::mixed(B, Ns), in_dev, entropy_dev, status_dev, true,
+                            group, n_fallback, stream);
 }
 
-// ---- rounds: proofs that share a seed and a bid list, sent once per round (include/bbp.h) ------------------------------------------
-extern "C" uint32_t bbp_round_row_size(uint32_t N) { return bbp_proof_record_size(N) + 64; }
-
-// The screening every form shares, after the NULL checks and B == 0: R, then check_ns's order over all R entries, then round_of.
-static int32_t check_rounds(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, uint32_t B, const uint32_t* round_of) {
-    if (R == 0) return ctx->err = "bbp_verify_rounds: no rounds", BBP_ERR_BAD_ARG;
-    if (int32_t rc = check_ns(ctx, R, round_Ns)) return rc;
-    if (!round_of && R > 1) return ctx->err = "bbp_verify_rounds: round_of may be NULL with one round only", BBP_ERR_BAD_ARG;
-    if (round_of)
-        for (uint32_t i = 0; i < B; i++)
-            if (round_of[i] >= R) return ctx->err = "bbp_verify_rounds: round_of names a round beyond R", BBP_ERR_BAD_ARG;
-    return BBP_OK;
-}
-
-static int32_t verify_rounds_host(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
-                                  const uint8_t* rows, int32_t* status, bool aggregated, uint32_t group, uint32_t* n_fallback) {
-    if (n_fallback) *n_fallback = 0;
-    if (!ctx || !round_Ns || !rounds || !rows || !status) return BBP_ERR_BAD_ARG;
-    if (B == 0) return BBP_OK;
-    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_rounds(ctx, R, round_Ns, B, round_of); });
-    if (rc) return rc;
-    const VRounds rd{R, round_Ns, rounds, round_of};
-    const uint32_t g = aggregated ? (group ? group : BBP_AGG_GROUP_DEFAULT) : 0;
-    if (is_pool(ctx)) return no_throw_ctx(ctx, [&]() -> int32_t { return pool_verify_rounds(ctx, rd, B, rows, status, aggregated, g, n_fallback); });
-    return no_throw_ctx(ctx, [&]() -> int32_t { return verify_batch_host(ctx, B, 0, 0, rows, status, g, n_fallback, nullptr, nullptr, &rd); });
-}
-
-static int32_t verify_rounds_dev(bbp_ctx* ctx, const char* what, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B,
-                                 const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, void* status_dev, bool aggregated,
-                                 uint32_t group, uint32_t* n_fallback, void* stream) {
-    if (n_fallback) *n_fallback = 0;
-    if (!ctx || !round_Ns || !rounds_dev || !rows_dev || !entropy_dev || !status_dev) return BBP_ERR_BAD_ARG;
-    if (is_pool(ctx)) return pool_reject(ctx, what);
-    return api_guard(ctx, [&]() -> int32_t {
-        if (B == 0) return BBP_OK;
-        if (int32_t rc = check_rounds(ctx, R, round_Ns, B, round_of)) return rc;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        const VRounds rd{R, round_Ns, (const u8*)rounds_dev, round_of};
-        if (aggregated)
-            return verify_batch_agg_dev(ctx, B, 0, group ? group : BBP_AGG_GROUP_DEFAULT, (const u8*)rows_dev, (const u8*)entropy_dev, (int32_t*)status_dev,
-                                        pick_stream(ctx, stream), n_fallback, nullptr, nullptr, &rd);
-        return verify_batch_dev_ex(ctx, B, 0, 0, 0, (const u8*)rows_dev, (const u8*)entropy_dev, (int32_t*)status_dev, pick_stream(ctx, stream), nullptr,
-                                   nullptr, &rd);
-    });
-}
+// rounds: proofs that share a seed and a bid list, sent once per round
+extern "C" uint32_t bbp_round_row_size(uint32_t N) { return (uint32_t)round_row_bytes(N); }
 
 extern "C" int32_t bbp_verify_rounds(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
                                      const uint8_t* rows, int32_t* status) {
-    return verify_rounds_host(ctx, R, round_Ns, rounds, B, round_of, rows, status, false, 0, nullptr);
+    return verify_entry_host(ctx, round_Ns && rounds, VerifyRows::of_rounds(B, R, round_Ns, rounds, round_of), rows, status, false, 0, nullptr);
 }
 
 extern "C" int32_t bbp_verify_rounds_aggregated(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B,
                                                 const uint32_t* round_of, const uint8_t* rows, int32_t* status, uint32_t group, uint32_t* n_fallback) {
-    return verify_rounds_host(ctx, R, round_Ns, rounds, B, round_of, rows, status, true, group, n_fallback);
+    return verify_entry_host(ctx, round_Ns && rounds, VerifyRows::of_rounds(B, R, round_Ns, rounds, round_of), rows, status, true, group, n_fallback);
 }
 
 extern "C" int32_t bbp_verify_rounds_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B, const uint32_t* round_of,
                                          const void* rows_dev, const void* entropy_dev, void* status_dev, void* stream) {
-    return verify_rounds_dev(ctx, "bbp_verify_rounds_dev", R, round_Ns, rounds_dev, B, round_of, rows_dev, entropy_dev, status_dev, false, 0, nullptr, stream);
+    return verify_entry_dev(ctx, "bbp_verify_rounds_dev", round_Ns && rounds_dev, VerifyRows::of_rounds(B, R, round_Ns, (const u8*)rounds_dev, round_of),
+                            rows_dev, entropy_dev, status_dev, false, 0, nullptr, stream);
 }
 
 extern "C" int32_t bbp_verify_rounds_aggregated_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B,
                                                     const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, void* status_dev,
                                                     uint32_t group, uint32_t* n_fallback, void* stream) {
-    return verify_rounds_dev(ctx, "bbp_verify_rounds_aggregated_dev", R, round_Ns, rounds_dev, B, round_of, rows_dev, entropy_dev, status_dev, true, group,
-                             n_fallback, stream);
+    return verify_entry_dev(ctx, "bbp_verify_rounds_aggregated_dev", round_Ns && rounds_dev,
+                            VerifyRows::of_rounds(B, R, round_Ns, (const u8*)rounds_dev, round_of), rows_dev, entropy_dev, status_dev, true, group,
+                            n_fallback, stream);
 }
 
 // Structural parse exactly as R1CSProof::from_bytes / InnerProductProof::from_bytes order their checks: a record of
@@ -1345,8 +1276,9 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
     }
     return no_throw_ctx(ctx, [&]() -> int32_t {
         const uint32_t B = max_batch;
-        const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, rec = bbp_proof_record_size(N), v_stride = rec + 96 + (size_t)N * 32;
-        std::vector<uint8_t> in(in_stride * B, 0), ent((size_t)bbp_entropy_size(N) * B, 0), out(rec * B), vin(v_stride * B, 0);
+        const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, rec = bbp_proof_record_size(N);
+        const VerifyRows vrows = VerifyRows::uniform(B, N);
+        std::vector<uint8_t> in(in_stride * B, 0), ent((size_t)bbp_entropy_size(N) * B, 0), out(rec * B), vin(vrows.row_bytes(0) * B, 0);
         std::vector<int32_t> st(B);
         int32_t rc = BBP_OK;
         // batches below 1024 proofs rotate three buffers and two opening streams, larger ones two buffers: both shapes, every slot
@@ -1362,12 +1294,12 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
             ctx->force_deep = true;
             for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data(), CHECK_OFF);
         }
-        for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++) rc = verify_batch_host(ctx, B, N, 0, vin.data(), st.data());
+        for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++) rc = verify_batch_host(ctx, vrows, vin.data(), st.data());
         // checked proving (only when it is on, and without running a check): the staging slots' and the device ring's check
         // scratch, and the aggregated verifier's buffers of every lane (the check's verifier)
         if (rc == BBP_OK && ctx->prove_check) {
             for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++)
-                rc = verify_batch_host(ctx, B, N, 0, vin.data(), st.data(), BBP_AGG_GROUP_DEFAULT);
+                rc = verify_batch_host(ctx, vrows, vin.data(), st.data(), BBP_AGG_GROUP_DEFAULT);
             if (rc == BBP_OK)
                 rc = api_guard(ctx, [&]() -> int32_t {
                     int32_t rc = BBP_OK;

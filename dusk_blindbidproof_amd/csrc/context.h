@@ -18,6 +18,7 @@
 #include "../../include/bbp.h"
 #include "point.h"
 #include "scalar.h"
+#include "verify_rows.h"
 
 namespace bbp {
 
@@ -461,25 +462,10 @@ void own_hw_queues();
 int hw_queues_state();
 // pool.cpp: the host-pointer batch calls on a pool handle (block split by index over the members, results in request order)
 int32_t pool_prove_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status);
-int32_t pool_verify_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group, uint32_t* n_fallback);
-int32_t pool_verify_batch_mixed(bbp_ctx* pool, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group,
-                                uint32_t* n_fallback);
-// bytes of one bbp_verify_batch row for list length N: record || score || z_img || seed || pub_list
-inline size_t verify_row_size(uint32_t N) { return (size_t)bbp_proof_record_size(N) + 96 + 32 * (size_t)N; }
-// bbp_verify_rounds*: the table of rounds of a call whose rows carry record || score || z_img only (verifier_mixed.inc).  round_ns and
-// round_of are host memory, screened by the entry points; rounds is host memory on the way into verify_batch_host and device memory
-// from there on.
-struct VRounds {
-    uint32_t R;
-    const uint32_t* round_ns;  // R entries
-    const uint8_t* rounds;     // round r: seed || pub_list(round_ns[r]), packed back to back
-    const uint32_t* round_of;  // B entries below R; null (R == 1 only): every row is of round 0
-    uint32_t n_of(uint32_t row) const { return round_ns[round_of ? round_of[row] : 0]; }
-};
-// bytes of one row of such a call: record || score || z_img
-inline size_t round_row_size(uint32_t N) { return (size_t)bbp_proof_record_size(N) + 64; }
-int32_t pool_verify_rounds(bbp_ctx* pool, const VRounds& rd, uint32_t B, const uint8_t* rows, int32_t* status, bool aggregated, uint32_t group,
-                           uint32_t* n_fallback);
+// every verify form on a pool handle: the rows block-split over the members (VerifyRows::slice); group == 0: the plain entry point
+int32_t pool_verify(bbp_ctx* pool, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback);
+// capi_prove.hip: the host-pointer verify path of a context or a pool, after the entry point's screening (what a pool runs on its members)
+int32_t verify_host(bbp_ctx* ctx, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback);
 int32_t pool_msm_batch(bbp_ctx* pool, uint32_t B, uint32_t n_terms, const uint8_t* scalars, uint32_t layout, uint8_t* out32);
 int32_t pool_reject(bbp_ctx* pool, const char* what);  // BBP_ERR_BAD_ARG + message: entry points that need ONE device
 void pool_workers_start(bbp_ctx* pool);

@@ -6,7 +6,7 @@
 // works and seven idle.  A pool handle is a bbp_ctx without device state whose `members` are ordinary contexts:
 //   * bbp_prove / bbp_verify: ONE call combiner (submit.cpp) collects the concurrent callers and deals every batch to the member
 //     with the fewest combined calls in flight; a burst is split into fair shares over the idle members;
-//   * bbp_prove_batch / bbp_verify_batch[_aggregated] / bbp_msm_batch: contiguous block split by index over the members, sizes
+//   * bbp_prove_batch / bbp_verify_batch* / bbp_verify_rounds* / bbp_msm_batch: contiguous block split by index over the members, sizes
 //     differing by at most one (= sharding.shard_range), one host thread per member, results land in request order
 //     because every member writes straight into its slice of the caller's buffers;
 //   * no data crosses between GPUs (proofs are independent units; tables are replicated per member at init).
@@ -251,48 +251,13 @@ int32_t pool_prove_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* i
     });
 }
 
-int32_t pool_verify_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group,
-                          uint32_t* n_fallback) {
-    const size_t stride = (size_t)bbp_proof_record_size(N) + 96 + (size_t)N * 32;
+// every verify form: contiguous blocks of rows by index, each member's block a call of its own (a rounds call: with the whole round
+// table).  group travels as the entry point resolved it, 0 = the plain form.
+int32_t pool_verify(bbp_ctx* pool, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback) {
+    const std::vector<size_t> off = rows.offsets();
     std::vector<uint32_t> nfb(pool->members.size(), 0);
-    const int32_t rc = for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
-        if (!aggregated) return bbp_verify_batch(m, hi - lo, N, in + stride * lo, status + lo);
-        return bbp_verify_batch_aggregated(m, hi - lo, N, in + stride * lo, status + lo, group, &nfb[m->member_index]);
-    });
-    if (n_fallback) {
-        *n_fallback = 0;
-        for (uint32_t v : nfb) *n_fallback += v;
-    }
-    return rc;
-}
-
-// mixed-N rows: the same contiguous blocks by index, byte offsets from Ns
-int32_t pool_verify_batch_mixed(bbp_ctx* pool, uint32_t B, const uint32_t* Ns, const uint8_t* in, int32_t* status, bool aggregated, uint32_t group,
-                                uint32_t* n_fallback) {
-    std::vector<size_t> off((size_t)B + 1, 0);
-    for (uint32_t i = 0; i < B; i++) off[i + 1] = off[i] + verify_row_size(Ns[i]);
-    std::vector<uint32_t> nfb(pool->members.size(), 0);
-    const int32_t rc = for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
-        if (!aggregated) return bbp_verify_batch_mixed(m, hi - lo, Ns + lo, in + off[lo], status + lo);
-        return bbp_verify_batch_mixed_aggregated(m, hi - lo, Ns + lo, in + off[lo], status + lo, group, &nfb[m->member_index]);
-    });
-    if (n_fallback) {
-        *n_fallback = 0;
-        for (uint32_t v : nfb) *n_fallback += v;
-    }
-    return rc;
-}
-
-// rows of rounds: the same contiguous blocks by index; every member receives the whole round table
-int32_t pool_verify_rounds(bbp_ctx* pool, const VRounds& rd, uint32_t B, const uint8_t* rows, int32_t* status, bool aggregated, uint32_t group,
-                           uint32_t* n_fallback) {
-    std::vector<size_t> off((size_t)B + 1, 0);
-    for (uint32_t i = 0; i < B; i++) off[i + 1] = off[i] + round_row_size(rd.n_of(i));
-    std::vector<uint32_t> nfb(pool->members.size(), 0);
-    const int32_t rc = for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
-        const uint32_t* of = rd.round_of ? rd.round_of + lo : nullptr;
-        if (!aggregated) return bbp_verify_rounds(m, rd.R, rd.round_ns, rd.rounds, hi - lo, of, rows + off[lo], status + lo);
-        return bbp_verify_rounds_aggregated(m, rd.R, rd.round_ns, rd.rounds, hi - lo, of, rows + off[lo], status + lo, group, &nfb[m->member_index]);
+    const int32_t rc = for_each_block(pool, rows.B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
+        return verify_host(m, rows.slice(lo, hi), in + off[lo], status + lo, group, &nfb[m->member_index]);
     });
     if (n_fallback) {
         *n_fallback = 0;

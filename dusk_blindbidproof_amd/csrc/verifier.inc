@@ -603,20 +603,21 @@ static int vlane_of(const bbp_ctx* ctx, hipStream_t s) {  // a lane's own stream
     return 0;
 }
 
-// ns (host, B entries): a mixed-N call (verifier_mixed.inc): row i is bbp_verify_batch's row for N = ns[i], rows packed back to back;
-// N and rec_ver are then unused.  vers (host, B bytes, with ns only): the record layout of every row, 0 compact / 1 two-phase; null =
-// compact records only.  Strides are those of the largest N; the launches are the same in number.
-// rd (bbp_verify_rounds*, with neither ns nor vers): in_dev holds rows of record || score || z_img, seed and bid list come from
-// rd->rounds (device memory).  One round runs the uniform front end behind k_vparse_round, several the mixed one behind
-// k_vparse_rounds_mx with every row's N taken from its round; N is unused either way.
-int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                            const u32* ns, const u8* vers, const VRounds* rd) {
+// v: what the rows at in_dev are (verify_rows.h).  A mixed front end runs with the strides of the largest N, the launches the same in
+// number; a rounds call takes seed and bid list from v.rounds (device memory) -- one round behind k_vparse_round, several behind
+// k_vparse_rounds_mx with every row's N taken from its round.
+int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
     const CircuitDev* cp;
     int32_t rc;
     MixedCall mx;
-    std::vector<u32> rd_ns, rd_off;  // rounds: N of every row (several rounds only), scalar offset of every round in the table
+    const u32 B = v.B, N = v.front_n(), rec_ver = v.rec_ver;  // rec_ver: only the launch geometry below reads it (the largest count of active points)
+    const bool mixed = v.mixed_front();
+    const u32* ns = v.ns;
+    const u8* vers = v.vers;
+    const VerifyRows* rd = v.kind == VerifyRows::ROUNDS ? &v : nullptr;
+    std::vector<u32> rd_off;  // rounds: scalar offset of every round in the table
     if (rd) {
         rd_off.resize((size_t)rd->R + 1);
         u64 total = 0;
@@ -629,21 +630,10 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
             return BBP_ERR_BAD_ARG;
         }
         rd_off[rd->R] = (u32)total;
-        rec_ver = 0;
-        if (rd->R == 1)
-            N = rd->round_ns[0];
-        else {
-            rd_ns.resize(B);
-            for (u32 i = 0; i < B; i++) rd_ns[i] = rd->n_of(i);
-            ns = rd_ns.data();
-        }
     }
-    if (ns) {
-        if ((rc = mixed_prepare(ctx, B, ns, mx))) return rc;
+    if (mixed) {
+        if ((rc = mixed_prepare(ctx, v, mx))) return rc;
         cp = &mx.cmax;
-        rec_ver = 0;  // ... unless a row says otherwise: only the launch geometry below reads it (the largest count of active points)
-        if (vers)
-            for (u32 i = 0; i < B && !rec_ver; i++) rec_ver = vers[i] ? 1u : 0u;
     } else if ((rc = circuit_get(ctx, N, &cp)))
         return rc;
     const CircuitDev& c = *cp;
@@ -664,9 +654,9 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     size_t o_vpts = take((size_t)B * np * 32), o_vchal = take((size_t)B * VC_COUNT * 32), o_vs = take((size_t)B * 4098 * 32),
            o_tab = take((size_t)B * np * 8 * sizeof(ge)), o_var = take((size_t)B * np * sizeof(ge)), o_fixed = take((size_t)B * sizeof(ge)),
            o_sp = take((size_t)B * np * 32);
-    const size_t o_rows = ns ? take((size_t)B * sizeof(VRow)) : 0, o_ns = ns && !rd ? take((size_t)B * 5) : 0;  // Ns, then the version bytes
+    const size_t o_rows = mixed ? take((size_t)B * sizeof(VRow)) : 0, o_ns = mixed && !rd ? take((size_t)B * 5) : 0;  // Ns, then the version bytes
     // rounds: round_of (several rounds only) and the R + 1 round offsets behind it; the reduced round block; the per-round flags
-    const u32 rd_S = rd ? rd_off[rd->R] : 0, rd_nof = rd && ns ? B : 0;
+    const u32 rd_S = rd ? rd_off[rd->R] : 0, rd_nof = rd && mixed ? B : 0;
     const size_t o_rof = rd ? take(4 * ((size_t)rd_nof + rd->R + 1)) : 0, o_rblk = rd ? take((size_t)rd_S * sizeof(sc)) : 0,
                  o_rflag = rd ? take(4 * (size_t)rd->R) : 0;
     if ((rc = dev_reserve(ctx, L.misc, off))) return rc;
@@ -685,8 +675,8 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     if (rd) {
         if ((rc = stage_host(ctx, L, rd->round_of, 4 * (size_t)rd_nof, rd_off.data(), 4 * ((size_t)rd->R + 1), base + o_rof, s))) return rc;
         LAUNCH(ctx, TAG_TRANSCRIPT, k_round_consts, cdiv(rd_S, 64), 64, s, rd->R, roff_dev, rd->rounds, (sc*)(base + o_rblk), (int32_t*)(base + o_rflag));
-        if (ns) LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows_rounds, 1, VROWS_BLK, s, B, round_of_dev, roff_dev, (VRow*)(base + o_rows));
-    } else if (ns) {
+        if (mixed) LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows_rounds, 1, VROWS_BLK, s, B, round_of_dev, roff_dev, (VRow*)(base + o_rows));
+    } else if (mixed) {
         if ((rc = stage_host(ctx, L, ns, 4 * (size_t)B, vers, vers ? (size_t)B : 0, base + o_ns, s))) return rc;
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, 1, VROWS_BLK, s, B, (const u32*)(base + o_ns), vers ? (const u8*)(base + o_ns + 4 * (size_t)B) : nullptr,
                (VRow*)(base + o_rows));
@@ -704,7 +694,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     const bool vb2 = vb_force ? vb_force == 2 : B < 4096;
     if (vb2) Q = 1;
     auto launch_varbase = [&](hipStream_t st, u32 agg_flag) -> int32_t {
-        if (ns) {
+        if (mixed) {
             if (vb2) {
                 LAUNCH(ctx, TAG_VARBASE, k_varprep_mx, cdiv(B * npa, 64), 64, st, B, npa, np, rows, vpts, vchal, bd.misc, bd.wv, m, tab, sp, status_dev,
                        agg_flag);
@@ -732,12 +722,12 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     constexpr int ko = 0;
 #endif
     LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);
-    if (rd && ns)
+    if (rd && mixed)
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_rounds_mx, cdiv(B, 64), 64, s, B, rows, round_of_dev, roff_dev, np * 8, c.n_cst, in_dev, rblk, rflag, vpts,
                vchal, bd.cst, status_dev);
     else if (rd)
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_round, cdiv(B, 64), 64, s, B, N, c.n_cst, in_dev, rblk, rflag, vpts, vchal, bd.cst, status_dev);
-    else if (ns)
+    else if (mixed)
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_mx, cdiv(B, 64), 64, s, B, rows, np * 8, c.n_cst, in_dev, vpts, vchal, bd.cst, status_dev);
     else
         LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse, cdiv(B, 64), 64, s, B, N, c.n_cst, rec_ver, in_dev, vpts, vchal, bd.cst, status_dev);
@@ -746,7 +736,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
         static const int fence = getenv("BBP_V_FENCE") ? atoi(getenv("BBP_V_FENCE")) : 0;
         const u32 vtw = B <= (u32)ctx->tr_wave_below ? 1u : 0u;  // the replay of a few proofs: a wavefront each (as the prover's transcript kernels)
         if (ko & 4) {
-        } else if (ns) {
+        } else if (mixed) {
             u32 hog = lds_token(ctx);
             if (fence && ctx->serial_lds > 0 && (rc = serial_lds_bytes(ctx, (const void*)k_vtranscript_mx, &hog))) return rc;
             LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript_mx, vtw ? B : cdiv(B, 64), 64, hog, s, B, rows, np * 8, prefix, vpts, ent_dev, vchal, bd.misc,
@@ -759,7 +749,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
             LAUNCH(ctx, TAG_TRANSCRIPT, k_vtranscript, vtw ? B : cdiv(B, 64), 64, s, B, m, prefix, vpts, ent_dev, vchal, bd.misc, status_dev, vtw);
     }
     if (!(ko & 32)) {
-        if (ns)
+        if (mixed)
             LAUNCH(ctx, TAG_POLY, k_powers_mx, cdiv(B * cdiv(c.n_cons + 1, 32), 64), 64, s, B, cdiv(c.n_cons + 1, 32), rows, mx.ctab, bd.misc, (int)MS_Z,
                    bd.zpow, c.n_cons + 1);
         else
@@ -768,7 +758,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     }
     const u32 n_tgt = 3 * n1 + m;
     if (ko & 8) {
-    } else if (ns)
+    } else if (mixed)
         LAUNCH(ctx, TAG_POLY, k_flatten_mx, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, rows, mx.ctab, bd.zpow, c.n_cons + 1, bd.wl, bd.wr, bd.wo, bd.wv, m);
     else
         LAUNCH(ctx, TAG_POLY, k_flatten, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, c.n_cons + 1, bd.wl, bd.wr,
@@ -787,7 +777,7 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
         BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vjoin, vs_stream));
     }
     if (ko & 16) {
-    } else if (ns)
+    } else if (mixed)
         LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars_mx, B, VS_BLK, s, rows, mx.ctab, c.n_cst, c.n_cons + 1, bd.cst, bd.zpow, bd.yipow, bd.wl, bd.wr, bd.wo,
                vchal, bd.misc, bd.a, vs, G ? 1u : 0u);
     else
@@ -832,19 +822,20 @@ int32_t verify_batch_dev_ex(bbp_ctx* ctx, u32 B, u32 N, u32 rec_ver, u32 G, cons
     return BBP_OK;
 }
 
-int32_t verify_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
-    return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, nullptr, nullptr, nullptr);
-}
-
 // Aggregated verification with exact per-proof statuses: groups of G proofs are checked with one weighted MSM each; the members
 // of every group that fails then get an MSM of their own over the (weighted) scalars the group pass left in memory -- no second
 // parse / transcript / scalar pass.  Entirely stream-ordered: which groups failed is decided on the device (k_compact_failing),
 // and the fallback kernels are launched for up to B proofs and size themselves from the device counter.  *n_fallback
 // (optional) receives the number of proofs that were checked individually -- asking for it synchronises `s`.
-int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
-                             u32* n_fallback, u32* total_out_dev, const u32* ns, const VRounds* rd) {
+int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
+                             u32* n_fallback, u32* total_out_dev) {
     if (n_fallback) *n_fallback = 0;
-    if (G <= 1) return verify_batch_dev_ex(ctx, B, N, 0, 0, in_dev, ent_dev, status_dev, s, ns, nullptr, rd);
+    if (v.rec_ver) {  // aggregation: compact records only (the host path runs such a call plain)
+        ctx->err = "aggregated verification takes compact records only";
+        return BBP_ERR_BAD_ARG;
+    }
+    if (G <= 1) return verify_batch_dev(ctx, v, 0, in_dev, ent_dev, status_dev, s);
+    const u32 B = v.B;
     int32_t rc;
     const int lane = vlane_of(ctx, s);
     bbp_ctx::VLane& L = ctx->vl[lane];
@@ -867,9 +858,9 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, u32 B, u32 N, u32 G, const u8* in_dev
     };
     const size_t o_fx = take((size_t)B * sizeof(ge)), o_idx = take(4 * (size_t)B);
     if ((rc = dev_reserve(ctx, L.agg_io, off))) return rc;
-    if ((rc = verify_batch_dev_ex(ctx, B, N, 0, G, in_dev, ent_dev, status_dev, s, ns, nullptr, rd))) return rc;  // aggregation: compact records only
+    if ((rc = verify_batch_dev(ctx, v, G, in_dev, ent_dev, status_dev, s))) return rc;
     const CircuitDev* cp;  // idx_ver is the same list for every N: any compiled circuit of the call serves
-    if ((rc = circuit_get(ctx, rd ? rd->n_of(0) : ns ? ns[0] : N, &cp))) return rc;
+    if ((rc = circuit_get(ctx, v.first_n(), &cp))) return rc;
     u8* base = static_cast<u8*>(L.agg_io.p);
     u32* idx_dev = (u32*)(base + o_idx);
     StreamGuard guard(ctx, s, 1 + lane);

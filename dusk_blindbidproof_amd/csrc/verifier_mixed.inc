@@ -705,14 +705,14 @@ struct MixedCall {
     CircuitDev cmax;  // the call's strides: every size field the largest over its N; idx_ver (the same list for every N) of one of them
     const VCirc* ctab = nullptr;
 };
-// Compiles every N of the call on first use (as the uniform calls do) and fills its entry of ctx->vctab.  Ns are host memory and
-// screened by the caller; checked again here because they index the device table.
-static int32_t mixed_prepare(bbp_ctx* ctx, u32 B, const u32* ns, MixedCall& mx) {
+// Compiles every N of the call on first use (as the uniform calls do) and fills its entry of ctx->vctab.  The rows' Ns are host
+// memory and screened by the caller; checked again here because they index the device table.
+static int32_t mixed_prepare(bbp_ctx* ctx, const VerifyRows& v, MixedCall& mx) {
     if (!ctx->vctab) BBP_HIP_TRY(ctx, hipMalloc(&ctx->vctab, sizeof(VCirc) * (BBP_MAX_ITEMS + 1)));
     bool seen[BBP_MAX_ITEMS + 1] = {};
     bool first = true;
-    for (u32 i = 0; i < B; i++) {
-        const u32 n = ns[i];
+    for (u32 i = 0; i < v.B; i++) {
+        const u32 n = v.n_of(i);
         if (n == 0 || n > BBP_MAX_ITEMS) {
             ctx->err = "mixed verification: bid-list length out of range";
             return BBP_ERR_BAD_ARG;

@@ -8,6 +8,7 @@
 #include "../dusk_blindbidproof_amd/csrc/keccak_wave.h"
 #include "../dusk_blindbidproof_amd/csrc/point.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
+#include "../dusk_blindbidproof_amd/csrc/verify_rows.h"
 #include "../dusk_blindbidproof_amd/csrc/witness.h"
 
 using namespace bbp;
@@ -218,6 +219,36 @@ int hc_witness_gates(uint32_t n_items, const uint8_t* in_raw, const uint8_t* mim
         memcpy(out_native + 32 * i, b[i].v, 32);
     }
     return (int)c.n_mul;
+}
+
+// The row-layout descriptor of the verify calls (csrc/verify_rows.h), built by its own constructors -- kind 0: uniform(B, N, rec_ver),
+// 1: mixed(B, ns, vers), 2: of_rounds(B, R, round_ns, table, round_of) -- and cut to rows [lo, hi) when lo <= hi <= B (lo > hi: the
+// call itself).  out_n / out_ver: one entry per row; out_off: one more (offsets()).  info: 0 B, 1 rec_ver, 2 vers kept, 3 mixed front
+// end, 4 front_n (uniform front end only), 5 R, 6 the table pointer, 7 table_bytes, 8 round_of kept, 9 round_of's distance from the
+// caller's array in entries, 10 first_n (B > 0 only).
+void hc_verify_rows(int kind, uint32_t B, uint32_t N, uint32_t rec_ver, const uint32_t* ns, const uint8_t* vers, uint32_t R, const uint32_t* round_ns,
+                    const uint8_t* table, const uint32_t* round_of, uint32_t lo, uint32_t hi, uint32_t* out_n, uint32_t* out_ver, uint64_t* out_off,
+                    uint64_t* info) {
+    VerifyRows v = kind == 0 ? VerifyRows::uniform(B, N, rec_ver) : kind == 1 ? VerifyRows::mixed(B, ns, vers) : VerifyRows::of_rounds(B, R, round_ns, table, round_of);
+    if (lo <= hi) v = v.slice(lo, hi);
+    const std::vector<size_t> off = v.offsets();
+    for (uint32_t i = 0; i < v.B; i++) {
+        out_n[i] = v.n_of(i);
+        out_ver[i] = v.ver_of(i);
+        if (off[i + 1] - off[i] != v.row_bytes(i)) out_n[i] = 0xffffffffu;  // reported as a wrong N
+    }
+    for (size_t i = 0; i < off.size(); i++) out_off[i] = off[i];
+    info[0] = v.B;
+    info[1] = v.rec_ver;
+    info[2] = v.vers != nullptr;
+    info[3] = v.mixed_front();
+    info[4] = v.mixed_front() ? 0 : v.front_n();
+    info[5] = v.R;
+    info[6] = (uint64_t)(uintptr_t)v.rounds;
+    info[7] = v.table_bytes();
+    info[8] = v.round_of != nullptr;
+    info[9] = v.round_of ? (uint64_t)(v.round_of - round_of) : 0;
+    info[10] = v.B ? v.first_n() : 0;
 }
 
 // The bit-interleaved form the one-wavefront Keccak keeps its words in (keccak_wave.h): even / odd bits of x as two 32-bit halves.

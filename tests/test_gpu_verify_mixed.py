@@ -278,6 +278,18 @@ def test_argument_screening(ctx, bbp, anchor):
     assert list(st) == [55]
 
 
+@pytest.mark.parametrize("chunk", [16, 1])
+def test_host_chunks_cut_a_mixed_call(ctx, anchor, monkeypatch, chunk):
+    """BBP_HOST_CHUNK_VERIFY is read at every call.  The 40 shuffled rows of five list lengths in chunks of 14, 14 and 12 rows
+    (40 / ceil(40 / 16)), every chunk edge between rows of different N and so at a byte offset no row stride gives; chunks of one
+    row as the extreme.  The aggregated form cuts its groups per chunk: same statuses, no claim about its fallback count."""
+    Ns, blob, oracle = anchor
+    assert len(Ns) == 40 and Ns[13] != Ns[14] and Ns[27] != Ns[28]
+    monkeypatch.setenv("BBP_HOST_CHUNK_VERIFY", str(chunk))
+    assert ctx.verify_batch_mixed(Ns, blob) == oracle
+    assert ctx.verify_batch_mixed_aggregated(Ns, blob, 4)[0] == oracle
+
+
 def test_pool_matches_single_context(ctx, scale, anchor, bbp):
     p = bbp.Pool([0, 0])
     try:
