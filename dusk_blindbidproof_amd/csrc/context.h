@@ -17,6 +17,7 @@
 
 #include "../../include/bbp.h"
 #include "point.h"
+#include "prove_plan.h"
 #include "scalar.h"
 #include "verify_rows.h"
 
@@ -45,7 +46,7 @@ constexpr int MSM_LOG_G = MSM_T == 128 ? 3 : 4;
 static_assert(MSM_T == 128 || MSM_T == 64, "the cross-lane fold is written for one or two wavefronts");
 // IPA tail (prover.hip): from round FOLD_ROUND the folded generators are explicit points; they are materialised by a
 // composite-bucket Pippenger pass over the same row table (msm.hip, the <1> instances of k_msm_sort / k_msm_acc)
-constexpr int FOLD_ROUND = 7;              // first tail round: vectors of length 32 (halves of 16)
+// (FOLD_ROUND, the first tail round, is prove_plan.h's: the plan of a prove call names it)
 constexpr int FOLD_CLS = 2048 >> (FOLD_ROUND - 1);  // 32 folded generators per side
 constexpr int FOLD_NAF = 9;                // width-9 NAF: odd digits |d| < 256
 constexpr int FOLD_W = 29;                 // most digits per scalar
@@ -99,57 +100,25 @@ struct bbp_ctx {
     hipStream_t side = nullptr;            // opening stage of the prover pipeline (prover.hip)
     hipStream_t copy = nullptr;            // the caller's ingest stream (bbp_context_copy_stream): never used by the engine
     hipStream_t side2 = nullptr;           // second opening stream: batches too small to fill three heavy slices alternate between the two
+    bbp::ProveKnobs knobs;                 // how prove calls are scheduled (prove_plan.h): read from the environment by bbp_init ...
+    bbp::ProveRuleState prove_state;       // ... and what the rules remember from call to call; prover.hip plans every call from the two
     int varbase_lanes = 65536;             // lanes the verifier's variable-base kernel is launched with (BBP_VARBASE_LANES): ~1 wave per SIMD
-    int rotate_below = 1023;               // batches of at most this many proofs run their heavy stage unsliced on a rotating internal stream (BBP_ROTATE_BELOW, 0 = never)
-    int rotate_deep_max = 4096;            // calls of up to this many proofs issued while deep_from or more earlier prove calls are still in flight take the rotating path too (BBP_ROTATE_DEEP_MAX, 0 = never; never with BBP_SLICES=1)
-    bool deep_mode = false, force_deep = false;  // (state of that rule; force_deep: bbp_reserve warming the rotating path's buffers)
-    int deep_idle_seen = 0;
     std::vector<hipStream_t> spare_streams;  // (experiment BBP_VL_SKIP: placeholders in the hardware-queue round-robin)
-    bool trace_prove = false;              // BBP_TRACE_PROVE: one stderr line per prove call with the schedule it took
     static constexpr int CALL_RING = 8;
     hipEvent_t ev_call[CALL_RING] = {};    // completion of the last CALL_RING prove calls (how many are still in flight)
     bool ev_call_valid[CALL_RING] = {};
-    int deep_from = 3;                     // earlier prove calls in flight that switch a caller to the rotating path (BBP_ROTATE_DEEP_FROM)
-    int mixed_from = 512;                  // ... but a batch of at least this many proofs that arrives while a sliced heavy stage is in flight takes the sliced path too (BBP_ROTATE_MIXED_FROM, 0 = never)
     int last_prove_par = -1;               // buffer of the last prove call (last_par is also set by the verifier lanes)
-    bool last_sliced = false;              // the last prove call's heavy stage ran as slices on the caller's stream + lanes
-    int dual_open_below = 1024;            // batches smaller than this open on alternating streams (BBP_DUAL_OPEN_BELOW, 0 = never)
-    static constexpr int MAX_SLICES = 4;   // heavy-stage slices of one batch, one stream each (slice 0 = caller's stream)
+    static constexpr int MAX_SLICES = bbp::PROVE_MAX_SLICES;  // heavy-stage slices of one batch, one stream each (slice 0 = caller's stream)
     hipStream_t lane[MAX_SLICES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_join[MAX_SLICES] = {nullptr, nullptr, nullptr, nullptr}, ev_stagger[MAX_SLICES] = {nullptr, nullptr, nullptr, nullptr};
-    int slices = 3;
     int sort_staged = 3;       // bit 0: generic MSMs, bit 1: the generator-fold pass sort with the scatter staged through LDS (msm.hip k_msm_sort_staged; BBP_SORT_STAGED)
     bool sort_lds_attr = false; // k_msm_sort_staged's dynamic-LDS limit has been raised on this context's device
     bool sort_lds_attr1 = false;  // ... and that of the generator-fold instance
     int debug_corrupt = 0;      // bbp_debug_corrupt_scratch: poison the next MSM launch's sorted scratch (tests)
     int fold_half_from = 512;  // MSM launches with at least this many MSMs fold on half a wavefront per MSM (msm.hip k_msm_fold_half; BBP_FOLD_HALF_FROM)
-    int tail_small_below = 65;    // heavy stages of fewer proofs than this keep ALL eleven IPA rounds on the fixed-base MSM kernels: a short chain of
-                                  // launches that fill the GPU by splitting beats the generator fold + table + tail kernels when latency is what counts
-                                  // (one proof 24.7 -> 23.5 ms, 8 proofs 26.2 -> 23.8, 64 proofs 30.2 -> 29.3; 256 proofs 38.9 -> 40.9: not there).  BBP_TAIL_SMALL_BELOW
-    int tail_round = bbp::FOLD_ROUND;  // first IPA round run on explicit folded generators (BBP_TAIL_ROUND=12 disables)
-    int serial_lds = 160 * 1024;  // LDS the one-lane-per-proof opening kernels reserve to keep their CU to themselves (BBP_SERIAL_LDS, 0 = off)
-    // TranscriptRng draw chain on 25 lanes per sponge (k_open_bulk) instead of one lane per proof.  The cooperative form is bound
-    // by the CU's LDS crossbar (18 ds_bpermute per round): with ONE wavefront (two proofs) per CU a permutation takes a third of
-    // the single-lane time -- a single proof 44 -> 25 ms, 256 proofs 55 -> 41 ms -- but 1024 proofs would need 512 CUs' worth of
-    // crossbar, and the single-lane chain hides under the previous batch's MSM stage anyway.  Auto (-1): cooperative for batches
-    // of at most rng_coop_below proofs (768; with four wavefronts per CU a 512-proof chain takes ~15 ms on 64 CUs).  BBP_RNG_COOP=0 / 1 forces, BBP_RNG_COOP_BELOW, BBP_RNG_BLOCK tune.
-    int rng_coop = -1;
-    int rng_coop_below = 768;
-    int tr_wave_below = 32;          // launches of at most this many proofs run the transcript kernels with one proof per wavefront and the permutations spread over its lanes (BBP_TR_WAVE_BELOW, 0 = never)
-    int ipa_wide_below = 32;         // launches of at most this many proofs run k_ipa_round on 1024 lanes per proof instead of 256 (BBP_IPA_WIDE_BELOW, 0 = never)
-    int commit_split_below = 1024;   // Pedersen-commitment launches of at most this many commitments put each on eight lanes (prover.hip k_commit_split; BBP_COMMIT_SPLIT_BELOW, 0 = never)
-    int witness_native = 1;          // the witness blocks of the cooperative opening launches write the gates from the gadget wiring itself instead of interpreting the compiled program (BBP_WITNESS_NATIVE=0)
     int msm_small = 1;               // split MSMs (launches of fewer than 128) use width-9 digits and 128 buckets (msm.hip msm_geom<2>); BBP_MSM_SMALL=0: 1024 like the others
-    int rng_coop_idle_below = 2300;  // ... and up to this many proofs when the call finds the device without an earlier prove call (BBP_RNG_COOP_IDLE_BELOW; 0: never)
-    int rng_dpp = 2;              // cooperative chain on one wavefront per proof: 2 = one half-word per lane, bit-interleaved (k_open_bulk50, keccak_wave.h); BBP_RNG_DPP=1: one word per lane, DPP / permlane-swap theta (k_open_bulk8); 0: the 25-lane ds_bpermute form (k_open_bulk)
-    int rng_block = 0;            // threads per workgroup of k_open_bulk (BBP_RNG_BLOCK); 0 = by batch size: 64 (one wavefront = two proofs per reserved CU) up to 128 proofs, 128 up to 256, 256 above
-    int serial_block = 64;        // threads per workgroup of those kernels: 256 = one serial wave per SIMD of the reserved CU (BBP_SERIAL_BLOCK)
     std::map<const void*, int> serial_attr;
-    int stagger_mode = 0;  // 0: slices start together, 1: next slice starts after this slice's first MSM, 3: after its third (BBP_STAGGER)
-#ifndef BBP_PROVE_BUFS
-#define BBP_PROVE_BUFS 5
-#endif
-    static constexpr int PROVE_BUFS = BBP_PROVE_BUFS;  // prover batch buffers in rotation (call k of the small-batch path uses buffer k % PROVE_BUFS; large batches alternate between 0 and 1)
+    static constexpr int PROVE_BUFS = bbp::PROVE_BUFS;  // prover batch buffers in rotation (call k of the small-batch path uses buffer k % PROVE_BUFS; large batches alternate between 0 and 1)
     hipEvent_t ev_open[PROVE_BUFS] = {}, ev_done[PROVE_BUFS] = {};
     hipEvent_t ev_entry[PROVE_BUFS] = {};  // caller's stream at entry of a prove call: out_dev is not written before it
     bool ev_done_valid[PROVE_BUFS] = {}, ev_open_valid[PROVE_BUFS] = {};
@@ -173,7 +142,6 @@ struct bbp_ctx {
     std::atomic<int> entropy_source{BBP_ENTROPY_SOURCE_OS};
     bool debug_key_armed = false;  // bbp_debug_next_entropy_key: the next device draw of a host-pointer call uses debug_key
     uint8_t debug_key[32] = {};
-    uint32_t seq = 0;
     int last_par = 0;
     // calls on one context share scratch buffers: a call issued on a different caller stream than the previous one is ordered
     // behind it (stream_guard_enter / stream_guard_leave)
@@ -355,18 +323,18 @@ struct ScopedEvent {  // records start now, stop at scope exit, when profiling i
 };
 
 // see prover.hip "serial_lds_bytes": kernels that must not share a CU with the long-lived serial waves ask for a few bytes of LDS
-inline unsigned lds_token(const bbp_ctx* ctx) { return ctx->serial_lds >= 160 * 1024 ? 64u : 0u; }
+inline unsigned lds_token(const bbp_ctx* ctx) { return ctx->knobs.lds_token(); }
 
 // One-lane-per-item serial kernels that run beside the MSM stage ask for (nearly) a whole CU's LDS so that nothing else is placed
 // on their CU (prover.hip "Serial waves get their own CUs"): raise the kernel's dynamic-LDS limit once per kernel.
 inline int32_t serial_lds_bytes(bbp_ctx* ctx, const void* kernel, unsigned* dyn_bytes = nullptr) {
     if (dyn_bytes) *dyn_bytes = 0;
-    if (ctx->serial_lds <= 0) return BBP_OK;
+    if (ctx->knobs.serial_lds <= 0) return BBP_OK;
     if (!ctx->serial_attr.count(kernel)) {
         // the reservation is dynamic LDS on top of whatever the kernel declares statically: together they must fit the CU's 160 KB
         hipFuncAttributes fa;
         BBP_HIP_TRY(ctx, hipFuncGetAttributes(&fa, kernel));
-        int dyn = ctx->serial_lds - (int)fa.sharedSizeBytes;
+        int dyn = ctx->knobs.serial_lds - (int)fa.sharedSizeBytes;
         if (dyn < 0) dyn = 0;
         BBP_HIP_TRY(ctx, hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, dyn));
         ctx->serial_attr[kernel] = dyn;

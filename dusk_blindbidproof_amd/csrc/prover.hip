@@ -301,7 +301,7 @@ int32_t commit_launch(bbp_ctx* ctx, u32 count, const sc* values, const sc* blind
                       ge* out, u32 out_stride, hipStream_t s) {
     if (!count) return BBP_OK;
     ScopedEvent ev(ctx, TAG_COMMIT, s);
-    if (count <= (u32)ctx->commit_split_below) {
+    if (count <= (u32)ctx->knobs.commit_split_below) {
         hipLaunchKernelGGL(k_commit_split, dim3((count * COMMIT_L + 63) / 64), dim3(64), 0, s, count, per_proof, values, blindings, stride_v, stride_b,
                            ctx->comb, out, out_stride);
         BBP_HIP_TRY(ctx, hipGetLastError());
@@ -1637,7 +1637,7 @@ int32_t tail_btab_build(bbp_ctx* ctx) {  // called once from bbp_init: the table
 }
 
 static BatchDev batch_view(const BatchDev& bd, const CircuitDev& c, u32 first);
-static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
+static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
                            hipEvent_t stagger, hipEvent_t out_guard);
 
 // in_dev: B * (7*32 + N*32 + 8) ; ent_dev: B * (32 m + 32) ; out_dev: B * (1121 + 32 m).  All device pointers.
@@ -1657,7 +1657,12 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     // opening (side) -> heavy stage (caller stream); a buffer is reused only after its previous heavy stage has finished.
     StreamGuard guard(ctx, s);
     if ((rc = guard.enter())) return rc;
-    const u32 call = ctx->seq++;
+    // 1. Earlier prove calls still on the device: a ring of per-call completion events (the buffers' own events say nothing beyond
+    // two calls while the calls are sliced: those alternate between two buffers)
+    int inflight = 0;
+    for (int k = 0; k < bbp_ctx::CALL_RING; k++)
+        if (ctx->ev_call_valid[k] && hipEventQuery(ctx->ev_call[k]) == hipErrorNotReady) inflight++;
+    // 2. The plan (prove_plan.h states the rules).  Why they are what they are:
     // Batches too small to fill three heavy slices are bound by the opening stage (its rng chain lasts ~40 ms whatever the
     // batch size), so their openings alternate between two streams and two of them are in flight at once; the heavy stage
     // is then cut in at most two slices so that no more than four queues are active (a fifth costs ~7 %).
@@ -1665,159 +1670,131 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     // chain would run beside that batch's three slices -- a fourth and fifth busy heavy stream -- and both lose.  Two host threads
     // alternating 870- and 2202-proof batches (what the combiner's two batch threads settle into under closed-loop load): 18.8 k
     // proofs/s that way, 21.6 k with the 870 sliced and stream-ordered behind the 2202 like any large batch (tools/host_pairs.py).
-    // A caller that keeps TWO OR MORE earlier prove calls in flight (device API, calls enqueued without host synchronisation) is
+    // A caller that keeps THREE OR MORE earlier prove calls in flight (device API, calls enqueued without host synchronisation) is
     // better served by whole calls in rotation than by slices of one call, whatever the batch size: three unsliced chains of three
-    // calls, each with its opening stage behind it, out of phase by construction (five buffers: context.h).  1024-proof calls back
+    // calls, each with its opening stage behind it, out of phase by construction (five buffers: with three, call k's opening had to
+    // wait for call k-3's heavy stage -- the chain on the very stream call k's heavy stage is queued on -- and every chain stream
+    // idled for an opening stage per call: 24 % at 256 proofs per call).  1024-proof calls back
     // to back: 48.8 ms per call sliced, 45.9-46.7 in rotation (21.0 k -> 21.9-22.3 k proofs/s); 2048: 90.4 -> 87.2 ms.  With at most
     // one earlier call in flight (the host-pointer path under the combiner's two batch threads) slices win: 21.4 k against 17.9 k.
-    int inflight = 0;  // earlier prove calls still on the device: a ring of per-call completion events (the buffers' own events say
-                       // nothing beyond two calls while the calls are sliced: those alternate between two buffers)
-    for (int k = 0; k < bbp_ctx::CALL_RING; k++)
-        if (ctx->ev_call_valid[k] && hipEventQuery(ctx->ev_call[k]) == hipErrorNotReady) inflight++;
-    // (sticky: entered with two earlier calls in flight, left after six calls in a row that found fewer -- a caller that
-    // synchronises now and then, bench.py's barriers around its timed loop, does not fall back to slices for the calls that refill
-    // its pipeline; the combiner's two batch threads never enter, and leave within six batches if a third caller once made them)
-    if (inflight >= ctx->deep_from) {
-        ctx->deep_mode = true;
-        ctx->deep_idle_seen = 0;
-    } else if (++ctx->deep_idle_seen >= 6) {
-        ctx->deep_mode = false;
-    }
-    const bool deep = (ctx->deep_mode || ctx->force_deep) && ctx->slices > 1 && ctx->rotate_deep_max > 0 && B <= (u32)ctx->rotate_deep_max;
-    bool behind_sliced = false;
-    if (!deep && ctx->mixed_from > 0 && B >= (u32)ctx->mixed_from && ctx->last_sliced && ctx->last_prove_par >= 0 && ctx->ev_done_valid[ctx->last_prove_par])
-        behind_sliced = hipEventQuery(ctx->ev_done[ctx->last_prove_par]) == hipErrorNotReady;
-    const bool dual = !behind_sliced && (deep || B < (u32)(ctx->dual_open_below > 0 ? ctx->dual_open_below : 0));
-    const int sidx = dual ? (int)(call & 1u) : 0;
-    const int par = dual ? (int)(call % (u32)bbp_ctx::PROVE_BUFS) : (int)(call & 1u);  // three heavy-stage chains + two openings in flight: five buffers.  (With three, call k's opening had to wait for call k-3's heavy stage -- the chain that runs on the very stream call k's heavy stage is queued on -- and every chain stream idled for an opening stage per call: 24 % at 256 proofs per call.)
-    if (dual && !ctx->side2) BBP_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking));
+    // (Deep mode is sticky so that a caller that synchronises now and then, bench.py's barriers around its timed loop, does not
+    // fall back to slices for the calls that refill its pipeline; the combiner's two batch threads never enter, and leave within
+    // six batches if a third caller once made them.)
+    // The draw chain takes a wavefront per proof always for small batches; for larger ones only when NO earlier prove call is on
+    // the device -- a lone 1024-proof call then returns after 58 instead of 81 ms, while a caller that keeps the device busy keeps
+    // the single-lane chain (a wavefront per proof costs a full pipeline 1-2 % of its throughput: two host threads 22.2 k -> 21.8 k
+    // proofs/s).  Its workgroup: one wavefront (two proofs) per reserved CU is the fastest chain, but at 256 proofs that reserves
+    // 128 CUs under the other in-flight calls' heavy stages; two wavefronts per CU there (measured 11.3 k -> 12.5 k proofs/s back to
+    // back), four above 256 proofs (384: 12.8 k -> 14.8 k, 512: 14.6 k -> 16.5 k against the single-lane chain).
+    const ProvePlan plan = plan_prove(ctx->knobs, ctx->prove_state, B, inflight, [&] {
+        const int lp = ctx->last_prove_par;
+        return lp >= 0 && ctx->ev_done_valid[lp] && hipEventQuery(ctx->ev_done[lp]) == hipErrorNotReady;
+    });
+    const int sidx = plan.open_stream, par = plan.par;
+    if (plan.dual && !ctx->side2) BBP_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking));
     BatchDev bd;
     if ((rc = batch_reserve(ctx, B, c, bd, par))) return rc;
     const u32 m = c.m, n1 = c.n_mul, encw = (m + 8 + 22) * 8;
     const merlin_transcript prefix = prover_prefix();
     const size_t n_draws = 3 + 2 * (size_t)n1;
     if ((rc = dev_reserve(ctx, ctx->raw[sidx], (size_t)B * n_draws * 64))) return rc;
-    hipStream_t main_s = s;
-    bool traced_coop = false;  // (BBP_TRACE_PROVE) the draw chain ran on a wavefront per proof
-    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_entry[par], main_s));
-    {
-        hipStream_t s = sidx ? ctx->side2 : ctx->side;  // opening stage
-        // NOTE the opening stage does NOT wait for the caller's stream: in_dev / ent_dev must be complete when the call is
-        // made (include/bbp.h).  Waiting on the caller's stream tail would serialise it behind the previous call's heavy stage.
-        if (ctx->ev_done_valid[par]) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_done[par], 0));
-        if (ctx->ev_prep_valid) {  // rows written by bbp_prepare_bids_dev since the last prove call
-            BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_prep, 0));
-            ctx->ev_prep_valid = false;
-        }
-        if (ctx->ev_draw_valid) {  // prove rows drawn by bbp_draw_entropy_dev since the last prove call
-            BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_draw, 0));
-            ctx->ev_draw_valid = false;
-        }
-        if (open_hook && (rc = (*open_hook)(s))) return rc;
-        LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);
-        // every launch asks for what serial_lds_bytes set the kernel's limit to (reservation minus the kernel's static LDS): the two
-        // cannot diverge when a kernel gains a __shared__ array
-        u32 hog = 0;
-        if ((rc = serial_lds_bytes(ctx, (const void*)k_open_serial, &hog))) return rc;
-        const u32 sblk = ctx->serial_lds > 0 ? (u32)ctx->serial_block : 64u;
-        LAUNCH(ctx, TAG_WITNESS, k_witness_head, cdiv(B, 64), 64, s, B, N, c.n_cst, in_dev, bd.cst, bd.v);
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_load_blindings, cdiv(B * m, 64), 64, s, B, m, ent_dev, bd.vb);
-        if ((rc = commit_launch(ctx, B * m, bd.v, bd.vb, m, m, m, bd.pts, m + 8, s))) return rc;
-        LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(B * m, 64), 64, s, B * m, m, bd.pts, m + 8, bd.enc, encw, 0u, 1u);
-        // one wavefront per proof for the draw chain: always for batches up to rng_coop_below proofs; for larger ones (up to
-        // rng_coop_idle_below) only when NO earlier prove call is on the device -- a lone 1024-proof call then returns after 58
-        // instead of 81 ms, while a caller that keeps the device busy keeps the single-lane chain (a wavefront per proof costs a
-        // full pipeline 1-2 % of its throughput: two host threads 22.2 k -> 21.8 k proofs/s)
-        const bool coop = ctx->rng_coop < 0 ? B <= (u32)ctx->rng_coop_below || (inflight == 0 && B <= (u32)ctx->rng_coop_idle_below) : ctx->rng_coop != 0;
-        traced_coop = coop;
-        u32 interleaved = 0;  // the draws' layout in `raw` (k_open_bulk50 writes bit-interleaved halves)
-        if (!coop) {
-            LAUNCH_LDS(ctx, TAG_RNG, k_open_serial, 2 * cdiv(B, sblk), sblk, hog, s, B, cdiv(B, sblk), m, n1, prefix, bd.enc, ent_dev, bd.vb,
-                       (u32*)ctx->raw[sidx].p, bd.tr, bd.rng, c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 0u);
-        } else {
-            // prefix: one lane per proof, ~20 permutations (V x m, "m", the rng's rekeys, the first draw): 0.3 ms, no witness blocks
-            if (B <= (u32)ctx->tr_wave_below)
-                LAUNCH(ctx, TAG_RNG, k_open_serial, B, 64, s, B, B, m, n1, prefix, bd.enc, ent_dev, bd.vb, (u32*)ctx->raw[sidx].p,
-                       bd.tr, bd.rng, c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 2u);
-            else
-                LAUNCH(ctx, TAG_RNG, k_open_serial, cdiv(B, 64), 64, s, B, cdiv(B, 64), m, n1, prefix, bd.enc, ent_dev, bd.vb, (u32*)ctx->raw[sidx].p,
-                       bd.tr, bd.rng, c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 1u);
-            // bulk: 32 lanes per proof for the draw chain + one lane per proof for the witness, in one launch of `cblk`-thread
-            // workgroups that keep their CU to themselves (LDS hog): cblk / 32 proofs per rng workgroup
-            // workgroup size: one wavefront (two proofs) per reserved CU is the fastest chain, but at 256 proofs that reserves 128 CUs
-            // under the other in-flight calls' heavy stages; two wavefronts per CU there (measured 11.3 k -> 12.5 k proofs/s back to back),
-            // four above 256 proofs (384: 12.8 k -> 14.8 k, 512: 14.6 k -> 16.5 k against the single-lane chain)
-            const u32 cblk = ctx->rng_block > 0 ? (u32)ctx->rng_block : (B <= 128 ? 64u : B <= 256 ? 128u : 256u);
-            if (ctx->rng_dpp) {
-                // one proof per wavefront (k_open_bulk50, or BBP_RNG_DPP=1: k_open_bulk8): the same number of proofs per reserved CU needs twice the lanes
-                const void* kfn = ctx->rng_dpp >= 2 ? (const void*)k_open_bulk50 : (const void*)k_open_bulk8;
-                u32 hog8 = 0;
-                if ((rc = serial_lds_bytes(ctx, kfn, &hog8))) return rc;
-                const u32 cblk8 = 2 * cblk > 1024u ? 1024u : 2 * cblk, nb_rng = cdiv(B * 64, cblk8), nb_wit = cdiv(B, cblk8);
-                if (ctx->rng_dpp >= 2) {
-                    interleaved = 1;
-                    LAUNCH_LDS(ctx, TAG_RNG, k_open_bulk50, nb_rng + nb_wit, cblk8, hog8, s, B, nb_rng, n1, 2 + 2 * n1, bd.rng, (u32*)ctx->raw[sidx].p, m,
-                               c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, hog8, (u32)ctx->witness_native);
-                } else {
-                    LAUNCH_LDS(ctx, TAG_RNG, k_open_bulk8, nb_rng + nb_wit, cblk8, hog8, s, B, nb_rng, n1, 2 + 2 * n1, bd.rng, (u32*)ctx->raw[sidx].p, m,
-                               c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, hog8, (u32)ctx->witness_native);
-                }
-            } else {
-                u32 hogb = 0;
-                if ((rc = serial_lds_bytes(ctx, (const void*)k_open_bulk, &hogb))) return rc;
-                const u32 nb_rng = cdiv(B * 32, cblk), nb_wit = cdiv(B, cblk);
-                LAUNCH_LDS(ctx, TAG_RNG, k_open_bulk, nb_rng + nb_wit, cblk, hogb, s, B, nb_rng, n1, 2 + 2 * n1, bd.rng, (u32*)ctx->raw[sidx].p, m,
-                           c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, hogb, (u32)ctx->witness_native);
-            }
-        }
-        LAUNCH(ctx, TAG_RNG, k_reduce_draws, cdiv((u32)(B * n_draws), 128), 128, s, B, n1, (const u32*)ctx->raw[sidx].p, bd.ai1, bd.ao1, bd.s1, interleaved);
-        BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_open[par], s));
-        ctx->ev_open_valid[par] = true;
+    u32* const raw = (u32*)ctx->raw[sidx].p;
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_entry[par], s));
+    // 3. OPENING stage, on `os`.  It does NOT wait for the caller's stream: in_dev / ent_dev must be complete when the call is made
+    // (include/bbp.h).  Waiting on the caller's stream tail would serialise it behind the previous call's heavy stage.
+    hipStream_t os = sidx ? ctx->side2 : ctx->side;
+    if (ctx->ev_done_valid[par]) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_done[par], 0));
+    if (ctx->ev_prep_valid) {  // rows written by bbp_prepare_bids_dev since the last prove call
+        BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_prep, 0));
+        ctx->ev_prep_valid = false;
     }
-    // HEAVY stage.  The batch is cut into slices (default 3, BBP_SLICES) that run the same kernel sequence on separate
-    // streams (slice 0 on the caller's -- a fifth concurrently active queue was measured 7 % slower): while one slice sits in a latency-bound step (the per-round transcript + scalar
-    // inversion in k_ipa_round, the small encode / commit kernels) the other half's MSM keeps the CUs busy.
-    u32 slices = B >= 64u * (u32)ctx->slices ? (u32)ctx->slices : (B >= 128 ? 2u : 1u);
-    if (dual && slices > 2) slices = 2;
-    const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (size_t)m;
-    // Small batches: a heavy stage of a few hundred proofs is a chain of ~110 mostly latency-bound launches that leaves most of
-    // the GPU idle (256 MSM workgroups for 1024 slots), and on the caller's stream the chains of consecutive calls run one
-    // after the other: 31 ms per 256-proof call whatever else is tuned.  Such calls therefore run their heavy stage UNSLICED on
+    if (ctx->ev_draw_valid) {  // prove rows drawn by bbp_draw_entropy_dev since the last prove call
+        BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_draw, 0));
+        ctx->ev_draw_valid = false;
+    }
+    if (open_hook && (rc = (*open_hook)(os))) return rc;
+    LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, os, B, c.n_cst, ctx->mimc_c, bd.cst);
+    // every launch asks for what serial_lds_bytes set the kernel's limit to (reservation minus the kernel's static LDS): the two
+    // cannot diverge when a kernel gains a __shared__ array
+    u32 hog = 0;
+    if ((rc = serial_lds_bytes(ctx, (const void*)k_open_serial, &hog))) return rc;
+    LAUNCH(ctx, TAG_WITNESS, k_witness_head, cdiv(B, 64), 64, os, B, N, c.n_cst, in_dev, bd.cst, bd.v);
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_load_blindings, cdiv(B * m, 64), 64, os, B, m, ent_dev, bd.vb);
+    if ((rc = commit_launch(ctx, B * m, bd.v, bd.vb, m, m, m, bd.pts, m + 8, os))) return rc;
+    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(B * m, 64), 64, os, B * m, m, bd.pts, m + 8, bd.enc, encw, 0u, 1u);
+    if (plan.coop) {
+        // prefix: one lane (or, for a few proofs, one wavefront) per proof, ~20 permutations (V x m, "m", the rng's rekeys, the first
+        // draw): 0.3 ms, no witness blocks
+        const u32 pgrid = plan.prefix_form == 2 ? B : cdiv(B, 64);
+        LAUNCH(ctx, TAG_RNG, k_open_serial, pgrid, 64, os, B, pgrid, m, n1, prefix, bd.enc, ent_dev, bd.vb, raw, bd.tr, bd.rng, c.n_cst, c.w_terms,
+               c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, plan.prefix_form);
+    }
+    // the cooperative chains: lanes for the draw chain + one lane per proof for the witness, in one launch of workgroups that keep
+    // their CU to themselves (LDS hog).  A wavefront per proof needs twice the lanes for the same number of proofs per reserved CU.
+    auto bulk = [&](decltype(&k_open_bulk) kern, u32 lanes, u32 blk) -> int32_t {
+        u32 hogb = 0;
+        if (int32_t rc = serial_lds_bytes(ctx, (const void*)kern, &hogb)) return rc;
+        const u32 nb_rng = cdiv(B * lanes, blk), nb_wit = cdiv(B, blk);
+        LAUNCH_LDS(ctx, TAG_RNG, kern, nb_rng + nb_wit, blk, hogb, os, B, nb_rng, n1, 2 + 2 * n1, bd.rng, raw, m, c.n_cst, c.w_terms, c.w_loff,
+                   c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, hogb, (u32)ctx->knobs.witness_native);
+        return BBP_OK;
+    };
+    switch (plan.chain) {
+        case ProvePlan::SERIAL:
+            LAUNCH_LDS(ctx, TAG_RNG, k_open_serial, 2 * cdiv(B, plan.serial_blk), plan.serial_blk, hog, os, B, cdiv(B, plan.serial_blk), m, n1, prefix,
+                       bd.enc, ent_dev, bd.vb, raw, bd.tr, bd.rng, c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 0u);
+            break;
+        case ProvePlan::LANES25: rc = bulk(k_open_bulk, 32, plan.cblk); break;
+        case ProvePlan::WORD: rc = bulk(k_open_bulk8, 64, plan.cblk_wave()); break;
+        case ProvePlan::HALFWORD: rc = bulk(k_open_bulk50, 64, plan.cblk_wave()); break;
+    }
+    if (rc) return rc;
+    // (k_open_bulk50 writes the draws as bit-interleaved halves)
+    LAUNCH(ctx, TAG_RNG, k_reduce_draws, cdiv((u32)(B * n_draws), 128), 128, os, B, n1, (const u32*)raw, bd.ai1, bd.ao1, bd.s1,
+           plan.chain == ProvePlan::HALFWORD ? 1u : 0u);
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_open[par], os));
+    ctx->ev_open_valid[par] = true;
+    if (ctx->knobs.trace_prove) fputs(plan.trace_line(plan.call, B, inflight).c_str(), stderr);
+    // 4. HEAVY stage.  Small batches: a heavy stage of a few hundred proofs is a chain of ~110 mostly latency-bound launches that
+    // leaves most of the GPU idle (256 MSM workgroups for 1024 slots), and on the caller's stream the chains of consecutive calls run
+    // one after the other: 31 ms per 256-proof call whatever else is tuned.  Such calls therefore run their heavy stage UNSLICED on
     // one of the three internal slice streams in rotation (own scratch slot each, like slices): up to three calls' chains in
     // flight; the caller's stream only waits for the result.
-    const bool rotate = dual && ((ctx->rotate_below > 0 && B <= (u32)ctx->rotate_below) || (deep && B > (u32)ctx->rotate_below));
-    if (ctx->trace_prove) fprintf(stderr, "prove call %u: B %u inflight %d deep %d behind_sliced %d dual %d rotate %d par %d coop %d\n", call, B, inflight, (int)deep, (int)behind_sliced, (int)dual, (int)rotate, par, (int)traced_coop);
-    if (rotate) {
-        const int hs = 1 + (int)(call % (u32)(bbp_ctx::MAX_SLICES - 1));
+    const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (size_t)m;
+    if (plan.rotate) {
+        const int hs = plan.heavy_stream;
         hipStream_t ls = ctx->lane[hs];
         BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_open[par], 0));
-        if ((rc = prove_heavy(ctx, c, bd, B, out_dev, ls, hs, nullptr, ctx->ev_entry[par]))) return rc;
+        if ((rc = prove_heavy(ctx, plan_heavy(ctx->knobs, B), c, bd, B, out_dev, ls, hs, nullptr, ctx->ev_entry[par]))) return rc;
         BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_join[hs], ls));
-        BBP_HIP_TRY(ctx, hipStreamWaitEvent(main_s, ctx->ev_join[hs], 0));
-        slices = 0;
+        BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[hs], 0));
     }
-    for (u32 i = 0; i < slices; i++) {
-        const u32 first = (u32)(((u64)B * i) / slices), last = (u32)(((u64)B * (i + 1)) / slices);
-        hipStream_t ls = i == 0 ? main_s : ctx->lane[i];
+    // Otherwise the batch is cut into slices that run the same kernel sequence on separate streams (slice 0 on the caller's -- a
+    // fifth concurrently active queue was measured 7 % slower): while one slice sits in a latency-bound step (the per-round
+    // transcript + scalar inversion in k_ipa_round, the small encode / commit kernels) the others' MSMs keep the CUs busy.
+    for (u32 i = 0; i < plan.slices; i++) {
+        const u32 first = plan.slice_first(B, i), last = plan.slice_first(B, i + 1);
+        hipStream_t ls = i == 0 ? s : ctx->lane[i];
         BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_open[par], 0));
         // stagger: slices run the same kernel sequence, so started together their latency-bound steps would coincide; each
         // slice waits for the previous slice's first MSM, which puts its serial steps under the neighbour's MSMs
-        if (i && ctx->stagger_mode) BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_stagger[i - 1], 0));
-        if ((rc = prove_heavy(ctx, c, batch_view(bd, c, first), last - first, out_dev + rec * first, ls, (int)i,
-                              i + 1 < slices ? ctx->ev_stagger[i] : nullptr, i ? ctx->ev_entry[par] : nullptr)))
+        const HeavyPlan hp = plan_heavy(ctx->knobs, last - first);
+        if (i && hp.stagger_after) BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_stagger[i - 1], 0));
+        if ((rc = prove_heavy(ctx, hp, c, batch_view(bd, c, first), last - first, out_dev + rec * first, ls, (int)i,
+                              i + 1 < plan.slices ? ctx->ev_stagger[i] : nullptr, i ? ctx->ev_entry[par] : nullptr)))
             return rc;
         if (i) {
             BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_join[i], ls));
-            BBP_HIP_TRY(ctx, hipStreamWaitEvent(main_s, ctx->ev_join[i], 0));
+            BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[i], 0));
         }
     }
-    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_done[par], main_s));
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_done[par], s));
     ctx->ev_done_valid[par] = true;
     ctx->last_par = par;
-    ctx->last_sliced = !rotate;
+    ctx->prove_state.last_sliced = !plan.rotate;
     ctx->last_prove_par = par;
-    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_call[call % (u32)bbp_ctx::CALL_RING], main_s));
-    ctx->ev_call_valid[call % (u32)bbp_ctx::CALL_RING] = true;
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_call[plan.call % (u32)bbp_ctx::CALL_RING], s));
+    ctx->ev_call_valid[plan.call % (u32)bbp_ctx::CALL_RING] = true;
     return BBP_OK;  // ~StreamGuard records ev_last on the caller's stream
 }
 
@@ -1834,7 +1811,7 @@ static BatchDev batch_view(const BatchDev& bd, const CircuitDev& c, u32 first) {
 }
 
 // everything after the opening stage for `B` proofs of the view `bd`, on stream `s`, with MSM scratch slot `slot`
-static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
+static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
                            hipEvent_t stagger, hipEvent_t out_guard) {
     int32_t rc;
     const u32 m = c.m, n1 = c.n_mul, encw = (m + 8 + 22) * 8;
@@ -1843,16 +1820,16 @@ static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd
     if ((rc = dev_reserve(ctx, ptsbuf, sizeof(ge) * (size_t)B * 3))) return rc;
     ge* tmp = static_cast<ge*>(ptsbuf.p);
     if ((rc = msm_launch(ctx, B, 1 + 2 * n1, (const u32*)bd.ai1, c.idx_ai, tmp, s, 1, slot))) return rc;
-    if (stagger && ctx->stagger_mode == 1) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
+    if (stagger && hp.stagger_after == 1) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
     if ((rc = msm_launch(ctx, B, 1 + n1, (const u32*)bd.ao1, c.idx_ao, tmp + B, s, 1, slot))) return rc;
     if ((rc = msm_launch(ctx, B, 1 + 2 * n1, (const u32*)bd.s1, c.idx_s1, tmp + 2 * (size_t)B, s, 1, slot))) return rc;
     // the next slice starts once this one has issued its three commitment MSMs: its own commitment MSMs then run under this
     // slice's long MSM-free stretch (encode, transcript, powers, flatten, poly, T commitments, l/r vectors)
-    if (stagger && ctx->stagger_mode == 3) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
+    if (stagger && hp.stagger_after == 3) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
     // the three commitments of a proof in ONE launch (they sit B points apart: tmp[k * B + p]); three launches were three
     // dependent-chain latencies (3 x 82 us for a small call)
     LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(3 * B, 64), 64, s, 3 * B, 3u, tmp, 1u, bd.enc, encw, 8 * m, B);
-    const u32 tw = B <= (u32)ctx->tr_wave_below ? 1u : 0u, tgrid = tw ? B : cdiv(B, 64);  // transcript kernels: one proof per wavefront for small launches
+    const u32 tw = hp.tw, tgrid = hp.tgrid;  // transcript kernels: one proof per wavefront for small launches
     LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_yz, tgrid, 64, s, B, m, bd.enc, bd.tr, bd.misc, tw);
     {
         const u32 widest = c.n_cons + 1 > 2049u ? c.n_cons + 1 : 2049u;
@@ -1860,7 +1837,7 @@ static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd
         LAUNCH(ctx, TAG_POLY, k_powers3, dim3(cdiv(B * cdiv(widest, 32), 64), 3), 64, s, B, bd.misc, jz, jy, jyi);
     }
     const u32 n_tgt = 3 * n1 + m;
-    if (B <= (u32)ctx->ipa_wide_below)
+    if (hp.wide_ipa)
         LAUNCH(ctx, TAG_POLY, k_flatten_split, cdiv(B * n_tgt * FLAT_L, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, c.n_cons + 1, bd.wl, bd.wr,
            bd.wo, bd.wv, 2048u);
     else
@@ -1869,7 +1846,7 @@ static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd
     LAUNCH(ctx, TAG_POLY, k_poly, B, POLY_BLK, s, n1, bd.ai1, bd.ao1, bd.s1, bd.wl, bd.wr, bd.wo, 2048u, bd.ypow, bd.yipow, bd.l1, bd.r0,
            bd.r1, bd.r3, bd.misc);
     LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_tblind, tgrid, 64, s, B, bd.rng, bd.misc, tw);
-    if (B * 5 <= (u32)ctx->commit_split_below)
+    if (hp.split_T)
         LAUNCH(ctx, TAG_COMMIT, k_commit_T_split, cdiv(B * 5 * COMMIT_L, 64), 64, s, B, bd.misc, ctx->comb, bd.pts, m + 8, m);
     else
         LAUNCH(ctx, TAG_COMMIT, k_commit_T, cdiv(B * 5, 64), 64, s, B, bd.misc, ctx->comb, bd.pts, m + 8, m);
@@ -1877,11 +1854,10 @@ static int32_t prove_heavy(bbp_ctx* ctx, const CircuitDev& c, const BatchDev& bd
     LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_ux, tgrid, 64, s, B, m, n1, bd.enc, bd.wv, bd.vb, bd.ai1, bd.ao1, bd.s1, bd.tr, bd.misc, tw);
     LAUNCH(ctx, TAG_POLY, k_lrvec, cdiv(B * 2048, 128), 128, s, B, n1, bd.l1, bd.r0, bd.r1, bd.r3, bd.ao1, bd.s1, bd.ypow, bd.yipow, bd.misc,
            bd.a, bd.b, bd.g, bd.h);
-    // FOLD_ROUND (7), or 12 = never leave the fixed-base formulation (small heavy stages: context.h tail_small_below)
-    const u32 tail_from = B < (u32)(ctx->tail_small_below > 0 ? ctx->tail_small_below : 0) ? 12u : (u32)ctx->tail_round;
+    const u32 tail_from = hp.tail_from;  // FOLD_ROUND (7), or 12 = never leave the fixed-base formulation (small heavy stages)
     for (u32 r = 1; r <= 11 && r < tail_from; r++) {
         if (r > 1) LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_challenge, tgrid, 64, s, B, r - 1, m, bd.enc, bd.tr, bd.misc, tw);
-        if (B <= (u32)ctx->ipa_wide_below)
+        if (hp.wide_ipa)
             LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK_WIDE>, B, IPA_BLK_WIDE, s, r, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, bd.lr);
         else
             LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK>, B, IPA_BLK, s, r, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, bd.lr);

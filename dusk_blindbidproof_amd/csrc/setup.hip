@@ -266,34 +266,11 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
     if (const char* e = getenv("BBP_VERIFY_SERIAL_ACC")) ctx->verify_serial_acc = atoi(e) != 0;
     for (auto& e : ctx->ev_vacc) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (const char* e = getenv("BBP_VERIFY_AGGREGATE")) ctx->verify_group = atoi(e) > 1 ? (uint32_t)atoi(e) : 0u;
-    if (const char* e = getenv("BBP_DUAL_OPEN_BELOW")) ctx->dual_open_below = atoi(e);
-    if (const char* e = getenv("BBP_ROTATE_BELOW")) ctx->rotate_below = atoi(e);
-    if (const char* e = getenv("BBP_ROTATE_MIXED_FROM")) ctx->mixed_from = atoi(e);
-    ctx->trace_prove = getenv("BBP_TRACE_PROVE") != nullptr;
-    if (const char* e = getenv("BBP_ROTATE_DEEP_MAX")) ctx->rotate_deep_max = atoi(e);
-    if (const char* e = getenv("BBP_ROTATE_DEEP_FROM")) ctx->deep_from = atoi(e) < 2 ? 2 : atoi(e);
+    ctx->knobs = ProveKnobs::from_env();  // every prove-schedule knob: prove_plan.h lists the names
     if (const char* e = getenv("BBP_VARBASE_LANES")) ctx->varbase_lanes = atoi(e) < 64 ? 64 : atoi(e);
-    if (const char* e = getenv("BBP_TAIL_ROUND")) ctx->tail_round = atoi(e) == bbp::FOLD_ROUND ? bbp::FOLD_ROUND : 12;
-    if (const char* e = getenv("BBP_STAGGER")) ctx->stagger_mode = atoi(e);
-    if (const char* e = getenv("BBP_RNG_COOP")) ctx->rng_coop = atoi(e) != 0;
-    if (const char* e = getenv("BBP_RNG_DPP")) ctx->rng_dpp = atoi(e);
-    if (const char* e = getenv("BBP_TAIL_SMALL_BELOW")) ctx->tail_small_below = atoi(e);
-    if (const char* e = getenv("BBP_RNG_COOP_BELOW")) ctx->rng_coop_below = atoi(e);
-    if (const char* e = getenv("BBP_RNG_COOP_IDLE_BELOW")) ctx->rng_coop_idle_below = atoi(e);
     if (const char* e = getenv("BBP_MSM_SMALL")) ctx->msm_small = atoi(e) != 0;
-    if (const char* e = getenv("BBP_WITNESS_NATIVE")) ctx->witness_native = atoi(e) != 0;
-    if (const char* e = getenv("BBP_COMMIT_SPLIT_BELOW")) ctx->commit_split_below = atoi(e);
-    if (const char* e = getenv("BBP_IPA_WIDE_BELOW")) ctx->ipa_wide_below = atoi(e);
-    if (const char* e = getenv("BBP_TR_WAVE_BELOW")) ctx->tr_wave_below = atoi(e);
-    if (const char* e = getenv("BBP_RNG_BLOCK")) {
-        const int v = atoi(e);
-        ctx->rng_block = v >= 1024 ? 1024 : v >= 512 ? 512 : v >= 256 ? 256 : v >= 128 ? 128 : 64;
-    }
-    if (const char* e = getenv("BBP_SERIAL_BLOCK")) ctx->serial_block = atoi(e) == 64 ? 64 : atoi(e) == 128 ? 128 : 256;
-    if (const char* e = getenv("BBP_SERIAL_LDS")) ctx->serial_lds = atoi(e) < 0 ? 0 : atoi(e) > 160 * 1024 ? 160 * 1024 : atoi(e);
     if (const char* e = getenv("BBP_SORT_STAGED")) ctx->sort_staged = atoi(e) & 7;
     if (const char* e = getenv("BBP_FOLD_HALF_FROM")) ctx->fold_half_from = atoi(e) < 1 ? 1 : atoi(e);
-    if (const char* e = getenv("BBP_SLICES")) ctx->slices = atoi(e) < 1 ? 1 : atoi(e) > bbp_ctx::MAX_SLICES ? bbp_ctx::MAX_SLICES : atoi(e);
     for (int i = 0; i < bbp_ctx::PROVE_BUFS; i++) {
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_entry[i], hipEventDisableTiming));
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_open[i], hipEventDisableTiming));
@@ -489,7 +466,7 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                           "device %d: %s (%s), %d CUs, %.0f MHz, %.1f of %.1f GiB free; prover: %d heavy-stage slices, tail from round %d, "
                                           "cooperative rng below %d proofs; verifier: %d lanes, accumulates %s, aggregate groups of %u%s\n",
                                           ctx->device, prop.name, prop.gcnArchName, prop.multiProcessorCount, prop.clockRate / 1e3, free_b / 1073741824.0,
-                                          total_b / 1073741824.0, ctx->slices, ctx->tail_round, ctx->rng_coop_below, (int)bbp_ctx::VLANES,
+                                          total_b / 1073741824.0, ctx->knobs.slices, ctx->knobs.tail_round, ctx->knobs.rng_coop_below, (int)bbp_ctx::VLANES,
                                           ctx->verify_serial_acc ? "chained" : "free-running", ctx->verify_group, ctx->verify_group ? "" : " (off)");
         // The engine keeps four streams busy during a prove call (caller's, opening stage, two more slices) and four more for
         // verification (one per lane), out of eleven it creates; how many hardware queues they get is read when the HIP runtime

@@ -734,14 +734,14 @@ int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_
     {
         // BBP_V_FENCE=1 (experiment): the transcript replay's serial waves get CUs of their own like the prover's opening kernels
         static const int fence = getenv("BBP_V_FENCE") ? atoi(getenv("BBP_V_FENCE")) : 0;
-        const u32 vtw = B <= (u32)ctx->tr_wave_below ? 1u : 0u;  // the replay of a few proofs: a wavefront each (as the prover's transcript kernels)
+        const u32 vtw = B <= (u32)ctx->knobs.tr_wave_below ? 1u : 0u;  // the replay of a few proofs: a wavefront each (as the prover's transcript kernels)
         if (ko & 4) {
         } else if (mixed) {
             u32 hog = lds_token(ctx);
-            if (fence && ctx->serial_lds > 0 && (rc = serial_lds_bytes(ctx, (const void*)k_vtranscript_mx, &hog))) return rc;
+            if (fence && ctx->knobs.serial_lds > 0 && (rc = serial_lds_bytes(ctx, (const void*)k_vtranscript_mx, &hog))) return rc;
             LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript_mx, vtw ? B : cdiv(B, 64), 64, hog, s, B, rows, np * 8, prefix, vpts, ent_dev, vchal, bd.misc,
                        status_dev, vtw);
-        } else if (fence && ctx->serial_lds > 0) {
+        } else if (fence && ctx->knobs.serial_lds > 0) {
             u32 hog = 0;
             if ((rc = serial_lds_bytes(ctx, (const void*)k_vtranscript, &hog))) return rc;
             LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript, vtw ? B : cdiv(B, 64), 64, hog, s, B, m, prefix, vpts, ent_dev, vchal, bd.misc, status_dev, vtw);
@@ -767,8 +767,8 @@ int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_
     // MSM (BBP_VERIFY_OVERLAP=0: on the caller's stream after them) and joins before the first kernel that reads its sums / status.
     // Not when prove calls are interleaved with the verifications: that stream is the prover's second slice, and queueing behind
     // this call's fork point delays the next batch's slice (measured 67.7 vs 66.3 ms per prove + verify pair).
-    const bool overlap = lane == 0 && ctx->verify_overlap && ctx->seq == ctx->seq_at_last_verify && !(ko & 2);
-    ctx->seq_at_last_verify = ctx->seq;
+    const bool overlap = lane == 0 && ctx->verify_overlap && ctx->prove_state.calls == ctx->seq_at_last_verify && !(ko & 2);
+    ctx->seq_at_last_verify = ctx->prove_state.calls;
     hipStream_t vs_stream = overlap ? ctx->lane[1] : s;
     if (overlap) {
         BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vfork, s));

@@ -7,6 +7,7 @@
 #include "../dusk_blindbidproof_amd/csrc/keccak.h"
 #include "../dusk_blindbidproof_amd/csrc/keccak_wave.h"
 #include "../dusk_blindbidproof_amd/csrc/point.h"
+#include "../dusk_blindbidproof_amd/csrc/prove_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
 #include "../dusk_blindbidproof_amd/csrc/verify_rows.h"
 #include "../dusk_blindbidproof_amd/csrc/witness.h"
@@ -249,6 +250,41 @@ void hc_verify_rows(int kind, uint32_t B, uint32_t N, uint32_t rec_ver, const ui
     info[8] = v.round_of != nullptr;
     info[9] = v.round_of ? (uint64_t)(v.round_of - round_of) : 0;
     info[10] = v.B ? v.first_n() : 0;
+}
+
+// The plan of one prove call (csrc/prove_plan.h).  knobs: n_knobs (environment name, text) pairs applied over the defaults through
+// ProveKnobs::set, clamps included; -1: a name is no prove knob.  state (in and out): deep_mode, deep_idle_seen, force_deep, last_sliced,
+// calls.  busy: what sliced_busy answers.  out: 0 call, 1 deep, 2 behind_sliced, 3 dual, 4 open_stream, 5 par, 6 coop, 7 chain, 8 prefix_form,
+// 9 serial_blk, 10 cblk, 11 cblk_wave, 12 rotate, 13 heavy_stream, 14 slices, 15 times sliced_busy was asked, 16..20 the slice bounds
+// (slices + 1 of them), then plan_heavy(knobs, B): 21 tw, 22 tgrid, 23 wide_ipa, 24 split_T, 25 tail_from, 26 stagger_after.
+// trace: trace_line(call, B, inflight).
+int hc_prove_plan(const char* const* knobs, int n_knobs, int32_t* state, uint32_t B, int inflight, int busy, int64_t* out, char* trace, size_t trace_cap) {
+    ProveKnobs k;
+    for (int i = 0; i < n_knobs; i++)
+        if (!k.set(knobs[2 * i], knobs[2 * i + 1])) return -1;
+    ProveRuleState st;
+    st.deep_mode = state[0], st.deep_idle_seen = state[1], st.force_deep = state[2], st.last_sliced = state[3], st.calls = (uint32_t)state[4];
+    int asked = 0;
+    const ProvePlan p = plan_prove(k, st, B, inflight, [&] { asked++; return busy != 0; });
+    state[0] = st.deep_mode, state[1] = st.deep_idle_seen, state[2] = st.force_deep, state[3] = st.last_sliced, state[4] = (int32_t)st.calls;
+    const int64_t plan[16] = {p.call, p.deep, p.behind_sliced, p.dual, p.open_stream, p.par, p.coop, p.chain, p.prefix_form, p.serial_blk, p.cblk, p.cblk_wave(),
+                              p.rotate, p.heavy_stream, p.slices, asked};
+    memcpy(out, plan, sizeof plan);
+    for (uint32_t i = 0; i < 5; i++) out[16 + i] = i <= p.slices && p.slices ? (int64_t)p.slice_first(B, i) : -1;
+    const HeavyPlan h = plan_heavy(k, B);
+    out[21] = h.tw, out[22] = h.tgrid, out[23] = h.wide_ipa, out[24] = h.split_T, out[25] = h.tail_from, out[26] = h.stagger_after;
+    snprintf(trace, trace_cap, "%s", p.trace_line(p.call, B, inflight).c_str());
+    return 0;
+}
+// one knob as ProveKnobs::from_env reads it from an environment that holds name=text (the variable is set for the call only)
+int hc_prove_knob_from_env(const char* name, const char* text, int which) {
+    setenv(name, text, 1);
+    const ProveKnobs k = ProveKnobs::from_env();
+    unsetenv(name);
+    const int v[] = {k.slices, k.rotate_below, k.rotate_deep_max, k.deep_from, k.mixed_from, k.dual_open_below, k.rng_coop, k.rng_coop_below, k.rng_coop_idle_below,
+                     k.rng_dpp, k.rng_block, k.serial_block, k.serial_lds, k.tr_wave_below, k.ipa_wide_below, k.commit_split_below, k.witness_native,
+                     k.tail_small_below, k.tail_round, k.stagger_mode, k.trace_prove};
+    return v[which];
 }
 
 // The bit-interleaved form the one-wavefront Keccak keeps its words in (keccak_wave.h): even / odd bits of x as two 32-bit halves.

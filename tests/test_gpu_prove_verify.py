@@ -458,6 +458,41 @@ def test_small_call_paths_give_identical_bytes(bbp, oc, knob, value):
         c2.close()
 
 
+def test_trace_lines_are_the_plan_headers(bbp, built, ctx, oc, capfd):
+    """The library schedules a call the way csrc/prove_plan.h says: synchronous host calls (nothing in flight) on each side of every
+    small-call threshold -- 32 | 33 wavefront transcripts and wide IPA round, 64 | 65 tail, 128 | 130 workgroup size, 204 | 205 split T
+    commitments -- print the trace line the CPU tier's probe gives for the same knobs, size and call index (test_prove_plan_host.py
+    holds that probe against literals), and return the C oracle's records."""
+    import ctypes
+    import os
+    from tests.prove_plan_probe import Plan
+    hc = ctypes.CDLL(built.build_hostcheck())
+    sizes, N = (1, 33, 65, 130, 205), 1
+    ins, ents, _ = _synth_batch(ctx, max(sizes), N, seed=2718)  # row i does not depend on the batch it is in
+    cout, cst = oc.prove_many(b"".join(ins), b"".join(ents), max(sizes), N, threads=8)
+    assert cst == [0] * max(sizes)
+    rs_ = bbp.record_size(N)
+    old = os.environ.get("BBP_TRACE_PROVE")
+    os.environ["BBP_TRACE_PROVE"] = "1"
+    try:
+        c2 = bbp.Context(0)
+    finally:
+        if old is None:
+            os.environ.pop("BBP_TRACE_PROVE", None)
+        else:
+            os.environ["BBP_TRACE_PROVE"] = old
+    try:
+        for call, B in enumerate(sizes):
+            capfd.readouterr()
+            out, st = c2.prove_batch(B, N, b"".join(ins[:B]), b"".join(ents[:B]))
+            trace = [l for l in capfd.readouterr().err.splitlines() if l.startswith("prove call")]
+            assert st == [0] * B and out == cout[:B * rs_], B
+            assert trace == [Plan(hc, B, inflight=0, calls=call, knobs={"BBP_TRACE_PROVE": "1"}).trace.rstrip("\n")], B
+        assert c2.health() == 0
+    finally:
+        c2.close()
+
+
 def test_pipelined_calls_of_mixed_batch_sizes(bbp, oc):
     """Back-to-back device calls without host synchronisation, alternating between batch sizes below and above the
     dual-opening threshold (two opening streams over three buffers vs one stream over two): every call must reproduce the
