@@ -60,6 +60,9 @@ SIGNATURES = {
     "bbp_verify_rounds_aggregated": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _vp]),
     "bbp_verify_rounds_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_rounds_aggregated_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _vp, _vp]),
+    "bbp_prepare_round_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_prove_round": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_prove_round_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_reserve": (_i32, [_vp, _u32, _u32]),
     "bbp_set_batching": (_i32, [_vp, _u32, _u32]),
     "bbp_set_verify_mixing": (_i32, [_vp, _i32]),
@@ -185,6 +188,19 @@ def expand_round_rows(round_Ns, table, round_of, rows):
     if at != len(rows):
         raise ValueError("rows do not have the size their rounds give")
     return Ns, b"".join(bytes(p) for p in parts)
+
+
+ROUND_BID_BYTES = 64  # BBP_ROUND_BID_BYTES
+
+
+def pack_round_bids(bids):
+    """[(d, k)] -> the bids of prove_round*: d || k, 64 bytes each, in request order."""
+    parts = []
+    for d, k in bids:
+        if len(d) != 32 or len(k) != 32:
+            raise ValueError("a bid is two 32-byte scalars d, k")
+        parts += [d, k]
+    return b"".join(bytes(p) for p in parts)
 
 
 def _u32s(values):
@@ -428,6 +444,31 @@ class Context:
             raise ValueError("without round_of the rows must be a whole number of rows of the one round")
         return len(rows) // round_row_size(round_Ns[0])
 
+    def prove_round(self, N, table, bids, entropy=None):
+        """One round (table = seed || pub_list: pack_rounds of one round) and raw bids (pack_round_bids): witness, toggle search and
+        proofs on the device.  Returns (rows, toggles, statuses); rows are record || score || z_img, what verify_rounds([N], table,
+        None, rows) takes; a refused bid (FORMAT: non-canonical seed, d or k; BAD_ARG: x is not in the list) has a zero row and toggle."""
+        if len(table) != 32 * (1 + N) or len(bids) % ROUND_BID_BYTES:
+            raise ValueError("a round is a 32-byte seed and N 32-byte items; bids are 64 bytes each")
+        B = len(bids) // ROUND_BID_BYTES
+        if entropy is not None and len(entropy) != B * entropy_size(N):
+            raise ValueError("entropy must hold entropy_size(N) bytes per bid")
+        rows = (ctypes.c_uint8 * max(1, B * round_row_size(N)))()
+        toggles = (ctypes.c_uint64 * max(1, B))()
+        status = (ctypes.c_int32 * max(1, B))()
+        self._check(lib.bbp_prove_round(self._h, N, _buf(table), B, _buf(bids) if B else rows, None if entropy is None else _buf(entropy), rows,
+                                        toggles, status))
+        return bytes(rows)[:B * round_row_size(N)], list(toggles)[:B], list(status)[:B]
+
+    def prepare_round_dev(self, N, table_ptr, B, bids_ptr, prove_in_ptr, status_ptr, tails_ptr=None, toggles_ptr=None, stream=None):
+        """bbp_prepare_round_dev: the device pass alone -- rows for prove_batch_dev (which waits for them by itself), optionally
+        score || z_img tails and u64 toggles, int32 statuses.  Stream-ordered, no synchronisation."""
+        self._check(lib.bbp_prepare_round_dev(self._h, N, table_ptr, B, bids_ptr, prove_in_ptr, tails_ptr, toggles_ptr, status_ptr, _stream(stream)))
+
+    def prove_round_dev(self, N, table_ptr, B, bids_ptr, ent_ptr, rows_out_ptr, status_ptr, toggles_ptr=None, stream=None):
+        """bbp_prove_round_dev: prove_round on device memory, ordered on `stream`, no synchronisation."""
+        self._check(lib.bbp_prove_round_dev(self._h, N, table_ptr, B, bids_ptr, ent_ptr, rows_out_ptr, toggles_ptr, status_ptr, _stream(stream)))
+
     def prove_batch_dev(self, B, N, in_ptr, ent_ptr, out_ptr, stream=None):
         self._check(lib.bbp_prove_batch_dev(self._h, B, N, in_ptr, ent_ptr, out_ptr, _stream(stream)))
 
@@ -540,7 +581,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / msm_batch (block-split over the members, results in request order); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):
@@ -561,6 +602,11 @@ class Pool(Context):
         if not h:
             raise IndexError(i)
         return Context(_borrowed=h)
+
+    def prove_round(self, N, table, bids, entropy=None):
+        """bbp_prove_round on the pool: the bids block-split by index over the members, every member receives the table; rows, toggles
+        and statuses in request order."""
+        return super().prove_round(N, table, bids, entropy)
 
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""

@@ -10,6 +10,7 @@
 
 #include "batch.h"
 #include "chacha.h"
+#include "round_bids.h"
 #include "submit.h"
 #include "witness_check.h"
 
@@ -21,6 +22,8 @@ int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
                              u32* n_fallback, u32* total_out_dev = nullptr);
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out);
+// verifier.inc: k_round_consts for one round (the prove side's table reduction)
+int32_t round_consts_launch(bbp_ctx* ctx, u32 N, const u8* round_dev, const u32* roff_dev, sc* rblk, int32_t* rflag, hipStream_t s);
 
 // native (non-circuit) image of the gadget wiring: what the reference's Go caller computes before Proof::prove
 // (src/gadgets.rs:20-33 for m,x,y,z; :70-86 for y_inv and q)
@@ -192,6 +195,50 @@ static int32_t draw_enqueue(bbp_ctx* ctx, u32 B, u32 N, u32 kind, const ChachaKe
     }
     ScopedEvent ev(ctx, TAG_RNG, s);
     hipLaunchKernelGGL(k_draw_entropy, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (u32)n, N, kind, row_base, key, (u32*)out);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+
+// The device pass of a round call on s (round_bids.h): bids first.. of a call whose scratch (round_scratch of the whole call) is at
+// `scratch`; `reduce`: the table is reduced first (once per call).  bids / prove_in / tails / toggles / status point at bid `first`.
+static int32_t round_prepare_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u8* scratch, const RoundScratch& rs, bool reduce, u32 first, u32 B,
+                                     const u8* bids, u32* prove_in, u32* tails, u32* toggles, int32_t* status, hipStream_t s) {
+    const u64 n = (u64)B * (round_in_words(N) + RB_EXTRA_WORDS);
+    if (n > 0x7fffffffull) {
+        ctx->err = "round prepare: too many bids for one call";
+        return BBP_ERR_BAD_ARG;
+    }
+    u32* roff = (u32*)(scratch + rs.roff);
+    sc* rblk = (sc*)(scratch + rs.rblk);
+    int32_t* rflag = (int32_t*)(scratch + rs.rflag);
+    u32* rb = (u32*)(scratch + rs.rb) + (size_t)RB_WORDS * first;
+    int32_t rc;
+    if (reduce) {  // the two round offsets k_round_consts reads, written in stream order (no host memory involved)
+        BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)roff, 0, 1, s));
+        BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(roff + 1), (int)(1 + N), 1, s));
+        if ((rc = round_consts_launch(ctx, N, table, roff, rblk, rflag, s))) return rc;
+    }
+    unsigned hog = 0;  // a serial wave of four MiMC chains beside other calls' heavy stages: fenced onto CUs of its own, as k_prepare_bids
+    if ((rc = serial_lds_bytes(ctx, (const void*)k_round_bids, &hog))) return rc;
+    ScopedEvent ev(ctx, TAG_WITNESS, s);
+    hipLaunchKernelGGL(k_round_bids, dim3((B + 63) / 64), dim3(64), hog, s, B, N, bids, (const sc*)rblk, (const int32_t*)rflag, ctx->mimc_c, rb);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_round_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), lds_token(ctx), s, (u32)n, N, bids, table, (const u32*)rb, prove_in,
+                       tails, toggles, status);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// record || score || z_img rows from the records and the per-bid results of the pass, on s
+static int32_t round_rows_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* recs, const u32* rb, u8* rows, hipStream_t s) {
+    const u64 n = (u64)round_row_bytes(N) * B;
+    if ((n + 255) / 256 > 0x7fffffffull) {
+        ctx->err = "round rows: too many bids for one call";
+        return BBP_ERR_BAD_ARG;
+    }
+    ScopedEvent ev(ctx, TAG_VERIFY_SCALARS, s);
+    hipLaunchKernelGGL(k_round_rows, dim3((unsigned)((n + 255) / 256)), dim3(256), lds_token(ctx), s, B, N, recs, rb, rows);
     BBP_HIP_TRY(ctx, hipGetLastError());
     return BBP_OK;
 }
@@ -525,20 +572,54 @@ static std::string refused_row_text(const bbp_ctx* ctx, const uint8_t* row, uint
 
 enum CheckMode { CHECK_AUTO, CHECK_OFF, CHECK_REPROVE };  // context's setting / never (bbp_reserve) / checked, no second prove
 
-// body of bbp_prove_batch.  Takes the context lock itself, for the enqueue phase only.
+// The other input stage of prove_batch_host (bbp_prove_round): the round's table and the raw bids in host memory instead of
+// expanded rows.  They are uploaded as they are and the device pass (round_bids.h) writes the prover's rows into the staging slot;
+// its per-bid statuses stand in for the host screening, and `out` receives rows record || score || z_img.
+struct RoundInput {
+    const uint8_t* table;   // seed || pub_list
+    const uint8_t* bids;    // B x (d || k)
+    uint64_t* toggles_out;  // B entries, or NULL
+};
+// Where a round call keeps what in its staging slot.  in: bids, table, the pass's scratch, the prover's rows.  out: the rows to
+// fetch, the check's results (checked calls), toggles and statuses of the pass -- fetched up to `fetch` -- then the raw records.
+struct RoundLayout {
+    RoundScratch rs;
+    size_t tab_bytes, tab_off, scr_off, rows_off, in_cap;       // staging slot `in`
+    size_t info_off, tog_off, st_off, fetch, recs_off, out_cap;  // staging slot `out`
+    RoundLayout(u32 B, u32 N, bool check) : rs(round_scratch(B, N)) {
+        const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, rec = bbp_proof_record_size(N);
+        tab_bytes = 32 * (1 + (size_t)N);
+        tab_off = align256(BBP_ROUND_BID_BYTES * (size_t)B);
+        scr_off = align256(tab_off + tab_bytes);
+        rows_off = scr_off + rs.end;
+        in_cap = rows_off + in_stride * B;
+        info_off = align256((rec + 64) * B);
+        tog_off = align256(info_off + (check ? 4 * (3 * (size_t)B + 1) : 0));
+        st_off = tog_off + 8 * (size_t)B;
+        fetch = st_off + 4 * (size_t)B;
+        recs_off = align256(fetch);
+        out_cap = recs_off + rec * B;
+    }
+};
+
+// body of bbp_prove_batch and, with `round`, of bbp_prove_round (in == NULL then).  Takes the context lock itself, for the enqueue
+// phase only.
 static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out,
-                                int32_t* status, CheckMode mode = CHECK_AUTO) {
+                                int32_t* status, CheckMode mode = CHECK_AUTO, const RoundInput* round = nullptr) {
     int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
     if (rc) return rc;
     if (B == 0) return BBP_OK;
     fault_injected("prove_batch");
     const bool check = mode == CHECK_REPROVE || (mode == CHECK_AUTO && ctx->prove_check.load());
     const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, ent_stride = bbp_entropy_size(N), out_stride = bbp_proof_record_size(N);
-    // host-side argument screening (the reference's typed API cannot express these states: SURVEY.md 8b)
+    const size_t res_stride = round ? out_stride + 64 : out_stride;  // what `out` holds per row
+    // host-side argument screening (the reference's typed API cannot express these states: SURVEY.md 8b); a round call's rows are
+    // screened by the device pass
     std::vector<uint8_t> fixed;
     for (uint32_t i = 0; i < B; i++) {
-        const uint8_t* r = in + in_stride * i;
         status[i] = BBP_OK;
+        if (round) continue;
+        const uint8_t* r = in + in_stride * i;
         uint64_t toggle;
         memcpy(&toggle, r + 7 * 32 + (size_t)N * 32, 8);
         if (toggle >= N) status[i] = BBP_ERR_BAD_ARG;
@@ -596,7 +677,10 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         up_ent = ent_all.data();
         up_ent_bytes = ent_all.size();
     }
-    const size_t info_off = check ? align256(out_stride * B) : out_stride * B, out_bytes = info_off + (check ? 4 * (3 * (size_t)B + 1) : 0);
+    const RoundLayout rl(B, N, check);  // (a round call's)
+    const size_t info_off = round ? rl.info_off : check ? align256(out_stride * B) : out_stride * B;
+    const size_t out_bytes = round ? rl.fetch : info_off + (check ? 4 * (3 * (size_t)B + 1) : 0);  // what comes back
+    const size_t out_cap = round ? rl.out_cap : out_bytes, rows_off = round ? rl.rows_off : 0, recs_off = round ? rl.recs_off : 0;
     std::vector<int32_t> dstatus;
     std::vector<u32> dmask, fail_rows;
     static const bool trace = getenv("BBP_TRACE") != nullptr;
@@ -611,9 +695,16 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         int32_t rc;
         t_lock = now_ms();
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = dev_reserve(ctx, sl.out, out_bytes)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, out_bytes)) ||
-            (check && (rc = dev_reserve(ctx, sl.chk, check_scratch_bytes(B, N)))) ||
-            (rc = upload_inputs(ctx, sl, src, in_stride * B, up_ent, up_ent_bytes, up_ent_off)))
+        if ((rc = dev_reserve(ctx, sl.out, out_cap)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, out_bytes)) ||
+            (check && (rc = dev_reserve(ctx, sl.chk, check_scratch_bytes(B, N)))))
+            return rc;
+        if (round) {  // bids and table travel as they are; the slot's input buffer also holds the pass's scratch and the rows it writes
+            if ((rc = dev_reserve(ctx, sl.in, rl.in_cap)) ||
+                (rc = upload_inputs(ctx, sl, round->bids, BBP_ROUND_BID_BYTES * (size_t)B, up_ent, up_ent_bytes, up_ent_off, round->table, rl.tab_bytes,
+                                    rl.tab_off)))
+                return rc;
+            if (!ctx->ev_round) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_round, hipEventDisableTiming));
+        } else if ((rc = upload_inputs(ctx, sl, src, in_stride * B, up_ent, up_ent_bytes, up_ent_off)))
             return rc;
         t_h2d = now_ms();
         u8* info = (u8*)sl.out.p + info_off;
@@ -626,23 +717,38 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         const uint32_t n_chunks = (B + host_chunk_prove() - 1) / host_chunk_prove(), chunk = (B + n_chunks - 1) / n_chunks;
         for (uint32_t first = 0; first < B; first += chunk) {
             const uint32_t nb = B - first < chunk ? B - first : chunk;
-            const u8 *cin = (const u8*)sl.in.p + in_stride * first, *cent = (const u8*)sl.ent.p + ent_stride * first;
-            u8* cout = (u8*)sl.out.p + out_stride * first;
+            const u8 *cin = (const u8*)sl.in.p + rows_off + in_stride * first, *cent = (const u8*)sl.ent.p + ent_stride * first;
+            u8* cout = (u8*)sl.out.p + recs_off + out_stride * first;
+            // what runs on the chunk's opening stream ahead of the opening stage.  A round call: the device pass writes this chunk's
+            // rows (the table is reduced by the first chunk; a later chunk may open on the other stream and waits for that).
             // (source DEVICE) this chunk's own rows of the call's key: no two chunks draw equal rows
             const std::function<int32_t(hipStream_t)> draw = [&](hipStream_t os) -> int32_t {
-                return draw_enqueue(ctx, nb, N, BBP_ENTROPY_PROVE, key, first, (void*)cent, os);
+                if (round) {
+                    int32_t rc;
+                    u8* base = (u8*)sl.in.p;
+                    if (first) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_round, 0));
+                    if ((rc = round_prepare_enqueue(ctx, N, base + rl.tab_off, base + rl.scr_off, rl.rs, first == 0, first, nb,
+                                                    base + BBP_ROUND_BID_BYTES * (size_t)first, (u32*)cin, nullptr,
+                                                    (u32*)((u8*)sl.out.p + rl.tog_off) + 2 * (size_t)first, (int32_t*)((u8*)sl.out.p + rl.st_off) + first, os)))
+                        return rc;
+                    if (!first && n_chunks > 1) BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_round, os));
+                }
+                return dev_draw ? draw_enqueue(ctx, nb, N, BBP_ENTROPY_PROVE, key, first, (void*)cent, os) : (int32_t)BBP_OK;
             };
+            const std::function<int32_t(hipStream_t)>* open = dev_draw || round ? &draw : nullptr;
             if (check) {
                 u8* scratch = (u8*)sl.chk.p;  // chunks are stream-ordered on ctx->stream; each chunk's check joins back before the next starts
                 if ((rc = prove_checked_enqueue(ctx, nb, N, cin, cent, (const u8*)sl.ent.p + ent_stride * B + 32 * (size_t)first, cout,
-                                                st_dev + first, mask_dev + first, scratch, fail_n, fail_idx, first, ctx->stream, nullptr,
-                                                dev_draw ? &draw : nullptr)))
+                                                st_dev + first, mask_dev + first, scratch, fail_n, fail_idx, first, ctx->stream, nullptr, open)))
                     return rc;
             } else {
-                if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream, dev_draw ? &draw : nullptr))) return rc;
+                if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream, open))) return rc;
                 if ((rc = corrupt_hook(ctx, first, nb, N, cout, ctx->stream))) return rc;
             }
         }
+        if (round && (rc = round_rows_enqueue(ctx, B, N, (const u8*)sl.out.p + recs_off, (const u32*)((u8*)sl.in.p + rl.scr_off + rl.rs.rb), (u8*)sl.out.p,
+                                              ctx->stream)))
+            return rc;
         ctx->debug_corrupt_proof = -1;  // armed for an index beyond this call: consumed all the same
         BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, ctx->stream));
         return BBP_OK;
@@ -650,7 +756,11 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
     if (rc) return rc;
     const double t_enq = now_ms();
     if ((rc = fetch_results(ctx, sl, out_bytes))) return rc;  // lock released: another thread may be enqueueing the next batch now
-    memcpy(out, sl.h_out, out_stride * B);
+    memcpy(out, sl.h_out, res_stride * B);
+    if (round) {  // the device pass's verdicts stand where the host screening's would
+        memcpy(status, (const u8*)sl.h_out + rl.st_off, 4 * (size_t)B);
+        if (round->toggles_out) memcpy(round->toggles_out, (const u8*)sl.h_out + rl.tog_off, 8 * (size_t)B);
+    }
     if (check) {
         const u8* info = (const u8*)sl.h_out + info_off;
         dstatus.resize(B);
@@ -667,7 +777,7 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
                 (int)(&sl - ctx->io), t_enter, t_slot - t_enter, t_lock - t_enter, t_h2d - t_enter, t_enq - t_enter, now_ms() - t_enter);
   }
     for (uint32_t i = 0; i < B; i++)
-        if (status[i] != BBP_OK) memset(out + out_stride * i, 0, out_stride);
+        if (status[i] != BBP_OK) memset(out + res_stride * i, 0, res_stride);
     if (!check) return BBP_OK;
     if (mode == CHECK_AUTO) ctx->chk_checked += B;
     // rows the host screening let through take the device's verdict (their records are already zeroed unless OK)
@@ -684,20 +794,24 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
     // fault: the whole call fails and health bit 1 is raised
     std::sort(fail_rows.begin(), fail_rows.end());
     const uint32_t nr = (uint32_t)fail_rows.size();
-    std::vector<uint8_t> rin(in_stride * nr), rent(ent_stride * nr), rout(out_stride * nr);
+    const size_t rin_stride = round ? (size_t)BBP_ROUND_BID_BYTES : in_stride;  // a round call proves the failed bids again, as a round
+    const uint8_t* rsrc = round ? round->bids : src;
+    std::vector<uint8_t> rin(rin_stride * nr), rent(ent_stride * nr), rout(res_stride * nr);
     std::vector<int32_t> rst(nr);
     for (uint32_t j = 0; j < nr; j++) {
-        memcpy(&rin[in_stride * j], src + in_stride * fail_rows[j], in_stride);
+        memcpy(&rin[rin_stride * j], rsrc + rin_stride * fail_rows[j], rin_stride);
         if (dev_draw)
             entropy_prove_row_bytes(key, N, fail_rows[j], &rent[ent_stride * j]);
         else
             memcpy(&rent[ent_stride * j], entropy + ent_stride * fail_rows[j], ent_stride);
     }
     ctx->chk_reproved += nr;
-    if ((rc = prove_batch_host(ctx, nr, N, rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE))) return rc;
+    const RoundInput again{round ? round->table : nullptr, rin.data(), nullptr};
+    if ((rc = prove_batch_host(ctx, nr, N, round ? nullptr : rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE, round ? &again : nullptr)))
+        return rc;
     for (uint32_t j = 0; j < nr; j++) {
         if (rst[j] != BBP_OK) return raise_check_failure(ctx, fail_rows[j]);
-        memcpy(out + out_stride * fail_rows[j], &rout[out_stride * j], out_stride);
+        memcpy(out + res_stride * fail_rows[j], &rout[res_stride * j], res_stride);
         status[fail_rows[j]] = BBP_OK;
     }
     return BBP_OK;
@@ -774,6 +888,80 @@ extern "C" int32_t bbp_prove_batch_checked_dev(bbp_ctx* ctx, uint32_t B, uint32_
         cb.ev_valid = true;
         ctx->chk_checked += B;
         return BBP_OK;
+    });
+}
+
+// ---- proving a round from raw bids (include/bbp.h; the device pass is round_bids.h) -----------------------------------------------
+extern "C" int32_t bbp_prove_round(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* bids, const uint8_t* entropy,
+                                   uint8_t* rows_out, uint64_t* toggles_out, int32_t* status) {
+    if (!ctx || !round || !bids || !rows_out || !status) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) {  // bids block-split over the members, every member receives the table (pool.cpp)
+        const int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
+        if (rc || B == 0) return rc;
+        return no_throw_ctx(ctx, [&]() -> int32_t { return pool_prove_round(ctx, N, round, B, bids, entropy, rows_out, toggles_out, status); });
+    }
+    const RoundInput r{round, bids, toggles_out};
+    return no_throw_ctx(ctx, [&]() -> int32_t { return prove_batch_host(ctx, B, N, nullptr, entropy, rows_out, status, CHECK_AUTO, &r); });
+}
+
+// bytes of a ring entry (context.h rnd): the pass's scratch; a prove call: its prove-input rows and its records behind it
+static size_t round_dev_bytes(u32 B, u32 N, bool prove) {
+    return round_scratch(B, N).end + (prove ? align256((7 * 32 + (size_t)N * 32 + 8) * B) + (size_t)bbp_proof_record_size(N) * B : 0);
+}
+
+// Both _dev forms (context lock held).  entropy_dev == NULL: the pass alone, rows into prove_in.  Else the pass into the ring entry,
+// the prover, and the output rows into rows_out, all ordered on s; the prover's opening stage waits for the pass through ev_prep.
+static int32_t round_dev_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u32 B, const u8* bids, u32* prove_in, u32* tails, u32* toggles,
+                                 int32_t* status, const u8* entropy_dev, u8* rows_out, hipStream_t s) {
+    int32_t rc;
+    const bool prove = entropy_dev != nullptr;
+    const RoundScratch rs = round_scratch(B, N);
+    // scratch in rotation: an entry waits for the last kernel of the call that used it last (several calls in flight, no host synchronisation)
+    bbp_ctx::CheckBuf& cb = ctx->rnd[ctx->rnd_next++ % (u32)bbp_ctx::CHECK_RING];
+    if ((rc = dev_reserve(ctx, cb.buf, round_dev_bytes(B, N, prove)))) return rc;
+    if (!cb.ev) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&cb.ev, hipEventDisableTiming));
+    if (cb.ev_valid) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, cb.ev, 0));
+    u8* base = (u8*)cb.buf.p;
+    u8 *in_rows = base + rs.end, *recs = in_rows + align256((7 * 32 + (size_t)N * 32 + 8) * B);
+    if (prove) prove_in = (u32*)in_rows;
+    if ((rc = round_prepare_enqueue(ctx, N, table, base, rs, true, 0, B, bids, prove_in, tails, toggles, status, s))) return rc;
+    // the prover's opening stage does not wait for the caller's stream (bbp.h); it does wait for this event
+    BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_prep, s));
+    ctx->ev_prep_valid = true;
+    if (prove) {
+        if ((rc = prove_batch_dev(ctx, B, N, in_rows, entropy_dev, recs, s))) return rc;
+        rc = corrupt_hook(ctx, 0, B, N, recs, s);
+        ctx->debug_corrupt_proof = -1;
+        if (rc || (rc = round_rows_enqueue(ctx, B, N, recs, (const u32*)(base + rs.rb), rows_out, s))) return rc;
+    }
+    BBP_HIP_TRY(ctx, hipEventRecord(cb.ev, s));
+    cb.ev_valid = true;
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_prepare_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, void* prove_in_dev,
+                                         void* tails_dev, void* toggles_dev, void* status_dev, void* stream) {
+    if (!ctx || !round_dev || !bids_dev || !prove_in_dev || !status_dev) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_prepare_round_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        const int32_t rc = check_n(ctx, N);
+        if (rc || B == 0) return rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return round_dev_enqueue(ctx, N, (const u8*)round_dev, B, (const u8*)bids_dev, (u32*)prove_in_dev, (u32*)tails_dev, (u32*)toggles_dev,
+                                 (int32_t*)status_dev, nullptr, nullptr, pick_stream(ctx, stream));
+    });
+}
+
+extern "C" int32_t bbp_prove_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, const void* entropy_dev,
+                                       void* rows_out_dev, void* toggles_out_dev, void* status_dev, void* stream) {
+    if (!ctx || !round_dev || !bids_dev || !entropy_dev || !rows_out_dev || !status_dev) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_prove_round_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        const int32_t rc = check_n(ctx, N);
+        if (rc || B == 0) return rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return round_dev_enqueue(ctx, N, (const u8*)round_dev, B, (const u8*)bids_dev, nullptr, nullptr, (u32*)toggles_out_dev, (int32_t*)status_dev,
+                                 (const u8*)entropy_dev, (u8*)rows_out_dev, pick_stream(ctx, stream));
     });
 }
 
@@ -1295,6 +1483,22 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
             for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data(), CHECK_OFF);
         }
         for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++) rc = verify_batch_host(ctx, vrows, vin.data(), st.data());
+        // round calls (bbp_prove_round*): what they keep beyond a bbp_prove_batch of the same size -- the staging slots' larger input and
+        // result buffers with their pinned mirrors (sized for a checked call, the larger), the device forms' scratch ring
+        if (rc == BBP_OK)
+            rc = api_guard(ctx, [&]() -> int32_t {
+                int32_t rc = BBP_OK;
+                BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+                const RoundLayout rl(B, N, true);
+                for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++) {
+                    bbp_ctx::IoSlot& sl = ctx->io[k];
+                    if (!(rc = dev_reserve(ctx, sl.in, rl.in_cap)) && !(rc = dev_reserve(ctx, sl.out, rl.out_cap)) &&
+                        !(rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, rl.fetch)))
+                        rc = pinned_reserve(ctx, sl.h_in, sl.h_in_cap, rl.tab_off + rl.tab_bytes + ((size_t)bbp_entropy_size(N) + 32) * B);
+                }
+                for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++) rc = dev_reserve(ctx, ctx->rnd[k].buf, round_dev_bytes(B, N, true));
+                return rc;
+            });
         // checked proving (only when it is on, and without running a check): the staging slots' and the device ring's check
         // scratch, and the aggregated verifier's buffers of every lane (the check's verifier)
         if (rc == BBP_OK && ctx->prove_check) {

@@ -202,6 +202,12 @@ struct bbp_ctx {
     };
     CheckBuf chk[CHECK_RING];
     uint32_t chk_next = 0;
+    // Scratch of bbp_prepare_round_dev / bbp_prove_round_dev calls (reduced table, per-bid results; the latter's prove-input rows and
+    // records), in rotation under the same rule: reused only after the last kernel of the call that used it last.  bbp_prove_round
+    // keeps its own in its staging slot.  ev_round: the table of a host-pointer round call has been reduced (its later chunks wait).
+    CheckBuf rnd[CHECK_RING];
+    uint32_t rnd_next = 0;
+    hipEvent_t ev_round = nullptr;
     // resident tables
     bbp::ge* gens = nullptr;           // [TAB_BASES] extended points: B_blinding, G[2048], H[2048], B, then the PAD_BASES range sums and the MRG_BASES merged bases
     bbp::niels_row* ptable = nullptr;      // [TAB_BASES * MSM_POS] affine cached 2^b * P_i, 128-byte limb rows (275 MB)
@@ -430,6 +436,9 @@ void own_hw_queues();
 int hw_queues_state();
 // pool.cpp: the host-pointer batch calls on a pool handle (block split by index over the members, results in request order)
 int32_t pool_prove_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status);
+// bbp_prove_round on a pool handle: the bids block-split like pool_prove_batch's rows, every member receives the table
+int32_t pool_prove_round(bbp_ctx* pool, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* bids, const uint8_t* entropy, uint8_t* rows_out,
+                         uint64_t* toggles_out, int32_t* status);
 // every verify form on a pool handle: the rows block-split over the members (VerifyRows::slice); group == 0: the plain entry point
 int32_t pool_verify(bbp_ctx* pool, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback);
 // capi_prove.hip: the host-pointer verify path of a context or a pool, after the entry point's screening (what a pool runs on its members)

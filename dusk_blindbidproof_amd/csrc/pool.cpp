@@ -251,6 +251,15 @@ int32_t pool_prove_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* i
     });
 }
 
+int32_t pool_prove_round(bbp_ctx* pool, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* bids, const uint8_t* entropy, uint8_t* rows_out,
+                         uint64_t* toggles_out, int32_t* status) {
+    const size_t ent_stride = bbp_entropy_size(N), row = bbp_round_row_size(N);
+    return for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
+        return bbp_prove_round(m, N, round, hi - lo, bids + (size_t)BBP_ROUND_BID_BYTES * lo, entropy ? entropy + ent_stride * lo : nullptr, rows_out + row * lo,
+                               toggles_out ? toggles_out + lo : nullptr, status + lo);
+    });
+}
+
 // every verify form: contiguous blocks of rows by index, each member's block a call of its own (a rounds call: with the whole round
 // table).  group travels as the entry point resolved it, 0 = the plain form.
 int32_t pool_verify(bbp_ctx* pool, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback) {

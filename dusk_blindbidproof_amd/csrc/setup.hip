@@ -375,7 +375,11 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
         if (cb.buf.p) (void)hipFree(cb.buf.p);
         if (cb.ev) (void)hipEventDestroy(cb.ev);
     }
-    for (hipEvent_t e : {ctx->ev_chk_fork, ctx->ev_chk_join})
+    for (auto& cb : ctx->rnd) {
+        if (cb.buf.p) (void)hipFree(cb.buf.p);
+        if (cb.ev) (void)hipEventDestroy(cb.ev);
+    }
+    for (hipEvent_t e : {ctx->ev_chk_fork, ctx->ev_chk_join, ctx->ev_round})
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_vacc)
         if (e) (void)hipEventDestroy(e);

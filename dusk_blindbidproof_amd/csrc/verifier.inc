@@ -878,4 +878,11 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8*
     return BBP_OK;
 }
 
+// The table reduction of ONE round for the prove side (capi_prove.hip, bbp_prove_round*): k_round_consts as the verifier launches it,
+// R = 1.  roff_dev: the two scalar offsets {0, 1 + N} in device memory; rblk: 1 + N scalars; rflag: one flag.
+int32_t round_consts_launch(bbp_ctx* ctx, u32 N, const u8* round_dev, const u32* roff_dev, sc* rblk, int32_t* rflag, hipStream_t s) {
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_round_consts, cdiv(1 + N, 64), 64, s, 1u, roff_dev, round_dev, rblk, rflag);
+    return BBP_OK;
+}
+
 }  // namespace bbp

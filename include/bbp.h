@@ -270,6 +270,41 @@ int32_t bbp_verify_rounds_aggregated_dev(bbp_ctx* ctx, uint32_t R, const uint32_
                                          const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, void* status_dev, uint32_t group,
                                          uint32_t* n_fallback, void* stream);
 
+/* Proving a round from raw bids: the prove side of the calls above.  What the reference's Go caller computes upstream of Proof::prove
+ *  -- the witness of bbp_witness_batch and the bid's place in the public list -- happens on the device, and seed and bid
+ * list travel once per call instead of once per proof (64 instead of 6 696 bytes per bid at N = 202).  One round per call:
+ *   round      seed(32) || pub_list(32 N): the table layout of bbp_verify_rounds with R = 1
+ *   bids       B rows of BBP_ROUND_BID_BYTES: d || k
+ *   entropy    B * bbp_entropy_size(N) as for bbp_prove_batch, or NULL (bbp_set_entropy_source; the ChaCha row is the bid's index)
+ *   rows_out   B * bbp_round_row_size(N): row i = record || score || z_img -- exactly the rows bbp_verify_rounds takes
+ * Per bid, decided on the device in every form (status[i]; a refused bid's row, score, z_img and toggle are all zero):
+ *   BBP_ERR_FORMAT    the seed is not canonical (every row: it is one of the seven scalars), or d or k is not
+ *   BBP_ERR_BAD_ARG   no list item equals x = mimc(d, mimc(k, 0)) under Scalar::from_bits (an item stored as x + l, or with bit 255
+ *                     set, matches): no witness exists -- the status bbp_prove_batch gives for toggle >= N
+ *   BBP_OK            m, x, y, y_inv, q, z_img are byte for byte bbp_witness_batch's; toggle is the LOWEST matching index; record is
+ *                     byte-equal to bbp_prove_batch's for the row d,k,y,y_inv,q,z_img,seed || pub_list || toggle under the same entropy
+ *                     row (the list bytes raw from the table); score = q
+ * Screening, before anything runs, the first failing check decides: a NULL required pointer BBP_ERR_BAD_ARG; N == 0 BBP_ERR_BAD_ARG,
+ * N > BBP_MAX_ITEMS BBP_ERR_GENS_LEN; B == 0 BBP_OK.
+ * bbp_prove_round honours the context's settings as bbp_prove_batch does on the expanded rows: entropy source, BBP_HOST_CHUNK_PROVE,
+ * checked proving (a failed record is proved once more from its bid, same entropy; a second failure raises health bit 1), the health
+ * word read back with the results, bbp_reserve (a reserved context allocates nothing in a round call).  A pool takes it (bids split by
+ * index into contiguous blocks, every member receives the table, results in request order) and refuses the two _dev forms.
+ * The _dev forms do no host screening of device data and no synchronisation; outputs are ordered on `stream`.
+ *   bbp_prepare_round_dev   the device pass alone.  Writes prove_in_dev rows in bbp_prove_batch_dev's input layout (a refused bid: the
+ *                           all-zero stand-in, so a batch keeps its geometry), tails_dev rows score || z_img (64 bytes; may be NULL),
+ *                           toggles_dev u64 (may be NULL), status_dev int32.  The next prove call on the context waits for these rows
+ *                           by itself, like bbp_prepare_bids_dev's (the same event).
+ *   bbp_prove_round_dev     that pass, bbp_prove_batch_dev, row assembly and statuses on the caller's stream; the prover's opening
+ *                           stage waits for the pass through the event, not for the caller's stream. */
+#define BBP_ROUND_BID_BYTES 64u /* d || k */
+int32_t bbp_prepare_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, void* prove_in_dev,
+                              void* tails_dev, void* toggles_dev, void* status_dev, void* stream);
+int32_t bbp_prove_round(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* bids, const uint8_t* entropy,
+                        uint8_t* rows_out, uint64_t* toggles_out, int32_t* status);
+int32_t bbp_prove_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, const void* entropy_dev,
+                            void* rows_out_dev, void* toggles_out_dev, void* status_dev, void* stream);
+
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.
  * Without it the buffers grow on demand, and a call that finds them too small frees and reallocates gigabytes under load (the
