@@ -17,6 +17,7 @@
 
 #include "../../include/bbp.h"
 #include "point.h"
+#include "msm_plan.h"
 #include "prove_plan.h"
 #include "scalar.h"
 #include "verify_rows.h"
@@ -24,10 +25,8 @@
 namespace bbp {
 
 // ---- MSM geometry (see DESIGN.md "K1") ---------------------------------------------------------------
-constexpr int MSM_NAF = 12;               // scalar recoding: width-12 NAF, odd digits |d| < 2048
+// (MSM_NAF / MSM_W / MSM_K and the split MSMs' SMALL_NAF / SMALL_K / SMALL_W are msm_plan.h's: the plan of a launch names them)
 constexpr int MSM_POS = 256;              // table rows per generator: 2^b * P for every bit position b
-constexpr int MSM_W = 22;                 // most digits one scalar can have (positions >= 12 apart, last <= 253)
-constexpr int MSM_K = 1 << (MSM_NAF - 2); // 1024 buckets: bucket k holds the digit magnitude 2k - 1
 #ifndef BBP_MSM_T
 #define BBP_MSM_T 128
 #endif
@@ -52,14 +51,7 @@ constexpr int FOLD_NAF = 9;                // width-9 NAF: odd digits |d| < 256
 constexpr int FOLD_W = 29;                 // most digits per scalar
 constexpr int FOLD_M = 128;                // buckets per class
 constexpr int FOLD_K = FOLD_CLS * FOLD_M;  // 4096 composite buckets
-// Geometry of SPLIT MSMs (round 4; small batches: an MSM is cut into sub-MSMs of a few hundred terms, one workgroup each, so that a
-// launch of a handful of MSMs fills the GPU): width-9 NAF digits into 128 buckets.  A sub-MSM of 128 terms has no use for 1024 buckets
-// (2.5 entries each), and the bucket FOLD -- 38 dependent point additions over 1024 buckets on 128 lanes, 160 us -- is the longest
-// link of a single proof's heavy chain; over 128 buckets it is 21.  More additions per term (25.6 against 19.85) in an accumulate
-// launch that takes 40 us.
-constexpr int SMALL_NAF = 9;
-constexpr int SMALL_K = 1 << (SMALL_NAF - 2);  // 128
-constexpr int SMALL_W = FOLD_W;                // most digits one scalar can have at width 9
+static_assert(SMALL_W == FOLD_W, "split MSMs recode at the generator-fold pass's width");
 // Extra table bases (internal, after the 4098 public ones): PAD_BASE0 + N - 1 = sum_{k = 418 + 3N}^{1023} H[k], the generators
 // that the first IPA round multiplies by ONE common scalar (the zero-padded multipliers n1 = 1442 + 3N .. 2047 contribute
 // b[i] h[i - 1024] = -y^1024 for every i): 582 table-row walks become one (prover.hip k_ipa_round, circuit_get).
@@ -111,12 +103,10 @@ struct bbp_ctx {
     static constexpr int MAX_SLICES = bbp::PROVE_MAX_SLICES;  // heavy-stage slices of one batch, one stream each (slice 0 = caller's stream)
     hipStream_t lane[MAX_SLICES] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t ev_join[MAX_SLICES] = {nullptr, nullptr, nullptr, nullptr}, ev_stagger[MAX_SLICES] = {nullptr, nullptr, nullptr, nullptr};
-    int sort_staged = 3;       // bit 0: generic MSMs, bit 1: the generator-fold pass sort with the scatter staged through LDS (msm.hip k_msm_sort_staged; BBP_SORT_STAGED)
+    bbp::MsmKnobs msm_knobs;    // which kernels an MSM launch takes (msm_plan.h): read from the environment by bbp_init; msm.hip plans every launch from them
     bool sort_lds_attr = false; // k_msm_sort_staged's dynamic-LDS limit has been raised on this context's device
     bool sort_lds_attr1 = false;  // ... and that of the generator-fold instance
     int debug_corrupt = 0;      // bbp_debug_corrupt_scratch: poison the next MSM launch's sorted scratch (tests)
-    int fold_half_from = 512;  // MSM launches with at least this many MSMs fold on half a wavefront per MSM (msm.hip k_msm_fold_half; BBP_FOLD_HALF_FROM)
-    int msm_small = 1;               // split MSMs (launches of fewer than 128) use width-9 digits and 128 buckets (msm.hip msm_geom<2>); BBP_MSM_SMALL=0: 1024 like the others
     std::map<const void*, int> serial_attr;
     static constexpr int PROVE_BUFS = bbp::PROVE_BUFS;  // prover batch buffers in rotation (call k of the small-batch path uses buffer k % PROVE_BUFS; large batches alternate between 0 and 1)
     hipEvent_t ev_open[PROVE_BUFS] = {}, ev_done[PROVE_BUFS] = {};

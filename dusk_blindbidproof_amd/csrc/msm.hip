@@ -278,13 +278,9 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort(const u32* __restrict__ sca
 // lane's NAF digits (cheap), places the entries of the window's buckets in an LDS image with the same LDS atomics as before, and the
 // workgroup then writes the image out as full cache lines (image: BBP_SORT_CAP entries, 84 KB).  A bucket larger than the image (adversarial scalars only) takes a pass of
 // its own with direct stores.  Entry order inside a bucket differs from the plain kernel's; sums do not care.
-#ifndef BBP_SORT_CAP
-#define BBP_SORT_CAP 21504  // two windows for a 2049-term MSM (40.7 k entries), three for 2933 terms; 16 384 (three / four, two workgroups per CU) measured 0.5 % slower per batch
-#endif
+// (BBP_SORT_CAP, SORT_CAP_WIDE, SORT_WIDE_FROM: msm_plan.h -- the plan of a launch states the image it sorts through)
 template <int MODE> struct sort_cap { static constexpr u32 V = BBP_SORT_CAP; };  // image entries (dynamic LDS: 4 bytes each) of an ordinary launch
 template <> struct sort_cap<1> { static constexpr u32 V = 8192; };
-constexpr u32 SORT_CAP_WIDE = 32768;  // ... of MSMs with more than SORT_WIDE_FROM terms (one workgroup per CU then)
-constexpr u32 SORT_WIDE_FROM = 3000;
 
 template <int MODE>
 __global__ __launch_bounds__(SORT_T) void k_msm_sort_staged(const u32* __restrict__ scal_a, const u32* __restrict__ aux, u32 n_total, u32 n_idx_sets,
@@ -908,19 +904,7 @@ __global__ __launch_bounds__(64) void k_msm_reduce(u32 n_out, u32 split, u32 ite
     if (o < n_out && j == 0) out[o] = acc;
 }
 
-// how many workgroups an MSM of n terms is cut into when the launch has only n_msm of them (fills the GPU for small batches)
-static u32 msm_split(u32 n_msm, u32 n_terms) {
-    // every sub-MSM pays a bucket fold of its own (k_msm_fold), so splitting only pays while the GPU would otherwise be mostly
-    // empty.  BBP_MSM_SPLIT_BELOW (launches with fewer MSMs than this are split) / BBP_MSM_SPLIT_TARGET (into about this many
-    // workgroups) are read once.
-    static const u32 below = [] { const char* e = getenv("BBP_MSM_SPLIT_BELOW"); return e ? (u32)atoi(e) : 128u; }();
-    static const u32 target = [] { const char* e = getenv("BBP_MSM_SPLIT_TARGET"); return e ? (u32)atoi(e) : 512u; }();
-    if (n_msm >= below) return 1;
-    u32 s = target / n_msm;
-    if (s > 16) s = 16;
-    while (s > 1 && n_terms / s < 128) s--;
-    return s ? s : 1;
-}
+// (msm_split -- how many workgroups an MSM is cut into when the launch has few of them -- is msm_plan.h's)
 
 // scratch of one launch: sorted entries (n * W u32 per MSM) | bucket end offsets (K + 1 u32) | bucket sums (K points) |
 // chunk-leading partial sums (T points)
@@ -979,7 +963,7 @@ int32_t fold_generators_launch(bbp_ctx* ctx, uint32_t n_proofs, const sc* g_dev,
     const MsmScratch m = msm_scratch_layout(scratch.p, n_work, n_sub, FOLD_W, FOLD_K, FOLD_CLS);
     {
         ScopedEvent ev(ctx, TAG_MSM_SORT, stream);
-        if (ctx->sort_staged & 2) {
+        if (ctx->msm_knobs.sort_staged & 2) {
             if (!ctx->sort_lds_attr1) {  // 36 KB static + 32 KB dynamic LDS: above the 64 KB a kernel gets without opting in (per context = per device)
                 BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sort_cap<1>::V * 4)));
                 ctx->sort_lds_attr1 = true;
@@ -1034,10 +1018,11 @@ int32_t msm_launch(bbp_ctx* ctx, uint32_t n_msm, uint32_t n_terms, const u32* sc
     DevBuf& scratch = scratch_slot ? ctx->slice_sorted[scratch_slot] : ctx->sorted;  // one scratch area per concurrently running stream
     int32_t rc = dev_reserve(ctx, scratch, msm_scratch_bytes(n_msm, n_terms));
     if (rc) return rc;
-    // device-sized launches (n_active_dev: n_msm is only the upper bound of how many MSMs there are) are never split
-    const u32 split = n_active_dev ? 1u : msm_split(n_msm, n_terms), n_sub = (n_terms + split - 1) / split;
-    const u32 n_work = n_msm * split;
-    if (split > 1 && ctx->msm_small) {  // BBP_MSM_SMALL=0: split MSMs keep the 1024-bucket geometry
+    // what this launch takes is msm_plan.h's decision (device-sized launches -- n_active_dev: n_msm is only the upper bound of how
+    // many MSMs there are -- are never split); from here on the plan is executed
+    const MsmPlan plan = plan_msm(ctx->msm_knobs, n_msm, n_terms, n_active_dev != nullptr);
+    const u32 split = plan.split, n_sub = plan.n_sub, n_work = plan.n_work;
+    if (plan.geom == MsmPlan::SMALL) {
         // SPLIT MSMs (small batches): width-9 digits into 128 buckets (context.h SMALL_*): same kernels, MODE 2
         const MsmScratch ms = msm_scratch_layout(scratch.p, n_work, n_sub, SMALL_W, SMALL_K);
         {
@@ -1069,11 +1054,8 @@ int32_t msm_launch(bbp_ctx* ctx, uint32_t n_msm, uint32_t n_terms, const u32* sc
     const MsmScratch m = msm_scratch_layout(scratch.p, n_work, n_sub, MSM_W, MSM_K);
     {
         ScopedEvent ev(ctx, TAG_MSM_SORT, stream);
-        // staged scatter: 84 KB image for the prover's 2049- / 2933-term MSMs (two / three windows); wider MSMs (the
-        // verifier's 4098 terms = 81 k entries: six windows, measured 3 % slower than the plain scatter) get a 128 KB image with bit 2 of the knob
-        const bool wide = n_sub > SORT_WIDE_FROM;
-        if ((ctx->sort_staged & 1) && (!wide || (ctx->sort_staged & 4))) {
-            const u32 cap = wide ? SORT_CAP_WIDE : sort_cap<0>::V;
+        if (plan.sort != MsmPlan::PLAIN) {  // staged scatter through an image of plan.sort_cap entries
+            const u32 cap = plan.sort_cap;
             if (!ctx->sort_lds_attr) {  // per context = per device: a process may hold one context per GPU (bbp-uds-server --devices)
                 BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SORT_CAP_WIDE * 4)));
                 ctx->sort_lds_attr = true;
@@ -1107,8 +1089,7 @@ int32_t msm_launch(bbp_ctx* ctx, uint32_t n_msm, uint32_t n_terms, const u32* sc
         ctx->vacc_valid = true;
     }
     ScopedEvent evf(ctx, TAG_MSM_FOLD, stream);
-    // many MSMs: the fold on half a wavefront per MSM (fewer wave-instructions); few: the 128-lane fold (shorter chain).  BBP_FOLD_HALF_FROM
-    if (n_work >= (u32)ctx->fold_half_from)
+    if (plan.fold == MsmPlan::HALF)  // (BBP_FOLD_HALF_FROM)
         hipLaunchKernelGGL(k_msm_fold_half, dim3((n_work + 1) / 2), dim3(64), 0, stream, m.cursor, m.bsum, m.psum, split > 1 ? m.tmp : out_points_dev,
                            n_work, n_active_dev);
     else
@@ -1119,7 +1100,7 @@ int32_t msm_launch(bbp_ctx* ctx, uint32_t n_msm, uint32_t n_terms, const u32* sc
         BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_vacc[ctx->vacc_seq % bbp_ctx::VACC_RING], stream));
         ctx->vacc_valid = true;
     }
-    if (split > 1) {
+    if (plan.reduce) {
         hipLaunchKernelGGL(k_msm_reduce, dim3((n_msm * REDUCE_L + 63) / 64), dim3(64), lds_token(ctx), stream, n_msm, split, 1u, m.tmp, out_points_dev);
         BBP_HIP_TRY(ctx, hipGetLastError());
     }

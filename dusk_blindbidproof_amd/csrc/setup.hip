@@ -268,9 +268,7 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
     if (const char* e = getenv("BBP_VERIFY_AGGREGATE")) ctx->verify_group = atoi(e) > 1 ? (uint32_t)atoi(e) : 0u;
     ctx->knobs = ProveKnobs::from_env();  // every prove-schedule knob: prove_plan.h lists the names
     if (const char* e = getenv("BBP_VARBASE_LANES")) ctx->varbase_lanes = atoi(e) < 64 ? 64 : atoi(e);
-    if (const char* e = getenv("BBP_MSM_SMALL")) ctx->msm_small = atoi(e) != 0;
-    if (const char* e = getenv("BBP_SORT_STAGED")) ctx->sort_staged = atoi(e) & 7;
-    if (const char* e = getenv("BBP_FOLD_HALF_FROM")) ctx->fold_half_from = atoi(e) < 1 ? 1 : atoi(e);
+    ctx->msm_knobs = MsmKnobs::from_env();  // BBP_SORT_STAGED, BBP_FOLD_HALF_FROM, BBP_MSM_SMALL and the split knobs: msm_plan.h
     for (int i = 0; i < bbp_ctx::PROVE_BUFS; i++) {
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_entry[i], hipEventDisableTiming));
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_open[i], hipEventDisableTiming));

@@ -6,6 +6,7 @@
 
 #include "../dusk_blindbidproof_amd/csrc/keccak.h"
 #include "../dusk_blindbidproof_amd/csrc/keccak_wave.h"
+#include "../dusk_blindbidproof_amd/csrc/msm_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/point.h"
 #include "../dusk_blindbidproof_amd/csrc/prove_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
@@ -285,6 +286,64 @@ int hc_prove_knob_from_env(const char* name, const char* text, int which) {
                      k.rng_dpp, k.rng_block, k.serial_block, k.serial_lds, k.tr_wave_below, k.ipa_wide_below, k.commit_split_below, k.witness_native,
                      k.tail_small_below, k.tail_round, k.stagger_mode, k.trace_prove};
     return v[which];
+}
+
+// The plan of one MSM launch (csrc/msm_plan.h).  knobs: n_knobs (environment name, text) pairs applied over the defaults through
+// MsmKnobs::set, clamps included; -1: a name is no MSM knob.  out: 0 split, 1 n_sub, 2 n_work, 3 geom, 4 sort, 5 sort_cap, 6 fold,
+// 7 reduce, 8 K, 9 W, 10 the recoding's width.
+int hc_msm_plan(const char* const* knobs, int n_knobs, uint32_t n_msm, uint32_t n_terms, int device_sized, int64_t* out) {
+    MsmKnobs k;
+    for (int i = 0; i < n_knobs; i++)
+        if (!k.set(knobs[2 * i], knobs[2 * i + 1])) return -1;
+    const MsmPlan p = plan_msm(k, n_msm, n_terms, device_sized != 0);
+    const int64_t v[11] = {p.split, p.n_sub, p.n_work, p.geom, p.sort, p.sort_cap, p.fold, p.reduce, p.K(), p.W(), p.naf()};
+    memcpy(out, v, sizeof v);
+    return 0;
+}
+// one knob as MsmKnobs::from_env reads it from an environment that holds name=text (the variable is set for the call only; the two
+// split knobs are the process's, read once: they show their defaults here)
+int hc_msm_knob_from_env(const char* name, const char* text, int which) {
+    MsmKnobs::process();
+    setenv(name, text, 1);
+    const MsmKnobs k = MsmKnobs::from_env();
+    unsetenv(name);
+    const int v[] = {k.sort_staged, k.fold_half_from, k.msm_small, (int)k.split_below, (int)k.split_target};
+    return v[which];
+}
+// msm_split over every launch of n_msm = 1..max_msm MSMs of n_terms = 1..max_terms terms under the default knobs: how many
+// (n_msm, n_terms) break a rule -- the sub-MSMs cover the terms, none lies wholly past the end, at most MSM_SPLIT_MAX of them, a
+// split MSM's sub-MSMs have 128 terms or more; first_bad: the first such pair.  *max_split: the largest split seen.
+int hc_msm_split_sweep(uint32_t max_msm, uint32_t max_terms, uint32_t* first_bad, uint32_t* max_split) {
+    const MsmKnobs k;
+    int bad = 0;
+    *max_split = 0;
+    for (uint32_t m = 1; m <= max_msm; m++)
+        for (uint32_t n = 1; n <= max_terms; n++) {
+            const MsmPlan p = plan_msm(k, m, n, false);
+            const bool ok = p.split >= 1 && p.split == msm_split(k, m, n) && (uint64_t)p.split * p.n_sub >= n && (uint64_t)(p.split - 1) * p.n_sub < n &&
+                            p.split <= 16 && (p.split == 1 || p.n_sub >= 128) && p.n_work == m * p.split;
+            if (p.split > *max_split) *max_split = p.split;
+            if (!ok && !bad++) first_bad[0] = m, first_bad[1] = n;
+        }
+    return bad;
+}
+// entries per bucket (|d| + 1) / 2 of n scalars under the product's recoder (width 12 or 9), and how many of them are negative digits;
+// -1: a digit fell outside buckets 1..K
+int hc_msm_histogram(int width, uint32_t n, const uint8_t* scalars, uint32_t K, uint32_t* hist, uint32_t* neg_hist) {
+    int rc = 0;
+    for (uint32_t i = 0; i < n; i++) {
+        u32 w[8];
+        ld(w, scalars + 32 * (size_t)i, 8);
+        auto emit = [&](u32, u32 mag, u32 neg) {
+            const u32 b = (mag + 1) >> 1;
+            if (b < 1 || b > K) { rc = -1; return; }
+            hist[b]++;
+            neg_hist[b] += neg;
+        };
+        if (width == 12) sc_for_each_naf_digit<12>(w, emit);
+        else sc_for_each_naf_digit<9>(w, emit);
+    }
+    return rc;
 }
 
 // The bit-interleaved form the one-wavefront Keccak keeps its words in (keccak_wave.h): even / odd bits of x as two 32-bit halves.

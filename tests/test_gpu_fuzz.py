@@ -6,12 +6,11 @@ import random
 
 import pytest
 
-from oracle.ref_py import ristretto as rs
+from tests import msm_cases as mc
 from tests import oracle_c
 from tests.test_gpu_prove_verify import _synth_batch
 
 pytestmark = pytest.mark.gpu
-L = rs.L
 
 
 @pytest.fixture(scope="module")
@@ -19,51 +18,12 @@ def oc(built):
     return oracle_c.load(built.build_oracle())
 
 
-def _pattern_scalar(rnd):
-    k = rnd.randrange(12)
-    if k == 0:
-        return 0
-    if k == 1:
-        return 1
-    if k == 2:
-        return L - 1 - rnd.randrange(3)
-    if k == 3:
-        return 1 << rnd.randrange(252)
-    if k == 4:
-        return ((1 << rnd.randrange(2, 252)) - 1) % L            # run of ones: one long carry chain in the NAF
-    if k == 5:
-        return int("10" * 126, 2) >> rnd.randrange(8)             # alternating bits
-    if k == 6:
-        return (0x7FF << rnd.randrange(0, 240)) % L               # a digit at the NAF magnitude limit
-    if k == 7:
-        return (0x801 << rnd.randrange(0, 240)) % L
-    if k == 8:
-        return rnd.getrandbits(rnd.randrange(1, 64))              # small values (witness-like)
-    return rnd.randrange(L)
-
-
-@pytest.mark.parametrize("seed", [1, 2, 3])
+@pytest.mark.parametrize("seed", mc.FUZZ_SEEDS)
 def test_msm_fuzz(ctx, bbp, oc, seed):
-    rnd = random.Random(1000 + seed)
-    for case in range(14):
-        layout = rnd.choice([bbp.LAYOUT_BLIND_G_H, bbp.LAYOUT_BLIND_G])
-        m = rnd.choice([1, 2, 3, 17, 63, 64, 65, 127, 128, 129, 300, 1023, 1466, 2048]) if case % 2 else rnd.randrange(1, 2049)
-        n_terms = 1 + (2 * m if layout == bbp.LAYOUT_BLIND_G_H else m)
-        B = rnd.choice([1, 2, 3, 5, 31, 64, 127, 128, 129, 200]) if n_terms < 700 else rnd.choice([1, 2, 3, 5, 9])
-        repeated = _pattern_scalar(rnd)
-        rows = []
-        for b in range(B):
-            style = rnd.randrange(4)
-            if style == 0:
-                row = [_pattern_scalar(rnd) for _ in range(n_terms)]
-            elif style == 1:
-                row = [repeated] * n_terms                           # every term in one bucket
-            elif style == 2:
-                row = [0] * n_terms                                  # empty MSM -> identity
-                row[rnd.randrange(n_terms)] = _pattern_scalar(rnd)
-            else:
-                row = [rnd.randrange(L) for _ in range(n_terms)]
-            rows.append(b"".join(rs.sc_bytes(v) for v in row))
+    """fourteen random shapes per seed (tests/msm_cases.py fuzz_cases): launches of fewer than 700 terms with up to 200 MSMs -- split
+    or through the staged sort, no bucket near its image -- and wider ones of at most 9 MSMs, all split"""
+    for case, layout, n_terms, B, int_rows in mc.fuzz_cases(seed):
+        rows = [mc.row_bytes(row) for row in int_rows]
         got = ctx.msm_batch(B, n_terms, b"".join(rows), layout)
         exp = oc.msm_layout_many(rows, [n_terms] * B, [layout] * B, threads=8)
         assert got == exp, (seed, case, layout, n_terms, B)
@@ -71,11 +31,13 @@ def test_msm_fuzz(ctx, bbp, oc, seed):
 
 def test_msm_fuzz_half_wavefront_fold(bbp, oc):
     """k_msm_fold_half (two MSMs per wavefront, 32 lanes x 32 buckets) serves launches of 512 MSMs and more by default; with
-    BBP_FOLD_HALF_FROM=1 every launch uses it: odd MSM counts (idle upper half), split MSMs, one-term and empty MSMs, every term in one
-    bucket (runs of chunk-leading partial sums), and the full-width 4097-term shape -- all against the C oracle."""
+    BBP_FOLD_HALF_FROM=1 every unsplit launch uses it: odd MSM counts (idle upper half), one-term and empty MSMs, every term in one
+    bucket (runs of chunk-leading partial sums), and the full-width 4097-term shape as a launch of 128 MSMs -- all against the C
+    oracle.  The list's split shapes (tests/msm_cases.py HALF_FOLD_SHAPES names each shape's fold) fold with k_msm_fold<2> as ever:
+    the knob must not disturb them."""
     import os
     old = os.environ.get("BBP_FOLD_HALF_FROM")
-    os.environ["BBP_FOLD_HALF_FROM"] = "1"
+    os.environ.update(mc.HALF_FOLD_KNOBS)
     try:
         c2 = bbp.Context(0)
     finally:
@@ -84,25 +46,8 @@ def test_msm_fuzz_half_wavefront_fold(bbp, oc):
         else:
             os.environ["BBP_FOLD_HALF_FROM"] = old
     try:
-        rnd = random.Random(77)
-        shapes = [(bbp.LAYOUT_BLIND_G_H, 1, 1), (bbp.LAYOUT_BLIND_G_H, 3, 3), (bbp.LAYOUT_BLIND_G, 34, 5), (bbp.LAYOUT_BLIND_G_H, 129, 127),
-                  (bbp.LAYOUT_BLIND_G_H, 257, 200), (bbp.LAYOUT_BLIND_G, 1467, 9), (bbp.LAYOUT_BLIND_G_H, 2933, 3), (bbp.LAYOUT_BLIND_G_H, 4097, 2),
-                  (bbp.LAYOUT_BLIND_G_H, 2049, 65)]
-        for layout, n_terms, B in shapes:
-            repeated = _pattern_scalar(rnd)
-            rows = []
-            for b in range(B):
-                style = (b + n_terms) % 4
-                if style == 0:
-                    row = [_pattern_scalar(rnd) for _ in range(n_terms)]
-                elif style == 1:
-                    row = [repeated] * n_terms
-                elif style == 2:
-                    row = [0] * n_terms
-                    row[rnd.randrange(n_terms)] = _pattern_scalar(rnd)
-                else:
-                    row = [rnd.randrange(L) for _ in range(n_terms)]
-                rows.append(b"".join(rs.sc_bytes(v) for v in row))
+        for layout, n_terms, B, int_rows in mc.half_fold_cases():
+            rows = [mc.row_bytes(row) for row in int_rows]
             got = c2.msm_batch(B, n_terms, b"".join(rows), layout)
             exp = oc.msm_layout_many(rows, [n_terms] * B, [layout] * B, threads=8)
             assert got == exp, (layout, n_terms, B)
@@ -111,37 +56,19 @@ def test_msm_fuzz_half_wavefront_fold(bbp, oc):
         c2.close()
 
 
-@pytest.mark.parametrize("knobs", [{}, {"BBP_SORT_STAGED": "7"}, {"BBP_SORT_STAGED": "0"}])
-def test_msm_sort_oversized_bucket(bbp, oc, knobs):
-    """k_msm_sort_staged places the entries of a window of buckets in an LDS image of 16 384 entries (32 768 for MSMs wider than 3000
-    terms with bit 2 of BBP_SORT_STAGED); a single bucket larger than the image takes a pass of its own with direct stores.  The scalar
-    sum_j 2^(13 j) has 19 NAF digits of magnitude 1: with every term equal to it, bucket 1 holds 19 n entries (55 727 at n = 2933,
-    77 843 at 4097) and every other bucket is empty; a second pattern puts two thirds of the terms there and spreads the rest."""
-    import os
-    old = {k: os.environ.get(k) for k in knobs}
-    os.environ.update(knobs)
+def test_msm_sort_oversized_bucket(bbp, oc):
+    """Giant buckets in the SPLIT geometry: the scalar sum_j 2^(13 j) has 19 digits of magnitude 1 at width 9 as at width 12, so with
+    every term equal to it bucket 1 of every sub-MSM holds all its entries (19 n_sub) and every other bucket is empty; a second
+    pattern puts two thirds of the terms there and spreads the rest.  All three launches are cut 16 ways into the small geometry
+    (k_msm_sort<2>: the plain scatter, whatever BBP_SORT_STAGED says -- the ledger in test_msm_plan_host.py shows it), so the knob is
+    not varied here; the staged sort's direct pass and its images are test_gpu_msm_paths.py's."""
+    c2 = bbp.Context(0)
     try:
-        c2 = bbp.Context(0)
-    finally:
-        for k, v in old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    try:
-        ones = sum(1 << (13 * j) for j in range(19))
-        rnd = random.Random(5)
-        for n_terms, B in ((2933, 3), (2049, 4), (4097, 2)):
-            rows = []
-            for b in range(B):
-                if b % 2 == 0:
-                    row = [ones] * n_terms
-                else:
-                    row = [ones if i % 3 else rnd.randrange(L) for i in range(n_terms)]
-                rows.append(b"".join(rs.sc_bytes(v) for v in row))
+        for n_terms, B, int_rows in mc.oversized_split_cases():
+            rows = [mc.row_bytes(row) for row in int_rows]
             got = c2.msm_batch(B, n_terms, b"".join(rows), bbp.LAYOUT_BLIND_G_H)
             exp = oc.msm_layout_many(rows, [n_terms] * B, [bbp.LAYOUT_BLIND_G_H] * B, threads=8)
-            assert got == exp, (knobs, n_terms)
+            assert got == exp, n_terms
         assert c2.health() == 0
     finally:
         c2.close()
