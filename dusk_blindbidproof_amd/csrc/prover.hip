@@ -32,6 +32,7 @@
 #include "batch.h"
 #include "hosthash.h"
 #include "keccak_wave.h"
+#include "scalarmul.h"
 #include "witness.h"
 
 namespace bbp {
@@ -187,31 +188,7 @@ __global__ void k_fill_mimc(u32 B, u32 n_cst, const sc* __restrict__ mimc, sc* _
 // ---------------------------------------------------------------------------------------------------------------
 // K2: Pedersen commitments through the radix-16 comb (64 signed digits per scalar, 8 cached multiples each)
 // ---------------------------------------------------------------------------------------------------------------
-__device__ ge comb_mul_add(ge acc, const niels_packed* __restrict__ comb_base, const sc& s) {
-    u32 carry = 0;
-    for (int j = 0; j < 64; j++) {
-        u32 d = ((s.v[j >> 3] >> (4 * (j & 7))) & 15u) + carry;
-        carry = d > 8u;
-        u32 mag = carry ? 16u - d : d;
-        if (mag) {
-            const uint4* q = reinterpret_cast<const uint4*>(comb_base + (size_t)j * 8 + (mag - 1));
-            uint4 q0 = q[0], q1 = q[1], q2 = q[2], q3 = q[3], q4 = q[4], q5 = q[5];
-            ge_niels n;
-            n.ypx = BBP_FE_LIT(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w);
-            n.ymx = BBP_FE_LIT(q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w);
-            n.xy2d = BBP_FE_LIT(q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w);
-            if (carry) {
-                fe t = n.ypx;
-                n.ypx = n.ymx;
-                n.ymx = t;
-                n.xy2d = fe_neg(n.xy2d);
-            }
-            acc = ge_madd(acc, n);
-        }
-    }
-    return acc;  // canonical scalars are < 2^253: the top digit never carries out
-}
-
+// comb_mul_add, comb_mul_add_part (COMMIT_L lanes per commitment) and commit_group_sum: scalarmul.h
 // commitment c of proof p: values[p*stride_v + c], blindings[p*stride_b + c] -> out[p*out_stride + c]
 __global__ BBP_LANE_KERNEL void k_commit(u32 count, u32 per_proof, const sc* __restrict__ values, const sc* __restrict__ blindings, u32 stride_v,
                          u32 stride_b, const niels_packed* __restrict__ comb, ge* __restrict__ out, u32 out_stride) {
@@ -225,65 +202,6 @@ __global__ BBP_LANE_KERNEL void k_commit(u32 count, u32 per_proof, const sc* __r
     out[(size_t)p * out_stride + c] = acc;
 }
 
-// Small launches: a commitment on COMMIT_L lanes.  One lane walks 2 x 64 comb digits (~120 dependent mixed additions: 380 us for
-// ONE proof's twelve commitments, and again for its five T commitments); here lane q of a group takes the digit positions
-// j = q (mod COMMIT_L) of both scalars (every lane recodes the whole scalar -- the carries -- which is cheap) and three shuffle
-// steps add the partial sums.  The sum is the same group element, its encoding the same bytes.
-constexpr int COMMIT_L = 8;
-__device__ ge comb_mul_add_part(ge acc, const niels_packed* __restrict__ comb_base, const sc& s, u32 q) {
-    // the signed radix-16 digits of the whole scalar first (the carries are a chain): magnitudes as nibbles, signs as a bit mask;
-    // then the lane's own eight positions q, q + 8, ... -- every lane of the wavefront adds at the same time
-    u32 mags[8];
-    u64 negs = 0;
-    u32 carry = 0;
-#pragma unroll
-    for (int w = 0; w < 8; w++) {
-        u32 mw = 0;
-#pragma unroll
-        for (int n = 0; n < 8; n++) {
-            const u32 d = ((s.v[w] >> (4 * n)) & 15u) + carry;
-            carry = d > 8u;
-            mw |= (carry ? 16u - d : d) << (4 * n);
-            negs |= (u64)carry << (8 * w + n);
-        }
-        mags[w] = mw;
-    }
-#pragma unroll 1
-    for (int i = 0; i < 64 / COMMIT_L; i++) {
-        u32 mw = mags[0];
-#pragma unroll
-        for (int w = 1; w < 8; w++) mw = i == w ? mags[w] : mw;
-        const u32 j = q + (u32)COMMIT_L * (u32)i, mag = (mw >> (4 * q)) & 15u, neg = (u32)(negs >> j) & 1u;
-        if (mag) {
-            const uint4* qq = reinterpret_cast<const uint4*>(comb_base + (size_t)j * 8 + (mag - 1));
-            uint4 q0 = qq[0], q1 = qq[1], q2 = qq[2], q3 = qq[3], q4 = qq[4], q5 = qq[5];
-            ge_niels n;
-            n.ypx = BBP_FE_LIT(q0.x, q0.y, q0.z, q0.w, q1.x, q1.y, q1.z, q1.w);
-            n.ymx = BBP_FE_LIT(q2.x, q2.y, q2.z, q2.w, q3.x, q3.y, q3.z, q3.w);
-            n.xy2d = BBP_FE_LIT(q4.x, q4.y, q4.z, q4.w, q5.x, q5.y, q5.z, q5.w);
-            if (neg) {
-                fe t = n.ypx;
-                n.ypx = n.ymx;
-                n.ymx = t;
-                n.xy2d = fe_neg(n.xy2d);
-            }
-            acc = ge_madd(acc, n);
-        }
-    }
-    return acc;
-}
-__device__ __forceinline__ ge commit_group_sum(ge acc) {  // lane 0 of every COMMIT_L-lane group ends up with the group's sum
-#pragma unroll 1
-    for (int d = COMMIT_L / 2; d >= 1; d >>= 1) {
-        ge other;
-        const u32* w = reinterpret_cast<const u32*>(&acc);
-        u32* o = reinterpret_cast<u32*>(&other);
-#pragma unroll
-        for (int i = 0; i < GE_WORDS; i++) o[i] = (u32)__shfl_down((int)w[i], d, 64);
-        acc = ge_add(acc, other);  // (lanes whose partner lies in the next group add something nobody reads)
-    }
-    return acc;
-}
 __global__ BBP_LANE_KERNEL void k_commit_split(u32 count, u32 per_proof, const sc* __restrict__ values, const sc* __restrict__ blindings, u32 stride_v,
                                                u32 stride_b, const niels_packed* __restrict__ comb, ge* __restrict__ out, u32 out_stride) {
     const u32 t = blockIdx.x * blockDim.x + threadIdx.x, g = t / COMMIT_L, q = t % COMMIT_L;
@@ -1106,73 +1024,8 @@ __global__ __launch_bounds__(BLK) void k_ipa_round(u32 round, u32 n1, sc* __rest
 // ---------------------------------------------------------------------------------------------------------------
 // IPA tail on explicit folded generators (rounds FOLD_ROUND..11, vectors of length <= 32)
 // ---------------------------------------------------------------------------------------------------------------
-// signed radix-16 digits of a canonical scalar: d[0..63] in [-8, 8], d[64] = final carry
-__device__ void sc_radix16(const sc& s, int8_t* d) {
-    u32 carry = 0;
-    for (int j = 0; j < 64; j++) {
-        u32 v = ((s.v[j >> 3] >> (4 * (j & 7))) & 15u) + carry;
-        carry = v > 8u;
-        d[j] = (int8_t)(carry ? (int)v - 16 : (int)v);
-    }
-    d[64] = (int8_t)carry;
-}
-
-// s1*P1 + s2*P2 with shared doublings; tab: 16 points of scratch owned by the calling lane (1..8 multiples of each point)
-__device__ ge ge_double_scalarmul(const sc& s1, const ge& P1, const sc& s2, const ge& P2, ge* tab, bool two) {
-    tab[0] = P1;
-    ge cur = P1;
-    for (int i = 1; i < 8; i++) {
-        cur = ge_add(cur, P1);
-        tab[i] = cur;
-    }
-    if (two) {
-        tab[8] = P2;
-        cur = P2;
-        for (int i = 1; i < 8; i++) {
-            cur = ge_add(cur, P2);
-            tab[8 + i] = cur;
-        }
-    }
-    int8_t d1[65], d2[65];
-    sc_radix16(s1, d1);
-    if (two) sc_radix16(s2, d2);
-    ge acc = ge_identity();
-    for (int j = 64; j >= 0; j--) {
-        if (j != 64) {
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-        }
-        int a = d1[j];
-        if (a != 0) {
-            ge q = tab[(a > 0 ? a : -a) - 1];
-            if (a < 0) q = ge_neg(q);
-            acc = ge_add(acc, q);
-        }
-        if (two) {
-            int b = d2[j];
-            if (b != 0) {
-                ge q = tab[8 + (b > 0 ? b : -b) - 1];
-                if (b < 0) q = ge_neg(q);
-                acc = ge_add(acc, q);
-            }
-        }
-    }
-    return acc;
-}
-
-// Tail tables: for a point P the multiples m * 2^(w k) * P, m = 1..8, k = 0..TAIL_PIECES-1, w = 256 / TAIL_PIECES.  A scalar
-// multiplication over such a table is (w - 4) doublings + 64 additions (signed radix-16 digits, the pieces share the doublings)
-// instead of 252 + 64 + 7, and the tables of the 64 materialised generators are built once and used by all five tail rounds.
-// Four 64-bit pieces: 60 doublings per multiplication, 192 to build a table; eight 32-bit pieces: 28 and 224 (+ 28 additions): the
-// tail launches are chain-bound, a table serves five rounds.
-#ifndef BBP_TAIL_PIECES
-#define BBP_TAIL_PIECES 8
-#endif
-constexpr int TAIL_PIECES = BBP_TAIL_PIECES, TAIL_PIECE_BITS = 256 / TAIL_PIECES, TAIL_DIGITS = TAIL_PIECE_BITS / 4;
-constexpr int TAIL_TAB = 8 * TAIL_PIECES;
-static_assert(TAIL_PIECES == 4 || TAIL_PIECES == 8 || TAIL_PIECES == 16, "tail table geometry");
+// the tail tables' geometry (TAIL_PIECES) and the carry-mask walk over them (ge_scalarmul_pieces, ge_scalarmul_pieces_pair): scalarmul.h;
+// k_tail_tables keeps its own loop (scalarmul.h tail_table_build is the same loop for the tests: called from here the kernel compiled differently)
 // (64-lane workgroups and a 2-3 waves/SIMD register budget: with the default 128-VGPR cap this kernel spilled 216 registers)
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 3))) void k_tail_tables(u32 count, const ge* __restrict__ pts, ge* __restrict__ tab) {
     BBP_THIN_PRIO();
@@ -1194,76 +1047,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2, 3))) void
             for (int i = 0; i < TAIL_PIECE_BITS; i++) P = ge_dbl(P);
         }
     }
-}
-
-// pieces k_lo <= k < k_hi only: the partial product sum_k 2^(w k) * (piece k of s) * P
-__device__ ge ge_scalarmul_pieces(const sc& s, const ge* __restrict__ T, int k_lo = 0, int k_hi = TAIL_PIECES) {
-    // carry mask of the signed radix-16 recoding: bit j = carry INTO digit j (a canonical scalar never carries out of digit 63)
-    u64 cm = 0;
-    u32 c = 0;
-    for (int j = 0; j < 64; j++) {
-        u32 v = ((s.v[j >> 3] >> (4 * (j & 7))) & 15u) + c;
-        c = v > 8u;
-        if (j < 63) cm |= (u64)c << (j + 1);
-    }
-    ge acc = ge_identity();
-    for (int r = TAIL_DIGITS - 1; r >= 0; r--) {
-        if (r != TAIL_DIGITS - 1) {
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-        }
-        for (int k = k_lo; k < k_hi; k++) {
-            const int j = TAIL_DIGITS * k + r;
-            const int d = (int)((s.v[j >> 3] >> (4 * (j & 7))) & 15u) + (int)((cm >> j) & 1u) - 16 * (int)((j < 63) ? ((cm >> (j + 1)) & 1u) : 0u);
-            if (d != 0) {
-                ge q = T[8 * k + (d > 0 ? d : -d) - 1];
-                if (d < 0) q = ge_neg(q);
-                acc = ge_add(acc, q);
-            }
-        }
-    }
-    return acc;
-}
-
-// s1 * P1 + s2 * P2 over tail tables T1, T2 with ONE doubling chain (the merged form of k_tail_lr: two terms per lane)
-__device__ ge ge_scalarmul_pieces_pair(const sc& s1, const ge* __restrict__ T1, const sc& s2, const ge* __restrict__ T2) {
-    u64 cm1 = 0, cm2 = 0;
-    u32 c1 = 0, c2 = 0;
-    for (int j = 0; j < 64; j++) {
-        const u32 v1 = ((s1.v[j >> 3] >> (4 * (j & 7))) & 15u) + c1, v2 = ((s2.v[j >> 3] >> (4 * (j & 7))) & 15u) + c2;
-        c1 = v1 > 8u;
-        c2 = v2 > 8u;
-        if (j < 63) {
-            cm1 |= (u64)c1 << (j + 1);
-            cm2 |= (u64)c2 << (j + 1);
-        }
-    }
-    ge acc = ge_identity();
-    for (int r = TAIL_DIGITS - 1; r >= 0; r--) {
-        if (r != TAIL_DIGITS - 1) {
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-            acc = ge_dbl(acc);
-        }
-#pragma unroll 1
-        for (int kk = 0; kk < 2 * TAIL_PIECES; kk++) {  // piece k of scalar 1, then piece k of scalar 2: one addition site
-            const int k = kk >> 1;
-            const bool second = kk & 1;
-            const int j = TAIL_DIGITS * k + r;
-            const u32 word = second ? s2.v[j >> 3] : s1.v[j >> 3];
-            const u64 cm = second ? cm2 : cm1;
-            const int d = (int)((word >> (4 * (j & 7))) & 15u) + (int)((cm >> j) & 1u) - 16 * (int)((j < 63) ? ((cm >> (j + 1)) & 1u) : 0u);
-            if (d != 0) {
-                ge q = (second ? T2 : T1)[8 * k + (d > 0 ? d : -d) - 1];
-                if (d < 0) q = ge_neg(q);
-                acc = ge_add(acc, q);
-            }
-        }
-    }
-    return acc;
 }
 
 // The tail never folds points either: like the main rounds it keeps per-generator factor scalars (gg, hh: 32 each, stored in

@@ -16,6 +16,7 @@
 #include "../dusk_blindbidproof_amd/csrc/keccak_wave.h"
 #include "../dusk_blindbidproof_amd/csrc/point.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
+#include "../dusk_blindbidproof_amd/csrc/scalarmul.h"
 
 using namespace bbp;
 
@@ -295,6 +296,161 @@ __global__ void k_merlin_rng_bulk(int n, const u8* w, int w_len, const u8* ent32
     ok[i] = good ? 1 : 0;
 }
 
+// ---- radix-16 scalar multiplication (csrc/scalarmul.h) -------------------------------------------------------------------------
+// Points come in as Ristretto encodings and are decoded once per DISTINCT point (ok[i] = 1 when point i decoded); the tables are
+// built on the device by the product's own builders; an item names its points by index.  Indices and piece ranges are checked on
+// the host before anything is launched.
+constexpr int STRAUS_MAX = 4;  // points per dc_straus item
+
+__device__ __forceinline__ bool ld_point(ge& P, const u8* p32) {
+    u32 w[8];
+    ld_words(w, p32, 8);
+    return ge_decode_words(P, w);
+}
+__device__ __forceinline__ sc ld_scalar(const u8* s32) {
+    sc s;
+    ld_words(s.v, s32, 8);
+    return s;
+}
+
+// thread (b, j): column j of base b's comb, as setup.hip k_build_comb
+__global__ void k_comb_tables(int nb, const u8* bases32, niels_packed* comb, i32* ok) {
+    const int t = item();
+    if (t >= nb * 64) return;
+    const int b = t / 64, j = t % 64;
+    ge P;
+    const bool good = ld_point(P, bases32 + 32 * (size_t)b);
+    if (j == 0) ok[b] = good ? 1 : 0;
+    comb_build_column(P, (u32)j, comb + ((size_t)b * 64 + j) * 8);
+}
+// one lane per commitment, as prover.hip k_commit
+__global__ void k_comb_one(int n, const niels_packed* comb, const u32* idx0, const u32* idx1, const u8* v32, const u8* b32, u8* out32) {
+    const int i = item();
+    if (i >= n) return;
+    ge acc = comb_mul_add(ge_identity(), comb + (size_t)idx0[i] * 64 * 8, ld_scalar(v32 + 32 * (size_t)i));
+    acc = comb_mul_add(acc, comb + (size_t)idx1[i] * 64 * 8, ld_scalar(b32 + 32 * (size_t)i));
+    ge_encode(out32 + 32 * (size_t)i, acc);
+}
+// COMMIT_L lanes per commitment, as prover.hip k_commit_split: whole wavefronts, the last group clamped
+__global__ __launch_bounds__(64) void k_comb_split(u32 n, const niels_packed* comb, const u32* idx0, const u32* idx1, const u8* v32, const u8* b32, u8* out32) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x, g = t / COMMIT_L, q = t % COMMIT_L;
+    const u32 gi = g < n ? g : n - 1;  // whole wavefronts reach the shuffles
+    ge acc = comb_mul_add_part(ge_identity(), comb + (size_t)idx0[gi] * 64 * 8, ld_scalar(v32 + 32 * (size_t)gi), q);
+    acc = comb_mul_add_part(acc, comb + (size_t)idx1[gi] * 64 * 8, ld_scalar(b32 + 32 * (size_t)gi), q);
+    acc = commit_group_sum(acc);
+    if (q == 0 && g < n) ge_encode(out32 + 32 * (size_t)g, acc);
+}
+// thread per table entry: loaded as comb_mul_add loads it, back to a point, encoded
+__global__ void k_comb_unpack(int n_entries, const niels_packed* comb, u8* out32) {
+    const int i = item();
+    if (i >= n_entries) return;
+    ge_niels e;
+    BBP_COMB_LOAD(e, comb + i);
+    ge_encode(out32 + 32 * (size_t)i, ge_from_niels(e));
+}
+
+// thread per point, as prover.hip k_tail_tables
+__global__ void k_tail_tabs(int np, const u8* pts32, ge* tab, i32* ok) {
+    const int t = item();
+    if (t >= np) return;
+    ge P;
+    ok[t] = ld_point(P, pts32 + 32 * (size_t)t) ? 1 : 0;
+    tail_table_build(P, tab + (size_t)t * TAIL_TAB);
+}
+__global__ void k_tail(int n, const ge* tab, const u32* pidx, const u8* s32, const i32* k_lo, const i32* k_hi, u8* out32) {
+    const int i = item();
+    if (i >= n) return;
+    ge_encode(out32 + 32 * (size_t)i, ge_scalarmul_pieces(ld_scalar(s32 + 32 * (size_t)i), tab + (size_t)pidx[i] * TAIL_TAB, k_lo[i], k_hi[i]));
+}
+__global__ void k_tail_pair(int n, const ge* tab, const u32* pidx1, const u8* s1, const u32* pidx2, const u8* s2, u8* out32) {
+    const int i = item();
+    if (i >= n) return;
+    ge_encode(out32 + 32 * (size_t)i, ge_scalarmul_pieces_pair(ld_scalar(s1 + 32 * (size_t)i), tab + (size_t)pidx1[i] * TAIL_TAB,
+                                                                ld_scalar(s2 + 32 * (size_t)i), tab + (size_t)pidx2[i] * TAIL_TAB));
+}
+
+// thread per point: 1P..8P; thread per (item, slot): the digit words
+__global__ void k_straus_tabs(int np, const u8* pts32, ge* tab, i32* ok) {
+    const int t = item();
+    if (t >= np) return;
+    ge P;
+    ok[t] = ld_point(P, pts32 + 32 * (size_t)t) ? 1 : 0;
+    straus_table(tab + (size_t)t * 8, P);
+}
+__global__ void k_straus_recode(int n, const i32* cnt, const u8* s32, u32* sp) {
+    const int t = item();
+    if (t >= n * STRAUS_MAX) return;
+    if (t % STRAUS_MAX < cnt[t / STRAUS_MAX]) straus_recode(sp + 8 * (size_t)t, ld_scalar(s32 + 32 * (size_t)t));
+}
+// digits 63..0 with four doublings between, as k_varbase
+__global__ void k_straus_top(int n, const i32* cnt, const ge* tab, const u32* pidx, const u32* sp, u8* out32) {
+    const int i = item();
+    if (i >= n) return;
+    ge acc = ge_identity();
+    for (int j = 63; j >= 0; j--) {
+        if (j != 63) {
+            acc = ge_dbl(acc);
+            acc = ge_dbl(acc);
+            acc = ge_dbl(acc);
+            acc = ge_dbl(acc);
+        }
+        for (int a = 0; a < cnt[i]; a++) {
+            const size_t pt = (size_t)i * STRAUS_MAX + a;
+            acc = straus_digit_step(acc, tab + (size_t)pidx[pt] * 8, sp + pt * 8, j);
+        }
+    }
+    ge_encode(out32 + 32 * (size_t)i, acc);
+}
+// half a wavefront per item, as k_varsum: lane l takes digits 2l + 1 and 2l of every point, 8 l doublings, then the 32-lane sum
+__global__ __launch_bounds__(64) void k_straus_lanes(u32 n, const i32* cnt, const ge* tab, const u32* pidx, const u32* sp, u8* out32) {
+    const u32 lane = threadIdx.x & 31u;
+    const u32 i = blockIdx.x * 2 + (threadIdx.x >> 5);
+    const bool live = i < n;  // (an odd n leaves the second half of the last wavefront without an item: it still takes part in the shuffles)
+    ge acc = ge_identity();
+    if (live) {
+#pragma unroll 1
+        for (int hi = 1; hi >= 0; hi--) {
+            if (!hi) {
+#pragma unroll 1
+                for (int k = 0; k < 4; k++) acc = ge_dbl(acc);
+            }
+            const u32 j = 2 * lane + (u32)hi;
+#pragma unroll 1
+            for (int a = 0; a < cnt[i]; a++) {
+                const size_t pt = (size_t)i * STRAUS_MAX + a;
+                acc = straus_digit_step(acc, tab + (size_t)pidx[pt] * 8, sp + pt * 8, j);
+            }
+        }
+#pragma unroll 1
+        for (u32 k = 0; k < 8 * lane; k++) acc = ge_dbl(acc);
+    }
+#pragma unroll 1
+    for (int d = 16; d >= 1; d >>= 1) {
+        ge other;
+        const u32* w = reinterpret_cast<const u32*>(&acc);
+        u32* o = reinterpret_cast<u32*>(&other);
+#pragma unroll
+        for (int k = 0; k < (int)(sizeof(ge) / 4); k++) o[k] = (u32)__shfl_down((int)w[k], d, 32);
+        if (lane < (u32)d) acc = ge_add(acc, other);
+    }
+    if (live && lane == 0) ge_encode(out32 + 32 * (size_t)i, acc);
+}
+
+// the 8-entry tables are indexed by digit magnitude: only canonical scalars (digits within [-8, 8]) may reach a kernel
+bool all_canonical(const uint8_t* s32, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        u32 w[8];
+        memcpy(w, s32 + 32 * i, 32);
+        if (!sc_is_canonical(w)) return false;
+    }
+    return true;
+}
+bool indices_below(const u32* idx, size_t n, int bound) {
+    for (size_t i = 0; i < n; i++)
+        if (idx[i] >= (u32)bound) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -453,6 +609,118 @@ int dc_merlin_rng_bulk(int n, const uint8_t* w, int w_len, const uint8_t* ent32,
     c.back(out_generic, g, per * m);
     c.back(out_bulk, b, per * m);
     c.back(ok, k, 4 * m);
+    return (int)c.err;
+}
+
+// ---- radix-16 scalar multiplication ------------------------------------------------------------------------------------------
+// bases32: nb encodings; item i commits v[i] to base idx0[i] and b[i] to base idx1[i]: out_one32 through comb_mul_add, out_split32
+// through comb_mul_add_part + commit_group_sum; base_ok: nb decode flags
+int dc_comb(int nb, const uint8_t* bases32, int n, const uint32_t* idx0, const uint32_t* idx1, const uint8_t* v32, const uint8_t* b32,
+            uint8_t* out_one32, uint8_t* out_split32, int32_t* base_ok) {
+    if (nb <= 0 || n <= 0 || !indices_below(idx0, (size_t)n, nb) || !indices_below(idx1, (size_t)n, nb)) return (int)hipErrorInvalidValue;
+    if (!all_canonical(v32, (size_t)n) || !all_canonical(b32, (size_t)n)) return (int)hipErrorInvalidValue;
+    Call c;
+    const size_t m = (size_t)n;
+    const u8* db = c.in<const u8>(bases32, 32 * (size_t)nb);
+    niels_packed* comb = c.out<niels_packed>(sizeof(niels_packed) * 64 * 8 * (size_t)nb);
+    i32* ok = c.out<i32>(4 * (size_t)nb);
+    const u32 *i0 = c.in<const u32>(idx0, 4 * m), *i1 = c.in<const u32>(idx1, 4 * m);
+    const u8 *v = c.in<const u8>(v32, 32 * m), *b = c.in<const u8>(b32, 32 * m);
+    u8 *o1 = c.out<u8>(32 * m), *o2 = c.out<u8>(32 * m);
+    c.launch(k_comb_tables, blocks_for(nb * 64), BLOCK, nb, db, comb, ok);
+    c.launch(k_comb_one, blocks_for(n), BLOCK, n, comb, i0, i1, v, b, o1);
+    c.launch(k_comb_split, blocks_for(n * COMMIT_L), 64, (u32)n, comb, i0, i1, v, b, o2);
+    c.back(out_one32, o1, 32 * m);
+    c.back(out_split32, o2, 32 * m);
+    c.back(base_ok, ok, 4 * (size_t)nb);
+    return (int)c.err;
+}
+
+// out32: nb * 64 * 8 encodings, entry [b][j][m - 1] of base b's comb as a point
+int dc_comb_table(int nb, const uint8_t* bases32, uint8_t* out32, int32_t* base_ok) {
+    if (nb <= 0) return (int)hipErrorInvalidValue;
+    Call c;
+    const size_t entries = 64 * 8 * (size_t)nb;
+    const u8* db = c.in<const u8>(bases32, 32 * (size_t)nb);
+    niels_packed* comb = c.out<niels_packed>(sizeof(niels_packed) * entries);
+    i32* ok = c.out<i32>(4 * (size_t)nb);
+    u8* o = c.out<u8>(32 * entries);
+    c.launch(k_comb_tables, blocks_for(nb * 64), BLOCK, nb, db, comb, ok);
+    c.launch(k_comb_unpack, blocks_for((int)entries), BLOCK, (int)entries, comb, o);
+    c.back(out32, o, 32 * entries);
+    c.back(base_ok, ok, 4 * (size_t)nb);
+    return (int)c.err;
+}
+
+int dc_tail_pieces() { return TAIL_PIECES; }
+
+// item i: the partial product of s[i] and point pidx[i] over pieces k_lo[i] <= k < k_hi[i] of the point's tail table
+int dc_tail(int np, const uint8_t* pts32, int n, const uint32_t* pidx, const uint8_t* s32, const int32_t* k_lo, const int32_t* k_hi,
+            uint8_t* out32, int32_t* pt_ok) {
+    if (np <= 0 || n <= 0 || !indices_below(pidx, (size_t)n, np) || !all_canonical(s32, (size_t)n)) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; i++)
+        if (k_lo[i] < 0 || k_lo[i] > k_hi[i] || k_hi[i] > TAIL_PIECES) return (int)hipErrorInvalidValue;
+    Call c;
+    const size_t m = (size_t)n;
+    const u8* dp = c.in<const u8>(pts32, 32 * (size_t)np);
+    ge* tab = c.out<ge>(sizeof(ge) * TAIL_TAB * (size_t)np);
+    i32* ok = c.out<i32>(4 * (size_t)np);
+    const u32* pi = c.in<const u32>(pidx, 4 * m);
+    const u8* s = c.in<const u8>(s32, 32 * m);
+    const i32 *lo = c.in<const i32>(k_lo, 4 * m), *hi = c.in<const i32>(k_hi, 4 * m);
+    u8* o = c.out<u8>(32 * m);
+    c.launch(k_tail_tabs, blocks_for(np), BLOCK, np, dp, tab, ok);
+    c.launch(k_tail, blocks_for(n), BLOCK, n, tab, pi, s, lo, hi, o);
+    c.back(out32, o, 32 * m);
+    c.back(pt_ok, ok, 4 * (size_t)np);
+    return (int)c.err;
+}
+
+// item i: s1[i] * point pidx1[i] + s2[i] * point pidx2[i] on one doubling chain
+int dc_tail_pair(int np, const uint8_t* pts32, int n, const uint32_t* pidx1, const uint8_t* s1, const uint32_t* pidx2, const uint8_t* s2,
+                 uint8_t* out32, int32_t* pt_ok) {
+    if (np <= 0 || n <= 0 || !indices_below(pidx1, (size_t)n, np) || !indices_below(pidx2, (size_t)n, np)) return (int)hipErrorInvalidValue;
+    if (!all_canonical(s1, (size_t)n) || !all_canonical(s2, (size_t)n)) return (int)hipErrorInvalidValue;
+    Call c;
+    const size_t m = (size_t)n;
+    const u8* dp = c.in<const u8>(pts32, 32 * (size_t)np);
+    ge* tab = c.out<ge>(sizeof(ge) * TAIL_TAB * (size_t)np);
+    i32* ok = c.out<i32>(4 * (size_t)np);
+    const u32 *p1 = c.in<const u32>(pidx1, 4 * m), *p2 = c.in<const u32>(pidx2, 4 * m);
+    const u8 *a = c.in<const u8>(s1, 32 * m), *b = c.in<const u8>(s2, 32 * m);
+    u8* o = c.out<u8>(32 * m);
+    c.launch(k_tail_tabs, blocks_for(np), BLOCK, np, dp, tab, ok);
+    c.launch(k_tail_pair, blocks_for(n), BLOCK, n, tab, p1, a, p2, b, o);
+    c.back(out32, o, 32 * m);
+    c.back(pt_ok, ok, 4 * (size_t)np);
+    return (int)c.err;
+}
+
+// item i: sum of s[4 i + a] * point pidx[4 i + a], a < cnt[i] <= 4: out_top32 digit by digit from the top, out_lane32 with the digits
+// spread over 32 lanes; sp_out: the 8 digit words of every (item, slot) (zero for unused slots)
+int dc_straus(int np, const uint8_t* pts32, int n, const int32_t* cnt, const uint32_t* pidx, const uint8_t* s32, uint8_t* out_top32,
+              uint8_t* out_lane32, uint32_t* sp_out, int32_t* pt_ok) {
+    if (np <= 0 || n <= 0 || !indices_below(pidx, (size_t)n * STRAUS_MAX, np) || !all_canonical(s32, (size_t)n * STRAUS_MAX)) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; i++)
+        if (cnt[i] < 0 || cnt[i] > STRAUS_MAX) return (int)hipErrorInvalidValue;
+    Call c;
+    const size_t m = (size_t)n, slots = m * STRAUS_MAX;
+    const u8* dp = c.in<const u8>(pts32, 32 * (size_t)np);
+    ge* tab = c.out<ge>(sizeof(ge) * 8 * (size_t)np);
+    i32* ok = c.out<i32>(4 * (size_t)np);
+    const i32* dc = c.in<const i32>(cnt, 4 * m);
+    const u32* pi = c.in<const u32>(pidx, 4 * slots);
+    const u8* s = c.in<const u8>(s32, 32 * slots);
+    u32* sp = c.out<u32>(32 * slots);
+    u8 *o1 = c.out<u8>(32 * m), *o2 = c.out<u8>(32 * m);
+    c.launch(k_straus_tabs, blocks_for(np), BLOCK, np, dp, tab, ok);
+    c.launch(k_straus_recode, blocks_for((int)slots), BLOCK, n, dc, s, sp);
+    c.launch(k_straus_top, blocks_for(n), BLOCK, n, dc, tab, pi, sp, o1);
+    c.launch(k_straus_lanes, (u32)((n + 1) / 2), 64, (u32)n, dc, tab, pi, sp, o2);
+    c.back(out_top32, o1, 32 * m);
+    c.back(out_lane32, o2, 32 * m);
+    c.back(sp_out, sp, 32 * slots);
+    c.back(pt_ok, ok, 4 * (size_t)np);
     return (int)c.err;
 }
 }

@@ -10,6 +10,7 @@
 #include "../dusk_blindbidproof_amd/csrc/point.h"
 #include "../dusk_blindbidproof_amd/csrc/prove_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
+#include "../dusk_blindbidproof_amd/csrc/scalarmul.h"
 #include "../dusk_blindbidproof_amd/csrc/verify_rows.h"
 #include "../dusk_blindbidproof_amd/csrc/witness.h"
 
@@ -487,5 +488,141 @@ void hc_merlin_rng(const uint8_t* label, int label_len, const uint8_t* wl, int w
     merlin_rng_finalize(r, ent32);
     merlin_rng_fill(r, out, n);
     merlin_rng_fill(r, out + n, n);
+}
+
+// ---- radix-16 scalar multiplication (csrc/scalarmul.h): the host twins of device_check.hip's dc_comb, dc_comb_table, dc_tail,
+// dc_tail_pair and dc_straus, same arguments, same outputs.  What a wavefront does with shuffles on the device (commit_group_sum, the
+// 32-lane sum of k_varsum) is a loop over the lanes' partial sums here.  Returns 0, or 1 for an index, a piece range
+// or a scalar the product never feeds these functions (non-canonical: the 8-entry tables are indexed by digit magnitude).
+static bool hc_canonical(const uint8_t* s32, size_t n) {
+    for (size_t i = 0; i < n; i++) {
+        u32 w[8];
+        ld(w, s32 + 32 * i, 8);
+        if (!sc_is_canonical(w)) return false;
+    }
+    return true;
+}
+static bool hc_below(const uint32_t* idx, size_t n, int bound) {
+    for (size_t i = 0; i < n; i++)
+        if (idx[i] >= (uint32_t)bound) return false;
+    return true;
+}
+static sc hc_scalar(const uint8_t* s32) {
+    sc s;
+    ld(s.v, s32, 8);
+    return s;
+}
+static std::vector<ge> hc_points(int np, const uint8_t* pts32, int32_t* ok) {
+    std::vector<ge> pts((size_t)np);
+    for (int i = 0; i < np; i++) {
+        u32 w[8];
+        ld(w, pts32 + 32 * (size_t)i, 8);
+        ok[i] = ge_decode_words(pts[i], w) ? 1 : 0;
+    }
+    return pts;
+}
+static std::vector<niels_packed> hc_comb_tables(const std::vector<ge>& bases) {
+    std::vector<niels_packed> comb(64 * 8 * bases.size());
+    for (size_t b = 0; b < bases.size(); b++)
+        for (u32 j = 0; j < 64; j++) comb_build_column(bases[b], j, comb.data() + (b * 64 + j) * 8);
+    return comb;
+}
+static std::vector<ge> hc_tail_tables(const std::vector<ge>& pts) {
+    std::vector<ge> tab((size_t)TAIL_TAB * pts.size());
+    for (size_t i = 0; i < pts.size(); i++) tail_table_build(pts[i], tab.data() + i * TAIL_TAB);
+    return tab;
+}
+
+int hc_comb(int nb, const uint8_t* bases32, int n, const uint32_t* idx0, const uint32_t* idx1, const uint8_t* v32, const uint8_t* b32,
+            uint8_t* out_one32, uint8_t* out_split32, int32_t* base_ok) {
+    if (nb <= 0 || n <= 0 || !hc_below(idx0, (size_t)n, nb) || !hc_below(idx1, (size_t)n, nb)) return 1;
+    if (!hc_canonical(v32, (size_t)n) || !hc_canonical(b32, (size_t)n)) return 1;
+    const std::vector<niels_packed> comb = hc_comb_tables(hc_points(nb, bases32, base_ok));
+    for (int i = 0; i < n; i++) {
+        const sc v = hc_scalar(v32 + 32 * (size_t)i), b = hc_scalar(b32 + 32 * (size_t)i);
+        const niels_packed *c0 = comb.data() + (size_t)idx0[i] * 64 * 8, *c1 = comb.data() + (size_t)idx1[i] * 64 * 8;
+        ge_encode(out_one32 + 32 * (size_t)i, comb_mul_add(comb_mul_add(ge_identity(), c0, v), c1, b));
+        ge part[COMMIT_L];
+        for (u32 q = 0; q < (u32)COMMIT_L; q++) part[q] = comb_mul_add_part(comb_mul_add_part(ge_identity(), c0, v, q), c1, b, q);
+        for (int d = COMMIT_L / 2; d >= 1; d >>= 1)  // commit_group_sum: lane q adds lane q + d
+            for (int q = 0; q < d; q++) part[q] = ge_add(part[q], part[q + d]);
+        ge_encode(out_split32 + 32 * (size_t)i, part[0]);
+    }
+    return 0;
+}
+
+int hc_comb_table(int nb, const uint8_t* bases32, uint8_t* out32, int32_t* base_ok) {
+    if (nb <= 0) return 1;
+    const std::vector<niels_packed> comb = hc_comb_tables(hc_points(nb, bases32, base_ok));
+    for (size_t i = 0; i < comb.size(); i++) {
+        ge_niels e;
+        BBP_COMB_LOAD(e, comb.data() + i);
+        ge_encode(out32 + 32 * i, ge_from_niels(e));
+    }
+    return 0;
+}
+
+int hc_tail_pieces() { return TAIL_PIECES; }
+
+int hc_tail(int np, const uint8_t* pts32, int n, const uint32_t* pidx, const uint8_t* s32, const int32_t* k_lo, const int32_t* k_hi,
+            uint8_t* out32, int32_t* pt_ok) {
+    if (np <= 0 || n <= 0 || !hc_below(pidx, (size_t)n, np) || !hc_canonical(s32, (size_t)n)) return 1;
+    for (int i = 0; i < n; i++)
+        if (k_lo[i] < 0 || k_lo[i] > k_hi[i] || k_hi[i] > TAIL_PIECES) return 1;
+    const std::vector<ge> tab = hc_tail_tables(hc_points(np, pts32, pt_ok));
+    for (int i = 0; i < n; i++)
+        ge_encode(out32 + 32 * (size_t)i, ge_scalarmul_pieces(hc_scalar(s32 + 32 * (size_t)i), tab.data() + (size_t)pidx[i] * TAIL_TAB, k_lo[i], k_hi[i]));
+    return 0;
+}
+
+int hc_tail_pair(int np, const uint8_t* pts32, int n, const uint32_t* pidx1, const uint8_t* s1, const uint32_t* pidx2, const uint8_t* s2,
+                 uint8_t* out32, int32_t* pt_ok) {
+    if (np <= 0 || n <= 0 || !hc_below(pidx1, (size_t)n, np) || !hc_below(pidx2, (size_t)n, np)) return 1;
+    if (!hc_canonical(s1, (size_t)n) || !hc_canonical(s2, (size_t)n)) return 1;
+    const std::vector<ge> tab = hc_tail_tables(hc_points(np, pts32, pt_ok));
+    for (int i = 0; i < n; i++)
+        ge_encode(out32 + 32 * (size_t)i, ge_scalarmul_pieces_pair(hc_scalar(s1 + 32 * (size_t)i), tab.data() + (size_t)pidx1[i] * TAIL_TAB,
+                                                                    hc_scalar(s2 + 32 * (size_t)i), tab.data() + (size_t)pidx2[i] * TAIL_TAB));
+    return 0;
+}
+
+int hc_straus(int np, const uint8_t* pts32, int n, const int32_t* cnt, const uint32_t* pidx, const uint8_t* s32, uint8_t* out_top32,
+              uint8_t* out_lane32, uint32_t* sp_out, int32_t* pt_ok) {
+    constexpr int STRAUS_MAX = 4;
+    if (np <= 0 || n <= 0 || !hc_below(pidx, (size_t)n * STRAUS_MAX, np) || !hc_canonical(s32, (size_t)n * STRAUS_MAX)) return 1;
+    for (int i = 0; i < n; i++)
+        if (cnt[i] < 0 || cnt[i] > STRAUS_MAX) return 1;
+    const std::vector<ge> pts = hc_points(np, pts32, pt_ok);
+    std::vector<ge> tab(8 * pts.size());
+    for (size_t i = 0; i < pts.size(); i++) straus_table(tab.data() + 8 * i, pts[i]);
+    memset(sp_out, 0, 32 * (size_t)n * STRAUS_MAX);
+    for (int i = 0; i < n; i++) {
+        const size_t pt0 = (size_t)i * STRAUS_MAX;
+        for (int a = 0; a < cnt[i]; a++) straus_recode(sp_out + 8 * (pt0 + a), hc_scalar(s32 + 32 * (pt0 + a)));
+        ge acc = ge_identity();  // as k_varbase
+        for (int j = 63; j >= 0; j--) {
+            if (j != 63)
+                for (int k = 0; k < 4; k++) acc = ge_dbl(acc);
+            for (int a = 0; a < cnt[i]; a++) acc = straus_digit_step(acc, tab.data() + (size_t)pidx[pt0 + a] * 8, sp_out + 8 * (pt0 + a), j);
+        }
+        ge_encode(out_top32 + 32 * (size_t)i, acc);
+        // as k_varsum: lane l's partial sum S_l over digits 2l + 1 and 2l; the kernel then doubles S_l 8 l times and adds the 32 lanes up
+        // with shuffles -- here sum_l 2^(8 l) S_l is taken by Horner's rule from the top lane down (the same group element, 248 doublings)
+        ge lanes = ge_identity();
+        for (int lane = 31; lane >= 0; lane--) {
+            ge l = ge_identity();
+            for (int hi = 1; hi >= 0; hi--) {
+                if (!hi)
+                    for (int k = 0; k < 4; k++) l = ge_dbl(l);
+                const u32 j = 2 * (u32)lane + (u32)hi;
+                for (int a = 0; a < cnt[i]; a++) l = straus_digit_step(l, tab.data() + (size_t)pidx[pt0 + a] * 8, sp_out + 8 * (pt0 + a), j);
+            }
+            if (lane != 31)
+                for (int k = 0; k < 8; k++) lanes = ge_dbl(lanes);
+            lanes = ge_add(lanes, l);
+        }
+        ge_encode(out_lane32 + 32 * (size_t)i, lanes);
+    }
+    return 0;
 }
 }
