@@ -18,6 +18,14 @@ BASE_BBLIND, BASE_G0, BASE_H0, BASE_B, NUM_BASES = 0, 1, 2049, 4097, 4098
 R1CS_PROOF_BYTES = 1121
 ENTROPY_PROVE, ENTROPY_VERIFY = 0, 1            # bbp_draw_entropy_dev kinds
 ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE = 0, 1  # bbp_set_entropy_source
+TABLE_GENS, TABLE_PTABLE, TABLE_COMB, TABLE_BTAB = 0, 1, 2, 3  # bbp_debug_table
+TABLE_IDX_AI, TABLE_IDX_AO, TABLE_IDX_S1, TABLE_IDX_IPA, TABLE_IDX_VER = 4, 5, 6, 7, 8  # ... its index lists: which = list | N << 8
+VARBASE_LANES, VARBASE_PREP_SUM, VARBASE_MX_LANES, VARBASE_MX_PREP_SUM = 0, 1, 2, 3  # bbp_debug_varbase forms
+
+
+def varbase_points(n):
+    """Point slots of one verification of list length n (bbp_debug_varbase): 6 + (4 + n) + 5 + 22."""
+    return 6 + (4 + n) + 5 + 22
 
 # every symbol include/bbp.h declares: (restype, argtypes)
 _vp, _u32, _i32, _u64, _cp = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_char_p
@@ -79,6 +87,8 @@ SIGNATURES = {
     "bbp_set_entropy_source": (_i32, [_vp, _i32]),
     "bbp_debug_next_entropy_key": (_i32, [_vp, _vp]),
     "bbp_debug_challenges": (_i32, [_vp, _u32, _u32, _u32, _vp]),
+    "bbp_debug_table": (_i32, [_vp, _u32, ctypes.POINTER(_vp), ctypes.POINTER(_u64)]),
+    "bbp_debug_varbase": (_i32, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_ubench": (_i32, [_vp, _i32, _u32, _u32, ctypes.POINTER(ctypes.c_double)]),
     "bbp_set_profiling": (_i32, [_vp, _i32]),
     "bbp_last_timings": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u32)]),
@@ -561,6 +571,37 @@ class Context:
         names = ["y", "z", "u", "x", "w", "y_inv", "t1", "t2", "t3", "t4", "t5", "t6", "tb1", "tb2", "tb3", "tb4", "tb5", "tb6",
                  "t_x", "t_x_blinding", "e_blinding", "uj", "uji", "a", "b", "r", "allinv", "wc", "delta"]
         return {n: raw[32 * i:32 * i + 32].hex() for i, n in enumerate(names)}
+
+    def debug_table(self, which):
+        """Test hook: (device pointer, bytes) of a resident table, which = TABLE_GENS / _PTABLE / _COMB / _BTAB, or TABLE_IDX_* | N << 8 for
+        a base-index list of list length N (bbp_debug_table)."""
+        dev, size = ctypes.c_void_p(), ctypes.c_uint64()
+        self._check(lib.bbp_debug_table(self._h, which, ctypes.byref(dev), ctypes.byref(size)))
+        return dev.value, size.value
+
+    def debug_varbase(self, form, rows, Q=1, agg=0):
+        """Test hook: the shipped variable-base kernels on caller-made rows (bbp_debug_varbase).  rows: [(N, version, pts, (x, r, u,
+        rho), wv, uj)] with pts the vnpts(N) 32-byte encodings, the scalars ints, wv 4 + N ints, uj the 11 u_j then the 11 u_j^-1.
+        Returns per row (sums: nq encodings, digit words: 8 per point slot, status)."""
+        B = len(rows)
+        sc = lambda vals: b"".join(int(v).to_bytes(32, "little") for v in vals)
+        for n, _, pts, scal, wv, uj in rows:
+            if len(pts) != varbase_points(n) or len(scal) != 4 or len(wv) != 4 + n or len(uj) != 22 or any(len(e) != 32 for e in pts):
+                raise ValueError("a row does not have the layout of list length %d" % n)
+        nq = Q if form in (VARBASE_LANES, VARBASE_MX_LANES) else 1
+        slots = [varbase_points(r[0]) for r in rows]
+        sums = (ctypes.c_uint8 * (32 * B * max(nq, 1)))()
+        digits = (_u32 * (8 * sum(slots)))()
+        status = (_i32 * B)()
+        self._check(lib.bbp_debug_varbase(self._h, form, B, Q, agg, _u32s([r[0] for r in rows]), _buf(bytes(r[1] for r in rows)),
+                                          _buf(b"".join(b"".join(r[2]) for r in rows)), _buf(b"".join(sc(r[3]) for r in rows)),
+                                          _buf(b"".join(sc(r[4]) for r in rows)), _buf(b"".join(sc(r[5]) for r in rows)), sums, digits, status))
+        raw, words, out, at = bytes(sums), list(digits), [], 0
+        for p in range(B):
+            out.append(([raw[32 * (p * nq + q):32 * (p * nq + q) + 32] for q in range(nq)],
+                        [words[8 * (at + k):8 * (at + k) + 8] for k in range(slots[p])], status[p]))
+            at += slots[p]
+        return out
 
     def ubench(self, kind, blocks=4096, iters=2000):
         v = ctypes.c_double()

@@ -22,6 +22,8 @@ int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_
 int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s,
                              u32* n_fallback, u32* total_out_dev = nullptr);
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out);
+int32_t debug_varbase(bbp_ctx* ctx, u32 form, u32 B, u32 Q, u32 agg, const u32* ns, const u8* vers, const u8* pts, const u8* scal, const u8* wv,
+                      const u8* uj, u8* sums_out, u32* digits_out, int32_t* status_out);
 // verifier.inc: k_round_consts for one round (the prove side's table reduction)
 int32_t round_consts_launch(bbp_ctx* ctx, u32 N, const u8* round_dev, const u32* roff_dev, sc* rblk, int32_t* rflag, hipStream_t s);
 
@@ -1557,6 +1559,48 @@ extern "C" int32_t bbp_debug_challenges(bbp_ctx* ctx, uint32_t B, uint32_t N, ui
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         BBP_HIP_TRY(ctx, hipDeviceSynchronize());
         return debug_read_misc(ctx, B, N, proof, out32x32);
+    });
+}
+
+extern "C" int32_t bbp_debug_table(bbp_ctx* ctx, uint32_t which, const void** dev, uint64_t* bytes) {
+    const uint32_t kind = which & 0xffu, N = which >> 8;
+    if (!ctx || !dev || !bytes || kind > BBP_TABLE_IDX_VER) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_table");
+    if (kind < BBP_TABLE_IDX_AI ? N != 0 : N == 0) return BBP_ERR_BAD_ARG;  // screened here: no circuit is synthesised for a length
+    if (N > BBP_MAX_ITEMS) return BBP_ERR_GENS_LEN;                          // the engine cannot prove
+    return api_guard(ctx, [&]() -> int32_t {
+        if (kind >= BBP_TABLE_IDX_AI) {  // the base-index lists of circuit N (prover.hip circuit_get), compiled now if need be
+            BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+            const CircuitDev* c;
+            if (int32_t rc = circuit_get(ctx, N, &c)) return rc;
+            const uint64_t n1 = c->n_mul;
+            switch (kind) {
+                case BBP_TABLE_IDX_AI: *dev = c->idx_ai, *bytes = 4 * (1 + 2 * n1); break;
+                case BBP_TABLE_IDX_AO: *dev = c->idx_ao, *bytes = 4 * (1 + n1); break;
+                case BBP_TABLE_IDX_S1: *dev = c->idx_s1, *bytes = 4 * (1 + 2 * n1); break;
+                case BBP_TABLE_IDX_IPA: *dev = c->idx_ipa, *bytes = 4 * (uint64_t)(11 * 2 * 2049); break;
+                default: *dev = c->idx_ver, *bytes = 4 * 4098; break;
+            }
+            return BBP_OK;
+        }
+        switch (kind) {
+            case BBP_TABLE_GENS: *dev = ctx->gens, *bytes = sizeof(ge) * (uint64_t)TAB_BASES; break;
+            case BBP_TABLE_PTABLE: *dev = ctx->ptable, *bytes = sizeof(niels_row) * (uint64_t)TAB_BASES * MSM_POS; break;
+            case BBP_TABLE_COMB: *dev = ctx->comb, *bytes = sizeof(niels_packed) * 2 * 64 * 8; break;
+            default: *dev = ctx->btab, *bytes = tail_btab_bytes(); break;
+        }
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_debug_varbase(bbp_ctx* ctx, uint32_t form, uint32_t B, uint32_t Q, uint32_t agg, const uint32_t* ns, const uint8_t* vers,
+                                     const uint8_t* pts, const uint8_t* scalars, const uint8_t* wv, const uint8_t* uj, uint8_t* sums_out,
+                                     uint32_t* digits_out, int32_t* status_out) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_varbase");
+    return api_guard(ctx, [&]() -> int32_t {
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        return debug_varbase(ctx, form, B, Q, agg, ns, vers, pts, scalars, wv, uj, sums_out, digits_out, status_out);
     });
 }
 

@@ -201,7 +201,7 @@ struct bbp_ctx {
     // resident tables
     bbp::ge* gens = nullptr;           // [TAB_BASES] extended points: B_blinding, G[2048], H[2048], B, then the PAD_BASES range sums and the MRG_BASES merged bases
     bbp::niels_row* ptable = nullptr;      // [TAB_BASES * MSM_POS] affine cached 2^b * P_i, 128-byte limb rows (275 MB)
-    bbp::ge* btab = nullptr;               // [32] m * 2^(64 k) * B, m = 1..8, k = 0..3 (prover.hip tail rounds)
+    bbp::ge* btab = nullptr;               // [TAIL_TAB] m * 2^(TAIL_PIECE_BITS k) * B, m = 1..8, k = 0..TAIL_PIECES-1 (scalarmul.h; prover.hip tail rounds)
     bbp::niels_packed* comb = nullptr;     // [2][64][8] radix-16 comb for B and B_blinding (small commits)
     bbp::sc* mimc_c = nullptr;         // [90]
     uint8_t gens_enc_host_valid = 0;
@@ -453,5 +453,6 @@ int32_t encode_launch(bbp_ctx* ctx, uint32_t n, const ge* pts_dev, uint8_t* out3
 size_t msm_scratch_bytes(uint32_t n_msm, uint32_t n_terms);
 // prover.hip
 int32_t tail_btab_build(bbp_ctx* ctx);
+size_t tail_btab_bytes();  // what it allocates for ctx->btab
 
 }  // namespace bbp

@@ -1419,6 +1419,8 @@ int32_t tail_btab_build(bbp_ctx* ctx) {  // called once from bbp_init: the table
     return BBP_OK;
 }
 
+size_t tail_btab_bytes() { return sizeof(ge) * TAIL_TAB; }
+
 static BatchDev batch_view(const BatchDev& bd, const CircuitDev& c, u32 first);
 static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
                            hipEvent_t stagger, hipEvent_t out_guard);

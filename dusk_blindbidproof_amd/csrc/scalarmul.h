@@ -3,7 +3,9 @@
 // data-dependent steps of the verifier's Straus sums (verifier.inc / verifier_mixed.inc k_varbase, k_varprep / k_varsum and their
 // mixed-N twins).  k_commit* and k_tail_lr call the functions here.  k_build_comb, k_tail_tables and the Straus kernels keep their
 // own copies of comb_build_column, tail_table_build and the straus_* steps (called from there, the kernels' instruction order
-// changed): for those the functions below state the same code for the tests, and a change to either side belongs in both.
+// changed): for those the functions below state the same code for the tests, and a change to either side belongs in both.  The
+// copies have tests of their own: tests/test_gpu_varbase_kernels.py runs the shipped Straus kernels (bbp_debug_varbase) over the
+// battery of tests/varbase_cases.py, tests/test_gpu_tables.py audits the comb and the tail table the shipped builders made at start-up.
 //
 // Everything here walks the signed radix-16 digits of a CANONICAL scalar (< l): the 8-entry tables are indexed by digit magnitude
 // 1..8 and no caller feeds anything else.  Two recodings:

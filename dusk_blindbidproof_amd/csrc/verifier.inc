@@ -603,6 +603,39 @@ static int vlane_of(const bbp_ctx* ctx, hipStream_t s) {  // a lane's own stream
     return 0;
 }
 
+// The variable-base launches of one call, in one place: verify_batch_dev and bbp_debug_varbase (the kernel tests) share the grid
+// formulas.  mixed: the _mx kernels (m, np, npa those of the call's largest row: the strides); vb2: k_varprep + k_varsum (one sum per
+// row), else k_varbase with Q lanes and Q sums per row.  one_phase: the uniform kernels' record layout (a mixed row carries its own).
+struct VarbaseLaunch {
+    bool mixed, vb2;
+    u32 B, Q, m, np, npa, one_phase;
+    const VRow* rows;
+    const u32* vpts;
+    const sc *vchal, *misc, *wv;
+    ge* tab;
+    u32* sp;
+    ge* var;
+    int32_t* status;
+};
+static int32_t varbase_launch(bbp_ctx* ctx, const VarbaseLaunch& v, hipStream_t st, u32 agg_flag) {
+    const u32 B = v.B, Q = v.Q, m = v.m, np = v.np, npa = v.npa;
+    if (v.mixed) {
+        if (v.vb2) {
+            LAUNCH(ctx, TAG_VARBASE, k_varprep_mx, cdiv(B * npa, 64), 64, st, B, npa, np, v.rows, v.vpts, v.vchal, v.misc, v.wv, m, v.tab, v.sp, v.status,
+                   agg_flag);
+            LAUNCH(ctx, TAG_VARBASE, k_varsum_mx, cdiv(B, 2), 64, st, B, np, v.rows, (const ge*)v.tab, (const u32*)v.sp, v.var);
+        } else
+            LAUNCH(ctx, TAG_VARBASE, k_varbase_mx, cdiv(B * Q, 64), 64, st, B, Q, np, v.rows, v.vpts, v.vchal, v.misc, v.wv, m, v.tab, v.sp, v.var,
+                   v.status, agg_flag);
+    } else if (v.vb2) {
+        LAUNCH(ctx, TAG_VARBASE, k_varprep, cdiv(B * npa, 64), 64, st, B, m, v.vpts, v.vchal, v.misc, v.wv, v.tab, v.sp, v.status, agg_flag, v.one_phase);
+        LAUNCH(ctx, TAG_VARBASE, k_varsum, cdiv(B, 2), 64, st, B, m, (const ge*)v.tab, (const u32*)v.sp, v.var, v.one_phase);
+    } else
+        LAUNCH(ctx, TAG_VARBASE, k_varbase, cdiv(B * Q, 64), 64, st, B, m, Q, v.vpts, v.vchal, v.misc, v.wv, v.tab, v.sp, v.var, v.status, agg_flag,
+               v.one_phase);
+    return BBP_OK;
+}
+
 // v: what the rows at in_dev are (verify_rows.h).  A mixed front end runs with the strides of the largest N, the launches the same in
 // number; a rounds call takes seed and bid list from v.rounds (device memory) -- one round behind k_vparse_round, several behind
 // k_vparse_rounds_mx with every row's N taken from its round.
@@ -693,23 +726,8 @@ int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_
     static const int vb_force = getenv("BBP_VARBASE_V1") ? (atoi(getenv("BBP_VARBASE_V1")) ? 1 : 2) : 0;
     const bool vb2 = vb_force ? vb_force == 2 : B < 4096;
     if (vb2) Q = 1;
-    auto launch_varbase = [&](hipStream_t st, u32 agg_flag) -> int32_t {
-        if (mixed) {
-            if (vb2) {
-                LAUNCH(ctx, TAG_VARBASE, k_varprep_mx, cdiv(B * npa, 64), 64, st, B, npa, np, rows, vpts, vchal, bd.misc, bd.wv, m, tab, sp, status_dev,
-                       agg_flag);
-                LAUNCH(ctx, TAG_VARBASE, k_varsum_mx, cdiv(B, 2), 64, st, B, np, rows, (const ge*)tab, (const u32*)sp, var);
-            } else
-                LAUNCH(ctx, TAG_VARBASE, k_varbase_mx, cdiv(B * Q, 64), 64, st, B, Q, np, rows, vpts, vchal, bd.misc, bd.wv, m, tab, sp, var,
-                       status_dev, agg_flag);
-        } else if (vb2) {
-            LAUNCH(ctx, TAG_VARBASE, k_varprep, cdiv(B * npa, 64), 64, st, B, m, vpts, vchal, bd.misc, bd.wv, tab, sp, status_dev, agg_flag, rec_ver ? 0u : 1u);
-            LAUNCH(ctx, TAG_VARBASE, k_varsum, cdiv(B, 2), 64, st, B, m, (const ge*)tab, (const u32*)sp, var, rec_ver ? 0u : 1u);
-        } else
-            LAUNCH(ctx, TAG_VARBASE, k_varbase, cdiv(B * Q, 64), 64, st, B, m, Q, vpts, vchal, bd.misc, bd.wv, tab, sp, var, status_dev, agg_flag,
-                   rec_ver ? 0u : 1u);
-        return BBP_OK;
-    };
+    const VarbaseLaunch vb{mixed, vb2, B, Q, m, np, npa, rec_ver ? 0u : 1u, rows, vpts, vchal, bd.misc, bd.wv, tab, sp, var, status_dev};
+    auto launch_varbase = [&](hipStream_t st, u32 agg_flag) -> int32_t { return varbase_launch(ctx, vb, st, agg_flag); };
 
     // Knock-out mask (timing experiments, WRONG results): skip 1 the MSM, 2 k_varbase, 4 k_vtranscript, 8 k_flatten, 16 k_vscalars,
     // 32 k_powers -- what a kernel costs the pipeline is what the step loses without it.  It changes VERDICTS (k_vfinal would judge
@@ -874,6 +892,112 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8*
     if (n_fallback) {
         BBP_HIP_TRY(ctx, hipMemcpyAsync(n_fallback, L.agg_count, sizeof(u32), hipMemcpyDeviceToHost, s));
         BBP_HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    return BBP_OK;
+}
+
+// bbp_debug_varbase (include/bbp.h): the shipped variable-base kernels on caller-made rows, through varbase_launch on lane 0's
+// stream.  The rows are packed into misc / vchal / wv / vpts at the slots the front end fills (MS_X, MS_R, MS_U, MS_RHO; VC_U, VC_UI;
+// point slot k of row p at p * np + k); every buffer is the call's own, sized from the screened counts, and freed on every path.
+// Digit words and status start out zero: a slot no kernel writes reads back as eight zero words.
+namespace {
+struct DebugScratch {
+    std::vector<void*> ptrs;
+    ~DebugScratch() {
+        for (void* p : ptrs) (void)hipFree(p);
+    }
+};
+}  // namespace
+
+int32_t debug_varbase(bbp_ctx* ctx, u32 form, u32 B, u32 Q, u32 agg, const u32* ns, const u8* vers, const u8* pts, const u8* scal, const u8* wv,
+                      const u8* uj, u8* sums_out, u32* digits_out, int32_t* status_out) {
+    auto bad = [&](const char* why) {
+        ctx->err = std::string("bbp_debug_varbase: ") + why;
+        return (int32_t)BBP_ERR_BAD_ARG;
+    };
+    if (form > BBP_VARBASE_MX_PREP_SUM) return bad("form is 0..3");
+    const bool mixed = form >= BBP_VARBASE_MX_LANES, vb2 = form == BBP_VARBASE_PREP_SUM || form == BBP_VARBASE_MX_PREP_SUM;
+    if (B < 1 || B > 1024) return bad("B is 1..1024");
+    if (vb2) Q = 1;
+    if (Q < 1 || Q > 1024) return bad("Q is 1..1024");
+    if (!ns || !vers || !pts || !scal || !wv || !uj || !sums_out || !digits_out || !status_out) return bad("null argument");
+    u32 n_max = 0, any_two = 0;
+    size_t n_wv = 0;  // wv scalars over all rows
+    for (u32 p = 0; p < B; p++) {
+        if (ns[p] < 1 || ns[p] > BBP_MAX_ITEMS) return bad("N is 1..202");
+        if (vers[p] > 1) return bad("a record version is 0 or 1");
+        if (!mixed && (ns[p] != ns[0] || vers[p] != vers[0])) return bad("the uniform forms take one N and one version");
+        n_max = std::max(n_max, ns[p]);
+        any_two |= vers[p];
+        n_wv += 4 + ns[p];
+    }
+    auto canonical = [](const u8* b, size_t count) {
+        for (size_t i = 0; i < count; i++) {
+            u32 w[8];
+            memcpy(w, b + 32 * i, 32);
+            if (!sc_is_canonical(w)) return false;
+        }
+        return true;
+    };
+    if (!canonical(scal, 4 * (size_t)B) || !canonical(wv, n_wv) || !canonical(uj, 22 * (size_t)B)) return bad("a scalar is not canonical");
+    // strides: the call's largest row (a uniform call: its one N), as verify_batch_dev takes them from the largest circuit
+    const u32 m = 4 + n_max, np = 6 + m + 5 + 22, npa = np - (any_two ? 0u : 3u), nq = Q;
+    std::vector<u8> h_vpts((size_t)B * np * 32, 0), h_misc((size_t)B * MS_COUNT * 32, 0), h_vchal((size_t)B * VC_COUNT * 32, 0), h_wv((size_t)B * m * 32, 0);
+    std::vector<VRow> h_rows(B);
+    {
+        const u8 *pp = pts, *pw = wv;
+        u64 off = 0;
+        for (u32 p = 0; p < B; p++) {
+            const u32 mp = 4 + ns[p], npp = 6 + mp + 5 + 22;
+            memcpy(&h_vpts[(size_t)p * np * 32], pp, (size_t)npp * 32);
+            memcpy(&h_wv[(size_t)p * m * 32], pw, (size_t)mp * 32);
+            pp += (size_t)npp * 32, pw += (size_t)mp * 32;
+            u8* ms = &h_misc[(size_t)p * MS_COUNT * 32];
+            const int slot[4] = {MS_X, MS_R, MS_U, MS_RHO};
+            for (int i = 0; i < 4; i++) memcpy(ms + 32 * slot[i], scal + 32 * (4 * (size_t)p + i), 32);
+            u8* vc = &h_vchal[(size_t)p * VC_COUNT * 32];
+            memcpy(vc + 32 * VC_U, uj + 32 * 22 * (size_t)p, 32 * 11);
+            memcpy(vc + 32 * VC_UI, uj + 32 * (22 * (size_t)p + 11), 32 * 11);
+            h_rows[p] = VRow{off, ns[p], (uint16_t)mp, (uint16_t)vers[p]};
+            off += vrow_bytes(ns[p], vers[p]);
+        }
+    }
+    DebugScratch scratch;
+    auto dev = [&](void** out, const void* host, size_t bytes) -> int32_t {  // zeroed, then the host image when there is one
+        BBP_HIP_TRY(ctx, hipMalloc(out, bytes));
+        scratch.ptrs.push_back(*out);
+        BBP_HIP_TRY(ctx, hipMemset(*out, 0, bytes));
+        if (host) BBP_HIP_TRY(ctx, hipMemcpy(*out, host, bytes, hipMemcpyHostToDevice));
+        return BBP_OK;
+    };
+    void *d_vpts, *d_misc, *d_vchal, *d_wv, *d_rows, *d_tab, *d_sp, *d_var, *d_status, *d_enc;
+    int32_t rc;
+    if ((rc = dev(&d_vpts, h_vpts.data(), h_vpts.size())) || (rc = dev(&d_misc, h_misc.data(), h_misc.size())) ||
+        (rc = dev(&d_vchal, h_vchal.data(), h_vchal.size())) || (rc = dev(&d_wv, h_wv.data(), h_wv.size())) ||
+        (rc = dev(&d_rows, h_rows.data(), (size_t)B * sizeof(VRow))) || (rc = dev(&d_tab, nullptr, (size_t)B * np * 8 * sizeof(ge))) ||
+        (rc = dev(&d_sp, nullptr, (size_t)B * np * 32)) || (rc = dev(&d_var, nullptr, (size_t)B * nq * sizeof(ge))) ||
+        (rc = dev(&d_status, nullptr, (size_t)B * 4)) || (rc = dev(&d_enc, nullptr, (size_t)B * nq * 32)))
+        return rc;
+    // the fills above went to the null stream, which a non-blocking stream does not wait for: they are done before anything is launched
+    BBP_HIP_TRY(ctx, hipDeviceSynchronize());
+    hipStream_t s = ctx->vl[0].stream;
+    {
+        StreamGuard guard(ctx, s, 1);
+        if ((rc = guard.enter())) return rc;
+        const VarbaseLaunch vb{mixed, vb2, B, Q, m, np, npa, vers[0] ? 0u : 1u, (const VRow*)d_rows, (const u32*)d_vpts, (const sc*)d_vchal,
+                               (const sc*)d_misc, (const sc*)d_wv, (ge*)d_tab, (u32*)d_sp, (ge*)d_var, (int32_t*)d_status};
+        if ((rc = varbase_launch(ctx, vb, s, agg ? 1u : 0u))) return rc;
+        if ((rc = encode_launch(ctx, B * nq, (const ge*)d_var, (uint8_t*)d_enc, s))) return rc;
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(s));
+    }
+    std::vector<u32> h_sp((size_t)B * np * 8);
+    BBP_HIP_TRY(ctx, hipMemcpy(h_sp.data(), d_sp, h_sp.size() * 4, hipMemcpyDeviceToHost));
+    BBP_HIP_TRY(ctx, hipMemcpy(sums_out, d_enc, (size_t)B * nq * 32, hipMemcpyDeviceToHost));
+    BBP_HIP_TRY(ctx, hipMemcpy(status_out, d_status, (size_t)B * 4, hipMemcpyDeviceToHost));
+    for (u32 p = 0; p < B; p++) {
+        const u32 npp = 6 + (4 + ns[p]) + 5 + 22;
+        memcpy(digits_out, &h_sp[(size_t)p * np * 8], (size_t)npp * 32);
+        digits_out += (size_t)npp * 8;
     }
     return BBP_OK;
 }

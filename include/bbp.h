@@ -82,8 +82,8 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
- * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_set_profiling / bbp_last_timings; the stream getters
- * return NULL. */
+ * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_set_profiling /
+ * bbp_last_timings; the stream getters return NULL. */
 int32_t bbp_init_all(bbp_ctx** out);
 int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp_ctx** out);
 uint32_t bbp_pool_size(const bbp_ctx* ctx);               /* number of members; 0 for an ordinary context */
@@ -430,6 +430,54 @@ int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]);
 /* Parity hook: the 32-scalar challenge block of proof `proof` of the LAST batch call of geometry (B, N):
  * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch.h), 32 x 32 bytes. */
 int32_t bbp_debug_challenges(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t proof, uint8_t* out32x32);
+
+/* Test hook: where one of the context's resident tables lives on the device and how large it is (csrc/context.h "resident tables"):
+ *   BBP_TABLE_GENS     8396 extended points of 160 bytes: the BBP_NUM_BASES public bases at their BBP_BASE_* indices, then the 202 range
+ *                      sums (index 4098 + N - 1 = H[418 + 3N] + .. + H[1023]), then MRG1(i) = G[i] + H[i] + H[i+1] at 4300 + i and
+ *                      MRG2(i) = G[i] + G[i+1] + H[i+1] at 4300 + 2048 + i, i = 0..2047 (i = 2047: some valid point, never referenced)
+ *   BBP_TABLE_PTABLE   8396 x 256 rows of 128 bytes: row (i, b) is 2^b * gens[i] in the MSM kernels' cached affine form
+ *   BBP_TABLE_COMB     2 x 64 x 8 entries of 96 bytes: entry (base, j, m - 1) is m * 16^j * Base, Base = B, B_blinding
+ *   BBP_TABLE_BTAB     the tail table of B that the prover's k_tail_tables built at bbp_init: 160-byte points
+ *   BBP_TABLE_IDX(list, N)   one of the base-index lists (uint32 indices into gens; 0xffffffff: a term that rides on a merged
+ *                      base) that the MSMs of list length N are launched with, the circuit compiled now if it was not yet:
+ *                      BBP_TABLE_IDX_AI / _AO / _S1 (1 + 2 n_mul, 1 + n_mul, 1 + 2 n_mul entries, n_mul = 1442 + 3N), _IPA
+ *                      (11 rounds x {L, R} x 2049), _VER (4098).  N == 0 is BBP_ERR_BAD_ARG, N > BBP_MAX_ITEMS BBP_ERR_GENS_LEN.
+ * The pointer stays valid until bbp_free and is for reading, by kernels of the same process.  A pool refuses it (take a member). */
+#define BBP_TABLE_GENS 0u
+#define BBP_TABLE_PTABLE 1u
+#define BBP_TABLE_COMB 2u
+#define BBP_TABLE_BTAB 3u
+#define BBP_TABLE_IDX_AI 4u
+#define BBP_TABLE_IDX_AO 5u
+#define BBP_TABLE_IDX_S1 6u
+#define BBP_TABLE_IDX_IPA 7u
+#define BBP_TABLE_IDX_VER 8u
+#define BBP_TABLE_IDX(list, N) ((list) | ((uint32_t)(N) << 8))
+int32_t bbp_debug_table(bbp_ctx* ctx, uint32_t which, const void** dev, uint64_t* bytes);
+
+/* Test hook: the verifier's variable-base kernels, as shipped and with the verify path's launch geometry, on caller-made rows; the
+ * call synchronises.  form:
+ *   BBP_VARBASE_LANES         k_varbase, Q lanes and Q partial sums per row
+ *   BBP_VARBASE_PREP_SUM      k_varprep + k_varsum, one sum per row (Q ignored)
+ *   BBP_VARBASE_MX_LANES      k_varbase_mx   } rows of any mix of list lengths and record versions, the row stride
+ *   BBP_VARBASE_MX_PREP_SUM   k_varprep_mx + k_varsum_mx   } that of the largest row; the first two forms take one N and one version
+ * Row p has list length ns[p] (m = 4 + N, np = 6 + m + 5 + 22 point slots) and record version vers[p] (0: one-phase, slots 3..5
+ * are skipped; 1: two-phase).  Host arrays, rows packed back to back:
+ *   pts       np 32-byte encodings per row, in slot order: A_I1 A_O1 S1 A_I2 A_O2 S2, the m commitments, T_1 T_3..T_6, L[11], R[11]
+ *   scalars   x, r, u, rho per row (4 x 32 bytes);  wv: m scalars per row;  uj: u_j[11] then u_j^-1[11] per row
+ * Every scalar must be canonical.  agg != 0: every slot's scalar is multiplied by rho (the aggregated verifier's weight).
+ * Outputs: sums_out, nq 32-byte encodings per row (nq = Q for the LANES forms, 1 otherwise; a lane without a point gives the
+ * identity); digits_out, 8 words per point slot, packed like pts (slots no kernel wrote stay 0); status_out, B statuses (BBP_OK,
+ * or BBP_ERR_VERIFY for a row with a point that does not decode).
+ * B is 1..1024, N 1..202, Q 1..1024: anything else, a null pointer or a non-canonical scalar is BBP_ERR_BAD_ARG and nothing is
+ * launched; every device buffer is sized from these counts.  A pool refuses it. */
+#define BBP_VARBASE_LANES 0u
+#define BBP_VARBASE_PREP_SUM 1u
+#define BBP_VARBASE_MX_LANES 2u
+#define BBP_VARBASE_MX_PREP_SUM 3u
+int32_t bbp_debug_varbase(bbp_ctx* ctx, uint32_t form, uint32_t B, uint32_t Q, uint32_t agg, const uint32_t* ns, const uint8_t* vers,
+                          const uint8_t* pts, const uint8_t* scalars, const uint8_t* wv, const uint8_t* uj, uint8_t* sums_out,
+                          uint32_t* digits_out, int32_t* status_out);
 
 /* Integer-ALU roofline microbenchmarks (register-resident chains, no memory): kind 0 = v_mad_u64_u32, 1 = field multiply,
  * 2 = field square, 3 = mixed point addition, 4 = Montgomery product mod l, 5 = mixed point addition with an operand the

@@ -436,6 +436,66 @@ __global__ __launch_bounds__(64) void k_straus_lanes(u32 n, const i32* cnt, cons
     if (live && lane == 0) ge_encode(out32 + 32 * (size_t)i, acc);
 }
 
+// ---- the engine's resident tables (bbp_debug_table): read in place, through device pointers of the same process -------------------
+// thread per point of a ge array (gens, btab): encoded
+__global__ void k_points_encode(int n, const ge* pts, u8* out32) {
+    const int i = item();
+    if (i >= n) return;
+    ge_encode(out32 + 32 * (size_t)i, pts[i]);
+}
+
+// exact equality of two points in extended coordinates (not the coset equality of ge_eq: a table row is the point itself)
+__device__ __forceinline__ bool same_point(const ge& p, const ge& q) {
+    return fe_eq(fe_mul(p.X, q.Z), fe_mul(q.X, p.Z)) && fe_eq(fe_mul(p.Y, q.Z), fe_mul(q.Y, p.Z));
+}
+
+// one lane per base: P, 2P, .. 2^(n_pos - 1) P by ge_dbl; at each bit the row is consumed as msm.hip consumes it, load_row_at +
+// ge_madd_row, in both signs, onto two accumulators: the identity (T = 0: the sum is the row's point itself, from y+x and y-x alone,
+// and must be +P and -P) and P (T != 0, so the row's 2dxy takes part: P + row must be 2P, P - row the identity).  bad[i]: mismatching
+// checks of base i (up to four per bit), first[i]: the first mismatching bit (n_pos when there is none)
+__global__ void k_ptable_walk(int n_bases, int n_pos, const ge* gens, const niels_row* table, u32* bad, u32* first) {
+    const int i = item();
+    if (i >= n_bases) return;
+    ge p = gens[i];
+    u32 n_bad = 0, at = (u32)n_pos;
+#pragma unroll 1
+    for (int b = 0; b < n_pos; b++) {
+        const niels_row* row = table + (size_t)i * n_pos + b;
+        const row_regs rp = load_row_at(row, 0u), rm = load_row_at(row, 1u);
+        const ge next = ge_dbl(p);
+        const ge plus = ge_madd_row(ge_identity(), rp, false), minus = ge_madd_row(ge_identity(), rm, true);
+        const ge sum = ge_madd_row(p, rp, false), diff = ge_madd_row(p, rm, true);
+        const u32 miss = (same_point(plus, p) ? 0u : 1u) + (same_point(minus, ge_neg(p)) ? 0u : 1u) + (same_point(sum, next) ? 0u : 1u) +
+                         (same_point(diff, ge_identity()) ? 0u : 1u);
+        if (miss && at == (u32)n_pos) at = (u32)b;
+        n_bad += miss;
+        p = next;
+    }
+    bad[i] = n_bad;
+    first[i] = at;
+}
+
+// thread per sampled row: identity + row and basepoint + row (an accumulator with T != 0: the row's 2dxy takes part), encoded
+__global__ void k_ptable_rows(int n, const niels_row* table, const u32* row_idx, u8* out32, u8* out_b32) {
+    const int i = item();
+    if (i >= n) return;
+    const row_regs r = load_row_at(table + row_idx[i], 0u);
+    ge_encode(out32 + 32 * (size_t)i, ge_madd_row(ge_identity(), r, false));
+    ge_encode(out_b32 + 32 * (size_t)i, ge_madd_row(ge_basepoint(), r, false));
+}
+
+// thread per comb entry: loaded as comb_mul_add loads it; the point from y+x and y-x, encoded, and whether the entry's third field
+// is 2d x y of that point (ge_from_niels does not read it, a mixed addition onto T != 0 does)
+__global__ void k_comb_entries(int n_entries, const niels_packed* comb, u8* out32, i32* xy2d_ok) {
+    const int i = item();
+    if (i >= n_entries) return;
+    ge_niels e;
+    BBP_COMB_LOAD(e, comb + i);
+    const ge p = ge_from_niels(e);  // Z = 1
+    ge_encode(out32 + 32 * (size_t)i, p);
+    xy2d_ok[i] = fe_eq(e.xy2d, fe_mul(p.T, fe_d2())) ? 1 : 0;
+}
+
 // the 8-entry tables are indexed by digit magnitude: only canonical scalars (digits within [-8, 8]) may reach a kernel
 bool all_canonical(const uint8_t* s32, size_t n) {
     for (size_t i = 0; i < n; i++) {
@@ -722,5 +782,61 @@ int dc_straus(int np, const uint8_t* pts32, int n, const int32_t* cnt, const uin
     c.back(sp_out, sp, 32 * slots);
     c.back(pt_ok, ok, 4 * (size_t)np);
     return (int)c.err;
+}
+// ---- the engine's resident tables ---------------------------------------------------------------------------------------------
+// `dev` is a device pointer of this process (bbp_debug_table) holding at least the stated number of elements; nothing is written to it
+// n points of 160 bytes -> n encodings
+int dc_points_encode(const void* dev, int n, uint8_t* out32) {
+    if (!dev || n <= 0) return (int)hipErrorInvalidValue;
+    Call c;
+    u8* o = c.out<u8>(32 * (size_t)n);
+    c.launch(k_points_encode, blocks_for(n), BLOCK, n, static_cast<const ge*>(dev), o);
+    c.back(out32, o, 32 * (size_t)n);
+    return (int)c.err;
+}
+
+// n comb entries of 96 bytes -> n encodings and n flags (k_comb_entries)
+int dc_comb_entries(const void* dev, int n, uint8_t* out32, int32_t* xy2d_ok) {
+    if (!dev || n <= 0) return (int)hipErrorInvalidValue;
+    Call c;
+    u8* o = c.out<u8>(32 * (size_t)n);
+    i32* f = c.out<i32>(4 * (size_t)n);
+    c.launch(k_comb_entries, blocks_for(n), BLOCK, n, static_cast<const niels_packed*>(dev), o, f);
+    c.back(out32, o, 32 * (size_t)n);
+    c.back(xy2d_ok, f, 4 * (size_t)n);
+    return (int)c.err;
+}
+
+// gens: n_bases points in gens_bytes; table: n_bases * n_pos rows in table_bytes.  bad / first: n_bases entries each (k_ptable_walk)
+int dc_ptable_walk(const void* gens_dev, uint64_t gens_bytes, const void* table_dev, uint64_t table_bytes, int n_bases, int n_pos, uint32_t* bad,
+                   uint32_t* first) {
+    if (!gens_dev || !table_dev || n_bases <= 0 || n_pos <= 0) return (int)hipErrorInvalidValue;
+    if (sizeof(ge) * (uint64_t)n_bases > gens_bytes || sizeof(niels_row) * (uint64_t)n_bases * (uint64_t)n_pos > table_bytes) return (int)hipErrorInvalidValue;
+    Call c;
+    u32 *b = c.out<u32>(4 * (size_t)n_bases), *f = c.out<u32>(4 * (size_t)n_bases);
+    c.launch(k_ptable_walk, blocks_for(n_bases), BLOCK, n_bases, n_pos, static_cast<const ge*>(gens_dev), static_cast<const niels_row*>(table_dev), b, f);
+    c.back(bad, b, 4 * (size_t)n_bases);
+    c.back(first, f, 4 * (size_t)n_bases);
+    return (int)c.err;
+}
+
+// rows row_idx[0..n) of a table of n_rows rows, each added to the identity (out32) and to the basepoint (out_b32) and encoded
+int dc_ptable_rows(const void* table_dev, uint64_t n_rows, int n, const uint32_t* row_idx, uint8_t* out32, uint8_t* out_b32) {
+    if (!table_dev || n <= 0) return (int)hipErrorInvalidValue;
+    for (int i = 0; i < n; i++)
+        if (row_idx[i] >= n_rows) return (int)hipErrorInvalidValue;
+    Call c;
+    const u32* ri = c.in<const u32>(row_idx, 4 * (size_t)n);
+    u8 *o = c.out<u8>(32 * (size_t)n), *ob = c.out<u8>(32 * (size_t)n);
+    c.launch(k_ptable_rows, blocks_for(n), BLOCK, n, static_cast<const niels_row*>(table_dev), ri, o, ob);
+    c.back(out32, o, 32 * (size_t)n);
+    c.back(out_b32, ob, 32 * (size_t)n);
+    return (int)c.err;
+}
+
+// n words of a device array (the base-index lists)
+int dc_read_u32(const void* dev, int n, uint32_t* out) {
+    if (!dev || n <= 0) return (int)hipErrorInvalidValue;
+    return (int)hipMemcpy(out, dev, 4 * (size_t)n, hipMemcpyDeviceToHost);
 }
 }

@@ -106,13 +106,14 @@ def test_exception_barrier_turns_a_throw_into_a_status(bbp, monkeypatch):
 def test_device_check_libraries_export_every_entry_point(built, bbp):
     """tests/device_check.hip (the gpu tier's view of the product headers) cross-compiles for gfx950 in both field variants, and both
     libraries load and export every dc_* entry point the source defines, each one bound in tests/test_gpu_device_arith.py or, for
-    the scalar multiplications of csrc/scalarmul.h, in tests/scalarmul_run.py"""
+    the scalar multiplications of csrc/scalarmul.h, in tests/scalarmul_run.py, for the table audit in tests/table_run.py"""
     from tests.scalarmul_run import SIGNATURES as SCALARMUL
+    from tests.table_run import SIGNATURES as TABLES
     from tests.test_gpu_device_arith import SIGNATURES, VARIANTS
     src = open(os.path.join(ROOT, "tests", "device_check.hip")).read()
     defined = sorted(set(re.findall(r"^int (dc_[a-z0-9_]+)\(", src, flags=re.M)))
-    bound = sorted(list(SIGNATURES) + ["dc_" + name for name in SCALARMUL])
-    assert len(defined) >= 13 + 6 and defined == bound
+    bound = sorted(list(SIGNATURES) + ["dc_" + name for name in SCALARMUL] + ["dc_" + name for name in TABLES])
+    assert len(defined) >= 13 + 6 + 5 and defined == bound
     for v in VARIANTS:
         path = built.build_devcheck(v)
         blob = open(path, "rb").read()

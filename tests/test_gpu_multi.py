@@ -216,6 +216,14 @@ def test_pool_refuses_device_pointer_calls(pool, bbp):
         pool.prove_batch_dev(1, 8, buf.data_ptr(), buf.data_ptr(), buf.data_ptr())
     assert e.value.status == 4 and "pool" in str(e.value)
     assert pool.stream is None and pool.member(0).stream is not None
+    with pytest.raises(bbp.BbpError) as e:  # the table pointers and the kernel hook belong to one device as well
+        pool.debug_table(bbp.TABLE_GENS)
+    assert e.value.status == 4 and "pool" in str(e.value)
+    one = (1, 0, [bytes(32)] * bbp.varbase_points(1), (1, 1, 1, 1), (1,) * 5, (1,) * 22)
+    with pytest.raises(bbp.BbpError) as e:
+        pool.debug_varbase(bbp.VARBASE_PREP_SUM, [one])
+    assert e.value.status == 4 and "pool" in str(e.value)
+    assert pool.member(0).debug_table(bbp.TABLE_GENS)[1] == 8396 * 160
     # a member is an ordinary context: the setup read-backs agree with the pool's (served by member 0)
     assert pool.generator(bbp.BASE_G0 + 5) == pool.member(1).generator(bbp.BASE_G0 + 5)
 
