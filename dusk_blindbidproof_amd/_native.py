@@ -74,6 +74,8 @@ SIGNATURES = {
     "bbp_reserve": (_i32, [_vp, _u32, _u32]),
     "bbp_set_batching": (_i32, [_vp, _u32, _u32]),
     "bbp_set_verify_mixing": (_i32, [_vp, _i32]),
+    "bbp_set_verify_round_sharing": (_i32, [_vp, _i32]),
+    "bbp_verify_round_sharing_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_batching_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u32)]),
     "bbp_debug_compile_circuit": (_i32, [_u32, ctypes.POINTER(_u32), ctypes.POINTER(_u32)]),
     "bbp_check_health": (_i32, [_vp, ctypes.POINTER(_u32)]),
@@ -502,6 +504,18 @@ class Context:
         whatever their bid-list length and record layout; off = one call per list length and layout.  Same verdicts either way."""
         self._check(lib.bbp_set_verify_mixing(self._h, 1 if on else 0))
 
+    def set_verify_round_sharing(self, on):
+        """Verify round sharing (bbp_set_verify_round_sharing, default off): concurrent verify() / verify_async() requests whose seed and
+        bid list are byte-equal leave as one rounds call, the table holding each distinct round once.  A batch shares when all its
+        records are compact and it holds fewer distinct rounds than requests; any other batch runs as with sharing off.  Same verdicts."""
+        self._check(lib.bbp_set_verify_round_sharing(self._h, 1 if on else 0))
+
+    def verify_round_sharing_stats(self):
+        """(rounds calls the combiner issued, rows they carried, rounds their tables held) since the context was created."""
+        a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib.bbp_verify_round_sharing_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+        return a.value, b.value, c.value
+
     def batching_stats(self):
         """(combined device calls, requests they carried, largest batch) since the context was created."""
         a, b, c = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
@@ -656,6 +670,14 @@ class Pool(Context):
     def set_verify_mixing(self, on):
         """bbp_set_verify_mixing on the pool: the pool's combiner, which deals the combined calls to the members."""
         super().set_verify_mixing(on)
+
+    def set_verify_round_sharing(self, on):
+        """bbp_set_verify_round_sharing on the pool: the pool's combiner."""
+        super().set_verify_round_sharing(on)
+
+    def verify_round_sharing_stats(self):
+        """bbp_verify_round_sharing_stats on the pool: the totals of the pool's combiner (`pool.member(i)`: the calls dealt to member i)."""
+        return super().verify_round_sharing_stats()
 
     def member_stats(self, i):
         """(combined prove / verify device calls dealt to member i, requests they carried)"""

@@ -1214,6 +1214,16 @@ int32_t bbp::verify_batch_mixed_locked(bbp_ctx* ctx, uint32_t B, const uint32_t*
     return rc;
 }
 
+// what the call combiner runs for concurrent bbp_verify callers that share rounds (submit.cpp: the runner handed to
+// Combiner::set_round_verify): bbp_verify_rounds' path from verify_host down -- the host chunk loop, the health word, device entropy,
+// the aggregated engine when the context verifies aggregated.  Table and rows come from requests that bbp_verify has screened.
+int32_t bbp::verify_rounds_locked(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                  const uint8_t* rows, int32_t* status, std::string* err) {
+    const int32_t rc = verify_host(ctx, VerifyRows::of_rounds(B, R, round_Ns, rounds, round_of), rows, status, 0, nullptr);
+    if (rc && err) *err = tls_error();
+    return rc;
+}
+
 // ---- the twelve verify entry points: uniform, mixed-N, rounds (include/bbp.h) x host / device pointers x plain / aggregated --------
 // Every row's N is screened on the host before anything is verified: a 0 anywhere is BBP_ERR_BAD_ARG, else an N above
 // BBP_MAX_ITEMS anywhere is BBP_ERR_GENS_LEN -- what a uniform call with that N returns.
@@ -1403,7 +1413,12 @@ extern "C" int32_t bbp_verify(bbp_ctx* ctx, const uint8_t* record, uint32_t reco
         r.rec_ver = ver;
         r.in = in.data();
         r.in_len = in.size();
-        const int32_t st = static_cast<Combiner*>(ctx->combiner)->submit(ctx, r);
+        Combiner* const comb = static_cast<Combiner*>(ctx->combiner);
+        if (comb->round_sharing()) {  // on the caller's thread: the cost spreads over the callers
+            r.round_hash = hash_bytes(r.in + record_len + 64, round_bytes(N));
+            r.round_hash_valid = true;
+        }
+        const int32_t st = comb->submit(ctx, r);
         if (st != BBP_OK) set_tls_error(ctx, !r.err.empty() ? r.err : st == BBP_ERR_VERIFY ? "proof rejected" : "malformed proof");
         return st;
     }, ctx);
@@ -1430,7 +1445,12 @@ extern "C" int32_t bbp_verify_async(bbp_ctx* ctx, const uint8_t* record, uint32_
         r->origin = ctx;
         r->user_fn = done;
         r->user = user;
-        if (!static_cast<Combiner*>(ctx->combiner)->submit_async(ctx, r)) {
+        Combiner* const comb = static_cast<Combiner*>(ctx->combiner);
+        if (comb->round_sharing()) {
+            r->round_hash = hash_bytes(r->in + record_len + 64, round_bytes(N));
+            r->round_hash_valid = true;
+        }
+        if (!comb->submit_async(ctx, r)) {
             delete r;
             set_tls_error(ctx, "call combiner: cannot start a batch thread");
             return BBP_ERR_INTERNAL;
@@ -1535,6 +1555,25 @@ extern "C" int32_t bbp_set_verify_mixing(bbp_ctx* ctx, int32_t on) {
     if (!ctx || !ctx->combiner) return BBP_ERR_BAD_ARG;
     return no_throw([&]() -> int32_t {
         static_cast<Combiner*>(ctx->combiner)->set_verify_mixing(on != 0);
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_set_verify_round_sharing(bbp_ctx* ctx, int32_t on) {
+    if (!ctx || !ctx->combiner) return BBP_ERR_BAD_ARG;
+    return no_throw([&]() -> int32_t {
+        static_cast<Combiner*>(ctx->combiner)->set_round_sharing(on != 0);
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_verify_round_sharing_stats(bbp_ctx* ctx, uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds) {
+    if (!ctx || !ctx->combiner) return BBP_ERR_BAD_ARG;
+    return no_throw([&]() -> int32_t {
+        if (ctx->owner && ctx->owner->combiner)  // a pool member: the rounds calls its pool's combiner has dealt to it
+            static_cast<Combiner*>(ctx->owner->combiner)->target_round_stats(ctx->member_index, n_calls, n_rows, n_rounds);
+        else
+            static_cast<Combiner*>(ctx->combiner)->round_stats(n_calls, n_rows, n_rounds);
         return BBP_OK;
     });
 }

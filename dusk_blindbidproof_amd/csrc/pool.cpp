@@ -335,6 +335,7 @@ extern "C" int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp
         pool->combiner = c;
         c->set_targets(made);
         c->set_mixed_verify(verify_batch_mixed_locked);
+        c->set_round_verify(verify_rounds_locked);
         if (const char* e = getenv("BBP_BATCH_WINDOW_US")) c->configure((uint32_t)atoi(e), 0);
         const char* e = getenv("BBP_BATCH_STAGGER_US");
         c->set_stagger(e ? (uint32_t)atoi(e) : 35000u);

@@ -192,6 +192,7 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
     *out = ctx;  // returned even on failure so bbp_last_error works; caller frees
     ctx->combiner = new Combiner();
     static_cast<Combiner*>(ctx->combiner)->set_mixed_verify(verify_batch_mixed_locked);  // concurrent bbp_verify callers of any N share a call
+    static_cast<Combiner*>(ctx->combiner)->set_round_verify(verify_rounds_locked);  // ... and, with round sharing on, their seed and bid list
     if (const char* e = getenv("BBP_BATCH_WINDOW_US")) static_cast<Combiner*>(ctx->combiner)->configure((uint32_t)atoi(e), 0);
     {  // the prover's opening stage lasts ~36 ms whatever the batch size: a second batch starts no earlier
         const char* e = getenv("BBP_BATCH_STAGGER_US");
@@ -493,6 +494,10 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                       static_cast<Combiner*>(ctx->owner && ctx->owner->combiner ? ctx->owner->combiner : ctx->combiner)->verify_mixing()
                                           ? "on (concurrent bbp_verify callers share a call whatever their bid-list length)"
                                           : "off (one call per bid-list length and record layout)");
+        if (off + 1 < cap && ctx->combiner &&
+            static_cast<Combiner*>(ctx->owner && ctx->owner->combiner ? ctx->owner->combiner : ctx->combiner)->round_sharing())
+            off += (uint32_t)snprintf(buf + off, cap - off,
+                                      "verify round sharing: on (concurrent bbp_verify callers with a byte-equal seed and bid list share one table entry)\n");
         if (off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "entropy source: %s\n",
                                       ctx->entropy_source == BBP_ENTROPY_SOURCE_DEVICE

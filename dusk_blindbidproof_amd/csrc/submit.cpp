@@ -6,6 +6,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <unordered_map>
 
 namespace bbp {
 
@@ -87,6 +88,31 @@ void Combiner::set_verify_mixing(bool on) {
 bool Combiner::verify_mixing() {
     std::lock_guard<std::mutex> lk(mu_);
     return mixing_ && mixed_fn_;
+}
+
+void Combiner::set_round_verify(RoundVerifyFn fn) {
+    std::lock_guard<std::mutex> lk(mu_);
+    round_fn_ = fn;
+}
+
+void Combiner::set_round_sharing(bool on) {
+    std::lock_guard<std::mutex> lk(mu_);
+    sharing_.store(on, std::memory_order_relaxed);
+}
+
+void Combiner::round_stats(uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds) {
+    std::lock_guard<std::mutex> lk(mu_);
+    if (n_calls) *n_calls = round_counts_.calls;
+    if (n_rows) *n_rows = round_counts_.rows;
+    if (n_rounds) *n_rounds = round_counts_.rounds;
+}
+
+void Combiner::target_round_stats(size_t i, uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds) {
+    std::lock_guard<std::mutex> lk(mu_);
+    const RoundCounts c = i < targets_.size() ? targets_[i].round_counts : RoundCounts{};
+    if (n_calls) *n_calls = c.calls;
+    if (n_rows) *n_rows = c.rows;
+    if (n_rounds) *n_rounds = c.rounds;
 }
 
 // verify requests are one class when the engine can run them in one call (a mixed-N runner is installed, mixing is on)
@@ -316,10 +342,18 @@ void Combiner::thread_main(int kind) {
         const size_t q_left = q_.size();
         const int inflight_before = proving ? targets_[ti].prove_inflight - 1 : 0;
         const MixedVerifyFn mixed = mixing_ ? mixed_fn_ : nullptr;
-        uint32_t n_distinct = 1;
+        const RoundVerifyFn rounds = sharing_.load(std::memory_order_relaxed) ? round_fn_ : nullptr;
+        uint32_t n_distinct = 1, n_rounds = 0;
         lk.unlock();
-        run_batch(where, batch, mixed, &n_distinct);
+        run_batch(where, batch, mixed, rounds, &n_distinct, &n_rounds);
         lk.lock();
+        if (n_rounds) {  // the batch left as a rounds call
+            for (RoundCounts* c : {&round_counts_, &targets_[ti].round_counts}) {
+                c->calls++;
+                c->rows += batch.size();
+                c->rounds += n_rounds;
+            }
+        }
         if (log_) {  // BBP_BATCH_LOG: start (ms since the combiner was made), duration, kind, target, size, prove batches already in flight, queue left behind
             const auto t_end = std::chrono::steady_clock::now();
             fprintf(log_, "%.2f %.2f %s %zu %zu %d %zu %.1f %u\n", std::chrono::duration<double, std::milli>(t_batch - t0_).count(),
@@ -367,13 +401,81 @@ void Combiner::thread_main(int kind) {
     }
 }
 
-void Combiner::run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerifyFn mixed, uint32_t* n_distinct) {
+// Round sharing: the batch as one rounds call, when it holds fewer distinct rounds than requests.  The round of a request is the
+// tail of its input; its hash finds the candidates, memcmp decides -- two lists that differ in one raw byte are two rounds even if they
+// reduce to the same scalars, so that every row meets exactly the bytes its caller sent.
+bool Combiner::run_rounds(bbp_ctx* ctx, std::vector<Request*>& batch, RoundVerifyFn rounds, uint32_t* n_distinct, uint32_t* n_rounds) {
+    const uint32_t B = (uint32_t)batch.size();
+    for (uint32_t i = 0; i < B; i++)
+        if (batch[i]->rec_ver != 0 || batch[i]->in_len < round_bytes(batch[i]->N)) return false;  // the rounds call takes compact records only
+    std::vector<uint32_t> round_of(B), round_ns, next_same_hash;
+    std::vector<const uint8_t*> round_at;
+    std::unordered_map<uint64_t, uint32_t> by_hash;  // hash -> the first round that has it; further ones chained through next_same_hash
+    const uint32_t NONE = 0xffffffffu;
+    size_t tab_bytes = 0, row_bytes = 0;
+    for (uint32_t i = 0; i < B; i++) {
+        Request& q = *batch[i];
+        const size_t len = round_bytes(q.N);
+        const uint8_t* mine = q.in + (q.in_len - len);
+        if (!q.round_hash_valid) {
+            q.round_hash = hash_bytes(mine, len);
+            q.round_hash_valid = true;
+        }
+        auto found = by_hash.find(q.round_hash);
+        uint32_t r = found == by_hash.end() ? NONE : found->second, last = NONE;
+        for (; r != NONE; last = r, r = next_same_hash[r])
+            if (round_ns[r] == q.N && memcmp(round_at[r], mine, len) == 0) break;
+        if (r == NONE) {  // first appearance: the next round of the table
+            r = (uint32_t)round_ns.size();
+            round_ns.push_back(q.N);
+            round_at.push_back(mine);
+            next_same_hash.push_back(NONE);
+            if (last == NONE)
+                by_hash.emplace(q.round_hash, r);
+            else
+                next_same_hash[last] = r;
+            tab_bytes += len;
+        }
+        round_of[i] = r;
+        row_bytes += q.in_len - len;
+    }
+    const uint32_t R = (uint32_t)round_ns.size();
+    if (R >= B) return false;  // nothing is shared: the expanded rows are no larger than rows and table
+    std::vector<uint8_t> table(tab_bytes), rows(row_bytes);
+    size_t off = 0;
+    for (uint32_t r = 0; r < R; r++) {
+        memcpy(&table[off], round_at[r], round_bytes(round_ns[r]));
+        off += round_bytes(round_ns[r]);
+    }
+    off = 0;
+    for (uint32_t i = 0; i < B; i++) {  // rows back to back in queue order
+        const size_t len = batch[i]->in_len - round_bytes(batch[i]->N);
+        memcpy(&rows[off], batch[i]->in, len);
+        off += len;
+    }
+    std::vector<uint32_t> seen = round_ns;
+    std::sort(seen.begin(), seen.end());
+    *n_distinct = (uint32_t)(std::unique(seen.begin(), seen.end()) - seen.begin());
+    std::vector<int32_t> status(B, 6);
+    std::string err;
+    *n_rounds = R;  // from here on the call is issued
+    const int32_t rc = rounds(ctx, R, round_ns.data(), table.data(), B, round_of.data(), rows.data(), status.data(), &err);
+    for (uint32_t i = 0; i < B; i++) {
+        batch[i]->status = rc ? rc : status[i];
+        if (rc) batch[i]->err = err;
+    }
+    return true;
+}
+
+void Combiner::run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerifyFn mixed, RoundVerifyFn rounds, uint32_t* n_distinct,
+                         uint32_t* n_rounds) {
     const Request& h = *batch[0];
     const uint32_t B = (uint32_t)batch.size();
     int32_t rc;
     std::string err;
     std::vector<int32_t> status(B, 6);
     try {
+        if (h.kind == 1 && rounds && B > 1 && run_rounds(ctx, batch, rounds, n_distinct, n_rounds)) return;
         // a verify batch formed as the merged class: uniform (every member of the head's list length, layout and row size: the call
         // every single-N workload has always made) unless a member differs
         bool uniform = true;

@@ -12,6 +12,10 @@
 // per device: the host-pointer batch calls hold the context lock only while they enqueue, so the second batch's host work and
 // its opening stage on the device run under the first batch's MSM stage -- the engine's cross-call pipeline, kept full by the
 // queue.
+// Round sharing (set_round_sharing, off by default): a verify batch of compact records in which some members carry a byte-equal
+// seed || pub_list leaves as ONE rounds call (set_round_verify: the engine's bbp_verify_rounds path) -- the table holds every
+// distinct round once, the rows are record || score || z_img.  Bytes decide which requests share a round; R < B decides whether
+// the batch takes the call at all.  Every other batch takes the path it took before.
 // Round 3: the batches are run by the combiner's OWN threads (two per target, started with the first request) instead of by
 // whichever caller found a free leader slot.  That is what makes the asynchronous entry points possible (bbp_prove_async /
 // bbp_verify_async: a request is queued and a callback fires when its batch is done -- what an epoll server or a Rust Future
@@ -20,7 +24,9 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <deque>
@@ -52,7 +58,36 @@ struct Request {
     void* user = nullptr;
     const void* origin = nullptr;  // the handle the request was made on (a pool or a context): whose error slot the message belongs to
     std::vector<uint8_t> own_in, own_entropy;  // storage of an asynchronous request's inputs (in / entropy point into them)
+    // verify, round sharing: hash_bytes over the request's round, the last 32 (1 + N) bytes of `in` (seed || pub_list).  Filled on the
+    // caller's thread when sharing is on; the combiner computes it for a request that comes without one.  It only finds the
+    // candidate round: memcmp decides.
+    uint64_t round_hash = 0;
+    bool round_hash_valid = false;
 };
+
+// the round of a verify request: seed || pub_list, the tail of its input
+inline size_t round_bytes(uint32_t N) { return 32 * (1 + (size_t)N); }
+
+// A fast 64-bit hash of a byte range (multiply-xorshift over 8-byte words; not cryptographic, and nothing relies on it being so:
+// a collision costs one memcmp).
+inline uint64_t hash_bytes(const uint8_t* p, size_t n) {
+    uint64_t h = 0x9e3779b97f4a7c15ull ^ ((uint64_t)n * 0xff51afd7ed558ccdull);
+    for (; n >= 8; p += 8, n -= 8) {
+        uint64_t w;
+        memcpy(&w, p, 8);
+        h = (h ^ w) * 0x9fb21c651e98df25ull;
+        h ^= h >> 29;
+    }
+    if (n) {
+        uint64_t w = 0;
+        memcpy(&w, p, n);
+        h = (h ^ w) * 0x9fb21c651e98df25ull;
+        h ^= h >> 29;
+    }
+    h ^= h >> 32;
+    h *= 0xd6e8feb86659fd93ull;
+    return h ^ (h >> 32);
+}
 
 // what a combined call runs (capi_prove.hip); both take the context lock themselves
 int32_t prove_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status,
@@ -65,6 +100,13 @@ int32_t verify_batch_mixed_locked(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, 
                                   std::string* err);
 using MixedVerifyFn = int32_t (*)(bbp_ctx* ctx, uint32_t B, const uint32_t* Ns, const uint8_t* vers, const uint8_t* in, int32_t* status,
                                   std::string* err);
+// ... and what a verify batch whose members share rounds runs (bbp_verify_rounds' arguments): the table is seed || pub_list of each of
+// the R distinct rounds, round_Ns[r] its list length; row i is record || score || z_img of round round_of[i], rows packed back to back
+// in queue order, compact records only.  Handed over with Combiner::set_round_verify like the mixed runner.
+int32_t verify_rounds_locked(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                             const uint8_t* rows, int32_t* status, std::string* err);
+using RoundVerifyFn = int32_t (*)(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                  const uint8_t* rows, int32_t* status, std::string* err);
 
 class Combiner {
   public:
@@ -112,14 +154,35 @@ class Combiner {
     void set_mixed_verify(MixedVerifyFn fn);
     void set_verify_mixing(bool on);
     bool verify_mixing();  // on AND a runner is installed
+    // Round sharing (default off).  With a rounds runner installed and sharing on, a verify batch takes ONE rounds call when every
+    // member has a compact record and the batch holds fewer distinct rounds than requests (R < B: the call then uploads strictly fewer
+    // bytes than the expanded rows).  Two requests are in the same round when their N is equal and their seed || pub_list bytes are
+    // memcmp-equal; rounds are numbered in order of first appearance in queue order.  Any other batch -- a two-phase record among the
+    // members, R == B (so every batch of one), sharing off, no runner -- takes exactly the path it takes without the switch.  How
+    // batches are formed does not change.
+    void set_round_verify(RoundVerifyFn fn);
+    void set_round_sharing(bool on);
+    bool round_sharing() const { return sharing_.load(std::memory_order_relaxed); }  // the switch alone (what a caller asks before it hashes)
+    // rounds calls issued / rows they carried / rounds their tables held (any may be NULL); per target for a pool
+    void round_stats(uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds);
+    void target_round_stats(size_t i, uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds);
 
   private:
-    // mixed: the runner as it stood when the batch was formed (a batch formed as one merged class needs it whatever happens to the
-    // switch meanwhile); *n_distinct: the number of distinct list lengths the batch held (batch log)
-    void run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerifyFn mixed, uint32_t* n_distinct);
+    // mixed / rounds: the runners as they stood when the batch was formed (a batch formed as one merged class needs the mixed one
+    // whatever happens to the switch meanwhile; rounds is null with sharing off); *n_distinct: the number of distinct list lengths the
+    // batch held (batch log); *n_rounds: the rounds in the table when the batch left as a rounds call, else 0
+    void run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerifyFn mixed, RoundVerifyFn rounds, uint32_t* n_distinct, uint32_t* n_rounds);
+    // the rounds call of a verify batch; false = the batch does not qualify and nothing was run
+    bool run_rounds(bbp_ctx* ctx, std::vector<Request*>& batch, RoundVerifyFn rounds, uint32_t* n_distinct, uint32_t* n_rounds);
     bool same_class_locked(const Request* a, const Request* b) const;
     MixedVerifyFn mixed_fn_ = nullptr;
     bool mixing_ = true;
+    RoundVerifyFn round_fn_ = nullptr;
+    std::atomic<bool> sharing_{false};  // written under mu_; read without it by callers that decide whether to hash
+    struct RoundCounts {
+        uint64_t calls = 0, rows = 0, rounds = 0;
+    };
+    RoundCounts round_counts_;
     struct Target {
         bbp_ctx* ctx = nullptr;
         int running[2] = {0, 0};  // combined calls reserved / running on this target, per kind (0 = prove, 1 = verify)
@@ -130,6 +193,7 @@ class Combiner {
         size_t last_done_size = 0;                           // ... and how many callers it carried
         std::chrono::steady_clock::time_point est_end{};     // when the prove batches dealt to this target so far are expected to be done
         uint64_t n_calls = 0, n_requests = 0;
+        RoundCounts round_counts;
     };
     std::vector<Target> targets_;  // empty until the first submit of a plain context (then: that context)
     size_t rr_ = 0;                // tie-break cursor

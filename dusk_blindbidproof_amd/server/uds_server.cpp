@@ -531,7 +531,7 @@ static void usage(const char* argv0) {
     fprintf(stderr,
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
-            "          [--check-proofs] [--entropy os|device] [--verify-mixing on|off]\n",
+            "          [--check-proofs] [--entropy os|device] [--verify-mixing on|off] [--verify-rounds on|off]\n",
             argv0);
 }
 
@@ -545,6 +545,7 @@ int main(int argc, char** argv) {
     bool check_proofs = false;  // --check-proofs: every proof is verified on the device before it is answered (bbp_set_prove_check)
     bool device_entropy = false;  // --entropy device: one OS key per engine call, expanded on the device (bbp_set_entropy_source)
     int verify_mixing = -1;  // --verify-mixing on|off: opcode-2 requests share device calls across bid-list lengths (bbp_set_verify_mixing); -1 = not given, the engine's default (on)
+    int verify_rounds = -1;  // --verify-rounds on|off: opcode-2 requests with a byte-equal seed and bid list share one rounds call (bbp_set_verify_round_sharing); -1 = not given, no call is made (the engine's default: off)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -593,6 +594,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
             verify_mixing = v == "on";
+        }
+        else if (a == "--verify-rounds") {
+            const std::string v = val();
+            if (v != "on" && v != "off") {
+                usage(argv[0]);
+                return 2;
+            }
+            verify_rounds = v == "on";
         }
         else if (a == "--reserve") {
             for (const char* p = val(); *p;) {
@@ -672,6 +681,20 @@ int main(int argc, char** argv) {
             if (!set_mixing) logf(1, "--verify-mixing on: the engine %s has no such switch; its own grouping of verify requests applies", engine_path.c_str());
             else logf(2, "verify mixing %s: opcode-2 requests %s", verify_mixing ? "on" : "off",
                       verify_mixing ? "share device calls whatever their bid-list length" : "are batched per bid-list length and record layout");
+        }
+        if (verify_rounds >= 0) {  // resolved only when asked for; an engine without the call verifies every request against its own copy of the round
+            auto set_rounds = (decltype(&bbp_set_verify_round_sharing))dlsym(g_eng.so, "bbp_set_verify_round_sharing");
+            if (set_rounds && set_rounds(g_eng.ctx, verify_rounds) != BBP_OK) {
+                logf(0, "--verify-rounds %s: the engine %s refused the setting (bbp_set_verify_round_sharing)", verify_rounds ? "on" : "off", engine_path.c_str());
+                g_eng.free_(g_eng.ctx);
+                return 2;
+            }
+            if (!set_rounds)
+                logf(1, "--verify-rounds %s: the engine %s has no such setting (bbp_set_verify_round_sharing); every opcode-2 request is verified with its own seed and bid list",
+                     verify_rounds ? "on" : "off", engine_path.c_str());
+            else
+                logf(2, "verify round sharing %s: opcode-2 requests %s", verify_rounds ? "on" : "off",
+                     verify_rounds ? "with a byte-equal seed and bid list share one rounds call, the round sent once" : "each carry their seed and bid list to the device");
         }
         if (g_eng.describe) {  // what the engine runs on; its WARNING lines (hardware queues, memory) at warn level
             static char report[8192];

@@ -323,6 +323,26 @@ int32_t bbp_set_batching(bbp_ctx* ctx, uint32_t window_us, uint32_t max_batch);
  * mixing misbehave.  The verdicts are the same either way.  A mixed call sizes its per-row scratch by its largest N (see
  * bbp_reserve: reserve for the largest N expected).  On a pool: the pool's combiner.  bbp_describe reports the setting. */
 int32_t bbp_set_verify_mixing(bbp_ctx* ctx, int32_t on);
+/* Verify round sharing (default OFF): concurrent bbp_verify / bbp_verify_async requests that carry a byte-equal seed || pub_list
+ * leave the call combiner as ONE bbp_verify_rounds call whose table holds every distinct round once, instead of a batch in which
+ * every row repeats its round (at N = 202: 7 777 instead of 14 273 bytes per request copied and uploaded, and the table's scalars
+ * reduced once per round instead of once per row).  Contract:
+ *   - The status of every request is exactly what bbp_verify returns with sharing off.
+ *   - Equality of rounds is equality of BYTES: two requests share a table entry when their N is equal and the 32 * (1 + N) bytes of
+ *     seed || pub_list are the same.  A hash only finds the candidate; it never decides.  Lists that differ in a raw byte are two
+ *     rounds even where they reduce to the same scalars, so every proof is checked against the very bytes its caller sent.
+ *   - A batch takes the rounds call when every member has a compact record and it holds fewer distinct rounds than requests
+ *     (R < B: the call then uploads strictly fewer bytes than the expanded rows; no tuned threshold).
+ *   - Every other batch takes the path it takes with sharing off, unchanged: a batch that holds a two-phase record, a batch in
+ *     which no two requests share a round (R == B, which covers a batch of one), any batch while sharing is off.
+ *   - How batches are formed does not change (bbp_set_batching, bbp_set_verify_mixing: with mixing off a batch is one N and layout,
+ *     and still shares the rounds of that N).
+ * A rounds call of several rounds sizes its per-row scratch by its largest N, as a mixed call does (bbp_set_verify_mixing, bbp_reserve).
+ * On a pool: the pool's combiner.  bbp_describe reports the setting while it is on.
+ * bbp_verify_round_sharing_stats: rounds calls the combiner has issued / rows they carried / rounds their tables held since
+ * bbp_init (any may be NULL); n_rounds < n_rows says that requests did share.  On a pool member: the calls dealt to that member. */
+int32_t bbp_set_verify_round_sharing(bbp_ctx* ctx, int32_t on);
+int32_t bbp_verify_round_sharing_stats(bbp_ctx* ctx, uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds);
 /* Combiner statistics since bbp_init: combined device calls issued / requests they carried / largest batch (any may be NULL). */
 int32_t bbp_batching_stats(bbp_ctx* ctx, uint64_t* n_calls, uint64_t* n_requests, uint32_t* max_seen);
 

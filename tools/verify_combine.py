@@ -14,6 +14,16 @@ every connection with one of the four N.  The arms alternate `--server-rounds` t
 of it, what one small device call costs for each of the four N and for a mixed call over them (the closed loop is bound by it).
 
     python tools/verify_combine.py --out profiles/r07_verify_combine.jsonl --server
+
+`--rounds`: round sharing instead (bbp_set_verify_round_sharing): the same bursts with sharing off and on, mixing left on.  Cases: one
+round at N = 8 and N = 202 (M from `--ms`), eight rounds of four list lengths (largest M), and rounds that are all distinct (smallest M:
+the fallback, which must come out level).  The arms alternate over `--runs` runs, each run the best of `--steps` after `--warmup`
+bursts per arm; a line reports every arm's median and range over the runs, the bytes each arm hands to the engine (expanded rows
+against short rows plus tables, from bbp_verify_round_sharing_stats), and `within_margin`: the on arm's median is not above the off
+arm's by more than the off arm's own range.  With `--server`: a verify-only closed loop of one round at N = 202 through
+bbp-uds-server `--verify-rounds off` and `on`.
+
+    python tools/verify_combine.py --rounds --server --out profiles/r11_verify_round_sharing.jsonl
 """
 import argparse
 import ctypes
@@ -55,6 +65,24 @@ def requests_for(ctx, N, count, r):
     assert st == [0] * count
     rs_ = bbp.record_size(N)
     return [(out[i * rs_:(i + 1) * rs_],) + tails[i] for i in range(count)]
+
+
+def round_requests(ctx, N, count, r):
+    """`count` valid requests (at most N) of ONE round: one seed, one list, the bids at list positions 0..count-1."""
+    count = min(count, N)
+    sd = sc(r)
+    dks = b"".join(r.getrandbits(64).to_bytes(8, "little") + bytes(24) + sc(r) + sd for _ in range(count))
+    w = ctx.witness_batch(dks)
+    wit = [[w[192 * i + 32 * j:192 * i + 32 * j + 32] for j in range(6)] for i in range(count)]
+    pub = [sc(r) for _ in range(N)]
+    for i in range(count):
+        pub[i] = wit[i][1]
+    pub = b"".join(pub)
+    ins = b"".join(dks[96 * i:96 * i + 64] + wit[i][2] + wit[i][3] + wit[i][4] + wit[i][5] + sd + pub + i.to_bytes(8, "little") for i in range(count))
+    out, st = ctx.prove_batch(count, N, ins)
+    assert st == [0] * count
+    rs_ = bbp.record_size(N)
+    return [(out[i * rs_:(i + 1) * rs_], wit[i][4], wit[i][5], sd, pub) for i in range(count)]
 
 
 class Burst:
@@ -103,6 +131,94 @@ def measure(ctx, b, warmup, steps):
         if best is None or dt < best["ms"] / 1e3:
             best = {"ms": round(dt * 1e3, 3), "submit_ms": round(t_sub * 1e3, 3), "calls": c1[0] - c0[0], "requests": c1[1] - c0[1]}
     return best
+
+
+def measure_rounds(ctx, b, warmup, steps):
+    """measure() with the round-sharing counters of the best burst beside it"""
+    for _ in range(warmup):
+        b.run()
+    best = None
+    for _ in range(steps):
+        c0, s0 = ctx.batching_stats(), ctx.verify_round_sharing_stats()
+        dt, t_sub = b.run()
+        c1, s1 = ctx.batching_stats(), ctx.verify_round_sharing_stats()
+        if best is None or dt < best["ms"] / 1e3:
+            best = {"ms": round(dt * 1e3, 3), "submit_ms": round(t_sub * 1e3, 3), "calls": c1[0] - c0[0], "round_calls": s1[0] - s0[0],
+                    "round_rows": s1[1] - s0[1], "round_tables": s1[2] - s0[2]}
+    return best
+
+
+def summarise(runs):
+    ms = sorted(x["ms"] for x in runs)
+    return {"median_ms": ms[len(ms) // 2], "range_ms": round(ms[-1] - ms[0], 3), "min_ms": ms[0], "max_ms": ms[-1]}
+
+
+def engine_bytes(reqs, n_rounds_case, best):
+    """Bytes the best burst handed to the engine: every request's expanded row, less what the rounds calls saved.  Exact when every
+    request left in a rounds call that held every round of the case (or when none did); else in proportion."""
+    expanded = sum(len(x) for q in reqs for x in q)
+    tails = sum(len(q[3]) + len(q[4]) for q in reqs)
+    distinct = {q[3] + q[4] for q in reqs}
+    tables = sum(len(t) for t in distinct)
+    M, rows, calls, held = len(reqs), best["round_rows"], best["round_calls"], best["round_tables"]
+    if calls == 0:
+        return expanded, True
+    exact = rows == M and held == calls * n_rounds_case
+    return int(expanded - tails * rows / M + tables * held / max(1, len(distinct))), exact
+
+
+def rounds_cases(a, ctx, r):
+    Ms = sorted(int(x) for x in a.ms.split(","))
+    cases, pool = [], {}
+    for n in (8, 202):
+        pool[n] = round_requests(ctx, n, a.per_n, r)
+        for M in Ms:
+            cases.append(("one_round_n%d" % n, 1, [pool[n][i % len(pool[n])] for i in range(M)]))
+    eight = [round_requests(ctx, n, a.per_n, r) for n in (8, 50, 120, 202) for _ in range(2)]
+    cases.append(("eight_rounds_four_lengths", 8, [eight[i % 8][(i // 8) % len(eight[i % 8])] for i in range(Ms[-1])]))
+    cases.append(("all_distinct_rounds_n8", Ms[0], requests_for(ctx, 8, Ms[0], r)))
+    return cases, pool
+
+
+def rounds_main(a):
+    ctx = bbp.Context(0)
+    ctx.set_batching(a.window_us, a.max_batch)
+    r = random.Random(1111)
+    cases, pool = rounds_cases(a, ctx, r)
+    lines = []
+    for name, n_rounds_case, reqs in cases:
+        b = Burst(ctx, reqs)
+        runs = {"off": [], "on": []}
+        for run in range(a.runs):
+            for arm in (("off", "on") if run % 2 == 0 else ("on", "off")):  # alternated: neither arm always runs on the warmer device
+                ctx.set_verify_round_sharing(arm == "on")
+                runs[arm].append(measure_rounds(ctx, b, a.warmup, a.steps))
+        ctx.set_verify_round_sharing(False)
+        line = {"case": name, "M": len(reqs), "rounds": n_rounds_case, "window_us": a.window_us, "max_batch": a.max_batch, "steps": a.steps,
+                "warmup": a.warmup, "runs": a.runs}
+        if a.label:
+            line["label"] = a.label
+        for arm in ("off", "on"):
+            best = min(runs[arm], key=lambda x: x["ms"])
+            nbytes, exact = engine_bytes(reqs, n_rounds_case, best)
+            line[arm] = dict(summarise(runs[arm]), best=best, engine_bytes=nbytes, engine_bytes_exact=exact)
+        line["off_over_on"] = round(line["off"]["median_ms"] / line["on"]["median_ms"], 3)
+        line["within_margin"] = line["on"]["median_ms"] <= line["off"]["median_ms"] + line["off"]["range_ms"]
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    assert ctx.health() == 0
+    ctx.close()
+    if a.server:
+        server_case(a, {202: pool[202]}, lines, flag="--verify-rounds", case="server_closed_loop_one_round_n202", reserve="202")
+        mine = [l for l in lines if l.get("case") == "server_closed_loop_one_round_n202"]
+        off = sorted(l["ops_per_s"] for l in mine if l["verify_rounds"] == "off")
+        on = sorted(l["ops_per_s"] for l in mine if l["verify_rounds"] == "on")
+        line = {"case": "server_closed_loop_one_round_n202_summary", "off_median_ops_per_s": off[len(off) // 2], "off_range": round(off[-1] - off[0], 1),
+                "on_median_ops_per_s": on[len(on) // 2], "on_range": round(on[-1] - on[0], 1)}
+        line["within_margin"] = line["on_median_ops_per_s"] >= line["off_median_ops_per_s"] - line["off_range"]
+        print(json.dumps(line), flush=True)
+        lines.append(line)
+    return lines
 
 
 def latency_case(ctx, pool, lines):
@@ -164,11 +280,11 @@ def client_main(path, frames_file, n_threads, seconds, index):
     print(json.dumps({"ops": sum(counts), "lat_ms": [round(x * 1e3, 3) for l in lat for x in l][::7], "errors": errors[:3]}))
 
 
-def server_case(a, pool, lines):
+def server_case(a, pool, lines, flag="--verify-mixing", case="server_closed_loop_four_values", reserve="202"):
     import pickle
     from tests import uds_client as uc
     frames = {}
-    for n in (8, 50, 120, 202):
+    for n in sorted(pool):
         frames[n] = []
         for r in pool[n]:
             body = r[0][1121:]
@@ -183,7 +299,7 @@ def server_case(a, pool, lines):
         for arm in ("off", "on"):
             d = tempfile.mkdtemp(prefix="bbp-vc-")
             path, blog = os.path.join(d, "sock"), os.path.join(d, "batches")
-            p = subprocess.Popen([server, "-b", path, "-l", "warn", "--engine", bbp.lib_path, "--device", "0", "--verify-mixing", arm, "--reserve", "202",
+            p = subprocess.Popen([server, "-b", path, "-l", "warn", "--engine", bbp.lib_path, "--device", "0", flag, arm, "--reserve", reserve,
                                   "--max-batch", "1024"], env=dict(os.environ, BBP_BATCH_LOG=blog))
             try:
                 for _ in range(6000):
@@ -202,7 +318,7 @@ def server_case(a, pool, lines):
             rows = [l.split() for l in open(blog) if l.strip()]
             v = [r for r in rows if r[2] == "verify"]
             all_lat = sorted(x for o in outs for x in o["lat_ms"])
-            line = {"case": "server_closed_loop_four_values", "verify_mixing": arm, "round": rnd, "connections": a.connections * a.client_procs,
+            line = {"case": case, flag[2:].replace("-", "_"): arm, "round": rnd, "connections": a.connections * a.client_procs,
                     "seconds": a.seconds, "client": "%d python processes x %d threads" % (a.client_procs, a.connections),
                     "ops_per_s": round(sum(o["ops"] for o in outs) / a.seconds, 1), "p50_ms": all_lat[len(all_lat) // 2],
                     "p99_ms": all_lat[int(len(all_lat) * 0.99)], "verify_batches": len(v),
@@ -214,7 +330,9 @@ def server_case(a, pool, lines):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default="profiles/r07_verify_combine.jsonl")
+    ap.add_argument("--out", default=None, help="default: profiles/r07_verify_combine.jsonl, with --rounds profiles/r11_verify_round_sharing.jsonl")
+    ap.add_argument("--rounds", action="store_true", help="round sharing off / on instead of verify mixing off / on")
+    ap.add_argument("--runs", type=int, default=5, help="--rounds: runs per case, arms alternated; median and range over them")
     ap.add_argument("--ms", default="1024,8192")
     ap.add_argument("--dists", default="uniform_1_202,four_values,one_n")
     ap.add_argument("--steps", type=int, default=5)
@@ -233,6 +351,15 @@ def main():
     global bbp
     import torch  # noqa: F401  (torch's HIP runtime first, as bench.py)
     import dusk_blindbidproof_amd as bbp
+    if a.out is None:
+        a.out = "profiles/r11_verify_round_sharing.jsonl" if a.rounds else "profiles/r07_verify_combine.jsonl"
+    if a.rounds:
+        lines = rounds_main(a)
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "a") as f:
+            for line in lines:
+                f.write(json.dumps(line) + "\n")
+        return
     ctx = bbp.Context(0)
     ctx.set_batching(a.window_us, a.max_batch)
     has_switch = hasattr(ctx, "set_verify_mixing")
@@ -273,7 +400,7 @@ def main():
     assert ctx.health() == 0
     ctx.close()
     if a.server:
-        server_case(a, pool, lines)
+        server_case(a, {n: pool[n] for n in (8, 50, 120, 202)}, lines)
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
     with open(a.out, "a") as f:
         for line in lines:
