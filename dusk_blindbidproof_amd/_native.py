@@ -127,6 +127,11 @@ def entropy_size(n):
     return 32 * (4 + n) + 32
 
 
+def prove_row_size(n):
+    """Bytes of one prove_batch input row for list length n: d, k, y, y_inv, q, z_img, seed || pub_list || toggle (u64)."""
+    return 7 * 32 + 32 * n + 8
+
+
 def verify_row_size(n):
     """Bytes of one verify row for list length n: record || score || z_img || seed || pub_list."""
     return record_size(n) + 96 + 32 * n

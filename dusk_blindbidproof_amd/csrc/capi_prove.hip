@@ -74,13 +74,13 @@ __global__ void k_prepare_bids(u32 B, u32 N, const u8* __restrict__ bids, const 
     sc yi = sc_invert(y);
     sc q = sc_mul(d, yi);
     const u64 toggle = toggles[p];
-    const size_t pw = 7 * 8 + (size_t)N * 8 + 2, vw = 3 * 8 + (size_t)N * 8;  // row lengths in words
+    const size_t pw = prove_in_words(N), vw = verify_tail_words(N);  // row lengths in words
     u32* o = prove_in + pw * p;
     const sc seven[7] = {d, k, y, yi, q, z, seed};
     for (int i = 0; i < 7; i++)
         for (int w = 0; w < 8; w++) o[8 * i + w] = seven[i].v[w];
-    o[56 + 8 * N] = (u32)toggle;
-    o[56 + 8 * N + 1] = (u32)(toggle >> 32);
+    o[prove_in_toggle_word(N)] = (u32)toggle;
+    o[prove_in_toggle_word(N) + 1] = (u32)(toggle >> 32);
     u32* v = verify_tail ? verify_tail + vw * p : nullptr;
     if (v)
         for (int w = 0; w < 8; w++) {
@@ -92,8 +92,8 @@ __global__ void k_prepare_bids(u32 B, u32 N, const u8* __restrict__ bids, const 
     for (u32 i = 0; i < N; i++)
         for (int w = 0; w < 8; w++) {
             const u32 word = (u64)i == toggle ? x.v[w] : li[8 * i + w];
-            o[56 + 8 * i + w] = word;
-            if (v) v[24 + 8 * i + w] = word;
+            o[PROVE_IN_LIST_WORD + 8 * i + w] = word;
+            if (v) v[VERIFY_TAIL_LIST_WORD + 8 * i + w] = word;
         }
 }
 
@@ -103,18 +103,17 @@ __global__ void k_prepare_bids(u32 B, u32 N, const u8* __restrict__ bids, const 
 __global__ void k_witness_check(u32 B, u32 N, const u8* __restrict__ in, const sc* __restrict__ mimc, u32* __restrict__ mask) {
     const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= B) return;
-    const size_t in_words = 7 * 8 + (size_t)N * 8 + 2;
-    mask[p] = witness_check_row(N, reinterpret_cast<const u32*>(in) + in_words * p, mimc);
+    mask[p] = witness_check_row(N, reinterpret_cast<const u32*>(in) + prove_in_words(N) * p, mimc);
 }
 
 // Verify-row assembly: record || q || z_img || seed || pub_list (bbp_verify_batch's row) from the output records and the input rows
 // (scalars 4, 5, 6 and the list).  Records are 1121 + 32 m bytes -- odd -- so the copy goes byte by byte, one byte per lane.
 __global__ void k_check_rows(u32 B, u32 N, const u8* __restrict__ in, const u8* __restrict__ recs, u8* __restrict__ rows) {
-    const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (4 + (size_t)N), in_stride = 7 * 32 + 32 * (size_t)N + 8, row = rec + 96 + 32 * (size_t)N;
+    const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (4 + (size_t)N), in_stride = prove_in_bytes(N), row = rec + verify_tail_bytes(N);
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= row * B) return;
     const size_t p = i / row, o = i - p * row;
-    rows[i] = o < rec ? recs[rec * p + o] : in[in_stride * p + 4 * 32 + (o - rec)];  // o - rec < 96: q, z_img, seed; beyond: the list at 7*32
+    rows[i] = o < rec ? recs[rec * p + o] : in[in_stride * p + PROVE_IN_Q + (o - rec)];  // o - rec < 96: q, z_img, seed; beyond: the list, which follows them
 }
 
 // Status merge (caller's stream, after the check has joined): per proof, in the host path's screening order,
@@ -179,6 +178,8 @@ static uint32_t env_chunk(const char* name, uint32_t dflt) {
 }
 static uint32_t host_chunk_prove() { return env_chunk("BBP_HOST_CHUNK_PROVE", 16384); }
 static uint32_t host_chunk_verify() { return env_chunk("BBP_HOST_CHUNK_VERIFY", 32768); }
+
+static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static bool os_random(uint8_t* buf, size_t n) {
     FILE* f = fopen("/dev/urandom", "rb");
@@ -283,7 +284,7 @@ static int32_t no_throw(F&& body, const void* ctx = nullptr) noexcept {
 }  // namespace bbp
 
 extern "C" uint32_t bbp_proof_record_size(uint32_t N) { return (uint32_t)proof_record_bytes(N); }
-extern "C" uint32_t bbp_entropy_size(uint32_t N) { return 32u * (4u + N) + 32u; }
+extern "C" uint32_t bbp_entropy_size(uint32_t N) { return (uint32_t)entropy_row_bytes(N); }
 
 extern "C" int32_t bbp_debug_compile_circuit(uint32_t N, uint32_t* n_mul, uint32_t* n_cons) {
     return no_throw([&]() -> int32_t {
@@ -460,6 +461,11 @@ static int32_t fetch_results(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, size_t bytes) {
 }
 }  // namespace bbp
 
+static int32_t no_os_random(bbp_ctx* ctx) {
+    api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
+    return BBP_ERR_DEVICE;
+}
+
 // key of a host-pointer call that draws on the device: the armed test key (bbp_debug_next_entropy_key), else 32 OS bytes
 static int32_t next_device_key(bbp_ctx* ctx, ChachaKey* key) {
     uint8_t k[32];
@@ -469,10 +475,7 @@ static int32_t next_device_key(bbp_ctx* ctx, ChachaKey* key) {
         ctx->debug_key_armed = false;
         return BBP_OK;
     });
-    if (!armed && !os_random(k, sizeof k)) {
-        api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
-        return BBP_ERR_DEVICE;
-    }
+    if (!armed && !os_random(k, sizeof k)) return no_os_random(ctx);
     *key = chacha_key_from_bytes(k);
     return BBP_OK;
 }
@@ -488,13 +491,9 @@ static int32_t corrupt_hook(bbp_ctx* ctx, u32 first, u32 nb, u32 N, u8* out_dev,
     return BBP_OK;
 }
 
-static size_t align256(size_t n) { return (n + 255) / 256 * 256; }
-// scratch of one checked call of B proofs: verify rows, then verifier statuses
-static size_t check_scratch_bytes(u32 B, u32 N) { return align256(verify_row_bytes(N) * B) + 4 * (size_t)B; }
-
 // One checked prove launch (context lock held): witness check on the opening stream, the prover, the verify rows and the aggregated
 // verifier on a verifier lane's stream -- forked from the records' completion on `s`, joined back before the status merge on `s`.
-// Everything this call writes is complete for work enqueued on `s` afterwards.  `scratch` holds check_scratch_bytes(B, N);
+// Everything this call writes is complete for work enqueued on `s` afterwards.  `scratch` holds CheckRing(B, N).scratch_bytes;
 // `reuse` (optional) is the event after which `scratch` and `mask` may be overwritten; `draw` (optional) writes `ent` on the opening stream.
 static int32_t prove_checked_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* in, const u8* ent, const u8* cent, u8* out, int32_t* status,
                                      u32* mask, u8* scratch, u32* fail_n, u32* fail_idx, u32 idx_base, hipStream_t s, hipEvent_t reuse,
@@ -523,7 +522,7 @@ static int32_t prove_checked_enqueue(bbp_ctx* ctx, u32 B, u32 N, const u8* in, c
     if ((rc = corrupt_hook(ctx, 0, B, N, out, s))) return rc;
     bbp_ctx::VLane& L = ctx->vl[ctx->chk_lane++ % (u32)bbp_ctx::VLANES];
     u8* rows = scratch;
-    int32_t* vstatus = reinterpret_cast<int32_t*>(scratch + align256(verify_row_bytes(N) * B));
+    int32_t* vstatus = reinterpret_cast<int32_t*>(scratch + CheckRing(B, N).vstatus);
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_chk_fork, s));
     BBP_HIP_TRY(ctx, hipStreamWaitEvent(L.stream, ctx->ev_chk_fork, 0));
     if (reuse) BBP_HIP_TRY(ctx, hipStreamWaitEvent(L.stream, reuse, 0));
@@ -567,256 +566,275 @@ static std::string refused_row_text(const bbp_ctx* ctx, const uint8_t* row, uint
     std::vector<sc> mc(BBP_MIMC_ROUNDS);
     if (c->mimc_host.size() < sizeof(sc) * BBP_MIMC_ROUNDS) return "toggle >= N";
     memcpy(mc.data(), c->mimc_host.data(), sizeof(sc) * BBP_MIMC_ROUNDS);
-    std::vector<u32> w(7 * 8 + (size_t)N * 8 + 2);
+    std::vector<u32> w(prove_in_words(N));
     memcpy(w.data(), row, 4 * w.size());
     return witness_check_text(witness_check_row(N, w.data(), mc.data()));
 }
 
 enum CheckMode { CHECK_AUTO, CHECK_OFF, CHECK_REPROVE };  // context's setting / never (bbp_reserve) / checked, no second prove
 
-// The other input stage of prove_batch_host (bbp_prove_round): the round's table and the raw bids in host memory instead of
-// expanded rows.  They are uploaded as they are and the device pass (round_bids.h) writes the prover's rows into the staging slot;
-// its per-bid statuses stand in for the host screening, and `out` receives rows record || score || z_img.
+// The other input of prove_batch_host (bbp_prove_round): the round's table and the raw bids in host memory instead of expanded
+// rows.  They are uploaded as they are and the device pass (round_bids.h) writes the prover's rows into the staging slot; its
+// per-bid statuses stand in for the host screening, and `out` receives rows record || score || z_img.
 struct RoundInput {
     const uint8_t* table;   // seed || pub_list
     const uint8_t* bids;    // B x (d || k)
     uint64_t* toggles_out;  // B entries, or NULL
 };
-// Where a round call keeps what in its staging slot.  in: bids, table, the pass's scratch, the prover's rows.  out: the rows to
-// fetch, the check's results (checked calls), toggles and statuses of the pass -- fetched up to `fetch` -- then the raw records.
-struct RoundLayout {
-    RoundScratch rs;
-    size_t tab_bytes, tab_off, scr_off, rows_off, in_cap;       // staging slot `in`
-    size_t info_off, tog_off, st_off, fetch, recs_off, out_cap;  // staging slot `out`
-    RoundLayout(u32 B, u32 N, bool check) : rs(round_scratch(B, N)) {
-        const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, rec = bbp_proof_record_size(N);
-        tab_bytes = 32 * (1 + (size_t)N);
-        tab_off = align256(BBP_ROUND_BID_BYTES * (size_t)B);
-        scr_off = align256(tab_off + tab_bytes);
-        rows_off = scr_off + rs.end;
-        in_cap = rows_off + in_stride * B;
-        info_off = align256((rec + 64) * B);
-        tog_off = align256(info_off + (check ? 4 * (3 * (size_t)B + 1) : 0));
-        st_off = tog_off + 8 * (size_t)B;
-        fetch = st_off + 4 * (size_t)B;
-        recs_off = align256(fetch);
-        out_cap = recs_off + rec * B;
-    }
+
+// One host-pointer prove call on its way through the steps below: the arguments, where things lie in its staging slot
+// (prove_io.h), the entropy decision, and what came back.
+struct ProveCall {
+    bbp_ctx* ctx;
+    uint32_t B, N;
+    const uint8_t* in;  // NULL for a round call
+    const uint8_t* entropy;
+    uint8_t* out;
+    int32_t* status;
+    CheckMode mode;
+    const RoundInput* round;
+    ProveStaging L;
+    // screening: what is uploaded into the slot's `in` -- the rows (with stand-ins for refused ones), or bids and table
+    std::vector<uint8_t> fixed;
+    const uint8_t *src = nullptr, *src2 = nullptr;
+    // entropy: the prover's rows in host memory (NULL: drawn on the device under `key`) and the one span that is uploaded
+    ChachaKey key{};
+    std::vector<uint8_t> ent_host, ent_all;
+    const uint8_t* up_ent = nullptr;
+    // the check's verdicts as read back
+    std::vector<int32_t> dstatus;
+    std::vector<u32> dmask, fail_rows;
+    double t_lock = 0, t_h2d = 0;  // BBP_TRACE
 };
 
-// body of bbp_prove_batch and, with `round`, of bbp_prove_round (in == NULL then).  Takes the context lock itself, for the enqueue
-// phase only.
-static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out,
-                                int32_t* status, CheckMode mode = CHECK_AUTO, const RoundInput* round = nullptr) {
-    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
-    if (rc) return rc;
-    if (B == 0) return BBP_OK;
-    fault_injected("prove_batch");
-    const bool check = mode == CHECK_REPROVE || (mode == CHECK_AUTO && ctx->prove_check.load());
-    const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, ent_stride = bbp_entropy_size(N), out_stride = bbp_proof_record_size(N);
-    const size_t res_stride = round ? out_stride + 64 : out_stride;  // what `out` holds per row
-    // host-side argument screening (the reference's typed API cannot express these states: SURVEY.md 8b); a round call's rows are
-    // screened by the device pass
-    std::vector<uint8_t> fixed;
-    for (uint32_t i = 0; i < B; i++) {
-        status[i] = BBP_OK;
-        if (round) continue;
-        const uint8_t* r = in + in_stride * i;
+// Step 1: host-side argument screening (the reference's typed API cannot express these states: SURVEY.md 8b).  A refused row is
+// replaced by a neutral stand-in so the batch geometry is unchanged.  A round call's rows are screened by the device pass.
+static void prove_screen(ProveCall& c) {
+    const size_t in_stride = c.L.in_stride;
+    for (uint32_t i = 0; i < c.B; i++) c.status[i] = BBP_OK;
+    if (c.round) {
+        c.src = c.round->bids, c.src2 = c.round->table;
+        return;
+    }
+    for (uint32_t i = 0; i < c.B; i++) {
+        const uint8_t* r = c.in + in_stride * i;
         uint64_t toggle;
-        memcpy(&toggle, r + 7 * 32 + (size_t)N * 32, 8);
-        if (toggle >= N) status[i] = BBP_ERR_BAD_ARG;
-        for (int k = 0; k < 7 && status[i] == BBP_OK; k++) {
+        memcpy(&toggle, r + prove_in_toggle(c.N), 8);
+        if (toggle >= c.N) c.status[i] = BBP_ERR_BAD_ARG;
+        for (int k = 0; k < 7 && c.status[i] == BBP_OK; k++) {
             u32 w[8];
             memcpy(w, r + 32 * k, 32);
-            if (!sc_is_canonical(w)) status[i] = BBP_ERR_FORMAT;  // serde Scalar deserialisation is canonical-only
+            if (!sc_is_canonical(w)) c.status[i] = BBP_ERR_FORMAT;  // serde Scalar deserialisation is canonical-only
         }
-        if (status[i] != BBP_OK) {
-            if (fixed.empty()) fixed.assign(in, in + in_stride * B);
-            memset(&fixed[in_stride * i], 0, in_stride);  // neutral stand-in so the batch geometry is unchanged
+        if (c.status[i] != BBP_OK) {
+            if (c.fixed.empty()) c.fixed.assign(c.in, c.in + in_stride * c.B);
+            memset(&c.fixed[in_stride * i], 0, in_stride);
         }
     }
-    const uint8_t* src = fixed.empty() ? in : fixed.data();
-    // source DEVICE: one key for the call, each chunk's rows drawn on its opening stream (k_draw_entropy); only the key leaves the OS
-    const bool dev_draw = !entropy && ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
-    ChachaKey key{};
-    if (dev_draw && (rc = next_device_key(ctx, &key))) return rc;
-    std::vector<uint8_t> ent_host;
-    if (!entropy && !dev_draw) {
+    c.src = c.fixed.empty() ? c.in : c.fixed.data();
+}
+
+// Step 2: the call's entropy -- the caller's, the OS's, or (source DEVICE) one key for the call, each chunk's rows drawn on its
+// opening stream (k_draw_entropy): only the key leaves the OS.  Checked: the verifier's weights come from the OS like
+// bbp_verify_batch's; they travel behind the prover's entropy.  The result is the one span up_ent that is uploaded.
+static int32_t prove_entropy(ProveCall& c) {
+    const uint32_t B = c.B, m = 4 + c.N;
+    const size_t ent_stride = c.L.ent_stride;
+    if (c.L.dev_draw) {
+        if (int32_t rc = next_device_key(c.ctx, &c.key)) return rc;
+    } else if (!c.entropy) {
         // thread_rng replacement: 64 OS bytes per blinding, wide-reduced like Scalar::random; 32 OS bytes for the rng seed
-        const uint32_t m = 4 + N;
         std::vector<uint8_t> raw((size_t)B * (64 * m + 32));
-        if (!os_random(raw.data(), raw.size())) {
-            api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
-            return BBP_ERR_DEVICE;
-        }
-        ent_host.resize(ent_stride * B);
+        if (!os_random(raw.data(), raw.size())) return no_os_random(c.ctx);
+        c.ent_host.resize(ent_stride * B);
         for (uint32_t i = 0; i < B; i++) {
             const uint8_t* rp = &raw[(size_t)i * (64 * m + 32)];
             for (uint32_t k = 0; k < m; k++) {
                 u32 w[16];
                 memcpy(w, rp + 64 * k, 64);
                 sc s = sc_from_wide(w);
-                sc_tobytes(&ent_host[ent_stride * i + 32 * k], s);
+                sc_tobytes(&c.ent_host[ent_stride * i + 32 * k], s);
             }
-            memcpy(&ent_host[ent_stride * i + 32 * m], rp + 64 * m, 32);
+            memcpy(&c.ent_host[ent_stride * i + 32 * m], rp + 64 * m, 32);
         }
-        entropy = ent_host.data();
+        c.entropy = c.ent_host.data();
     }
-    // checked: the verifier's weights come from the OS like bbp_verify_batch's; they travel behind the prover's entropy.  The results
-    // come back behind the records: statuses, witness masks, the count and the rows of rejected records (k_check_merge)
-    std::vector<uint8_t> ent_all;
-    const uint8_t* up_ent = entropy;
-    size_t up_ent_bytes = dev_draw ? 0 : ent_stride * B;
-    const size_t up_ent_off = dev_draw ? ent_stride * B : 0;  // (drawn rows below it)
-    if (check) {
-        const size_t own = dev_draw ? 0 : ent_stride * B;
-        ent_all.resize(own + 32 * (size_t)B);
-        if (own) memcpy(ent_all.data(), entropy, own);
-        if (!os_random(ent_all.data() + own, 32 * (size_t)B)) {
-            api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
-            return BBP_ERR_DEVICE;
-        }
-        up_ent = ent_all.data();
-        up_ent_bytes = ent_all.size();
-    }
-    const RoundLayout rl(B, N, check);  // (a round call's)
-    const size_t info_off = round ? rl.info_off : check ? align256(out_stride * B) : out_stride * B;
-    const size_t out_bytes = round ? rl.fetch : info_off + (check ? 4 * (3 * (size_t)B + 1) : 0);  // what comes back
-    const size_t out_cap = round ? rl.out_cap : out_bytes, rows_off = round ? rl.rows_off : 0, recs_off = round ? rl.recs_off : 0;
-    std::vector<int32_t> dstatus;
-    std::vector<u32> dmask, fail_rows;
-    static const bool trace = getenv("BBP_TRACE") != nullptr;
-    auto now_ms = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_enter = now_ms();
-  {  // the staging slot is held for this block only: a second prove of rejected rows below takes a slot of its own
-    SlotLease lease(ctx);  // may wait for the call two back to collect its results; the context lock is NOT held here
-    bbp_ctx::IoSlot& sl = *lease.sl;
-    const double t_slot = now_ms();
-    double t_lock = 0, t_h2d = 0;
-    rc = api_guard(ctx, [&]() -> int32_t {
-        int32_t rc;
-        t_lock = now_ms();
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = dev_reserve(ctx, sl.out, out_cap)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, out_bytes)) ||
-            (check && (rc = dev_reserve(ctx, sl.chk, check_scratch_bytes(B, N)))))
-            return rc;
-        if (round) {  // bids and table travel as they are; the slot's input buffer also holds the pass's scratch and the rows it writes
-            if ((rc = dev_reserve(ctx, sl.in, rl.in_cap)) ||
-                (rc = upload_inputs(ctx, sl, round->bids, BBP_ROUND_BID_BYTES * (size_t)B, up_ent, up_ent_bytes, up_ent_off, round->table, rl.tab_bytes,
-                                    rl.tab_off)))
-                return rc;
-            if (!ctx->ev_round) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_round, hipEventDisableTiming));
-        } else if ((rc = upload_inputs(ctx, sl, src, in_stride * B, up_ent, up_ent_bytes, up_ent_off)))
-            return rc;
-        t_h2d = now_ms();
-        u8* info = (u8*)sl.out.p + info_off;
-        int32_t* st_dev = (int32_t*)info;
-        u32 *mask_dev = (u32*)(info + 4 * (size_t)B), *fail_n = mask_dev + B, *fail_idx = fail_n + 1;
-        if (check) BBP_HIP_TRY(ctx, hipMemsetAsync(fail_n, 0, sizeof(u32), ctx->stream));
-        // Very large host batches go through the engine in equal chunks of at most host_chunk_prove proofs so that scratch stays
-        // bounded (~1.3 MB per proof of the largest call, three buffers); consecutive calls pipeline -- chunk k+1's opening stage
-        // under chunk k's MSMs.  One 16384-proof call was measured 5 % faster than four of 4096, hence the large default.
-        const uint32_t n_chunks = (B + host_chunk_prove() - 1) / host_chunk_prove(), chunk = (B + n_chunks - 1) / n_chunks;
-        for (uint32_t first = 0; first < B; first += chunk) {
-            const uint32_t nb = B - first < chunk ? B - first : chunk;
-            const u8 *cin = (const u8*)sl.in.p + rows_off + in_stride * first, *cent = (const u8*)sl.ent.p + ent_stride * first;
-            u8* cout = (u8*)sl.out.p + recs_off + out_stride * first;
-            // what runs on the chunk's opening stream ahead of the opening stage.  A round call: the device pass writes this chunk's
-            // rows (the table is reduced by the first chunk; a later chunk may open on the other stream and waits for that).
-            // (source DEVICE) this chunk's own rows of the call's key: no two chunks draw equal rows
-            const std::function<int32_t(hipStream_t)> draw = [&](hipStream_t os) -> int32_t {
-                if (round) {
-                    int32_t rc;
-                    u8* base = (u8*)sl.in.p;
-                    if (first) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_round, 0));
-                    if ((rc = round_prepare_enqueue(ctx, N, base + rl.tab_off, base + rl.scr_off, rl.rs, first == 0, first, nb,
-                                                    base + BBP_ROUND_BID_BYTES * (size_t)first, (u32*)cin, nullptr,
-                                                    (u32*)((u8*)sl.out.p + rl.tog_off) + 2 * (size_t)first, (int32_t*)((u8*)sl.out.p + rl.st_off) + first, os)))
-                        return rc;
-                    if (!first && n_chunks > 1) BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_round, os));
-                }
-                return dev_draw ? draw_enqueue(ctx, nb, N, BBP_ENTROPY_PROVE, key, first, (void*)cent, os) : (int32_t)BBP_OK;
-            };
-            const std::function<int32_t(hipStream_t)>* open = dev_draw || round ? &draw : nullptr;
-            if (check) {
-                u8* scratch = (u8*)sl.chk.p;  // chunks are stream-ordered on ctx->stream; each chunk's check joins back before the next starts
-                if ((rc = prove_checked_enqueue(ctx, nb, N, cin, cent, (const u8*)sl.ent.p + ent_stride * B + 32 * (size_t)first, cout,
-                                                st_dev + first, mask_dev + first, scratch, fail_n, fail_idx, first, ctx->stream, nullptr, open)))
-                    return rc;
-            } else {
-                if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream, open))) return rc;
-                if ((rc = corrupt_hook(ctx, first, nb, N, cout, ctx->stream))) return rc;
-            }
-        }
-        if (round && (rc = round_rows_enqueue(ctx, B, N, (const u8*)sl.out.p + recs_off, (const u32*)((u8*)sl.in.p + rl.scr_off + rl.rs.rb), (u8*)sl.out.p,
-                                              ctx->stream)))
-            return rc;
-        ctx->debug_corrupt_proof = -1;  // armed for an index beyond this call: consumed all the same
-        BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, ctx->stream));
-        return BBP_OK;
-    });
-    if (rc) return rc;
-    const double t_enq = now_ms();
-    if ((rc = fetch_results(ctx, sl, out_bytes))) return rc;  // lock released: another thread may be enqueueing the next batch now
-    memcpy(out, sl.h_out, res_stride * B);
-    if (round) {  // the device pass's verdicts stand where the host screening's would
-        memcpy(status, (const u8*)sl.h_out + rl.st_off, 4 * (size_t)B);
-        if (round->toggles_out) memcpy(round->toggles_out, (const u8*)sl.h_out + rl.tog_off, 8 * (size_t)B);
-    }
-    if (check) {
-        const u8* info = (const u8*)sl.h_out + info_off;
-        dstatus.resize(B);
-        dmask.resize(B);
-        memcpy(dstatus.data(), info, 4 * (size_t)B);
-        memcpy(dmask.data(), info + 4 * (size_t)B, 4 * (size_t)B);
-        u32 n_fail = 0;
-        memcpy(&n_fail, info + 8 * (size_t)B, 4);
-        fail_rows.resize(std::min<u32>(n_fail, B));
-        memcpy(fail_rows.data(), info + 8 * (size_t)B + 4, 4 * fail_rows.size());
-    }
-    if (trace)
-        fprintf(stderr, "[bbp trace] prove_batch B=%u slot=%d: enter %.1f, slot +%.1f, lock +%.1f, h2d +%.1f, enqueued +%.1f, done +%.1f\n", B,
-                (int)(&sl - ctx->io), t_enter, t_slot - t_enter, t_lock - t_enter, t_h2d - t_enter, t_enq - t_enter, now_ms() - t_enter);
-  }
-    for (uint32_t i = 0; i < B; i++)
-        if (status[i] != BBP_OK) memset(out + res_stride * i, 0, res_stride);
-    if (!check) return BBP_OK;
-    if (mode == CHECK_AUTO) ctx->chk_checked += B;
-    // rows the host screening let through take the device's verdict (their records are already zeroed unless OK)
-    int64_t first_refused = -1;
-    for (uint32_t i = 0; i < B; i++) {
-        if (status[i] != BBP_OK) continue;
-        status[i] = dstatus[i];
-        if (dstatus[i] != BBP_OK && dstatus[i] != BBP_ERR_VERIFY && first_refused < 0) first_refused = i;
-    }
-    if (first_refused >= 0) set_tls_error(ctx, std::string("row ") + std::to_string(first_refused) + ": " + witness_check_text(dmask[first_refused]));
-    if (mode == CHECK_REPROVE || fail_rows.empty()) return BBP_OK;
-    // a record that failed its check is proved once more with the same inputs and the same entropy (the drawn entropy when the
-    // caller gave none; source DEVICE: the row re-derived from the call's key), and checked again; a second failure is a device
-    // fault: the whole call fails and health bit 1 is raised
-    std::sort(fail_rows.begin(), fail_rows.end());
-    const uint32_t nr = (uint32_t)fail_rows.size();
-    const size_t rin_stride = round ? (size_t)BBP_ROUND_BID_BYTES : in_stride;  // a round call proves the failed bids again, as a round
-    const uint8_t* rsrc = round ? round->bids : src;
-    std::vector<uint8_t> rin(rin_stride * nr), rent(ent_stride * nr), rout(res_stride * nr);
-    std::vector<int32_t> rst(nr);
-    for (uint32_t j = 0; j < nr; j++) {
-        memcpy(&rin[rin_stride * j], rsrc + rin_stride * fail_rows[j], rin_stride);
-        if (dev_draw)
-            entropy_prove_row_bytes(key, N, fail_rows[j], &rent[ent_stride * j]);
-        else
-            memcpy(&rent[ent_stride * j], entropy + ent_stride * fail_rows[j], ent_stride);
-    }
-    ctx->chk_reproved += nr;
-    const RoundInput again{round ? round->table : nullptr, rin.data(), nullptr};
-    if ((rc = prove_batch_host(ctx, nr, N, round ? nullptr : rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE, round ? &again : nullptr)))
-        return rc;
-    for (uint32_t j = 0; j < nr; j++) {
-        if (rst[j] != BBP_OK) return raise_check_failure(ctx, fail_rows[j]);
-        memcpy(out + res_stride * fail_rows[j], &rout[res_stride * j], res_stride);
-        status[fail_rows[j]] = BBP_OK;
+    c.up_ent = c.entropy;
+    if (c.L.check) {
+        const size_t own = c.L.ent_up_bytes - 32 * (size_t)B;  // the prover's rows, unless they are drawn
+        c.ent_all.resize(c.L.ent_up_bytes);
+        if (own) memcpy(c.ent_all.data(), c.entropy, own);
+        if (!os_random(c.ent_all.data() + own, 32 * (size_t)B)) return no_os_random(c.ctx);
+        c.up_ent = c.ent_all.data();
     }
     return BBP_OK;
+}
+
+// every buffer of a staging slot at what the layout says (the enqueue step; bbp_reserve, ahead of time)
+static int32_t staging_reserve(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, const ProveStaging& L) {
+    int32_t rc;
+    if ((rc = dev_reserve(ctx, sl.out, L.out_cap)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, L.h_out_bytes)) ||
+        (L.check && (rc = dev_reserve(ctx, sl.chk, L.chk_bytes))) || (rc = dev_reserve(ctx, sl.in, L.in_cap)) ||
+        (rc = dev_reserve(ctx, sl.ent, L.ent_cap)))
+        return rc;
+    return pinned_reserve(ctx, sl.h_in, sl.h_in_cap, L.h_in_bytes);
+}
+
+// Step 3, under the context lock: reserve, upload, the chunk loop, a round call's output rows, the slot's event.
+static int32_t prove_enqueue(ProveCall& c, bbp_ctx::IoSlot& sl) {
+    bbp_ctx* const ctx = c.ctx;
+    const ProveStaging& L = c.L;
+    const uint32_t B = c.B, N = c.N;
+    int32_t rc;
+    BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // a round call's bids and table travel as they are; the slot's input buffer also holds the pass's scratch and the rows it writes
+    if ((rc = staging_reserve(ctx, sl, L)) ||
+        (rc = upload_inputs(ctx, sl, c.src, L.in_first_bytes, c.up_ent, L.ent_up_bytes, L.ent_up_off, c.src2, L.in_tab_bytes, L.in_tab)))
+        return rc;
+    if (L.round && !ctx->ev_round) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_round, hipEventDisableTiming));
+    c.t_h2d = now_ms();
+    u8 *const d_in = (u8*)sl.in.p, *const d_ent = (u8*)sl.ent.p, *const d_out = (u8*)sl.out.p;
+    int32_t* st_dev = (int32_t*)(d_out + L.out_status);
+    u32 *mask_dev = (u32*)(d_out + L.out_mask), *fail_n = (u32*)(d_out + L.out_fail_n), *fail_idx = (u32*)(d_out + L.out_fail_idx);
+    if (L.check) BBP_HIP_TRY(ctx, hipMemsetAsync(fail_n, 0, sizeof(u32), ctx->stream));
+    // Very large host batches go through the engine in equal chunks of at most host_chunk_prove proofs so that scratch stays
+    // bounded (~1.3 MB per proof of the largest call, three buffers); consecutive calls pipeline -- chunk k+1's opening stage
+    // under chunk k's MSMs.  One 16384-proof call was measured 5 % faster than four of 4096, hence the large default.
+    const uint32_t n_chunks = (B + host_chunk_prove() - 1) / host_chunk_prove(), chunk = (B + n_chunks - 1) / n_chunks;
+    for (uint32_t first = 0; first < B; first += chunk) {
+        const uint32_t nb = B - first < chunk ? B - first : chunk;
+        const u8 *cin = d_in + L.in_rows + L.in_stride * first, *cent = d_ent + L.ent_stride * first;
+        u8* cout = d_out + L.out_recs + L.rec * first;
+        // what runs on the chunk's opening stream ahead of the opening stage.  A round call: the device pass writes this chunk's
+        // rows (the table is reduced by the first chunk; a later chunk may open on the other stream and waits for that).
+        // (source DEVICE) this chunk's own rows of the call's key: no two chunks draw equal rows
+        const std::function<int32_t(hipStream_t)> draw = [&](hipStream_t os) -> int32_t {
+            if (L.round) {
+                int32_t rc;
+                if (first) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_round, 0));
+                if ((rc = round_prepare_enqueue(ctx, N, d_in + L.in_tab, d_in + L.in_scratch, L.rs, first == 0, first, nb,
+                                                d_in + ROUND_BID_BYTES * first, (u32*)cin, nullptr, (u32*)(d_out + L.out_tog) + 2 * (size_t)first,
+                                                (int32_t*)(d_out + L.out_pass_st) + first, os)))
+                    return rc;
+                if (!first && n_chunks > 1) BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_round, os));
+            }
+            return L.dev_draw ? draw_enqueue(ctx, nb, N, BBP_ENTROPY_PROVE, c.key, first, (void*)cent, os) : (int32_t)BBP_OK;
+        };
+        const std::function<int32_t(hipStream_t)>* open = L.dev_draw || L.round ? &draw : nullptr;
+        if (L.check) {
+            u8* scratch = (u8*)sl.chk.p;  // chunks are stream-ordered on ctx->stream; each chunk's check joins back before the next starts
+            if ((rc = prove_checked_enqueue(ctx, nb, N, cin, cent, d_ent + L.ent_check(first), cout, st_dev + first, mask_dev + first, scratch,
+                                            fail_n, fail_idx, first, ctx->stream, nullptr, open)))
+                return rc;
+        } else {
+            if ((rc = prove_batch_dev(ctx, nb, N, cin, cent, cout, ctx->stream, open))) return rc;
+            if ((rc = corrupt_hook(ctx, first, nb, N, cout, ctx->stream))) return rc;
+        }
+    }
+    if (L.round && (rc = round_rows_enqueue(ctx, B, N, d_out + L.out_recs, (const u32*)(d_in + L.in_scratch + L.rs.rb), d_out, ctx->stream))) return rc;
+    ctx->debug_corrupt_proof = -1;  // armed for an index beyond this call: consumed all the same
+    BBP_HIP_TRY(ctx, hipEventRecord(sl.ev, ctx->stream));
+    return BBP_OK;
+}
+
+// Step 4, lock released (another thread may be enqueueing the next batch now): the results out of the slot's pinned mirror.  A
+// round call: the device pass's verdicts stand where the host screening's would.  Checked: the info block behind the records --
+// statuses, witness masks, the count and the rows of rejected records (k_check_merge).
+static int32_t prove_collect(ProveCall& c, bbp_ctx::IoSlot& sl) {
+    const ProveStaging& L = c.L;
+    const size_t b = c.B;
+    if (int32_t rc = fetch_results(c.ctx, sl, L.out_fetch)) return rc;
+    const u8* h = (const u8*)sl.h_out;
+    memcpy(c.out, h, L.res_stride * b);
+    if (L.round) {
+        memcpy(c.status, h + L.out_pass_st, 4 * b);
+        if (c.round->toggles_out) memcpy(c.round->toggles_out, h + L.out_tog, 8 * b);
+    }
+    if (L.check) {
+        c.dstatus.resize(b);
+        c.dmask.resize(b);
+        memcpy(c.dstatus.data(), h + L.out_status, 4 * b);
+        memcpy(c.dmask.data(), h + L.out_mask, 4 * b);
+        u32 n_fail = 0;
+        memcpy(&n_fail, h + L.out_fail_n, 4);
+        c.fail_rows.resize(std::min<u32>(n_fail, c.B));
+        memcpy(c.fail_rows.data(), h + L.out_fail_idx, 4 * c.fail_rows.size());
+    }
+    return BBP_OK;
+}
+
+static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out,
+                                int32_t* status, CheckMode mode = CHECK_AUTO, const RoundInput* round = nullptr);
+
+// Step 5 (checked calls): rows the screening let through take the device's verdict (their records are already zeroed unless OK),
+// and a record that failed its check is proved once more with the same inputs and the same entropy (the drawn entropy when the
+// caller gave none; source DEVICE: the row re-derived from the call's key), and checked again; a second failure is a device
+// fault: the whole call fails and health bit 1 is raised.  Runs without a staging slot: the second prove takes one of its own.
+static int32_t prove_merge(ProveCall& c) {
+    bbp_ctx* const ctx = c.ctx;
+    const ProveStaging& L = c.L;
+    if (c.mode == CHECK_AUTO) ctx->chk_checked += c.B;
+    int64_t first_refused = -1;
+    for (uint32_t i = 0; i < c.B; i++) {
+        if (c.status[i] != BBP_OK) continue;
+        c.status[i] = c.dstatus[i];
+        if (c.dstatus[i] != BBP_OK && c.dstatus[i] != BBP_ERR_VERIFY && first_refused < 0) first_refused = i;
+    }
+    if (first_refused >= 0) set_tls_error(ctx, std::string("row ") + std::to_string(first_refused) + ": " + witness_check_text(c.dmask[first_refused]));
+    if (c.mode == CHECK_REPROVE || c.fail_rows.empty()) return BBP_OK;
+    std::sort(c.fail_rows.begin(), c.fail_rows.end());
+    const uint32_t nr = (uint32_t)c.fail_rows.size();
+    const size_t rin_stride = L.in_first_stride;  // a round call proves the failed bids again, as a round
+    std::vector<uint8_t> rin(rin_stride * nr), rent(L.ent_stride * nr), rout(L.res_stride * nr);
+    std::vector<int32_t> rst(nr);
+    for (uint32_t j = 0; j < nr; j++) {
+        memcpy(&rin[rin_stride * j], c.src + rin_stride * c.fail_rows[j], rin_stride);
+        if (L.dev_draw)
+            entropy_prove_row_bytes(c.key, c.N, c.fail_rows[j], &rent[L.ent_stride * j]);
+        else
+            memcpy(&rent[L.ent_stride * j], c.entropy + L.ent_stride * c.fail_rows[j], L.ent_stride);
+    }
+    ctx->chk_reproved += nr;
+    const RoundInput again{c.src2, rin.data(), nullptr};
+    if (int32_t rc = prove_batch_host(ctx, nr, c.N, L.round ? nullptr : rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE, L.round ? &again : nullptr))
+        return rc;
+    for (uint32_t j = 0; j < nr; j++) {
+        if (rst[j] != BBP_OK) return raise_check_failure(ctx, c.fail_rows[j]);
+        memcpy(c.out + L.res_stride * c.fail_rows[j], &rout[L.res_stride * j], L.res_stride);
+        c.status[c.fail_rows[j]] = BBP_OK;
+    }
+    return BBP_OK;
+}
+
+// body of bbp_prove_batch and, with `round`, of bbp_prove_round (in == NULL then); the combiner's runner and bbp_reserve's warm-up
+// call it too.  Takes the context lock itself, for the enqueue step only.
+static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status,
+                                CheckMode mode, const RoundInput* round) {
+    int32_t rc = api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
+    if (rc) return rc;
+    if (B == 0) return BBP_OK;
+    fault_injected("prove_batch");
+    const bool check = mode == CHECK_REPROVE || (mode == CHECK_AUTO && ctx->prove_check.load());
+    const bool dev_draw = !entropy && ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
+    ProveCall c{ctx, B, N, in, entropy, out, status, mode, round, ProveStaging(B, N, round != nullptr, check, dev_draw)};
+    prove_screen(c);
+    if ((rc = prove_entropy(c))) return rc;
+    static const bool trace = getenv("BBP_TRACE") != nullptr;
+    const double t_enter = now_ms();
+    {  // the staging slot is held for this block only: a second prove of rejected rows (prove_merge) takes a slot of its own
+        SlotLease lease(ctx);  // may wait for the call two back to collect its results; the context lock is NOT held here
+        bbp_ctx::IoSlot& sl = *lease.sl;
+        const double t_slot = now_ms();
+        if ((rc = api_guard(ctx, [&]() -> int32_t { return c.t_lock = now_ms(), prove_enqueue(c, sl); }))) return rc;
+        const double t_enq = now_ms();
+        if ((rc = prove_collect(c, sl))) return rc;
+        if (trace)
+            fprintf(stderr, "[bbp trace] prove_batch B=%u slot=%d: enter %.1f, slot +%.1f, lock +%.1f, h2d +%.1f, enqueued +%.1f, done +%.1f\n", B,
+                    (int)(&sl - ctx->io), t_enter, t_slot - t_enter, c.t_lock - t_enter, c.t_h2d - t_enter, t_enq - t_enter, now_ms() - t_enter);
+    }
+    for (uint32_t i = 0; i < B; i++)
+        if (status[i] != BBP_OK) memset(out + c.L.res_stride * i, 0, c.L.res_stride);
+    return check ? prove_merge(c) : (int32_t)BBP_OK;
 }
 
 template <class F>
@@ -878,12 +896,12 @@ extern "C" int32_t bbp_prove_batch_checked_dev(bbp_ctx* ctx, uint32_t B, uint32_
         // scratch in rotation: verify rows + verifier statuses, then the witness masks; a ring entry waits for the status kernel of
         // the call that used it last (several calls in flight, no host synchronisation)
         bbp_ctx::CheckBuf& cb = ctx->chk[ctx->chk_next++ % (u32)bbp_ctx::CHECK_RING];
-        const size_t mask_off = align256(check_scratch_bytes(B, N));
-        if ((rc = dev_reserve(ctx, cb.buf, mask_off + 4 * (size_t)B))) return rc;
+        const CheckRing ring(B, N);
+        if ((rc = dev_reserve(ctx, cb.buf, ring.bytes))) return rc;
         if (!cb.ev) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&cb.ev, hipEventDisableTiming));
         u8* base = (u8*)cb.buf.p;
         rc = prove_checked_enqueue(ctx, B, N, (const u8*)in_dev, (const u8*)entropy_dev, (const u8*)check_entropy_dev, (u8*)out_dev,
-                                   (int32_t*)status_dev, (u32*)(base + mask_off), base, nullptr, nullptr, 0, s, cb.ev_valid ? cb.ev : nullptr);
+                                   (int32_t*)status_dev, (u32*)(base + ring.mask), base, nullptr, nullptr, 0, s, cb.ev_valid ? cb.ev : nullptr);
         ctx->debug_corrupt_proof = -1;
         if (rc) return rc;
         BBP_HIP_TRY(ctx, hipEventRecord(cb.ev, s));
@@ -906,25 +924,21 @@ extern "C" int32_t bbp_prove_round(bbp_ctx* ctx, uint32_t N, const uint8_t* roun
     return no_throw_ctx(ctx, [&]() -> int32_t { return prove_batch_host(ctx, B, N, nullptr, entropy, rows_out, status, CHECK_AUTO, &r); });
 }
 
-// bytes of a ring entry (context.h rnd): the pass's scratch; a prove call: its prove-input rows and its records behind it
-static size_t round_dev_bytes(u32 B, u32 N, bool prove) {
-    return round_scratch(B, N).end + (prove ? align256((7 * 32 + (size_t)N * 32 + 8) * B) + (size_t)bbp_proof_record_size(N) * B : 0);
-}
-
 // Both _dev forms (context lock held).  entropy_dev == NULL: the pass alone, rows into prove_in.  Else the pass into the ring entry,
 // the prover, and the output rows into rows_out, all ordered on s; the prover's opening stage waits for the pass through ev_prep.
 static int32_t round_dev_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u32 B, const u8* bids, u32* prove_in, u32* tails, u32* toggles,
                                  int32_t* status, const u8* entropy_dev, u8* rows_out, hipStream_t s) {
     int32_t rc;
     const bool prove = entropy_dev != nullptr;
-    const RoundScratch rs = round_scratch(B, N);
+    const RoundRing ring(B, N, prove);
+    const RoundScratch& rs = ring.rs;
     // scratch in rotation: an entry waits for the last kernel of the call that used it last (several calls in flight, no host synchronisation)
     bbp_ctx::CheckBuf& cb = ctx->rnd[ctx->rnd_next++ % (u32)bbp_ctx::CHECK_RING];
-    if ((rc = dev_reserve(ctx, cb.buf, round_dev_bytes(B, N, prove)))) return rc;
+    if ((rc = dev_reserve(ctx, cb.buf, ring.bytes))) return rc;
     if (!cb.ev) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&cb.ev, hipEventDisableTiming));
     if (cb.ev_valid) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, cb.ev, 0));
     u8* base = (u8*)cb.buf.p;
-    u8 *in_rows = base + rs.end, *recs = in_rows + align256((7 * 32 + (size_t)N * 32 + 8) * B);
+    u8 *in_rows = base + ring.rows, *recs = base + ring.recs;
     if (prove) prove_in = (u32*)in_rows;
     if ((rc = round_prepare_enqueue(ctx, N, table, base, rs, true, 0, B, bids, prove_in, tails, toggles, status, s))) return rc;
     // the prover's opening stage does not wait for the caller's stream (bbp.h); it does wait for this event
@@ -1076,10 +1090,10 @@ static void async_done(Request* r) {
 }
 
 static void fill_prove_input(std::vector<uint8_t>& in, const uint8_t scalars7[7 * 32], const uint8_t* pub_list, uint32_t N, uint64_t toggle) {
-    in.resize(7 * 32 + (size_t)N * 32 + 8);
-    memcpy(&in[0], scalars7, 7 * 32);
-    memcpy(&in[7 * 32], pub_list, (size_t)N * 32);
-    memcpy(&in[7 * 32 + (size_t)N * 32], &toggle, 8);
+    in.resize(prove_in_bytes(N));
+    memcpy(&in[0], scalars7, PROVE_IN_LIST);
+    memcpy(&in[PROVE_IN_LIST], pub_list, (size_t)N * 32);
+    memcpy(&in[prove_in_toggle(N)], &toggle, 8);
 }
 
 extern "C" int32_t bbp_prove(bbp_ctx* ctx, const uint8_t scalars7[7 * 32], const uint8_t* pub_list, uint32_t N, uint64_t toggle,
@@ -1156,8 +1170,7 @@ static int32_t verify_batch_host(bbp_ctx* ctx, const VerifyRows& rows, const uin
     if (dev_draw) {
         if (int32_t rc = next_device_key(ctx, &key)) return rc;
     } else if (!os_random(ent.data(), ent.size())) {
-        api_guard(ctx, [&]() -> int32_t { return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE; });
-        return BBP_ERR_DEVICE;
+        return no_os_random(ctx);
     }
     SlotLease lease(ctx, true);
     bbp_ctx::IoSlot& sl = *lease.sl;
@@ -1486,9 +1499,8 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
     }
     return no_throw_ctx(ctx, [&]() -> int32_t {
         const uint32_t B = max_batch;
-        const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, rec = bbp_proof_record_size(N);
         const VerifyRows vrows = VerifyRows::uniform(B, N);
-        std::vector<uint8_t> in(in_stride * B, 0), ent((size_t)bbp_entropy_size(N) * B, 0), out(rec * B), vin(vrows.row_bytes(0) * B, 0);
+        std::vector<uint8_t> in(prove_in_bytes(N) * B, 0), ent(entropy_row_bytes(N) * B, 0), out(proof_record_bytes(N) * B), vin(vrows.row_bytes(0) * B, 0);
         std::vector<int32_t> st(B);
         int32_t rc = BBP_OK;
         // batches below 1024 proofs rotate three buffers and two opening streams, larger ones two buffers: both shapes, every slot
@@ -1505,40 +1517,22 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
             for (int k = 0; k < bbp_ctx::PROVE_BUFS && rc == BBP_OK; k++) rc = prove_batch_host(ctx, B, N, in.data(), ent.data(), out.data(), st.data(), CHECK_OFF);
         }
         for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++) rc = verify_batch_host(ctx, vrows, vin.data(), st.data());
-        // round calls (bbp_prove_round*): what they keep beyond a bbp_prove_batch of the same size -- the staging slots' larger input and
-        // result buffers with their pinned mirrors (sized for a checked call, the larger), the device forms' scratch ring
+        // What the warm-up calls above did not size, from the layouts the calls themselves use (prove_io.h): every buffer of every
+        // staging slot for a round call (bbp_prove_round) and a plain one, as checked calls when checking is on -- the check's scratch,
+        // its info block behind the records, its weights behind the entropy (uploaded entropy: the larger input mirror) -- and the
+        // device forms' scratch rings.  Checked proving also runs the aggregated verifier (the check's) once per lane.
+        const bool check = ctx->prove_check;
+        for (int k = 0; check && k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++) rc = verify_batch_host(ctx, vrows, vin.data(), st.data(), BBP_AGG_GROUP_DEFAULT);
         if (rc == BBP_OK)
             rc = api_guard(ctx, [&]() -> int32_t {
                 int32_t rc = BBP_OK;
                 BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-                const RoundLayout rl(B, N, true);
-                for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++) {
-                    bbp_ctx::IoSlot& sl = ctx->io[k];
-                    if (!(rc = dev_reserve(ctx, sl.in, rl.in_cap)) && !(rc = dev_reserve(ctx, sl.out, rl.out_cap)) &&
-                        !(rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, rl.fetch)))
-                        rc = pinned_reserve(ctx, sl.h_in, sl.h_in_cap, rl.tab_off + rl.tab_bytes + ((size_t)bbp_entropy_size(N) + 32) * B);
-                }
-                for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++) rc = dev_reserve(ctx, ctx->rnd[k].buf, round_dev_bytes(B, N, true));
+                for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++)
+                    if (!(rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, true, check, false)))) rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, false, check, false));
+                for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++)
+                    if (!(rc = dev_reserve(ctx, ctx->rnd[k].buf, RoundRing(B, N, true).bytes)) && check) rc = dev_reserve(ctx, ctx->chk[k].buf, CheckRing(B, N).bytes);
                 return rc;
             });
-        // checked proving (only when it is on, and without running a check): the staging slots' and the device ring's check
-        // scratch, and the aggregated verifier's buffers of every lane (the check's verifier)
-        if (rc == BBP_OK && ctx->prove_check) {
-            for (int k = 0; k < bbp_ctx::IO_VSLOTS && rc == BBP_OK; k++)
-                rc = verify_batch_host(ctx, vrows, vin.data(), st.data(), BBP_AGG_GROUP_DEFAULT);
-            if (rc == BBP_OK)
-                rc = api_guard(ctx, [&]() -> int32_t {
-                    int32_t rc = BBP_OK;
-                    BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-                    const size_t out_bytes = align256(rec * B) + 4 * (3 * (size_t)B + 1);
-                    for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++)
-                        if (!(rc = dev_reserve(ctx, ctx->io[k].chk, check_scratch_bytes(B, N))) && !(rc = dev_reserve(ctx, ctx->io[k].out, out_bytes)))
-                            rc = pinned_reserve(ctx, ctx->io[k].h_out, ctx->io[k].h_cap, out_bytes);
-                    for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++)
-                        rc = dev_reserve(ctx, ctx->chk[k].buf, align256(check_scratch_bytes(B, N)) + 4 * (size_t)B);
-                    return rc;
-                });
-        }
         return rc;
     });
 }

@@ -18,6 +18,7 @@
 #include "../../include/bbp.h"
 #include "point.h"
 #include "msm_plan.h"
+#include "prove_io.h"
 #include "prove_plan.h"
 #include "scalar.h"
 #include "verify_rows.h"

@@ -245,7 +245,7 @@ static int32_t for_each_block(bbp_ctx* pool, uint32_t B, F&& body) {
 }
 
 int32_t pool_prove_batch(bbp_ctx* pool, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status) {
-    const size_t in_stride = 7 * 32 + (size_t)N * 32 + 8, ent_stride = bbp_entropy_size(N), out_stride = bbp_proof_record_size(N);
+    const size_t in_stride = prove_in_bytes(N), ent_stride = bbp_entropy_size(N), out_stride = bbp_proof_record_size(N);
     return for_each_block(pool, B, [&](bbp_ctx* m, uint32_t lo, uint32_t hi) {
         return bbp_prove_batch(m, hi - lo, N, in + in_stride * lo, entropy ? entropy + ent_stride * lo : nullptr, out + out_stride * lo, status + lo);
     });

@@ -106,7 +106,7 @@ __device__ sc sc_pow_small(const sc& x, u32 e) {
 __global__ void k_witness_head(u32 B, u32 n_items, u32 n_cst, const u8* __restrict__ in_raw, sc* __restrict__ cst_all, sc* __restrict__ v_all) {
     u32 p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= B) return;
-    const size_t in_stride = 7 * 32 + (size_t)n_items * 32 + 8;
+    const size_t in_stride = prove_in_bytes(n_items);
     const u32* in = reinterpret_cast<const u32*>(in_raw + in_stride * p);
     sc* cst = cst_all + (size_t)p * n_cst;
     const u32 m = 4 + n_items;

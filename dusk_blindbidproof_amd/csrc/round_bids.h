@@ -8,18 +8,20 @@
 //   k_round_rows     one lane per byte: record || score || z_img, the rows bbp_verify_rounds takes
 #pragma once
 #include "../../include/bbp.h"
+#include "prove_io.h"
 #include "witness_check.h"
 
 namespace bbp {
 
-// what k_round_bids leaves per bid, as 32-bit words: y, y_inv, q, z_img (8 each), toggle (u64 LE), status, one word of padding.
-// A refused bid (status != BBP_OK) has every other word zero.
-enum : u32 { RB_Y = 0, RB_YINV = 8, RB_Q = 16, RB_ZIMG = 24, RB_TOGGLE = 32, RB_STATUS = 34, RB_WORDS = 36 };
+// what k_round_bids leaves per bid, as 32-bit words (RB_WORDS of them, prove_io.h): y, y_inv, q, z_img (8 each), toggle (u64 LE),
+// status, one word of padding.  A refused bid (status != BBP_OK) has every other word zero.
+enum : u32 { RB_Y = 0, RB_YINV = 8, RB_Q = 16, RB_ZIMG = 24, RB_TOGGLE = 32, RB_STATUS = 34 };
+static_assert(RB_STATUS + 2 == RB_WORDS, "prove_io.h sizes the pass's scratch by RB_WORDS");
 // k_round_expand's outputs per bid, in words: the prove-input row (56 + 8 N + 2), then score || z_img, the toggle, the status
 enum : u32 { RB_TAIL_WORDS = 16, RB_EXTRA_WORDS = RB_TAIL_WORDS + 2 + 1 };
 
 BBP_HD u32 rb_le32(const u8* b) { return (u32)b[0] | ((u32)b[1] << 8) | ((u32)b[2] << 16) | ((u32)b[3] << 24); }
-BBP_HD u32 round_in_words(u32 N) { return 7 * 8 + 8 * N + 2; }  // bbp_prove_batch's input row
+BBP_HD u32 round_in_words(u32 N) { return prove_in_toggle_word(N) + 2; }  // prove_in_words(N) in 32 bits: the toggle's two words end the row
 
 // One bid against the reduced round.  bid: d || k (64 bytes, any alignment); rblk: seed mod l, then the N items as Scalar::from_bits
 // values (k_round_consts' block for R = 1); seed_flag: BBP_ERR_FORMAT for a non-canonical seed, else BBP_OK; out: RB_WORDS words.
@@ -82,21 +84,7 @@ BBP_HD u8 round_row_byte(u32 N, u32 o, const u8* record, const u32* rb) {
     return (u8)(rb[RB_Q + (t >> 2)] >> (8 * (t & 3)));
 }
 
-// Scratch of one device pass, byte offsets (256-aligned): the two round offsets k_round_consts reads, its flag, its reduced block, the
-// RB_WORDS words per bid
-struct RoundScratch {
-    size_t roff, rflag, rblk, rb, end;
-};
-inline RoundScratch round_scratch(u32 B, u32 N) {
-    auto up = [](size_t n) { return (n + 255) / 256 * 256; };
-    RoundScratch s;
-    s.roff = 0;
-    s.rflag = 256;
-    s.rblk = 512;
-    s.rb = s.rblk + up(32 * (1 + (size_t)N));
-    s.end = s.rb + up(4 * (size_t)RB_WORDS * B);
-    return s;
-}
+// (the scratch of one device pass, RoundScratch / round_scratch: prove_io.h)
 
 #ifdef __HIPCC__
 // One lane per bid; the four chains are 1440 dependent Montgomery products, so the wave lives for milliseconds and is fenced onto

@@ -77,7 +77,7 @@ __global__ BBP_LANE_KERNEL void k_vparse(u32 B, u32 n_items, u32 n_cst, u32 rec_
     if (p >= B) return;
     const u32 m = 4 + n_items;
     const u32 plen = rec_ver ? 1217u : 1121u;
-    const size_t stride = (size_t)plen + 32 * (size_t)m + 96 + 32 * (size_t)n_items;
+    const size_t stride = (size_t)plen + 32 * (size_t)m + verify_tail_bytes(n_items);
     const u8* r = in + stride * p;
     int32_t st = BBP_OK;
     if (r[0] != (u8)rec_ver) st = BBP_ERR_FORMAT;  // version byte must match the layout implied by the length

@@ -8,6 +8,7 @@
 #include "../dusk_blindbidproof_amd/csrc/keccak_wave.h"
 #include "../dusk_blindbidproof_amd/csrc/msm_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/point.h"
+#include "../dusk_blindbidproof_amd/csrc/prove_io.h"
 #include "../dusk_blindbidproof_amd/csrc/prove_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
 #include "../dusk_blindbidproof_amd/csrc/scalarmul.h"
@@ -252,6 +253,31 @@ void hc_verify_rows(int kind, uint32_t B, uint32_t N, uint32_t rec_ver, const ui
     info[8] = v.round_of != nullptr;
     info[9] = v.round_of ? (uint64_t)(v.round_of - round_of) : 0;
     info[10] = v.B ? v.first_n() : 0;
+}
+
+// The row sizes of the prove side and the staging layout of one host-pointer prove call with its two ring siblings
+// (csrc/prove_io.h).  sizes: 0 prove_in_bytes, 1 prove_in_words, 2 PROVE_IN_Q, 3 PROVE_IN_LIST, 4 PROVE_IN_LIST_WORD, 5 prove_in_toggle,
+// 6 prove_in_toggle_word, 7 entropy_row_bytes, 8 verify_tail_bytes, 9 verify_tail_words, 10 VERIFY_TAIL_LIST_WORD, 11 ROUND_BID_BYTES,
+// 12 round_table_bytes.  lay: the ProveStaging of (B, N, round, check, dev_draw) -- 0 in_stride, 1 ent_stride, 2 rec, 3 res_stride,
+// 4 in_first_bytes, 5 in_tab, 6 in_tab_bytes, 7 in_scratch, 8 in_rows, 9 in_upload, 10 in_cap, 11 rs.end, 12 rs.rb, 13 ent_drawn,
+// 14 ent_up_off, 15 ent_up_bytes, 16 ent_cap, 17 ent_check(first), 18 out_recs, 19 out_info, 20 out_status, 21 out_mask, 22 out_fail_n,
+// 23 out_fail_idx, 24 out_tog, 25 out_pass_st, 26 out_fetch, 27 out_cap, 28 chk_vstatus, 29 chk_bytes, 30 h_in_bytes, 31 h_out_bytes.
+// rings: CheckRing(B, N) -- 0 vstatus, 1 scratch_bytes, 2 mask, 3 bytes; RoundRing(B, N, false).bytes at 4; RoundRing(B, N, true) --
+// 5 rows, 6 recs, 7 bytes.
+void hc_prove_staging(uint32_t B, uint32_t N, int round, int check, int dev_draw, uint32_t first, uint64_t* sizes, uint64_t* lay, uint64_t* rings) {
+    const uint64_t sz[13] = {prove_in_bytes(N), prove_in_words(N), PROVE_IN_Q, PROVE_IN_LIST, PROVE_IN_LIST_WORD, prove_in_toggle(N), prove_in_toggle_word(N),
+                             entropy_row_bytes(N), verify_tail_bytes(N), verify_tail_words(N), VERIFY_TAIL_LIST_WORD, ROUND_BID_BYTES, round_table_bytes(N)};
+    memcpy(sizes, sz, sizeof sz);
+    const ProveStaging L(B, N, round != 0, check != 0, dev_draw != 0);
+    const uint64_t lv[32] = {L.in_stride, L.ent_stride, L.rec, L.res_stride, L.in_first_bytes, L.in_tab, L.in_tab_bytes, L.in_scratch, L.in_rows, L.in_upload, L.in_cap,
+                             L.rs.end, L.rs.rb, L.ent_drawn, L.ent_up_off, L.ent_up_bytes, L.ent_cap, L.ent_check(first), L.out_recs, L.out_info, L.out_status,
+                             L.out_mask, L.out_fail_n, L.out_fail_idx, L.out_tog, L.out_pass_st, L.out_fetch, L.out_cap, L.chk_vstatus, L.chk_bytes, L.h_in_bytes,
+                             L.h_out_bytes};
+    memcpy(lay, lv, sizeof lv);
+    const CheckRing c(B, N);
+    const RoundRing r0(B, N, false), r1(B, N, true);
+    const uint64_t rv[8] = {c.vstatus, c.scratch_bytes, c.mask, c.bytes, r0.bytes, r1.rows, r1.recs, r1.bytes};
+    memcpy(rings, rv, sizeof rv);
 }
 
 // The plan of one prove call (csrc/prove_plan.h).  knobs: n_knobs (environment name, text) pairs applied over the defaults through

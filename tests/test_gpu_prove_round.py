@@ -279,3 +279,30 @@ def test_reserved_context_allocates_nothing_in_round_calls(bbp, ctx):
         assert _allocs(c) == a0, (a0, _allocs(c))
     finally:
         c.close()
+
+
+def test_reserved_context_allocates_nothing_in_checked_calls(bbp, ctx):
+    """bbp_reserve on a context with checked proving on sizes every staging buffer for a checked call: the check's weights travel
+    behind the prover's entropy (32 bytes per row more than an unchecked call uploads).  (640, 1) is the smallest shape at which a
+    slot's entropy buffer sized for unchecked calls (a row of 192 bytes plus an eighth of slack) is too small for that."""
+    N, B = 1, 640
+    r = rc.honest(N, B, tag=8)
+    rows, ent = r.in_rows(), rc.entropy(17, B, N)
+    c = bbp.Context(0)
+    try:
+        c.set_prove_check(True)
+        c.reserve(B, N)
+        a0 = _allocs(c)
+        assert a0 > 0
+        results = [c.prove_batch(B, N, rows, ent) for _ in range(3)]  # three staging slots
+        c.set_entropy_source("device")
+        results.append(c.prove_batch(B, N, rows))
+        assert _allocs(c) == a0, (a0, _allocs(c))
+        rs_ = bbp.record_size(N)
+        for recs, st in results:
+            assert st == [OK] * B
+            vin = b"".join(recs[rs_ * i:rs_ * (i + 1)] + r.tail(i) + r.table for i in range(B))
+            assert c.verify_batch(B, N, vin) == [OK] * B
+        assert c.health() == 0
+    finally:
+        c.close()
