@@ -1531,6 +1531,15 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
                     if (!(rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, true, check, false)))) rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, false, check, false));
                 for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++)
                     if (!(rc = dev_reserve(ctx, ctx->rnd[k].buf, RoundRing(B, N, true).bytes)) && check) rc = dev_reserve(ctx, ctx->chk[k].buf, CheckRing(B, N).bytes);
+                // the draw buffers, one per stream that opens (ProvePlan::raw_index): side's has seen a call of B; the others open dual calls
+                // only, below dual_open_below proofs or up to rotate_deep_max in a deep pipeline, and the warm-up reaches those sizes only
+                // while B itself is one (a deep warm-up call is skipped beyond rotate_deep_max)
+                const CircuitDev* c = nullptr;
+                if (rc == BBP_OK && !(rc = circuit_get(ctx, N, &c))) {
+                    const uint32_t dual_max = std::max((uint32_t)std::max(ctx->knobs.dual_open_below - 1, 0), ctx->knobs.deep_eligible(1) ? (uint32_t)ctx->knobs.rotate_deep_max : 0u);
+                    for (auto& r : ctx->raw)
+                        if (rc == BBP_OK) rc = dev_reserve(ctx, r, (size_t)std::min(B, dual_max) * (3 + 2 * (size_t)c->n_mul) * 64);
+                }
                 return rc;
             });
         return rc;

@@ -208,7 +208,7 @@ struct bbp_ctx {
     uint8_t gens_enc_host_valid = 0;
     std::vector<uint8_t> mimc_host;    // 90 * 32
     // grow-only scratch
-    bbp::DevBuf scal, idx, sorted, pts, enc, batch[PROVE_BUFS + VLANES], io_in, io_out, io_ent, raw[2];  // batch[3 + lane]: the verifier lanes'; raw[i]: draw buffer of opening stream i
+    bbp::DevBuf scal, idx, sorted, pts, enc, batch[PROVE_BUFS + VLANES], io_in, io_out, io_ent, raw[4];  // batch[3 + lane]: the verifier lanes'; raw[i]: draw buffer of the stream that opens (ProvePlan::raw_index: side, side2, lane[1], lane[2])
     static constexpr int VERIFY_SLOT = MAX_SLICES;  // MSM scratch slots of the verifier lanes: VERIFY_SLOT + lane
     bbp::DevBuf slice_sorted[MAX_SLICES + VLANES], slice_pts[MAX_SLICES + VLANES], slice_fold[MAX_SLICES], slice_vtab[MAX_SLICES];  // per-slice MSM scratch (slice 0 uses sorted / pts)
     // Host-pointer batch calls stage through one of three slots (device in / entropy / out + a pinned host mirror of the results):

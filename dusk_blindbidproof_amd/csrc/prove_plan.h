@@ -40,6 +40,8 @@ struct ProveKnobs {
     int tail_round = FOLD_ROUND;      // BBP_TAIL_ROUND: first IPA round on folded generators; anything but FOLD_ROUND = 12 = none
     int stagger_mode = 0;             // BBP_STAGGER: 0 = slices start together, 1 / 3 = the next slice starts after this slice's first / third MSM
     int trace_prove = 0;              // BBP_TRACE_PROVE (present = on): one stderr line per prove call with its plan
+    int open_on_chain = -1;           // BBP_OPEN_ON_CHAIN: a rotating call's opening stage runs on the stream of its heavy stage: 0 never, 1 every rotating call, unset (-1) = the calls of a deep pipeline, by hw_queues
+    int hw_queues = 4;                // no environment name of its own: the hardware queues the process's HIP runtime was given, filled in by bbp_init (HIP's default)
 
     // the one list of environment names; a null clamp takes the number as it is
     struct Env {
@@ -71,6 +73,7 @@ struct ProveKnobs {
             {"BBP_TAIL_ROUND", &ProveKnobs::tail_round, [](int v) { return v == FOLD_ROUND ? FOLD_ROUND : 12; }},
             {"BBP_STAGGER", &ProveKnobs::stagger_mode, nullptr},
             {"BBP_TRACE_PROVE", &ProveKnobs::trace_prove, [](int) { return 1; }},
+            {"BBP_OPEN_ON_CHAIN", &ProveKnobs::open_on_chain, [](int v) { return v < 0 ? -1 : v ? 1 : 0; }},
         };
         for (const Env& e : table) f(e);
     }
@@ -94,6 +97,11 @@ struct ProveKnobs {
 
     // a call of B proofs may take the rotating path in deep mode
     bool deep_eligible(uint32_t B) const { return slices > 1 && rotate_deep_max > 0 && B <= (uint32_t)rotate_deep_max; }
+    // a rotating call runs as one chain, opening stage and heavy stage on one stream: with fewer than seven hardware queues the five
+    // internal streams that a deep pipeline keeps busy in the two-stream form (side, side2, lane[1..3]) cannot all have a queue apart
+    // from the caller's stream's.  Unset, the rule holds for calls planned `deep` only: a caller that mixes rotating and sliced calls
+    // without being in deep mode (two host threads) would find every third chain on side, where its sliced calls open
+    bool chain_rule(bool deep) const { return open_on_chain == 1 || (open_on_chain < 0 && deep && hw_queues < 7); }
     // launches that must stay off the CUs the serial opening kernels reserve carry a token 64 bytes of LDS (prover.hip "LAUNCH")
     unsigned lds_token() const { return serial_lds >= 160 * 1024 ? 64u : 0u; }
 };
@@ -128,6 +136,9 @@ inline HeavyPlan plan_heavy(const ProveKnobs& k, uint32_t B) {
     return h;
 }
 
+// The streams of a context by role, in the order bbp_init creates them (hardware queues are handed out in that order).
+enum StreamRole { ROLE_CALLER = 0, ROLE_SIDE, ROLE_LANE1, ROLE_LANE2, ROLE_LANE3, ROLE_COPY, ROLE_SIDE2, ROLE_COUNT };
+
 struct ProvePlan {
     enum Chain { SERIAL, LANES25, WORD, HALFWORD };  // the draw chain: k_open_serial alone | k_open_bulk | k_open_bulk8 | k_open_bulk50
     uint32_t call = 0;           // this call's index
@@ -144,7 +155,22 @@ struct ProvePlan {
     bool rotate = false;         // the heavy stage runs unsliced on lane[heavy_stream]
     int heavy_stream = 0;
     uint32_t slices = 0;         // 0 when rotating
+    bool open_on_chain = false;  // rotating, and the opening stage runs on the heavy stage's stream: the call is one chain
+    int chain_stream = -1;       // ... the role of that stream: heavy_stream 1 -> ROLE_LANE1, 2 -> ROLE_LANE2, 3 -> ROLE_SIDE; -1 otherwise
 
+    // the stream the opening stage runs on, the one the rotated heavy stage runs on, the one slice i runs on
+    int open_role() const { return open_on_chain ? chain_stream : open_stream ? ROLE_SIDE2 : ROLE_SIDE; }
+    int heavy_role() const { return open_on_chain ? chain_stream : ROLE_LANE1 + heavy_stream - 1; }
+    static int slice_role(uint32_t i) { return i == 0 ? ROLE_CALLER : ROLE_LANE1 + (int)i - 1; }
+    // every stream the call enqueues on, as a mask of 1 << role (the caller's stream always: entry, join and completion events)
+    uint32_t roles() const {
+        uint32_t mask = 1u << ROLE_CALLER | 1u << open_role();
+        if (rotate) mask |= 1u << heavy_role();
+        for (uint32_t i = 0; i < slices; i++) mask |= 1u << slice_role(i);
+        return mask;
+    }
+    // the draw buffer (bbp_ctx::raw) of the opening stage: one per stream that opens, so that stream order alone guards it
+    int raw_index() const { return !open_on_chain ? open_stream : chain_stream == ROLE_SIDE ? 0 : 1 + heavy_stream; }
     uint32_t cblk_wave() const { return 2 * cblk > 1024u ? 1024u : 2 * cblk; }
     // slice i of a call of B proofs is [slice_first(B, i), slice_first(B, i + 1))
     uint32_t slice_first(uint32_t B, uint32_t i) const { return (uint32_t)(((uint64_t)B * i) / slices); }
@@ -185,6 +211,8 @@ ProvePlan plan_prove(const ProveKnobs& k, ProveRuleState& st, uint32_t B, int in
     p.slices = B >= 64u * (uint32_t)k.slices ? (uint32_t)k.slices : (B >= 128 ? 2u : 1u);
     if (p.dual && p.slices > 2) p.slices = 2;
     if (p.rotate) p.slices = 0;
+    p.open_on_chain = p.rotate && k.chain_rule(p.deep);
+    p.chain_stream = !p.open_on_chain ? -1 : p.heavy_stream == 3 ? (int)ROLE_SIDE : (int)ROLE_LANE1 + p.heavy_stream - 1;
     return p;
 }
 

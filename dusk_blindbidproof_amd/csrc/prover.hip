@@ -1422,6 +1422,17 @@ int32_t tail_btab_build(bbp_ctx* ctx) {  // called once from bbp_init: the table
 size_t tail_btab_bytes() { return sizeof(ge) * TAIL_TAB; }
 
 static BatchDev batch_view(const BatchDev& bd, const CircuitDev& c, u32 first);
+static hipStream_t role_stream(bbp_ctx* ctx, int role, hipStream_t caller) {  // prove_plan.h StreamRole
+    switch (role) {
+        case ROLE_CALLER: return caller;
+        case ROLE_SIDE: return ctx->side;
+        case ROLE_SIDE2: return ctx->side2;
+        case ROLE_LANE1: return ctx->lane[1];
+        case ROLE_LANE2: return ctx->lane[2];
+        case ROLE_LANE3: return ctx->lane[3];
+        default: return nullptr;  // no plan asks for another
+    }
+}
 static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
                            hipEvent_t stagger, hipEvent_t out_guard);
 
@@ -1471,23 +1482,42 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     // proofs/s).  Its workgroup: one wavefront (two proofs) per reserved CU is the fastest chain, but at 256 proofs that reserves
     // 128 CUs under the other in-flight calls' heavy stages; two wavefronts per CU there (measured 11.3 k -> 12.5 k proofs/s back to
     // back), four above 256 proofs (384: 12.8 k -> 14.8 k, 512: 14.6 k -> 16.5 k against the single-lane chain).
+    // ONE CHAIN PER ROTATING CALL (plan.open_on_chain, the rule for the calls of a deep pipeline with fewer than seven hardware queues:
+    // prove_plan.h chain_rule; a rotating call that is not deep keeps the two-stream form, and the two forms may alternate).  A rotating
+    // call's opening stage feeds its own heavy stage only, so both go on one stream, the chain stream, and calls rotate over three
+    // chains: lane[1], lane[2], side -- with the caller's stream the first four streams the context creates, which have a hardware
+    // queue each from four queues up.  In the two-stream form five internal streams are busy at once (side, side2, lane[1..3]); with
+    // four queues side2 shares side's queue and lane[3] shares lane[2]'s (kernel trace, profiles/r12_prove_queue_map_before.txt): two 30 ms
+    // single-lane draw chains in one in-order queue, and every third heavy stage behind another call's.  Three chains of opening -> heavy are out of phase by construction:
+    // about one is in its opening stage (a few CUs) while two run heavy stages.  side2, lane[3] and copy receive nothing.
+    // Every wait a chain makes is for an event that an OLDER call recorded, or this call on the caller's stream before anything else
+    // of this call: ev_done[par] (call - PROVE_BUFS, on the caller's stream behind that call's join), ev_prep / ev_draw (API calls
+    // made before this one), ev_join[3] (the last user of MSM scratch slot 3: a chain on side, a two-stream call or a slice on lane[3] --
+    // the only slot two streams use; slots 1 and 2 stay on lane[1] and lane[2] in either form), ev_entry[par] (recorded at this call's entry; the caller's stream holds only older
+    // calls' joins before it).  The caller's stream waits for ev_join[hs], recorded at the chain's end.  So no cycle.  The draw buffer
+    // is the chain stream's own (raw[plan.raw_index()]): written and read inside the opening stage, stream order guards it; the MSM
+    // scratch slot stays heavy_stream, and a slice on lane[i] uses slot i behind any older chain on that stream.  A call that falls
+    // back to slices after deep mode may find an older chain still on side: its opening stage queues behind it, correct by stream order.
     const ProvePlan plan = plan_prove(ctx->knobs, ctx->prove_state, B, inflight, [&] {
         const int lp = ctx->last_prove_par;
         return lp >= 0 && ctx->ev_done_valid[lp] && hipEventQuery(ctx->ev_done[lp]) == hipErrorNotReady;
     });
-    const int sidx = plan.open_stream, par = plan.par;
-    if (plan.dual && !ctx->side2) BBP_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking));
+    const int ridx = plan.raw_index(), par = plan.par;
+    if (plan.open_role() == ROLE_SIDE2 && !ctx->side2) BBP_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking));
     BatchDev bd;
     if ((rc = batch_reserve(ctx, B, c, bd, par))) return rc;
     const u32 m = c.m, n1 = c.n_mul, encw = (m + 8 + 22) * 8;
     const merlin_transcript prefix = prover_prefix();
     const size_t n_draws = 3 + 2 * (size_t)n1;
-    if ((rc = dev_reserve(ctx, ctx->raw[sidx], (size_t)B * n_draws * 64))) return rc;
-    u32* const raw = (u32*)ctx->raw[sidx].p;
+    if ((rc = dev_reserve(ctx, ctx->raw[ridx], (size_t)B * n_draws * 64))) return rc;
+    u32* const raw = (u32*)ctx->raw[ridx].p;
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_entry[par], s));
     // 3. OPENING stage, on `os`.  It does NOT wait for the caller's stream: in_dev / ent_dev must be complete when the call is made
     // (include/bbp.h).  Waiting on the caller's stream tail would serialise it behind the previous call's heavy stage.
-    hipStream_t os = sidx ? ctx->side2 : ctx->side;
+    hipStream_t os = role_stream(ctx, plan.open_role(), s);
+    // (a chain on side uses MSM scratch slot 3, which a two-stream rotating call and the fourth slice use on lane[3]: behind the slot's
+    // last user, an older call; nothing to wait for when that was this stream)
+    if (plan.chain_stream == ROLE_SIDE) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_join[3], 0));
     if (ctx->ev_done_valid[par]) BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_done[par], 0));
     if (ctx->ev_prep_valid) {  // rows written by bbp_prepare_bids_dev since the last prove call
         BBP_HIP_TRY(ctx, hipStreamWaitEvent(os, ctx->ev_prep, 0));
@@ -1548,8 +1578,9 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     const size_t rec = BBP_R1CS_PROOF_BYTES + 32 * (size_t)m;
     if (plan.rotate) {
         const int hs = plan.heavy_stream;
-        hipStream_t ls = ctx->lane[hs];
-        BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_open[par], 0));
+        hipStream_t ls = role_stream(ctx, plan.heavy_role(), s);
+        if (!plan.open_on_chain) BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_open[par], 0));  // one chain: plain stream order
+        if (!plan.open_on_chain && hs == 3) BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_join[3], 0));  // slot 3's last user may be a chain on side
         if ((rc = prove_heavy(ctx, plan_heavy(ctx->knobs, B), c, bd, B, out_dev, ls, hs, nullptr, ctx->ev_entry[par]))) return rc;
         BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_join[hs], ls));
         BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[hs], 0));
@@ -1559,7 +1590,8 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     // transcript + scalar inversion in k_ipa_round, the small encode / commit kernels) the others' MSMs keep the CUs busy.
     for (u32 i = 0; i < plan.slices; i++) {
         const u32 first = plan.slice_first(B, i), last = plan.slice_first(B, i + 1);
-        hipStream_t ls = i == 0 ? s : ctx->lane[i];
+        hipStream_t ls = role_stream(ctx, ProvePlan::slice_role(i), s);
+        if (i == 3) BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_join[3], 0));  // slot 3, as above
         BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_open[par], 0));
         // stagger: slices run the same kernel sequence, so started together their latency-bound steps would coincide; each
         // slice waits for the previous slice's first MSM, which puts its serial steps under the neighbour's MSMs

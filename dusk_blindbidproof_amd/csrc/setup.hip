@@ -233,8 +233,8 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join[i], hipEventDisableTiming));
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_stagger[i - 1], hipEventDisableTiming));
     }
-    // created AFTER the engine's own streams: hardware queues are handed out in creation order, and the four streams the heavy
-    // stage keeps busy (stream, side, lane[1], lane[2]) must not share one (measured: with the copy stream created third, a
+    // created AFTER the engine's own streams: hardware queues are handed out in creation order, and the four streams a prove call
+    // keeps busy (stream, side, lane[1], lane[2]: slices, or the three chains of rotating calls, prove_plan.h) must not share one (measured: with the copy stream created third, a
     // 1024-proof batch took 60.9 instead of 55.6 ms)
     BBP_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->copy, hipStreamNonBlocking));
     // the small-batch path's second opening stream, BEFORE the verifier lanes: with 8 hardware queues (what bbp-uds-server exports) the seventh
@@ -268,6 +268,8 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
     for (auto& e : ctx->ev_vacc) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
     if (const char* e = getenv("BBP_VERIFY_AGGREGATE")) ctx->verify_group = atoi(e) > 1 ? (uint32_t)atoi(e) : 0u;
     ctx->knobs = ProveKnobs::from_env();  // every prove-schedule knob: prove_plan.h lists the names
+    // ... and the queue count the schedule is fitted to, read only: the caller's value, else the one own_hw_queues exported, else HIP's default
+    if (const char* e = getenv("GPU_MAX_HW_QUEUES")) ctx->knobs.hw_queues = atoi(e) > 0 ? atoi(e) : 4;
     if (const char* e = getenv("BBP_VARBASE_LANES")) ctx->varbase_lanes = atoi(e) < 64 ? 64 : atoi(e);
     ctx->msm_knobs = MsmKnobs::from_env();  // BBP_SORT_STAGED, BBP_FOLD_HALF_FROM, BBP_MSM_SMALL and the split knobs: msm_plan.h
     for (int i = 0; i < bbp_ctx::PROVE_BUFS; i++) {
@@ -341,7 +343,8 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     std::vector<void*> ptrs = {ctx->gens, ctx->ptable, ctx->btab, ctx->comb, ctx->mimc_c, ctx->scal.p, ctx->idx.p, ctx->sorted.p, ctx->pts.p, ctx->enc.p,
-                               ctx->io_in.p, ctx->io_out.p, ctx->io_ent.p, ctx->raw[0].p, ctx->raw[1].p};
+                               ctx->io_in.p, ctx->io_out.p, ctx->io_ent.p};
+    for (auto& b : ctx->raw) ptrs.push_back(b.p);
     for (auto& b : ctx->batch) ptrs.push_back(b.p);
     for (auto& b : ctx->slice_sorted) ptrs.push_back(b.p);
     for (auto& b : ctx->slice_pts) ptrs.push_back(b.p);
@@ -486,6 +489,12 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                       " before the process first touches HIP (or call bbp_init first: it does so itself), or streams of this context share "
                                       "fewer hardware queues and serialise\n",
                                       hwq ? hwq : "not set", hst == 3 ? " and HIP was initialised before bbp_init could set it" : "");
+        if (off + 1 < cap)
+            off += (uint32_t)snprintf(buf + off, cap - off, "rotating prove calls: opening stage %s (BBP_OPEN_ON_CHAIN %s, schedule fitted to %d hardware queue(s))\n",
+                                      ctx->knobs.chain_rule(false) ? "on the call's own chain stream: three chains on side, lane[1], lane[2]"
+                                      : ctx->knobs.chain_rule(true) ? "on the call's own chain stream for the calls of a deep pipeline (three chains on side, lane[1], lane[2]), else on side / side2"
+                                                                    : "on side / side2, heavy stage on lane[1..3]",
+                                      ctx->knobs.open_on_chain < 0 ? "unset: deep pipelines below 7 queues" : ctx->knobs.open_on_chain ? "= 1" : "= 0", ctx->knobs.hw_queues);
         if (off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "checked proving: %s\n",
                                       ctx->prove_check ? "on (every record is verified on the device before it is returned)" : "off");
