@@ -177,7 +177,7 @@ static uint32_t env_chunk(const char* name, uint32_t dflt) {
     return v >= 1 ? (uint32_t)v : dflt;
 }
 static uint32_t host_chunk_prove() { return env_chunk("BBP_HOST_CHUNK_PROVE", 16384); }
-static uint32_t host_chunk_verify() { return env_chunk("BBP_HOST_CHUNK_VERIFY", 32768); }
+static uint32_t host_chunk_verify() { return VerifyKnobs::host_chunk_now(); }  // verify_plan.h lists the name
 
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
@@ -1158,15 +1158,12 @@ extern "C" int32_t bbp_prove_async(bbp_ctx* ctx, const uint8_t scalars7[7 * 32],
 // uploaded behind the rows in the same staging slot).  Takes the context lock itself, for the enqueue phase only.
 static int32_t verify_batch_host(bbp_ctx* ctx, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group = 0,
                                  uint32_t* n_fallback = nullptr) {
-    const uint32_t B = rows.B, rec_ver = rows.rec_ver, N = rows.kind == VerifyRows::UNIFORM ? rows.N : 0;
-    const std::vector<size_t> row_off = rows.offsets();
-    const size_t in_bytes = row_off[B], tab_bytes = rows.table_bytes(), tab_off = align256(in_bytes);
-    if (rec_ver) group = 0;  // the aggregated path takes compact records only: one two-phase row and the call runs plain
-    if (group == 0 && rec_ver == 0 && ctx->verify_group > 1 && B >= 2 * ctx->verify_group) group = ctx->verify_group;  // BBP_VERIFY_AGGREGATE
+    const uint32_t B = rows.B, N = rows.kind == VerifyRows::UNIFORM ? rows.N : 0;
     // Verifier::verify mixes thread_rng into its TranscriptRng (A.7): 32 OS bytes per proof, or (source DEVICE) rows of one key
     const bool dev_draw = ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
+    const VerifyStaging st(rows, group, (uint32_t)ctx->vknobs.group, dev_draw, host_chunk_verify());  // BBP_VERIFY_AGGREGATE, BBP_HOST_CHUNK_VERIFY
     ChachaKey key{};
-    std::vector<uint8_t> ent(dev_draw ? 0 : (size_t)B * 32);
+    std::vector<uint8_t> ent(st.ent_up_bytes);
     if (dev_draw) {
         if (int32_t rc = next_device_key(ctx, &key)) return rc;
     } else if (!os_random(ent.data(), ent.size())) {
@@ -1178,20 +1175,19 @@ static int32_t verify_batch_host(bbp_ctx* ctx, const VerifyRows& rows, const uin
     int32_t rc = api_guard(ctx, [&]() -> int32_t {
         int32_t rc;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        if ((rc = dev_reserve(ctx, sl.out, 4 * ((size_t)B + 1))) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, 4 * ((size_t)B + 1))) ||
-            (rc = upload_inputs(ctx, sl, in, in_bytes, ent.data(), ent.size(), dev_draw ? 32 * (size_t)B : 0, rows.rounds, tab_bytes, tab_off)))
+        if ((rc = dev_reserve(ctx, sl.out, st.out_bytes)) || (rc = pinned_reserve(ctx, sl.h_out, sl.h_cap, st.out_bytes)) ||
+            (rc = upload_inputs(ctx, sl, in, st.in_bytes, ent.data(), ent.size(), st.ent_drawn, rows.rounds, st.tab_bytes, st.tab_off)))
             return rc;
         if (dev_draw && (rc = draw_enqueue(ctx, B, N, BBP_ENTROPY_VERIFY, key, 0, sl.ent.p, L.stream))) return rc;  // ahead of every chunk on the lane
-        const uint32_t n_chunks = (B + host_chunk_verify() - 1) / host_chunk_verify(), chunk = (B + n_chunks - 1) / n_chunks;
-        for (uint32_t first = 0; first < B; first += chunk) {  // bounded scratch for any B (see bbp_prove_batch)
-            const uint32_t nb = B - first < chunk ? B - first : chunk;
-            const u8 *cin = (const u8*)sl.in.p + row_off[first], *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
+        for (uint32_t first = 0; first < B; first += st.chunk) {
+            const uint32_t nb = B - first < st.chunk ? B - first : st.chunk;
+            const u8 *cin = (const u8*)sl.in.p + st.row_off[first], *cent = (const u8*)sl.ent.p + 32 * (size_t)first;
             int32_t* cst = (int32_t*)sl.out.p + first;
             VerifyRows c = rows.slice(first, first + nb);  // a chunk may begin and end inside a round: it takes the whole table
-            if (c.rounds) c.rounds = (const u8*)sl.in.p + tab_off;
-            if (group > 1) {  // stream-ordered: no synchronisation while the context lock is held
+            if (c.rounds) c.rounds = (const u8*)sl.in.p + st.tab_off;
+            if (st.group > 1) {  // stream-ordered: no synchronisation while the context lock is held
                 if (first == 0 && L.agg_count) BBP_HIP_TRY(ctx, hipMemsetAsync(L.agg_count + 1, 0, sizeof(u32), L.stream));
-                if ((rc = verify_batch_agg_dev(ctx, c, group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B))) return rc;
+                if ((rc = verify_batch_agg_dev(ctx, c, st.group, cin, cent, cst, L.stream, nullptr, (u32*)sl.out.p + B))) return rc;
             } else if ((rc = verify_batch_dev(ctx, c, 0, cin, cent, cst, L.stream)))
                 return rc;
         }
@@ -1199,9 +1195,9 @@ static int32_t verify_batch_host(bbp_ctx* ctx, const VerifyRows& rows, const uin
         return BBP_OK;
     });
     if (rc) return rc;
-    if ((rc = fetch_results(ctx, sl, 4 * ((size_t)B + (group > 1 ? 1 : 0))))) return rc;
+    if ((rc = fetch_results(ctx, sl, st.fetch_bytes))) return rc;
     memcpy(status, sl.h_out, 4 * (size_t)B);
-    if (group > 1 && n_fallback) memcpy(n_fallback, (const uint8_t*)sl.h_out + 4 * (size_t)B, 4);  // running total of this call's chunks
+    if (st.group > 1 && n_fallback) memcpy(n_fallback, (const uint8_t*)sl.h_out + 4 * (size_t)B, 4);  // running total of this call's chunks
     return BBP_OK;
 }
 

@@ -21,6 +21,7 @@
 #include "prove_io.h"
 #include "prove_plan.h"
 #include "scalar.h"
+#include "verify_plan.h"
 #include "verify_rows.h"
 
 namespace bbp {
@@ -95,7 +96,7 @@ struct bbp_ctx {
     hipStream_t side2 = nullptr;           // second opening stream: batches too small to fill three heavy slices alternate between the two
     bbp::ProveKnobs knobs;                 // how prove calls are scheduled (prove_plan.h): read from the environment by bbp_init ...
     bbp::ProveRuleState prove_state;       // ... and what the rules remember from call to call; prover.hip plans every call from the two
-    int varbase_lanes = 65536;             // lanes the verifier's variable-base kernel is launched with (BBP_VARBASE_LANES): ~1 wave per SIMD
+    bbp::VerifyKnobs vknobs;               // how verify calls are laid out and launched (verify_plan.h): read from the environment by bbp_init
     std::vector<hipStream_t> spare_streams;  // (experiment BBP_VL_SKIP: placeholders in the hardware-queue round-robin)
     static constexpr int CALL_RING = 8;
     hipEvent_t ev_call[CALL_RING] = {};    // completion of the last CALL_RING prove calls (how many are still in flight)
@@ -113,7 +114,6 @@ struct bbp_ctx {
     hipEvent_t ev_open[PROVE_BUFS] = {}, ev_done[PROVE_BUFS] = {};
     hipEvent_t ev_entry[PROVE_BUFS] = {};  // caller's stream at entry of a prove call: out_dev is not written before it
     bool ev_done_valid[PROVE_BUFS] = {}, ev_open_valid[PROVE_BUFS] = {};
-    int verify_overlap = 1;                              // BBP_VERIFY_OVERLAP: lane 0's variable-base kernels on a side stream (no measurable difference with four lanes)
     // BBP_VERIFY_SERIAL_ACC=1: the verifier lanes' MSM accumulate launches are chained by events so that no two of them are
     // co-resident (each then runs beside the other lanes' thin front-end kernels only).  Helps two lanes that share hardware queues
     // with other streams (6.5 -> 6.3 ms per 1024); with four lanes on queues of their own free-running is faster (5.2 vs 6.05 ms): off.
@@ -122,8 +122,6 @@ struct bbp_ctx {
     hipEvent_t ev_vacc[VACC_RING] = {};
     uint32_t vacc_seq = 0;
     bool vacc_valid = false;
-    uint32_t verify_group = 0;  // BBP_VERIFY_AGGREGATE=G: bbp_verify / bbp_verify_batch (host API, hence the UDS server) check proofs in
-                                // groups of G with per-proof fallback -- same statuses, 2-3x the rate; 0 = one MSM per proof like the reference
     uint32_t seq_at_last_verify = 0;                     // prover call counter seen by the last verification (interleaving test)
     hipEvent_t ev_prep = nullptr;  // end of the last bbp_prepare_bids_dev: the next prove call's opening stage waits for it
     bool ev_prep_valid = false;

@@ -263,14 +263,12 @@ static int32_t init_body(int32_t device, bbp_ctx** out) {
     }
     BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_prep, hipEventDisableTiming));
     BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_draw, hipEventDisableTiming));
-    if (const char* e = getenv("BBP_VERIFY_OVERLAP")) ctx->verify_overlap = atoi(e) != 0;
     if (const char* e = getenv("BBP_VERIFY_SERIAL_ACC")) ctx->verify_serial_acc = atoi(e) != 0;
     for (auto& e : ctx->ev_vacc) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    if (const char* e = getenv("BBP_VERIFY_AGGREGATE")) ctx->verify_group = atoi(e) > 1 ? (uint32_t)atoi(e) : 0u;
     ctx->knobs = ProveKnobs::from_env();  // every prove-schedule knob: prove_plan.h lists the names
     // ... and the queue count the schedule is fitted to, read only: the caller's value, else the one own_hw_queues exported, else HIP's default
     if (const char* e = getenv("GPU_MAX_HW_QUEUES")) ctx->knobs.hw_queues = atoi(e) > 0 ? atoi(e) : 4;
-    if (const char* e = getenv("BBP_VARBASE_LANES")) ctx->varbase_lanes = atoi(e) < 64 ? 64 : atoi(e);
+    ctx->vknobs = VerifyKnobs::from_env();  // BBP_VARBASE_LANES, BBP_VERIFY_OVERLAP, BBP_VERIFY_AGGREGATE and the process's: verify_plan.h lists the names
     ctx->msm_knobs = MsmKnobs::from_env();  // BBP_SORT_STAGED, BBP_FOLD_HALF_FROM, BBP_MSM_SMALL and the split knobs: msm_plan.h
     for (int i = 0; i < bbp_ctx::PROVE_BUFS; i++) {
         BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_entry[i], hipEventDisableTiming));
@@ -473,7 +471,7 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                           "cooperative rng below %d proofs; verifier: %d lanes, accumulates %s, aggregate groups of %u%s\n",
                                           ctx->device, prop.name, prop.gcnArchName, prop.multiProcessorCount, prop.clockRate / 1e3, free_b / 1073741824.0,
                                           total_b / 1073741824.0, ctx->knobs.slices, ctx->knobs.tail_round, ctx->knobs.rng_coop_below, (int)bbp_ctx::VLANES,
-                                          ctx->verify_serial_acc ? "chained" : "free-running", ctx->verify_group, ctx->verify_group ? "" : " (off)");
+                                          ctx->verify_serial_acc ? "chained" : "free-running", (unsigned)ctx->vknobs.group, ctx->vknobs.group ? "" : " (off)");
         // The engine keeps four streams busy during a prove call (caller's, opening stage, two more slices) and four more for
         // verification (one per lane), out of eleven it creates; how many hardware queues they get is read when the HIP runtime
         // initialises, i.e. possibly long before bbp_init.

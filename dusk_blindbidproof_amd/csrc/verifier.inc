@@ -67,7 +67,6 @@ __device__ sc v_challenge_sc(merlin_transcript& t, const uint8_t* label, u32 lle
 // vpts words per proof: [A_I1 A_O1 S1 A_I2 A_O2 S2 | V[m] | T_1 T_3 T_4 T_5 T_6 | L_1..L_11 | R_1..R_11]   (8 words each)
 __device__ __forceinline__ u32 vnpts(u32 m) { return 6 + m + 5 + 22; }
 // vchal per proof (scalars): [u_j (11) | u_j^-1 (11) | t_x t_xb e_bl a b (5)]
-constexpr int VC_U = 0, VC_UI = 11, VC_TX = 22, VC_TXB = 23, VC_EBL = 24, VC_A = 25, VC_B = 26, VC_COUNT = 27;
 
 // rec_ver: 0 = compact 1-phase records (1121 bytes), 1 = 2-phase layout (1217 bytes)
 __global__ BBP_LANE_KERNEL void k_vparse(u32 B, u32 n_items, u32 n_cst, u32 rec_ver, const u8* __restrict__ in, u32* __restrict__ vpts, sc* __restrict__ vchal,
@@ -214,7 +213,6 @@ __global__ BBP_LANE_KERNEL void k_vtranscript(u32 B, u32 m, merlin_transcript pr
     if (!ok && status[p] == BBP_OK) status[p] = BBP_ERR_VERIFY;
 }
 
-constexpr int VS_BLK = 256;
 // wc, s, delta, generator scalars.  vs per proof: [g (2048) | h (2048) | B | B~]
 __global__ __launch_bounds__(VS_BLK) void k_vscalars(u32 n1, u32 n_cterms, u32 n_cst, u32 zstride, const u32* __restrict__ c_q,
                                                       const u32* __restrict__ c_cst, const sc* __restrict__ cst_all, const sc* __restrict__ zpow,
@@ -527,7 +525,6 @@ __global__ BBP_LANE_KERNEL void k_vfinal(u32 B, u32 nq, const ge* __restrict__ f
 //   sum_i (sum_p rho_p vs[p][i]) Base_i + sum_p sum_k rho_p sv[p][k] P[p][k] == 0
 // -- ONE 4098-term fixed-base MSM per group instead of one per proof.  A group that fails is verified again proof by proof
 // (verify_batch_agg_dev), so the per-proof statuses are those of the plain path (a bad proof passing needs a ~2^-250 accident).
-constexpr u32 GS_BLK = 256;
 __global__ __launch_bounds__(GS_BLK) void k_group_sum(u32 B, u32 G, const sc* __restrict__ vs_all, const int32_t* __restrict__ status,
                                                        sc* __restrict__ vsg) {
     const u32 i = blockIdx.x * GS_BLK + threadIdx.x, g = blockIdx.y;
@@ -603,36 +600,239 @@ static int vlane_of(const bbp_ctx* ctx, hipStream_t s) {  // a lane's own stream
     return 0;
 }
 
-// The variable-base launches of one call, in one place: verify_batch_dev and bbp_debug_varbase (the kernel tests) share the grid
-// formulas.  mixed: the _mx kernels (m, np, npa those of the call's largest row: the strides); vb2: k_varprep + k_varsum (one sum per
-// row), else k_varbase with Q lanes and Q sums per row.  one_phase: the uniform kernels' record layout (a mixed row carries its own).
+// The variable-base launches of one call, in one place: verify_batch_dev and bbp_debug_varbase (the kernel tests) share the geometry
+// (verify_plan.h varbase_geom).  mixed: the _mx kernels (m, np, npa those of the call's largest row: the strides).
 struct VarbaseLaunch {
-    bool mixed, vb2;
-    u32 B, Q, m, np, npa, one_phase;
+    bool mixed;
+    VarbaseGeom g;
     const VRow* rows;
     const u32* vpts;
     const sc *vchal, *misc, *wv;
-    ge* tab;
+    ge *tab, *var;
     u32* sp;
-    ge* var;
     int32_t* status;
 };
 static int32_t varbase_launch(bbp_ctx* ctx, const VarbaseLaunch& v, hipStream_t st, u32 agg_flag) {
-    const u32 B = v.B, Q = v.Q, m = v.m, np = v.np, npa = v.npa;
+    const VarbaseGeom& g = v.g;
+    const u32 B = g.B, Q = g.Q, m = g.m, np = g.np, npa = g.npa;
     if (v.mixed) {
-        if (v.vb2) {
-            LAUNCH(ctx, TAG_VARBASE, k_varprep_mx, cdiv(B * npa, 64), 64, st, B, npa, np, v.rows, v.vpts, v.vchal, v.misc, v.wv, m, v.tab, v.sp, v.status,
+        if (g.vb2) {
+            LAUNCH(ctx, TAG_VARBASE, k_varprep_mx, g.prep.grid, g.prep.block, st, B, npa, np, v.rows, v.vpts, v.vchal, v.misc, v.wv, m, v.tab, v.sp, v.status,
                    agg_flag);
-            LAUNCH(ctx, TAG_VARBASE, k_varsum_mx, cdiv(B, 2), 64, st, B, np, v.rows, (const ge*)v.tab, (const u32*)v.sp, v.var);
+            LAUNCH(ctx, TAG_VARBASE, k_varsum_mx, g.sum.grid, g.sum.block, st, B, np, v.rows, (const ge*)v.tab, (const u32*)v.sp, v.var);
         } else
-            LAUNCH(ctx, TAG_VARBASE, k_varbase_mx, cdiv(B * Q, 64), 64, st, B, Q, np, v.rows, v.vpts, v.vchal, v.misc, v.wv, m, v.tab, v.sp, v.var,
+            LAUNCH(ctx, TAG_VARBASE, k_varbase_mx, g.lanes.grid, g.lanes.block, st, B, Q, np, v.rows, v.vpts, v.vchal, v.misc, v.wv, m, v.tab, v.sp, v.var,
                    v.status, agg_flag);
-    } else if (v.vb2) {
-        LAUNCH(ctx, TAG_VARBASE, k_varprep, cdiv(B * npa, 64), 64, st, B, m, v.vpts, v.vchal, v.misc, v.wv, v.tab, v.sp, v.status, agg_flag, v.one_phase);
-        LAUNCH(ctx, TAG_VARBASE, k_varsum, cdiv(B, 2), 64, st, B, m, (const ge*)v.tab, (const u32*)v.sp, v.var, v.one_phase);
+    } else if (g.vb2) {
+        LAUNCH(ctx, TAG_VARBASE, k_varprep, g.prep.grid, g.prep.block, st, B, m, v.vpts, v.vchal, v.misc, v.wv, v.tab, v.sp, v.status, agg_flag, g.one_phase);
+        LAUNCH(ctx, TAG_VARBASE, k_varsum, g.sum.grid, g.sum.block, st, B, m, (const ge*)v.tab, (const u32*)v.sp, v.var, g.one_phase);
     } else
-        LAUNCH(ctx, TAG_VARBASE, k_varbase, cdiv(B * Q, 64), 64, st, B, m, Q, v.vpts, v.vchal, v.misc, v.wv, v.tab, v.sp, v.var, v.status, agg_flag,
-               v.one_phase);
+        LAUNCH(ctx, TAG_VARBASE, k_varbase, g.lanes.grid, g.lanes.block, st, B, m, Q, v.vpts, v.vchal, v.misc, v.wv, v.tab, v.sp, v.var, v.status, agg_flag,
+               g.one_phase);
+    return BBP_OK;
+}
+
+// The lane's scratch as typed pointers: made from the plan's layouts here and nowhere else.
+struct VerifyBufs {
+    u32 *vpts, *sp;
+    sc *vchal, *vs, *rblk, *vsg;  // (vsg, fixedg, varsum, gstatus: L.agg, the aggregated pass)
+    ge *tab, *var, *fixed;
+    VRow* rows;
+    u8* ns;           // a mixed call's Ns, then its version bytes
+    u32* round_of;    // a rounds call: round_of (several rounds only) ...
+    const u32* roff;  // ... and the R + 1 round offsets behind it
+    int32_t *rflag, *gstatus;
+    ge *fixedg, *varsum;
+    VerifyBufs(const VerifyPlan& p, void* misc_base, void* agg_base) {
+        u8 *b = static_cast<u8*>(misc_base), *a = static_cast<u8*>(agg_base);
+        const VerifyPlan::Misc& m = p.misc;
+        vpts = (u32*)(b + m.vpts.off), vchal = (sc*)(b + m.vchal.off), vs = (sc*)(b + m.vs.off), tab = (ge*)(b + m.tab.off), var = (ge*)(b + m.var.off);
+        fixed = (ge*)(b + m.fixed.off), sp = (u32*)(b + m.sp.off), rows = (VRow*)(b + m.rows.off), ns = b + m.ns.off;
+        round_of = (u32*)(b + m.rof.off), roff = round_of + p.rd_nof, rblk = (sc*)(b + m.rblk.off), rflag = (int32_t*)(b + m.rflag.off);
+        vsg = (sc*)(a + p.agg.vsg.off), fixedg = (ge*)(a + p.agg.fixedg.off), varsum = (ge*)(a + p.agg.varsum.off), gstatus = (int32_t*)(a + p.agg.gstatus.off);
+    }
+};
+
+// One device call while it is enqueued: what its steps share, and the steps in the order verify_batch_dev takes them.
+struct VerifyCall {
+    bbp_ctx* ctx;
+    bbp_ctx::VLane& L;
+    int lane;
+    hipStream_t s;
+    const VerifyRows& v;
+    const VerifyPlan& p;
+    const VerifyCircuit& c;
+    const BatchDev& bd;
+    const VerifyBufs& b;
+    const u8 *in_dev, *ent_dev;
+    int32_t* status_dev;
+    int ko;        // knock-out mask: 0 in the product
+    bool overlap;  // the variable-base part runs on a second stream beside the generator scalars and the MSM
+
+    // the host arrays of a mixed or rounds call go up; the kernels that turn them into row descriptors and the reduced round table
+    int32_t stage_rows() const {
+        const u32 B = p.B;
+        int32_t rc;
+        if (p.rounds) {
+            if ((rc = stage_host(ctx, L, v.round_of, 4 * (size_t)p.rd_nof, p.rd_off.data(), 4 * ((size_t)p.R + 1), b.round_of, s))) return rc;
+            LAUNCH(ctx, TAG_TRANSCRIPT, k_round_consts, p.round_consts.grid, p.round_consts.block, s, p.R, b.roff, v.rounds, b.rblk, b.rflag);
+            if (p.mixed) LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows_rounds, p.vrows.grid, p.vrows.block, s, B, (const u32*)b.round_of, b.roff, b.rows);
+        } else if (p.mixed) {
+            if ((rc = stage_host(ctx, L, v.ns, 4 * (size_t)B, v.vers, v.vers ? (size_t)B : 0, b.ns, s))) return rc;
+            LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, p.vrows.grid, p.vrows.block, s, B, (const u32*)b.ns, v.vers ? (const u8*)(b.ns + 4 * (size_t)B) : nullptr, b.rows);
+        }
+        return BBP_OK;
+    }
+
+    // parse, transcript replay, z and y^-1 powers, flatten
+    int32_t front() const {
+        const VerifyDims& d = p.d;
+        const u32 B = p.B, N = v.front_n(), m = d.m;
+        const VRow* rows = b.rows;
+        int32_t rc;
+        LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, p.fill_mimc.grid, p.fill_mimc.block, s, B, d.n_cst, ctx->mimc_c, bd.cst);
+        switch (p.front) {
+            case VerifyPlan::ROUNDS_MX:
+                LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_rounds_mx, p.parse.grid, p.parse.block, s, B, rows, (const u32*)b.round_of, b.roff, p.vstride, d.n_cst, in_dev,
+                       (const sc*)b.rblk, (const int32_t*)b.rflag, b.vpts, b.vchal, bd.cst, status_dev);
+                break;
+            case VerifyPlan::ROUND1:
+                LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_round, p.parse.grid, p.parse.block, s, B, N, d.n_cst, in_dev, (const sc*)b.rblk, (const int32_t*)b.rflag, b.vpts,
+                       b.vchal, bd.cst, status_dev);
+                break;
+            case VerifyPlan::MIXED:
+                LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_mx, p.parse.grid, p.parse.block, s, B, rows, p.vstride, d.n_cst, in_dev, b.vpts, b.vchal, bd.cst, status_dev);
+                break;
+            case VerifyPlan::UNIFORM:
+                LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse, p.parse.grid, p.parse.block, s, B, N, d.n_cst, v.rec_ver, in_dev, b.vpts, b.vchal, bd.cst, status_dev);
+                break;
+        }
+        const merlin_transcript prefix = prover_prefix();
+        // BBP_V_FENCE=1 (experiment): the transcript replay's serial waves get CUs of their own like the prover's opening kernels
+        const bool fence = ctx->vknobs.fence && ctx->knobs.serial_lds > 0;
+        if (ko & 4) {
+        } else if (p.mixed) {
+            u32 hog = lds_token(ctx);
+            if (fence && (rc = serial_lds_bytes(ctx, (const void*)k_vtranscript_mx, &hog))) return rc;
+            LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript_mx, p.transcript.grid, p.transcript.block, hog, s, B, rows, p.vstride, prefix, b.vpts, ent_dev, b.vchal,
+                       bd.misc, status_dev, p.vtw);
+        } else if (fence) {
+            u32 hog = 0;
+            if ((rc = serial_lds_bytes(ctx, (const void*)k_vtranscript, &hog))) return rc;
+            LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript, p.transcript.grid, p.transcript.block, hog, s, B, m, prefix, b.vpts, ent_dev, b.vchal, bd.misc, status_dev,
+                       p.vtw);
+        } else
+            LAUNCH(ctx, TAG_TRANSCRIPT, k_vtranscript, p.transcript.grid, p.transcript.block, s, B, m, prefix, b.vpts, ent_dev, b.vchal, bd.misc, status_dev, p.vtw);
+        if (!(ko & 32)) {
+            if (p.mixed)
+                LAUNCH(ctx, TAG_POLY, k_powers_mx, p.powers_z.grid, p.powers_z.block, s, B, p.zchunks, rows, c.ctab, bd.misc, (int)MS_Z, bd.zpow, p.zstride);
+            else
+                LAUNCH(ctx, TAG_POLY, k_powers, p.powers_z.grid, p.powers_z.block, s, B, p.zstride, bd.misc, (int)MS_Z, bd.zpow, p.zstride, 0u);
+            LAUNCH(ctx, TAG_POLY, k_powers, p.powers_yinv.grid, p.powers_yinv.block, s, B, 2048u, bd.misc, (int)MS_YINV, bd.yipow, 2048u, 1u);  // y^-i R
+        }
+        if (ko & 8) {
+        } else if (p.mixed)
+            LAUNCH(ctx, TAG_POLY, k_flatten_mx, p.flatten.grid, p.flatten.block, s, B, p.n_tgt, rows, c.ctab, bd.zpow, p.zstride, bd.wl, bd.wr, bd.wo, bd.wv, m);
+        else
+            LAUNCH(ctx, TAG_POLY, k_flatten, p.flatten.grid, p.flatten.block, s, B, p.n_tgt, d.n_mul, m, c.uniform->f_off, c.uniform->f_ent, bd.zpow, p.zstride, bd.wl,
+                   bd.wr, bd.wo, bd.wv, 2048u);
+        return BBP_OK;
+    }
+
+    int32_t varbase(hipStream_t st) const {
+        const VarbaseLaunch vb{p.mixed, p.vb, b.rows, b.vpts, b.vchal, bd.misc, bd.wv, b.tab, b.var, b.sp, status_dev};
+        return varbase_launch(ctx, vb, st, p.agg_flag);
+    }
+    // The variable-base part needs only the challenges and wV: it runs on a second stream beside the generator scalars and the
+    // MSM (BBP_VERIFY_OVERLAP=0: on the caller's stream after them) and joins before the first kernel that reads its sums / status.
+    int32_t fork_varbase() const {
+        if (!overlap) return BBP_OK;
+        hipStream_t side = ctx->lane[1];
+        BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vfork, s));
+        BBP_HIP_TRY(ctx, hipStreamWaitEvent(side, L.ev_vfork, 0));
+        if (int32_t rc = varbase(side)) return rc;
+        BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vjoin, side));
+        return BBP_OK;
+    }
+    // ... the join, or the launches themselves on the caller's stream when the call did not fork
+    int32_t join_varbase() const {
+        if (!overlap) return varbase(s);
+        BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, L.ev_vjoin, 0));
+        return BBP_OK;
+    }
+
+    int32_t scalars() const {
+        const VerifyDims& d = p.d;
+        if (ko & 16) {
+        } else if (p.mixed)
+            LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars_mx, p.vscalars.grid, p.vscalars.block, s, (const VRow*)b.rows, c.ctab, d.n_cst, p.zstride, bd.cst, bd.zpow,
+                   bd.yipow, bd.wl, bd.wr, bd.wo, b.vchal, bd.misc, bd.a, b.vs, p.agg_flag);
+        else
+            LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars, p.vscalars.grid, p.vscalars.block, s, d.n_mul, c.uniform->n_cterms, d.n_cst, p.zstride, c.uniform->c_q,
+                   c.uniform->c_cst, bd.cst, bd.zpow, bd.yipow, bd.wl, bd.wr, bd.wo, b.vchal, bd.misc, bd.a, b.vs, p.agg_flag);
+        return BBP_OK;
+    }
+
+    // G = 0: one MSM per proof, then the verdicts
+    int32_t tail_plain() const {
+        int32_t rc;
+        if (!(ko & 1) &&
+            (rc = msm_launch(ctx, p.B, VERIFY_MSM_TERMS, (const u32*)b.vs, c.idx_ver, b.fixed, s, 1, bbp_ctx::VERIFY_SLOT + lane, nullptr, nullptr, true)))
+            return rc;
+        if (!(ko & 2) && (rc = join_varbase())) return rc;  // (a knocked-out variable-base part never forked)
+        LAUNCH(ctx, TAG_VARBASE, k_vfinal, p.per_row.grid, p.per_row.block, s, p.B, p.vb.Q, b.fixed, b.var, status_dev);
+        return BBP_OK;
+    }
+    // G > 0: one weighted MSM per group; the group verdicts, the per-proof sums and the weighted scalars stay in the lane for the fallback
+    int32_t tail_groups() const {
+        const u32 B = p.B, G = p.G, ng = p.ng;
+        int32_t rc;
+        L.agg_gstatus = b.gstatus, L.agg_varsum = b.varsum, L.agg_vs = b.vs;
+        if ((rc = join_varbase())) return rc;
+        LAUNCH(ctx, TAG_VERIFY_SCALARS, k_group_sum, dim3(p.group_sum.grid, ng), p.group_sum.block, s, B, G, (const sc*)b.vs, status_dev, b.vsg);
+        if ((rc = msm_launch(ctx, ng, VERIFY_MSM_TERMS, (const u32*)b.vsg, c.idx_ver, b.fixedg, s, 1, bbp_ctx::VERIFY_SLOT + lane, nullptr, nullptr, true))) return rc;
+        LAUNCH(ctx, TAG_VARBASE, k_var_sum, p.per_row.grid, p.per_row.block, s, B, p.vb.Q, b.var, status_dev, b.varsum);
+        LAUNCH(ctx, TAG_VARBASE, k_group_final, p.group_final.grid, p.group_final.block, s, B, G, ng, b.fixedg, b.varsum, b.gstatus);
+        return BBP_OK;
+    }
+};
+
+// The circuit side and the plan of one call.  The round table's size is judged first: it needs no circuit.
+static int32_t verify_prepare(bbp_ctx* ctx, const VerifyRows& v, u32 G, VerifyCircuit& c, VerifyPlan& p) {
+    if (round_table_too_large(v)) {
+        ctx->err = "round table too large";
+        return BBP_ERR_BAD_ARG;
+    }
+    if (int32_t rc = verify_circuit(ctx, v, c)) return rc;
+    ctx->vknobs.adopt_process();  // BBP_VARBASE_V1, BBP_V_FENCE: read by the first verify call of the process
+    p = plan_verify(v, c.d, G, ctx->vknobs, ctx->knobs.tr_wave_below);
+    return BBP_OK;
+}
+
+// One pass over the rows, plain (p.G = 0) or in groups.  The steps: reserve, host arrays, front end, variable-base fork, generator
+// scalars, the plain or the aggregated tail (verify_plan.h; DESIGN.md "The plan of a verify call").
+static int32_t verify_pass(bbp_ctx* ctx, const VerifyRows& v, const VerifyCircuit& c, const VerifyPlan& p, const u8* in_dev, const u8* ent_dev,
+                           int32_t* status_dev, hipStream_t s) {
+    const int lane = vlane_of(ctx, s);
+    bbp_ctx::VLane& L = ctx->vl[lane];
+    int32_t rc;
+    BatchDev bd;
+    StreamGuard guard(ctx, s, 1 + lane);  // this verifier lane: own batch buffer, own misc scratch, own MSM scratch slot
+    if ((rc = guard.enter())) return rc;
+    // the verifier has a batch buffer of its own (index 2) and runs entirely on the caller's stream: sharing buffer 0 with the
+    // prover made every second prove call's opening stage wait for the verification in between (98 ms per prove + verify pair
+    // instead of 77)
+    if ((rc = batch_reserve(ctx, v.B, batch_sizes(c.d), bd, bbp_ctx::PROVE_BUFS + lane))) return rc;
+    if ((rc = dev_reserve(ctx, L.misc, p.misc.bytes)) || (p.G && (rc = dev_reserve(ctx, L.agg, p.agg.bytes)))) return rc;
+    const VerifyBufs b(p, L.misc.p, L.agg.p);
+    const int ko = ctx->vknobs.knocked_out();  // knock-out mask of the experiment builds (verify_plan.h); the constant 0 in the product
+    // Not beside the MSM when prove calls are interleaved with the verifications: that stream is the prover's second slice, and queueing
+    // behind this call's fork point delays the next batch's slice (measured 67.7 vs 66.3 ms per prove + verify pair).
+    const bool overlap = lane == 0 && ctx->vknobs.overlap && ctx->prove_state.calls == ctx->seq_at_last_verify && !(ko & 2);
+    ctx->seq_at_last_verify = ctx->prove_state.calls;
+    const VerifyCall k{ctx, L, lane, s, v, p, c, bd, b, in_dev, ent_dev, status_dev, ko, overlap};
+    if ((rc = k.stage_rows()) || (rc = k.front()) || (rc = k.fork_varbase()) || (rc = k.scalars()) || (rc = p.G ? k.tail_groups() : k.tail_plain())) return rc;
+    ctx->last_par = bbp_ctx::PROVE_BUFS + lane;
     return BBP_OK;
 }
 
@@ -640,204 +840,10 @@ static int32_t varbase_launch(bbp_ctx* ctx, const VarbaseLaunch& v, hipStream_t 
 // number; a rounds call takes seed and bid list from v.rounds (device memory) -- one round behind k_vparse_round, several behind
 // k_vparse_rounds_mx with every row's N taken from its round.
 int32_t verify_batch_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8* in_dev, const u8* ent_dev, int32_t* status_dev, hipStream_t s) {
-    const int lane = vlane_of(ctx, s);
-    bbp_ctx::VLane& L = ctx->vl[lane];
-    const CircuitDev* cp;
-    int32_t rc;
-    MixedCall mx;
-    const u32 B = v.B, N = v.front_n(), rec_ver = v.rec_ver;  // rec_ver: only the launch geometry below reads it (the largest count of active points)
-    const bool mixed = v.mixed_front();
-    const u32* ns = v.ns;
-    const u8* vers = v.vers;
-    const VerifyRows* rd = v.kind == VerifyRows::ROUNDS ? &v : nullptr;
-    std::vector<u32> rd_off;  // rounds: scalar offset of every round in the table
-    if (rd) {
-        rd_off.resize((size_t)rd->R + 1);
-        u64 total = 0;
-        for (u32 r = 0; r < rd->R; r++) {
-            rd_off[r] = (u32)total;
-            total += 1 + (u64)rd->round_ns[r];
-        }
-        if (total > 0x7fffffffu) {
-            ctx->err = "round table too large";
-            return BBP_ERR_BAD_ARG;
-        }
-        rd_off[rd->R] = (u32)total;
-    }
-    if (mixed) {
-        if ((rc = mixed_prepare(ctx, v, mx))) return rc;
-        cp = &mx.cmax;
-    } else if ((rc = circuit_get(ctx, N, &cp)))
-        return rc;
-    const CircuitDev& c = *cp;
-    BatchDev bd;
-    StreamGuard guard(ctx, s, 1 + lane);  // this verifier lane: own batch buffer, own misc scratch, own MSM scratch slot
-    if ((rc = guard.enter())) return rc;
-    // the verifier has a batch buffer of its own (index 2) and runs entirely on the caller's stream: sharing buffer 0 with the
-    // prover made every second prove call's opening stage wait for the verification in between (98 ms per prove + verify pair
-    // instead of 77)
-    if ((rc = batch_reserve(ctx, B, c, bd, bbp_ctx::PROVE_BUFS + lane))) return rc;
-    const u32 m = c.m, n1 = c.n_mul, np = 6 + m + 5 + 22;
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += ((bytes + 255) / 256) * 256;
-        return o;
-    };
-    size_t o_vpts = take((size_t)B * np * 32), o_vchal = take((size_t)B * VC_COUNT * 32), o_vs = take((size_t)B * 4098 * 32),
-           o_tab = take((size_t)B * np * 8 * sizeof(ge)), o_var = take((size_t)B * np * sizeof(ge)), o_fixed = take((size_t)B * sizeof(ge)),
-           o_sp = take((size_t)B * np * 32);
-    const size_t o_rows = mixed ? take((size_t)B * sizeof(VRow)) : 0, o_ns = mixed && !rd ? take((size_t)B * 5) : 0;  // Ns, then the version bytes
-    // rounds: round_of (several rounds only) and the R + 1 round offsets behind it; the reduced round block; the per-round flags
-    const u32 rd_S = rd ? rd_off[rd->R] : 0, rd_nof = rd && mixed ? B : 0;
-    const size_t o_rof = rd ? take(4 * ((size_t)rd_nof + rd->R + 1)) : 0, o_rblk = rd ? take((size_t)rd_S * sizeof(sc)) : 0,
-                 o_rflag = rd ? take(4 * (size_t)rd->R) : 0;
-    if ((rc = dev_reserve(ctx, L.misc, off))) return rc;
-    u8* base = static_cast<u8*>(L.misc.p);
-    u32* vpts = (u32*)(base + o_vpts);
-    sc* vchal = (sc*)(base + o_vchal);
-    sc* vs = (sc*)(base + o_vs);
-    ge* tab = (ge*)(base + o_tab);
-    ge* var = (ge*)(base + o_var);
-    ge* fixed = (ge*)(base + o_fixed);
-    u32* sp = (u32*)(base + o_sp);
-    const VRow* rows = (const VRow*)(base + o_rows);
-    const u32 *round_of_dev = (const u32*)(base + o_rof), *roff_dev = round_of_dev + rd_nof;
-    const sc* rblk = (const sc*)(base + o_rblk);
-    const int32_t* rflag = (const int32_t*)(base + o_rflag);
-    if (rd) {
-        if ((rc = stage_host(ctx, L, rd->round_of, 4 * (size_t)rd_nof, rd_off.data(), 4 * ((size_t)rd->R + 1), base + o_rof, s))) return rc;
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_round_consts, cdiv(rd_S, 64), 64, s, rd->R, roff_dev, rd->rounds, (sc*)(base + o_rblk), (int32_t*)(base + o_rflag));
-        if (mixed) LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows_rounds, 1, VROWS_BLK, s, B, round_of_dev, roff_dev, (VRow*)(base + o_rows));
-    } else if (mixed) {
-        if ((rc = stage_host(ctx, L, ns, 4 * (size_t)B, vers, vers ? (size_t)B : 0, base + o_ns, s))) return rc;
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_vrows, 1, VROWS_BLK, s, B, (const u32*)(base + o_ns), vers ? (const u8*)(base + o_ns + 4 * (size_t)B) : nullptr,
-               (VRow*)(base + o_rows));
-    }
-    const merlin_transcript prefix = prover_prefix();
-    // lanes per proof in k_varbase: as few as still give the launch ctx->varbase_lanes lanes (fewer lanes = more points per lane
-    // sharing one doubling chain)
-    const u32 npa = np - (rec_ver ? 0u : 3u);
-    u32 Q = (u32)ctx->varbase_lanes / B;
-    Q = Q < 1 ? 1 : Q > npa ? npa : Q;
-    // k_varbase2 (half a wavefront per proof, shared doublings, one partial sum per proof) unless BBP_VARBASE_V1=1
-    // ... for calls below 4096 proofs: above, the machine is throughput-bound either way and the first version's shorter chain wins
-    // (8192 per call: 40.8 vs 42.2 ms, aggregated 14.8 vs 16.3 ms).  BBP_VARBASE_V1=1 / 0 forces one or the other.
-    static const int vb_force = getenv("BBP_VARBASE_V1") ? (atoi(getenv("BBP_VARBASE_V1")) ? 1 : 2) : 0;
-    const bool vb2 = vb_force ? vb_force == 2 : B < 4096;
-    if (vb2) Q = 1;
-    const VarbaseLaunch vb{mixed, vb2, B, Q, m, np, npa, rec_ver ? 0u : 1u, rows, vpts, vchal, bd.misc, bd.wv, tab, sp, var, status_dev};
-    auto launch_varbase = [&](hipStream_t st, u32 agg_flag) -> int32_t { return varbase_launch(ctx, vb, st, agg_flag); };
-
-    // Knock-out mask (timing experiments, WRONG results): skip 1 the MSM, 2 k_varbase, 4 k_vtranscript, 8 k_flatten, 16 k_vscalars,
-    // 32 k_powers -- what a kernel costs the pipeline is what the step loses without it.  It changes VERDICTS (k_vfinal would judge
-    // whatever an earlier call left in the lane's buffers), so it exists only in experiment builds (tools/build_variant.py NAME
-    // -DBBP_EXPERIMENTS, read from the environment there); in the product library it is the constant 0 and the variable is not even
-    // a string in the binary (tests/test_capi_symbols.py::test_no_verdict_changing_knobs_in_the_product).
-#ifdef BBP_EXPERIMENTS
-    static const int ko = getenv("BBP_KO_VERIFY") ? atoi(getenv("BBP_KO_VERIFY")) : 0;
-#else
-    constexpr int ko = 0;
-#endif
-    LAUNCH(ctx, TAG_WITNESS, k_fill_mimc, cdiv(B * BBP_MIMC_ROUNDS, 64), 64, s, B, c.n_cst, ctx->mimc_c, bd.cst);
-    if (rd && mixed)
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_rounds_mx, cdiv(B, 64), 64, s, B, rows, round_of_dev, roff_dev, np * 8, c.n_cst, in_dev, rblk, rflag, vpts,
-               vchal, bd.cst, status_dev);
-    else if (rd)
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_round, cdiv(B, 64), 64, s, B, N, c.n_cst, in_dev, rblk, rflag, vpts, vchal, bd.cst, status_dev);
-    else if (mixed)
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse_mx, cdiv(B, 64), 64, s, B, rows, np * 8, c.n_cst, in_dev, vpts, vchal, bd.cst, status_dev);
-    else
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_vparse, cdiv(B, 64), 64, s, B, N, c.n_cst, rec_ver, in_dev, vpts, vchal, bd.cst, status_dev);
-    {
-        // BBP_V_FENCE=1 (experiment): the transcript replay's serial waves get CUs of their own like the prover's opening kernels
-        static const int fence = getenv("BBP_V_FENCE") ? atoi(getenv("BBP_V_FENCE")) : 0;
-        const u32 vtw = B <= (u32)ctx->knobs.tr_wave_below ? 1u : 0u;  // the replay of a few proofs: a wavefront each (as the prover's transcript kernels)
-        if (ko & 4) {
-        } else if (mixed) {
-            u32 hog = lds_token(ctx);
-            if (fence && ctx->knobs.serial_lds > 0 && (rc = serial_lds_bytes(ctx, (const void*)k_vtranscript_mx, &hog))) return rc;
-            LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript_mx, vtw ? B : cdiv(B, 64), 64, hog, s, B, rows, np * 8, prefix, vpts, ent_dev, vchal, bd.misc,
-                       status_dev, vtw);
-        } else if (fence && ctx->knobs.serial_lds > 0) {
-            u32 hog = 0;
-            if ((rc = serial_lds_bytes(ctx, (const void*)k_vtranscript, &hog))) return rc;
-            LAUNCH_LDS(ctx, TAG_TRANSCRIPT, k_vtranscript, vtw ? B : cdiv(B, 64), 64, hog, s, B, m, prefix, vpts, ent_dev, vchal, bd.misc, status_dev, vtw);
-        } else
-            LAUNCH(ctx, TAG_TRANSCRIPT, k_vtranscript, vtw ? B : cdiv(B, 64), 64, s, B, m, prefix, vpts, ent_dev, vchal, bd.misc, status_dev, vtw);
-    }
-    if (!(ko & 32)) {
-        if (mixed)
-            LAUNCH(ctx, TAG_POLY, k_powers_mx, cdiv(B * cdiv(c.n_cons + 1, 32), 64), 64, s, B, cdiv(c.n_cons + 1, 32), rows, mx.ctab, bd.misc, (int)MS_Z,
-                   bd.zpow, c.n_cons + 1);
-        else
-            LAUNCH(ctx, TAG_POLY, k_powers, cdiv(B * cdiv(c.n_cons + 1, 32), 64), 64, s, B, c.n_cons + 1, bd.misc, (int)MS_Z, bd.zpow, c.n_cons + 1, 0u);
-        LAUNCH(ctx, TAG_POLY, k_powers, cdiv(B * cdiv(2048, 32), 64), 64, s, B, 2048u, bd.misc, (int)MS_YINV, bd.yipow, 2048u, 1u);  // y^-i R
-    }
-    const u32 n_tgt = 3 * n1 + m;
-    if (ko & 8) {
-    } else if (mixed)
-        LAUNCH(ctx, TAG_POLY, k_flatten_mx, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, rows, mx.ctab, bd.zpow, c.n_cons + 1, bd.wl, bd.wr, bd.wo, bd.wv, m);
-    else
-        LAUNCH(ctx, TAG_POLY, k_flatten, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, c.n_cons + 1, bd.wl, bd.wr,
-               bd.wo, bd.wv, 2048u);
-    // The variable-base part needs only the challenges and wV: it runs on a second stream beside the generator scalars and the
-    // MSM (BBP_VERIFY_OVERLAP=0: on the caller's stream after them) and joins before the first kernel that reads its sums / status.
-    // Not when prove calls are interleaved with the verifications: that stream is the prover's second slice, and queueing behind
-    // this call's fork point delays the next batch's slice (measured 67.7 vs 66.3 ms per prove + verify pair).
-    const bool overlap = lane == 0 && ctx->verify_overlap && ctx->prove_state.calls == ctx->seq_at_last_verify && !(ko & 2);
-    ctx->seq_at_last_verify = ctx->prove_state.calls;
-    hipStream_t vs_stream = overlap ? ctx->lane[1] : s;
-    if (overlap) {
-        BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vfork, s));
-        BBP_HIP_TRY(ctx, hipStreamWaitEvent(vs_stream, L.ev_vfork, 0));
-        if ((rc = launch_varbase(vs_stream, G ? 1u : 0u))) return rc;
-        BBP_HIP_TRY(ctx, hipEventRecord(L.ev_vjoin, vs_stream));
-    }
-    if (ko & 16) {
-    } else if (mixed)
-        LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars_mx, B, VS_BLK, s, rows, mx.ctab, c.n_cst, c.n_cons + 1, bd.cst, bd.zpow, bd.yipow, bd.wl, bd.wr, bd.wo,
-               vchal, bd.misc, bd.a, vs, G ? 1u : 0u);
-    else
-        LAUNCH(ctx, TAG_VERIFY_SCALARS, k_vscalars, B, VS_BLK, s, n1, c.n_cterms, c.n_cst, c.n_cons + 1, c.c_q, c.c_cst, bd.cst, bd.zpow, bd.yipow,
-               bd.wl, bd.wr, bd.wo, vchal, bd.misc, bd.a, vs, G ? 1u : 0u);
-    if (G == 0) {
-        if (!(ko & 1) && (rc = msm_launch(ctx, B, 4098, (const u32*)vs, c.idx_ver, fixed, s, 1, bbp_ctx::VERIFY_SLOT + lane, nullptr, nullptr, true))) return rc;
-        if (overlap)
-            BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, L.ev_vjoin, 0));
-        else if (!(ko & 2)) {
-            if ((rc = launch_varbase(s, 0u))) return rc;
-        }
-        LAUNCH(ctx, TAG_VARBASE, k_vfinal, cdiv(B, 64), 64, s, B, Q, fixed, var, status_dev);
-    } else {
-        const u32 ng = cdiv(B, G);
-        size_t aoff = 0;
-        auto atake = [&](size_t bytes) {
-            size_t o = aoff;
-            aoff += ((bytes + 255) / 256) * 256;
-            return o;
-        };
-        const size_t o_vsg = atake((size_t)ng * 4098 * 32), o_fg = atake((size_t)ng * sizeof(ge)), o_vsum = atake((size_t)B * sizeof(ge)),
-                     o_gst = atake((size_t)ng * 4);
-        if ((rc = dev_reserve(ctx, L.agg, aoff))) return rc;
-        u8* ab = static_cast<u8*>(L.agg.p);
-        sc* vsg = (sc*)(ab + o_vsg);
-        ge* fixedg = (ge*)(ab + o_fg);
-        ge* varsum = (ge*)(ab + o_vsum);
-        L.agg_gstatus = (int32_t*)(ab + o_gst);
-        L.agg_varsum = varsum;
-        L.agg_vs = vs;
-        if (overlap)
-            BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, L.ev_vjoin, 0));
-        else if ((rc = launch_varbase(s, 1u)))
-            return rc;
-        LAUNCH(ctx, TAG_VERIFY_SCALARS, k_group_sum, dim3(cdiv(4098u, GS_BLK), ng), GS_BLK, s, B, G, (const sc*)vs, status_dev, vsg);
-        if ((rc = msm_launch(ctx, ng, 4098, (const u32*)vsg, c.idx_ver, fixedg, s, 1, bbp_ctx::VERIFY_SLOT + lane, nullptr, nullptr, true))) return rc;
-        LAUNCH(ctx, TAG_VARBASE, k_var_sum, cdiv(B, 64), 64, s, B, Q, var, status_dev, varsum);
-        LAUNCH(ctx, TAG_VARBASE, k_group_final, cdiv(ng, 64), 64, s, B, G, ng, fixedg, varsum, L.agg_gstatus);
-    }
-    ctx->last_par = bbp_ctx::PROVE_BUFS + lane;
-    return BBP_OK;
+    VerifyCircuit c;
+    VerifyPlan p;
+    const int32_t rc = verify_prepare(ctx, v, G, c, p);
+    return rc ? rc : verify_pass(ctx, v, c, p, in_dev, ent_dev, status_dev, s);
 }
 
 // Aggregated verification with exact per-proof statuses: groups of G proofs are checked with one weighted MSM each; the members
@@ -866,28 +872,21 @@ int32_t verify_batch_agg_dev(bbp_ctx* ctx, const VerifyRows& v, u32 G, const u8*
     }
     // the fallback may need one MSM per proof: have that scratch in place BEFORE anything of this call is enqueued (growing a
     // buffer frees it, and the group pass -- same scratch slot, same stream -- would still be using it)
-    if ((rc = dev_reserve(ctx, ctx->slice_sorted[bbp_ctx::VERIFY_SLOT + lane], msm_scratch_bytes(B, 4098)))) return rc;
-    const u32 ng = cdiv(B, G);
-    size_t off = 0;
-    auto take = [&](size_t bytes) {
-        size_t o = off;
-        off += ((bytes + 255) / 256) * 256;
-        return o;
-    };
-    const size_t o_fx = take((size_t)B * sizeof(ge)), o_idx = take(4 * (size_t)B);
-    if ((rc = dev_reserve(ctx, L.agg_io, off))) return rc;
-    if ((rc = verify_batch_dev(ctx, v, G, in_dev, ent_dev, status_dev, s))) return rc;
-    const CircuitDev* cp;  // idx_ver is the same list for every N: any compiled circuit of the call serves
-    if ((rc = circuit_get(ctx, v.first_n(), &cp))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->slice_sorted[bbp_ctx::VERIFY_SLOT + lane], msm_scratch_bytes(B, VERIFY_MSM_TERMS)))) return rc;
+    VerifyCircuit c;
+    VerifyPlan p;
+    if ((rc = verify_prepare(ctx, v, G, c, p)) || (rc = dev_reserve(ctx, L.agg_io, p.agg_io.bytes))) return rc;
+    if ((rc = verify_pass(ctx, v, c, p, in_dev, ent_dev, status_dev, s))) return rc;
     u8* base = static_cast<u8*>(L.agg_io.p);
-    u32* idx_dev = (u32*)(base + o_idx);
+    u32* idx_dev = (u32*)(base + p.agg_io.idx.off);
+    ge* fixed = (ge*)(base + p.agg_io.fixed.off);
     StreamGuard guard(ctx, s, 1 + lane);
     if ((rc = guard.enter())) return rc;
-    LAUNCH(ctx, TAG_VERIFY_SCALARS, k_compact_failing, 1, 1024, s, B, G, ng, (const int32_t*)L.agg_gstatus, (const int32_t*)status_dev, idx_dev,
-           L.agg_count);
-    if ((rc = msm_launch(ctx, B, 4098, (const u32*)L.agg_vs, cp->idx_ver, (ge*)(base + o_fx), s, 1, bbp_ctx::VERIFY_SLOT + lane, idx_dev, L.agg_count, true)))
+    LAUNCH(ctx, TAG_VERIFY_SCALARS, k_compact_failing, p.compact.grid, p.compact.block, s, B, G, p.ng, (const int32_t*)L.agg_gstatus,
+           (const int32_t*)status_dev, idx_dev, L.agg_count);
+    if ((rc = msm_launch(ctx, B, VERIFY_MSM_TERMS, (const u32*)L.agg_vs, c.idx_ver, fixed, s, 1, bbp_ctx::VERIFY_SLOT + lane, idx_dev, L.agg_count, true)))
         return rc;
-    LAUNCH(ctx, TAG_VARBASE, k_fallback_final, cdiv(B, 64), 64, s, (const u32*)L.agg_count, (const u32*)idx_dev, (const ge*)(base + o_fx),
+    LAUNCH(ctx, TAG_VARBASE, k_fallback_final, p.per_row.grid, p.per_row.block, s, (const u32*)L.agg_count, (const u32*)idx_dev, (const ge*)fixed,
            (const ge*)L.agg_varsum, status_dev, total_out_dev);
     if (n_fallback) {
         BBP_HIP_TRY(ctx, hipMemcpyAsync(n_fallback, L.agg_count, sizeof(u32), hipMemcpyDeviceToHost, s));
@@ -941,7 +940,8 @@ int32_t debug_varbase(bbp_ctx* ctx, u32 form, u32 B, u32 Q, u32 agg, const u32* 
     };
     if (!canonical(scal, 4 * (size_t)B) || !canonical(wv, n_wv) || !canonical(uj, 22 * (size_t)B)) return bad("a scalar is not canonical");
     // strides: the call's largest row (a uniform call: its one N), as verify_batch_dev takes them from the largest circuit
-    const u32 m = 4 + n_max, np = 6 + m + 5 + 22, npa = np - (any_two ? 0u : 3u), nq = Q;
+    const VarbaseGeom g = varbase_geom(B, 4 + n_max, any_two != 0, vb2, Q);
+    const u32 m = g.m, np = g.np, nq = g.Q;
     std::vector<u8> h_vpts((size_t)B * np * 32, 0), h_misc((size_t)B * MS_COUNT * 32, 0), h_vchal((size_t)B * VC_COUNT * 32, 0), h_wv((size_t)B * m * 32, 0);
     std::vector<VRow> h_rows(B);
     {
@@ -984,8 +984,8 @@ int32_t debug_varbase(bbp_ctx* ctx, u32 form, u32 B, u32 Q, u32 agg, const u32* 
     {
         StreamGuard guard(ctx, s, 1);
         if ((rc = guard.enter())) return rc;
-        const VarbaseLaunch vb{mixed, vb2, B, Q, m, np, npa, vers[0] ? 0u : 1u, (const VRow*)d_rows, (const u32*)d_vpts, (const sc*)d_vchal,
-                               (const sc*)d_misc, (const sc*)d_wv, (ge*)d_tab, (u32*)d_sp, (ge*)d_var, (int32_t*)d_status};
+        const VarbaseLaunch vb{mixed, g, (const VRow*)d_rows, (const u32*)d_vpts, (const sc*)d_vchal,
+                               (const sc*)d_misc, (const sc*)d_wv, (ge*)d_tab, (ge*)d_var, (u32*)d_sp, (int32_t*)d_status};
         if ((rc = varbase_launch(ctx, vb, s, agg ? 1u : 0u))) return rc;
         if ((rc = encode_launch(ctx, B * nq, (const ge*)d_var, (uint8_t*)d_enc, s))) return rc;
         BBP_HIP_TRY(ctx, hipStreamSynchronize(s));

@@ -10,11 +10,6 @@
 
 namespace bbp {
 
-struct VRow {  // one row of a mixed call: byte offset of its input row, N, m = 4 + N, record layout (0 compact, 1 two-phase)
-    u64 off;
-    u32 n;
-    uint16_t m, ver;
-};
 struct VCirc {  // what the front end needs of circuit N (ctx->vctab[N], filled when circuit N is first used by a mixed call)
     u32 n_mul, n_cons, n_cst, n_cterms;
     const u32 *f_off, *f_ent, *c_q, *c_cst;
@@ -24,7 +19,6 @@ __host__ __device__ __forceinline__ u64 vrow_bytes(u32 n, u32 ver) { return (ver
 
 // row offsets: one workgroup, a contiguous run of rows per lane, a scan over the lanes' sums.  vers (one byte per row) may be
 // null: every row is then a compact record
-constexpr u32 VROWS_BLK = 1024;
 __global__ __launch_bounds__(VROWS_BLK) void k_vrows(u32 B, const u32* __restrict__ ns, const u8* __restrict__ vers, VRow* __restrict__ rows) {
     __shared__ u64 part[VROWS_BLK];
     const u32 tid = threadIdx.x, per = (B + VROWS_BLK - 1) / VROWS_BLK;
@@ -701,16 +695,27 @@ __global__ BBP_LANE_KERNEL void k_vparse_rounds_mx(u32 B, const VRow* __restrict
 }
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
-struct MixedCall {
-    CircuitDev cmax;  // the call's strides: every size field the largest over its N; idx_ver (the same list for every N) of one of them
+// What the launches of one call take of its circuit or circuits: the counts the plan is made from (verify_plan.h), the generator
+// list of the check (the same for every N), and the tables -- the uniform front ends' one circuit, or the mixed ones' ctx->vctab.
+struct VerifyCircuit {
+    VerifyDims d;
+    const u32* idx_ver = nullptr;
+    const CircuitDev* uniform = nullptr;
     const VCirc* ctab = nullptr;
 };
-// Compiles every N of the call on first use (as the uniform calls do) and fills its entry of ctx->vctab.  The rows' Ns are host
-// memory and screened by the caller; checked again here because they index the device table.
-static int32_t mixed_prepare(bbp_ctx* ctx, const VerifyRows& v, MixedCall& mx) {
+static VerifyDims dims_of(const CircuitDev& c) { return VerifyDims{c.m, c.n_mul, c.n_cons, c.n_cst}; }
+// batch_reserve sizes a batch buffer by a circuit's counts: here those of the plan
+static CircuitDev batch_sizes(const VerifyDims& d) {
+    CircuitDev c;
+    c.n_items = d.m - 4, c.m = d.m, c.n_mul = d.n_mul, c.n_cons = d.n_cons, c.n_cst = d.n_cst;
+    return c;
+}
+// Compiles every N of the call on first use (as the uniform calls do) and fills its entry of ctx->vctab; c.d becomes the largest of
+// every count over the call's N.  The rows' Ns are host memory and screened by the caller; checked again here because they index the
+// device table.
+static int32_t mixed_prepare(bbp_ctx* ctx, const VerifyRows& v, VerifyCircuit& c) {
     if (!ctx->vctab) BBP_HIP_TRY(ctx, hipMalloc(&ctx->vctab, sizeof(VCirc) * (BBP_MAX_ITEMS + 1)));
     bool seen[BBP_MAX_ITEMS + 1] = {};
-    bool first = true;
     for (u32 i = 0; i < v.B; i++) {
         const u32 n = v.n_of(i);
         if (n == 0 || n > BBP_MAX_ITEMS) {
@@ -726,21 +731,17 @@ static int32_t mixed_prepare(bbp_ctx* ctx, const VerifyRows& v, MixedCall& mx) {
             BBP_HIP_TRY(ctx, hipMemcpy((VCirc*)ctx->vctab + n, &v, sizeof v, hipMemcpyHostToDevice));
             ctx->vctab_has[n] = 1;
         }
-        CircuitDev& c = mx.cmax;
-        if (first) {
-            c = CircuitDev();
-            c.idx_ver = cp->idx_ver;
-            first = false;
-        }
-        c.n_items = std::max(c.n_items, cp->n_items);
-        c.m = std::max(c.m, cp->m);
-        c.n_mul = std::max(c.n_mul, cp->n_mul);
-        c.n_cons = std::max(c.n_cons, cp->n_cons);
-        c.n_cst = std::max(c.n_cst, cp->n_cst);
-        c.n_cterms = std::max(c.n_cterms, cp->n_cterms);
-        c.padded = cp->padded;
+        if (!c.idx_ver) c.idx_ver = cp->idx_ver;
+        c.d.widen(dims_of(*cp));
     }
-    mx.ctab = (const VCirc*)ctx->vctab;
+    c.ctab = (const VCirc*)ctx->vctab;
+    return BBP_OK;
+}
+// the circuit side of any call: a mixed front end's table, or the one circuit of a uniform one
+static int32_t verify_circuit(bbp_ctx* ctx, const VerifyRows& v, VerifyCircuit& c) {
+    if (v.mixed_front()) return mixed_prepare(ctx, v, c);
+    if (int32_t rc = circuit_get(ctx, v.front_n(), &c.uniform)) return rc;
+    c.d = dims_of(*c.uniform), c.idx_ver = c.uniform->idx_ver;
     return BBP_OK;
 }
 

@@ -213,7 +213,9 @@ int32_t bbp_verify_batch_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const void* i
  * groups failed is decided on the device, the per-proof pass sizes itself from a device counter -- unless n_fallback is non-NULL:
  * delivering that count synchronises `stream`.  The rows of entropy_dev must be distinct and unpredictable to whoever produced
  * the proofs (the _dev forms here and the mixed-N ones below): proofs that share a row share a weight, and forged proofs whose
- * residuals add up to the identity then pass their group's check. */
+ * residuals add up to the identity then pass their group's check.
+ * Environment of the verify calls (BBP_VERIFY_AGGREGATE, BBP_VERIFY_OVERLAP, BBP_VARBASE_LANES, BBP_VARBASE_V1,
+ * BBP_HOST_CHUNK_VERIFY): one list, with defaults, clamps and when each is read, in csrc/verify_plan.h (VerifyKnobs). */
 #define BBP_AGG_GROUP_DEFAULT 32u
 int32_t bbp_verify_batch_aggregated(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, int32_t* status, uint32_t group,
                                     uint32_t* n_fallback);

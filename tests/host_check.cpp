@@ -12,6 +12,7 @@
 #include "../dusk_blindbidproof_amd/csrc/prove_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/scalar.h"
 #include "../dusk_blindbidproof_amd/csrc/scalarmul.h"
+#include "../dusk_blindbidproof_amd/csrc/verify_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/verify_rows.h"
 #include "../dusk_blindbidproof_amd/csrc/witness.h"
 
@@ -335,6 +336,64 @@ int hc_msm_knob_from_env(const char* name, const char* text, int which) {
     const MsmKnobs k = MsmKnobs::from_env();
     unsetenv(name);
     const int v[] = {k.sort_staged, k.fold_half_from, k.msm_small, (int)k.split_below, (int)k.split_target};
+    return v[which];
+}
+// The plan of one verify device call (csrc/verify_plan.h).  knobs: n_knobs (environment name, text) pairs applied over the defaults
+// through VerifyKnobs::set, clamps included; -1: a name is no verify knob.  The rows as hc_verify_rows takes them (kind 0 uniform, 1
+// mixed, 2 rounds).  dims: n_dims circuits of (m, n_mul, n_cons, n_cst), widened into one VerifyDims as mixed_prepare does.
+// geo: 0 front, 1 mixed, 2 rounds, 3 np, 4 npa, 5 Q, 6 vb2, 7 one_phase, 8 vstride, 9 zstride, 10 zchunks, 11 n_tgt, 12 vtw, 13 ng,
+// 14 agg_flag, 15 rd_S, 16 rd_nof, 17 rd_too_large, 18..21 the dims, then (grid, block) of fill_mimc, round_consts, vrows, parse,
+// transcript, powers_z, powers_yinv, flatten, vscalars, per_row, group_sum, group_final, vb.prep, vb.sum, vb.lanes, compact from 22.
+// lay: (offset, bytes) of misc's twelve regions in the order of the struct, misc.bytes; of agg's four, agg.bytes; of agg_io's two,
+// agg_io.bytes.  rd_off: R + 1 entries (rounds only).
+int hc_verify_plan(const char* const* knobs, int n_knobs, int kind, uint32_t B, uint32_t N, uint32_t rec_ver, const uint32_t* ns, const uint8_t* vers,
+                   uint32_t R, const uint32_t* round_ns, const uint32_t* round_of, const uint32_t* dims, int n_dims, uint32_t G, int tr_wave_below,
+                   int64_t* geo, uint64_t* lay, uint32_t* rd_off) {
+    VerifyKnobs k;
+    for (int i = 0; i < n_knobs; i++)
+        if (!k.set(knobs[2 * i], knobs[2 * i + 1])) return -1;
+    const VerifyRows v = kind == 0 ? VerifyRows::uniform(B, N, rec_ver) : kind == 1 ? VerifyRows::mixed(B, ns, vers) : VerifyRows::of_rounds(B, R, round_ns, nullptr, round_of);
+    VerifyDims d;
+    for (int i = 0; i < n_dims; i++) d.widen(VerifyDims{dims[4 * i], dims[4 * i + 1], dims[4 * i + 2], dims[4 * i + 3]});
+    const VerifyPlan p = plan_verify(v, d, G, k, tr_wave_below);
+    const int64_t g[22] = {p.front, p.mixed, p.rounds, p.vb.np, p.vb.npa, p.vb.Q, p.vb.vb2, p.vb.one_phase, p.vstride, p.zstride, p.zchunks, p.n_tgt, p.vtw, p.ng,
+                           p.agg_flag, p.rd_S, p.rd_nof, p.rd_too_large, p.d.m, p.d.n_mul, p.d.n_cons, p.d.n_cst};
+    memcpy(geo, g, sizeof g);
+    const VLaunch ls[16] = {p.fill_mimc, p.round_consts, p.vrows, p.parse, p.transcript, p.powers_z, p.powers_yinv, p.flatten, p.vscalars, p.per_row,
+                            p.group_sum, p.group_final, p.vb.prep, p.vb.sum, p.vb.lanes, p.compact};
+    for (int i = 0; i < 16; i++) geo[22 + 2 * i] = ls[i].grid, geo[23 + 2 * i] = ls[i].block;
+    const VerifyPlan::Misc& m = p.misc;
+    const VRegion rs[18] = {m.vpts, m.vchal, m.vs, m.tab, m.var, m.fixed, m.sp, m.rows, m.ns, m.rof, m.rblk, m.rflag,
+                            p.agg.vsg, p.agg.fixedg, p.agg.varsum, p.agg.gstatus, p.agg_io.fixed, p.agg_io.idx};
+    const size_t totals[3] = {m.bytes, p.agg.bytes, p.agg_io.bytes};
+    for (int i = 0, o = 0; i < 18; i++) {
+        lay[o++] = rs[i].off, lay[o++] = rs[i].bytes;
+        if (i == 11 || i == 15 || i == 17) lay[o++] = totals[i == 11 ? 0 : i == 15 ? 1 : 2];
+    }
+    for (size_t i = 0; i < p.rd_off.size(); i++) rd_off[i] = p.rd_off[i];
+    return 0;
+}
+// The staging layout of one host-pointer verify call (VerifyStaging).  out: 0 in_bytes, 1 tab_off, 2 tab_bytes, 3 ent_up_bytes,
+// 4 ent_drawn, 5 out_bytes, 6 fetch_bytes, 7 group, 8 n_chunks, 9 chunk, 10 row_off[B - 1]; 11, 12: sizeof(ge), sizeof(VRow).
+void hc_verify_staging(int kind, uint32_t B, uint32_t N, uint32_t rec_ver, const uint32_t* ns, const uint8_t* vers, uint32_t R, const uint32_t* round_ns,
+                       const uint32_t* round_of, uint32_t group, uint32_t ctx_group, int dev_draw, uint32_t host_chunk, uint64_t* out) {
+    const VerifyRows v = kind == 0 ? VerifyRows::uniform(B, N, rec_ver) : kind == 1 ? VerifyRows::mixed(B, ns, vers) : VerifyRows::of_rounds(B, R, round_ns, nullptr, round_of);
+    const VerifyStaging s(v, group, ctx_group, dev_draw != 0, host_chunk);
+    const uint64_t o[13] = {s.in_bytes, s.tab_off, s.tab_bytes, s.ent_up_bytes, s.ent_drawn, s.out_bytes, s.fetch_bytes, s.group, s.n_chunks, s.chunk,
+                            B ? s.row_off[B - 1] : 0, sizeof(ge), sizeof(VRow)};
+    memcpy(out, o, sizeof o);
+}
+// one knob as the engine reads it from an environment that holds name=text (the variable is set for the call only): which 0..2 the
+// context's (VerifyKnobs::from_env), 3, 4 the process's as adopt_process hands them on (read once, before the variable is set: they
+// show their defaults here), 5 the per-call chunk (host_chunk_now)
+int hc_verify_knob_from_env(const char* name, const char* text, int which) {
+    VerifyKnobs::process();
+    setenv(name, text, 1);
+    VerifyKnobs k = VerifyKnobs::from_env();
+    k.adopt_process();
+    const int chunk = (int)VerifyKnobs::host_chunk_now();
+    unsetenv(name);
+    const int v[] = {k.varbase_lanes, k.overlap, k.group, k.varbase_v1, k.fence, chunk};
     return v[which];
 }
 // msm_split over every launch of n_msm = 1..max_msm MSMs of n_terms = 1..max_terms terms under the default knobs: how many
