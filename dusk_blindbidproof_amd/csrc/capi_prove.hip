@@ -1607,7 +1607,7 @@ extern "C" int32_t bbp_debug_table(bbp_ctx* ctx, uint32_t which, const void** de
     if (kind < BBP_TABLE_IDX_AI ? N != 0 : N == 0) return BBP_ERR_BAD_ARG;  // screened here: no circuit is synthesised for a length
     if (N > BBP_MAX_ITEMS) return BBP_ERR_GENS_LEN;                          // the engine cannot prove
     return api_guard(ctx, [&]() -> int32_t {
-        if (kind >= BBP_TABLE_IDX_AI) {  // the base-index lists of circuit N (prover.hip circuit_get), compiled now if need be
+        if (kind >= BBP_TABLE_IDX_AI) {  // the base-index lists of circuit N (msm_index.h, uploaded by circuit_get), compiled now if need be
             BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
             const CircuitDev* c;
             if (int32_t rc = circuit_get(ctx, N, &c)) return rc;
@@ -1616,7 +1616,7 @@ extern "C" int32_t bbp_debug_table(bbp_ctx* ctx, uint32_t which, const void** de
                 case BBP_TABLE_IDX_AI: *dev = c->idx_ai, *bytes = 4 * (1 + 2 * n1); break;
                 case BBP_TABLE_IDX_AO: *dev = c->idx_ao, *bytes = 4 * (1 + n1); break;
                 case BBP_TABLE_IDX_S1: *dev = c->idx_s1, *bytes = 4 * (1 + 2 * n1); break;
-                case BBP_TABLE_IDX_IPA: *dev = c->idx_ipa, *bytes = 4 * (uint64_t)(11 * 2 * 2049); break;
+                case BBP_TABLE_IDX_IPA: *dev = c->idx_ipa, *bytes = 4 * (uint64_t)(IPA_ROUNDS * 2 * IPA_TERMS); break;
                 default: *dev = c->idx_ver, *bytes = 4 * 4098; break;
             }
             return BBP_OK;

@@ -17,6 +17,7 @@
 
 #include "../../include/bbp.h"
 #include "point.h"
+#include "msm_index.h"
 #include "msm_plan.h"
 #include "prove_io.h"
 #include "prove_plan.h"
@@ -48,24 +49,13 @@ static_assert(MSM_T == 128 || MSM_T == 64, "the cross-lane fold is written for o
 // IPA tail (prover.hip): from round FOLD_ROUND the folded generators are explicit points; they are materialised by a
 // composite-bucket Pippenger pass over the same row table (msm.hip, the <1> instances of k_msm_sort / k_msm_acc)
 // (FOLD_ROUND, the first tail round, is prove_plan.h's: the plan of a prove call names it)
-constexpr int FOLD_CLS = 2048 >> (FOLD_ROUND - 1);  // 32 folded generators per side
+// (FOLD_CLS, the folded generators per side, is batch_layout.h's: the batch buffer holds them)
 constexpr int FOLD_NAF = 9;                // width-9 NAF: odd digits |d| < 256
 constexpr int FOLD_W = 29;                 // most digits per scalar
 constexpr int FOLD_M = 128;                // buckets per class
 constexpr int FOLD_K = FOLD_CLS * FOLD_M;  // 4096 composite buckets
 static_assert(SMALL_W == FOLD_W, "split MSMs recode at the generator-fold pass's width");
-// Extra table bases (internal, after the 4098 public ones): PAD_BASE0 + N - 1 = sum_{k = 418 + 3N}^{1023} H[k], the generators
-// that the first IPA round multiplies by ONE common scalar (the zero-padded multipliers n1 = 1442 + 3N .. 2047 contribute
-// b[i] h[i - 1024] = -y^1024 for every i): 582 table-row walks become one (prover.hip k_ipa_round, circuit_get).
-constexpr int PAD_BASES = 202;                             // one per list length N = 1..202
-constexpr unsigned PAD_BASE0 = BBP_NUM_BASES;
-// Merged bases for multiplier inputs that always carry the same value (the MiMC rounds wire a to L_i, R_i, R_{i+1} and a^2 to
-// L_{i+1}, L_{i+2}, R_{i+2}: circuit_get): MRG1(i) = G[i] + H[i] + H[i+1], MRG2(i) = G[i] + G[i+1] + H[i+1], i = 0..2046 --
-// A_I1 then needs one term where it had three.
-constexpr unsigned MRG_BASE0 = PAD_BASE0 + PAD_BASES;
-constexpr int MRG_BASES = 2 * 2048;
-constexpr unsigned MSM_SKIP_BASE = 0xffffffffu;            // index-list entry: this term's scalar rides on another term's merged base
-constexpr unsigned TAB_BASES = BBP_NUM_BASES + PAD_BASES + MRG_BASES;  // bases with rows in ptable
+// (the extra table bases behind the public ones -- PAD_BASE0, MRG_BASE0, MSM_SKIP_BASE, TAB_BASES -- are msm_index.h's: the index lists name them)
 constexpr int GE_WORDS = sizeof(ge) / 4;  // 40: a point in registers / LDS / scratch
 
 struct DevBuf {

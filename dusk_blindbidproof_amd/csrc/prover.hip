@@ -255,16 +255,15 @@ __global__ BBP_LANE_KERNEL BBP_ENCODE_ATTR void k_encode_strided(u32 count, u32 
 // ---------------------------------------------------------------------------------------------------------------
 // K7: transcript stages (one lane per proof)
 // ---------------------------------------------------------------------------------------------------------------
-// enc layout per proof (words): V[m] | A_I1 A_O1 S1 | T_1 T_3 T_4 T_5 T_6 | (L_j R_j) x 11
-__device__ __forceinline__ u32 enc_stride_words(u32 m) { return (m + 8 + 22) * 8; }
+// (the enc block of a proof -- enc_words, enc_V, enc_A, enc_T, enc_LR -- is batch_layout.h's)
 
 __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& prefix, const u32* __restrict__ enc, const u8* __restrict__ entropy,
                              const sc* __restrict__ vb_all, u32* __restrict__ raw, merlin_transcript* __restrict__ tr_out,
                              merlin_transcript* __restrict__ rng_out, bool coop, u32 wave) {
     merlin_transcript t = prefix;  // Transcript::new(b"BlindBidProofGadget") + r1cs_domain_sep (A.4)
     t.wave = wave;
-    const u32* e = enc + (size_t)p * enc_stride_words(m);
-    for (u32 i = 0; i < m; i++) tr_append_words(t, LBL("V"), e + 8 * i);
+    const u32* e = enc + (size_t)p * enc_words(m);
+    for (u32 i = 0; i < m; i++) tr_append_words(t, LBL("V"), e + enc_V(i));
     merlin_append_u64(t, LBL("m"), (u64)m);
     // TranscriptRng: rekey with every v_blinding in commit order, then 32 bytes of external entropy (A.5 step 2)
     merlin_transcript r = t;
@@ -618,7 +617,7 @@ __global__ BBP_LANE_KERNEL void k_tr_yz(u32 B, u32 m, const u32* __restrict__ en
     if (p >= B) return;
     merlin_transcript t = tr[p];
     t.wave = wave;
-    const u32* e = enc + (size_t)p * enc_stride_words(m) + 8 * m;
+    const u32* e = enc + (size_t)p * enc_words(m) + enc_A(m);
     tr_append_words(t, LBL("A_I1"), e);
     tr_append_words(t, LBL("A_O1"), e + 8);
     tr_append_words(t, LBL("S1"), e + 16);
@@ -780,7 +779,7 @@ __global__ __launch_bounds__(POLY_BLK) void k_poly(u32 n1, const sc* __restrict_
     const sc* sL = s1 + (size_t)p * (1 + 2 * n1) + 1;
     const sc* sR = sL + n1;
     const sc *WL = wl + (size_t)p * wstride, *WR = wr + (size_t)p * wstride, *WO = wo + (size_t)p * wstride;
-    const sc *Y = ypow + (size_t)p * 2049, *YI = yipow + (size_t)p * 2048;
+    const sc *Y = ypow + (size_t)p * IPA_TERMS, *YI = yipow + (size_t)p * IPA_N;
     sc t[6];
 #pragma unroll
     for (int k = 0; k < 6; k++) t[k] = sc_zero();
@@ -839,7 +838,7 @@ __global__ BBP_LANE_KERNEL void k_commit_T_split(u32 B, const sc* __restrict__ m
     ge acc = comb_mul_add_part(ge_identity(), comb, ld_sc(&ms[MS_T1 + slot[k]]), q);
     acc = comb_mul_add_part(acc, comb + 64 * 8, ld_sc(&ms[MS_TB1 + slot[k]]), q);
     acc = commit_group_sum(acc);
-    if (q == 0 && g < B * 5) pts[(size_t)p * pts_stride + m + 3 + k] = acc;
+    if (q == 0 && g < B * 5) pts[(size_t)p * pts_stride + pts_T(m) + k] = acc;
 }
 __global__ BBP_LANE_KERNEL void k_commit_T(u32 B, const sc* __restrict__ misc, const niels_packed* __restrict__ comb, ge* __restrict__ pts, u32 pts_stride, u32 m) {
     BBP_THIN_PRIO();
@@ -850,7 +849,7 @@ __global__ BBP_LANE_KERNEL void k_commit_T(u32 B, const sc* __restrict__ misc, c
     const sc* ms = misc + (size_t)p * MS_COUNT;
     ge acc = comb_mul_add(ge_identity(), comb, ld_sc(&ms[MS_T1 + slot[k]]));
     acc = comb_mul_add(acc, comb + 64 * 8, ld_sc(&ms[MS_TB1 + slot[k]]));
-    pts[(size_t)p * pts_stride + m + 3 + k] = acc;
+    pts[(size_t)p * pts_stride + pts_T(m) + k] = acc;
 }
 
 __global__ BBP_LANE_KERNEL void k_tr_ux(u32 B, u32 m, u32 n1, const u32* __restrict__ enc, const sc* __restrict__ wv, const sc* __restrict__ vb,
@@ -862,7 +861,7 @@ __global__ BBP_LANE_KERNEL void k_tr_ux(u32 B, u32 m, u32 n1, const u32* __restr
     if (p >= B) return;
     merlin_transcript t = tr[p];
     t.wave = wave;
-    const u32* e = enc + (size_t)p * enc_stride_words(m) + 8 * (m + 3);
+    const u32* e = enc + (size_t)p * enc_words(m) + enc_T(m);
     tr_append_words(t, LBL("T_1"), e);
     tr_append_words(t, LBL("T_3"), e + 8);
     tr_append_words(t, LBL("T_4"), e + 16);
@@ -888,7 +887,7 @@ __global__ BBP_LANE_KERNEL void k_tr_ux(u32 B, u32 m, u32 n1, const u32* __restr
     sc w = tr_challenge_sc(t, LBL("w"));
     // InnerProductProof::create opens with its domain separator (A.6)
     merlin_append(t, LBL("dom-sep"), LBL("ipp v1"));
-    merlin_append_u64(t, LBL("n"), 2048);
+    merlin_append_u64(t, LBL("n"), IPA_N);
     st_sc(&ms[MS_U], u);
     st_sc(&ms[MS_X], x);
     st_sc(&ms[MS_W], w);
@@ -905,7 +904,7 @@ __global__ void k_lrvec(u32 B, u32 n1, const sc* __restrict__ l1, const sc* __re
                         const sc* __restrict__ misc, sc* __restrict__ a, sc* __restrict__ b, sc* __restrict__ g, sc* __restrict__ h) {
     BBP_THIN_PRIO();
     u32 t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= B * 2048) return;
+    if (t >= B * IPA_N) return;
     u32 p = t >> 11, i = t & 2047;
     const sc* ms = misc + (size_t)p * MS_COUNT;
     sc x = ld_sc(&ms[MS_X]);
@@ -920,15 +919,15 @@ __global__ void k_lrvec(u32 B, u32 n1, const sc* __restrict__ l1, const sc* __re
         gv = sc_one();
     } else {
         av = sc_zero();
-        bv = sc_neg(ld_sc(&ypow[(size_t)p * 2049 + i]));
+        bv = sc_neg(ld_sc(&ypow[(size_t)p * IPA_TERMS + i]));
         gv = ld_sc(&ms[MS_U]);
     }
-    st_sc(&a[(size_t)p * 2048 + i], av);
-    st_sc(&b[(size_t)p * 2048 + i], bv);
+    st_sc(&a[(size_t)p * IPA_N + i], av);
+    st_sc(&b[(size_t)p * IPA_N + i], bv);
     // the factor vectors live in Montgomery form (x R mod l) through the MSM rounds: every use is a product with a plain
     // scalar, which then costs ONE Montgomery multiplication instead of two (k_ipa_round)
-    st_sc(&g[(size_t)p * 2048 + i], sc_to_mont(gv));
-    st_sc(&h[(size_t)p * 2048 + i], sc_montmul(sc_to_mont(ld_sc(&yipow[(size_t)p * 2048 + i])), sc_to_mont(gv)));
+    st_sc(&g[(size_t)p * IPA_N + i], sc_to_mont(gv));
+    st_sc(&h[(size_t)p * IPA_N + i], sc_montmul(sc_to_mont(ld_sc(&yipow[(size_t)p * IPA_N + i])), sc_to_mont(gv)));
 }
 
 // Fiat-Shamir step between IPA rounds: absorb L_j, R_j (j = prev_round), draw u_j, invert it.  One lane per proof.
@@ -940,7 +939,7 @@ __global__ BBP_LANE_KERNEL void k_ipa_challenge(u32 B, u32 prev_round, u32 m, co
     if (p >= B) return;
     merlin_transcript t = tr[p];
     t.wave = wave;
-    const u32* e = enc + (size_t)p * enc_stride_words(m) + 8 * (m + 8) + 16 * (prev_round - 1);
+    const u32* e = enc + (size_t)p * enc_words(m) + enc_LR(m, prev_round);
     tr_append_words(t, LBL("L"), e);
     tr_append_words(t, LBL("R"), e + 8);
     sc u = tr_challenge_sc(t, LBL("u"));
@@ -962,7 +961,7 @@ __global__ __launch_bounds__(BLK) void k_ipa_round(u32 round, u32 n1, sc* __rest
     __shared__ u32 lds[2 * 8 * BLK];
     const u32 p = blockIdx.x, tid = threadIdx.x;
     sc* ms = misc + (size_t)p * MS_COUNT;
-    sc *a = a_all + (size_t)p * 2048, *b = b_all + (size_t)p * 2048, *g = g_all + (size_t)p * 2048, *h = h_all + (size_t)p * 2048;
+    sc *a = a_all + (size_t)p * IPA_N, *b = b_all + (size_t)p * IPA_N, *g = g_all + (size_t)p * IPA_N, *h = h_all + (size_t)p * IPA_N;
     const u32 n = 1024u >> (round - 1);
     if (round > 1) {
         // u, u^-1 of the previous round were produced by k_ipa_challenge (one lane per proof, its own tiny launch, so that
@@ -979,7 +978,7 @@ __global__ __launch_bounds__(BLK) void k_ipa_round(u32 round, u32 n1, sc* __rest
         // generator factors (Montgomery form in, Montgomery form out): low half of each 2*n2 block took u^-1 (G) / u (H); high
         // half the opposite.  The tail preparation call hands them to the generator-fold MSM, which needs plain scalars.
         const bool to_plain = lr_all == nullptr;
-        for (u32 k = tid; k < 2048; k += BLK) {
+        for (u32 k = tid; k < IPA_N; k += BLK) {
             bool hi = (k & (2 * n2 - 1)) >= n2;
             sc gk = sc_montmul(ld_sc(&g[k]), hi ? u : ui), hk = sc_montmul(ld_sc(&h[k]), hi ? ui : u);
             st_sc(&g[k], to_plain ? sc_from_mont(gk) : gk);
@@ -989,10 +988,10 @@ __global__ __launch_bounds__(BLK) void k_ipa_round(u32 round, u32 n1, sc* __rest
     }
     if (lr_all == nullptr) return;  // tail preparation: only the fold of a, b and the factor update were wanted
     // scalars of L and R; c_L = <a_lo, b_hi>, c_R = <a_hi, b_lo>
-    sc* L = lr_all + (size_t)p * 2 * 2049;
-    sc* R = L + 2049;
+    sc* L = lr_all + (size_t)p * 2 * IPA_TERMS;
+    sc* R = L + IPA_TERMS;
     sc c[2] = {sc_zero(), sc_zero()};
-    for (u32 k = tid; k < 2048; k += BLK) {
+    for (u32 k = tid; k < IPA_N; k += BLK) {
         const u32 i = k & (2 * n - 1), blk = k / (2 * n);
         const bool hi = i >= n;
         const u32 io = hi ? i - n : i, rank = blk * n + io;
@@ -1003,7 +1002,7 @@ __global__ __launch_bounds__(BLK) void k_ipa_round(u32 round, u32 n1, sc* __rest
         } else {
             st_sc(&R[rank], sc_montmul(ld_sc(&a[n + io]), gk));        // a_R[io] * G_L
             // b_R[io] * H_L.  Round 1: for the zero-padded multipliers i = n + io >= n1 this product is -y^1024 whatever io is;
-            // only the first of them keeps it, on the precomputed sum of those H's (PAD_BASE0, circuit_get), the rest are zero
+            // only the first of them keeps it, on the precomputed sum of those H's (PAD_BASE0, msm_index.h index_ipa), the rest are zero
             const bool dup = round == 1 && n + io > n1;
             st_sc(&L[1024 + rank], dup ? sc_zero() : sc_montmul(ld_sc(&b[n + io]), hk));
         }
@@ -1016,8 +1015,8 @@ __global__ __launch_bounds__(BLK) void k_ipa_round(u32 round, u32 n1, sc* __rest
     block_sum_sc<2, BLK>(c, lds);
     if (tid == 0) {
         const sc wr = sc_montmul(sc_to_mont(ld_sc(&ms[MS_W])), sc_rr());  // w R^2: (c R^-1) * (w R^2) * R^-1 = c w.  Q = w B, c * Q = (c w) B
-        st_sc(&L[2048], sc_montmul(c[0], wr));
-        st_sc(&R[2048], sc_montmul(c[1], wr));
+        st_sc(&L[IPA_N], sc_montmul(c[0], wr));
+        st_sc(&R[IPA_N], sc_montmul(c[1], wr));
     }
 }
 
@@ -1057,8 +1056,8 @@ __global__ void k_tail_init(u32 B, sc* __restrict__ g_all, sc* __restrict__ h_al
     u32 t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= B * FOLD_CLS) return;
     const u32 p = t / FOLD_CLS, k = t % FOLD_CLS;
-    st_sc(&g_all[(size_t)p * 2048 + k], sc_one());
-    st_sc(&h_all[(size_t)p * 2048 + k], sc_one());
+    st_sc(&g_all[(size_t)p * IPA_N + k], sc_one());
+    st_sc(&h_all[(size_t)p * IPA_N + k], sc_one());
 }
 
 // L and R of a tail round (half length n <= 16) over the 32 + 32 materialised generators: one lane per (side, term), 33 terms a side.
@@ -1096,11 +1095,11 @@ __global__ __launch_bounds__(TAIL_BLK) void k_tail_lr(u32 B, u32 n, u32 prev_rou
     const u32 side = l / TAIL_LS, rem = l % TAIL_LS;        // lane `rem` of its side: share rem % TAIL_SPLIT of term j
     const u32 j = TAIL_MERGE == 2 ? 2 * rem : rem / TAIL_SPLIT, share = rem % TAIL_SPLIT;  // j: 0..15 G terms, 16..31 H terms, 32 the B term (merged: terms j and j + 1)
     const size_t po = live ? (size_t)p : 0;
-    sc *a = a_all + po * 2048, *b = b_all + po * 2048, *gg = g_all + po * 2048, *hh = h_all + po * 2048;
+    sc *a = a_all + po * IPA_N, *b = b_all + po * IPA_N, *gg = g_all + po * IPA_N, *hh = h_all + po * IPA_N;
     if (prev_round) {
         if (live && l == 0) {
             merlin_transcript t = tr[p];
-            const u32* e = enc + (size_t)p * enc_stride_words(m) + 8 * (m + 8) + 16 * (prev_round - 1);
+            const u32* e = enc + (size_t)p * enc_words(m) + enc_LR(m, prev_round);
             tr_append_words(t, LBL("L"), e);
             tr_append_words(t, LBL("R"), e + 8);
             const sc u = tr_challenge_sc(t, LBL("u")), ui = sc_invert(u);
@@ -1207,12 +1206,12 @@ __global__ BBP_LANE_KERNEL void k_ipa_final(u32 B, u32 m, const u32* __restrict_
     if (p >= B) return;
     merlin_transcript t = tr[p];
     t.wave = wave;
-    const u32* e = enc + (size_t)p * enc_stride_words(m) + 8 * (m + 8) + 16 * 10;
+    const u32* e = enc + (size_t)p * enc_words(m) + enc_LR(m, IPA_ROUNDS);
     tr_append_words(t, LBL("L"), e);
     tr_append_words(t, LBL("R"), e + 8);
     sc u = tr_challenge_sc(t, LBL("u"));
     sc ui = sc_invert(u);
-    const sc *a = a_all + (size_t)p * 2048, *b = b_all + (size_t)p * 2048;
+    const sc *a = a_all + (size_t)p * IPA_N, *b = b_all + (size_t)p * IPA_N;
     sc* ms = misc + (size_t)p * MS_COUNT;
     st_sc(&ms[MS_A0], sc_add(sc_mul(ld_sc(&a[0]), u), sc_mul(ui, ld_sc(&a[1]))));
     st_sc(&ms[MS_B0], sc_add(sc_mul(ld_sc(&b[0]), ui), sc_mul(u, ld_sc(&b[1]))));
@@ -1225,7 +1224,7 @@ __global__ BBP_LANE_KERNEL void k_assemble(u32 B, u32 m, const u32* __restrict__
     BBP_THIN_PRIO();
     u32 p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= B) return;
-    const u32* e = enc + (size_t)p * enc_stride_words(m);
+    const u32* e = enc + (size_t)p * enc_words(m);
     const sc* ms = misc + (size_t)p * MS_COUNT;
     u8* o = out + (size_t)p * (BBP_R1CS_PROOF_BYTES + 32 * (size_t)m);
     *o++ = 0;  // ONE_PHASE_COMMITMENTS
@@ -1233,15 +1232,15 @@ __global__ BBP_LANE_KERNEL void k_assemble(u32 B, u32 m, const u32* __restrict__
         words_to_bytes32(o, w);
         o += 32;
     };
-    for (u32 i = 0; i < 8; i++) put(e + 8 * (m + i));  // A_I1 A_O1 S1 T_1 T_3 T_4 T_5 T_6
+    for (u32 i = 0; i < 8; i++) put(e + enc_rec(m + i));  // A_I1 A_O1 S1 T_1 T_3 T_4 T_5 T_6
     sc s;
     s = ld_sc(&ms[MS_TX]); put(s.v);
     s = ld_sc(&ms[MS_TXB]); put(s.v);
     s = ld_sc(&ms[MS_EBL]); put(s.v);
-    for (u32 j = 0; j < 22; j++) put(e + 8 * (m + 8 + j));  // L_1 R_1 ... L_11 R_11
+    for (u32 j = 0; j < 22; j++) put(e + enc_rec(m + 8 + j));  // L_1 R_1 ... L_11 R_11
     s = ld_sc(&ms[MS_A0]); put(s.v);
     s = ld_sc(&ms[MS_B0]); put(s.v);
-    for (u32 i = 0; i < m; i++) put(e + 8 * i);
+    for (u32 i = 0; i < m; i++) put(e + enc_V(i));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1264,7 +1263,7 @@ int32_t circuit_get(bbp_ctx* ctx, uint32_t n_items, const CircuitDev** out) {
     }
     fault_injected("compile");
     circuit::Compiled c = circuit::compile(n_items);
-    if (c.padded != 2048) {
+    if (c.padded != IPA_N) {
         ctx->err = "circuit does not pad to 2048 multipliers";
         return BBP_ERR_GENS_LEN;
     }
@@ -1285,104 +1284,21 @@ int32_t circuit_get(bbp_ctx* ctx, uint32_t n_items, const CircuitDev** out) {
         (rc = upload(ctx, c.f_off, &d->f_off)) || (rc = upload(ctx, c.f_ent, &d->f_ent)) || (rc = upload(ctx, c.c_q, &d->c_q)) ||
         (rc = upload(ctx, c.c_cst, &d->c_cst)))
         return rc;
-    std::vector<u32> ai, ao, ipa, ver;
-    ai.push_back(BBP_BASE_BBLIND);
-    ao.push_back(BBP_BASE_BBLIND);
-    for (u32 i = 0; i < c.n_mul; i++) ai.push_back(BBP_BASE_G0 + i), ao.push_back(BBP_BASE_G0 + i);
-    for (u32 i = 0; i < c.n_mul; i++) ai.push_back(BBP_BASE_H0 + i);
-    const std::vector<u32> s1 = ai;
-    // Multiplier inputs wired to the SAME linear combination always carry the same scalar: where three of them sit as
-    // {L_i, R_i, R_i+1} or {L_i, L_i+1, R_i+1} (every MiMC round has one of each: a and a^2) the first keeps the scalar on the
-    // merged base G/H sum and the other two are skipped by the sort kernel -- 1440 of A_I1's 2933 terms.
-    {
-        const u32 n = c.n_mul;
-        auto side = [&](u32 s) {  // s < n: left input of multiplier s, else right input of multiplier s - n
-            const bool right = s >= n;
-            const u32 i = right ? s - n : s;
-            const u32 b = right ? c.w_roff[i] : c.w_loff[i], e = right ? c.w_loff[i + 1] : c.w_roff[i];
-            return std::vector<u32>(c.w_terms.begin() + b, c.w_terms.begin() + e);
-        };
-        auto same = [&](u32 a, u32 b, u32 d) { return side(a) == side(b) && side(a) == side(d); };
-        std::vector<char> used(2 * n, 0);
-        for (u32 i = 0; i + 1 < n; i++) {
-            const u32 Li = i, Ri = n + i, Li1 = i + 1, Ri1 = n + i + 1;
-            if (!used[Li] && !used[Ri] && !used[Ri1] && same(Li, Ri, Ri1)) {
-                ai[1 + Li] = MRG_BASE0 + i;
-                ai[1 + Ri] = ai[1 + Ri1] = MSM_SKIP_BASE;
-                used[Li] = used[Ri] = used[Ri1] = 1;
-            } else if (!used[Li] && !used[Li1] && !used[Ri1] && same(Li, Li1, Ri1)) {
-                ai[1 + Li] = MRG_BASE0 + 2048 + i;
-                ai[1 + Li1] = ai[1 + Ri1] = MSM_SKIP_BASE;
-                used[Li] = used[Li1] = used[Ri1] = 1;
-            }
-        }
-        d->n_ai_terms = 0;
-        for (u32 v : ai) d->n_ai_terms += v != MSM_SKIP_BASE;
-    }
-    // IPA round r (1-based), n = 1024 >> (r-1): term rank = blk*n + io of block blk = k / 2n
-    for (u32 r = 1; r <= 11; r++) {
-        const u32 n = 1024u >> (r - 1);
-        std::vector<u32> L(2049), R(2049);
-        for (u32 rank = 0; rank < 1024; rank++) {
-            u32 blk = rank / n, io = rank % n;
-            u32 k_lo = blk * 2 * n + io, k_hi = k_lo + n;
-            L[rank] = BBP_BASE_G0 + k_hi;
-            L[1024 + rank] = BBP_BASE_H0 + k_lo;
-            R[rank] = BBP_BASE_G0 + k_lo;
-            R[1024 + rank] = BBP_BASE_H0 + k_hi;
-        }
-        L[2048] = R[2048] = BBP_BASE_B;
-        // round 1: the padded multipliers' terms of L share one scalar; their first slot carries it on the range-sum base, the
-        // others carry zero (k_ipa_round)
-        if (r == 1 && c.n_mul < 2048) L[1024 + (c.n_mul - 1024)] = PAD_BASE0 + n_items - 1;
-        ipa.insert(ipa.end(), L.begin(), L.end());
-        ipa.insert(ipa.end(), R.begin(), R.end());
-    }
-    for (u32 i = 0; i < 2048; i++) ver.push_back(BBP_BASE_G0 + i);
-    for (u32 i = 0; i < 2048; i++) ver.push_back(BBP_BASE_H0 + i);
-    ver.push_back(BBP_BASE_B);
-    ver.push_back(BBP_BASE_BBLIND);
-    if ((rc = upload(ctx, ai, &d->idx_ai)) || (rc = upload(ctx, s1, &d->idx_s1)) || (rc = upload(ctx, ao, &d->idx_ao)) || (rc = upload(ctx, ipa, &d->idx_ipa)) ||
-        (rc = upload(ctx, ver, &d->idx_ver)))
+    // the base-index lists of the MSMs (msm_index.h)
+    if ((rc = upload(ctx, index_ai(c, &d->n_ai_terms), &d->idx_ai)) || (rc = upload(ctx, index_s1(c), &d->idx_s1)) || (rc = upload(ctx, index_ao(c), &d->idx_ao)) ||
+        (rc = upload(ctx, index_ipa(c), &d->idx_ipa)) || (rc = upload(ctx, index_ver(), &d->idx_ver)))
         return rc;
     ctx->circuits[n_items] = d;
     *out = d;
     return BBP_OK;
 }
 
-int32_t batch_reserve(bbp_ctx* ctx, uint32_t B, const CircuitDev& c, BatchDev& bd, int parity) {
-    const size_t n1 = c.n_mul, m = c.m;
-    DevBuf& buf = ctx->batch[parity];  // 0..2: the prover's buffers in rotation, 3 (VERIFY_BUF): the verifier's
-    size_t off = 0;
-    auto take = [&](size_t bytes_per_proof) {
-        size_t o = off;
-        off += ((bytes_per_proof * B + 255) / 256) * 256;
-        return o;
-    };
-    const size_t S = sizeof(sc);
-    size_t o_cst = take(c.n_cst * S), o_v = take(m * S), o_vb = take(m * S), o_ai1 = take((1 + 2 * n1) * S), o_ao1 = take((1 + n1) * S),
-           o_s1 = take((1 + 2 * n1) * S), o_tr = take(sizeof(merlin_transcript)), o_rng = take(sizeof(merlin_transcript)),
-           o_misc = take(MS_COUNT * S), o_zpow = take(((size_t)c.n_cons + 1) * S), o_ypow = take(2049 * S), o_yipow = take(2048 * S),
-           o_wl = take(2048 * S), o_wr = take(2048 * S), o_wo = take(2048 * S), o_wv = take(m * S), o_l1 = take(n1 * S), o_r0 = take(n1 * S),
-           o_r1 = take(n1 * S), o_r3 = take(n1 * S), o_a = take(2048 * S), o_b = take(2048 * S), o_g = take(2048 * S), o_h = take(2048 * S),
-           o_lr = take(2 * 2049 * S), o_pts = take((m + 8) * sizeof(ge)), o_lrpts = take(2 * sizeof(ge)), o_fpts = take(2 * FOLD_CLS * sizeof(ge)),
-           o_enc = take((m + 8 + 22) * 32), o_ent = take(32 * m + 32);
-    int32_t rc = dev_reserve(ctx, buf, off);
-    if (rc) return rc;
-    u8* base = static_cast<u8*>(buf.p);
-    bd.B = B;
-    bd.n_items = c.n_items;
-    bd.m = c.m;
-    bd.n1 = c.n_mul;
-    bd.n_cons = c.n_cons;
-    bd.cst = (sc*)(base + o_cst); bd.v = (sc*)(base + o_v); bd.vb = (sc*)(base + o_vb); bd.ai1 = (sc*)(base + o_ai1);
-    bd.ao1 = (sc*)(base + o_ao1); bd.s1 = (sc*)(base + o_s1); bd.tr = (merlin_transcript*)(base + o_tr);
-    bd.rng = (merlin_transcript*)(base + o_rng); bd.misc = (sc*)(base + o_misc); bd.zpow = (sc*)(base + o_zpow);
-    bd.ypow = (sc*)(base + o_ypow); bd.yipow = (sc*)(base + o_yipow); bd.wl = (sc*)(base + o_wl); bd.wr = (sc*)(base + o_wr);
-    bd.wo = (sc*)(base + o_wo); bd.wv = (sc*)(base + o_wv); bd.l1 = (sc*)(base + o_l1); bd.r0 = (sc*)(base + o_r0);
-    bd.r1 = (sc*)(base + o_r1); bd.r3 = (sc*)(base + o_r3); bd.a = (sc*)(base + o_a); bd.b = (sc*)(base + o_b); bd.g = (sc*)(base + o_g);
-    bd.h = (sc*)(base + o_h); bd.lr = (sc*)(base + o_lr); bd.pts = (ge*)(base + o_pts); bd.lrpts = (ge*)(base + o_lrpts); bd.fpts = (ge*)(base + o_fpts);
-    bd.enc = (u32*)(base + o_enc); bd.entropy = base + o_ent;
+// the batch buffer `buf` of the context (0 .. PROVE_BUFS - 1: the prover's, in rotation; PROVE_BUFS + lane: a verifier lane's) grown to
+// B proofs of dimensions d and carved (batch_layout.h)
+int32_t batch_reserve(bbp_ctx* ctx, uint32_t B, const BatchDims& d, BatchDev& bd, int buf) {
+    const BatchOffsets o = batch_offsets(B, d);
+    if (int32_t rc = dev_reserve(ctx, ctx->batch[buf], o.bytes)) return rc;
+    bd = batch_carve(static_cast<u8*>(ctx->batch[buf].p), o);
     return BBP_OK;
 }
 
@@ -1419,7 +1335,6 @@ int32_t tail_btab_build(bbp_ctx* ctx) {  // called once from bbp_init: the table
 
 size_t tail_btab_bytes() { return sizeof(ge) * TAIL_TAB; }
 
-static BatchDev batch_view(const BatchDev& bd, const CircuitDev& c, u32 first);
 static hipStream_t role_stream(bbp_ctx* ctx, int role, hipStream_t caller) {  // prove_plan.h StreamRole
     switch (role) {
         case ROLE_CALLER: return caller;
@@ -1431,8 +1346,87 @@ static hipStream_t role_stream(bbp_ctx* ctx, int role, hipStream_t caller) {  //
         default: return nullptr;  // no plan asks for another
     }
 }
+
+// everything after the opening stage for `B` proofs of the view `bd`, on stream `s`, with MSM scratch slot `slot`
 static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
-                           hipEvent_t stagger, hipEvent_t out_guard);
+                           hipEvent_t stagger, hipEvent_t out_guard) {
+    int32_t rc;
+    const u32 m = c.m, n1 = c.n_mul;
+    const BatchStrides st = batch_strides(c.dims());  // elements per proof of every array of bd (batch_layout.h)
+    DevBuf& ptsbuf = slot ? ctx->slice_pts[slot] : ctx->pts;
+    // A_I1, A_O1, S1 -> pts[m + 0..2] (strided output: launch per commitment with an output view)
+    if ((rc = dev_reserve(ctx, ptsbuf, sizeof(ge) * (size_t)B * 3))) return rc;
+    ge* tmp = static_cast<ge*>(ptsbuf.p);
+    if ((rc = msm_launch(ctx, B, st.ai1, (const u32*)bd.ai1, c.idx_ai, tmp, s, 1, slot))) return rc;
+    if (stagger && hp.stagger_after == 1) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
+    if ((rc = msm_launch(ctx, B, st.ao1, (const u32*)bd.ao1, c.idx_ao, tmp + B, s, 1, slot))) return rc;
+    if ((rc = msm_launch(ctx, B, st.s1, (const u32*)bd.s1, c.idx_s1, tmp + 2 * (size_t)B, s, 1, slot))) return rc;
+    // the next slice starts once this one has issued its three commitment MSMs: its own commitment MSMs then run under this
+    // slice's long MSM-free stretch (encode, transcript, powers, flatten, poly, T commitments, l/r vectors)
+    if (stagger && hp.stagger_after == 3) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
+    // the three commitments of a proof in ONE launch (they sit B points apart: tmp[k * B + p]); three launches were three
+    // dependent-chain latencies (3 x 82 us for a small call)
+    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(3 * B, 64), 64, s, 3 * B, 3u, tmp, 1u, bd.enc, st.enc, enc_A(m), B);
+    const u32 tw = hp.tw, tgrid = hp.tgrid;  // transcript kernels: one proof per wavefront for small launches
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_yz, tgrid, 64, s, B, m, bd.enc, bd.tr, bd.misc, tw);
+    {
+        const u32 widest = st.zpow > st.ypow ? st.zpow : st.ypow;  // each table is filled to its stride
+        const PowersJob jz{st.zpow, (int)MS_Z, bd.zpow, st.zpow, 0u}, jy{st.ypow, (int)MS_Y, bd.ypow, st.ypow, 0u}, jyi{st.yipow, (int)MS_YINV, bd.yipow, st.yipow, 0u};
+        LAUNCH(ctx, TAG_POLY, k_powers3, dim3(cdiv(B * cdiv(widest, 32), 64), 3), 64, s, B, bd.misc, jz, jy, jyi);
+    }
+    const u32 n_tgt = 3 * n1 + m;
+    if (hp.wide_ipa)
+        LAUNCH(ctx, TAG_POLY, k_flatten_split, cdiv(B * n_tgt * FLAT_L, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, st.zpow, bd.wl, bd.wr,
+           bd.wo, bd.wv, st.wl);
+    else
+        LAUNCH(ctx, TAG_POLY, k_flatten, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, st.zpow, bd.wl, bd.wr,
+           bd.wo, bd.wv, st.wl);
+    LAUNCH(ctx, TAG_POLY, k_poly, B, POLY_BLK, s, n1, bd.ai1, bd.ao1, bd.s1, bd.wl, bd.wr, bd.wo, st.wl, bd.ypow, bd.yipow, bd.l1, bd.r0,
+           bd.r1, bd.r3, bd.misc);
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_tblind, tgrid, 64, s, B, bd.rng, bd.misc, tw);
+    if (hp.split_T)
+        LAUNCH(ctx, TAG_COMMIT, k_commit_T_split, cdiv(B * 5 * COMMIT_L, 64), 64, s, B, bd.misc, ctx->comb, bd.pts, st.pts, m);
+    else
+        LAUNCH(ctx, TAG_COMMIT, k_commit_T, cdiv(B * 5, 64), 64, s, B, bd.misc, ctx->comb, bd.pts, st.pts, m);
+    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(B * 5, 64), 64, s, B * 5, 5u, bd.pts + pts_T(m), st.pts, bd.enc, st.enc, enc_T(m), 1u);
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_ux, tgrid, 64, s, B, m, n1, bd.enc, bd.wv, bd.vb, bd.ai1, bd.ao1, bd.s1, bd.tr, bd.misc, tw);
+    LAUNCH(ctx, TAG_POLY, k_lrvec, cdiv(B * IPA_N, 128), 128, s, B, n1, bd.l1, bd.r0, bd.r1, bd.r3, bd.ao1, bd.s1, bd.ypow, bd.yipow, bd.misc,
+           bd.a, bd.b, bd.g, bd.h);
+    const u32 tail_from = hp.tail_from;  // FOLD_ROUND (7), or 12 = never leave the fixed-base formulation (small heavy stages)
+    for (u32 r = 1; r <= IPA_ROUNDS && r < tail_from; r++) {
+        if (r > 1) LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_challenge, tgrid, 64, s, B, r - 1, m, bd.enc, bd.tr, bd.misc, tw);
+        if (hp.wide_ipa)
+            LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK_WIDE>, B, IPA_BLK_WIDE, s, r, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, bd.lr);
+        else
+            LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK>, B, IPA_BLK, s, r, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, bd.lr);
+        if ((rc = msm_launch(ctx, 2 * B, IPA_TERMS, (const u32*)bd.lr, c.idx_ipa + (size_t)(r - 1) * st.lr, bd.lrpts, s, 2, slot))) return rc;
+        LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(2 * B, 64), 64, s, 2 * B, 2u, bd.lrpts, st.lrpts, bd.enc, st.enc, enc_LR(m, r), 1u);
+    }
+    if (tail_from <= IPA_ROUNDS) {
+        // switch to explicit folded generators: absorb round FOLD_ROUND-1, fold a, b, update g, h (no scalar rows), then one
+        // composite-bucket pass materialises F_G[32], F_H[32]; the remaining rounds are small variable-base kernels
+        DevBuf& vt = ctx->slice_vtab[slot];
+        if ((rc = dev_reserve(ctx, vt, (size_t)B * 2 * FOLD_CLS * TAIL_TAB * sizeof(ge)))) return rc;
+        ge* ftab = static_cast<ge*>(vt.p);
+        LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_challenge, tgrid, 64, s, B, tail_from - 1, m, bd.enc, bd.tr, bd.misc, tw);
+        LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK>, B, IPA_BLK, s, tail_from, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, (sc*)nullptr);
+        if ((rc = fold_generators_launch(ctx, B, bd.g, bd.h, bd.fpts, s, slot))) return rc;
+        LAUNCH(ctx, TAG_VARBASE, k_tail_init, cdiv(B * FOLD_CLS, 64), 64, s, B, bd.g, bd.h);
+        LAUNCH(ctx, TAG_VARBASE, k_tail_tables, cdiv(B * 2 * FOLD_CLS, 64), 64, s, B * 2 * FOLD_CLS, bd.fpts, ftab);
+        for (u32 r = tail_from; r <= IPA_ROUNDS; r++) {
+            const u32 n = IPA_HALF >> (r - 1);
+            LAUNCH(ctx, TAG_VARBASE, k_tail_lr, cdiv(B, TAIL_PPB), TAIL_BLK, s, B, n, r > tail_from ? r - 1 : 0u, m, bd.enc, bd.tr, bd.misc, bd.a, bd.b, bd.g, bd.h, ftab,
+                   ctx->btab, bd.lrpts);
+            LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(2 * B, 64), 64, s, 2 * B, 2u, bd.lrpts, st.lrpts, bd.enc, st.enc, enc_LR(m, r), 1u);
+        }
+    }
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_final, tgrid, 64, s, B, m, bd.enc, bd.tr, bd.misc, bd.a, bd.b, tw);
+    // a slice on an internal stream runs ahead of the caller's: its records must not land in out_dev before the work that was
+    // enqueued on the caller's stream ahead of this call (a consumer of the previous call's records, say) has finished
+    if (out_guard) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, out_guard, 0));
+    LAUNCH(ctx, TAG_TRANSCRIPT, k_assemble, cdiv(B, 64), 64, s, B, m, bd.enc, bd.misc, out_dev);
+    return BBP_OK;
+}
 
 // in_dev: B * (7*32 + N*32 + 8) ; ent_dev: B * (32 m + 32) ; out_dev: B * (1121 + 32 m).  All device pointers.
 // open_hook (optional): called once with the opening stream after its waits, before the opening kernels -- work that reads the
@@ -1503,8 +1497,10 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     const int ridx = plan.raw_index(), par = plan.par;
     if (plan.open_role() == ROLE_SIDE2 && !ctx->side2) BBP_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side2, hipStreamNonBlocking));
     BatchDev bd;
-    if ((rc = batch_reserve(ctx, B, c, bd, par))) return rc;
-    const u32 m = c.m, n1 = c.n_mul, encw = (m + 8 + 22) * 8;
+    const BatchDims dims = c.dims();
+    if ((rc = batch_reserve(ctx, B, dims, bd, par))) return rc;
+    const BatchStrides st = batch_strides(dims);
+    const u32 m = c.m, n1 = c.n_mul;
     const merlin_transcript prefix = prover_prefix();
     const size_t n_draws = 3 + 2 * (size_t)n1;
     if ((rc = dev_reserve(ctx, ctx->raw[ridx], (size_t)B * n_draws * 64))) return rc;
@@ -1533,8 +1529,8 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     if ((rc = serial_lds_bytes(ctx, (const void*)k_open_serial, &hog))) return rc;
     LAUNCH(ctx, TAG_WITNESS, k_witness_head, cdiv(B, 64), 64, os, B, N, c.n_cst, in_dev, bd.cst, bd.v);
     LAUNCH(ctx, TAG_TRANSCRIPT, k_load_blindings, cdiv(B * m, 64), 64, os, B, m, ent_dev, bd.vb);
-    if ((rc = commit_launch(ctx, B * m, bd.v, bd.vb, m, m, m, bd.pts, m + 8, os))) return rc;
-    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(B * m, 64), 64, os, B * m, m, bd.pts, m + 8, bd.enc, encw, 0u, 1u);
+    if ((rc = commit_launch(ctx, B * m, bd.v, bd.vb, st.v, st.vb, m, bd.pts, st.pts, os))) return rc;
+    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(B * m, 64), 64, os, B * m, m, bd.pts, st.pts, bd.enc, st.enc, enc_V(0), 1u);
     if (plan.coop) {
         // prefix: one lane (or, for a few proofs, one wavefront) per proof, ~20 permutations (V x m, "m", the rng's rekeys, the first
         // draw): 0.3 ms, no witness blocks
@@ -1595,7 +1591,7 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
         // slice waits for the previous slice's first MSM, which puts its serial steps under the neighbour's MSMs
         const HeavyPlan hp = plan_heavy(ctx->knobs, last - first);
         if (i && hp.stagger_after) BBP_HIP_TRY(ctx, hipStreamWaitEvent(ls, ctx->ev_stagger[i - 1], 0));
-        if ((rc = prove_heavy(ctx, hp, c, batch_view(bd, c, first), last - first, out_dev + rec * first, ls, (int)i,
+        if ((rc = prove_heavy(ctx, hp, c, batch_view(bd, dims, first), last - first, out_dev + rec * first, ls, (int)i,
                               i + 1 < plan.slices ? ctx->ev_stagger[i] : nullptr, i ? ctx->ev_entry[par] : nullptr)))
             return rc;
         if (i) {
@@ -1613,105 +1609,13 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     return BBP_OK;  // ~StreamGuard records ev_last on the caller's stream
 }
 
-// pointers of `bd` advanced to proof `first` (every array is [proof][stride])
-static BatchDev batch_view(const BatchDev& bd, const CircuitDev& c, u32 first) {
-    BatchDev v = bd;
-    const size_t f = first, n1 = c.n_mul, m = c.m;
-    v.cst += f * c.n_cst; v.v += f * m; v.vb += f * m; v.ai1 += f * (1 + 2 * n1); v.ao1 += f * (1 + n1); v.s1 += f * (1 + 2 * n1);
-    v.tr += f; v.rng += f; v.misc += f * MS_COUNT; v.zpow += f * ((size_t)c.n_cons + 1); v.ypow += f * 2049; v.yipow += f * 2048;
-    v.wl += f * 2048; v.wr += f * 2048; v.wo += f * 2048; v.wv += f * m; v.l1 += f * n1; v.r0 += f * n1; v.r1 += f * n1; v.r3 += f * n1;
-    v.a += f * 2048; v.b += f * 2048; v.g += f * 2048; v.h += f * 2048; v.lr += f * 2 * 2049; v.pts += f * (m + 8); v.lrpts += f * 2; v.fpts += f * 2 * FOLD_CLS;
-    v.enc += f * (m + 8 + 22) * 8; v.entropy += f * (32 * m + 32);
-    return v;
-}
-
-// everything after the opening stage for `B` proofs of the view `bd`, on stream `s`, with MSM scratch slot `slot`
-static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& c, const BatchDev& bd, u32 B, u8* out_dev, hipStream_t s, int slot,
-                           hipEvent_t stagger, hipEvent_t out_guard) {
-    int32_t rc;
-    const u32 m = c.m, n1 = c.n_mul, encw = (m + 8 + 22) * 8;
-    DevBuf& ptsbuf = slot ? ctx->slice_pts[slot] : ctx->pts;
-    // A_I1, A_O1, S1 -> pts[m + 0..2] (strided output: launch per commitment with an output view)
-    if ((rc = dev_reserve(ctx, ptsbuf, sizeof(ge) * (size_t)B * 3))) return rc;
-    ge* tmp = static_cast<ge*>(ptsbuf.p);
-    if ((rc = msm_launch(ctx, B, 1 + 2 * n1, (const u32*)bd.ai1, c.idx_ai, tmp, s, 1, slot))) return rc;
-    if (stagger && hp.stagger_after == 1) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
-    if ((rc = msm_launch(ctx, B, 1 + n1, (const u32*)bd.ao1, c.idx_ao, tmp + B, s, 1, slot))) return rc;
-    if ((rc = msm_launch(ctx, B, 1 + 2 * n1, (const u32*)bd.s1, c.idx_s1, tmp + 2 * (size_t)B, s, 1, slot))) return rc;
-    // the next slice starts once this one has issued its three commitment MSMs: its own commitment MSMs then run under this
-    // slice's long MSM-free stretch (encode, transcript, powers, flatten, poly, T commitments, l/r vectors)
-    if (stagger && hp.stagger_after == 3) BBP_HIP_TRY(ctx, hipEventRecord(stagger, s));
-    // the three commitments of a proof in ONE launch (they sit B points apart: tmp[k * B + p]); three launches were three
-    // dependent-chain latencies (3 x 82 us for a small call)
-    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(3 * B, 64), 64, s, 3 * B, 3u, tmp, 1u, bd.enc, encw, 8 * m, B);
-    const u32 tw = hp.tw, tgrid = hp.tgrid;  // transcript kernels: one proof per wavefront for small launches
-    LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_yz, tgrid, 64, s, B, m, bd.enc, bd.tr, bd.misc, tw);
-    {
-        const u32 widest = c.n_cons + 1 > 2049u ? c.n_cons + 1 : 2049u;
-        const PowersJob jz{c.n_cons + 1, (int)MS_Z, bd.zpow, c.n_cons + 1, 0u}, jy{2049u, (int)MS_Y, bd.ypow, 2049u, 0u}, jyi{2048u, (int)MS_YINV, bd.yipow, 2048u, 0u};
-        LAUNCH(ctx, TAG_POLY, k_powers3, dim3(cdiv(B * cdiv(widest, 32), 64), 3), 64, s, B, bd.misc, jz, jy, jyi);
-    }
-    const u32 n_tgt = 3 * n1 + m;
-    if (hp.wide_ipa)
-        LAUNCH(ctx, TAG_POLY, k_flatten_split, cdiv(B * n_tgt * FLAT_L, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, c.n_cons + 1, bd.wl, bd.wr,
-           bd.wo, bd.wv, 2048u);
-    else
-        LAUNCH(ctx, TAG_POLY, k_flatten, cdiv(B * n_tgt, 128), 128, s, B, n_tgt, n1, m, c.f_off, c.f_ent, bd.zpow, c.n_cons + 1, bd.wl, bd.wr,
-           bd.wo, bd.wv, 2048u);
-    LAUNCH(ctx, TAG_POLY, k_poly, B, POLY_BLK, s, n1, bd.ai1, bd.ao1, bd.s1, bd.wl, bd.wr, bd.wo, 2048u, bd.ypow, bd.yipow, bd.l1, bd.r0,
-           bd.r1, bd.r3, bd.misc);
-    LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_tblind, tgrid, 64, s, B, bd.rng, bd.misc, tw);
-    if (hp.split_T)
-        LAUNCH(ctx, TAG_COMMIT, k_commit_T_split, cdiv(B * 5 * COMMIT_L, 64), 64, s, B, bd.misc, ctx->comb, bd.pts, m + 8, m);
-    else
-        LAUNCH(ctx, TAG_COMMIT, k_commit_T, cdiv(B * 5, 64), 64, s, B, bd.misc, ctx->comb, bd.pts, m + 8, m);
-    LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(B * 5, 64), 64, s, B * 5, 5u, bd.pts + (m + 3), m + 8, bd.enc, encw, 8 * (m + 3), 1u);
-    LAUNCH(ctx, TAG_TRANSCRIPT, k_tr_ux, tgrid, 64, s, B, m, n1, bd.enc, bd.wv, bd.vb, bd.ai1, bd.ao1, bd.s1, bd.tr, bd.misc, tw);
-    LAUNCH(ctx, TAG_POLY, k_lrvec, cdiv(B * 2048, 128), 128, s, B, n1, bd.l1, bd.r0, bd.r1, bd.r3, bd.ao1, bd.s1, bd.ypow, bd.yipow, bd.misc,
-           bd.a, bd.b, bd.g, bd.h);
-    const u32 tail_from = hp.tail_from;  // FOLD_ROUND (7), or 12 = never leave the fixed-base formulation (small heavy stages)
-    for (u32 r = 1; r <= 11 && r < tail_from; r++) {
-        if (r > 1) LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_challenge, tgrid, 64, s, B, r - 1, m, bd.enc, bd.tr, bd.misc, tw);
-        if (hp.wide_ipa)
-            LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK_WIDE>, B, IPA_BLK_WIDE, s, r, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, bd.lr);
-        else
-            LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK>, B, IPA_BLK, s, r, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, bd.lr);
-        if ((rc = msm_launch(ctx, 2 * B, 2049, (const u32*)bd.lr, c.idx_ipa + (size_t)(r - 1) * 2 * 2049, bd.lrpts, s, 2, slot))) return rc;
-        LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(2 * B, 64), 64, s, 2 * B, 2u, bd.lrpts, 2u, bd.enc, encw, 8 * (m + 8 + 2 * (r - 1)), 1u);
-    }
-    if (tail_from <= 11) {
-        // switch to explicit folded generators: absorb round FOLD_ROUND-1, fold a, b, update g, h (no scalar rows), then one
-        // composite-bucket pass materialises F_G[32], F_H[32]; the remaining rounds are small variable-base kernels
-        DevBuf& vt = ctx->slice_vtab[slot];
-        if ((rc = dev_reserve(ctx, vt, (size_t)B * 2 * FOLD_CLS * TAIL_TAB * sizeof(ge)))) return rc;
-        ge* ftab = static_cast<ge*>(vt.p);
-        LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_challenge, tgrid, 64, s, B, tail_from - 1, m, bd.enc, bd.tr, bd.misc, tw);
-        LAUNCH(ctx, TAG_IPA_SCALARS, k_ipa_round<IPA_BLK>, B, IPA_BLK, s, tail_from, n1, bd.misc, bd.a, bd.b, bd.g, bd.h, (sc*)nullptr);
-        if ((rc = fold_generators_launch(ctx, B, bd.g, bd.h, bd.fpts, s, slot))) return rc;
-        LAUNCH(ctx, TAG_VARBASE, k_tail_init, cdiv(B * FOLD_CLS, 64), 64, s, B, bd.g, bd.h);
-        LAUNCH(ctx, TAG_VARBASE, k_tail_tables, cdiv(B * 2 * FOLD_CLS, 64), 64, s, B * 2 * FOLD_CLS, bd.fpts, ftab);
-        for (u32 r = tail_from; r <= 11; r++) {
-            const u32 n = 1024u >> (r - 1);
-            LAUNCH(ctx, TAG_VARBASE, k_tail_lr, cdiv(B, TAIL_PPB), TAIL_BLK, s, B, n, r > tail_from ? r - 1 : 0u, m, bd.enc, bd.tr, bd.misc, bd.a, bd.b, bd.g, bd.h, ftab,
-                   ctx->btab, bd.lrpts);
-            LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(2 * B, 64), 64, s, 2 * B, 2u, bd.lrpts, 2u, bd.enc, encw, 8 * (m + 8 + 2 * (r - 1)), 1u);
-        }
-    }
-    LAUNCH(ctx, TAG_TRANSCRIPT, k_ipa_final, tgrid, 64, s, B, m, bd.enc, bd.tr, bd.misc, bd.a, bd.b, tw);
-    // a slice on an internal stream runs ahead of the caller's: its records must not land in out_dev before the work that was
-    // enqueued on the caller's stream ahead of this call (a consumer of the previous call's records, say) has finished
-    if (out_guard) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, out_guard, 0));
-    LAUNCH(ctx, TAG_TRANSCRIPT, k_assemble, cdiv(B, 64), 64, s, B, m, bd.enc, bd.misc, out_dev);
-    return BBP_OK;
-}
-
 // debug / parity hook: copy a proof's challenge block (MS_COUNT scalars) to the host
 int32_t debug_read_misc(bbp_ctx* ctx, u32 B, u32 N, u32 proof, uint8_t* out) {
     const CircuitDev* cp;
     int32_t rc = circuit_get(ctx, N, &cp);
     if (rc) return rc;
     BatchDev bd;
-    if ((rc = batch_reserve(ctx, B, *cp, bd, ctx->last_par))) return rc;
+    if ((rc = batch_reserve(ctx, B, cp->dims(), bd, ctx->last_par))) return rc;
     BBP_HIP_TRY(ctx, hipMemcpy(out, bd.misc + (size_t)proof * MS_COUNT, MS_COUNT * 32, hipMemcpyDeviceToHost));
     return BBP_OK;
 }

@@ -46,7 +46,7 @@ __global__ void k_pad_sums(ge* __restrict__ gens) {
     }
 }
 
-// merged bases (context.h): MRG1(i) = G[i] + H[i] + H[i+1] at MRG_BASE0 + i, MRG2(i) = G[i] + G[i+1] + H[i+1] at MRG_BASE0 + 2048 + i
+// merged bases (msm_index.h): MRG1(i) = G[i] + H[i] + H[i+1] at MRG_BASE0 + i, MRG2(i) = G[i] + G[i+1] + H[i+1] at MRG_BASE0 + 2048 + i
 __global__ void k_merge_sums(ge* __restrict__ gens) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= 2048u) return;

@@ -164,7 +164,7 @@ __global__ BBP_LANE_KERNEL void k_vtranscript(u32 B, u32 m, merlin_transcript pr
     v_append_words(t, VLBL("e_blinding"), ebl.v);
     sc w = v_challenge_sc(t, VLBL("w"));
     merlin_append(t, VLBL("dom-sep"), VLBL("ipp v1"));
-    merlin_append_u64(t, VLBL("n"), 2048);
+    merlin_append_u64(t, VLBL("n"), IPA_N);
     const u32 *Lp = pt + 8 * (6 + m + 5), *Rp = Lp + 8 * 11;
     // The eleven challenges and the prefix products of the batch inversion below live in the proof's own OUTPUT rows (vc[VC_U + j],
     // vc[VC_UI + j]: this lane's, L2-resident) instead of two local arrays: indexed by a loop variable those were 736 bytes of
@@ -224,9 +224,9 @@ __global__ __launch_bounds__(VS_BLK) void k_vscalars(u32 n1, u32 n_cterms, u32 n
     const u32 p = blockIdx.x, tid = threadIdx.x;
     const sc* vc = vchal + (size_t)p * VC_COUNT;
     sc* ms = misc + (size_t)p * MS_COUNT;
-    const sc *zp = zpow + (size_t)p * zstride, *cst = cst_all + (size_t)p * n_cst, *YI = yipow + (size_t)p * 2048;
-    const sc *WL = wl + (size_t)p * 2048, *WR = wr + (size_t)p * 2048, *WO = wo + (size_t)p * 2048;
-    sc* s = s_all + (size_t)p * 2048;
+    const sc *zp = zpow + (size_t)p * zstride, *cst = cst_all + (size_t)p * n_cst, *YI = yipow + (size_t)p * IPA_N;
+    const sc *WL = wl + (size_t)p * IPA_N, *WR = wr + (size_t)p * IPA_N, *WO = wo + (size_t)p * IPA_N;
+    sc* s = s_all + (size_t)p * IPA_N;
     sc* vs = vs_all + (size_t)p * 4098;
     const sc x = ld_sc(&ms[MS_X]), u = ld_sc(&ms[MS_U]), allinv = ld_sc(&ms[MS_ALLINV]);
     const sc a = ld_sc(&vc[VC_A]), b = ld_sc(&vc[VC_B]);
@@ -254,7 +254,7 @@ __global__ __launch_bounds__(VS_BLK) void k_vscalars(u32 n1, u32 n_cterms, u32 n
     sc acc[2] = {sc_zero(), sc_zero()};  // acc[0] = delta, acc[1] = -wc
     const sc xr = sc_to_mont(x), ar = sc_to_mont(a), br = sc_to_mont(b), ur = sc_to_mont(u);  // v * (c R) * R^-1 = v c: one multiplication
     const sc rho_r = sc_to_mont(ld_sc(&ms[MS_RHO]));  // aggregated mode: every generator scalar of this proof times its weight
-    for (u32 i = tid; i < 2048; i += VS_BLK) {
+    for (u32 i = tid; i < IPA_N; i += VS_BLK) {
         const bool live = i < n1;
         const sc yir = ld_sc(&YI[i]);  // y^-i R (k_powers, Montgomery output): a product with it is ONE multiplication
         sc ynw = live ? sc_montmul(ld_sc(&WR[i]), yir) : sc_zero();
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(VS_BLK) void k_vscalars(u32 n1, u32 n_cterms, u32 n
         gs = live ? gs : sc_montmul(gs, ur);
         hs = live ? hs : sc_montmul(hs, ur);
         st_sc(&vs[i], agg ? sc_montmul(gs, rho_r) : gs);
-        st_sc(&vs[2048 + i], agg ? sc_montmul(hs, rho_r) : hs);
+        st_sc(&vs[IPA_N + i], agg ? sc_montmul(hs, rho_r) : hs);
     }
     for (u32 e = tid; e < n_cterms; e += VS_BLK) {
         u32 w = c_q[e];
@@ -687,6 +687,7 @@ struct VerifyCall {
     // parse, transcript replay, z and y^-1 powers, flatten
     int32_t front() const {
         const VerifyDims& d = p.d;
+        const BatchStrides st = batch_strides(d);  // elements per proof of bd's arrays (batch_layout.h)
         const u32 B = p.B, N = v.front_n(), m = d.m;
         const VRow* rows = b.rows;
         int32_t rc;
@@ -728,14 +729,14 @@ struct VerifyCall {
                 LAUNCH(ctx, TAG_POLY, k_powers_mx, p.powers_z.grid, p.powers_z.block, s, B, p.zchunks, rows, c.ctab, bd.misc, (int)MS_Z, bd.zpow, p.zstride);
             else
                 LAUNCH(ctx, TAG_POLY, k_powers, p.powers_z.grid, p.powers_z.block, s, B, p.zstride, bd.misc, (int)MS_Z, bd.zpow, p.zstride, 0u);
-            LAUNCH(ctx, TAG_POLY, k_powers, p.powers_yinv.grid, p.powers_yinv.block, s, B, 2048u, bd.misc, (int)MS_YINV, bd.yipow, 2048u, 1u);  // y^-i R
+            LAUNCH(ctx, TAG_POLY, k_powers, p.powers_yinv.grid, p.powers_yinv.block, s, B, st.yipow, bd.misc, (int)MS_YINV, bd.yipow, st.yipow, 1u);  // y^-i R
         }
         if (ko & 8) {
         } else if (p.mixed)
             LAUNCH(ctx, TAG_POLY, k_flatten_mx, p.flatten.grid, p.flatten.block, s, B, p.n_tgt, rows, c.ctab, bd.zpow, p.zstride, bd.wl, bd.wr, bd.wo, bd.wv, m);
         else
             LAUNCH(ctx, TAG_POLY, k_flatten, p.flatten.grid, p.flatten.block, s, B, p.n_tgt, d.n_mul, m, c.uniform->f_off, c.uniform->f_ent, bd.zpow, p.zstride, bd.wl,
-                   bd.wr, bd.wo, bd.wv, 2048u);
+                   bd.wr, bd.wo, bd.wv, st.wl);
         return BBP_OK;
     }
 
@@ -819,10 +820,10 @@ static int32_t verify_pass(bbp_ctx* ctx, const VerifyRows& v, const VerifyCircui
     BatchDev bd;
     StreamGuard guard(ctx, s, 1 + lane);  // this verifier lane: own batch buffer, own misc scratch, own MSM scratch slot
     if ((rc = guard.enter())) return rc;
-    // the verifier has a batch buffer of its own (index 2) and runs entirely on the caller's stream: sharing buffer 0 with the
+    // the verifier has a batch buffer of its own (PROVE_BUFS + lane) and runs entirely on the caller's stream: sharing buffer 0 with the
     // prover made every second prove call's opening stage wait for the verification in between (98 ms per prove + verify pair
     // instead of 77)
-    if ((rc = batch_reserve(ctx, v.B, batch_sizes(c.d), bd, bbp_ctx::PROVE_BUFS + lane))) return rc;
+    if ((rc = batch_reserve(ctx, v.B, c.d, bd, bbp_ctx::PROVE_BUFS + lane))) return rc;
     if ((rc = dev_reserve(ctx, L.misc, p.misc.bytes)) || (p.G && (rc = dev_reserve(ctx, L.agg, p.agg.bytes)))) return rc;
     const VerifyBufs b(p, L.misc.p, L.agg.p);
     const int ko = ctx->vknobs.knocked_out();  // knock-out mask of the experiment builds (verify_plan.h); the constant 0 in the product

@@ -123,7 +123,7 @@ __device__ __forceinline__ void vtranscript_row(u32 p, u32 m, const merlin_trans
     v_append_words(t, VLBL("e_blinding"), ebl.v);
     sc w = v_challenge_sc(t, VLBL("w"));
     merlin_append(t, VLBL("dom-sep"), VLBL("ipp v1"));
-    merlin_append_u64(t, VLBL("n"), 2048);
+    merlin_append_u64(t, VLBL("n"), IPA_N);
     const u32 *Lp = pt + 8 * (6 + m + 5), *Rp = Lp + 8 * 11;
     // The eleven challenges and the prefix products of the batch inversion below live in the proof's own OUTPUT rows (vc[VC_U + j],
     // vc[VC_UI + j]: this lane's, L2-resident) instead of two local arrays: indexed by a loop variable those were 736 bytes of
@@ -181,9 +181,9 @@ __device__ __forceinline__ void vscalars_block(u32 p, u32 n1, u32 n_cterms, cons
     const u32 tid = threadIdx.x;
     const sc* vc = vchal + (size_t)p * VC_COUNT;
     sc* ms = misc + (size_t)p * MS_COUNT;
-    const sc* YI = yipow + (size_t)p * 2048;
-    const sc *WL = wl + (size_t)p * 2048, *WR = wr + (size_t)p * 2048, *WO = wo + (size_t)p * 2048;
-    sc* s = s_all + (size_t)p * 2048;
+    const sc* YI = yipow + (size_t)p * IPA_N;
+    const sc *WL = wl + (size_t)p * IPA_N, *WR = wr + (size_t)p * IPA_N, *WO = wo + (size_t)p * IPA_N;
+    sc* s = s_all + (size_t)p * IPA_N;
     sc* vs = vs_all + (size_t)p * 4098;
     const sc x = ld_sc(&ms[MS_X]), u = ld_sc(&ms[MS_U]), allinv = ld_sc(&ms[MS_ALLINV]);
     const sc a = ld_sc(&vc[VC_A]), b = ld_sc(&vc[VC_B]);
@@ -211,7 +211,7 @@ __device__ __forceinline__ void vscalars_block(u32 p, u32 n1, u32 n_cterms, cons
     sc acc[2] = {sc_zero(), sc_zero()};  // acc[0] = delta, acc[1] = -wc
     const sc xr = sc_to_mont(x), ar = sc_to_mont(a), br = sc_to_mont(b), ur = sc_to_mont(u);  // v * (c R) * R^-1 = v c: one multiplication
     const sc rho_r = sc_to_mont(ld_sc(&ms[MS_RHO]));  // aggregated mode: every generator scalar of this proof times its weight
-    for (u32 i = tid; i < 2048; i += VS_BLK) {
+    for (u32 i = tid; i < IPA_N; i += VS_BLK) {
         const bool live = i < n1;
         const sc yir = ld_sc(&YI[i]);  // y^-i R (k_powers, Montgomery output): a product with it is ONE multiplication
         sc ynw = live ? sc_montmul(ld_sc(&WR[i]), yir) : sc_zero();
@@ -222,7 +222,7 @@ __device__ __forceinline__ void vscalars_block(u32 p, u32 n1, u32 n_cterms, cons
         gs = live ? gs : sc_montmul(gs, ur);
         hs = live ? hs : sc_montmul(hs, ur);
         st_sc(&vs[i], agg ? sc_montmul(gs, rho_r) : gs);
-        st_sc(&vs[2048 + i], agg ? sc_montmul(hs, rho_r) : hs);
+        st_sc(&vs[IPA_N + i], agg ? sc_montmul(hs, rho_r) : hs);
     }
     for (u32 e = tid; e < n_cterms; e += VS_BLK) {
         u32 w = c_q[e];
@@ -508,7 +508,7 @@ __global__ void k_flatten_mx(u32 B, u32 n_tgt_max, const VRow* __restrict__ rows
     const VRow r = rows[p];
     const VCirc& c = ctab[r.n];
     if (k >= 3 * c.n_mul + r.m) return;
-    flatten_target(p, k, c.n_mul, c.f_off, c.f_ent, zpow + (size_t)p * zstride, wl, wr, wo, wv + (size_t)p * wv_stride, 2048u);
+    flatten_target(p, k, c.n_mul, c.f_off, c.f_ent, zpow + (size_t)p * zstride, wl, wr, wo, wv + (size_t)p * wv_stride, IPA_N);
 }
 
 __global__ __launch_bounds__(VS_BLK) void k_vscalars_mx(const VRow* __restrict__ rows, const VCirc* __restrict__ ctab, u32 cst_stride, u32 zstride,
@@ -703,13 +703,6 @@ struct VerifyCircuit {
     const CircuitDev* uniform = nullptr;
     const VCirc* ctab = nullptr;
 };
-static VerifyDims dims_of(const CircuitDev& c) { return VerifyDims{c.m, c.n_mul, c.n_cons, c.n_cst}; }
-// batch_reserve sizes a batch buffer by a circuit's counts: here those of the plan
-static CircuitDev batch_sizes(const VerifyDims& d) {
-    CircuitDev c;
-    c.n_items = d.m - 4, c.m = d.m, c.n_mul = d.n_mul, c.n_cons = d.n_cons, c.n_cst = d.n_cst;
-    return c;
-}
 // Compiles every N of the call on first use (as the uniform calls do) and fills its entry of ctx->vctab; c.d becomes the largest of
 // every count over the call's N.  The rows' Ns are host memory and screened by the caller; checked again here because they index the
 // device table.
@@ -732,7 +725,7 @@ static int32_t mixed_prepare(bbp_ctx* ctx, const VerifyRows& v, VerifyCircuit& c
             ctx->vctab_has[n] = 1;
         }
         if (!c.idx_ver) c.idx_ver = cp->idx_ver;
-        c.d.widen(dims_of(*cp));
+        c.d.widen(cp->dims());
     }
     c.ctab = (const VCirc*)ctx->vctab;
     return BBP_OK;
@@ -741,7 +734,7 @@ static int32_t mixed_prepare(bbp_ctx* ctx, const VerifyRows& v, VerifyCircuit& c
 static int32_t verify_circuit(bbp_ctx* ctx, const VerifyRows& v, VerifyCircuit& c) {
     if (v.mixed_front()) return mixed_prepare(ctx, v, c);
     if (int32_t rc = circuit_get(ctx, v.front_n(), &c.uniform)) return rc;
-    c.d = dims_of(*c.uniform), c.idx_ver = c.uniform->idx_ver;
+    c.d = c.uniform->dims(), c.idx_ver = c.uniform->idx_ver;
     return BBP_OK;
 }
 

@@ -9,6 +9,7 @@
 
 #include <vector>
 
+#include "batch_layout.h"
 #include "point.h"
 #include "prove_io.h"
 #include "scalar.h"
@@ -120,14 +121,9 @@ struct VerifyKnobs {
 #endif
 };
 
-// What the plan needs of the circuit; a mixed front end: the largest of each over the call's N (the per-row strides).
-struct VerifyDims {
-    u32 m = 0, n_mul = 0, n_cons = 0, n_cst = 0;
-    void widen(const VerifyDims& o) {
-        m = m > o.m ? m : o.m, n_mul = n_mul > o.n_mul ? n_mul : o.n_mul;
-        n_cons = n_cons > o.n_cons ? n_cons : o.n_cons, n_cst = n_cst > o.n_cst ? n_cst : o.n_cst;
-    }
-};
+// What the plan needs of the circuit is what the batch buffer needs (batch_layout.h): the prover passes a circuit's, a mixed front end
+// the largest of each over the call's N.
+using VerifyDims = BatchDims;
 
 struct VLaunch {
     u32 grid = 0, block = 0;
@@ -256,7 +252,7 @@ inline VerifyPlan plan_verify(const VerifyRows& v, const VerifyDims& d, u32 G, c
     p.parse = {cdiv(B, 64), 64};
     p.transcript = {p.vtw ? B : cdiv(B, 64), 64};
     p.powers_z = {cdiv(B * p.zchunks, 64), 64};
-    p.powers_yinv = {cdiv(B * cdiv(2048, 32), 64), 64};
+    p.powers_yinv = {cdiv(B * cdiv(IPA_N, 32), 64), 64};
     p.flatten = {cdiv(B * p.n_tgt, 128), 128};
     p.vscalars = {B, (u32)VS_BLK};
     p.per_row = {cdiv(B, 64), 64};

@@ -450,7 +450,7 @@ int32_t bbp_set_entropy_source(bbp_ctx* ctx, int32_t source);
 int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]);
 
 /* Parity hook: the 32-scalar challenge block of proof `proof` of the LAST batch call of geometry (B, N):
- * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch.h), 32 x 32 bytes. */
+ * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch_layout.h), 32 x 32 bytes. */
 int32_t bbp_debug_challenges(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t proof, uint8_t* out32x32);
 
 /* Test hook: where one of the context's resident tables lives on the device and how large it is (csrc/context.h "resident tables"):

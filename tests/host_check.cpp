@@ -2,10 +2,14 @@
 // tier can compare them with the oracle.  Nothing in the shipped library calls this.
 #include <string.h>
 
+#include <map>
+#include <string>
 #include <vector>
 
+#include "../dusk_blindbidproof_amd/csrc/batch_layout.h"
 #include "../dusk_blindbidproof_amd/csrc/keccak.h"
 #include "../dusk_blindbidproof_amd/csrc/keccak_wave.h"
+#include "../dusk_blindbidproof_amd/csrc/msm_index.h"
 #include "../dusk_blindbidproof_amd/csrc/msm_plan.h"
 #include "../dusk_blindbidproof_amd/csrc/point.h"
 #include "../dusk_blindbidproof_amd/csrc/prove_io.h"
@@ -396,6 +400,74 @@ int hc_verify_knob_from_env(const char* name, const char* text, int which) {
     const int v[] = {k.varbase_lanes, k.overlap, k.group, k.varbase_v1, k.fence, chunk};
     return v[which];
 }
+// ---- the batch buffer (csrc/batch_layout.h) and the MSM base-index lists (csrc/msm_index.h) --------------------------------------
+static const circuit::Compiled& hc_compiled(uint32_t N) {  // compiled once per N
+    static std::map<uint32_t, circuit::Compiled> cache;
+    auto it = cache.find(N);
+    if (it == cache.end()) it = cache.emplace(N, circuit::compile(N)).first;
+    return it->second;
+}
+// the sizes alone: sizeof(sc), sizeof(ge), sizeof(merlin_transcript)
+void hc_batch_elem_sizes(uint64_t* out3) { out3[0] = sizeof(sc), out3[1] = sizeof(ge), out3[2] = sizeof(merlin_transcript); }
+// (m, n_mul, n_cons, n_cst) of circuit N, as circuit_get fills a CircuitDev
+void hc_circuit_dims(uint32_t N, uint32_t* out4) {
+    const circuit::Compiled& c = hc_compiled(N);
+    out4[0] = c.m, out4[1] = c.n_mul, out4[2] = c.n_cons, out4[3] = circuit::cst_count(N);
+}
+// The carve of B proofs of dimensions dims (m, n_mul, n_cons, n_cst).  Per array, in list order: its byte offset, its stride in
+// elements, its element size; names: the field names, space separated.  Returns the number of arrays; *total: the reservation.
+int hc_batch_layout(uint32_t B, const uint32_t* dims, uint64_t* off, uint64_t* stride, uint64_t* elem, uint64_t* total, char* names, size_t names_cap) {
+    const BatchDims d{dims[0], dims[1], dims[2], dims[3]};
+    const BatchOffsets o = batch_offsets(B, d);
+    const BatchStrides s = batch_strides(d);
+    int n = 0;
+    std::string all;
+#define X(name, T, count) off[n] = o.name, stride[n] = s.name, elem[n] = sizeof(T), all += (n ? " " : ""), all += #name, n++;
+    BBP_BATCH_ARRAYS(X)
+#undef X
+    *total = o.bytes;
+    snprintf(names, names_cap, "%s", all.c_str());
+    return n;
+}
+// batch_view(batch_carve(base, B, dims), dims, first): every pointer's distance from `base` in bytes (the base is never dereferenced)
+int hc_batch_view(uint32_t B, const uint32_t* dims, uint32_t first, uint64_t* delta) {
+    const BatchDims d{dims[0], dims[1], dims[2], dims[3]};
+    u8* const base = reinterpret_cast<u8*>((uintptr_t)1 << 40);
+    const BatchDev v = batch_view(batch_carve(base, batch_offsets(B, d)), d, first);
+    int n = 0;
+#define X(name, T, count) delta[n++] = (uint64_t)(reinterpret_cast<uintptr_t>(v.name) - reinterpret_cast<uintptr_t>(base));
+    BBP_BATCH_ARRAYS(X)
+#undef X
+    return n;
+}
+// ProvePlan::slice_first of a call cut into `slices`
+uint32_t hc_slice_first(uint32_t B, uint32_t slices, uint32_t i) {
+    ProvePlan p;
+    p.slices = slices;
+    return p.slice_first(B, i);
+}
+// the encoding and point blocks of one proof: 0 enc_words, 1 enc_V(0), 2 enc_V(m - 1), 3 enc_A, 4 enc_T, 5..15 enc_LR(r = 1..11), 16 pts_count, 17 pts_T
+void hc_enc_slots(uint32_t m, uint64_t* out18) {
+    out18[0] = enc_words(m), out18[1] = enc_V(0), out18[2] = enc_V(m - 1), out18[3] = enc_A(m), out18[4] = enc_T(m);
+    for (uint32_t r = 1; r <= IPA_ROUNDS; r++) out18[4 + r] = enc_LR(m, r);
+    out18[16] = pts_count(m), out18[17] = pts_T(m);
+}
+// the base-index lists of circuit N.  which: 0 idx_ai, 1 idx_s1, 2 idx_ao, 3 idx_ipa, 4 idx_ver.  Returns the length (the first `cap`
+// entries are written); *n_ai_terms: index_ai's count (which 0 only)
+int hc_index_lists(uint32_t N, int which, uint32_t* out, uint32_t cap, uint32_t* n_ai_terms) {
+    const circuit::Compiled& c = hc_compiled(N);
+    const std::vector<u32> v = which == 0 ? index_ai(c, n_ai_terms) : which == 1 ? index_s1(c) : which == 2 ? index_ao(c) : which == 3 ? index_ipa(c) : index_ver();
+    for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+// the gadget program of circuit N.  which: 0 w_terms, 1 w_loff, 2 w_roff; as hc_index_lists
+int hc_circuit_wires(uint32_t N, int which, uint32_t* out, uint32_t cap) {
+    const circuit::Compiled& c = hc_compiled(N);
+    const std::vector<u32>& v = which == 0 ? c.w_terms : which == 1 ? c.w_loff : c.w_roff;
+    for (size_t i = 0; i < v.size() && i < cap; i++) out[i] = v[i];
+    return (int)v.size();
+}
+
 // msm_split over every launch of n_msm = 1..max_msm MSMs of n_terms = 1..max_terms terms under the default knobs: how many
 // (n_msm, n_terms) break a rule -- the sub-MSMs cover the terms, none lies wholly past the end, at most MSM_SPLIT_MAX of them, a
 // split MSM's sub-MSMs have 128 terms or more; first_bad: the first such pair.  *max_split: the largest split seen.
