@@ -5,6 +5,10 @@
 //
 //   closed loop:  bbp-uds-loadgen --socket PATH --requests FILE --connections C --ops M [--no-verify]
 //                 C connections, each runs one op after the other until M ops are done: throughput at a given concurrency.
+//                 --depth K: every connection keeps K independent ops outstanding (the server's --pipeline-depth); an op's verify
+//                 frame is written as soon as its proof arrives, replies are matched to ops by order, latency runs from the op's
+//                 first write.  A reply out of order, or a connection closed with ops outstanding, counts as failed.
+//                 --verify-only: FILE's first element per bid is a complete opcode-2 request; one op = that one verdict.
 //   open loop:    bbp-uds-loadgen --socket PATH --requests FILE --rate R --duration S [--connections CAP] [--no-verify]
 //                 ops ARRIVE as a Poisson process of R per second whatever the server does (the load a network of bidders puts
 //                 on a node); an arrival takes an idle connection, opens a new one (up to CAP), or waits in the generator's
@@ -82,19 +86,28 @@ static int dial_inner(const std::string& path) {
     return -1;
 }
 
-enum State { IDLE, WAIT_PROOF, WAIT_VERIFY };
+// one reply the server owes a connection.  The server answers in request order, so the replies of a connection are matched to its
+// outstanding requests by position: `q` is that order.
+struct Expect {
+    bool verify = false;  // the [0x01] of an op's second half; else its proof blob
+    size_t bid = 0;
+    Clock::time_point t_sched, t_sent, t_proof;  // of the op: scheduled arrival, first write, proof reply
+};
 struct Conn {
     int fd = -1;
-    State st = IDLE;
-    size_t bid = 0;
-    Clock::time_point t_sched, t_sent, t_proof;
+    std::deque<Expect> q;
     tlv::Bytes in;
+    tlv::Bytes out;  // request bytes the socket did not take yet (a pipelining connection never blocks in send: the server may be
+                     // waiting for this side to read replies first)
+    size_t out_off = 0;
+    bool want_out = false;
 };
 
 struct Shared {
     std::string sock;
     std::vector<Bid> bids;
     bool do_verify = true;
+    bool verify_only = false;  // --verify-only: FILE's first element per bid is a complete opcode-2 request, one op = one verdict
     std::atomic<long> next{0}, failed{0}, rejected{0};
     long ops = 0;  // closed loop
 };
@@ -103,7 +116,8 @@ struct Worker {
     Shared* sh = nullptr;
     int ep = -1;
     std::vector<Conn> conns;
-    std::vector<int> idle;  // indices into conns
+    std::vector<int> idle;  // indices into conns: one entry per op a connection may still take (closed loop: --depth per connection)
+    int depth = 1;          // closed loop: independent ops every connection keeps outstanding
     std::vector<float> lat_p, lat_v, lat_o;
     std::vector<double> t_done;  // completion time of every op, seconds on the steady clock
     // open loop
@@ -127,29 +141,64 @@ struct Worker {
         ev.events = EPOLLIN;
         ev.data.u32 = (uint32_t)(conns.size() - 1);
         epoll_ctl(ep, EPOLL_CTL_ADD, fd, &ev);
-        idle.push_back((int)conns.size() - 1);
+        for (int k = 0; k < depth; k++) idle.push_back((int)conns.size() - 1);  // `depth` places for an op on this connection
         return true;
     }
+    // the connection is lost with everything it had outstanding: one failure per op (one for a connection that had none)
     void fail(Conn& c) {
-        sh->failed++;
+        const long ops = (long)c.q.size();  // an op has exactly one reply outstanding at any time
+        sh->failed += ops ? ops : 1;
+        active -= (int)ops;
+        c.q.clear();
         if (c.fd >= 0) {
             epoll_ctl(ep, EPOLL_CTL_DEL, c.fd, nullptr);
             close(c.fd);
-            c.fd = -1;
+            c.fd = -1;  // never reused: take_idle() passes over it
         }
-        if (c.st != IDLE) active--;
-        c.st = IDLE;  // never reused: not in `idle`
+    }
+    // queue n request bytes and write what the socket takes now; the rest goes when it is writable again
+    bool send_some(Conn& c, const uint8_t* p, size_t n) {
+        if (depth == 1 && c.out.empty()) return write_all(c.fd, p, n);  // request-response: a few KB, far below the socket buffer
+        c.out.insert(c.out.end(), p, p + n);
+        return flush(c);
+    }
+    bool flush(Conn& c) {
+        while (c.out_off < c.out.size()) {
+            const ssize_t r = send(c.fd, c.out.data() + c.out_off, c.out.size() - c.out_off, MSG_NOSIGNAL | MSG_DONTWAIT);
+            if (r > 0) {
+                c.out_off += (size_t)r;
+                continue;
+            }
+            if (r < 0 && errno == EINTR) continue;
+            if (r < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
+            return false;
+        }
+        const bool pending = c.out_off < c.out.size();
+        if (!pending) {
+            c.out.clear();
+            c.out_off = 0;
+        }
+        if (pending != c.want_out) {
+            epoll_event ev;
+            memset(&ev, 0, sizeof ev);
+            ev.events = EPOLLIN | (pending ? EPOLLOUT : 0);
+            ev.data.u32 = (uint32_t)(&c - conns.data());
+            epoll_ctl(ep, EPOLL_CTL_MOD, c.fd, &ev);
+            c.want_out = pending;
+        }
+        return true;
     }
     void start(int ci, long k, Clock::time_point t_sched) {
         Conn& c = conns[(size_t)ci];
-        c.bid = (size_t)k % sh->bids.size();
-        c.t_sched = t_sched;
-        c.t_sent = Clock::now();
-        c.st = WAIT_PROOF;
-        c.in.clear();
+        Expect e;
+        e.bid = (size_t)k % sh->bids.size();
+        e.t_sched = t_sched;
+        e.t_sent = e.t_proof = Clock::now();
+        e.verify = sh->verify_only;  // the bid's frame is an opcode-2 request then: the op is that one verdict
+        c.q.push_back(e);
         active++;
-        const Bid& b = sh->bids[c.bid];
-        if (!write_all(c.fd, b.prove_frame.data(), b.prove_frame.size())) fail(c);
+        const Bid& b = sh->bids[e.bid];
+        if (!send_some(c, b.prove_frame.data(), b.prove_frame.size())) fail(c);
     }
     // a whole frame in c.in?  -> payload
     static int take_frame(Conn& c, tlv::Bytes* payload) {
@@ -163,9 +212,7 @@ struct Worker {
         return 1;
     }
     void op_done(int ci) {
-        Conn& c = conns[(size_t)ci];
         t_done.push_back(std::chrono::duration<double>(Clock::now().time_since_epoch()).count());
-        c.st = IDLE;
         active--;
         idle.push_back(ci);
     }
@@ -181,7 +228,7 @@ struct Worker {
             }
             if (r < 0 && errno == EINTR) continue;
             if (r < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) break;
-            if (c.st != IDLE || r < 0) fail(c);  // closed under a request (prove error: the server writes nothing and drops the connection)
+            if (!c.q.empty() || r < 0) fail(c);  // closed under a request (prove error: the server writes nothing and drops the connection)
             else {
                 epoll_ctl(ep, EPOLL_CTL_DEL, c.fd, nullptr);
                 close(c.fd);
@@ -191,27 +238,44 @@ struct Worker {
             return;
         }
         tlv::Bytes payload;
-        const int got = take_frame(c, &payload);
-        if (got < 0) return fail(c);
-        if (got == 0) return;
-        const auto now = Clock::now();
-        const auto base = rate > 0 ? c.t_sched : c.t_sent;
-        if (c.st == WAIT_PROOF) {
-            lat_p.push_back(std::chrono::duration<float, std::milli>(now - base).count());
-            c.t_proof = now;
-            if (!sh->do_verify) return op_done(ci);
-            tlv::Bytes body(1, 0x02), frame;
-            tlv::write(body, payload);
-            const Bid& b = sh->bids[c.bid];
-            body.insert(body.end(), b.verify_tail.begin(), b.verify_tail.end());
-            tlv::write(frame, body);
-            c.st = WAIT_VERIFY;
-            if (!write_all(c.fd, frame.data(), frame.size())) fail(c);
-        } else if (c.st == WAIT_VERIFY) {
-            if (payload.size() != 1 || payload[0] != 0x01) sh->rejected++;
-            lat_v.push_back(std::chrono::duration<float, std::milli>(now - c.t_proof).count());
-            lat_o.push_back(std::chrono::duration<float, std::milli>(now - base).count());
-            op_done(ci);
+        for (;;) {  // every whole frame that has arrived, each the reply to the oldest outstanding request
+            const int got = take_frame(c, &payload);
+            if (got < 0) return fail(c);
+            if (got == 0) return;
+            if (c.q.empty()) return fail(c);  // a reply nobody asked for
+            Expect e = c.q.front();
+            c.q.pop_front();
+            const auto now = Clock::now();
+            const auto base = rate > 0 ? e.t_sched : e.t_sent;
+            if (!e.verify) {
+                if (payload.size() <= 1) {  // a verdict where a proof is due: the replies are out of order
+                    c.q.push_front(e);
+                    return fail(c);
+                }
+                lat_p.push_back(std::chrono::duration<float, std::milli>(now - base).count());
+                if (!sh->do_verify) {
+                    op_done(ci);
+                    continue;
+                }
+                tlv::Bytes body(1, 0x02), frame;
+                tlv::write(body, payload);
+                const Bid& b = sh->bids[e.bid];
+                body.insert(body.end(), b.verify_tail.begin(), b.verify_tail.end());
+                tlv::write(frame, body);
+                e.verify = true;
+                e.t_proof = now;
+                c.q.push_back(e);  // written after everything outstanding: answered after it
+                if (!send_some(c, frame.data(), frame.size())) return fail(c);
+            } else {
+                if (payload.size() != 1) {  // a proof where a verdict is due
+                    c.q.push_front(e);
+                    return fail(c);
+                }
+                if (payload[0] != 0x01) sh->rejected++;
+                lat_v.push_back(std::chrono::duration<float, std::milli>(now - e.t_proof).count());
+                lat_o.push_back(std::chrono::duration<float, std::milli>(now - base).count());
+                op_done(ci);
+            }
         }
     }
     int take_idle() {
@@ -225,7 +289,12 @@ struct Worker {
     void pump(int timeout_ms) {
         epoll_event evs[256];
         const int n = epoll_wait(ep, evs, 256, timeout_ms);
-        for (int i = 0; i < n; i++) on_readable((int)evs[i].data.u32);
+        for (int i = 0; i < n; i++) {
+            const int ci = (int)evs[i].data.u32;
+            Conn& c = conns[(size_t)ci];
+            if ((evs[i].events & EPOLLOUT) && c.fd >= 0 && !flush(c)) fail(c);
+            if ((evs[i].events & ~(uint32_t)EPOLLOUT) && c.fd >= 0) on_readable(ci);
+        }
     }
     void run_closed(int n_conns) {
         for (int i = 0; i < n_conns; i++)
@@ -289,7 +358,7 @@ struct Worker {
 int main(int argc, char** argv) {
     Shared sh;
     std::string file;
-    int conns = 64, threads = 2, preconnect = 0;
+    int conns = 64, threads = 2, preconnect = 0, depth = 1;
     double rate = 0, duration = 10;
     sh.ops = 1024;
     for (int i = 1; i < argc; i++) {
@@ -302,13 +371,17 @@ int main(int argc, char** argv) {
         else if (a == "--duration" && i + 1 < argc) duration = atof(argv[++i]);
         else if (a == "--threads" && i + 1 < argc) threads = atoi(argv[++i]);
         else if (a == "--preconnect" && i + 1 < argc) preconnect = atoi(argv[++i]);
+        else if (a == "--depth" && i + 1 < argc) depth = atoi(argv[++i]);
         else if (a == "--no-verify") sh.do_verify = false;
+        else if (a == "--verify-only") sh.verify_only = true;
         else {
             fprintf(stderr,
-                    "usage: %s --socket PATH --requests FILE [--connections C] [--ops M | --rate R --duration S] [--threads T] [--no-verify]\n", argv[0]);
+                    "usage: %s --socket PATH --requests FILE [--connections C] [--ops M [--depth K] | --rate R --duration S] [--threads T] [--no-verify]\n",
+                    argv[0]);
             return 2;
         }
     }
+    if (depth < 1 || rate > 0) depth = 1;  // pipelining is the closed loop's: an open-loop arrival takes a connection of its own
     {
         rlimit rl;
         if (getrlimit(RLIMIT_NOFILE, &rl) == 0 && rl.rlim_cur < rl.rlim_max) {
@@ -352,6 +425,7 @@ int main(int argc, char** argv) {
         ws[(size_t)t].duration = duration;
         ws[(size_t)t].cap = conns / threads + (t < conns % threads ? 1 : 0);
         ws[(size_t)t].preconnect = preconnect / threads;
+        ws[(size_t)t].depth = depth;
     }
     const auto T0 = Clock::now();
     std::vector<std::thread> th;
@@ -390,12 +464,12 @@ int main(int argc, char** argv) {
     printf("{\"mode\": \"%s\", \"connections\": %zu, \"ops\": %zu, \"wall_s\": %.3f, \"proofs_per_s\": %.1f, \"verifies_per_s\": %.1f, \"failed\": %ld, "
            "\"rejected\": %ld, \"prove_latency_ms\": {\"p50\": %.2f, \"p99\": %.2f}, \"verify_latency_ms\": {\"p50\": %.2f, \"p99\": %.2f}, "
            "\"op_latency_ms\": {\"p50\": %.2f, \"p99\": %.2f}",
-           rate > 0 ? "open-loop (Poisson arrivals; latency from the scheduled arrival)" : "closed-loop", n_conns, p.size(), wall, p.size() / wall,
+           rate > 0 ? "open-loop (Poisson arrivals; latency from the scheduled arrival)" : "closed-loop", n_conns, sh.verify_only ? v.size() : p.size(), wall, p.size() / wall,
            v.size() / wall, sh.failed.load(), sh.rejected.load(), at(p, 0.5), at(p, 0.99), at(v, 0.5), at(v, 0.99), at(o, 0.5), at(o, 0.99));
     if (rate > 0)
         printf(", \"offered_per_s\": %.1f, \"duration_s\": %.1f, \"arrivals\": %ld, \"max_client_backlog\": %zu, \"connection_cap\": %d", rate, duration,
                arrivals, max_backlog, conns);
-    printf(", \"sustained_ops_per_s\": %.1f, \"generator_threads\": %d, \"dial_ms_total\": %.1f, \"dial_retries\": %ld}\n", sustained, threads,
-           g_dial_us.load() / 1e3, g_dial_retries.load());
+    printf(", \"sustained_ops_per_s\": %.1f, \"depth\": %d, \"generator_threads\": %d, \"dial_ms_total\": %.1f, \"dial_retries\": %ld}\n", sustained, depth,
+           threads, g_dial_us.load() / 1e3, g_dial_retries.load());
     return sh.failed.load() || sh.rejected.load() ? 1 : 0;
 }

@@ -20,6 +20,12 @@
 // engine's rate.)  With --devices a,b,.. the engine handle is a device pool (include/bbp.h): one combiner deals the batches to
 // the least-loaded GPU.  The engine is loaded with dlopen (--engine), so this binary holds no GPU code and the CPU-tier tests
 // run it against a stub.
+//
+// Pipelining.  A peer may write frames without waiting for replies: up to --pipeline-depth requests of one connection are with
+// the engine at once, so one connection can fill a device batch.  Every dispatched frame owns a slot in the connection's reply
+// FIFO; completions arrive in any order (prove and verify are separate combiner lanes, two batches each) and only the ready prefix
+// of the FIFO is written, so the peer sees replies strictly in request order.  A connection at depth, or with more than
+// MAX_UNSENT reply bytes waiting, is not read until it falls below both: the socket buffer pushes back on the peer.
 #include <dlfcn.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -38,6 +44,7 @@
 
 #include <atomic>
 #include <chrono>
+#include <deque>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -114,23 +121,44 @@ struct Engine {
 static Engine g_eng;
 static std::atomic<uint64_t> g_served{0}, g_errors{0}, g_next_id{1};
 static std::atomic<int> g_live{0}, g_inflight{0};
+static std::atomic<int> g_peak_inflight{0};      // the most requests with the engine at once (logged at shutdown)
+static std::atomic<uint32_t> g_deepest{0};       // the most requests any ONE connection had with the engine at once
 static int g_max_conn = 65536;
-static volatile sig_atomic_t g_stop = 0;
+static uint32_t g_depth = 64;                    // --pipeline-depth: requests of one connection with the engine at once
+static int g_max_inflight = -1;                  // --max-inflight: beyond a connection's first request, requests are admitted only below this (default: --max-connections)
+static std::atomic<int> g_stop{0};  // set by the signal handler and by the I/O thread that sees a device failure, read by every I/O thread (lock-free: safe in a handler)
 static std::atomic<int> g_fatal{0};  // the engine handle reported BBP_ERR_DEVICE: stop accepting, drain, exit non-zero
 static int g_listen_fd = -1;
 constexpr int EXIT_ENGINE_DEAD = 3;
 
 constexpr uint64_t MAX_FRAME = 1u << 16;  // the largest legitimate request (verify, N = 202) is ~ 16 KB; per-connection buffering is bounded by 2 x this
+constexpr size_t MAX_UNREAD = 2 * MAX_FRAME + 16;  // unparsed bytes held per connection: kept by not reading beyond it
+constexpr size_t MAX_UNSENT = 1u << 20;   // reply bytes of one connection not yet taken by its peer (written or waiting in the FIFO): above it the connection is not read
 
 // ---- one connection ---------------------------------------------------------------------------------------------------------------
+// one dispatched frame's place in the reply order
+struct Slot {
+    bool ready = false;
+    bool poison = false;  // the request's outcome is "nothing written, connection dropped": `why` is logged when the slot is reached
+    tlv::Bytes reply;
+    std::string why;
+};
 struct Conn {
     int fd = -1;
     uint64_t id = 0;
     tlv::Bytes in;      // bytes received and not yet consumed
     tlv::Bytes out;     // reply bytes not yet written
     size_t out_off = 0;
-    bool busy = false;  // a request of this connection is with the engine: replies keep request order, the next frame waits
-    bool eof = false;   // the peer has closed its sending side: close once the pending reply is out
+    std::deque<Slot> fifo;   // reply slots in request order; fifo[0] belongs to sequence number head_seq
+    uint64_t head_seq = 0;
+    size_t fifo_bytes = 0;   // reply bytes in ready slots that wait behind an unready one
+    uint32_t engine = 0;     // requests of this connection with the engine (<= --pipeline-depth)
+    uint32_t mask = 0;       // the epoll interest set as last registered
+    bool poisoned = false;   // a poison slot is in the FIFO: nothing after it is dispatched, nothing more is read
+    bool closing = false;    // the poison slot was reached: the connection goes once `out` is written
+    bool held = false;       // its next frame waits for --max-inflight; the completion path resumes it
+    bool touched = false;    // in the reactor's list of connections to settle after this round of completions
+    bool eof = false;   // the peer has closed its sending side: close once every reply is out
     bool want_out = false;
 };
 
@@ -139,6 +167,7 @@ struct Reactor;
 struct Pending {
     Reactor* reactor = nullptr;
     uint64_t conn_id = 0;
+    uint64_t seq = 0;  // the reply slot of this request in its connection's FIFO
     uint8_t opcode = 0;
     uint32_t n_items = 0;
     tlv::Bytes record;  // prove: the engine writes the proof record here
@@ -156,10 +185,21 @@ struct Reactor {
 
     void run();
     void accept_some();
+    std::vector<uint64_t> touched;  // connections with a completion in this round, settled once each
+    std::vector<uint64_t> held;     // connections whose next frame waits for --max-inflight
+
+    enum Verdict { TAKEN, POISON, HOLD };  // dispatch: the frame got a slot / poisons the connection / waits for --max-inflight
     void on_readable(Conn* c);
     void process(Conn* c);
-    bool dispatch(Conn* c, const uint8_t* req, size_t len);
+    Verdict dispatch(Conn* c, const uint8_t* req, size_t len, std::string* why);
+    bool admit(Conn* c);
+    Slot& push_slot(Conn* c);
+    void poison(Conn* c, const std::string& why);
     void complete(Pending* p);
+    void settle(Conn* c);
+    void settle_id(uint64_t id);
+    void resume_held();
+    void interest(Conn* c);
     void flush(Conn* c);
     void drop(Conn* c);
     void set_listening(bool on);
@@ -215,7 +255,7 @@ void Reactor::accept_some() {
         c->id = g_next_id.fetch_add(1);
         epoll_event ev;
         memset(&ev, 0, sizeof ev);
-        ev.events = EPOLLIN | EPOLLRDHUP;
+        ev.events = c->mask = EPOLLIN | EPOLLRDHUP;
         ev.data.u64 = c->id;
         if (epoll_ctl(ep, EPOLL_CTL_ADD, fd, &ev) != 0) {
             close(fd);
@@ -226,6 +266,23 @@ void Reactor::accept_some() {
     }
 }
 
+// The interest set follows the connection's state.  It is READ only while it may take another frame: not after the peer's EOF (the
+// level-triggered RDHUP would spin), not once poisoned, not at --pipeline-depth, not with MAX_UNSENT reply bytes waiting, not while
+// held back by --max-inflight, and not with MAX_UNREAD bytes already buffered.  Whatever the peer sends meanwhile stays in the
+// socket buffer, and the kernel makes the peer wait.  (EPOLLHUP and EPOLLERR are reported whatever the set is.)
+void Reactor::interest(Conn* c) {
+    const bool rd = !c->eof && !c->poisoned && !c->held && c->engine < g_depth && c->in.size() < MAX_UNREAD &&
+                    (c->out.size() - c->out_off) + c->fifo_bytes <= MAX_UNSENT;
+    const uint32_t want = (rd ? EPOLLIN | EPOLLRDHUP : 0) | (c->want_out ? EPOLLOUT : 0);
+    if (want == c->mask) return;
+    epoll_event ev;
+    memset(&ev, 0, sizeof ev);
+    ev.events = want;
+    ev.data.u64 = c->id;
+    if (epoll_ctl(ep, EPOLL_CTL_MOD, c->fd, &ev) == 0) c->mask = want;
+}
+
+// writes what it can of c->out; may drop the connection (the peer is gone)
 void Reactor::flush(Conn* c) {
     while (c->out_off < c->out.size()) {
         const ssize_t w = send(c->fd, c->out.data() + c->out_off, c->out.size() - c->out_off, MSG_NOSIGNAL);
@@ -235,14 +292,7 @@ void Reactor::flush(Conn* c) {
         }
         if (w < 0 && errno == EINTR) continue;
         if (w < 0 && (errno == EAGAIN || errno == EWOULDBLOCK)) {
-            if (!c->want_out) {
-                epoll_event ev;
-                memset(&ev, 0, sizeof ev);
-                ev.events = EPOLLIN | EPOLLRDHUP | EPOLLOUT;
-                ev.data.u64 = c->id;
-                epoll_ctl(ep, EPOLL_CTL_MOD, c->fd, &ev);
-                c->want_out = true;
-            }
+            c->want_out = true;
             return;
         }
         drop(c);  // the peer is gone
@@ -250,39 +300,64 @@ void Reactor::flush(Conn* c) {
     }
     c->out.clear();
     c->out_off = 0;
-    if (c->want_out) {
-        epoll_event ev;
-        memset(&ev, 0, sizeof ev);
-        ev.events = EPOLLIN | EPOLLRDHUP;
-        ev.data.u64 = c->id;
-        epoll_ctl(ep, EPOLL_CTL_MOD, c->fd, &ev);
-        c->want_out = false;
+    c->want_out = false;
+}
+
+Slot& Reactor::push_slot(Conn* c) {
+    c->fifo.emplace_back();
+    return c->fifo.back();
+}
+
+// the frame at the next position has the outcome "nothing written, connection dropped": replies before it still go out in order
+void Reactor::poison(Conn* c, const std::string& why) {
+    Slot& s = push_slot(c);
+    s.ready = s.poison = true;
+    s.why = why;
+    c->poisoned = true;
+    tlv::Bytes().swap(c->in);  // nothing after it is dispatched
+}
+
+// a request is about to go to the engine.  A connection with none there is always admitted (the request-response client of before:
+// no starvation); further requests of a connection only while fewer than --max-inflight are with the engine.
+bool Reactor::admit(Conn* c) {
+    int now;
+    if (c->engine == 0) now = ++g_inflight;
+    else {
+        int cur = g_inflight.load();
+        do {
+            if (cur >= g_max_inflight) return false;
+        } while (!g_inflight.compare_exchange_weak(cur, cur + 1));
+        now = cur + 1;
+    }
+    int peak = g_peak_inflight.load();
+    while (now > peak && !g_peak_inflight.compare_exchange_weak(peak, now)) {
+    }
+    return true;
+}
+
+static void sent_to_engine(Conn* c) {
+    c->engine++;
+    uint32_t d = g_deepest.load(std::memory_order_relaxed);
+    while (c->engine > d && !g_deepest.compare_exchange_weak(d, c->engine)) {
     }
 }
 
-// one request frame (payload of the outer TLV element, main.rs:70-79).  false = the connection is to be dropped without a reply
-bool Reactor::dispatch(Conn* c, const uint8_t* req, size_t len) {
-    if (len == 0) {
-        logf(0, "Error resolving the request: The request was not provided");
-        g_errors++;
-        return false;
-    }
+// one request frame (payload of the outer TLV element, main.rs:70-79).  TAKEN: it has a reply slot (with the engine, or answered
+// already).  POISON: its outcome is "nothing written, connection dropped" (*why says which).  HOLD: not consumed, --max-inflight.
+Reactor::Verdict Reactor::dispatch(Conn* c, const uint8_t* req, size_t len, std::string* why) {
+    if (len == 0) return *why = "The request was not provided", POISON;
     const uint8_t opcode = req[0];
-    std::string why;
     if (opcode == OP_PROVE) {
         ProveRequest pr;
-        if (!parse_prove_request(req + 1, len - 1, &pr, &why)) {
-            logf(0, "Error resolving the request: %s", why.c_str());
-            g_errors++;
-            return false;  // prove error -> no payload (main.rs:86-92 via try_result_future!), connection dropped
-        }
+        if (!parse_prove_request(req + 1, len - 1, &pr, why)) return POISON;  // prove error -> no payload (main.rs:86-92 via try_result_future!), connection dropped
+        if (!admit(c)) return HOLD;
         Pending* p = new Pending();
         p->reactor = this;
         p->conn_id = c->id;
+        p->seq = c->head_seq + c->fifo.size();
         p->opcode = opcode;
         p->n_items = pr.n_items;
         p->record.resize(g_eng.record_size(pr.n_items));
-        g_inflight++;
         const double t0 = g_trace ? now_ms() : 0;
         const int32_t rc = g_eng.prove_async(g_eng.ctx, pr.scalars7, pr.pub_list.data(), pr.n_items, pr.toggle, nullptr, p->record.data(), on_engine_done, p);
         if (g_trace) {
@@ -292,85 +367,146 @@ bool Reactor::dispatch(Conn* c, const uint8_t* req, size_t len) {
         }
         if (rc != BBP_OK) {  // decided at once: the callback will not fire
             g_inflight--;
-            logf(0, "Error resolving the request: engine status %d: %s", rc, g_eng.last_error(g_eng.ctx));
+            *why = "engine status " + std::to_string(rc) + ": " + g_eng.last_error(g_eng.ctx);
             delete p;
-            g_errors++;
-            return false;
+            return POISON;
         }
-        c->busy = true;
-        return true;
+        push_slot(c);
+        sent_to_engine(c);
+        return TAKEN;
     }
     if (opcode == OP_VERIFY) {
         VerifyRequest vr;
         int32_t rc = BBP_ERR_FORMAT;
-        if (parse_verify_request(req + 1, len - 1, &vr, &why)) {
+        if (parse_verify_request(req + 1, len - 1, &vr, why)) {
+            if (!admit(c)) return HOLD;
             Pending* p = new Pending();
             p->reactor = this;
             p->conn_id = c->id;
+            p->seq = c->head_seq + c->fifo.size();
             p->opcode = opcode;
-            g_inflight++;
             rc = g_eng.verify_async(g_eng.ctx, vr.record.data(), (uint32_t)vr.record.size(), vr.score, vr.z_img, vr.seed, vr.pub_list.data(), vr.n_items,
                                     on_engine_done, p);
             if (rc == BBP_OK) {
-                c->busy = true;
-                return true;
+                push_slot(c);
+                sent_to_engine(c);
+                return TAKEN;
             }
             g_inflight--;
             delete p;  // the structural parse on the host already decided: answered right here
             if (rc > BBP_ERR_FORMAT) logf(1, "verify: engine status %d: %s", rc, g_eng.last_error(g_eng.ctx));
         } else {
-            logf(3, "verify request rejected while parsing: %s", why.c_str());
+            logf(3, "verify request rejected while parsing: %s", why->c_str());
         }
-        const tlv::Bytes reply = frame(tlv::Bytes(1, 0x00));  // main.rs:95-99: parse errors and verification failures both answer 0x00
-        c->out.insert(c->out.end(), reply.begin(), reply.end());
-        g_served++;
-        logf(4, "Request resolved");
-        return true;
+        Slot& s = push_slot(c);  // main.rs:95-99: parse errors and verification failures both answer 0x00 -- in this request's place in the order
+        s.reply = frame(tlv::Bytes(1, 0x00));
+        s.ready = true;
+        c->fifo_bytes += s.reply.size();
+        return TAKEN;
     }
-    logf(0, "Error resolving the request: Undefined operation code");
-    g_errors++;
-    return false;
+    return *why = "Undefined operation code", POISON;
 }
 
-// frames that are complete in c->in, in order, one engine request at a time
+// frames that are complete in c->in, in arrival order, while fewer than --pipeline-depth requests of the connection are with the
+// engine.  Touches neither the socket nor the connection's lifetime: settle() follows every call.
 void Reactor::process(Conn* c) {
     size_t pos = 0;
-    bool alive = true;
-    while (alive && !c->busy) {
+    std::string why;
+    const bool was_held = c->held;
+    c->held = false;
+    while (!c->poisoned && c->engine < g_depth) {
         const uint8_t* p = c->in.data() + pos;
         const size_t avail = c->in.size() - pos;
-        if (!tlv::header_complete(p, avail)) break;
-        uint64_t len;
-        const size_t h = tlv::parse_header(p, avail, &len);
-        if (!h || len > MAX_FRAME) {
-            logf(0, "Error resolving the request: unreadable frame");
-            g_errors++;
-            alive = false;
+        uint64_t len = 0;
+        const size_t h = tlv::header_complete(p, avail) ? tlv::parse_header(p, avail, &len) : 0;
+        if (tlv::header_complete(p, avail) && (!h || len > MAX_FRAME)) {
+            poison(c, "unreadable frame");
+            return;
+        }
+        if (!h || avail - h < len) {
+            if (c->eof && avail) poison(c, "unreadable frame");  // the stream ended inside a frame
             break;
         }
-        if (avail - h < len) break;
-        alive = dispatch(c, p + h, (size_t)len);
+        why.clear();
+        const Verdict v = dispatch(c, p + h, (size_t)len, &why);
+        if (v == POISON) {
+            poison(c, why);
+            return;
+        }
+        if (v == HOLD) {
+            c->held = true;
+            break;
+        }
         pos += h + (size_t)len;
     }
-    if (!alive) {
+    if (c->poisoned) return;
+    if (c->held && !was_held) held.push_back(c->id);
+    if (pos) c->in.erase(c->in.begin(), c->in.begin() + (ptrdiff_t)pos);
+}
+
+// After any change to a connection: move the ready prefix of the reply FIFO to `out`, write, and decide whether the connection
+// stays.  The one place that closes a connection in an orderly way; may drop it.
+void Reactor::settle(Conn* c) {
+    while (!c->closing && !c->fifo.empty() && c->fifo.front().ready) {
+        Slot& s = c->fifo.front();
+        if (s.poison) {  // every reply before it is in `out`: this request gets no payload, the connection goes
+            logf(0, "Error resolving the request: %s", s.why.c_str());
+            g_errors++;
+            c->closing = true;
+            break;
+        }
+        c->fifo_bytes -= s.reply.size();
+        c->out.insert(c->out.end(), s.reply.begin(), s.reply.end());
+        c->fifo.pop_front();
+        c->head_seq++;
+        g_served++;
+        logf(4, "Request resolved");
+    }
+    if (c->out_off < c->out.size()) {
+        const uint64_t id = c->id;
+        flush(c);
+        if (conns.find(id) == conns.end()) return;
+    }
+    if (c->out.empty() && (c->closing || (c->eof && c->fifo.empty()))) {
         drop(c);
         return;
     }
-    if (pos) c->in.erase(c->in.begin(), c->in.begin() + (ptrdiff_t)pos);
-    if (!c->out.empty()) flush(c);
+    interest(c);
+}
+
+void Reactor::settle_id(uint64_t id) {
+    auto it = conns.find(id);
+    if (it == conns.end()) return;
+    Conn* c = it->second.get();
+    c->touched = false;
+    process(c);
+    settle(c);
+}
+
+// connections whose next frame waited for --max-inflight: requests have come back, try them again
+void Reactor::resume_held() {
+    if (held.empty()) return;
+    std::vector<uint64_t> ids;
+    ids.swap(held);
+    for (uint64_t id : ids) {
+        auto it = conns.find(id);
+        if (it == conns.end() || !it->second->held) continue;
+        Conn* c = it->second.get();
+        c->held = false;  // process() lists it again if it still has to wait
+        process(c);
+        settle(c);
+    }
 }
 
 void Reactor::on_readable(Conn* c) {
     uint8_t buf[16384];
-    for (;;) {
-        const ssize_t r = read(c->fd, buf, sizeof buf);
+    while (c->in.size() < MAX_UNREAD) {  // never more than MAX_UNREAD unparsed bytes: the rest waits in the socket buffer
+        const size_t room = MAX_UNREAD - c->in.size();
+        const size_t want = room < sizeof buf ? room : sizeof buf;
+        const ssize_t r = read(c->fd, buf, want);
         if (r > 0) {
-            if (c->in.size() + (size_t)r > 2 * MAX_FRAME + 16) {  // a peer that keeps sending while its request is with the engine
-                drop(c);
-                return;
-            }
             c->in.insert(c->in.end(), buf, buf + r);
-            if ((size_t)r < sizeof buf) break;
+            if ((size_t)r < want) break;
             continue;
         }
         if (r < 0 && errno == EINTR) continue;
@@ -378,21 +514,12 @@ void Reactor::on_readable(Conn* c) {
         c->eof = true;  // 0 = the peer closed (or an error: same treatment)
         break;
     }
-    const uint64_t id = c->id;
     process(c);
-    auto it = conns.find(id);
-    if (it == conns.end()) return;  // dropped while processing
-    c = it->second.get();
-    if (c->eof && !c->busy && c->out.empty()) {
-        if (!c->in.empty()) {
-            logf(0, "Error resolving the request: unreadable frame");  // the stream ended inside a frame
-            g_errors++;
-        }
-        drop(c);
-    }
+    settle(c);
 }
 
-// a request is back from the engine: write the reply (this thread owns the connection), then look at the next frame
+// a request is back from the engine: fill its reply slot (this thread owns the connection).  The connection is settled once per
+// round of completions, so a pipeline's replies leave in one write.
 void Reactor::complete(Pending* p) {
     std::unique_ptr<Pending> own(p);
     g_inflight--;
@@ -409,37 +536,36 @@ void Reactor::complete(Pending* p) {
             g_stop = 1;
             if (g_listen_fd >= 0) shutdown(g_listen_fd, SHUT_RDWR);
         }
+        // Every other request of the connection's pipeline goes with it: those of the failed call come back BBP_ERR_DEVICE to no
+        // connection, and a verdict that is ready behind an unjudged request is never written.
         g_errors++;
         if (it != conns.end()) drop(it->second.get());
         return;
     }
     if (it == conns.end()) return;  // the peer went away meanwhile
     Conn* c = it->second.get();
-    c->busy = false;
+    c->engine--;
+    if (!c->touched) {
+        c->touched = true;
+        touched.push_back(c->id);
+    }
+    if (c->closing) return;  // a request dispatched before the poisoned one was reached: its result has nowhere to go
+    Slot& s = c->fifo[(size_t)(p->seq - c->head_seq)];
+    s.ready = true;
     if (p->opcode == OP_PROVE) {
-        if (p->status != BBP_OK) {
-            logf(0, "Error resolving the request: engine status %d: %s", p->status, p->err.c_str());
-            g_errors++;
-            drop(c);  // prove error -> nothing written
+        if (p->status != BBP_OK) {  // prove error -> nothing written: the connection is poisoned at this request's position
+            s.poison = true;
+            s.why = "engine status " + std::to_string(p->status) + ": " + p->err;
+            c->poisoned = true;
+            tlv::Bytes().swap(c->in);
             return;
         }
-        const tlv::Bytes reply = frame(encode_proof(p->record.data(), BBP_R1CS_PROOF_BYTES, p->n_items));
-        c->out.insert(c->out.end(), reply.begin(), reply.end());
+        s.reply = frame(encode_proof(p->record.data(), BBP_R1CS_PROOF_BYTES, p->n_items));
     } else {
         if (p->status > BBP_ERR_FORMAT) logf(1, "verify: engine status %d: %s", p->status, p->err.c_str());
-        const tlv::Bytes reply = frame(tlv::Bytes(1, p->status == BBP_OK ? 0x01 : 0x00));
-        c->out.insert(c->out.end(), reply.begin(), reply.end());
+        s.reply = frame(tlv::Bytes(1, p->status == BBP_OK ? 0x01 : 0x00));
     }
-    g_served++;
-    logf(4, "Request resolved");
-    const uint64_t id = c->id;
-    flush(c);
-    if (conns.find(id) == conns.end()) return;
-    process(c);
-    auto again = conns.find(id);
-    if (again == conns.end()) return;
-    c = again->second.get();
-    if (c->eof && !c->busy && c->out.empty()) drop(c);
+    c->fifo_bytes += s.reply.size();
 }
 
 void Reactor::run() {
@@ -477,35 +603,24 @@ void Reactor::run() {
                 }
                 const double c0 = g_trace ? now_ms() : 0;
                 for (Pending* p : batch) complete(p);
+                for (size_t k = 0; k < touched.size(); k++) settle_id(touched[k]);  // the next frames of each, its ready replies in one write
+                touched.clear();
+                resume_held();
                 if (g_trace) t_comp_ms += now_ms() - c0;
                 continue;
             }
             auto it = conns.find(id);
             if (it == conns.end()) continue;
             Conn* c = it->second.get();
-            if (evs[i].events & EPOLLOUT) {
-                flush(c);
-                if (conns.find(id) == conns.end()) continue;
-                if (c->eof && !c->busy && c->out.empty()) {
-                    drop(c);
-                    continue;
-                }
+            if ((evs[i].events & (EPOLLHUP | EPOLLERR)) && !(evs[i].events & EPOLLIN)) {
+                drop(c);  // the peer is gone altogether: what it still has with the engine finds no connection when it completes
+                continue;
             }
-            if (evs[i].events & (EPOLLIN | EPOLLRDHUP | EPOLLHUP | EPOLLERR)) {
-                if ((evs[i].events & (EPOLLHUP | EPOLLERR)) && !(evs[i].events & EPOLLIN)) {
-                    c->eof = true;
-                    if (!c->busy) drop(c);
-                    else epoll_ctl(ep, EPOLL_CTL_DEL, c->fd, nullptr);  // the pending completion finds it and drops it
-                    continue;
-                }
-                if (c->eof) {  // already seen: nothing more to read, the level-triggered RDHUP would spin
-                    epoll_event ev;
-                    memset(&ev, 0, sizeof ev);
-                    ev.events = c->want_out ? EPOLLOUT : 0;
-                    ev.data.u64 = c->id;
-                    epoll_ctl(ep, EPOLL_CTL_MOD, c->fd, &ev);
-                    continue;
-                }
+            if (evs[i].events & EPOLLOUT) {
+                settle(c);
+                if (conns.find(id) == conns.end()) continue;
+            }
+            if ((evs[i].events & (EPOLLIN | EPOLLRDHUP)) && (c->mask & EPOLLIN)) {
                 const double r0 = g_trace ? now_ms() : 0;
                 on_readable(c);
                 if (g_trace) t_read_ms += now_ms() - r0;
@@ -531,7 +646,12 @@ static void usage(const char* argv0) {
     fprintf(stderr,
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
-            "          [--check-proofs] [--entropy os|device] [--verify-mixing on|off] [--verify-rounds on|off]\n",
+            "          [--check-proofs] [--entropy os|device] [--verify-mixing on|off] [--verify-rounds on|off]\n"
+            "          [--pipeline-depth D] [--max-inflight M]\n"
+            "  --pipeline-depth D  requests of ONE connection with the engine at once, replies in request order (1..4096, default 64;\n"
+            "                      1 = one request per connection at a time)\n"
+            "  --max-inflight M    beyond each connection's first request, requests are admitted only while fewer than M are with\n"
+            "                      the engine (default: the value of --max-connections)\n",
             argv0);
 }
 
@@ -576,6 +696,11 @@ int main(int argc, char** argv) {
         else if (a == "--max-batch") max_batch = (uint32_t)atoi(val());
         else if (a == "--max-connections") g_max_conn = atoi(val());
         else if (a == "--io-threads") io_threads = atoi(val());
+        else if (a == "--pipeline-depth") {
+            const long d = atol(val());
+            g_depth = (uint32_t)(d < 1 ? 1 : d > 4096 ? 4096 : d);
+        }
+        else if (a == "--max-inflight") g_max_inflight = atoi(val());
         else if (a == "--verify-aggregate") setenv("BBP_VERIFY_AGGREGATE", val(), 1);  // opcode-2 batches of >= 2 G proofs are checked in groups of G with
                                                                                          // per-proof fallback: same verdicts, 2-3x the rate (include/bbp.h)
         else if (a == "--check-proofs") check_proofs = true;
@@ -720,6 +845,7 @@ int main(int argc, char** argv) {
         const int hi = fcntl(0, F_DUPFD_CLOEXEC, g_max_conn + 32);
         if (hi >= 0) close(hi);
     }
+    if (g_max_inflight < 1) g_max_inflight = g_max_conn;  // one request per connection was the worst case before pipelining: memory does not grow by default
 
     struct sigaction sa;
     memset(&sa, 0, sizeof sa);
@@ -757,8 +883,8 @@ int main(int argc, char** argv) {
         r->set_listening(true);
         g_reactors.push_back(std::move(r));
     }
-    logf(2, "listening on %s (engine %s, %zu device context(s), batching window %u us, max batch %u, %d I/O thread(s))", bind_path.c_str(),
-         engine_path.c_str(), g_eng.n_devices, window_us, max_batch, io_threads);
+    logf(2, "listening on %s (engine %s, %zu device context(s), batching window %u us, max batch %u, %d I/O thread(s), pipeline depth %u, max inflight %d)",
+         bind_path.c_str(), engine_path.c_str(), g_eng.n_devices, window_us, max_batch, io_threads, g_depth, g_max_inflight);
     try {
         for (auto& r : g_reactors) r->th = std::thread([p = r.get()] { p->run(); });
     } catch (const std::exception& e) {
@@ -788,8 +914,9 @@ int main(int argc, char** argv) {
     uint64_t calls = 0, reqs = 0;
     uint32_t biggest = 0;
     g_eng.batching_stats(g_eng.ctx, &calls, &reqs, &biggest);
-    logf(2, "served %llu requests (%llu errors) in %llu device calls, largest batch %u", (unsigned long long)g_served.load(),
-         (unsigned long long)g_errors.load(), (unsigned long long)calls, biggest);
+    logf(2, "served %llu requests (%llu errors) in %llu device calls, largest batch %u, deepest pipeline %u", (unsigned long long)g_served.load(),
+         (unsigned long long)g_errors.load(), (unsigned long long)calls, biggest, g_deepest.load());
+    logf(2, "peak requests with the engine at once: %d (max inflight %d)", g_peak_inflight.load(), g_max_inflight);
     if (g_eng.n_devices > 1)
         for (size_t i = 0; i < g_eng.n_devices; i++) {
             uint64_t c = 0, q = 0;
