@@ -17,7 +17,7 @@ LAYOUT_BLIND_G_H, LAYOUT_BLIND_G = 0, 1
 BASE_BBLIND, BASE_G0, BASE_H0, BASE_B, NUM_BASES = 0, 1, 2049, 4097, 4098
 R1CS_PROOF_BYTES = 1121
 ENTROPY_PROVE, ENTROPY_VERIFY = 0, 1            # bbp_draw_entropy_dev kinds
-ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE = 0, 1  # bbp_set_entropy_source
+ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE, ENTROPY_SOURCE_HEDGED = 0, 1, 2  # bbp_set_entropy_source
 TABLE_GENS, TABLE_PTABLE, TABLE_COMB, TABLE_BTAB = 0, 1, 2, 3  # bbp_debug_table
 TABLE_IDX_AI, TABLE_IDX_AO, TABLE_IDX_S1, TABLE_IDX_IPA, TABLE_IDX_VER = 4, 5, 6, 7, 8  # ... its index lists: which = list | N << 8
 VARBASE_LANES, VARBASE_PREP_SUM, VARBASE_MX_LANES, VARBASE_MX_PREP_SUM = 0, 1, 2, 3  # bbp_debug_varbase forms
@@ -86,6 +86,7 @@ SIGNATURES = {
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_corrupt_next_proof": (_i32, [_vp, _u32]),
     "bbp_draw_entropy_dev": (_i32, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "bbp_draw_entropy_hedged_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "bbp_set_entropy_source": (_i32, [_vp, _i32]),
     "bbp_debug_next_entropy_key": (_i32, [_vp, _vp]),
     "bbp_debug_challenges": (_i32, [_vp, _u32, _u32, _u32, _vp]),
@@ -571,10 +572,20 @@ class Context:
             raise ValueError("key must be 32 bytes")
         self._check(lib.bbp_draw_entropy_dev(self._h, B, N, kind, None if key is None else _buf(key), out_ptr, _stream(stream)))
 
+    def draw_entropy_hedged_dev(self, B, N, in_ptr, out_ptr, key=None, stream=None):
+        """bbp_draw_entropy_hedged_dev: B prove rows of hedged entropy into device memory at out_ptr, each under a ChaCha20 key derived
+        on the device from `key` and the row's own inputs at in_ptr (B prove-input rows).  It waits for a pending prepare_bids_dev /
+        prepare_round_dev by itself and the next prove_batch_dev waits for it.  key: 32 bytes, or None for 32 fresh OS bytes.
+        Stream-ordered, no synchronisation."""
+        if key is not None and len(key) != 32:
+            raise ValueError("key must be 32 bytes")
+        self._check(lib.bbp_draw_entropy_hedged_dev(self._h, B, N, None if key is None else _buf(key), in_ptr, out_ptr, _stream(stream)))
+
     def set_entropy_source(self, source):
-        """Where host-pointer calls without caller entropy get theirs (bbp_set_entropy_source): "os" / ENTROPY_SOURCE_OS (default) or
-        "device" / ENTROPY_SOURCE_DEVICE (one OS key per call, expanded on the device).  A pool: every member."""
-        src = {"os": ENTROPY_SOURCE_OS, "device": ENTROPY_SOURCE_DEVICE}.get(source, source)
+        """Where host-pointer calls without caller entropy get theirs (bbp_set_entropy_source): "os" / ENTROPY_SOURCE_OS (default),
+        "device" / ENTROPY_SOURCE_DEVICE (one OS key per call, expanded on the device) or "hedged" / ENTROPY_SOURCE_HEDGED (as device,
+        each prove row under a key bound to the row's own inputs).  A pool: every member."""
+        src = {"os": ENTROPY_SOURCE_OS, "device": ENTROPY_SOURCE_DEVICE, "hedged": ENTROPY_SOURCE_HEDGED}.get(source, source)
         self._check(lib.bbp_set_entropy_source(self._h, src))
 
     def debug_next_entropy_key(self, key):

@@ -10,6 +10,7 @@
 
 #include "batch.h"
 #include "chacha.h"
+#include "hedge.h"
 #include "round_bids.h"
 #include "submit.h"
 #include "witness_check.h"
@@ -166,6 +167,45 @@ __global__ void __launch_bounds__(64) k_draw_entropy(u32 n_slots, u32 N, u32 kin
     for (int i = 0; i < 8; i++) o[i] = w[i];
 }
 
+// Hedged on-device entropy (bbp_set_entropy_source(HEDGED), bbp_draw_entropy_hedged_dev; the derivation is csrc/hedge.h).
+// A device row as 64-bit words: one 64-bit load where the rows are 8-byte aligned (their stride always is), else two 32-bit loads.
+template <bool A8>
+struct HedgeRowDev {
+    const u32* p;
+    __device__ __forceinline__ u64 operator()(u32 r) const {
+        if (A8) return reinterpret_cast<const u64*>(p)[r];
+        return (u64)p[2 * r] | (u64)p[2 * r + 1] << 32;
+    }
+};
+// Row keys: one wavefront (one 64-lane workgroup) per row, the sponge spread over the lanes (hedge.h hedge_row_key_wave; 3 blocks at
+// N = 8, 50 at N = 202): the state stays in registers, a block is one 136-byte load of 17 lanes.  Row p of `in` (stride
+// prove_in_words(N)) -> 8 words at keys + key_stride p.  No LDS memory, no atomics, no private segment.
+template <bool A8>
+__global__ void __launch_bounds__(64) k_hedge_keys(u32 B, u32 N, ChachaKey key, const u32* __restrict__ in, u32* __restrict__ keys, u32 key_stride) {
+    const u32 p = blockIdx.x;
+    if (p >= B) return;
+    hedge_row_key_wave(key, N, HedgeRowDev<A8>{in + prove_in_words(N) * p}, threadIdx.x, keys + (size_t)key_stride * p);
+}
+// The draw under per-row keys: k_draw_entropy's layout (one lane per 32-byte slot, consecutive lanes on consecutive slots), the key read
+// from keys + key_stride r.  A launch covers slots slot0 .. slot0 + per - 1 of every row (the whole row: slot0 = 0, per = 5 + N).
+// keys may lie inside out (bbp_draw_entropy_hedged_dev keeps each row's key in the row's seed slot): the launch that writes that slot
+// has per = 1, so the only lane that reads the key is the one that overwrites it, after reading.
+__global__ void __launch_bounds__(64) k_draw_entropy_rowkey(u32 n_slots, u32 N, u32 row_base, u32 per, u32 slot0, const u32* keys, u32 key_stride,
+                                                            u32* out) {
+    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_slots) return;
+    const u32 r = g / per, slot = slot0 + (g - r * per);
+    ChachaKey k;
+    const u32* kp = keys + (size_t)key_stride * r;
+#pragma unroll
+    for (int i = 0; i < 8; i++) k.w[i] = kp[i];
+    u32 w[8];
+    hedge_prove_slot(k, N, row_base + r, slot, w);
+    u32* o = out + 8 * ((size_t)r * (5 + N) + slot);
+#pragma unroll
+    for (int i = 0; i < 8; i++) o[i] = w[i];
+}
+
 __global__ void k_health_or(u32* __restrict__ health, u32 bits) {
     if (threadIdx.x == 0) atomicOr(health, bits);
 }
@@ -198,6 +238,40 @@ static int32_t draw_enqueue(bbp_ctx* ctx, u32 B, u32 N, u32 kind, const ChachaKe
     }
     ScopedEvent ev(ctx, TAG_RNG, s);
     hipLaunchKernelGGL(k_draw_entropy, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (u32)n, N, kind, row_base, key, (u32*)out);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// Hedged: B prove rows (rows row_base.. of the call) into out on s from the device rows `in` under call key `key`.  keys != NULL: the
+// row keys go to keys (32 bytes per row) and stay there; NULL: each passes through its row's seed slot in `out` and is overwritten by
+// the seed (slots 0 .. 3+N first, then the seed slot by the lane that read the key).
+static int32_t hedged_draw_enqueue(bbp_ctx* ctx, u32 B, u32 N, const ChachaKey& key, u32 row_base, const void* in, void* keys, void* out, hipStream_t s) {
+    const u32 per = 5 + N;
+    const u64 n = (u64)B * per;
+    if (n > 0x7fffffffull || (u64)row_base + B > 0x100000000ull) {
+        ctx->err = "entropy draw: too many rows for one call";
+        return BBP_ERR_BAD_ARG;
+    }
+    u32* const kp = keys ? (u32*)keys : (u32*)out + 8 * (per - 1);
+    const u32 kstride = keys ? 8 : 8 * per;
+    {  // bbp_set_profiling: two TAG_RNG entries per call, the row keys and then the draw
+        ScopedEvent ev(ctx, TAG_RNG, s);
+        if (((uintptr_t)in & 7) == 0)
+            hipLaunchKernelGGL(k_hedge_keys<true>, dim3(B), dim3(64), 0, s, B, N, key, (const u32*)in, kp, kstride);
+        else
+            hipLaunchKernelGGL(k_hedge_keys<false>, dim3(B), dim3(64), 0, s, B, N, key, (const u32*)in, kp, kstride);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+    }
+    ScopedEvent ev(ctx, TAG_RNG, s);
+    if (keys) {
+        hipLaunchKernelGGL(k_draw_entropy_rowkey, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, s, (u32)n, N, row_base, per, 0u, (const u32*)kp, kstride, (u32*)out);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        return BBP_OK;
+    }
+    const u64 n1 = n - B;
+    hipLaunchKernelGGL(k_draw_entropy_rowkey, dim3((unsigned)((n1 + 63) / 64)), dim3(64), 0, s, (u32)n1, N, row_base, per - 1, 0u, (const u32*)kp, kstride, (u32*)out);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(k_draw_entropy_rowkey, dim3((B + 63) / 64), dim3(64), 0, s, B, N, row_base, 1u, per - 1, (const u32*)kp, kstride, (u32*)out);
     BBP_HIP_TRY(ctx, hipGetLastError());
     return BBP_OK;
 }
@@ -604,6 +678,7 @@ struct ProveCall {
     // the check's verdicts as read back
     std::vector<int32_t> dstatus;
     std::vector<u32> dmask, fail_rows;
+    std::vector<uint8_t> fail_keys;  // hedged round call: the row keys of fail_rows, in that order (as read back)
     double t_lock = 0, t_h2d = 0;  // BBP_TRACE
 };
 
@@ -707,7 +782,7 @@ static int32_t prove_enqueue(ProveCall& c, bbp_ctx::IoSlot& sl) {
         u8* cout = d_out + L.out_recs + L.rec * first;
         // what runs on the chunk's opening stream ahead of the opening stage.  A round call: the device pass writes this chunk's
         // rows (the table is reduced by the first chunk; a later chunk may open on the other stream and waits for that).
-        // (source DEVICE) this chunk's own rows of the call's key: no two chunks draw equal rows
+        // (source DEVICE / HEDGED) this chunk's own rows of the call's key: no two chunks draw equal rows
         const std::function<int32_t(hipStream_t)> draw = [&](hipStream_t os) -> int32_t {
             if (L.round) {
                 int32_t rc;
@@ -718,6 +793,8 @@ static int32_t prove_enqueue(ProveCall& c, bbp_ctx::IoSlot& sl) {
                     return rc;
                 if (!first && n_chunks > 1) BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_round, os));
             }
+            if (L.hedged)  // the rows are complete on os (uploaded, or just written by the pass above): row keys, then the draw under them
+                return hedged_draw_enqueue(ctx, nb, N, c.key, first, cin, d_ent + L.ent_keys + 32 * (size_t)first, (void*)cent, os);
             return L.dev_draw ? draw_enqueue(ctx, nb, N, BBP_ENTROPY_PROVE, c.key, first, (void*)cent, os) : (int32_t)BBP_OK;
         };
         const std::function<int32_t(hipStream_t)>* open = L.dev_draw || L.round ? &draw : nullptr;
@@ -759,6 +836,20 @@ static int32_t prove_collect(ProveCall& c, bbp_ctx::IoSlot& sl) {
         memcpy(&n_fail, h + L.out_fail_n, 4);
         c.fail_rows.resize(std::min<u32>(n_fail, c.B));
         memcpy(c.fail_rows.data(), h + L.out_fail_idx, 4 * c.fail_rows.size());
+        // hedged round call: the expanded rows exist on the device only, so the failed rows' keys are fetched (failure path only; the
+        // slot is still this call's, and everything that wrote the keys finished before sl.ev)
+        if (L.hedged && L.round && !c.fail_rows.empty() && c.mode != CHECK_REPROVE) {
+            c.fail_keys.resize(32 * c.fail_rows.size());
+            hipError_t e = hipSuccess;
+            for (size_t j = 0; j < c.fail_rows.size() && e == hipSuccess; j++)
+                e = hipMemcpyAsync(&c.fail_keys[32 * j], (const u8*)sl.ent.p + L.ent_keys + 32 * (size_t)c.fail_rows[j], 32, hipMemcpyDeviceToHost, c.ctx->copy);
+            if (e == hipSuccess) e = hipEventRecord(sl.ev_in, c.ctx->copy);
+            if (e == hipSuccess) e = wait_event_polling(sl.ev_in);
+            if (e != hipSuccess) {
+                api_guard(c.ctx, [&]() -> int32_t { return c.ctx->err = std::string("collecting row keys: ") + hipGetErrorString(e), BBP_ERR_DEVICE; });
+                return BBP_ERR_DEVICE;
+            }
+        }
     }
     return BBP_OK;
 }
@@ -782,6 +873,14 @@ static int32_t prove_merge(ProveCall& c) {
     }
     if (first_refused >= 0) set_tls_error(ctx, std::string("row ") + std::to_string(first_refused) + ": " + witness_check_text(c.dmask[first_refused]));
     if (c.mode == CHECK_REPROVE || c.fail_rows.empty()) return BBP_OK;
+    if (!c.fail_keys.empty()) {  // keys travel with their rows through the sort
+        std::vector<std::pair<u32, size_t>> order(c.fail_rows.size());
+        for (size_t j = 0; j < order.size(); j++) order[j] = {c.fail_rows[j], j};
+        std::sort(order.begin(), order.end());
+        std::vector<uint8_t> keys(c.fail_keys.size());
+        for (size_t j = 0; j < order.size(); j++) memcpy(&keys[32 * j], &c.fail_keys[32 * order[j].second], 32);
+        c.fail_keys.swap(keys);
+    }
     std::sort(c.fail_rows.begin(), c.fail_rows.end());
     const uint32_t nr = (uint32_t)c.fail_rows.size();
     const size_t rin_stride = L.in_first_stride;  // a round call proves the failed bids again, as a round
@@ -789,7 +888,10 @@ static int32_t prove_merge(ProveCall& c) {
     std::vector<int32_t> rst(nr);
     for (uint32_t j = 0; j < nr; j++) {
         memcpy(&rin[rin_stride * j], c.src + rin_stride * c.fail_rows[j], rin_stride);
-        if (L.dev_draw)
+        if (L.hedged)  // the row's own key: a rows call re-derives it from the row as uploaded, a round call fetched it (prove_collect)
+            hedge_prove_row_bytes(L.round ? chacha_key_from_bytes(&c.fail_keys[32 * j]) : hedge_row_key_bytes(c.key, c.N, c.src + L.in_stride * c.fail_rows[j]), c.N,
+                                  c.fail_rows[j], &rent[L.ent_stride * j]);
+        else if (L.dev_draw)
             entropy_prove_row_bytes(c.key, c.N, c.fail_rows[j], &rent[L.ent_stride * j]);
         else
             memcpy(&rent[L.ent_stride * j], c.entropy + L.ent_stride * c.fail_rows[j], L.ent_stride);
@@ -815,8 +917,9 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
     if (B == 0) return BBP_OK;
     fault_injected("prove_batch");
     const bool check = mode == CHECK_REPROVE || (mode == CHECK_AUTO && ctx->prove_check.load());
-    const bool dev_draw = !entropy && ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
-    ProveCall c{ctx, B, N, in, entropy, out, status, mode, round, ProveStaging(B, N, round != nullptr, check, dev_draw)};
+    const int source = ctx->entropy_source.load();
+    const bool hedged = !entropy && source == BBP_ENTROPY_SOURCE_HEDGED, dev_draw = hedged || (!entropy && source == BBP_ENTROPY_SOURCE_DEVICE);
+    ProveCall c{ctx, B, N, in, entropy, out, status, mode, round, ProveStaging(B, N, round != nullptr, check, dev_draw, hedged)};
     prove_screen(c);
     if ((rc = prove_entropy(c))) return rc;
     static const bool trace = getenv("BBP_TRACE") != nullptr;
@@ -1046,8 +1149,32 @@ extern "C" int32_t bbp_draw_entropy_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, ui
     });
 }
 
+extern "C" int32_t bbp_draw_entropy_hedged_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* key32, const void* in_dev, void* out_dev, void* stream) {
+    if (!ctx || !in_dev || !out_dev) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_draw_entropy_hedged_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc;
+        if ((rc = check_n(ctx, N))) return rc;
+        if (((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) return ctx->err = "hedged entropy draw: rows must be 4-byte aligned", BBP_ERR_BAD_ARG;
+        if (B == 0) return BBP_OK;
+        uint8_t k[32];
+        if (key32)
+            memcpy(k, key32, sizeof k);
+        else if (!os_random(k, sizeof k))
+            return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = pick_stream(ctx, stream);
+        // the draw reads the rows: a pending prepare is waited for here, and stays pending for the next prove call (which reads them too)
+        if (ctx->ev_prep_valid) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_prep, 0));
+        if ((rc = hedged_draw_enqueue(ctx, B, N, chacha_key_from_bytes(k), 0, in_dev, nullptr, out_dev, s))) return rc;
+        BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_draw, s));
+        ctx->ev_draw_valid = true;
+        return BBP_OK;
+    });
+}
+
 extern "C" int32_t bbp_set_entropy_source(bbp_ctx* ctx, int32_t source) {
-    if (!ctx || (source != BBP_ENTROPY_SOURCE_OS && source != BBP_ENTROPY_SOURCE_DEVICE)) return BBP_ERR_BAD_ARG;
+    if (!ctx || (source != BBP_ENTROPY_SOURCE_OS && source != BBP_ENTROPY_SOURCE_DEVICE && source != BBP_ENTROPY_SOURCE_HEDGED)) return BBP_ERR_BAD_ARG;
     for (bbp_ctx* m : ctx->members) bbp_set_entropy_source(m, source);
     ctx->entropy_source = source;
     return BBP_OK;
@@ -1160,7 +1287,7 @@ static int32_t verify_batch_host(bbp_ctx* ctx, const VerifyRows& rows, const uin
                                  uint32_t* n_fallback = nullptr) {
     const uint32_t B = rows.B, N = rows.kind == VerifyRows::UNIFORM ? rows.N : 0;
     // Verifier::verify mixes thread_rng into its TranscriptRng (A.7): 32 OS bytes per proof, or (source DEVICE) rows of one key
-    const bool dev_draw = ctx->entropy_source.load() == BBP_ENTROPY_SOURCE_DEVICE;
+    const bool dev_draw = ctx->entropy_source.load() != BBP_ENTROPY_SOURCE_OS;  // HEDGED: as DEVICE (a verify row carries no secret to hedge with)
     const VerifyStaging st(rows, group, (uint32_t)ctx->vknobs.group, dev_draw, host_chunk_verify());  // BBP_VERIFY_AGGREGATE, BBP_HOST_CHUNK_VERIFY
     ChachaKey key{};
     std::vector<uint8_t> ent(st.ent_up_bytes);
@@ -1525,6 +1652,9 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
                 BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
                 for (int k = 0; k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++)
                     if (!(rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, true, check, false)))) rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, false, check, false));
+                // source HEDGED: the row keys lie behind everything else in the entropy buffer (32 bytes per row more than the uploaded rows take)
+                for (int k = 0; ctx->entropy_source == BBP_ENTROPY_SOURCE_HEDGED && k < bbp_ctx::IO_SLOTS && rc == BBP_OK; k++)
+                    rc = staging_reserve(ctx, ctx->io[k], ProveStaging(B, N, false, check, true, true));
                 for (int k = 0; k < bbp_ctx::CHECK_RING && rc == BBP_OK; k++)
                     if (!(rc = dev_reserve(ctx, ctx->rnd[k].buf, RoundRing(B, N, true).bytes)) && check) rc = dev_reserve(ctx, ctx->chk[k].buf, CheckRing(B, N).bytes);
                 // the draw buffers, one per stream that opens (ProvePlan::raw_index): side's has seen a call of B; the others open dual calls

@@ -77,17 +77,19 @@ struct RoundRing {
 // ---- the staging slot of one host-pointer prove call (context.h IoSlot) -----------------------------------------------------------
 // Byte offsets into the slot's four device buffers and what of them travels through the pinned mirrors.  round: the call is a
 // bbp_prove_round (raw bids and the round's table come in, rows record || score || z_img go out); check: checked proving; dev_draw:
-// the prover's entropy is drawn on the device (only the check's weights are uploaded then).
+// the prover's entropy is drawn on the device (only the check's weights are uploaded then); hedged (with dev_draw): each row is drawn
+// under a key of its own (hedge.h), and the slot's entropy buffer holds the B row keys behind everything else.
 struct ProveStaging {
     u32 B, N;
-    bool round, check, dev_draw;
+    bool round, check, dev_draw, hedged;
     size_t in_stride, ent_stride, rec, res_stride;  // per row: prove input, entropy, record, what the caller's `out` holds
     // `in`: the first uploaded region (the rows; a round call: the bids) at 0, then for a round call the table, the pass's scratch
     // and the rows the pass writes
     size_t in_first_stride, in_first_bytes, in_tab, in_tab_bytes, in_scratch, in_rows, in_upload, in_cap;
     RoundScratch rs;
     // `ent`: the prover's rows at 0 -- drawn there or uploaded -- then the check's weights, 32 bytes per row (always uploaded)
-    size_t ent_drawn, ent_up_off, ent_up_bytes, ent_cap;
+    // hedged: the row keys, 32 bytes per row, at ent_keys (0 bytes otherwise: ent_cap is then what it was)
+    size_t ent_drawn, ent_up_off, ent_up_bytes, ent_keys, ent_keys_bytes, ent_cap;
     size_t ent_check(u32 first) const { return ent_stride * B + 32 * (size_t)first; }
     // `out`: what the caller receives at 0 (records; a round call: its output rows, the raw records lie at out_recs, unfetched), the
     // check's info block (statuses, witness masks, the count and the rows of rejected records), a round call's toggles and pass
@@ -97,8 +99,8 @@ struct ProveStaging {
     size_t chk_vstatus, chk_bytes;
     size_t h_in_bytes, h_out_bytes;  // the pinned mirrors
 
-    ProveStaging(u32 B_, u32 N_, bool round_, bool check_, bool dev_draw_)
-        : B(B_), N(N_), round(round_), check(check_), dev_draw(dev_draw_), rs(round_scratch(B_, N_)) {
+    ProveStaging(u32 B_, u32 N_, bool round_, bool check_, bool dev_draw_, bool hedged_ = false)
+        : B(B_), N(N_), round(round_), check(check_), dev_draw(dev_draw_), hedged(dev_draw_ && hedged_), rs(round_scratch(B_, N_)) {
         const size_t b = B;
         in_stride = prove_in_bytes(N), ent_stride = entropy_row_bytes(N), rec = proof_record_bytes(N);
         res_stride = round ? round_row_bytes(N) : rec;
@@ -113,7 +115,9 @@ struct ProveStaging {
         ent_drawn = dev_draw ? ent_stride * b : 0;
         ent_up_off = ent_drawn;
         ent_up_bytes = (ent_stride * b - ent_drawn) + (check ? 32 * b : 0);
-        ent_cap = ent_up_off + ent_up_bytes;
+        ent_keys = ent_up_off + ent_up_bytes;  // a multiple of 32
+        ent_keys_bytes = hedged ? 32 * b : 0;
+        ent_cap = ent_keys + ent_keys_bytes;
 
         const size_t info_bytes = check ? 4 * (3 * b + 1) : 0;
         out_info = round || check ? align256(res_stride * b) : res_stride * b;

@@ -507,7 +507,9 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                       "verify round sharing: on (concurrent bbp_verify callers with a byte-equal seed and bid list share one table entry)\n");
         if (off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "entropy source: %s\n",
-                                      ctx->entropy_source == BBP_ENTROPY_SOURCE_DEVICE
+                                      ctx->entropy_source == BBP_ENTROPY_SOURCE_HEDGED
+                                          ? "hedged (one 32-byte OS key per call; each prove row's ChaCha20 key is SHA3-256 over that key and the row's inputs, on the device)"
+                                      : ctx->entropy_source == BBP_ENTROPY_SOURCE_DEVICE
                                           ? "device (one 32-byte OS key per call, expanded with ChaCha20 on the device)"
                                           : "os (the calling thread reads /dev/urandom and reduces the blindings on the host)");
         if (free_b < ((size_t)6 << 30) && off + 1 < cap)

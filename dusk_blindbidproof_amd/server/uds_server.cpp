@@ -646,7 +646,7 @@ static void usage(const char* argv0) {
     fprintf(stderr,
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
-            "          [--check-proofs] [--entropy os|device] [--verify-mixing on|off] [--verify-rounds on|off]\n"
+            "          [--check-proofs] [--entropy os|device|hedged] [--verify-mixing on|off] [--verify-rounds on|off]\n"
             "          [--pipeline-depth D] [--max-inflight M]\n"
             "  --pipeline-depth D  requests of ONE connection with the engine at once, replies in request order (1..4096, default 64;\n"
             "                      1 = one request per connection at a time)\n"
@@ -663,7 +663,9 @@ int main(int argc, char** argv) {
     uint32_t window_us = 200, max_batch = 4096;
     int io_threads = 2;
     bool check_proofs = false;  // --check-proofs: every proof is verified on the device before it is answered (bbp_set_prove_check)
-    bool device_entropy = false;  // --entropy device: one OS key per engine call, expanded on the device (bbp_set_entropy_source)
+    // --entropy device: one OS key per engine call, expanded on the device; hedged: each row's key also bound to the row's own inputs
+    // (bbp_set_entropy_source)
+    int32_t entropy_source = BBP_ENTROPY_SOURCE_OS;
     int verify_mixing = -1;  // --verify-mixing on|off: opcode-2 requests share device calls across bid-list lengths (bbp_set_verify_mixing); -1 = not given, the engine's default (on)
     int verify_rounds = -1;  // --verify-rounds on|off: opcode-2 requests with a byte-equal seed and bid list share one rounds call (bbp_set_verify_round_sharing); -1 = not given, no call is made (the engine's default: off)
     for (int i = 1; i < argc; i++) {
@@ -706,11 +708,11 @@ int main(int argc, char** argv) {
         else if (a == "--check-proofs") check_proofs = true;
         else if (a == "--entropy") {
             const std::string v = val();
-            if (v != "os" && v != "device") {
+            if (v != "os" && v != "device" && v != "hedged") {
                 usage(argv[0]);
                 return 2;
             }
-            device_entropy = v == "device";
+            entropy_source = v == "device" ? BBP_ENTROPY_SOURCE_DEVICE : v == "hedged" ? BBP_ENTROPY_SOURCE_HEDGED : BBP_ENTROPY_SOURCE_OS;
         }
         else if (a == "--verify-mixing") {
             const std::string v = val();
@@ -786,14 +788,17 @@ int main(int argc, char** argv) {
             }
             logf(2, "checked proving on: every proof is verified on the device before it is answered");
         }
-        if (device_entropy) {  // resolved only when asked for: an engine without it cannot honour the flag, so the server does not start
+        if (entropy_source != BBP_ENTROPY_SOURCE_OS) {  // resolved only when asked for: an engine without it (or one that rejects the value) cannot honour the flag, so the server does not start
+            const bool hedged = entropy_source == BBP_ENTROPY_SOURCE_HEDGED;
             auto set_source = (decltype(&bbp_set_entropy_source))dlsym(g_eng.so, "bbp_set_entropy_source");
-            if (!set_source || set_source(g_eng.ctx, BBP_ENTROPY_SOURCE_DEVICE) != BBP_OK) {
-                logf(0, "--entropy device: the engine %s does not provide on-device entropy (bbp_set_entropy_source)", engine_path.c_str());
+            if (!set_source || set_source(g_eng.ctx, entropy_source) != BBP_OK) {
+                logf(0, "--entropy %s: the engine %s does not provide %s on-device entropy (bbp_set_entropy_source)", hedged ? "hedged" : "device",
+                     engine_path.c_str(), hedged ? "hedged" : "plain");
                 g_eng.free_(g_eng.ctx);
                 return 2;
             }
-            logf(2, "entropy source: device (one OS key per engine call, expanded with ChaCha20 on the device)");
+            logf(2, hedged ? "entropy source: hedged (one OS key per engine call; each row's ChaCha20 key is SHA3-256 over that key and the row's inputs, on the device)"
+                           : "entropy source: device (one OS key per engine call, expanded with ChaCha20 on the device)");
         }
         if (verify_mixing >= 0) {  // resolved only when asked for: an engine without the call batches per bid-list length, which is what "off" means
             auto set_mixing = (decltype(&bbp_set_verify_mixing))dlsym(g_eng.so, "bbp_set_verify_mixing");

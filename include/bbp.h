@@ -441,11 +441,47 @@ int32_t bbp_draw_entropy_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t kind
  *                               before the prover's opening stage / the verifier; the host reads 32 bytes per call
  * Rows with caller entropy are untouched; a host batch cut into chunks (BBP_HOST_CHUNK_PROVE) draws each chunk's own row range of the
  * call's key; checked proving re-proves a failed record with its row re-derived from the same key (the bytes an unchecked call returns
- * under that key).  The *_dev entry points still require entropy_dev.  On a pool: every member.  bbp_describe reports the source. */
+ * under that key).  The *_dev entry points still require entropy_dev.  On a pool: every member.  bbp_describe reports the source.
+ *   BBP_ENTROPY_SOURCE_HEDGED   prove calls: as DEVICE, but every row draws under a key of its own, derived on the device from the
+ *                               call's key and the row's inputs ("Hedged on-device entropy" below); verify calls draw exactly as
+ *                               under DEVICE (a verification row carries no secret to hedge with) */
 #define BBP_ENTROPY_SOURCE_OS 0
 #define BBP_ENTROPY_SOURCE_DEVICE 1
+#define BBP_ENTROPY_SOURCE_HEDGED 2
 int32_t bbp_set_entropy_source(bbp_ctx* ctx, int32_t source);
-/* Test hook: the key of the next host-pointer call that draws on the device (source DEVICE, no caller entropy) instead of 32 OS bytes,
+/* ---- Hedged on-device entropy -----------------------------------------------------------------------------------------------------
+ * Under source DEVICE the 32 OS bytes of an engine call are all that keeps its blindings from repeating: a VM snapshot restored
+ * twice, a forked supervisor or a broken /dev/urandom gives the same key again, and row i of the second call then carries the
+ * blindings of row i of the first over another witness (the warning in capitals above).  Source HEDGED binds each row's entropy to
+ * the row itself.  For prove row i of a call with list length N, call key K (32 bytes) and input row
+ *   row_i    = scalars7 || pub_list || toggle (u64 LE)            232 + 32 N raw bytes, as bbp_prove_batch takes them
+ *   rowkey_i = SHA3-256("BBP-hedge-v1" || K || u32le(N) || row_i)   (FIPS 202: rate 136, suffix 0x06; 12 + 32 + 4 + 232 + 32 N bytes)
+ *   nonce_i  = "BBPH" || u32le(N) || u32le(i)
+ *   blinding k < 4+N = block(rowkey_i, k, nonce_i) as a little-endian integer mod l, 32 canonical bytes at 32 k
+ *   rng seed         = the first 32 bytes of block(rowkey_i, 4+N, nonce_i), at 32 (4+N)
+ * i.e. the prove row above under the row's own key and the nonce word "BBPH".  i is the row's index in the host call: in the
+ * combined batch for combined callers, first + r in a call cut into chunks (source DEVICE numbers rows the same way).
+ *   - With a repeated K, two rows share entropy only when N, all 232 + 32 N input bytes and the index are equal; their records are
+ *     then byte-identical and nothing new is revealed.
+ *   - With a K the adversary knows, the blindings are still unpredictable without the row's secret k (the hash's input holds it).
+ * It does not hedge caller-supplied entropy or source OS, is not constant-time, and is opt-in: the default source stays OS.
+ * Host-pointer prove calls without caller entropy (bbp_prove, bbp_prove_async, bbp_prove_batch, bbp_prove_round; combined or not; a
+ * context or a pool) follow DEVICE's path with one change of order: the rows first (a round call: its device pass), then the row
+ * keys, then the draw, all on the chunk's opening stream.  bbp_prove_round under K returns what bbp_prove_batch returns for the
+ * expanded rows under K.  Checked proving keeps its contract: a failed record is proved again under the entropy row it had -- a rows
+ * call re-derives the row key on the host, a round call (whose expanded row never exists on the host) fetches the failed rows' keys
+ * from the device with the check's verdicts.  Row keys are secret like the rows; they live in the call's entropy buffer behind the
+ * drawn rows and nowhere else.
+ *
+ * The device form: B prove rows into out_dev (B * bbp_entropy_size(N) bytes) from the rows at in_dev (B * (232 + 32 N) bytes, 4-byte
+ * aligned; 8-byte aligned rows are read with 64-bit loads) under key32 (host memory; NULL = 32 fresh OS bytes).  Arguments are screened
+ * as bbp_draw_entropy_dev screens them for prove rows; a pool refuses it.  Stream-ordered on `stream`, no synchronisation.  It READS
+ * in_dev: when a bbp_prepare_bids_dev / bbp_prepare_round_dev is pending on the context, `stream` is made to wait for it first (the
+ * pending prepare stays pending: the next prove call still waits for it), and the draw is then recorded as bbp_draw_entropy_dev's
+ * is, so the next prove call waits for both.  Rows written by anything else are ordered by the caller.  The row keys pass through
+ * the rows' own seed slots and are overwritten by the seeds: out_dev is the only memory written. */
+int32_t bbp_draw_entropy_hedged_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* key32, const void* in_dev, void* out_dev, void* stream);
+/* Test hook: the key of the next host-pointer call that draws on the device (source DEVICE or HEDGED, no caller entropy) instead of 32 OS bytes,
  * so that its records can be compared with an explicit-entropy call; consumed by that call.  A pool refuses it (take a member). */
 int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]);
 
