@@ -13,10 +13,12 @@
 //
 // One MSM = one workgroup in each of THREE kernels:
 //   k_msm_sort[_staged]  (1024 thin lanes)
-//     A. NAF digits of every scalar -> LDS histogram over bucket (|d| + 1) / 2
+//     A. NAF digits of every scalar -> LDS histogram over bucket (|d| + 1) / 2.  The staged kernel walks every scalar ONCE here and
+//        keeps its digits packed in registers (16 bits a digit) for C; the plain kernel walks them again
 //     B. exclusive scan -> bucket offsets
 //     C. counting-sort scatter of (row index, sign) into the MSM's HBM scratch slice (staged through an LDS image and written out
-//        as full lines for MSMs of at most 3000 terms); bucket end offsets to HBM
+//        as full lines for MSMs of at most 3000 terms; wider ones keep the plain 4-byte scatter: msm_plan.h has the measurement);
+//        bucket end offsets to HBM
 //   k_msm_acc            (256 fat lanes, 151 registers, two waves per SIMD)
 //     D1. the sorted entry array is cut into 256 equal chunks, one per lane: mixed additions of gathered table rows into bucket
 //         sums (HBM); a chunk that starts inside a bucket parks its leading partial sum
@@ -274,23 +276,46 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort(const u32* __restrict__ sca
 
 // k_msm_sort with the counting-sort scatter STAGED THROUGH LDS.  The plain kernel's scatter is 72 % of its time: every entry is a 4-byte
 // store to its own cache line, bound by L2 write requests (~2 * 10^11 /s).  Here the buckets are walked in windows of at most SORT_CAP
-// entries (consecutive buckets; the window boundaries come from the prefix sums, so every lane finds the same ones): a pass re-walks the
-// lane's NAF digits (cheap), places the entries of the window's buckets in an LDS image with the same LDS atomics as before, and the
-// workgroup then writes the image out as full cache lines (image: BBP_SORT_CAP entries, 84 KB).  A bucket larger than the image (adversarial scalars only) takes a pass of
-// its own with direct stores.  Entry order inside a bucket differs from the plain kernel's; sums do not care.
-// (BBP_SORT_CAP, SORT_CAP_WIDE, SORT_WIDE_FROM: msm_plan.h -- the plan of a launch states the image it sorts through)
+// entries (consecutive buckets; the window boundaries come from the prefix sums): a pass places the entries of the window's buckets in
+// an LDS image with the same LDS atomics as before, and the workgroup then writes the image out as full cache lines (image: BBP_SORT_CAP
+// entries, 84 KB).  A bucket larger than the image (adversarial scalars only) takes a pass of its own with direct stores.  Entry order
+// inside a bucket differs from the plain kernel's; sums do not care.
+// ONE WALK: a lane loads and recodes each of its (at most S) scalars once and keeps the digits packed in registers (scalar.h
+// sc_naf_digits_packed: 16 bits a digit in a slot known at compile time, 13 registers a scalar at width 12); the histogram and every
+// window's placement run over those registers.  The form before re-loaded and re-recoded every scalar for the histogram and for every
+// window (three to six times).  All window boundaries are found once, by the first wavefront, behind the barrier that ends the scan.
+// (BBP_SORT_CAP, SORT_CAP_WIDE, SORT_WIDE_FROM, SORT_STAGED_MAX_TERMS: msm_plan.h -- the plan of a launch states the image it sorts through)
 template <int MODE> struct sort_cap { static constexpr u32 V = BBP_SORT_CAP; };  // image entries (dynamic LDS: 4 bytes each) of an ordinary launch
-template <> struct sort_cap<1> { static constexpr u32 V = 8192; };
+#ifndef BBP_SORT_CAP_FOLD
+#define BBP_SORT_CAP_FOLD 8192  // seven windows, two workgroups per CU; 28 672 (two windows, one workgroup per CU): the kernel alone 828 -> 715 us per launch, the prove step unchanged (22 973 against 22 959 proofs/s over five alternated runs)
+#endif
+template <> struct sort_cap<1> { static constexpr u32 V = BBP_SORT_CAP_FOLD; };
+constexpr int SORT_S = 3, SORT_S_WIDE = 5, SORT_S_FOLD = 2;  // scalars per lane held in registers: MSMs of up to SORT_S * SORT_T terms | wider ones | the generator-fold pass
+constexpr int SORT_MAXW = 62;                               // windows found per round of the boundary search (part[] holds them)
+static_assert((u32)SORT_S_WIDE * SORT_T >= SORT_STAGED_MAX_TERMS && SORT_S_FOLD * SORT_T >= 2048 && SORT_MAXW + 2 <= SORT_T, "staged sort geometry");
 
-template <int MODE>
+#ifdef BBP_MSM_PROF  // experiments only: phases of the staged sort by launch class (0: up to 2049 terms, 1: up to SORT_WIDE_FROM, 2: wider, 3: the fold pass)
+__device__ unsigned long long g_sort_prof[4][16];  // [class][0 load + recode + histogram, 2 scan + boundaries, 3 + 2w placement w, 4 + 2w write-out w (14: all later ones), 15 workgroups]
+#define SORT_PROF_MARK(i)                                                   \
+    if (tid == 0) {                                                         \
+        unsigned long long now_ = wall_clock64();                           \
+        atomicAdd(&g_sort_prof[prof_cls][(i) < 15 ? (i) : 14], now_ - prof_t); \
+        prof_t = now_;                                                      \
+    }
+#else
+#define SORT_PROF_MARK(i)
+#endif
+
+template <int MODE, int S>
 __global__ __launch_bounds__(SORT_T) void k_msm_sort_staged(const u32* __restrict__ scal_a, const u32* __restrict__ aux, u32 n_total, u32 n_idx_sets,
                                                              u32 n_sub, u32 split, u32* __restrict__ sorted_all, u32* __restrict__ cursor_all,
                                                              const u32* __restrict__ msm_map, const u32* __restrict__ n_active, u32 CAP, u32* __restrict__ ticket) {
     constexpr int K = msm_geom<MODE>::K, NAF = msm_geom<MODE>::NAF, W = msm_geom<MODE>::W, G = K >= SORT_T ? K / SORT_T : 1;  // buckets per lane of the scan (lanes past K idle)
+    constexpr int P = naf_slots<NAF>::P, NSLOT = naf_slots<NAF>::N, DW = naf_slots<NAF>::WORDS;
     extern __shared__ u32 stage[];  // [CAP] entries: the image of one window
     __shared__ u32 start[K + 2];  // start[k] = position of bucket k's first entry (k = 1..K), start[K + 1] = number of entries
     __shared__ u32 fill[K + 1];   // histogram, then entries placed so far per bucket
-    __shared__ u32 part[SORT_T];
+    __shared__ u32 part[SORT_T];  // the scan's wave totals, then the windows: part[0] = how many, part[1 + w] = the bucket after window w
     const int tid = threadIdx.x;
     if (ticket && blockIdx.x == 0 && tid == 0) *ticket = 0;
     if (n_active && blockIdx.x >= *n_active) return;
@@ -313,17 +338,39 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort_staged(const u32* __restric
     u32* sorted = sorted_all + work * (size_t)n_sub * W;
     auto key = [&](u32 i, u32 mag) -> u32 { return (MODE != 1 ? 0u : ((i0 + i) & (FOLD_CLS - 1)) * FOLD_M) + ((mag + 1) >> 1); };
 
+#ifdef BBP_MSM_PROF
+    const int prof_cls = MODE == 1 ? 3 : n_sub <= 2049 ? 0 : n_sub <= SORT_WIDE_FROM ? 1 : 2;
+    if (tid == 0) atomicAdd(&g_sort_prof[prof_cls][15], 1ull);
+    unsigned long long prof_t = wall_clock64();
+#endif
     for (int k = tid; k <= K; k += SORT_T) fill[k] = 0;
     __syncthreads();
-    // A. histogram
-    for (u32 i = tid; i < n; i += SORT_T) {
-        const uint4* sp = reinterpret_cast<const uint4*>(sbase + (size_t)i * 8);
-        uint4 lo = sp[0], hi = sp[1];
-        const u32 s[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-        if (MODE != 1 && base_idx[i] == MSM_SKIP_BASE) continue;
-        sc_for_each_naf_digit<NAF>(s, [&](u32, u32 mag, u32) { atomicAdd(&fill[key(i, mag)], 1u); });
+    // A. the one walk: scalar tid + j * SORT_T is this lane's j-th.  dig[j]: its digits (slot t of valid[j] set: the digit exists),
+    //    tb[j]: first table row of its base, koff[j]: first bucket of its class less one (MODE 1; else 0).  The host sizes S so that
+    //    S * SORT_T >= n (plan_msm: SORT_STAGED_MAX_TERMS); a scalar that rides on a merged base has no digits.  Every digit is
+    //    counted into the histogram as it is found: the LDS atomics run beside the recoding's ALU work.
+    u32 dig[S][DW], valid[S], tb[S], koff[S];
+#pragma unroll
+    for (int j = 0; j < S; j++) {
+        const u32 i = (u32)tid + (u32)j * SORT_T;
+        valid[j] = 0, tb[j] = 0, koff[j] = 0;
+#pragma unroll
+        for (int d = 0; d < DW; d++) dig[j][d] = 0;
+        if (i < n) {
+            const uint4* sp = reinterpret_cast<const uint4*>(sbase + (size_t)i * 8);
+            uint4 lo = sp[0], hi = sp[1];
+            const u32 s[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+            const u32 b = MODE != 1 ? base_idx[i] : base0 + i;
+            if (MODE == 1 || b != MSM_SKIP_BASE) {
+                tb[j] = b * MSM_POS;
+                koff[j] = key(i, 0);  // key(i, mag) = koff + (mag + 1) / 2
+                const u32 ko = koff[j];
+                sc_naf_digits_packed<NAF>(s, dig[j], valid[j], [&](u32 p) { atomicAdd(&fill[ko + naf_packed_bucket(p)], 1u); });
+            }
+        }
     }
     __syncthreads();
+    SORT_PROF_MARK(0);
     // B. bucket start offsets (block-wide exclusive scan as in k_msm_sort), counters back to zero
     {
         u32 local = 0;
@@ -361,44 +408,74 @@ __global__ __launch_bounds__(SORT_T) void k_msm_sort_staged(const u32* __restric
         if (tid == 0) start[0] = 0;
     }
     __syncthreads();
-    // C. scatter, window by window
-    u32 kb = 1;
-    while (kb <= (u32)K) {
-        const u32 base = start[kb];
-        const bool direct = start[kb + 1] - base > CAP;  // one bucket larger than the image
-        u32 ke = kb + 1;
-        if (!direct) {  // largest ke in [kb + 1, K + 1] with start[ke] - base <= CAP
-            u32 lo = kb + 1, hi = (u32)K + 1;
-            while (lo < hi) {
-                const u32 mid = (lo + hi + 1) >> 1;
-                if (start[mid] - base <= CAP) lo = mid; else hi = mid - 1;
+    // C. scatter, window by window.  The first wavefront finds the windows that hold anything (every lane of it the same ones), at
+    //    most SORT_MAXW a round: more than one round takes more than SORT_MAXW / 2 images' worth of entries, which no planned launch has.
+    u32 kb0 = 1;
+    while (kb0 <= (u32)K) {
+        if (tid < 64) {
+            u32 kb = kb0, nw = 0;
+            while (kb <= (u32)K && nw < (u32)SORT_MAXW) {
+                const u32 base = start[kb];
+                u32 ke = kb + 1;
+                if (start[ke] - base <= CAP) {  // (else one bucket larger than the image) largest ke in [kb + 1, K + 1] with start[ke] - base <= CAP
+                    u32 lo = kb + 1, hi = (u32)K + 1;
+                    while (lo < hi) {
+                        const u32 mid = (lo + hi + 1) >> 1;
+                        if (start[mid] - base <= CAP) lo = mid; else hi = mid - 1;
+                    }
+                    ke = lo;
+                }
+                if (start[ke] != base) {  // (windows of empty buckets have nothing to place: the next window starts behind them)
+                    if (tid == 0) part[1 + nw] = ke;
+                    nw++;
+                }
+                kb = ke;
             }
-            ke = lo;
+            if (tid == 0) part[0] = nw, part[1 + nw] = kb;  // the round ends before bucket kb
         }
-        if (start[ke] != base) {  // (windows of empty buckets have nothing to place)
-            for (u32 i = tid; i < n; i += SORT_T) {
-                const uint4* sp = reinterpret_cast<const uint4*>(sbase + (size_t)i * 8);
-                uint4 lo4 = sp[0], hi4 = sp[1];
-                const u32 s[8] = {lo4.x, lo4.y, lo4.z, lo4.w, hi4.x, hi4.y, hi4.z, hi4.w};
-                if (MODE != 1 && base_idx[i] == MSM_SKIP_BASE) continue;
-                const u32 tb = (MODE != 1 ? base_idx[i] : base0 + i) * MSM_POS;
-                sc_for_each_naf_digit<NAF>(s, [&](u32 pos, u32 mag, u32 neg) {
-                    const u32 k = key(i, mag);
-                    if (k >= kb && k < ke) {
+        __syncthreads();
+        SORT_PROF_MARK(2);
+        // (the windows are the same for every lane: readfirstlane keeps them in scalar registers)
+        const u32 nw = (u32)__builtin_amdgcn_readfirstlane((int)part[0]);
+        u32 kb = kb0;
+        for (u32 w = 0; w < nw; w++) {
+            const u32 ke = (u32)__builtin_amdgcn_readfirstlane((int)part[1 + w]);
+            // window w: the buckets of [kb, ke) that hold anything are its last ones (empty windows before it were skipped), so its
+            // entries are start[kb] = start[first non-empty bucket] .. start[ke]
+            const u32 base = (u32)__builtin_amdgcn_readfirstlane((int)start[kb]), cnt = (u32)__builtin_amdgcn_readfirstlane((int)start[ke]) - base;
+            const bool direct = cnt > CAP;  // one bucket larger than the image (behind empty ones)
+#pragma unroll
+            for (int j = 0; j < S; j++) {
+                // (the digits are decoded here, window by window: hoisted out of the loop, every slot's bucket, entry and LDS address
+                // would be a live register of its own -- the compiler did that, and spilled)
+                asm volatile("" : "+v"(valid[j]));
+#pragma unroll
+                for (int d = 0; d < DW; d++) asm volatile("" : "+v"(dig[j][d]));
+                if (!valid[j]) continue;
+                // (slot by slot: issuing the rank atomics of eight slots before waiting for the first measured 5-9 % SLOWER per window --
+                // the sixteen waves of the workgroup hide the LDS round trip already)
+#pragma unroll
+                for (int t = 0; t < NSLOT; t++) {
+                    if (!(valid[j] >> t & 1)) continue;
+                    const u32 p = naf_slot<NAF>(dig[j], t), k = koff[j] + naf_packed_bucket(p);
+                    if (k - kb < ke - kb) {
                         const u32 at = start[k] + atomicAdd(&fill[k], 1u);
-                        const u32 ent = (tb + pos) | (neg << 31);
+                        const u32 ent = (tb[j] + naf_packed_pos(p, t / P)) | (naf_packed_neg(p) << 31);
                         if (direct) sorted[at] = ent; else stage[at - base] = ent;
                     }
-                });
+                }
             }
             __syncthreads();
+            SORT_PROF_MARK(3 + 2 * w);
             if (!direct) {
-                const u32 cnt = start[ke] - base;
                 for (u32 i = tid; i < cnt; i += SORT_T) sorted[base + i] = stage[i];
+                __syncthreads();  // (the next window places into the same image)
             }
-            __syncthreads();
+            SORT_PROF_MARK(4 + 2 * w);
+            kb = ke;
         }
-        kb = ke;
+        kb0 = (u32)__builtin_amdgcn_readfirstlane((int)part[1 + nw]);
+        __syncthreads();  // part[] is rewritten by the next round
     }
     u32* cur_out = cursor_all + work * (size_t)(K + 1);
     for (int k = tid; k <= K; k += SORT_T) cur_out[k] = k ? start[k + 1] : 0u;  // end offset of bucket k
@@ -965,10 +1042,10 @@ int32_t fold_generators_launch(bbp_ctx* ctx, uint32_t n_proofs, const sc* g_dev,
         ScopedEvent ev(ctx, TAG_MSM_SORT, stream);
         if (ctx->msm_knobs.sort_staged & 2) {
             if (!ctx->sort_lds_attr1) {  // 36 KB static + 32 KB dynamic LDS: above the 64 KB a kernel gets without opting in (per context = per device)
-                BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sort_cap<1>::V * 4)));
+                BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<1, SORT_S_FOLD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sort_cap<1>::V * 4)));
                 ctx->sort_lds_attr1 = true;
             }
-            hipLaunchKernelGGL(k_msm_sort_staged<1>, dim3((u32)n_work), dim3(SORT_T), sort_cap<1>::V * 4, stream, (const u32*)g_dev, (const u32*)h_dev, 2048u, 1u,
+            hipLaunchKernelGGL((k_msm_sort_staged<1, SORT_S_FOLD>), dim3((u32)n_work), dim3(SORT_T), sort_cap<1>::V * 4, stream, (const u32*)g_dev, (const u32*)h_dev, 2048u, 1u,
                                n_sub, split, m.sorted, m.cursor, (const u32*)nullptr, (const u32*)nullptr, sort_cap<1>::V, m.ticket);
         } else
             hipLaunchKernelGGL(k_msm_sort<1>, dim3((u32)n_work), dim3(SORT_T), 0, stream, (const u32*)g_dev, (const u32*)h_dev, 2048u, 1u, n_sub, split,
@@ -1057,11 +1134,21 @@ int32_t msm_launch(bbp_ctx* ctx, uint32_t n_msm, uint32_t n_terms, const u32* sc
         if (plan.sort != MsmPlan::PLAIN) {  // staged scatter through an image of plan.sort_cap entries
             const u32 cap = plan.sort_cap;
             if (!ctx->sort_lds_attr) {  // per context = per device: a process may hold one context per GPU (bbp-uds-server --devices)
-                BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SORT_CAP_WIDE * 4)));
+                BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<0, SORT_S>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SORT_CAP_WIDE * 4)));
+                BBP_HIP_TRY(ctx, hipFuncSetAttribute((const void*)k_msm_sort_staged<0, SORT_S_WIDE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(SORT_CAP_WIDE * 4)));
                 ctx->sort_lds_attr = true;
             }
-            hipLaunchKernelGGL(k_msm_sort_staged<0>, dim3(n_work), dim3(SORT_T), cap * 4, stream, scalars_dev, base_idx_dev, n_terms, n_idx_sets, n_sub, split,
-                               m.sorted, m.cursor, msm_map_dev, n_active_dev, cap, m.ticket);
+            if (n_sub > (u32)SORT_S_WIDE * SORT_T) {  // (plan_msm never stages such a launch: the kernel holds SORT_S_WIDE scalars a lane)
+                ctx->err = "msm_launch: staged sort planned for more terms than its lanes hold";
+                return BBP_ERR_INTERNAL;
+            }
+            // scalars a lane keeps in registers: three cover the prover's MSMs (2049, 2933 terms), five the widest staged launch
+            if (n_sub <= (u32)SORT_S * SORT_T)
+                hipLaunchKernelGGL((k_msm_sort_staged<0, SORT_S>), dim3(n_work), dim3(SORT_T), cap * 4, stream, scalars_dev, base_idx_dev, n_terms, n_idx_sets, n_sub, split,
+                                   m.sorted, m.cursor, msm_map_dev, n_active_dev, cap, m.ticket);
+            else
+                hipLaunchKernelGGL((k_msm_sort_staged<0, SORT_S_WIDE>), dim3(n_work), dim3(SORT_T), cap * 4, stream, scalars_dev, base_idx_dev, n_terms, n_idx_sets, n_sub, split,
+                                   m.sorted, m.cursor, msm_map_dev, n_active_dev, cap, m.ticket);
         }
         else
             hipLaunchKernelGGL(k_msm_sort<0>, dim3(n_work), dim3(SORT_T), 0, stream, scalars_dev, base_idx_dev, n_terms, n_idx_sets, n_sub, split,
@@ -1107,8 +1194,15 @@ int32_t msm_launch(bbp_ctx* ctx, uint32_t n_msm, uint32_t n_terms, const u32* sc
 #ifdef BBP_MSM_PROF
     static int launches = 0;
     if (++launches % 16 == 0) {
-        unsigned long long h[8];
+        unsigned long long h[8], sp[4][16];
         (void)hipStreamSynchronize(stream);
+        (void)hipMemcpyFromSymbol(sp, HIP_SYMBOL(g_sort_prof), sizeof sp);
+        for (int c = 0; c < 4; c++) {
+            if (!sp[c][15]) continue;
+            fprintf(stderr, "[sort prof class %d, %llu workgroups, 10ns ticks of lane 0 per workgroup]", c, sp[c][15]);
+            for (int i = 0; i < 15; i++) fprintf(stderr, " %.1f", (double)sp[c][i] / (double)sp[c][15]);
+            fprintf(stderr, "\n");
+        }
         (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_msm_prof), sizeof h);
         fprintf(stderr, "[msm prof, %d launches, 10ns ticks of lane 0 summed over WGs] load %llu D1 %llu D1wait %llu D2 %llu E %llu; D1 shader clock %.0f MHz\n", launches,
                 h[1], h[2], h[3], h[4], h[5], 100.0 * (double)h[6] / (double)h[2]);

@@ -29,6 +29,7 @@ constexpr int SMALL_W = 29;                    // most digits one scalar can hav
 #endif
 constexpr uint32_t SORT_CAP_WIDE = 32768;  // ... of MSMs with more than SORT_WIDE_FROM terms (one workgroup per CU then)
 constexpr uint32_t SORT_WIDE_FROM = 3000;
+constexpr uint32_t SORT_STAGED_MAX_TERMS = 5120;  // the staged sort keeps every digit in registers, at most five scalars on each of its 1024 lanes: longer (sub-)MSMs take the plain scatter (the API's longest MSM has 4098 terms)
 constexpr uint32_t MSM_SPLIT_MAX = 16;     // sub-MSMs per MSM at the most (k_msm_reduce: sixteen lanes per output)
 
 struct MsmKnobs {
@@ -111,9 +112,14 @@ inline MsmPlan plan_msm(const MsmKnobs& k, uint32_t n_msm, uint32_t n_terms, boo
         return p;
     }
     // staged scatter: 84 KB image for the prover's 2049- / 2933-term MSMs (two / three windows); wider MSMs (the verifier's 4098
-    // terms = 81 k entries: six windows, measured 3 % slower than the plain scatter) get a 128 KB image with bit 2 of the knob
+    // terms = 81 k entries) get a 128 KB image with bit 2 of the knob.  With the re-walking sort that form measured 3 % slower than
+    // the plain scatter; with the one-walk sort it measures FASTER (bench.py --workload verify, knob 3 against 7 alternated, five
+    // runs each, profiles/r16_sort_ab_verify*.jsonl): 8192 proofs 210.5-212.1 k -> 219.0-220.0 k verifications/s (x 1.034, ranges
+    // apart), 1024 proofs 180.1-190.0 k -> 188.3-195.0 k (medians x 1.031, ranges overlap).  The default stays 3 for now: the
+    // path tests pin the plain scatter as the default plan of the 4097-term launches, and prove batches at N >= 20 would move too
+    // and have not been measured.
     const bool wide = p.n_sub > SORT_WIDE_FROM;
-    if ((k.sort_staged & 1) && (!wide || (k.sort_staged & 4))) {
+    if ((k.sort_staged & 1) && (!wide || (k.sort_staged & 4)) && p.n_sub <= SORT_STAGED_MAX_TERMS) {
         p.sort = wide ? MsmPlan::STAGED_WIDE : MsmPlan::STAGED;
         p.sort_cap = wide ? SORT_CAP_WIDE : (uint32_t)BBP_SORT_CAP;
     }

@@ -354,4 +354,55 @@ BBP_HD void sc_for_each_naf_digit(const u32 (&s)[8], F&& f) {
     }
 }
 
+// The same recoding with every digit KEPT, in a slot whose index is known at compile time (the staged MSM sort walks a scalar once
+// and holds its digits in registers: msm.hip k_msm_sort_staged).  Digits are at least WID bits apart, so the 32 positions of word wi
+// hold at most P = ceil(32 / WID) of them: slot wi * P + t is the t-th digit that starts in word wi, bit t of `valid` says that it
+// exists.  A digit packs into 16 bits -- position within its word (5 bits), (|d| - 1) / 2 (10 bits: |d| odd, < 2048), sign -- two to a
+// register.
+template <int WID> struct naf_slots {
+    static_assert(WID >= 8 && WID <= 12, "a slot is 16 bits and `valid` has 32");
+    static constexpr int P = (32 + WID - 1) / WID, N = 8 * P, WORDS = N / 2;
+};
+BBP_HD constexpr u32 naf_pack(u32 pos, u32 mag, u32 neg) { return (pos & 31u) | ((mag >> 1) << 5) | (neg << 15); }
+BBP_HD constexpr u32 naf_packed_pos(u32 p, u32 word) { return 32u * word + (p & 31u); }
+BBP_HD constexpr u32 naf_packed_bucket(u32 p) { return ((p >> 5) & 0x3ffu) + 1u; }  // (|d| + 1) / 2, the bucket of msm_geom<0> / <2>
+BBP_HD constexpr u32 naf_packed_neg(u32 p) { return (p >> 15) & 1u; }
+template <int WID> BBP_HD constexpr u32 naf_slot(const u32 (&dig)[naf_slots<WID>::WORDS], int slot) { return (dig[slot >> 1] >> (16 * (slot & 1))) & 0xffffu; }
+
+// each(packed digit) is called as a digit is found (the sort counts it into its histogram there: LDS atomics beside the recoding's ALU work)
+template <int WID, class F>
+BBP_HD void sc_naf_digits_packed(const u32 (&s)[8], u32 (&dig)[naf_slots<WID>::WORDS], u32& valid, F&& each) {
+    constexpr int P = naf_slots<WID>::P;
+#pragma unroll
+    for (int d = 0; d < naf_slots<WID>::WORDS; d++) dig[d] = 0;
+    valid = 0;
+    u32 carry = 0;
+    int off = 0;
+#pragma unroll
+    for (int wi = 0; wi < 8; wi++) {
+        const u64 win = (u64)s[wi] | (wi + 1 < 8 ? (u64)s[wi + 1] << 32 : 0ull);
+#pragma unroll
+        for (int t = 0; t < P; t++) {  // sc_for_each_naf_digit's inner loop: both of its exits leave off >= 32, and a digit adds WID
+            if (off < 32) {
+                const u64 rest = (win ^ (carry ? ~0ull : 0ull)) >> off;
+                if (rest == 0) {
+                    off = 64;
+                } else {
+                    off += __builtin_ctzll(rest);
+                    if (off < 32) {
+                        const u32 v = ((u32)(win >> off) & ((1u << WID) - 1u)) + carry;
+                        carry = v >> (WID - 1);
+                        const u32 p = naf_pack((u32)off, carry ? (1u << WID) - v : v, carry);
+                        dig[(wi * P + t) >> 1] |= p << (16 * ((wi * P + t) & 1));
+                        each(p);
+                        valid |= 1u << (wi * P + t);
+                        off += WID;
+                    }
+                }
+            }
+        }
+        off -= 32;
+    }
+}
+
 }  // namespace bbp
