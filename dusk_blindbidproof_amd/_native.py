@@ -89,6 +89,11 @@ SIGNATURES = {
     "bbp_draw_entropy_hedged_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "bbp_set_entropy_source": (_i32, [_vp, _i32]),
     "bbp_debug_next_entropy_key": (_i32, [_vp, _vp]),
+    "bbp_set_secret_wipe": (_i32, [_vp, _i32]),
+    "bbp_wipe_secrets": (_i32, [_vp]),
+    "bbp_debug_secret_residue": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u32]),
+    "bbp_debug_secret_scan": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
+    "bbp_debug_wipe_cost": (_i32, [_vp, _i32, ctypes.POINTER(_u64), ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_float)]),
     "bbp_debug_challenges": (_i32, [_vp, _u32, _u32, _u32, _vp]),
     "bbp_debug_table": (_i32, [_vp, _u32, ctypes.POINTER(_vp), ctypes.POINTER(_u64)]),
     "bbp_debug_varbase": (_i32, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -594,6 +599,39 @@ class Context:
             raise ValueError("key must be 32 bytes")
         self._check(lib.bbp_debug_next_entropy_key(self._h, _buf(key)))
 
+    def set_secret_wipe(self, on):
+        """Secret wiping (bbp_set_secret_wipe): while on, every prove-side call erases the witness, blindings, entropy and keys it left in
+        the context's device buffers and pinned staging mirrors; turning it on erases everything once and synchronises.  Off by
+        default; a pool: every member."""
+        self._check(lib.bbp_set_secret_wipe(self._h, 1 if on else 0))
+
+    def wipe_secrets(self):
+        """Erase every secret-class buffer of the context now, whatever the setting (bbp_wipe_secrets); synchronises.  A pool: every member."""
+        self._check(lib.bbp_wipe_secrets(self._h))
+
+    def debug_secret_residue(self):
+        """Test hook: (non-zero device bytes, non-zero pinned host bytes, name of the first buffer with residue or "") over the whole
+        capacity of every secret-class buffer (bbp_debug_secret_residue); synchronises."""
+        dev, host = ctypes.c_uint64(), ctypes.c_uint64()
+        where = ctypes.create_string_buffer(64)
+        self._check(lib.bbp_debug_secret_residue(self._h, ctypes.byref(dev), ctypes.byref(host), where, len(where)))
+        return dev.value, host.value, where.value.decode()
+
+    def debug_secret_scan(self, pattern):
+        """Test hook: (device hits, pinned host hits) of `pattern` (4 .. 64 bytes, a multiple of 4) at every 4-byte offset of every
+        grow-only buffer, ring, staging slot, pinned mirror and resident table of the context, secret or public (bbp_debug_secret_scan);
+        synchronises."""
+        dev, host = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(lib.bbp_debug_secret_scan(self._h, _buf(pattern), len(pattern), ctypes.byref(dev), ctypes.byref(host)))
+        return dev.value, host.value
+
+    def debug_wipe_cost(self, clear=False):
+        """Test hook: (bytes, launches, lone_us) -- what the wipes since the log was last cleared stored, in how many k_wipe_spans launches,
+        and the device time of one lone launch over exactly those spans on the idle device (bbp_debug_wipe_cost); synchronises."""
+        nbytes, launches, us = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_float()
+        self._check(lib.bbp_debug_wipe_cost(self._h, 1 if clear else 0, ctypes.byref(nbytes), ctypes.byref(launches), ctypes.byref(us)))
+        return nbytes.value, launches.value, us.value
+
     def debug_challenges(self, B, N, proof):
         out = (ctypes.c_uint8 * (32 * 32))()
         self._check(lib.bbp_debug_challenges(self._h, B, N, proof, out))
@@ -682,6 +720,14 @@ class Pool(Context):
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""
         super().set_entropy_source(source)
+
+    def set_secret_wipe(self, on):
+        """bbp_set_secret_wipe on the pool: every member takes the setting, and the pool's combiner erases its gathered rows."""
+        super().set_secret_wipe(on)
+
+    def wipe_secrets(self):
+        """bbp_wipe_secrets on the pool: every member."""
+        super().wipe_secrets()
 
     def set_verify_mixing(self, on):
         """bbp_set_verify_mixing on the pool: the pool's combiner, which deals the combined calls to the members."""

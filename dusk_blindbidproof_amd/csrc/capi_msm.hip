@@ -72,7 +72,14 @@ static int32_t msm_batch_dev(bbp_ctx* ctx, uint32_t B, uint32_t n_terms, const v
     StreamGuard guard(ctx, stream);
     if ((rc = guard.enter())) return rc;
     if ((rc = msm_launch(ctx, B, n_terms, (const u32*)scalars_dev, idx_dev, (ge*)ctx->pts.p, stream))) return rc;
-    return encode_launch(ctx, B, (const ge*)ctx->pts.p, (uint8_t*)out32_dev, stream);
+    if ((rc = encode_launch(ctx, B, (const ge*)ctx->pts.p, (uint8_t*)out32_dev, stream))) return rc;
+    if (wipe_on(ctx)) {  // secret wiping: the hook's scalars are its caller's secret -- their digits and the unencoded sums, stream-ordered
+        WipeList wl;
+        wipe_take(wl, ctx->pts);
+        wipe_take(wl, ctx->sorted);
+        if ((rc = wipe_enqueue(ctx, wl, stream))) return rc;
+    }
+    return BBP_OK;
 }
 
 }  // namespace bbp
@@ -118,6 +125,12 @@ extern "C" int32_t bbp_msm_batch(bbp_ctx* ctx, uint32_t B, uint32_t n_terms, con
         BBP_HIP_TRY(ctx, hipMemcpyAsync(out32, ctx->enc.p, (size_t)B * 32, hipMemcpyDeviceToHost, ctx->stream));
         u32 flags = 0;
         BBP_HIP_TRY(ctx, hipMemcpyAsync(&flags, ctx->health, sizeof(u32), hipMemcpyDeviceToHost, ctx->stream));
+        if (wipe_on(ctx)) {  // ... and the staged copies of the scalars and of the results
+            WipeList wl;
+            wipe_take(wl, ctx->scal);
+            wipe_take(wl, ctx->enc);
+            if ((rc = wipe_enqueue(ctx, wl, ctx->stream))) return rc;
+        }
         BBP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         if (flags) {  // (see fetch_results in capi_prove.hip)
             ctx->err = "engine health flags raised: an MSM table gather was out of range (corrupted engine scratch); results are not trustworthy";

@@ -12,6 +12,7 @@
 #include "chacha.h"
 #include "hedge.h"
 #include "round_bids.h"
+#include "secret_map.h"
 #include "submit.h"
 #include "witness_check.h"
 
@@ -389,6 +390,12 @@ extern "C" int32_t bbp_witness_batch(bbp_ctx* ctx, uint32_t B, const uint8_t* dk
             BBP_HIP_TRY(ctx, hipGetLastError());
         }
         BBP_HIP_TRY(ctx, hipMemcpyAsync(out, ctx->io_out.p, 192 * (size_t)B, hipMemcpyDeviceToHost, ctx->stream));
+        if (wipe_on(ctx)) {  // secret wiping: d, k, seed and what was computed from them, behind the copy that hands the results out
+            WipeList wl;
+            wipe_take(wl, ctx->io_in);
+            wipe_take(wl, ctx->io_out);
+            if ((rc = wipe_enqueue(ctx, wl, ctx->stream))) return rc;
+        }
         BBP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
         return BBP_OK;
     });
@@ -473,11 +480,13 @@ static hipError_t wait_event_polling(hipEvent_t ev) {
 
 static int32_t pinned_reserve(bbp_ctx* ctx, void*& p, size_t& cap, size_t bytes) {
     if (cap >= bytes) return BBP_OK;
+    if (p && wipe_on(ctx)) secure_zero(p, cap);  // secret wiping: a mirror goes back to the driver erased (its slot is this call's: nothing is in flight on it)
     if (p) BBP_HIP_TRY(ctx, hipHostFree(p));
     p = nullptr;
     cap = 0;
     const size_t want = bytes + (bytes >> 3) + 4096;
     BBP_HIP_TRY(ctx, hipHostMalloc(&p, want, hipHostMallocDefault));
+    if (wipe_on(ctx)) memset(p, 0, want);  // ... and a new one starts out zero: a call erases what it wrote, not the capacity
     cap = want;
     return BBP_OK;
 }
@@ -551,6 +560,7 @@ static int32_t next_device_key(bbp_ctx* ctx, ChachaKey* key) {
     });
     if (!armed && !os_random(k, sizeof k)) return no_os_random(ctx);
     *key = chacha_key_from_bytes(k);
+    if (wipe_on(ctx)) secure_zero(k, sizeof k);
     return BBP_OK;
 }
 
@@ -729,9 +739,11 @@ static int32_t prove_entropy(ProveCall& c) {
                 memcpy(w, rp + 64 * k, 64);
                 sc s = sc_from_wide(w);
                 sc_tobytes(&c.ent_host[ent_stride * i + 32 * k], s);
+                if (wipe_on(c.ctx)) secure_zero(w, sizeof w), secure_zero(&s, sizeof s);
             }
             memcpy(&c.ent_host[ent_stride * i + 32 * m], rp + 64 * m, 32);
         }
+        if (wipe_on(c.ctx)) secure_zero_vec(raw);
         c.entropy = c.ent_host.data();
     }
     c.up_ent = c.entropy;
@@ -857,6 +869,44 @@ static int32_t prove_collect(ProveCall& c, bbp_ctx::IoSlot& sl) {
 static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out,
                                 int32_t* status, CheckMode mode = CHECK_AUTO, const RoundInput* round = nullptr);
 
+// Secret wiping, the staging slot of a host-pointer prove call: after its last reader -- the results are in the caller's memory and a
+// hedged round call's failed row keys have been fetched (prove_collect); a second prove of failed rows takes a slot of its own and
+// wipes that.  One launch on the copy stream for the three device buffers, waited for; then the pinned mirrors, on the host.
+// enqueued == false (the enqueue step failed half-way, streams may still read the slot): this slot and whatever the call reserved and
+// did not wipe, behind a device synchronise (wipe_failed_call); other calls' slots are left to them.
+static int32_t slot_wipe(bbp_ctx* ctx, bbp_ctx::IoSlot& sl, const ProveStaging& L, bool enqueued) {
+    int32_t rc = api_guard(ctx, [&]() -> int32_t {  // the lock for the enqueue only, as everywhere on the host path
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if (!enqueued) return wipe_failed_call(ctx, sl);
+        WipeList wl;
+        wipe_take(wl, sl.in);
+        wipe_take(wl, sl.ent);
+        wipe_take(wl, sl.out);
+        if (int32_t rc = wipe_enqueue(ctx, wl, ctx->copy)) return rc;
+        BBP_HIP_TRY(ctx, hipEventRecord(sl.ev_in, ctx->copy));
+        return BBP_OK;
+    });
+    if (rc || !enqueued) return rc;
+    // the wait with the lock released (the copy stream may be queued behind another thread's upload); the slot is still this call's
+    const hipError_t e = wait_event_polling(sl.ev_in);
+    if (sl.h_in) secure_zero(sl.h_in, std::min(sl.h_in_cap, L.h_in_bytes));
+    if (sl.h_out) secure_zero(sl.h_out, std::min(sl.h_cap, L.h_out_bytes));
+    if (e != hipSuccess) {
+        api_guard(ctx, [&]() -> int32_t { return ctx->err = std::string("secret wipe of a staging slot: ") + hipGetErrorString(e), BBP_ERR_DEVICE; });
+        return BBP_ERR_DEVICE;
+    }
+    return BBP_OK;
+}
+// ... and the call's own host copies (stand-in rows, drawn entropy, the call key, fetched row keys), on every way out
+struct ProveCallWipe {
+    ProveCall& c;
+    ~ProveCallWipe() {
+        if (!wipe_on(c.ctx)) return;
+        secure_zero_vec(c.fixed), secure_zero_vec(c.ent_host), secure_zero_vec(c.ent_all), secure_zero_vec(c.fail_keys);
+        secure_zero(&c.key, sizeof c.key);
+    }
+};
+
 // Step 5 (checked calls): rows the screening let through take the device's verdict (their records are already zeroed unless OK),
 // and a record that failed its check is proved once more with the same inputs and the same entropy (the drawn entropy when the
 // caller gave none; source DEVICE: the row re-derived from the call's key), and checked again; a second failure is a device
@@ -880,6 +930,7 @@ static int32_t prove_merge(ProveCall& c) {
         std::vector<uint8_t> keys(c.fail_keys.size());
         for (size_t j = 0; j < order.size(); j++) memcpy(&keys[32 * j], &c.fail_keys[32 * order[j].second], 32);
         c.fail_keys.swap(keys);
+        if (wipe_on(ctx)) secure_zero_vec(keys);  // the unsorted copy
     }
     std::sort(c.fail_rows.begin(), c.fail_rows.end());
     const uint32_t nr = (uint32_t)c.fail_rows.size();
@@ -888,18 +939,20 @@ static int32_t prove_merge(ProveCall& c) {
     std::vector<int32_t> rst(nr);
     for (uint32_t j = 0; j < nr; j++) {
         memcpy(&rin[rin_stride * j], c.src + rin_stride * c.fail_rows[j], rin_stride);
-        if (L.hedged)  // the row's own key: a rows call re-derives it from the row as uploaded, a round call fetched it (prove_collect)
-            hedge_prove_row_bytes(L.round ? chacha_key_from_bytes(&c.fail_keys[32 * j]) : hedge_row_key_bytes(c.key, c.N, c.src + L.in_stride * c.fail_rows[j]), c.N,
-                                  c.fail_rows[j], &rent[L.ent_stride * j]);
-        else if (L.dev_draw)
+        if (L.hedged) {  // the row's own key: a rows call re-derives it from the row as uploaded, a round call fetched it (prove_collect)
+            ChachaKey rk = L.round ? chacha_key_from_bytes(&c.fail_keys[32 * j]) : hedge_row_key_bytes(c.key, c.N, c.src + L.in_stride * c.fail_rows[j]);
+            hedge_prove_row_bytes(rk, c.N, c.fail_rows[j], &rent[L.ent_stride * j]);
+            if (wipe_on(ctx)) secure_zero(&rk, sizeof rk);
+        } else if (L.dev_draw)
             entropy_prove_row_bytes(c.key, c.N, c.fail_rows[j], &rent[L.ent_stride * j]);
         else
             memcpy(&rent[L.ent_stride * j], c.entropy + L.ent_stride * c.fail_rows[j], L.ent_stride);
     }
     ctx->chk_reproved += nr;
     const RoundInput again{c.src2, rin.data(), nullptr};
-    if (int32_t rc = prove_batch_host(ctx, nr, c.N, L.round ? nullptr : rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE, L.round ? &again : nullptr))
-        return rc;
+    const int32_t rc2 = prove_batch_host(ctx, nr, c.N, L.round ? nullptr : rin.data(), rent.data(), rout.data(), rst.data(), CHECK_REPROVE, L.round ? &again : nullptr);
+    if (wipe_on(ctx)) secure_zero_vec(rin), secure_zero_vec(rent);  // the failed rows and their re-derived entropy
+    if (rc2) return rc2;
     for (uint32_t j = 0; j < nr; j++) {
         if (rst[j] != BBP_OK) return raise_check_failure(ctx, c.fail_rows[j]);
         memcpy(c.out + L.res_stride * c.fail_rows[j], &rout[L.res_stride * j], L.res_stride);
@@ -920,6 +973,7 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
     const int source = ctx->entropy_source.load();
     const bool hedged = !entropy && source == BBP_ENTROPY_SOURCE_HEDGED, dev_draw = hedged || (!entropy && source == BBP_ENTROPY_SOURCE_DEVICE);
     ProveCall c{ctx, B, N, in, entropy, out, status, mode, round, ProveStaging(B, N, round != nullptr, check, dev_draw, hedged)};
+    const ProveCallWipe host_wipe{c};
     prove_screen(c);
     if ((rc = prove_entropy(c))) return rc;
     static const bool trace = getenv("BBP_TRACE") != nullptr;
@@ -928,9 +982,17 @@ static int32_t prove_batch_host(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint
         SlotLease lease(ctx);  // may wait for the call two back to collect its results; the context lock is NOT held here
         bbp_ctx::IoSlot& sl = *lease.sl;
         const double t_slot = now_ms();
-        if ((rc = api_guard(ctx, [&]() -> int32_t { return c.t_lock = now_ms(), prove_enqueue(c, sl); }))) return rc;
+        if ((rc = api_guard(ctx, [&]() -> int32_t { return c.t_lock = now_ms(), prove_enqueue(c, sl); }))) {
+            if (wipe_on(ctx)) (void)slot_wipe(ctx, sl, c.L, false);
+            return rc;
+        }
         const double t_enq = now_ms();
-        if ((rc = prove_collect(c, sl))) return rc;
+        rc = prove_collect(c, sl);
+        if (wipe_on(ctx)) {
+            const int32_t wrc = slot_wipe(ctx, sl, c.L, true);
+            if (rc == BBP_OK) rc = wrc;
+        }
+        if (rc) return rc;
         if (trace)
             fprintf(stderr, "[bbp trace] prove_batch B=%u slot=%d: enter %.1f, slot +%.1f, lock +%.1f, h2d +%.1f, enqueued +%.1f, done +%.1f\n", B,
                     (int)(&sl - ctx->io), t_enter, t_slot - t_enter, c.t_lock - t_enter, c.t_h2d - t_enter, t_enq - t_enter, now_ms() - t_enter);
@@ -1053,6 +1115,11 @@ static int32_t round_dev_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u32 B, co
         ctx->debug_corrupt_proof = -1;
         if (rc || (rc = round_rows_enqueue(ctx, B, N, recs, (const u32*)(base + rs.rb), rows_out, s))) return rc;
     }
+    if (wipe_on(ctx)) {  // secret wiping: the ring entry (bids' results, expanded rows), ahead of its event -- the entry's reuse rule covers the wipe
+        WipeList wl;
+        wipe_take(wl, cb.buf);
+        if ((rc = wipe_enqueue(ctx, wl, s))) return rc;
+    }
     BBP_HIP_TRY(ctx, hipEventRecord(cb.ev, s));
     cb.ev_valid = true;
     return BBP_OK;
@@ -1126,6 +1193,16 @@ extern "C" int32_t bbp_debug_corrupt_next_proof(bbp_ctx* ctx, uint32_t index) {
     });
 }
 
+// the key of a device draw in host memory, as bytes and as words
+struct DrawKey {
+    bbp_ctx* ctx;
+    uint8_t k[32] = {};
+    ChachaKey ck{};
+    ~DrawKey() {
+        if (wipe_on(ctx)) secure_zero(k, sizeof k), secure_zero(&ck, sizeof ck);
+    }
+};
+
 extern "C" int32_t bbp_draw_entropy_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t kind, const uint8_t* key32, void* out_dev, void* stream) {
     if (!ctx || !out_dev || (kind != BBP_ENTROPY_PROVE && kind != BBP_ENTROPY_VERIFY)) return BBP_ERR_BAD_ARG;
     if (is_pool(ctx)) return pool_reject(ctx, "bbp_draw_entropy_dev");
@@ -1133,14 +1210,16 @@ extern "C" int32_t bbp_draw_entropy_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, ui
         int32_t rc;
         if (kind == BBP_ENTROPY_PROVE && (rc = check_n(ctx, N))) return rc;
         if (B == 0) return BBP_OK;
-        uint8_t k[32];
+        DrawKey dk{ctx};  // erased on every way out while secret wiping is on
+        uint8_t* const k = dk.k;
         if (key32)
-            memcpy(k, key32, sizeof k);
-        else if (!os_random(k, sizeof k))
+            memcpy(k, key32, sizeof dk.k);
+        else if (!os_random(k, sizeof dk.k))
             return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = pick_stream(ctx, stream);
-        if ((rc = draw_enqueue(ctx, B, N, kind, chacha_key_from_bytes(k), 0, out_dev, s))) return rc;
+        dk.ck = chacha_key_from_bytes(k);
+        if ((rc = draw_enqueue(ctx, B, N, kind, dk.ck, 0, out_dev, s))) return rc;  // (the launch takes the key by value)
         if (kind == BBP_ENTROPY_PROVE) {  // the next prove call's opening stage waits for these rows (not ev_prep: see context.h)
             BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_draw, s));
             ctx->ev_draw_valid = true;
@@ -1157,16 +1236,18 @@ extern "C" int32_t bbp_draw_entropy_hedged_dev(bbp_ctx* ctx, uint32_t B, uint32_
         if ((rc = check_n(ctx, N))) return rc;
         if (((uintptr_t)in_dev | (uintptr_t)out_dev) & 3) return ctx->err = "hedged entropy draw: rows must be 4-byte aligned", BBP_ERR_BAD_ARG;
         if (B == 0) return BBP_OK;
-        uint8_t k[32];
+        DrawKey dk{ctx};  // erased on every way out while secret wiping is on
+        uint8_t* const k = dk.k;
         if (key32)
-            memcpy(k, key32, sizeof k);
-        else if (!os_random(k, sizeof k))
+            memcpy(k, key32, sizeof dk.k);
+        else if (!os_random(k, sizeof dk.k))
             return ctx->err = "cannot read /dev/urandom", BBP_ERR_DEVICE;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         hipStream_t s = pick_stream(ctx, stream);
         // the draw reads the rows: a pending prepare is waited for here, and stays pending for the next prove call (which reads them too)
         if (ctx->ev_prep_valid) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_prep, 0));
-        if ((rc = hedged_draw_enqueue(ctx, B, N, chacha_key_from_bytes(k), 0, in_dev, nullptr, out_dev, s))) return rc;
+        dk.ck = chacha_key_from_bytes(k);
+        if ((rc = hedged_draw_enqueue(ctx, B, N, dk.ck, 0, in_dev, nullptr, out_dev, s))) return rc;  // (the launch takes the key by value)
         BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_draw, s));
         ctx->ev_draw_valid = true;
         return BBP_OK;
@@ -1212,6 +1293,7 @@ static void async_done(Request* r) {
     void (*fn)(void*, int32_t) = r->user_fn;
     void* user = r->user;
     const int32_t st = r->status;
+    if (r->origin && wipe_on(static_cast<const bbp_ctx*>(r->origin))) secure_zero_vec(r->own_in), secure_zero_vec(r->own_entropy);
     delete r;
     fn(user, st);
 }
@@ -1243,8 +1325,10 @@ extern "C" int32_t bbp_prove(bbp_ctx* ctx, const uint8_t scalars7[7 * 32], const
         if (st != BBP_OK) {
             set_tls_error(ctx, !r.err.empty() ? r.err : st == BBP_ERR_BAD_ARG ? (ctx->prove_check ? refused_row_text(ctx, in.data(), N) : "toggle >= N")
                                                                              : "non-canonical scalar input");
+            if (wipe_on(ctx)) secure_zero_vec(in);
             return st;
         }
+        if (wipe_on(ctx)) secure_zero_vec(in);
         if (proof_len) *proof_len = BBP_R1CS_PROOF_BYTES;
         return BBP_OK;
     }, ctx);
@@ -1273,6 +1357,7 @@ extern "C" int32_t bbp_prove_async(bbp_ctx* ctx, const uint8_t scalars7[7 * 32],
         r->user_fn = done;
         r->user = user;
         if (!static_cast<Combiner*>(ctx->combiner)->submit_async(ctx, r)) {
+            if (wipe_on(ctx)) secure_zero_vec(r->own_in), secure_zero_vec(r->own_entropy);
             delete r;
             set_tls_error(ctx, "call combiner: cannot start a batch thread");
             return BBP_ERR_INTERNAL;
@@ -1724,6 +1809,7 @@ extern "C" int32_t bbp_debug_challenges(bbp_ctx* ctx, uint32_t B, uint32_t N, ui
     if (!ctx || !out32x32 || proof >= B) return BBP_ERR_BAD_ARG;
     if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_challenges");
     return api_guard(ctx, [&]() -> int32_t {
+        if (wipe_on(ctx)) return ctx->err = "bbp_debug_challenges: secret wiping is on, the challenge block has been erased", BBP_ERR_BAD_ARG;
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         BBP_HIP_TRY(ctx, hipDeviceSynchronize());
         return debug_read_misc(ctx, B, N, proof, out32x32);

@@ -61,6 +61,7 @@ constexpr int GE_WORDS = sizeof(ge) / 4;  // 40: a point in registers / LDS / sc
 struct DevBuf {
     void* p = nullptr;
     size_t cap = 0;
+    size_t dirty = 0;  // secret wiping on: the most bytes asked of the buffer since its last wipe (wipe.hip wipe_take erases those)
 };
 
 }  // namespace bbp
@@ -166,6 +167,17 @@ struct bbp_ctx {
                                  // satisfied witness failed its check twice (checked proving) -- bbp_check_health
     // Checked proving (bbp_set_prove_check, capi_prove.hip): every record is verified on the device before it is handed out.
     std::atomic<int> prove_check{0};
+    // Secret wiping (bbp_set_secret_wipe, wipe.hip; the classes are secret_map.h's): while on, every SECRET buffer reads zero whenever
+    // no prove-side call is in flight -- each call erases what it wrote, at the end of the stream that guards the buffer
+    std::atomic<int> secret_wipe{0};
+    struct WipeLog {  // the wipes enqueued since the log was cleared (bbp_debug_wipe_cost): how many bytes in how many launches, over which buffers
+        static constexpr int CAP = 24;  // = WIPE_SPANS: what one lone launch replays
+        uint64_t bytes = 0;
+        uint32_t launches = 0;
+        int n = 0;
+        bbp::DevBuf* buf[CAP] = {};
+        uint64_t span_bytes[CAP] = {};
+    } wipe_log;
     std::atomic<uint64_t> chk_checked{0}, chk_reproved{0};  // rows handed to checked calls / records proved a second time
     unsigned long long* chk_counts = nullptr;  // device [2]: rows refused by the witness check / records that failed verification
     int64_t debug_corrupt_proof = -1;          // bbp_debug_corrupt_next_proof: record index of the next prove call to corrupt (tests)
@@ -267,8 +279,14 @@ inline bool device_affinity_ok(bbp_ctx* ctx, const char* what) {
     } while (0)
 
 inline int32_t dev_reserve(bbp_ctx* ctx, DevBuf& b, size_t bytes) {
+    const bool wipe = ctx->secret_wipe.load(std::memory_order_relaxed) != 0;
+    if (wipe && bytes > b.dirty) b.dirty = bytes;  // what the call is about to write: its wipe erases that much
     if (b.cap >= bytes) return BBP_OK;
     if (b.p) {
+        if (wipe) {  // old contents never go back to the driver as they are (hipFree would wait for the device anyway)
+            BBP_HIP_TRY(ctx, hipDeviceSynchronize());
+            BBP_HIP_TRY(ctx, hipMemset(b.p, 0, b.cap));
+        }
         BBP_HIP_TRY(ctx, hipFree(b.p));
         ctx->scratch_bytes -= b.cap;
     }
@@ -276,6 +294,10 @@ inline int32_t dev_reserve(bbp_ctx* ctx, DevBuf& b, size_t bytes) {
     b.cap = 0;
     size_t want = bytes + (bytes >> 3) + 4096;
     BBP_HIP_TRY(ctx, hipMalloc(&b.p, want));
+    if (wipe) {  // ... and a new one starts out zero (the driver hands out whatever was freed last): a call erases what it wrote, not the capacity
+        BBP_HIP_TRY(ctx, hipMemsetAsync(b.p, 0, want, nullptr));
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(nullptr));  // the context's streams do not wait for the null stream
+    }
     b.cap = want;
     ctx->scratch_bytes += want;
     ctx->scratch_allocs++;  // bbp_describe reports both: after bbp_reserve the count must stand still (tests/test_gpu_boundary.py)
@@ -287,7 +309,7 @@ inline int32_t dev_reserve(bbp_ctx* ctx, DevBuf& b, size_t bytes) {
 }
 
 enum { TAG_MSM = 1, TAG_ENCODE = 2, TAG_WITNESS = 3, TAG_RNG = 4, TAG_POLY = 5, TAG_IPA_SCALARS = 6, TAG_COMMIT = 7,
-       TAG_TRANSCRIPT = 8, TAG_VERIFY_SCALARS = 9, TAG_VARBASE = 10, TAG_MSM_SORT = 11, TAG_MSM_FOLD = 12 };
+       TAG_TRANSCRIPT = 8, TAG_VERIFY_SCALARS = 9, TAG_VARBASE = 10, TAG_MSM_SORT = 11, TAG_MSM_FOLD = 12, TAG_WIPE = 13 /* k_wipe_spans */ };
 
 struct ScopedEvent {  // records start now, stop at scope exit, when profiling is on
     bbp_ctx* ctx;
@@ -440,6 +462,22 @@ int32_t fold_generators_launch(bbp_ctx* ctx, uint32_t n_proofs, const sc* g_dev,
                                int scratch_slot);
 int32_t encode_launch(bbp_ctx* ctx, uint32_t n, const ge* pts_dev, uint8_t* out32_dev, hipStream_t stream);
 size_t msm_scratch_bytes(uint32_t n_msm, uint32_t n_terms);
+// wipe.hip (secret wiping).  A wipe is one k_wipe_spans launch over up to WIPE_SPANS spans; every span is checked against its buffer.
+constexpr int WIPE_SPANS = 24;  // the most one launch takes (a call's own lists hold at most four; bbp_debug_wipe_cost replays a whole call's)
+struct WipeSpan {
+    void* p;
+    unsigned long long bytes;  // a multiple of 16
+};
+struct WipeList {
+    int n = 0;
+    WipeSpan s[WIPE_SPANS];
+    DevBuf* buf[WIPE_SPANS];  // the buffer behind each span
+};
+inline bool wipe_on(const bbp_ctx* ctx) { return ctx->secret_wipe.load(std::memory_order_relaxed) != 0; }
+void wipe_take(WipeList& l, DevBuf& b);                              // what the buffer's users asked of it since its last wipe
+int32_t wipe_enqueue(bbp_ctx* ctx, const WipeList& l, hipStream_t s);  // one launch on s (none for an empty list)
+int32_t wipe_all(bbp_ctx* ctx);                                      // every SECRET buffer over its capacity, device and pinned; synchronises
+int32_t wipe_failed_call(bbp_ctx* ctx, bbp_ctx::IoSlot& sl);         // what a half-enqueued host call reserved, and its slot; synchronises
 // prover.hip
 int32_t tail_btab_build(bbp_ctx* ctx);
 size_t tail_btab_bytes();  // what it allocates for ctx->btab

@@ -1425,6 +1425,16 @@ static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& 
     // enqueued on the caller's stream ahead of this call (a consumer of the previous call's records, say) has finished
     if (out_guard) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, out_guard, 0));
     LAUNCH(ctx, TAG_TRANSCRIPT, k_assemble, cdiv(B, 64), 64, s, B, m, bd.enc, bd.misc, out_dev);
+    // secret wiping: the MSM scratch slot of this stage, at the end of the stream that guards it (the slot's next user is a later launch
+    // on this stream, or waits for the join event recorded behind this)
+    if (wipe_on(ctx)) {
+        WipeList wl;
+        wipe_take(wl, ptsbuf);
+        wipe_take(wl, slot ? ctx->slice_sorted[slot] : ctx->sorted);
+        wipe_take(wl, ctx->slice_fold[slot]);
+        wipe_take(wl, ctx->slice_vtab[slot]);
+        if ((rc = wipe_enqueue(ctx, wl, s))) return rc;
+    }
     return BBP_OK;
 }
 
@@ -1561,6 +1571,11 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     // (k_open_bulk50 writes the draws as bit-interleaved halves)
     LAUNCH(ctx, TAG_RNG, k_reduce_draws, cdiv((u32)(B * n_draws), 128), 128, os, B, n1, (const u32*)raw, bd.ai1, bd.ao1, bd.s1,
            plan.chain == ProvePlan::HALFWORD ? 1u : 0u);
+    if (wipe_on(ctx)) {  // secret wiping: the draws are reduced; their buffer is the opening stream's own, stream order guards it
+        WipeList wl;
+        wipe_take(wl, ctx->raw[ridx]);
+        if ((rc = wipe_enqueue(ctx, wl, os))) return rc;
+    }
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_open[par], os));
     ctx->ev_open_valid[par] = true;
     if (ctx->knobs.trace_prove) fputs(plan.trace_line(plan.call, B, inflight).c_str(), stderr);
@@ -1598,6 +1613,13 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
             BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_join[i], ls));
             BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_join[i], 0));
         }
+    }
+    // secret wiping: the batch buffer, behind the last join and ahead of ev_done[par] -- the buffer's next user waits for that event and
+    // nothing else, so the wipe neither runs under this call's slices nor eats into that call's opening stage
+    if (wipe_on(ctx)) {
+        WipeList wl;
+        wipe_take(wl, ctx->batch[par]);
+        if ((rc = wipe_enqueue(ctx, wl, s))) return rc;
     }
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_done[par], s));
     ctx->ev_done_valid[par] = true;

@@ -340,6 +340,7 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
     ctx->combiner = nullptr;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
+    if (wipe_on(ctx)) (void)wipe_all(ctx);  // secret wiping: nothing goes back to the driver as it is (an interrupted call may have left its spans)
     std::vector<void*> ptrs = {ctx->gens, ctx->ptable, ctx->btab, ctx->comb, ctx->mimc_c, ctx->scal.p, ctx->idx.p, ctx->sorted.p, ctx->pts.p, ctx->enc.p,
                                ctx->io_in.p, ctx->io_out.p, ctx->io_ent.p};
     for (auto& b : ctx->raw) ptrs.push_back(b.p);
@@ -496,6 +497,9 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
         if (off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "checked proving: %s\n",
                                       ctx->prove_check ? "on (every record is verified on the device before it is returned)" : "off");
+        if (off + 1 < cap)
+            off += (uint32_t)snprintf(buf + off, cap - off, "secret wipe: %s\n",
+                                      wipe_on(ctx) ? "on (every prove-side call erases what it wrote, on the device and in the staging mirrors)" : "off");
         if (off + 1 < cap && ctx->combiner)
             off += (uint32_t)snprintf(buf + off, cap - off, "verify mixing: %s\n",
                                       static_cast<Combiner*>(ctx->owner && ctx->owner->combiner ? ctx->owner->combiner : ctx->combiner)->verify_mixing()

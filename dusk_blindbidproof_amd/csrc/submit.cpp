@@ -512,7 +512,13 @@ void Combiner::run_batch(bbp_ctx* ctx, std::vector<Request*>& batch, MixedVerify
                 ent.resize((size_t)B * ent_len);
                 for (uint32_t i = 0; i < B; i++) memcpy(&ent[(size_t)i * ent_len], batch[i]->entropy, ent_len);
             }
-            rc = prove_batch_locked(ctx, B, h.N, in.data(), h.entropy ? ent.data() : nullptr, out.data(), status.data(), &err);
+            try {
+                rc = prove_batch_locked(ctx, B, h.N, in.data(), h.entropy ? ent.data() : nullptr, out.data(), status.data(), &err);
+            } catch (...) {
+                if (secret_wipe()) secure_zero_vec(in), secure_zero_vec(ent);
+                throw;
+            }
+            if (secret_wipe()) secure_zero_vec(in), secure_zero_vec(ent);  // the gathered rows and entropy, before the vectors release them
             if (rc == 0)
                 for (uint32_t i = 0; i < B; i++)
                     if (status[i] == 0) memcpy(batch[i]->out, &out[(size_t)i * rec_len], rec_len);

@@ -35,6 +35,8 @@
 #include <thread>
 #include <vector>
 
+#include "secure_zero.h"
+
 struct bbp_ctx;
 
 namespace bbp {
@@ -163,6 +165,9 @@ class Combiner {
     void set_round_verify(RoundVerifyFn fn);
     void set_round_sharing(bool on);
     bool round_sharing() const { return sharing_.load(std::memory_order_relaxed); }  // the switch alone (what a caller asks before it hashes)
+    // Secret wiping (bbp_set_secret_wipe; default off): a prove batch's gathered rows and entropy are erased before their memory is released
+    void set_secret_wipe(bool on) { wipe_.store(on, std::memory_order_relaxed); }
+    bool secret_wipe() const { return wipe_.load(std::memory_order_relaxed); }
     // rounds calls issued / rows they carried / rounds their tables held (any may be NULL); per target for a pool
     void round_stats(uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds);
     void target_round_stats(size_t i, uint64_t* n_calls, uint64_t* n_rows, uint64_t* n_rounds);
@@ -179,6 +184,7 @@ class Combiner {
     bool mixing_ = true;
     RoundVerifyFn round_fn_ = nullptr;
     std::atomic<bool> sharing_{false};  // written under mu_; read without it by callers that decide whether to hash
+    std::atomic<bool> wipe_{false};
     struct RoundCounts {
         uint64_t calls = 0, rows = 0, rounds = 0;
     };

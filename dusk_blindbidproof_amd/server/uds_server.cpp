@@ -647,11 +647,12 @@ static void usage(const char* argv0) {
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
             "          [--check-proofs] [--entropy os|device|hedged] [--verify-mixing on|off] [--verify-rounds on|off]\n"
-            "          [--pipeline-depth D] [--max-inflight M]\n"
+            "          [--pipeline-depth D] [--max-inflight M] [--wipe-secrets]\n"
             "  --pipeline-depth D  requests of ONE connection with the engine at once, replies in request order (1..4096, default 64;\n"
             "                      1 = one request per connection at a time)\n"
             "  --max-inflight M    beyond each connection's first request, requests are admitted only while fewer than M are with\n"
-            "                      the engine (default: the value of --max-connections)\n",
+            "                      the engine (default: the value of --max-connections)\n"
+            "  --wipe-secrets      every prove call erases the witness, blindings and keys it left in engine memory (bbp_set_secret_wipe)\n",
             argv0);
 }
 
@@ -666,6 +667,7 @@ int main(int argc, char** argv) {
     // --entropy device: one OS key per engine call, expanded on the device; hedged: each row's key also bound to the row's own inputs
     // (bbp_set_entropy_source)
     int32_t entropy_source = BBP_ENTROPY_SOURCE_OS;
+    bool wipe_secrets = false;  // --wipe-secrets: no witness, blinding or key outlives its call in engine memory (bbp_set_secret_wipe); the SIGTERM path erases through bbp_free
     int verify_mixing = -1;  // --verify-mixing on|off: opcode-2 requests share device calls across bid-list lengths (bbp_set_verify_mixing); -1 = not given, the engine's default (on)
     int verify_rounds = -1;  // --verify-rounds on|off: opcode-2 requests with a byte-equal seed and bid list share one rounds call (bbp_set_verify_round_sharing); -1 = not given, no call is made (the engine's default: off)
     for (int i = 1; i < argc; i++) {
@@ -706,6 +708,7 @@ int main(int argc, char** argv) {
         else if (a == "--verify-aggregate") setenv("BBP_VERIFY_AGGREGATE", val(), 1);  // opcode-2 batches of >= 2 G proofs are checked in groups of G with
                                                                                          // per-proof fallback: same verdicts, 2-3x the rate (include/bbp.h)
         else if (a == "--check-proofs") check_proofs = true;
+        else if (a == "--wipe-secrets") wipe_secrets = true;
         else if (a == "--entropy") {
             const std::string v = val();
             if (v != "os" && v != "device" && v != "hedged") {
@@ -787,6 +790,20 @@ int main(int argc, char** argv) {
                 return 2;
             }
             logf(2, "checked proving on: every proof is verified on the device before it is answered");
+        }
+        if (wipe_secrets) {  // resolved only when asked for: an engine without it cannot honour the flag, so the server does not start
+            auto set_wipe = (decltype(&bbp_set_secret_wipe))dlsym(g_eng.so, "bbp_set_secret_wipe");
+            if (!set_wipe) {
+                logf(0, "--wipe-secrets: the engine %s does not provide secret wiping (bbp_set_secret_wipe)", engine_path.c_str());
+                g_eng.free_(g_eng.ctx);
+                return 2;
+            }
+            if (const int32_t rc = set_wipe(g_eng.ctx, 1)) {
+                logf(0, "--wipe-secrets: bbp_set_secret_wipe failed with status %d: %s", rc, g_eng.last_error(g_eng.ctx));
+                g_eng.free_(g_eng.ctx);
+                return 1;
+            }
+            logf(2, "secret wiping on: every prove call erases what it left in engine memory");
         }
         if (entropy_source != BBP_ENTROPY_SOURCE_OS) {  // resolved only when asked for: an engine without it (or one that rejects the value) cannot honour the flag, so the server does not start
             const bool hedged = entropy_source == BBP_ENTROPY_SOURCE_HEDGED;

@@ -485,6 +485,51 @@ int32_t bbp_draw_entropy_hedged_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const 
  * so that its records can be compared with an explicit-entropy call; consumed by that call.  A pool refuses it (take a member). */
 int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]);
 
+/* ---- Secret wiping ------------------------------------------------------------------------------------------------------------------
+ * The engine proves with the bidder's secrets -- d, k, y, y^-1, the toggle, every commitment blinding, the TranscriptRng seed, a call's
+ * entropy key and its hedged row keys -- and by default keeps what it computed in its batch buffers, MSM scratch, draw buffers,
+ * staging slots and their pinned host mirrors until a later call overwrites it.  With wiping on, no blinding and no witness outlives
+ * the call that used it.  Opt-in, default off; with it off no launch, copy or host write is added anywhere.
+ *
+ * Invariant while on: whenever no prove-side call is in flight on the context, every byte of every buffer the context owns and that
+ * csrc/secret_map.h classes SECRET is zero, in device memory and in pinned host memory.  (Default-secret: whatever a prove-side call
+ * writes is SECRET unless that table names it PUBLIC and says why.)
+ *   bbp_set_secret_wipe(ctx, 1)   erases everything once and synchronises, so the invariant holds from that moment (call it while no
+ *                                 call is in flight); afterwards each call erases only what it wrote.  0: erases nothing, adds nothing.
+ *                                 On a pool: every member.
+ *   bbp_wipe_secrets(ctx)         erases every SECRET buffer over its whole capacity now, whatever the setting; synchronises the
+ *                                 device.  On a pool: every member.
+ * Per call: when a host-pointer prove-side call returns, or its `done` callback fires, that call's wipes have completed (bbp_prove,
+ * bbp_prove_async, bbp_prove_batch, bbp_prove_round, bbp_witness_batch, bbp_msm_batch; combined or not; a context or a pool).  For the
+ * _dev forms (bbp_prove_batch_dev, bbp_prove_batch_checked_dev, bbp_prove_round_dev, bbp_prepare_round_dev, bbp_msm_batch_dev) the wipes
+ * of library-owned memory are stream-ordered: complete for anything enqueued on `stream` after the call.  bbp_prepare_bids_dev and
+ * bbp_draw_entropy*_dev write the caller's buffers only.  Records, statuses, toggles and every other output are byte for byte what
+ * they are with wiping off; verify calls are untouched.  Also while on: a buffer that is about to be freed to grow is erased first,
+ * bbp_free erases before it frees, bbp_debug_challenges returns BBP_ERR_BAD_ARG (the challenge block is erased), and bbp_describe
+ * prints "secret wipe: on".
+ * After a FAILED prove-side call the invariant may lapse: a _dev form that returns an error after some of its launches were enqueued
+ * erases nothing more (what it reserved is erased by the next call that uses the same buffers, or by bbp_wipe_secrets); a failed
+ * host-pointer call erases its staging slot and whatever it had reserved, behind a device synchronise (other calls are untouched).  Call bbp_wipe_secrets after an error that must leave nothing.
+ * What it is NOT: it does not scrub caches, LDS or registers; it does not erase the caller's own buffers (inputs, entropy, device
+ * rows handed to a _dev form); and it is not a constant-time claim. */
+int32_t bbp_set_secret_wipe(bbp_ctx* ctx, int32_t on);
+int32_t bbp_wipe_secrets(bbp_ctx* ctx);
+/* Test hooks; both synchronise the whole context; a pool refuses them (take a member).
+ * residue: the number of non-zero bytes over the whole capacity of every SECRET buffer, device and pinned; `where` (cap bytes, may be
+ * NULL with cap 0) receives the table name of the first buffer with residue, or "".
+ * scan: exact matches of pattern[0 .. len) at every 4-byte offset of every grow-only device buffer, ring, staging slot and pinned mirror
+ * of the context, SECRET and PUBLIC alike, and of the resident tables (gens, ptable, btab, comb, MiMC constants).  Not walked: the
+ * compiled circuits' lists and the mixed-N circuit table (uploaded once from host tables that are functions of N) and the counter
+ * words (health, check counts, aggregation counts, the pinned health mirror).  len is a multiple of 4 from 4 to 64, anything else is
+ * BBP_ERR_BAD_ARG.
+ * wipe_cost: what the wipes enqueued since the log was last cleared stored -- *bytes in *launches k_wipe_spans launches -- and
+ * *lone_us, the device time (events) of ONE k_wipe_spans launch over exactly those spans, made now on the idle device; clear != 0
+ * empties the log afterwards (turning wiping on and bbp_wipe_secrets empty it too).  At most 24 spans replay in one launch (one prove
+ * call logs 6 to 18): with more in the log the call is BBP_ERR_BAD_ARG, and bytes / launches are still reported. */
+int32_t bbp_debug_secret_residue(bbp_ctx* ctx, uint64_t* dev_bytes, uint64_t* host_bytes, char* where, uint32_t cap);
+int32_t bbp_debug_secret_scan(bbp_ctx* ctx, const uint8_t* pattern, uint32_t len, uint64_t* dev_hits, uint64_t* host_hits);
+int32_t bbp_debug_wipe_cost(bbp_ctx* ctx, int32_t clear, uint64_t* bytes, uint32_t* launches, float* lone_us);
+
 /* Parity hook: the 32-scalar challenge block of proof `proof` of the LAST batch call of geometry (B, N):
  * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch_layout.h), 32 x 32 bytes. */
 int32_t bbp_debug_challenges(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t proof, uint8_t* out32x32);

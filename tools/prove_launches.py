@@ -22,7 +22,7 @@ import sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 TAGS = {1: "msm_acc", 2: "encode", 3: "witness", 4: "rng", 5: "poly", 6: "ipa_scalars", 7: "commit", 8: "transcript", 9: "verify_scalars",
-        10: "varbase", 11: "msm_sort", 12: "msm_fold"}
+        10: "varbase", 11: "msm_sort", 12: "msm_fold", 13: "wipe"}
 
 
 def main():
