@@ -1,4 +1,5 @@
 """ctypes binding of include/bbp.h. Fails loudly when the HIP library is missing: there is no fallback."""
+import collections
 import ctypes
 import os
 
@@ -81,6 +82,9 @@ SIGNATURES = {
     "bbp_check_health": (_i32, [_vp, ctypes.POINTER(_u32)]),
     "bbp_debug_corrupt_scratch": (_i32, [_vp]),
     "bbp_describe": (_i32, [_vp, _vp, _u32]),
+    "bbp_select_round_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_prove_round_select": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_round_select": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "bbp_set_prove_check": (_i32, [_vp, _i32]),
     "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -224,6 +228,18 @@ def pack_round_bids(bids):
             raise ValueError("a bid is two 32-byte scalars d, k")
         parts += [d, k]
     return b"".join(bytes(p) for p in parts)
+
+
+SELECT_MAX_BIDS = 1 << 20  # BBP_SELECT_MAX_BIDS
+RoundSelection = collections.namedtuple("RoundSelection", "rc rows sel n_sel n_qualified toggles scores status")
+
+
+def select_floor(floor):
+    """floor32 of the select calls from an int in [0, 2^256) or 32 bytes (unsigned, little-endian)."""
+    b = floor.to_bytes(32, "little") if isinstance(floor, int) else bytes(floor)
+    if len(b) != 32:
+        raise ValueError("a floor is 32 bytes")
+    return b
 
 
 def _u32s(values):
@@ -483,6 +499,55 @@ class Context:
                                         toggles, status))
         return bytes(rows)[:B * round_row_size(N)], list(toggles)[:B], list(status)[:B]
 
+    def prove_round_select(self, N, table, bids, floor=0, K=0, cap=None, entropy=None, want_scores=False, check=True):
+        """bbp_prove_round_select: score every bid of the round, select the K best at or above `floor` (K = 0: all of them), prove only
+        those.  cap: room for rows (default: K, or every bid when K = 0); entropy: cap rows, row j for sel[j], or None.  Returns a
+        RoundSelection: rows / sel / toggles of the n_sel selected bids in ascending index order, n_qualified, the B scores when
+        want_scores, the B statuses.  check=False: a failing call returns with its rc (n_sel > cap: counts, scores, statuses are valid)."""
+        if len(table) != 32 * (1 + N) or len(bids) % ROUND_BID_BYTES:
+            raise ValueError("a round is a 32-byte seed and N 32-byte items; bids are 64 bytes each")
+        B = len(bids) // ROUND_BID_BYTES
+        if cap is None:
+            cap = K if K else B
+        if entropy is not None and len(entropy) != cap * entropy_size(N):
+            raise ValueError("entropy must hold entropy_size(N) bytes per row of cap")
+        row = round_row_size(N)
+        rows = (ctypes.c_uint8 * max(1, cap * row))()
+        sel = (_u32 * max(1, cap))()
+        toggles = (ctypes.c_uint64 * max(1, cap))()
+        scores = (ctypes.c_uint8 * max(1, 32 * B))() if want_scores else None
+        status = (ctypes.c_int32 * max(1, B))()
+        n_sel, n_q = _u32(0), _u32(0)
+        rc = lib.bbp_prove_round_select(self._h, N, _buf(table), B, _buf(bids) if B else rows, _buf(select_floor(floor)), K, cap,
+                                        None if entropy is None else _buf(entropy), rows, sel, ctypes.byref(n_sel), ctypes.byref(n_q), toggles, scores,
+                                        status)
+        if check:
+            self._check(rc)
+        n = min(n_sel.value, cap) if rc == 0 else 0
+        return RoundSelection(rc, bytes(rows)[:n * row], list(sel)[:n], n_sel.value, n_q.value, list(toggles)[:n],
+                              bytes(scores)[:32 * B] if want_scores else None, list(status)[:B])
+
+    def select_round_dev(self, N, table_ptr, B, bids_ptr, floor, K, cap, sel_ptr, counts_ptr, status_ptr, scores_ptr=None, prove_in_ptr=None,
+                         tails_ptr=None, toggles_ptr=None, stream=None):
+        """bbp_select_round_dev: scoring, selection and -- when any of prove_in_ptr / tails_ptr / toggles_ptr is given -- the selected
+        bids' rows for prove_batch_dev (which waits for them by itself).  Stream-ordered, no synchronisation; counts = n_sel, n_qualified."""
+        self._check(lib.bbp_select_round_dev(self._h, N, table_ptr, B, bids_ptr, _buf(select_floor(floor)), K, cap, sel_ptr, counts_ptr, status_ptr,
+                                             scores_ptr, prove_in_ptr, tails_ptr, toggles_ptr, _stream(stream)))
+
+    def debug_round_select(self, scores, statuses, floor=0, K=0, cap=None):
+        """bbp_debug_round_select (test hook): the shipped selection kernel on made-up scores (B x 32 bytes) and statuses.  Returns
+        (sel[:min(n_sel, cap)], n_sel, n_qualified)."""
+        B = len(statuses)
+        if len(scores) != 32 * B:
+            raise ValueError("scores are 32 bytes per status")
+        if cap is None:
+            cap = B
+        sel = (_u32 * max(1, cap))()
+        n_sel, n_q = _u32(0), _u32(0)
+        self._check(lib.bbp_debug_round_select(self._h, B, _buf(scores), (ctypes.c_int32 * max(1, B))(*statuses), _buf(select_floor(floor)), K, cap, sel,
+                                               ctypes.byref(n_sel), ctypes.byref(n_q)))
+        return list(sel)[:min(n_sel.value, cap)], n_sel.value, n_q.value
+
     def prepare_round_dev(self, N, table_ptr, B, bids_ptr, prove_in_ptr, status_ptr, tails_ptr=None, toggles_ptr=None, stream=None):
         """bbp_prepare_round_dev: the device pass alone -- rows for prove_batch_dev (which waits for them by itself), optionally
         score || z_img tails and u64 toggles, int32 statuses.  Stream-ordered, no synchronisation."""
@@ -690,7 +755,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):
@@ -716,6 +781,11 @@ class Pool(Context):
         """bbp_prove_round on the pool: the bids block-split by index over the members, every member receives the table; rows, toggles
         and statuses in request order."""
         return super().prove_round(N, table, bids, entropy)
+
+    def prove_round_select(self, N, table, bids, floor=0, K=0, cap=None, entropy=None, want_scores=False, check=True):
+        """bbp_prove_round_select on the pool: member 0 scores and selects, the selected bids are proved as prove_round proves them
+        (block-split over the members, rows in the order of sel)."""
+        return super().prove_round_select(N, table, bids, floor, K, cap, entropy, want_scores, check)
 
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""

@@ -12,6 +12,7 @@
 #include "chacha.h"
 #include "hedge.h"
 #include "round_bids.h"
+#include "round_select.h"
 #include "secret_map.h"
 #include "submit.h"
 #include "witness_check.h"
@@ -278,34 +279,52 @@ static int32_t hedged_draw_enqueue(bbp_ctx* ctx, u32 B, u32 N, const ChachaKey& 
 }
 
 
-// The device pass of a round call on s (round_bids.h): bids first.. of a call whose scratch (round_scratch of the whole call) is at
-// `scratch`; `reduce`: the table is reduced first (once per call).  bids / prove_in / tails / toggles / status point at bid `first`.
-static int32_t round_prepare_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u8* scratch, const RoundScratch& rs, bool reduce, u32 first, u32 B,
-                                     const u8* bids, u32* prove_in, u32* tails, u32* toggles, int32_t* status, hipStream_t s) {
+// The device pass of a round call on s (round_bids.h), in the three steps that can be enqueued separately.  scratch: the RoundScratch
+// `rs` of the whole call.  (1) the table, reduced once per call: the two round offsets k_round_consts reads are written in stream order
+// (no host memory involved)
+static int32_t round_reduce_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u8* scratch, const RoundScratch& rs, hipStream_t s) {
+    u32* roff = (u32*)(scratch + rs.roff);
+    BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)roff, 0, 1, s));
+    BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(roff + 1), (int)(1 + N), 1, s));
+    return round_consts_launch(ctx, N, table, roff, (sc*)(scratch + rs.rblk), (int32_t*)(scratch + rs.rflag), s);
+}
+// (2) the bid kernel over B bids into rb; n_dev (or NULL): a device-side count below B (round_bids.h)
+static int32_t round_bids_enqueue(bbp_ctx* ctx, u32 N, u8* scratch, const RoundScratch& rs, u32 B, const u8* bids, u32* rb, const u32* n_dev,
+                                  hipStream_t s) {
+    int32_t rc;
+    unsigned hog = 0;  // a serial wave of four MiMC chains beside other calls' heavy stages: fenced onto CUs of its own, as k_prepare_bids
+    if ((rc = serial_lds_bytes(ctx, (const void*)k_round_bids, &hog))) return rc;
+    hipLaunchKernelGGL(k_round_bids, dim3((B + 63) / 64), dim3(64), hog, s, B, N, bids, (const sc*)(scratch + rs.rblk), (const int32_t*)(scratch + rs.rflag),
+                       ctx->mimc_c, rb, n_dev);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+// (3) the expansion of rb into the prover's rows, tails, toggles, statuses
+static int32_t round_expand_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u32 B, const u8* bids, const u32* rb, u32* prove_in, u32* tails, u32* toggles,
+                                    int32_t* status, const u32* n_dev, hipStream_t s) {
     const u64 n = (u64)B * (round_in_words(N) + RB_EXTRA_WORDS);
-    if (n > 0x7fffffffull) {
+    hipLaunchKernelGGL(k_round_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), lds_token(ctx), s, (u32)n, N, bids, table, rb, prove_in, tails, toggles,
+                       status, n_dev);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+static int32_t round_lanes_ok(bbp_ctx* ctx, u32 N, u32 B) {
+    if ((u64)B * (round_in_words(N) + RB_EXTRA_WORDS) > 0x7fffffffull) {
         ctx->err = "round prepare: too many bids for one call";
         return BBP_ERR_BAD_ARG;
     }
-    u32* roff = (u32*)(scratch + rs.roff);
-    sc* rblk = (sc*)(scratch + rs.rblk);
-    int32_t* rflag = (int32_t*)(scratch + rs.rflag);
-    u32* rb = (u32*)(scratch + rs.rb) + (size_t)RB_WORDS * first;
-    int32_t rc;
-    if (reduce) {  // the two round offsets k_round_consts reads, written in stream order (no host memory involved)
-        BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)roff, 0, 1, s));
-        BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)(roff + 1), (int)(1 + N), 1, s));
-        if ((rc = round_consts_launch(ctx, N, table, roff, rblk, rflag, s))) return rc;
-    }
-    unsigned hog = 0;  // a serial wave of four MiMC chains beside other calls' heavy stages: fenced onto CUs of its own, as k_prepare_bids
-    if ((rc = serial_lds_bytes(ctx, (const void*)k_round_bids, &hog))) return rc;
-    ScopedEvent ev(ctx, TAG_WITNESS, s);
-    hipLaunchKernelGGL(k_round_bids, dim3((B + 63) / 64), dim3(64), hog, s, B, N, bids, (const sc*)rblk, (const int32_t*)rflag, ctx->mimc_c, rb);
-    BBP_HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_round_expand, dim3((unsigned)((n + 255) / 256)), dim3(256), lds_token(ctx), s, (u32)n, N, bids, table, (const u32*)rb, prove_in,
-                       tails, toggles, status);
-    BBP_HIP_TRY(ctx, hipGetLastError());
     return BBP_OK;
+}
+// All three: bids first.. of a call; `reduce`: the table is reduced first.  bids / prove_in / tails / toggles / status point at bid `first`.
+static int32_t round_prepare_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u8* scratch, const RoundScratch& rs, bool reduce, u32 first, u32 B,
+                                     const u8* bids, u32* prove_in, u32* tails, u32* toggles, int32_t* status, hipStream_t s) {
+    int32_t rc;
+    if ((rc = round_lanes_ok(ctx, N, B))) return rc;
+    u32* rb = (u32*)(scratch + rs.rb) + (size_t)RB_WORDS * first;
+    if (reduce && (rc = round_reduce_enqueue(ctx, N, table, scratch, rs, s))) return rc;
+    ScopedEvent ev(ctx, TAG_WITNESS, s);
+    if ((rc = round_bids_enqueue(ctx, N, scratch, rs, B, bids, rb, nullptr, s))) return rc;
+    return round_expand_enqueue(ctx, N, table, B, bids, rb, prove_in, tails, toggles, status, nullptr, s);
 }
 
 // record || score || z_img rows from the records and the per-bid results of the pass, on s
@@ -1148,6 +1167,233 @@ extern "C" int32_t bbp_prove_round_dev(bbp_ctx* ctx, uint32_t N, const void* rou
         BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
         return round_dev_enqueue(ctx, N, (const u8*)round_dev, B, (const u8*)bids_dev, nullptr, nullptr, (u32*)toggles_out_dev, (int32_t*)status_dev,
                                  (const u8*)entropy_dev, (u8*)rows_out_dev, pick_stream(ctx, stream));
+    });
+}
+
+// ---- selecting a round's bids (include/bbp.h; rules and kernels: round_select.h) ---------------------------------------------------
+// The selection launches on s (round_select.h): the state zeroed, one launch per key byte, the counts, the ordered compaction
+static int32_t select_kernels_enqueue(bbp_ctx* ctx, u32 B, const u32* recs, const RsFloor& floor, u32 K, u32 cap, u32* sel, u32* counts, u8* state,
+                                      hipStream_t s) {
+    const RsGeom g = rs_geom(B);
+    RsState* st = (RsState*)state;
+    ScopedEvent ev(ctx, TAG_SELECT, s);
+    BBP_HIP_TRY(ctx, hipMemsetAsync(st, 0, sizeof(RsState), s));
+    for (u32 pass = 0; pass < 32; pass++) hipLaunchKernelGGL(k_round_select_pass, dim3(g.G), dim3(RS_SEL_T), 0, s, B, g.span, recs, floor, K, pass, st);
+    hipLaunchKernelGGL(k_round_select_count, dim3(g.G), dim3(RS_SEL_T), 0, s, B, g.span, recs, floor, counts, st);
+    hipLaunchKernelGGL(k_round_select_write, dim3(g.G), dim3(RS_SEL_T), 0, s, B, g.span, recs, floor, cap, sel, (const RsState*)st);
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// Scoring and selection on s: the table reduced into the scratch at `base` (its RoundScratch header), one record per bid, then sel and
+// counts.  Device pointers throughout; cap <= B entries of sel.
+static int32_t select_enqueue(bbp_ctx* ctx, u32 N, const u8* table, u32 B, const u8* bids, const RsFloor& floor, u32 K, u32 cap, u32* sel, u32* counts,
+                              int32_t* status, u32* scores, u8* base, const SelectScratch& ss, hipStream_t s) {
+    int32_t rc;
+    if ((rc = round_reduce_enqueue(ctx, N, table, base, ss.rs, s))) return rc;
+    u32* recs = (u32*)(base + ss.recs);
+    {  // a throughput launch: no LDS reservation, the waves of many workgroups share each SIMD
+        ScopedEvent ev(ctx, TAG_WITNESS, s);
+        hipLaunchKernelGGL(k_round_scores, dim3((B + RS_SCORE_T - 1) / RS_SCORE_T), dim3(RS_SCORE_T), 0, s, B, N, bids, (const sc*)(base + ss.rs.rblk),
+                           (const int32_t*)(base + ss.rs.rflag), ctx->mimc_c, recs, status, scores);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+    }
+    return select_kernels_enqueue(ctx, B, recs, floor, K, cap, sel, counts, base + ss.state, s);
+}
+
+extern "C" int32_t bbp_select_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, const uint8_t floor32[32],
+                                        uint32_t K, uint32_t cap, void* sel_dev, void* counts_dev, void* status_dev, void* scores_dev, void* prove_in_dev,
+                                        void* tails_dev, void* toggles_dev, void* stream) {
+    if (!ctx || !round_dev || !bids_dev || !floor32 || !counts_dev || !status_dev || (cap && !sel_dev)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_select_round_dev");
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc = check_n(ctx, N);
+        if (rc) return rc;
+        if (B > BBP_SELECT_MAX_BIDS) return ctx->err = "bbp_select_round_dev: more than BBP_SELECT_MAX_BIDS bids", BBP_ERR_BAD_ARG;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        hipStream_t s = pick_stream(ctx, stream);
+        if (B == 0) {  // nothing qualifies: the counts say so, in stream order
+            BBP_HIP_TRY(ctx, hipMemsetAsync(counts_dev, 0, 8, s));
+            return BBP_OK;
+        }
+        if (cap > B) cap = B;  // no more than B bids can be selected
+        const bool expand = cap && (prove_in_dev || tails_dev || toggles_dev);
+        if (expand && (rc = round_lanes_ok(ctx, N, cap))) return rc;
+        const SelectScratch ss = select_scratch(B, expand ? cap : 0, N);
+        // scratch in rotation, under the rule of round_dev_enqueue
+        bbp_ctx::CheckBuf& cb = ctx->rnd[ctx->rnd_next++ % (u32)bbp_ctx::CHECK_RING];
+        if ((rc = dev_reserve(ctx, cb.buf, ss.end))) return rc;
+        if (!cb.ev) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&cb.ev, hipEventDisableTiming));
+        if (cb.ev_valid) BBP_HIP_TRY(ctx, hipStreamWaitEvent(s, cb.ev, 0));
+        u8* base = (u8*)cb.buf.p;
+        const u32* counts = (const u32*)counts_dev;
+        if ((rc = select_enqueue(ctx, N, (const u8*)round_dev, B, (const u8*)bids_dev, rs_floor_load(floor32), K, cap, (u32*)sel_dev, (u32*)counts_dev,
+                                 (int32_t*)status_dev, (u32*)scores_dev, base, ss, s)))
+            return rc;
+        if (expand) {  // the selected bids, gathered, through the existing pass: launches sized by cap, lanes at or beyond counts[0] leave at once
+            u8* gb = base + ss.gbids;
+            u32* rb = (u32*)(base + ss.rs.rb);
+            ScopedEvent ev(ctx, TAG_WITNESS, s);
+            hipLaunchKernelGGL(k_round_gather, dim3((unsigned)(((u64)cap * BBP_ROUND_BID_BYTES + 255) / 256)), dim3(256), 0, s, cap, (const u32*)sel_dev, counts,
+                               (const u8*)bids_dev, gb);
+            BBP_HIP_TRY(ctx, hipGetLastError());
+            if ((rc = round_bids_enqueue(ctx, N, base, ss.rs, cap, gb, rb, counts, s)) ||
+                (rc = round_expand_enqueue(ctx, N, (const u8*)round_dev, cap, gb, rb, (u32*)prove_in_dev, (u32*)tails_dev, (u32*)toggles_dev, nullptr, counts, s)))
+                return rc;
+            // the rows are announced as bbp_prepare_round_dev's are: the next prove call's opening stage waits for them by itself
+            BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_prep, s));
+            ctx->ev_prep_valid = true;
+        }
+        if (wipe_on(ctx)) {  // secret wiping: the ring entry (score records, gathered bids, their results), ahead of its event
+            WipeList wl;
+            wipe_take(wl, cb.buf);
+            if ((rc = wipe_enqueue(ctx, wl, s))) return rc;
+        }
+        BBP_HIP_TRY(ctx, hipEventRecord(cb.ev, s));
+        cb.ev_valid = true;
+        return BBP_OK;
+    });
+}
+
+// Phase A of bbp_prove_round_select on ONE device's context: table and bids up, scoring and selection, counts / sel / statuses (/ scores)
+// down -- the one synchronisation of the call, waited for with the context lock released.  cap <= B: entries of sel_out.  recs_host
+// (the debug hook): B records that stand where the scoring's would, nothing is scored then.
+static int32_t select_phase_a(bbp_ctx* ctx, u32 N, const u8* round, u32 B, const u8* bids, const u32* recs_host, const uint8_t* floor32, u32 K, u32 cap,
+                              u32* sel_out, u32 counts_out[2], int32_t* status, u8* scores_out) {
+    std::lock_guard<std::mutex> phase(ctx->sel_mu);
+    const SelectStaging L(B, cap, N, scores_out != nullptr);
+    const size_t up = recs_host ? 0 : L.up_bytes;
+    int32_t rc = api_guard(ctx, [&]() -> int32_t {
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        auto body = [&]() -> int32_t {
+            int32_t rc;
+            if ((rc = dev_reserve(ctx, ctx->sel_dev, L.bytes)) || (rc = pinned_reserve(ctx, ctx->sel_h, ctx->sel_h_cap, L.h_bytes))) return rc;
+            if (!ctx->ev_sel) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_sel, hipEventDisableTiming));
+            hipStream_t s = ctx->stream;
+            u8 *d = (u8*)ctx->sel_dev.p, *h = (u8*)ctx->sel_h;
+            u32* recs = (u32*)(d + L.scratch + L.ss.recs);
+            if (recs_host) {
+                BBP_HIP_TRY(ctx, hipMemcpyAsync(recs, recs_host, 4 * (size_t)RS_WORDS * B, hipMemcpyHostToDevice, s));
+                if ((rc = select_kernels_enqueue(ctx, B, recs, rs_floor_load(floor32), K, cap, (u32*)(d + L.sel), (u32*)(d + L.counts),
+                                                 d + L.scratch + L.ss.state, s)))
+                    return rc;
+            } else {
+                memcpy(h + L.bids, bids, ROUND_BID_BYTES * (size_t)B);
+                memcpy(h + L.tab, round, round_table_bytes(N));
+                BBP_HIP_TRY(ctx, hipMemcpyAsync(d, h, L.up_bytes, hipMemcpyHostToDevice, s));
+                if ((rc = select_enqueue(ctx, N, d + L.tab, B, d + L.bids, rs_floor_load(floor32), K, cap, (u32*)(d + L.sel), (u32*)(d + L.counts),
+                                         (int32_t*)(d + L.status), scores_out ? (u32*)(d + L.scores) : nullptr, d + L.scratch, L.ss, s)))
+                    return rc;
+            }
+            BBP_HIP_TRY(ctx, hipMemcpyAsync(h + up, d + L.counts, L.down_bytes, hipMemcpyDeviceToHost, s));
+            if (wipe_on(ctx)) {  // secret wiping: bids, records, selection, behind the copy that hands the results out
+                WipeList wl;
+                wipe_take(wl, ctx->sel_dev);
+                if ((rc = wipe_enqueue(ctx, wl, s))) return rc;
+            }
+            BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_sel, s));
+            return BBP_OK;
+        };
+        const int32_t rc = body();
+        if (rc && wipe_on(ctx)) {  // a half-enqueued phase: everything SECRET, behind a device synchronise; the message stays this failure's
+            const std::string why = ctx->err;
+            (void)wipe_all(ctx);
+            ctx->err = why;
+        }
+        return rc;
+    });
+    if (rc) return rc;
+    const hipError_t e = wait_event_polling(ctx->ev_sel);
+    if (e == hipSuccess) {
+        const u8* down = (const u8*)ctx->sel_h + up;  // the fetched region starts at L.counts on the device
+        memcpy(counts_out, down, 8);
+        const u32 n = counts_out[0] < cap ? counts_out[0] : cap;
+        if (n) memcpy(sel_out, down + (L.sel - L.counts), 4 * (size_t)n);
+        if (!recs_host) memcpy(status, down + (L.status - L.counts), 4 * (size_t)B);
+        if (scores_out) memcpy(scores_out, down + (L.scores - L.counts), 32 * (size_t)B);
+    }
+    if (wipe_on(ctx)) secure_zero(ctx->sel_h, std::min(ctx->sel_h_cap, L.h_bytes));
+    if (e != hipSuccess) {
+        api_guard(ctx, [&]() -> int32_t { return ctx->err = std::string("collecting the selection: ") + hipGetErrorString(e), BBP_ERR_DEVICE; });
+        return BBP_ERR_DEVICE;
+    }
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_prove_round_select(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* bids, const uint8_t floor32[32],
+                                          uint32_t K, uint32_t cap, const uint8_t* entropy, uint8_t* rows_out, uint32_t* sel_out, uint32_t* n_sel,
+                                          uint32_t* n_qualified, uint64_t* toggles_out, uint8_t* scores_out, int32_t* status) {
+    if (!ctx || !round || !bids || !floor32 || !n_sel || !status || (cap && (!rows_out || !sel_out))) return BBP_ERR_BAD_ARG;
+    bool done;
+    const int32_t screened = round_select_screen(N, B, &done);
+    if (screened || done) {
+        *n_sel = 0;
+        if (n_qualified) *n_qualified = 0;
+        return api_guard(ctx, [&]() -> int32_t {
+            if (int32_t rc = check_n(ctx, N)) return rc;  // (names the list length)
+            if (screened) ctx->err = "bbp_prove_round_select: more than BBP_SELECT_MAX_BIDS bids";
+            return screened;
+        });
+    }
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;  // phase A: one member scores, as bbp_witness_batch
+        auto fail = [&](int32_t rc, const std::string& why) {
+            api_guard(ctx, [&]() -> int32_t { return ctx->err = why, rc; });
+            return rc;
+        };
+        const u32 cap_sel = cap < B ? cap : B;
+        std::vector<u32> sel(cap_sel);
+        u32 counts[2] = {0, 0};
+        int32_t rc = select_phase_a(dev, N, round, B, bids, nullptr, floor32, K, cap_sel, sel.data(), counts, status, scores_out);
+        if (rc) return dev == ctx ? rc : fail(rc, bbp_last_error(dev));
+        *n_sel = counts[0];
+        if (n_qualified) *n_qualified = counts[1];
+        if (counts[0] > cap)
+            return fail(BBP_ERR_BAD_ARG, "bbp_prove_round_select: " + std::to_string(counts[0]) + " bids selected, room for " + std::to_string(cap) +
+                                             " (cap): nothing proved");
+        const u32 n = counts[0];
+        if (n == 0) return BBP_OK;
+        // phase B: the selected bids from the CALLER's memory through bbp_prove_round's own path; entropy row j goes to sel[j]
+        std::vector<uint8_t> picked(ROUND_BID_BYTES * (size_t)n);
+        for (u32 j = 0; j < n; j++) memcpy(&picked[ROUND_BID_BYTES * (size_t)j], bids + ROUND_BID_BYTES * (size_t)sel[j], ROUND_BID_BYTES);
+        std::vector<int32_t> st(n, BBP_ERR_INTERNAL);
+        rc = bbp_prove_round(ctx, N, round, n, picked.data(), entropy, rows_out, toggles_out, st.data());
+        secure_zero(picked.data(), picked.size());
+        if (rc) return rc;
+        memcpy(sel_out, sel.data(), 4 * (size_t)n);
+        for (u32 j = 0; j < n; j++)
+            if (st[j] != BBP_OK)
+                return fail(BBP_ERR_INTERNAL, "bbp_prove_round_select: scoring accepted bid " + std::to_string(sel[j]) + ", proving refused it (status " +
+                                                  std::to_string(st[j]) + ")");
+        return BBP_OK;
+    });
+}
+
+// Test hook: the shipped selection kernel on caller-made scores and statuses.  Synchronises.
+extern "C" int32_t bbp_debug_round_select(bbp_ctx* ctx, uint32_t B, const uint8_t* scores, const int32_t* statuses, const uint8_t floor32[32], uint32_t K,
+                                          uint32_t cap, uint32_t* sel_out, uint32_t* n_sel, uint32_t* n_qualified) {
+    if (!ctx || !scores || !statuses || !floor32 || !n_sel || !n_qualified || (cap && !sel_out)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_round_select");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        auto refuse = [&](const char* why) {
+            api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
+            return (int32_t)BBP_ERR_BAD_ARG;
+        };
+        if (B == 0 || B > BBP_SELECT_MAX_BIDS) return refuse("bbp_debug_round_select: B is 0 or above BBP_SELECT_MAX_BIDS");
+        std::vector<u32> recs((size_t)RS_WORDS * B, 0);
+        for (u32 i = 0; i < B; i++) {
+            u32* r = &recs[(size_t)RS_WORDS * i];
+            for (int w = 0; w < 8; w++) r[RS_Q + w] = rb_le32(scores + 32 * (size_t)i + 4 * w);
+            r[RS_STATUS] = (u32)statuses[i];
+            if (!sc_is_canonical(r + RS_Q)) return refuse("bbp_debug_round_select: a score is not below l");
+            if (statuses[i] != BBP_OK && statuses[i] != BBP_ERR_FORMAT && statuses[i] != BBP_ERR_BAD_ARG)
+                return refuse("bbp_debug_round_select: a status is none of BBP_OK, BBP_ERR_FORMAT, BBP_ERR_BAD_ARG");
+        }
+        u32 counts[2] = {0, 0};
+        const u32 cap_sel = cap < B ? cap : B;
+        const int32_t rc = select_phase_a(ctx, 1, nullptr, B, nullptr, recs.data(), floor32, K, cap_sel, sel_out, counts, nullptr, nullptr);
+        *n_sel = counts[0], *n_qualified = counts[1];
+        return rc;
     });
 }
 

@@ -199,6 +199,14 @@ struct bbp_ctx {
     CheckBuf rnd[CHECK_RING];
     uint32_t rnd_next = 0;
     hipEvent_t ev_round = nullptr;
+    // Phase A of bbp_prove_round_select and bbp_debug_round_select (capi_prove.hip; the layout is prove_io.h's SelectStaging): bids,
+    // table, score records, selection on the device and a pinned mirror of what travels.  Both grow on demand (bbp_reserve does not
+    // size them); sel_mu serialises the calls that use them, and is taken BEFORE the context lock.
+    std::mutex sel_mu;
+    bbp::DevBuf sel_dev;
+    void* sel_h = nullptr;
+    size_t sel_h_cap = 0;
+    hipEvent_t ev_sel = nullptr;
     // resident tables
     bbp::ge* gens = nullptr;           // [TAB_BASES] extended points: B_blinding, G[2048], H[2048], B, then the PAD_BASES range sums and the MRG_BASES merged bases
     bbp::niels_row* ptable = nullptr;      // [TAB_BASES * MSM_POS] affine cached 2^b * P_i, 128-byte limb rows (275 MB)
@@ -309,7 +317,8 @@ inline int32_t dev_reserve(bbp_ctx* ctx, DevBuf& b, size_t bytes) {
 }
 
 enum { TAG_MSM = 1, TAG_ENCODE = 2, TAG_WITNESS = 3, TAG_RNG = 4, TAG_POLY = 5, TAG_IPA_SCALARS = 6, TAG_COMMIT = 7,
-       TAG_TRANSCRIPT = 8, TAG_VERIFY_SCALARS = 9, TAG_VARBASE = 10, TAG_MSM_SORT = 11, TAG_MSM_FOLD = 12, TAG_WIPE = 13 /* k_wipe_spans */ };
+       TAG_TRANSCRIPT = 8, TAG_VERIFY_SCALARS = 9, TAG_VARBASE = 10, TAG_MSM_SORT = 11, TAG_MSM_FOLD = 12, TAG_WIPE = 13 /* k_wipe_spans */,
+       TAG_SELECT = 14 /* k_round_select_*: the selection launches */ };
 
 struct ScopedEvent {  // records start now, stop at scope exit, when profiling is on
     bbp_ctx* ctx;

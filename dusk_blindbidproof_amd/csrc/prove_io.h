@@ -50,6 +50,44 @@ inline RoundScratch round_scratch(u32 B, u32 N) {
     return s;
 }
 
+// Scratch of one selection pass (round_select.h), byte offsets (256-aligned): a RoundScratch for the `cap` bids that are expanded (its
+// header serves the scoring too), the selection's state, the RS_WORDS words per bid of all B bids, the gathered bids
+constexpr u32 RS_WORDS = 10;
+constexpr size_t RS_STATE_BYTES = 4096;
+struct SelectScratch {
+    RoundScratch rs;
+    size_t state, recs, gbids, end;
+};
+inline SelectScratch select_scratch(u32 B, u32 cap, u32 N) {
+    SelectScratch s;
+    s.rs = round_scratch(cap, N);
+    s.state = s.rs.end;
+    s.recs = s.state + RS_STATE_BYTES;
+    s.gbids = s.recs + align256(4 * (size_t)RS_WORDS * B);
+    s.end = s.gbids + align256(ROUND_BID_BYTES * cap);
+    return s;
+}
+// Phase A of bbp_prove_round_select (context.h sel_dev and its pinned mirror sel_h): what is uploaded (bids, table), what is fetched
+// (counts, sel, statuses, scores when asked for), the pass's scratch.  cap: entries of sel, at most B.  The mirror holds the uploaded
+// region and then the fetched one.
+struct SelectStaging {
+    size_t bids, tab, up_bytes, counts, sel, status, scores, down_bytes, scratch, bytes, h_bytes;
+    SelectScratch ss;
+    SelectStaging(u32 B, u32 cap, u32 N, bool want_scores) : ss(select_scratch(B, 0, N)) {
+        bids = 0;
+        tab = align256(ROUND_BID_BYTES * B);
+        up_bytes = tab + round_table_bytes(N);
+        counts = align256(up_bytes);
+        sel = counts + 256;
+        status = sel + align256(4 * (size_t)cap);
+        scores = status + align256(4 * (size_t)B);
+        down_bytes = scores + (want_scores ? 32 * (size_t)B : 0) - counts;
+        scratch = align256(counts + down_bytes);
+        bytes = scratch + ss.end;
+        h_bytes = up_bytes + down_bytes;
+    }
+};
+
 // ---- the device forms' scratch rings (context.h chk, rnd) -----------------------------------------------------------------------------
 // one entry of bbp_prove_batch_checked_dev: the check's scratch (verify rows, verifier statuses) as a staging slot's `chk`, then the
 // witness masks

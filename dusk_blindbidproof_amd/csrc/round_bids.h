@@ -89,10 +89,12 @@ BBP_HD u8 round_row_byte(u32 N, u32 o, const u8* record, const u32* rb) {
 #ifdef __HIPCC__
 // One lane per bid; the four chains are 1440 dependent Montgomery products, so the wave lives for milliseconds and is fenced onto
 // CUs of its own by its launch (serial_lds_bytes), like k_prepare_bids.  Writes the bid's RB_WORDS words, nothing else.
+// n_dev (NULL: all B): a device-side count -- only the first min(B, *n_dev) bids exist (bbp_select_round_dev sizes the launch by its cap).
 __global__ void __launch_bounds__(64) k_round_bids(u32 B, u32 N, const u8* __restrict__ bids, const sc* __restrict__ rblk,
-                                                   const int32_t* __restrict__ rflag, const sc* __restrict__ mimc, u32* __restrict__ rb) {
+                                                   const int32_t* __restrict__ rflag, const sc* __restrict__ mimc, u32* __restrict__ rb,
+                                                   const u32* __restrict__ n_dev) {
     const u32 p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= B) return;
+    if (p >= B || (n_dev && p >= n_dev[0])) return;
     u32 o[RB_WORDS];
     round_bid_eval(N, bids + BBP_ROUND_BID_BYTES * (size_t)p, rblk, rflag[0], mimc, o);
     u32* dst = rb + (size_t)RB_WORDS * p;
@@ -101,16 +103,17 @@ __global__ void __launch_bounds__(64) k_round_bids(u32 B, u32 N, const u8* __res
 }
 
 // One lane per output word, consecutive lanes on consecutive words of a bid: per bid the prove-input row, then (each unless NULL)
-// score || z_img into tails, the toggle, the status.  n = B * (round_in_words(N) + RB_EXTRA_WORDS) lanes.
+// score || z_img into tails, the toggle, the status.  n = B * (round_in_words(N) + RB_EXTRA_WORDS) lanes.  n_dev: as k_round_bids'.
 __global__ void __launch_bounds__(256) k_round_expand(u32 n, u32 N, const u8* __restrict__ bids, const u8* __restrict__ table,
                                                       const u32* __restrict__ rb, u32* __restrict__ prove_in, u32* __restrict__ tails,
-                                                      u32* __restrict__ toggles, int32_t* __restrict__ status) {
+                                                      u32* __restrict__ toggles, int32_t* __restrict__ status, const u32* __restrict__ n_dev) {
     const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n) return;
     const u32 pw = round_in_words(N), per = pw + RB_EXTRA_WORDS, p = g / per, w = g - p * per;
+    if (n_dev && p >= n_dev[0]) return;
     const u32* r = rb + (size_t)RB_WORDS * p;
     if (w < pw) {
-        prove_in[(size_t)pw * p + w] = round_expand_word(N, w, bids + BBP_ROUND_BID_BYTES * (size_t)p, table, r);
+        if (prove_in) prove_in[(size_t)pw * p + w] = round_expand_word(N, w, bids + BBP_ROUND_BID_BYTES * (size_t)p, table, r);
     } else if (w < pw + RB_TAIL_WORDS) {
         if (tails) tails[(size_t)RB_TAIL_WORDS * p + (w - pw)] = r[RB_Q + (w - pw)];
     } else if (w < pw + RB_TAIL_WORDS + 2) {

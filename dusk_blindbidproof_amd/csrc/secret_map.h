@@ -139,7 +139,8 @@ inline bool batch_spans(u32 B, const BatchDims& d, int cls, BatchSpans& out) {
     X("io.in", c->io[i].in, S + bbp_ctx::IO_VSLOTS, i < S)   /* prove staging slots: rows, entropy and row keys, records and a round */ \
     X("io.ent", c->io[i].ent, S + bbp_ctx::IO_VSLOTS, i < S) /* call's toggles; slots S.. are the verify calls' (public) */             \
     X("io.out", c->io[i].out, S + bbp_ctx::IO_VSLOTS, i < S)                                                                            \
-    X("rnd", c->rnd[i].buf, bbp_ctx::CHECK_RING, true)       /* round rings: bids' results, expanded rows */                            \
+    X("rnd", c->rnd[i].buf, bbp_ctx::CHECK_RING, true)       /* round rings: bids' results, expanded rows; score records, gathered bids */ \
+    X("sel", c->sel_dev, 1, true)                            /* bbp_prove_round_select phase A: every bid of the call, its score record */ \
     /* PUBLIC: checked proving's verify rows (record || q || z_img || seed || list, what any verifier is handed), verifier statuses and  \
        witness masks -- a mask is zero for a satisfied row and names the failed relation of a refused one, which the caller is told as   \
        status and message anyway */                                                                                                     \
@@ -152,7 +153,8 @@ inline bool batch_spans(u32 B, const BatchDims& d, int cls, BatchSpans& out) {
 // X(name, pointer, capacity, count, secret): the pinned mirrors of the staging slots
 #define BBP_CTX_PINNED_BUFFERS(X, S)                                                                                                    \
     X("io.h_in", c->io[i].h_in, c->io[i].h_in_cap, S + bbp_ctx::IO_VSLOTS, i < S)                                                        \
-    X("io.h_out", c->io[i].h_out, c->io[i].h_cap, S + bbp_ctx::IO_VSLOTS, i < S)
+    X("io.h_out", c->io[i].h_out, c->io[i].h_cap, S + bbp_ctx::IO_VSLOTS, i < S)                                                        \
+    X("sel.h", c->sel_h, c->sel_h_cap, 1, true)              /* ... and its mirror: the bids going up, scores and selection coming down */
 // Not DevBufs, all PUBLIC, walked by the scan from wipe.hip: the resident tables gens, ptable, btab, comb, mimc_c (functions of public
 // constants) and the verifier lanes' pinned ns_ring.  Not walked: the compiled circuits' lists and vctab (uploaded from host tables that
 // are functions of N), and the counter words health, chk_counts, agg_count and the pinned h_flag.

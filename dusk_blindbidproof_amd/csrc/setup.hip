@@ -380,7 +380,9 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
         if (cb.buf.p) (void)hipFree(cb.buf.p);
         if (cb.ev) (void)hipEventDestroy(cb.ev);
     }
-    for (hipEvent_t e : {ctx->ev_chk_fork, ctx->ev_chk_join, ctx->ev_round})
+    if (ctx->sel_dev.p) (void)hipFree(ctx->sel_dev.p);
+    if (ctx->sel_h) (void)hipHostFree(ctx->sel_h);
+    for (hipEvent_t e : {ctx->ev_chk_fork, ctx->ev_chk_join, ctx->ev_round, ctx->ev_sel})
         if (e) (void)hipEventDestroy(e);
     for (auto& e : ctx->ev_vacc)
         if (e) (void)hipEventDestroy(e);

@@ -79,10 +79,11 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *                           gets [i*B/n ...), the split of SURVEY.md 8e), one host thread per member, outputs and per-item
  *                           statuses in request order; the call returns the first member's non-zero status, if any
  *   bbp_witness_batch, bbp_get_generator, bbp_get_mimc_constant, bbp_ubench   served by member 0
+ *   bbp_prove_round_select  scoring and selection served by member 0, the selected bids proved as bbp_prove_round on the pool
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
- * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_set_profiling /
+ * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_set_profiling /
  * bbp_last_timings; the stream getters return NULL. */
 int32_t bbp_init_all(bbp_ctx** out);
 int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp_ctx** out);
@@ -306,6 +307,65 @@ int32_t bbp_prove_round(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t
                         uint8_t* rows_out, uint64_t* toggles_out, int32_t* status);
 int32_t bbp_prove_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, const void* entropy_dev,
                             void* rows_out_dev, void* toggles_out_dev, void* status_dev, void* stream);
+
+/* Selecting a round's bids: a round ends with "the proof with the highest score wins", so a holder of many bids wants proofs for the few
+ * that can still win -- the K highest scores, none below the best score already seen.  These calls score every bid on the device (three
+ * MiMC chains and one inversion per bid; 40 bytes written per bid instead of an expanded row), select, and prove only the selected bids.
+ * For round (seed, pub_list), bids 0..B-1 (B <= BBP_SELECT_MAX_BIDS), floor32 and K:
+ *   floor32      32 bytes, an unsigned 256-bit little-endian integer; any value
+ *   status[i]    exactly what bbp_prove_round reports for bid i (BBP_ERR_FORMAT, BBP_ERR_BAD_ARG, BBP_OK; the same order of checks)
+ *   score[i]     q = d * y^-1 mod l as the canonical integer in [0, l) for an accepted bid (score_gadget, src/gadgets.rs:70-86), zero for a
+ *                refused one; scores are ordered as integers, the only order the 32-byte score field of a record admits
+ *   Q            { i : status[i] == BBP_OK and score[i] >= floor }: floor 0 admits every accepted bid, a floor >= l none; "strictly
+ *                better than the best seen" is best + 1
+ *   Sel          Q when K == 0 or |Q| <= K, else the K members of Q that come first under (score descending, index ascending) -- equal
+ *                scores happen: the same (d, k) twice
+ *   sel          Sel in ASCENDING INDEX order; n_sel = |Sel|, n_qualified = |Q|
+ * Proving is bbp_prove_round over bids[sel[0]], bids[sel[1]], ...: entropy row j goes to sel[j] (the row follows the rank in sel, not
+ * the bid's index -- a caller cannot know the indices in advance), and under entropy source DEVICE or HEDGED the row index of sel[j] is j.
+ *
+ * bbp_prove_round_select, the host form, runs in two phases.  A: table and bids are uploaded, scored and selected; counts, sel, statuses
+ * and (scores_out != NULL) scores come back -- the call's one synchronisation.  Phase A calls of one context are serialised among
+ * themselves; their device scratch and pinned mirror grow on demand: bbp_reserve does NOT size them (it sizes everything phase B uses).
+ * B: the selected bids are gathered from the caller's `bids` on the host (no secret travels back from the device) and proved by
+ * bbp_prove_round's own path, so entropy source, BBP_HOST_CHUNK_PROVE, checked proving, hedged row keys, secret wiping and bbp_reserve
+ * hold as they do there and rows_out is byte-equal to bbp_prove_round's on the gathered bids.  A bid that scoring accepted and proving
+ * refuses is BBP_ERR_INTERNAL.
+ *   entropy      cap * bbp_entropy_size(N), row j for sel[j]; or NULL (bbp_set_entropy_source)
+ *   rows_out     cap * bbp_round_row_size(N); sel_out cap entries; toggles_out cap entries or NULL: rows j < n_sel are written
+ *   scores_out   B * 32 or NULL; status B entries; n_qualified may be NULL
+ * Screening, before anything runs, the first failing check decides: a NULL required pointer BBP_ERR_BAD_ARG (rows_out and sel_out may
+ * be NULL only when cap == 0); N == 0 BBP_ERR_BAD_ARG, N > BBP_MAX_ITEMS BBP_ERR_GENS_LEN; B > BBP_SELECT_MAX_BIDS BBP_ERR_BAD_ARG;
+ * B == 0 BBP_OK with n_sel = 0.  After phase A: n_sel > cap is BBP_ERR_BAD_ARG (bbp_last_error names both numbers) -- status, scores_out,
+ * n_sel and n_qualified are written, sel_out and rows_out are untouched, nothing is proved; with K > 0 and cap >= K it cannot happen.
+ * n_sel == 0 is BBP_OK and no prove call is made.  Scoring alone is the call with the all-ones floor and cap = 0.
+ * A pool takes it: phase A is served by member 0 (as bbp_witness_batch), phase B is bbp_prove_round on the pool.
+ * Secret wiping: the phase-A buffers are SECRET and erased before the call returns.
+ *
+ * bbp_select_round_dev, the device form: stream-ordered, no synchronisation, no host screening of device data; a pool refuses it.
+ * Scoring, selection, then -- when cap > 0 and any of prove_in_dev, tails_dev, toggles_dev is given -- the selected bids gathered and
+ * taken through bbp_prepare_round_dev's own kernels, sized by cap (lanes at or beyond the device-side count leave at once).
+ *   sel_dev      cap x u32: the first min(n_sel, cap) entries of sel, in index order
+ *   counts_dev   2 x u32: n_sel, n_qualified -- the true values also when n_sel > cap
+ *   status_dev   B x int32; scores_dev B x 32 or NULL
+ *   prove_in_dev, tails_dev (64 bytes: score || z_img), toggles_dev (u64): each cap rows or NULL; row j < min(n_sel, cap) is byte for
+ *                byte what bbp_prepare_round_dev writes for bid sel[j], rows at or beyond that are not written
+ * The rows are announced as bbp_prepare_round_dev's are (the same event): the next prove call on the context waits for them by itself.
+ * A caller reads counts, calls bbp_prove_batch_dev(min(n_sel, cap), ...) and joins records and tails itself.  NULL is BBP_ERR_BAD_ARG for
+ * round_dev, bids_dev, floor32, counts_dev, status_dev, and for sel_dev when cap > 0; then N, then B as above; B == 0 writes zero counts.
+ *
+ * bbp_debug_round_select, test hook: the shipped selection kernel on caller-made host arrays -- scores B x 32 (each below l), statuses B
+ * (each one of the three) -- with a floor, K and cap; sel_out receives min(n_sel, cap) entries.  Synchronises.  BBP_ERR_BAD_ARG, nothing
+ * launched: a NULL pointer, B == 0 or above BBP_SELECT_MAX_BIDS, a score >= l, a status outside the three.  A pool refuses it. */
+#define BBP_SELECT_MAX_BIDS (1u << 20)
+int32_t bbp_select_round_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* bids_dev, const uint8_t floor32[32], uint32_t K,
+                             uint32_t cap, void* sel_dev, void* counts_dev, void* status_dev, void* scores_dev, void* prove_in_dev, void* tails_dev,
+                             void* toggles_dev, void* stream);
+int32_t bbp_prove_round_select(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* bids, const uint8_t floor32[32], uint32_t K,
+                               uint32_t cap, const uint8_t* entropy, uint8_t* rows_out, uint32_t* sel_out, uint32_t* n_sel, uint32_t* n_qualified,
+                               uint64_t* toggles_out, uint8_t* scores_out, int32_t* status);
+int32_t bbp_debug_round_select(bbp_ctx* ctx, uint32_t B, const uint8_t* scores, const int32_t* statuses, const uint8_t floor32[32], uint32_t K,
+                               uint32_t cap, uint32_t* sel_out, uint32_t* n_sel, uint32_t* n_qualified);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.
