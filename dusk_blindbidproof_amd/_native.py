@@ -85,6 +85,9 @@ SIGNATURES = {
     "bbp_select_round_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_prove_round_select": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_round_select": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "bbp_verify_round_best": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_round_best_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_round_best": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "bbp_set_prove_check": (_i32, [_vp, _i32]),
     "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -232,6 +235,11 @@ def pack_round_bids(bids):
 
 SELECT_MAX_BIDS = 1 << 20  # BBP_SELECT_MAX_BIDS
 RoundSelection = collections.namedtuple("RoundSelection", "rc rows sel n_sel n_qualified toggles scores status")
+
+
+ROW_SKIPPED = -1            # BBP_ROW_SKIPPED: bbp_verify_round_best did not have to verify this row
+BEST_TRANCHE_DEFAULT = 16   # BBP_BEST_TRANCHE_DEFAULT
+RoundBest = collections.namedtuple("RoundBest", "best n_best n_candidates n_examined status raw")
 
 
 def select_floor(floor):
@@ -548,6 +556,56 @@ class Context:
                                                ctypes.byref(n_sel), ctypes.byref(n_q)))
         return list(sel)[:min(n_sel.value, cap)], n_sel.value, n_q.value
 
+    def verify_round_best(self, N, table, rows, floor=0, K=1, tranche=0, cap=None, fill=0):
+        """bbp_verify_round_best: the K best valid proofs (K = 0: all valid ones) among the rows record || score || z_img of one round
+        (table = seed || pub_list), verifying in order of claimed score and stopping at the K-th proof that holds.  Returns a RoundBest:
+        best (row indices in rank order, at most cap), n_best, n_candidates, n_examined and the B statuses -- OK / VERIFY / FORMAT for an
+        examined row, ROW_SKIPPED for one the call did not have to verify.  cap: room in best (default: K, or every row when K = 0);
+        fill: the byte the output buffers start as."""
+        row = round_row_size(N)
+        if len(table) != 32 * (1 + N) or len(rows) % row:
+            raise ValueError("a round is a 32-byte seed and N 32-byte items; rows are round_row_size(N) bytes each")
+        B = len(rows) // row
+        cap, best, status, counts = self._best_buffers(B, K, cap, fill)
+        self._check(lib.bbp_verify_round_best(self._h, N, _buf(table), B, _buf(rows) if B else best, _buf(select_floor(floor)), K, tranche, cap, best,
+                                              ctypes.byref(counts[0]), ctypes.byref(counts[1]), ctypes.byref(counts[2]), status))
+        return self._best_result(B, cap, best, status, counts)
+
+    def verify_round_best_dev(self, N, table_ptr, B, rows_ptr, ent_ptr, status_ptr, floor=0, K=1, tranche=0, cap=None, stream=None, fill=0):
+        """bbp_verify_round_best_dev: rows (any alignment) and B x 32 entropy bytes resident on the device; synchronises `stream` once per
+        tranche.  Returns a RoundBest whose status is None: the B statuses are at status_ptr, complete on `stream`."""
+        cap, best, _, counts = self._best_buffers(B, K, cap, fill)
+        self._check(lib.bbp_verify_round_best_dev(self._h, N, table_ptr, B, rows_ptr, ent_ptr, _buf(select_floor(floor)), K, tranche, cap, best,
+                                                  ctypes.byref(counts[0]), ctypes.byref(counts[1]), ctypes.byref(counts[2]), status_ptr, _stream(stream)))
+        return self._best_result(B, cap, best, None, counts)
+
+    def debug_round_best(self, keys, verdicts, floor=0, K=1, tranche=0, cap=None, fill=0):
+        """bbp_debug_round_best (test hook): the shipped key, selection, mark and ranking kernels on made-up keys (B x 32 bytes) and
+        verdicts (what verification would say of each row); nothing is verified.  Returns a RoundBest."""
+        B = len(verdicts)
+        if len(keys) != 32 * B:
+            raise ValueError("keys are 32 bytes per verdict")
+        cap, best, status, counts = self._best_buffers(B, K, cap, fill)
+        self._check(lib.bbp_debug_round_best(self._h, B, _buf(keys) if B else best, (ctypes.c_int32 * max(1, B))(*verdicts), _buf(select_floor(floor)), K,
+                                             tranche, cap, best, ctypes.byref(counts[0]), ctypes.byref(counts[1]), ctypes.byref(counts[2]), status))
+        return self._best_result(B, cap, best, status, counts)
+
+    @staticmethod
+    def _best_buffers(B, K, cap, fill):
+        if cap is None:
+            cap = K if K else B
+        best = (_u32 * max(1, cap))()
+        status = (ctypes.c_int32 * max(1, B))()
+        ctypes.memset(best, fill, ctypes.sizeof(best))
+        ctypes.memset(status, fill, ctypes.sizeof(status))
+        return cap, best, status, (_u32(0), _u32(0), _u32(0))
+
+    @staticmethod
+    def _best_result(B, cap, best, status, counts):
+        """best: the first min(n_best, cap) entries; raw: all cap entries as the call left them (the rest is still the fill)"""
+        raw = list(best)[:cap]
+        return RoundBest(raw[:min(counts[0].value, cap)], counts[0].value, counts[1].value, counts[2].value, None if status is None else list(status)[:B], raw)
+
     def prepare_round_dev(self, N, table_ptr, B, bids_ptr, prove_in_ptr, status_ptr, tails_ptr=None, toggles_ptr=None, stream=None):
         """bbp_prepare_round_dev: the device pass alone -- rows for prove_batch_dev (which waits for them by itself), optionally
         score || z_img tails and u64 toggles, int32 statuses.  Stream-ordered, no synchronisation."""
@@ -755,7 +813,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best (member 0 selects, the pool verifies); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):
@@ -786,6 +844,11 @@ class Pool(Context):
         """bbp_prove_round_select on the pool: member 0 scores and selects, the selected bids are proved as prove_round proves them
         (block-split over the members, rows in the order of sel)."""
         return super().prove_round_select(N, table, bids, floor, K, cap, entropy, want_scores, check)
+
+    def verify_round_best(self, N, table, rows, floor=0, K=1, tranche=0, cap=None, fill=0):
+        """bbp_verify_round_best on the pool: member 0 keeps the keys, selects and marks; every tranche is verified as
+        verify_rounds_aggregated verifies it (block-split over the members)."""
+        return super().verify_round_best(N, table, rows, floor, K, tranche, cap, fill)
 
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""

@@ -12,6 +12,7 @@
 #include "chacha.h"
 #include "hedge.h"
 #include "round_bids.h"
+#include "round_best.h"
 #include "round_select.h"
 #include "secret_map.h"
 #include "submit.h"
@@ -1394,6 +1395,302 @@ extern "C" int32_t bbp_debug_round_select(bbp_ctx* ctx, uint32_t B, const uint8_
         const int32_t rc = select_phase_a(ctx, 1, nullptr, B, nullptr, recs.data(), floor32, K, cap_sel, sel_out, counts, nullptr, nullptr);
         *n_sel = counts[0], *n_qualified = counts[1];
         return rc;
+    });
+}
+
+// ---- best valid proofs of a round (include/bbp.h; rules and kernels: round_best.h) ----------------------------------------------------
+// The launch sequence of one call, on ONE device's context and one stream (context lock held by every step):
+//   open      the state reserved, ctr zeroed
+//   keys      k_best_keys: records, winners' records, initial statuses
+//   per tranche   select (the candidates' records, K = the tranche's size; 0: all) -> counts, sel;  [the rows verified];  mark
+//   finish    select (the winners' records, the call's K), k_best_pairs, then ctr, counts and pairs into the pinned mirror
+struct BestCall {
+    bbp_ctx* ctx;
+    u32 B;
+    BestLayout L;
+    hipStream_t s;
+    u8 *d = nullptr, *h = nullptr;
+    BestCall(bbp_ctx* c, u32 B_, bool host_keys, hipStream_t s_) : ctx(c), B(B_), L(B_, host_keys), s(s_) {}
+    u32* at(size_t off) const { return (u32*)(d + off); }
+};
+static const RsFloor BEST_NO_FLOOR = {};  // k_best_keys has applied the floor: a record is a member by its status alone
+
+static int32_t best_open(BestCall& c) {
+    bbp_ctx* ctx = c.ctx;
+    int32_t rc;
+    if ((rc = dev_reserve(ctx, ctx->best_dev, c.L.bytes)) || (rc = pinned_reserve(ctx, ctx->best_h, ctx->best_h_cap, c.L.h_bytes))) return rc;
+    if (!ctx->ev_best) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_best, hipEventDisableTiming));
+    c.d = (u8*)ctx->best_dev.p, c.h = (u8*)ctx->best_h;
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.L.ctr, 0, 16, c.s));
+    return BBP_OK;
+}
+
+// keys at base + i stride + off (device memory), status: B x int32 (device memory)
+static int32_t best_keys_enqueue(const BestCall& c, const u8* base, size_t stride, size_t off, const uint8_t* floor32, int32_t* status) {
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_best_keys, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, base, stride, off, rs_floor_load(floor32), c.at(c.L.recs),
+                       c.at(c.L.win), status);
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// the next `rows` candidates in the candidate order (0: every one that is left) -> counts, sel
+static int32_t best_select_enqueue(const BestCall& c, u32 rows) {
+    return select_kernels_enqueue(c.ctx, c.B, c.at(c.L.recs), BEST_NO_FLOOR, rows, rows ? rows : c.B, c.at(c.L.sel), c.at(c.L.counts), c.d + c.L.state, c.s);
+}
+
+// the tranche in sel (n rows) has the statuses at tstat (device memory)
+static int32_t best_mark_enqueue(const BestCall& c, u32 n, const int32_t* tstat, int32_t* status) {
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_best_mark, dim3((n + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, n, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts), tstat, status,
+                       c.at(c.L.recs), c.at(c.L.win), c.at(c.L.ctr));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// the K best winners (K == 0: all): selection, pairs, and everything the host reads into the mirror.  *room: pairs fetched at most.
+static int32_t best_finish_enqueue(const BestCall& c, u32 K, const int32_t* status_to_fetch, u32* room) {
+    bbp_ctx* ctx = c.ctx;
+    const u32 n = K && K < c.B ? K : c.B;
+    *room = n;
+    if (int32_t rc = select_kernels_enqueue(ctx, c.B, c.at(c.L.win), BEST_NO_FLOOR, K, n, c.at(c.L.sel), c.at(c.L.counts), c.d + c.L.state, c.s)) return rc;
+    {
+        ScopedEvent ev(ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_best_pairs, dim3((n + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, n, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
+                           (const u32*)c.at(c.L.win), c.at(c.L.pairs));
+        BBP_HIP_TRY(ctx, hipGetLastError());
+    }
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_pairs, c.d + c.L.pairs, 4 * (size_t)BEST_PAIR_WORDS * n, hipMemcpyDeviceToHost, c.s));
+    if (status_to_fetch) BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_status, status_to_fetch, 4 * (size_t)c.B, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+
+// after the finish has arrived: the host's tally against the device's counters, then the outputs
+static int32_t best_deliver(const BestCall& c, u32 room, u32 examined, u32 valid, u32 n_candidates, u32 cap, u32* best_out, u32* n_best, u32* n_cand_out,
+                            u32* n_examined, std::string* why) {
+    u32 ctr[2], counts[2];
+    memcpy(ctr, c.h + c.L.h_ctr, 8);
+    memcpy(counts, c.h + c.L.h_counts, 8);
+    if (ctr[0] != examined || ctr[1] != valid || counts[0] > room) {
+        *why = "best valid proofs: the device marked " + std::to_string(ctr[0]) + " rows examined and " + std::to_string(ctr[1]) + " valid, the call counted " +
+               std::to_string(examined) + " and " + std::to_string(valid);
+        return BBP_ERR_INTERNAL;
+    }
+    best_rank_pairs(counts[0], (const u32*)(c.h + c.L.h_pairs), cap, best_out);
+    *n_best = counts[0], *n_cand_out = n_candidates, *n_examined = examined;
+    return BBP_OK;
+}
+
+// The host forms on ONE device's context.  fill_keys(dst): the B x 32 key bytes into the pinned staging area; verdicts(n, sel, st): the
+// statuses of the tranche's rows sel[0..n) -- called with no lock of `dev` held (the host form verifies through the caller's handle).
+template <class Fill, class Verdicts>
+static int32_t best_run_host(bbp_ctx* dev, u32 B, Fill&& fill_keys, Verdicts&& verdicts, const uint8_t* floor32, u32 K, u32 tranche, u32 cap, u32* best_out,
+                             u32* n_best, u32* n_candidates, u32* n_examined, int32_t* status) {
+    std::lock_guard<std::mutex> call(dev->best_mu);
+    BestCall c(dev, B, true, dev->stream);
+    u32 T0 = 0, nc = 0, examined = 0, valid = 0, pending = 0, room = 0;
+    std::vector<int32_t> st;
+    bool more = true;
+    for (u32 t = 0;; t++) {
+        const bool finish = !more;
+        const u32 rows = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(T0, t, nc - examined);
+        const u32 room_sel = rows ? rows : B;
+        int32_t rc = api_guard(dev, [&]() -> int32_t {
+            int32_t rc;
+            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
+            if (t == 0 && (rc = best_open(c))) return rc;
+            int32_t* dstatus = (int32_t*)c.at(c.L.status);  // (the state's base is known once it is open)
+            if (t == 0) {
+                fill_keys(c.h + c.L.h_keys);
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.keys, c.h + c.L.h_keys, 32 * (size_t)B, hipMemcpyHostToDevice, c.s));
+                if ((rc = best_keys_enqueue(c, c.d + c.L.keys, 32, 0, floor32, dstatus))) return rc;
+            }
+            if (pending) {  // the tranche just verified: its statuses up, the rows marked
+                memcpy(c.h + c.L.h_tstat, st.data(), 4 * (size_t)pending);
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.tstat, c.h + c.L.h_tstat, 4 * (size_t)pending, hipMemcpyHostToDevice, c.s));
+                if ((rc = best_mark_enqueue(c, pending, (const int32_t*)c.at(c.L.tstat), dstatus))) return rc;
+            }
+            if (finish) {
+                if ((rc = best_finish_enqueue(c, K, dstatus, &room))) return rc;
+            } else {
+                if ((rc = best_select_enqueue(c, rows))) return rc;
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 256 + 4 * (size_t)room_sel, hipMemcpyDeviceToHost, c.s));
+            }
+            BBP_HIP_TRY(dev, hipEventRecord(dev->ev_best, c.s));
+            return BBP_OK;
+        });
+        if (rc) return rc;
+        const hipError_t e = wait_event_polling(dev->ev_best);
+        if (e != hipSuccess) {
+            api_guard(dev, [&]() -> int32_t { return dev->err = std::string("best valid proofs: ") + hipGetErrorString(e), BBP_ERR_DEVICE; });
+            return BBP_ERR_DEVICE;
+        }
+        if (finish) break;
+        u32 counts[2];
+        memcpy(counts, c.h + c.L.h_counts, 8);
+        if (t == 0) nc = counts[1], T0 = best_tranche0(K, tranche, nc);
+        const u32 n = counts[0];
+        pending = 0;
+        if (n != best_tranche_rows(T0, t, nc - examined)) {
+            api_guard(dev, [&]() -> int32_t { return dev->err = "best valid proofs: a tranche of unexpected size", BBP_ERR_INTERNAL; });
+            return BBP_ERR_INTERNAL;
+        }
+        if (n) {
+            st.assign(n, BBP_ERR_INTERNAL);
+            if ((rc = verdicts(n, (const u32*)(c.h + c.L.h_sel), st.data()))) return rc;
+            examined += n, pending = n;
+            for (u32 j = 0; j < n; j++) valid += st[j] == BBP_OK;
+        }
+        more = n && examined < nc && !(K && valid >= K);
+    }
+    std::string why;
+    const int32_t rc = best_deliver(c, room, examined, valid, nc, cap, best_out, n_best, n_candidates, n_examined, &why);
+    if (rc) {
+        api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
+        return rc;
+    }
+    memcpy(status, c.h + c.L.h_status, 4 * (size_t)B);
+    return BBP_OK;
+}
+
+// screening shared by the three forms' numbers: N, then B (round_select.h round_select_screen: the same checks in the same order)
+static int32_t best_screen(bbp_ctx* ctx, const char* what, u32 N, u32 B, bool* done) {
+    const int32_t screened = round_select_screen(N, B, done);
+    if (!screened) return BBP_OK;
+    return api_guard(ctx, [&]() -> int32_t {
+        if (int32_t rc = check_n(ctx, N)) return rc;  // (names the list length)
+        ctx->err = std::string(what) + ": more than BBP_SELECT_MAX_BIDS rows";
+        return screened;
+    });
+}
+
+extern "C" int32_t bbp_verify_round_best(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* rows, const uint8_t floor32[32], uint32_t K,
+                                         uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined,
+                                         int32_t* status) {
+    if (!ctx || !round || !rows || !floor32 || !n_best || !n_candidates || !n_examined || !status || (cap && !best_out)) return BBP_ERR_BAD_ARG;
+    *n_best = *n_candidates = *n_examined = 0;
+    bool done;
+    if (int32_t rc = best_screen(ctx, "bbp_verify_round_best", N, B, &done)) return rc;
+    if (done) return BBP_OK;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;  // keys, selection and marks: one device
+        const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
+        std::vector<uint8_t> picked;
+        auto fill = [&](u8* dst) {
+            for (u32 i = 0; i < B; i++) memcpy(dst + 32 * (size_t)i, rows + rb * i + key_off, 32);
+        };
+        auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // the tranche from the CALLER's memory, through the rounds verifier's own path
+            picked.resize(rb * n);
+            for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * sel[j], rb);
+            return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, round, nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
+        };
+        const int32_t rc = best_run_host(dev, B, fill, verdicts, floor32, K, tranche, cap, best_out, n_best, n_candidates, n_examined, status);
+        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+        return rc;
+    });
+}
+
+// Test hook: the shipped key, selection, mark and ranking kernels on caller-made keys and verdicts.  Synchronises.
+extern "C" int32_t bbp_debug_round_best(bbp_ctx* ctx, uint32_t B, const uint8_t* keys, const int32_t* verdicts, const uint8_t floor32[32], uint32_t K,
+                                        uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined,
+                                        int32_t* status) {
+    if (!ctx || !keys || !verdicts || !floor32 || !n_best || !n_candidates || !n_examined || !status || (cap && !best_out)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_round_best");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        auto refuse = [&](const char* why) {
+            api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
+            return (int32_t)BBP_ERR_BAD_ARG;
+        };
+        if (B == 0 || B > BBP_SELECT_MAX_BIDS) return refuse("bbp_debug_round_best: B is 0 or above BBP_SELECT_MAX_BIDS");
+        for (u32 i = 0; i < B; i++)
+            if (verdicts[i] != BBP_OK && verdicts[i] != BBP_ERR_VERIFY && verdicts[i] != BBP_ERR_FORMAT)
+                return refuse("bbp_debug_round_best: a verdict is none of BBP_OK, BBP_ERR_VERIFY, BBP_ERR_FORMAT");
+        auto fill = [&](u8* dst) { memcpy(dst, keys, 32 * (size_t)B); };
+        auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
+            for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j]];
+            return BBP_OK;
+        };
+        return best_run_host(ctx, B, fill, read, floor32, K, tranche, cap, best_out, n_best, n_candidates, n_examined, status);
+    });
+}
+
+// The device form, everything on s.  It synchronises s after the first selection (the candidate count), once per tranche (the two
+// counters) and once to deliver the results; the context lock is held throughout, as by a _dev call that delivers n_fallback.
+static int32_t best_run_dev(bbp_ctx* ctx, u32 N, const u8* round_dev, u32 B, const u8* rows_dev, const u8* entropy_dev, const uint8_t* floor32, u32 K,
+                            u32 tranche, u32 cap, u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, int32_t* status, hipStream_t s) {
+    std::lock_guard<std::mutex> call(ctx->best_mu);
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        BestCall c(ctx, B, false, s);
+        const u32 rb = (u32)round_row_bytes(N);
+        if ((rc = best_open(c)) || (rc = best_keys_enqueue(c, rows_dev, rb, proof_record_bytes(N), floor32, status))) return rc;
+        u32 T0 = 0, nc = 0, examined = 0, valid = 0, room = 0;
+        for (u32 t = 0;; t++) {
+            // tranche 0: its size needs the candidate count, which the selection delivers; a later one: the host knows it
+            u32 n = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(T0, t, nc - examined);
+            if ((rc = best_select_enqueue(c, n))) return rc;
+            if (t == 0) {
+                BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
+                BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+                u32 counts[2];
+                memcpy(counts, c.h + c.L.h_counts, 8);
+                n = counts[0], nc = counts[1], T0 = best_tranche0(K, tranche, nc);
+                if (n != best_tranche_rows(T0, 0, nc)) return ctx->err = "best valid proofs: a tranche of unexpected size", BBP_ERR_INTERNAL;
+            }
+            if (n == 0) break;
+            // the tranche's rows and entropy rows, packed; verified through the aggregated rounds path in engine calls of at most
+            // BBP_HOST_CHUNK_VERIFY rows, as a host-pointer call's are (the packed rows of a part are read before the next part's are
+            // written: one stream); marked
+            const u32 part = std::min(n, host_chunk_verify());
+            const BestRows R(part, N);
+            if ((rc = dev_reserve(ctx, ctx->best_rows, R.bytes))) return rc;
+            u8* g = (u8*)ctx->best_rows.p;
+            int32_t* tstat = (int32_t*)c.at(c.L.tstat);
+            for (u32 first = 0; first < n; first += part) {
+                const u32 m = std::min(part, n - first);
+                {
+                    ScopedEvent ev(ctx, TAG_SELECT, c.s);
+                    hipLaunchKernelGGL(k_best_gather, dim3(m), dim3(BEST_GATHER_T), 0, c.s, rb, first, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
+                                       rows_dev, entropy_dev, g + R.rows, g + R.ent);
+                    BBP_HIP_TRY(ctx, hipGetLastError());
+                }
+                if ((rc = verify_batch_agg_dev(ctx, VerifyRows::of_rounds(m, 1, &N, round_dev, nullptr), BBP_AGG_GROUP_DEFAULT, g + R.rows, g + R.ent,
+                                               tstat + first, c.s, nullptr)))
+                    return rc;
+            }
+            if ((rc = best_mark_enqueue(c, n, tstat, status))) return rc;
+            BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
+            BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));  // the two counters: rows examined, rows OK
+            u32 ctr[2];
+            memcpy(ctr, c.h + c.L.h_ctr, 8);
+            examined += n, valid = ctr[1];
+            if (ctr[0] != examined) return ctx->err = "best valid proofs: the device's count of examined rows is not the call's", BBP_ERR_INTERNAL;
+            if (examined >= nc || (K && valid >= K)) break;
+        }
+        if ((rc = best_finish_enqueue(c, K, nullptr, &room))) return rc;
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+        std::string why;
+        if ((rc = best_deliver(c, room, examined, valid, nc, cap, best_out, n_best, n_candidates, n_examined, &why))) ctx->err = why;
+        return rc;
+    });
+}
+
+extern "C" int32_t bbp_verify_round_best_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* rows_dev, const void* entropy_dev,
+                                             const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best,
+                                             uint32_t* n_candidates, uint32_t* n_examined, void* status_dev, void* stream) {
+    if (!ctx || !round_dev || !rows_dev || !entropy_dev || !floor32 || !n_best || !n_candidates || !n_examined || !status_dev || (cap && !best_out))
+        return BBP_ERR_BAD_ARG;
+    *n_best = *n_candidates = *n_examined = 0;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_round_best_dev");
+    bool done;
+    if (int32_t rc = best_screen(ctx, "bbp_verify_round_best_dev", N, B, &done)) return rc;
+    if (done) return BBP_OK;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        return best_run_dev(ctx, N, (const u8*)round_dev, B, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, K, tranche, cap, best_out, n_best,
+                            n_candidates, n_examined, (int32_t*)status_dev, pick_stream(ctx, stream));
     });
 }
 

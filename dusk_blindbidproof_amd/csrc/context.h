@@ -207,6 +207,15 @@ struct bbp_ctx {
     void* sel_h = nullptr;
     size_t sel_h_cap = 0;
     hipEvent_t ev_sel = nullptr;
+    // bbp_verify_round_best, its _dev form and bbp_debug_round_best (capi_prove.hip; the layout is round_best.h's BestLayout): keys,
+    // candidate and winner records, statuses, one tranche's selection and verdicts on the device, a pinned mirror of what travels, and
+    // -- the _dev form only -- the gathered rows of one tranche with their entropy rows.  All PUBLIC (secret_map.h), all grow on demand
+    // (bbp_reserve does not size them); best_mu serialises the calls that use them, and is taken BEFORE the context lock.
+    std::mutex best_mu;
+    bbp::DevBuf best_dev, best_rows;
+    void* best_h = nullptr;
+    size_t best_h_cap = 0;
+    hipEvent_t ev_best = nullptr;
     // resident tables
     bbp::ge* gens = nullptr;           // [TAB_BASES] extended points: B_blinding, G[2048], H[2048], B, then the PAD_BASES range sums and the MRG_BASES merged bases
     bbp::niels_row* ptable = nullptr;      // [TAB_BASES * MSM_POS] affine cached 2^b * P_i, 128-byte limb rows (275 MB)

@@ -149,12 +149,16 @@ inline bool batch_spans(u32 B, const BatchDims& d, int cls, BatchSpans& out) {
     X("idx", c->idx, 1, false)                               /* index lists: functions of N */                                          \
     X("vl.misc", c->vl[i].misc, bbp_ctx::VLANES, false)      /* the verifier lanes: everything a verifier reads is public */            \
     X("vl.agg", c->vl[i].agg, bbp_ctx::VLANES, false)                                                                                   \
-    X("vl.agg_io", c->vl[i].agg_io, bbp_ctx::VLANES, false)
+    X("vl.agg_io", c->vl[i].agg_io, bbp_ctx::VLANES, false)                                                                             \
+    /* bbp_verify_round_best: proof rows, their claimed scores and the verifier's verdicts are what any verifier is handed or tells */   \
+    X("best", c->best_dev, 1, false)                         /* keys, candidate and winner records, statuses, selections */             \
+    X("best.rows", c->best_rows, 1, false)                   /* the _dev form's gathered rows and verifier entropy rows of one tranche */
 // X(name, pointer, capacity, count, secret): the pinned mirrors of the staging slots
 #define BBP_CTX_PINNED_BUFFERS(X, S)                                                                                                    \
     X("io.h_in", c->io[i].h_in, c->io[i].h_in_cap, S + bbp_ctx::IO_VSLOTS, i < S)                                                        \
     X("io.h_out", c->io[i].h_out, c->io[i].h_cap, S + bbp_ctx::IO_VSLOTS, i < S)                                                        \
-    X("sel.h", c->sel_h, c->sel_h_cap, 1, true)              /* ... and its mirror: the bids going up, scores and selection coming down */
+    X("sel.h", c->sel_h, c->sel_h_cap, 1, true)              /* ... and its mirror: the bids going up, scores and selection coming down */ \
+    X("best.h", c->best_h, c->best_h_cap, 1, false)          /* bbp_verify_round_best's mirror: claimed scores up, verdicts and ranks down (public) */
 // Not DevBufs, all PUBLIC, walked by the scan from wipe.hip: the resident tables gens, ptable, btab, comb, mimc_c (functions of public
 // constants) and the verifier lanes' pinned ns_ring.  Not walked: the compiled circuits' lists and vctab (uploaded from host tables that
 // are functions of N), and the counter words health, chk_counts, agg_count and the pinned h_flag.

@@ -80,10 +80,11 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *                           statuses in request order; the call returns the first member's non-zero status, if any
  *   bbp_witness_batch, bbp_get_generator, bbp_get_mimc_constant, bbp_ubench   served by member 0
  *   bbp_prove_round_select  scoring and selection served by member 0, the selected bids proved as bbp_prove_round on the pool
+ *   bbp_verify_round_best   keys, selection and marks served by member 0, every tranche verified as bbp_verify_rounds_aggregated on the pool
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
- * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_set_profiling /
+ * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_debug_round_best, bbp_set_profiling /
  * bbp_last_timings; the stream getters return NULL. */
 int32_t bbp_init_all(bbp_ctx** out);
 int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp_ctx** out);
@@ -366,6 +367,62 @@ int32_t bbp_prove_round_select(bbp_ctx* ctx, uint32_t N, const uint8_t* round, u
                                uint64_t* toggles_out, uint8_t* scores_out, int32_t* status);
 int32_t bbp_debug_round_select(bbp_ctx* ctx, uint32_t B, const uint8_t* scores, const int32_t* statuses, const uint8_t floor32[32], uint32_t K,
                                uint32_t cap, uint32_t* sel_out, uint32_t* n_sel, uint32_t* n_qualified);
+
+/* Best valid proofs of a round: the verify side of "the proof with the highest score wins".  A node that has collected B candidate
+ * proofs of one round wants the best valid one, or the K best.  The score is a public input of the circuit, so a valid proof cannot
+ * claim a score it did not earn and a forged high score costs the verifier one failed check: these calls order the rows by CLAIMED
+ * score, verify from the top in tranches that double, and stop at the K-th proof that holds -- one small tranche for honest traffic,
+ * at most all B verifications for a flood of forged high scores.
+ * Inputs: one round seed || pub_list (N items) and B rows record || score || z_img -- bbp_verify_rounds' layout with R = 1, compact
+ * records, bbp_round_row_size(N) bytes each, packed back to back (B <= BBP_SELECT_MAX_BIDS) -- and floor32, K, tranche.
+ *   key[i]        the 32 score bytes of row i as an unsigned 256-bit little-endian integer: the field the verifier reads
+ *   screening     in this order: key[i] >= l: status[i] = BBP_ERR_FORMAT, the row is never verified (what bbp_verify_rounds reports for
+ *                 a non-canonical score whatever else the row holds); key[i] < floor: status[i] = BBP_ROW_SKIPPED ("the call did not
+ *                 have to verify this row"; not a bbp_status); any other row is a candidate, n_candidates counts them
+ *   order         candidates by key descending, then index ascending (byte-equal rows do occur)
+ *   tranches      T_0 = max(tranche, K), tranche == 0 meaning BBP_BEST_TRANCHE_DEFAULT; with K == 0, T_0 = n_candidates (one tranche,
+ *                 every candidate is examined); T_t = T_0 * 2^t.  Tranche t is the next min(T_t, remaining) candidates in that order;
+ *                 every row of it is verified, and its status[i] is exactly what bbp_verify_rounds reports for that row in that round
+ *                 (BBP_OK / BBP_ERR_VERIFY / BBP_ERR_FORMAT)
+ *   stopping      at the end of the first tranche after which at least K rows have verified OK (K > 0), or when no candidate is left;
+ *                 candidates never reached keep BBP_ROW_SKIPPED; n_examined counts the verified rows
+ *   best          the OK rows in candidate order, the first K of them (all when K == 0), in rank order: best[0] is the winner.
+ *                 n_best is its true length, best_out receives min(n_best, cap) entries (entries beyond are not written)
+ * Which rows are examined depends only on the inputs and `tranche`, never on timing.  At most n_candidates rows are verified, in at
+ * most ceil(log2(n_candidates / T_0 + 1)) tranches.
+ * Screening of the arguments, before anything runs, the first failing check decides: a NULL required pointer BBP_ERR_BAD_ARG (best_out
+ * may be NULL only when cap == 0); N == 0 BBP_ERR_BAD_ARG; N > BBP_MAX_ITEMS BBP_ERR_GENS_LEN; B > BBP_SELECT_MAX_BIDS BBP_ERR_BAD_ARG;
+ * B == 0 BBP_OK with all counts zero.
+ *
+ * bbp_verify_round_best, the host form (a context or a pool): only the 32 key bytes of every row go up (gathered into a pinned staging
+ * area); keys, selection and the examined marks live on one device -- the context, or member 0 of a pool.  Per tranche the selected
+ * indices come down, the tranche's rows are gathered from the caller's memory and verified through bbp_verify_rounds_aggregated's own
+ * path (so the pool split, BBP_HOST_CHUNK_VERIFY, the entropy source, verify mixing and the health word hold as they do there), and its
+ * statuses go back up to mark the rows.  A row that is not examined never crosses PCIe.  Calls on one context are serialised among
+ * themselves; their device state and pinned mirror grow on demand: bbp_reserve does NOT size them.
+ *
+ * bbp_verify_round_best_dev, rows resident in device memory; a pool refuses it.  rows_dev may have any alignment; entropy_dev holds
+ * B x 32 bytes, row i for row i under bbp_verify_batch_dev's contract (distinct, unpredictable rows), gathered with its row; a tranche
+ * runs through bbp_verify_rounds_aggregated_dev's path on the gathered rows, in engine calls of at most BBP_HOST_CHUNK_VERIFY rows as a
+ * host-pointer call's are (which also bounds the gathered copy).  The call SYNCHRONISES `stream`: once after the first
+ * selection (the candidate count), once per tranche to read two counters (rows examined, rows OK), and once to deliver the results.
+ * The host outputs are valid on return; status_dev (B x int32) is complete on `stream`.  No host screening of device data.
+ *
+ * bbp_debug_round_best, test hook (synchronises; a pool refuses it): the shipped key, selection, mark and ranking kernels on caller-made
+ * host arrays -- keys B x 32 bytes, verdicts B x int32, each BBP_OK, BBP_ERR_VERIFY or BBP_ERR_FORMAT: what verification would say of
+ * that row.  Nothing is verified: a tranche's statuses are read from verdicts.  BBP_ERR_BAD_ARG, nothing launched: a NULL pointer, B == 0
+ * or above BBP_SELECT_MAX_BIDS, a verdict outside the three. */
+#define BBP_ROW_SKIPPED (-1)
+#define BBP_BEST_TRANCHE_DEFAULT 16u
+int32_t bbp_verify_round_best(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* rows, const uint8_t floor32[32], uint32_t K,
+                              uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined,
+                              int32_t* status);
+int32_t bbp_verify_round_best_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* rows_dev, const void* entropy_dev,
+                                  const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best,
+                                  uint32_t* n_candidates, uint32_t* n_examined, void* status_dev, void* stream);
+int32_t bbp_debug_round_best(bbp_ctx* ctx, uint32_t B, const uint8_t* keys, const int32_t* verdicts, const uint8_t floor32[32], uint32_t K,
+                             uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined,
+                             int32_t* status);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.

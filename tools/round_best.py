@@ -1,0 +1,208 @@
+"""What finding a round's best valid proof costs on one MI355X (include/bbp.h "Best valid proofs of a round"; DESIGN.md has the figures).
+One JSON line per cell, to stdout and to --out (default profiles/r19_round_best.jsonl) with the box id and --commit.
+
+  cells   shapes (N, B) = (8, 8192), (202, 8192), (8, 65536); traffic: every row honest / the top 1 % by claimed score forged / the top
+          25 % forged / every row forged (a forged row is a valid row with one record byte flipped: it keeps its claim and fails).
+          Arm A: bbp_verify_round_best with K = 1 and the default tranche, and its _dev form on resident rows.  Arm B, the route a caller
+          had before: bbp_verify_rounds_aggregated (or its _dev form, in calls of at most 32 768 rows) over all rows, then the pick on the
+          host.  Per cell: ms per call for the four arms, rows examined and tranches (asserted equal to what the rules predict), bytes
+          uploaded by the host forms, A / B.
+  sweep   tranche in {16, 64, 256, 1024} on the honest and the 25 % traffic at B = 8192, host form: what picks BBP_BEST_TRANCHE_DEFAULT.
+
+Rows are 64 proved bids of the round repeated (byte-equal rows do occur in the protocol too); arms alternate in one process; every figure
+is the best of --calls calls, taken --runs times after a warm-up: median and range."""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from ab import box_id  # noqa: E402
+
+T_X = 257  # byte offset of t_x in a record
+DEV_CALL_ROWS = 32768
+TRAFFIC = (("honest", 0.0), ("top_1pct_forged", 0.01), ("top_25pct_forged", 0.25), ("all_forged", 1.0))
+
+
+def stats(v):
+    return {"median": round(statistics.median(v), 3), "min": round(min(v), 3), "max": round(max(v), 3)}
+
+
+def predict(n_candidates, forged, K, tranche):
+    """(rows examined, tranches) by the rules when the first `forged` candidates in the candidate order fail and the rest hold"""
+    T, at, t = max(tranche, K), 0, 0
+    while at < n_candidates:
+        at, T, t = min(at + T, n_candidates), 2 * T, t + 1
+        if at - min(at, forged) >= K:
+            break
+    return at, t
+
+
+class Cell:
+    """one shape and traffic: the rows on the host (a ctypes buffer) and on the device, what every arm must answer"""
+
+    def __init__(self, torch, bbp, np, N, B, base_rows, table, frac):
+        row = bbp.round_row_size(N)
+        n_base = len(base_rows) // row
+        rows = bytearray(base_rows * (B // n_base))
+        key_off = bbp.record_size(N)
+        keys = np.frombuffer(bytes(rows), dtype=np.uint8).reshape(B, row)[:, key_off:key_off + 32].copy().view("<u8")  # B x 4 words
+        idx = np.arange(B)
+        self.order = np.lexsort((idx, ~keys[:, 0], ~keys[:, 1], ~keys[:, 2], ~keys[:, 3]))  # key descending, index ascending
+        self.forged = int(round(frac * B))
+        for i in self.order[:self.forged].tolist():
+            rows[row * i + T_X] ^= 0x01
+        self.N, self.B, self.row, self.keys = N, B, row, keys
+        self.best = int(self.order[self.forged]) if self.forged < B else None
+        self.host = (ctypes.c_uint8 * len(rows)).from_buffer(rows)
+        self.table = (ctypes.c_uint8 * len(table)).from_buffer_copy(table)
+        self.d_rows = torch.frombuffer(rows, dtype=torch.uint8).cuda()
+        self.d_table = torch.frombuffer(bytearray(table), dtype=torch.uint8).cuda()
+        self.d_ent = torch.randint(0, 256, (32 * B,), dtype=torch.uint8, device="cuda")
+        self.d_status = torch.zeros(4 * B, dtype=torch.uint8, device="cuda")
+        self.status = (ctypes.c_int32 * B)()
+        self.floor = (ctypes.c_uint8 * 32)()
+
+
+def make_arms(ctx, bbp, torch, np, c, tranche):
+    lib, h = bbp.lib, ctx.handle
+    best, n = (ctypes.c_uint32 * 1)(), [ctypes.c_uint32() for _ in range(3)]
+    nfb = ctypes.c_uint32()
+    Ns = (ctypes.c_uint32 * 1)(c.N)
+    stream = torch.cuda.Stream()
+
+    def answer():
+        return (best[0] if n[0].value else None, n[0].value, n[1].value, n[2].value)
+
+    def a_host():
+        rc = lib.bbp_verify_round_best(h, c.N, c.table, c.B, c.host, c.floor, 1, tranche, 1, best, ctypes.byref(n[0]), ctypes.byref(n[1]), ctypes.byref(n[2]),
+                                       c.status)
+        assert rc == 0, (rc, lib.bbp_last_error(h))
+        return answer()
+
+    def a_dev():
+        rc = lib.bbp_verify_round_best_dev(h, c.N, c.d_table.data_ptr(), c.B, c.d_rows.data_ptr(), c.d_ent.data_ptr(), c.floor, 1, tranche, 1, best,
+                                           ctypes.byref(n[0]), ctypes.byref(n[1]), ctypes.byref(n[2]), c.d_status.data_ptr(), stream.cuda_stream)
+        assert rc == 0, (rc, lib.bbp_last_error(h))
+        stream.synchronize()
+        return answer()
+
+    def pick(status):
+        ok = np.nonzero(status == 0)[0]
+        if not len(ok):
+            return None
+        k = c.keys[ok]
+        return int(ok[np.lexsort((ok, ~k[:, 0], ~k[:, 1], ~k[:, 2], ~k[:, 3]))[0]])
+
+    def b_host():
+        rc = lib.bbp_verify_rounds_aggregated(h, 1, Ns, c.table, c.B, None, c.host, c.status, 0, ctypes.byref(nfb))
+        assert rc == 0, (rc, lib.bbp_last_error(h))
+        return (pick(np.frombuffer(c.status, dtype="<i4")),)
+
+    def b_dev():  # in calls of at most 32 768 rows, the size of a host-pointer call's engine calls (BBP_HOST_CHUNK_VERIFY)
+        for first in range(0, c.B, DEV_CALL_ROWS):
+            m = min(DEV_CALL_ROWS, c.B - first)
+            rc = lib.bbp_verify_rounds_aggregated_dev(h, 1, Ns, c.d_table.data_ptr(), m, None, c.d_rows.data_ptr() + c.row * first,
+                                                      c.d_ent.data_ptr() + 32 * first, c.d_status.data_ptr() + 4 * first, 0, None, stream.cuda_stream)
+            assert rc == 0, (rc, lib.bbp_last_error(h))
+        stream.synchronize()
+        return (pick(c.d_status.cpu().numpy().view("<i4")),)
+    return {"best_host": a_host, "best_dev": a_dev, "all_then_pick_host": b_host, "all_then_pick_dev": b_dev}
+
+
+def timed(arms, names, args):
+    for name in names:  # the warm-up, and the answers
+        arms[name]()
+    runs = {name: [] for name in names}
+    for _ in range(args.runs):
+        for name in names:
+            best = None
+            for _c in range(args.calls):
+                t = time.perf_counter()
+                arms[name]()
+                dt = (time.perf_counter() - t) * 1e3
+                best = dt if best is None else min(best, dt)
+            runs[name].append(best)
+    return {name: stats(v) for name, v in runs.items()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19_round_best.jsonl"))
+    ap.add_argument("--commit", default="")
+    ap.add_argument("--runs", type=int, default=5)
+    ap.add_argument("--calls", type=int, default=2)
+    ap.add_argument("--sections", default="cells,sweep")
+    args = ap.parse_args()
+    import numpy as np
+    import torch
+    torch.cuda.init()
+    import dusk_blindbidproof_amd as bbp
+    from tests import prove_round_cases as rc
+    box = box_id()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    T_DEFAULT = bbp.BEST_TRANCHE_DEFAULT
+    with open(args.out, "w") as f:
+        def emit(rec):
+            rec.update(box=box, commit=args.commit)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        ctx = bbp.Context(0)
+        try:
+            base = {}
+            for N in (8, 202):
+                r = rc.honest(N, 64, tag=19)
+                rows, _t, st = ctx.prove_round(N, r.table, r.bid_bytes)
+                assert st == [0] * 64
+                base[N] = (rows, r.table)
+            unit = "ms of host time per call, best of %d, %d runs after a warm-up" % (args.calls, args.runs)
+            if "cells" in args.sections:
+                for N, B in ((8, 8192), (202, 8192), (8, 65536)):
+                    for tname, frac in TRAFFIC:
+                        c = Cell(torch, bbp, np, N, B, base[N][0], base[N][1], frac)
+                        arms = make_arms(ctx, bbp, torch, np, c, 0)
+                        examined, tranches = predict(B, c.forged, 1, T_DEFAULT)
+                        want = (c.best, 1 if c.best is not None else 0, B, examined)
+                        assert arms["best_host"]() == want and arms["best_dev"]() == want, (arms["best_host"](), want)  # nothing here is tuned: the rules predict it
+                        assert arms["all_then_pick_host"]() == (c.best,) and arms["all_then_pick_dev"]() == (c.best,)
+                        rec = {"section": "cells", "N": N, "B": B, "traffic": tname, "K": 1, "tranche": T_DEFAULT, "rows_examined": examined,
+                               "tranches": tranches, "unit": unit}
+                        rec.update(timed(arms, list(arms), args))
+                        tab = 32 * (1 + N)
+                        rec["bytes_uploaded"] = {"best_host": 32 * B + examined * (c.row + 32 + 4) + tranches * tab, "all_then_pick_host": B * (c.row + 32) + tab}
+                        rec["ratio_A_over_B"] = {"host": round(rec["best_host"]["median"] / rec["all_then_pick_host"]["median"], 4),
+                                                 "dev": round(rec["best_dev"]["median"] / rec["all_then_pick_dev"]["median"], 4)}
+                        for form in ("host", "dev"):
+                            a, b = rec["best_" + form], rec["all_then_pick_" + form]
+                            rec["A_loses_by_more_than_B_range_" + form] = a["median"] - b["median"] > b["max"] - b["min"]
+                        emit(rec)
+                        del c, arms
+            if "sweep" in args.sections:
+                for N in (8, 202):
+                    for tname, frac in (TRAFFIC[0], TRAFFIC[2]):
+                        c = Cell(torch, bbp, np, N, 8192, base[N][0], base[N][1], frac)
+                        rec = {"section": "sweep", "N": N, "B": 8192, "traffic": tname, "K": 1, "unit": unit}
+                        sweep = {}
+                        for tranche in (16, 64, 256, 1024):
+                            sweep[tranche] = make_arms(ctx, bbp, torch, np, c, tranche)["best_host"]
+                            examined, tranches = predict(8192, c.forged, 1, tranche)
+                            assert sweep[tranche]() == (c.best, 1, 8192, examined)
+                            rec["rows_examined_%d" % tranche] = examined
+                        for k, v in timed(sweep, list(sweep), args).items():
+                            rec["tranche_%d" % k] = v
+                        emit(rec)
+                        del c
+            assert ctx.health() == 0
+        finally:
+            ctx.close()
+
+
+if __name__ == "__main__":
+    main()
