@@ -88,6 +88,9 @@ SIGNATURES = {
     "bbp_verify_round_best": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_round_best_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_round_best": (_i32, [_vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_round_best_distinct": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_round_best_distinct_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_round_best_distinct": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_set_prove_check": (_i32, [_vp, _i32]),
     "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -240,6 +243,8 @@ RoundSelection = collections.namedtuple("RoundSelection", "rc rows sel n_sel n_q
 ROW_SKIPPED = -1            # BBP_ROW_SKIPPED: bbp_verify_round_best did not have to verify this row
 BEST_TRANCHE_DEFAULT = 16   # BBP_BEST_TRANCHE_DEFAULT
 RoundBest = collections.namedtuple("RoundBest", "best n_best n_candidates n_examined status raw")
+ROW_DUPLICATE = -2          # BBP_ROW_DUPLICATE: the row's identity (z_img) already had a verified row; not verified
+RoundBestDistinct = collections.namedtuple("RoundBestDistinct", "best n_best n_candidates n_examined n_duplicates status raw")
 
 
 def select_floor(floor):
@@ -590,6 +595,47 @@ class Context:
                                              tranche, cap, best, ctypes.byref(counts[0]), ctypes.byref(counts[1]), ctypes.byref(counts[2]), status))
         return self._best_result(B, cap, best, status, counts)
 
+    def verify_round_best_distinct(self, N, table, rows, floor=0, K=1, tranche=0, cap=None, fill=0):
+        """bbp_verify_round_best_distinct: as verify_round_best, with at most one row per z_img in best; rows of an identity that already
+        has a verified row leave unverified with ROW_DUPLICATE.  Returns a RoundBestDistinct (n_duplicates counts those rows)."""
+        row = round_row_size(N)
+        if len(table) != 32 * (1 + N) or len(rows) % row:
+            raise ValueError("a round is a 32-byte seed and N 32-byte items; rows are round_row_size(N) bytes each")
+        B = len(rows) // row
+        cap, best, status, counts = self._best_buffers(B, K, cap, fill)
+        dups = _u32(0)
+        self._check(lib.bbp_verify_round_best_distinct(self._h, N, _buf(table), B, _buf(rows) if B else best, _buf(select_floor(floor)), K, tranche, cap, best,
+                                                       ctypes.byref(counts[0]), ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
+        return self._best_distinct_result(B, cap, best, status, counts, dups)
+
+    def verify_round_best_distinct_dev(self, N, table_ptr, B, rows_ptr, ent_ptr, status_ptr, floor=0, K=1, tranche=0, cap=None, stream=None, fill=0):
+        """bbp_verify_round_best_distinct_dev: rows (any alignment) and B x 32 entropy bytes resident on the device; synchronises `stream`
+        as verify_round_best_dev does.  Returns a RoundBestDistinct whose status is None: the B statuses are at status_ptr."""
+        cap, best, _, counts = self._best_buffers(B, K, cap, fill)
+        dups = _u32(0)
+        self._check(lib.bbp_verify_round_best_distinct_dev(self._h, N, table_ptr, B, rows_ptr, ent_ptr, _buf(select_floor(floor)), K, tranche, cap, best,
+                                                           ctypes.byref(counts[0]), ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups),
+                                                           status_ptr, _stream(stream)))
+        return self._best_distinct_result(B, cap, best, None, counts, dups)
+
+    def debug_round_best_distinct(self, keys, ids, verdicts, floor=0, K=1, tranche=0, cap=None, table_log2=0, fill=0):
+        """bbp_debug_round_best_distinct (test hook): the shipped kernels on made-up keys and ids (B x 32 bytes each) and verdicts; nothing
+        is verified.  table_log2: 0, or an explicit size of the identity table.  Returns a RoundBestDistinct."""
+        B = len(verdicts)
+        if len(keys) != 32 * B or len(ids) != 32 * B:
+            raise ValueError("keys and ids are 32 bytes per verdict")
+        cap, best, status, counts = self._best_buffers(B, K, cap, fill)
+        dups = _u32(0)
+        self._check(lib.bbp_debug_round_best_distinct(self._h, B, _buf(keys) if B else best, _buf(ids) if B else best, (ctypes.c_int32 * max(1, B))(*verdicts),
+                                                      _buf(select_floor(floor)), K, tranche, cap, table_log2, best, ctypes.byref(counts[0]),
+                                                      ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
+        return self._best_distinct_result(B, cap, best, status, counts, dups)
+
+    @staticmethod
+    def _best_distinct_result(B, cap, best, status, counts, dups):
+        r = Context._best_result(B, cap, best, status, counts)
+        return RoundBestDistinct(r.best, r.n_best, r.n_candidates, r.n_examined, dups.value, r.status, r.raw)
+
     @staticmethod
     def _best_buffers(B, K, cap, fill):
         if cap is None:
@@ -813,7 +859,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best (member 0 selects, the pool verifies); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best / verify_round_best_distinct (member 0 selects, the pool verifies); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):
@@ -849,6 +895,11 @@ class Pool(Context):
         """bbp_verify_round_best on the pool: member 0 keeps the keys, selects and marks; every tranche is verified as
         verify_rounds_aggregated verifies it (block-split over the members)."""
         return super().verify_round_best(N, table, rows, floor, K, tranche, cap, fill)
+
+    def verify_round_best_distinct(self, N, table, rows, floor=0, K=1, tranche=0, cap=None, fill=0):
+        """bbp_verify_round_best_distinct on the pool: member 0 keeps the keys and identities, selects, marks and drops; every tranche is
+        verified as verify_rounds_aggregated verifies it (block-split over the members)."""
+        return super().verify_round_best_distinct(N, table, rows, floor, K, tranche, cap, fill)
 
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""

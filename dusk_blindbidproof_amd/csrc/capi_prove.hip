@@ -1694,6 +1694,323 @@ extern "C" int32_t bbp_verify_round_best_dev(bbp_ctx* ctx, uint32_t N, const voi
     });
 }
 
+// ---- best proofs of a round, one per bidder (include/bbp.h; rules and kernels: round_best.h) ------------------------------------------
+// The launch sequence of one call, on ONE device's context and one stream:
+//   open      the state reserved (BestLayout(B, false) with BestDistinctLayout behind it), ctr and dctr zeroed, the table emptied
+//   keys      k_best_keys and k_best_ids
+//   per tranche   select -> counts, sel;  [the rows verified];  mark, k_best_settle, k_best_holders, k_best_drop (which does nothing once
+//                 the call stops), then ctr and dctr into the mirror: settled identities and dropped rows decide the next tranche
+//   finish    as the calls above, plus dctr
+struct BestDistinctCall : BestCall {
+    BestDistinctLayout D;
+    u32 K;
+    BestDistinctCall(bbp_ctx* c, u32 B_, u32 K_, u32 table_log2, bool host_rows, hipStream_t s_)
+        : BestCall(c, B_, false, s_), D(L, B_, table_log2, host_rows), K(K_) {}
+    u32 mask() const { return D.slots - 1; }
+};
+
+static int32_t best_distinct_open(BestDistinctCall& c) {
+    bbp_ctx* ctx = c.ctx;
+    int32_t rc;
+    if ((rc = dev_reserve(ctx, ctx->best_dev, c.D.bytes)) || (rc = pinned_reserve(ctx, ctx->best_h, ctx->best_h_cap, c.D.h_bytes))) return rc;
+    if (!ctx->ev_best) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_best, hipEventDisableTiming));
+    c.d = (u8*)ctx->best_dev.p, c.h = (u8*)ctx->best_h;
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.L.ctr, 0, 16, c.s));
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.D.dctr, 0, 16, c.s));
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.D.table, 0xff, 4 * (size_t)c.D.slots, c.s));
+    return BBP_OK;
+}
+
+// keys at base + i stride + off, ids 32 bytes behind them (score || z_img are adjacent in a row)
+static int32_t best_distinct_keys_enqueue(const BestDistinctCall& c, const u8* base, size_t stride, size_t off, const uint8_t* floor32, int32_t* status) {
+    if (int32_t rc = best_keys_enqueue(c, base, stride, off, floor32, status)) return rc;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_best_ids, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, base, stride, off + 32, c.at(c.D.ids));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// behind the mark of a tranche of n rows: identities settled, holders' winner records opened, duplicates dropped unless the call stops
+// here (`drop`: false when the host knows that no live candidate is left), the five counters into the mirror
+static int32_t best_settle_enqueue(const BestDistinctCall& c, u32 n, const int32_t* tstat, int32_t* status, bool drop) {
+    bbp_ctx* ctx = c.ctx;
+    const u32 *sel = c.at(c.L.sel), *counts = c.at(c.L.counts), *ids = c.at(c.D.ids);
+    u32 *table = c.at(c.D.table), *dctr = c.at(c.D.dctr);
+    {
+        ScopedEvent ev(ctx, TAG_SELECT, c.s);
+        const dim3 grid((n + BEST_T - 1) / BEST_T), block(BEST_T);
+        hipLaunchKernelGGL(k_best_settle, grid, block, 0, c.s, n, sel, counts, tstat, (const u32*)c.at(c.L.recs), ids, table, c.mask(), dctr);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_best_holders, grid, block, 0, c.s, n, sel, counts, tstat, ids, (const u32*)table, c.mask(), c.at(c.L.win), dctr);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        if (drop) {
+            hipLaunchKernelGGL(k_best_drop, dim3((c.B + BEST_T - 1) / BEST_T), block, 0, c.s, c.B, c.K, c.at(c.L.recs), ids, (const u32*)table, c.mask(), status,
+                               dctr);
+            BBP_HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.D.h_dctr, c.d + c.D.dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+
+// What a call knows between tranches, and the checks that hold it to the device's counters.
+struct BestDistinctTally {
+    u32 T0 = 0, nc = 0, examined = 0, settled = 0, dups = 0;
+    u32 live() const { return nc - examined - dups; }
+    // the counters that arrived behind tranche's settle: false (with *why) when they are not what the call counted
+    bool take(const BestDistinctCall& c, std::string* why) {
+        u32 ctr[2], d[BEST_D_WORDS];
+        memcpy(ctr, c.h + c.L.h_ctr, 8);
+        memcpy(d, c.h + c.D.h_dctr, sizeof d);
+        if (d[BEST_D_FLAG]) return *why = "best proofs, one per bidder: a bounded loop of the identity table ran out (flag " + std::to_string(d[BEST_D_FLAG]) + ")", false;
+        if (ctr[0] != examined || d[BEST_D_SETTLED] < settled || d[BEST_D_SETTLED] > ctr[1] || d[BEST_D_DUPLICATES] < dups ||
+            (unsigned long long)examined + d[BEST_D_DUPLICATES] > nc)
+            return *why = "best proofs, one per bidder: the device counted " + std::to_string(ctr[0]) + " rows examined, " + std::to_string(d[BEST_D_SETTLED]) +
+                          " identities settled and " + std::to_string(d[BEST_D_DUPLICATES]) + " rows dropped; the call examined " + std::to_string(examined) +
+                          " of " + std::to_string(nc) + " candidates",
+                   false;
+        settled = d[BEST_D_SETTLED], dups = d[BEST_D_DUPLICATES];
+        return true;
+    }
+    bool stop(u32 K) const { return live() == 0 || (K && settled >= K); }
+};
+
+static int32_t best_distinct_finish_enqueue(const BestDistinctCall& c, const int32_t* status_to_fetch, u32* room) {
+    if (int32_t rc = best_finish_enqueue(c, c.K, status_to_fetch, room)) return rc;
+    BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + c.D.h_dctr, c.d + c.D.dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+
+// after the finish has arrived: examined, settled (against the winners' records the last selection counted) and duplicates, then the outputs
+static int32_t best_distinct_deliver(const BestDistinctCall& c, u32 room, BestDistinctTally& t, u32 cap, u32* best_out, u32* n_best, u32* n_candidates,
+                                     u32* n_examined, u32* n_duplicates, std::string* why) {
+    const u32 settled = t.settled, dups = t.dups;
+    if (!t.take(c, why)) return BBP_ERR_INTERNAL;
+    u32 counts[2];
+    memcpy(counts, c.h + c.L.h_counts, 8);
+    if (t.settled != settled || t.dups != dups || counts[1] != settled || counts[0] > room || counts[0] != (c.K && c.K < settled ? c.K : settled)) {
+        *why = "best proofs, one per bidder: " + std::to_string(counts[1]) + " winner records are open and " + std::to_string(counts[0]) + " selected for " +
+               std::to_string(settled) + " identities settled";
+        return BBP_ERR_INTERNAL;
+    }
+    best_rank_pairs(counts[0], (const u32*)(c.h + c.L.h_pairs), cap, best_out);
+    *n_best = counts[0], *n_candidates = t.nc, *n_examined = t.examined, *n_duplicates = t.dups;
+    return BBP_OK;
+}
+
+// counts = {n, live} of the selection of tranche t against the call's tally
+static bool best_distinct_tranche_ok(const u32* counts, u32 t, u32 K, u32 tranche, BestDistinctTally& ty) {
+    if (t == 0) ty.nc = counts[1], ty.T0 = best_tranche0(K, tranche, ty.nc);
+    return counts[1] == ty.live() && counts[0] == best_tranche_rows(ty.T0, t, counts[1]);
+}
+
+// The host forms on ONE device's context.  fill_rows(dst): the B x 64 bytes score || z_img into the pinned staging area; verdicts as in
+// best_run_host.  Two waits per tranche: for the selection, and for the counters behind the settle.
+template <class Fill, class Verdicts>
+static int32_t best_run_host_distinct(bbp_ctx* dev, u32 B, Fill&& fill_rows, Verdicts&& verdicts, const uint8_t* floor32, u32 K, u32 tranche, u32 cap,
+                                      u32 table_log2, u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status) {
+    std::lock_guard<std::mutex> call(dev->best_mu);
+    BestDistinctCall c(dev, B, K, table_log2, true, dev->stream);
+    BestDistinctTally ty;
+    std::vector<int32_t> st;
+    u32 room = 0;
+    auto fail = [&](const std::string& why, int32_t rc) {
+        api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
+        return rc;
+    };
+    // one submission under the context lock, then the wait for it with the lock released
+    auto submit = [&](auto&& enqueue) -> int32_t {
+        int32_t rc = api_guard(dev, [&]() -> int32_t {
+            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
+            if (int32_t r = enqueue()) return r;
+            BBP_HIP_TRY(dev, hipEventRecord(dev->ev_best, c.s));
+            return BBP_OK;
+        });
+        if (rc) return rc;
+        const hipError_t e = wait_event_polling(dev->ev_best);
+        return e == hipSuccess ? (int32_t)BBP_OK : fail(std::string("best proofs, one per bidder: ") + hipGetErrorString(e), BBP_ERR_DEVICE);
+    };
+    auto dstatus = [&] { return (int32_t*)c.at(c.L.status); };
+    for (u32 t = 0;; t++) {
+        const u32 rows = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(ty.T0, t, ty.live());
+        const u32 room_sel = rows ? rows : B;
+        int32_t rc = submit([&]() -> int32_t {
+            int32_t r;
+            if (t == 0) {
+                if ((r = best_distinct_open(c))) return r;
+                fill_rows(c.h + c.D.h_kid);
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.D.kid, c.h + c.D.h_kid, 64 * (size_t)B, hipMemcpyHostToDevice, c.s));
+                if ((r = best_distinct_keys_enqueue(c, c.d + c.D.kid, 64, 0, floor32, dstatus()))) return r;
+            }
+            if ((r = best_select_enqueue(c, rows))) return r;
+            BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 256 + 4 * (size_t)room_sel, hipMemcpyDeviceToHost, c.s));
+            return BBP_OK;
+        });
+        if (rc) return rc;
+        u32 counts[2];
+        memcpy(counts, c.h + c.L.h_counts, 8);
+        if (!best_distinct_tranche_ok(counts, t, K, tranche, ty)) return fail("best proofs, one per bidder: a tranche of unexpected size", BBP_ERR_INTERNAL);
+        const u32 n = counts[0];
+        if (n == 0) break;
+        st.assign(n, BBP_ERR_INTERNAL);
+        if ((rc = verdicts(n, (const u32*)(c.h + c.L.h_sel), st.data()))) return rc;
+        ty.examined += n;
+        const bool drop = ty.live() > 0;
+        rc = submit([&]() -> int32_t {  // the tranche's statuses up, the rows marked, identities settled
+            int32_t r;
+            memcpy(c.h + c.L.h_tstat, st.data(), 4 * (size_t)n);
+            BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.tstat, c.h + c.L.h_tstat, 4 * (size_t)n, hipMemcpyHostToDevice, c.s));
+            if ((r = best_mark_enqueue(c, n, (const int32_t*)c.at(c.L.tstat), dstatus()))) return r;
+            return best_settle_enqueue(c, n, (const int32_t*)c.at(c.L.tstat), dstatus(), drop);
+        });
+        if (rc) return rc;
+        std::string why;
+        if (!ty.take(c, &why)) return fail(why, BBP_ERR_INTERNAL);
+        if (ty.stop(K)) break;
+    }
+    int32_t rc = submit([&]() -> int32_t { return best_distinct_finish_enqueue(c, dstatus(), &room); });
+    if (rc) return rc;
+    std::string why;
+    if ((rc = best_distinct_deliver(c, room, ty, cap, best_out, n_best, n_candidates, n_examined, n_duplicates, &why))) return fail(why, rc);
+    memcpy(status, c.h + c.L.h_status, 4 * (size_t)B);
+    return BBP_OK;
+}
+
+extern "C" int32_t bbp_verify_round_best_distinct(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* rows, const uint8_t floor32[32],
+                                                  uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates,
+                                                  uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status) {
+    if (!ctx || !round || !rows || !floor32 || !n_best || !n_candidates || !n_examined || !n_duplicates || !status || (cap && !best_out)) return BBP_ERR_BAD_ARG;
+    *n_best = *n_candidates = *n_examined = *n_duplicates = 0;
+    bool done;
+    if (int32_t rc = best_screen(ctx, "bbp_verify_round_best_distinct", N, B, &done)) return rc;
+    if (done) return BBP_OK;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;  // keys, identities, selection and marks: one device
+        const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
+        std::vector<uint8_t> picked;
+        auto fill = [&](u8* dst) {  // score || z_img: one gather per row
+            for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, rows + rb * i + key_off, 64);
+        };
+        auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // the tranche from the CALLER's memory, through the rounds verifier's own path
+            picked.resize(rb * n);
+            for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * sel[j], rb);
+            return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, round, nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
+        };
+        const int32_t rc =
+            best_run_host_distinct(dev, B, fill, verdicts, floor32, K, tranche, cap, 0, best_out, n_best, n_candidates, n_examined, n_duplicates, status);
+        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+        return rc;
+    });
+}
+
+// Test hook: the shipped key, identity, selection, mark, settle, holder, drop and ranking kernels on caller-made keys, ids and verdicts.
+extern "C" int32_t bbp_debug_round_best_distinct(bbp_ctx* ctx, uint32_t B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts,
+                                                 const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t table_log2, uint32_t* best_out,
+                                                 uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status) {
+    if (!ctx || !keys || !ids || !verdicts || !floor32 || !n_best || !n_candidates || !n_examined || !n_duplicates || !status || (cap && !best_out))
+        return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_round_best_distinct");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        auto refuse = [&](const char* why) {
+            api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
+            return (int32_t)BBP_ERR_BAD_ARG;
+        };
+        if (B == 0 || B > BBP_SELECT_MAX_BIDS) return refuse("bbp_debug_round_best_distinct: B is 0 or above BBP_SELECT_MAX_BIDS");
+        u32 n_ok = 0;
+        for (u32 i = 0; i < B; i++) {
+            if (verdicts[i] != BBP_OK && verdicts[i] != BBP_ERR_VERIFY && verdicts[i] != BBP_ERR_FORMAT)
+                return refuse("bbp_debug_round_best_distinct: a verdict is none of BBP_OK, BBP_ERR_VERIFY, BBP_ERR_FORMAT");
+            n_ok += verdicts[i] == BBP_OK;
+        }
+        if (table_log2 > BEST_TABLE_LOG2_MAX || (table_log2 && (1u << table_log2) <= n_ok))
+            return refuse("bbp_debug_round_best_distinct: table_log2 is above 21, or the table has no slot more than there are BBP_OK verdicts");
+        auto fill = [&](u8* dst) {
+            for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, keys + 32 * (size_t)i, 32), memcpy(dst + 64 * (size_t)i + 32, ids + 32 * (size_t)i, 32);
+        };
+        auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
+            for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j]];
+            return BBP_OK;
+        };
+        return best_run_host_distinct(ctx, B, fill, read, floor32, K, tranche, cap, table_log2, best_out, n_best, n_candidates, n_examined, n_duplicates, status);
+    });
+}
+
+// The device form, everything on s; the synchronisation points are best_run_dev's: after the first selection, once per tranche (the
+// counters behind the settle, which size the next tranche) and once to deliver the results.
+static int32_t best_run_dev_distinct(bbp_ctx* ctx, u32 N, const u8* round_dev, u32 B, const u8* rows_dev, const u8* entropy_dev, const uint8_t* floor32, u32 K,
+                                     u32 tranche, u32 cap, u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status,
+                                     hipStream_t s) {
+    std::lock_guard<std::mutex> call(ctx->best_mu);
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        BestDistinctCall c(ctx, B, K, 0, false, s);
+        const u32 rb = (u32)round_row_bytes(N);
+        if ((rc = best_distinct_open(c)) || (rc = best_distinct_keys_enqueue(c, rows_dev, rb, proof_record_bytes(N), floor32, status))) return rc;
+        BestDistinctTally ty;
+        std::string why;
+        u32 room = 0;
+        for (u32 t = 0;; t++) {
+            // tranche 0: its size needs the candidate count, which the selection delivers; a later one: the host knows it
+            u32 n = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(ty.T0, t, ty.live());
+            if ((rc = best_select_enqueue(c, n))) return rc;
+            if (t == 0) {
+                BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
+                BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+                u32 counts[2];
+                memcpy(counts, c.h + c.L.h_counts, 8);
+                if (!best_distinct_tranche_ok(counts, 0, K, tranche, ty)) return ctx->err = "best proofs, one per bidder: a tranche of unexpected size", BBP_ERR_INTERNAL;
+                n = counts[0];
+            }
+            if (n == 0) break;
+            const u32 part = std::min(n, host_chunk_verify());
+            const BestRows R(part, N);
+            if ((rc = dev_reserve(ctx, ctx->best_rows, R.bytes))) return rc;
+            u8* g = (u8*)ctx->best_rows.p;
+            int32_t* tstat = (int32_t*)c.at(c.L.tstat);
+            for (u32 first = 0; first < n; first += part) {
+                const u32 m = std::min(part, n - first);
+                {
+                    ScopedEvent ev(ctx, TAG_SELECT, c.s);
+                    hipLaunchKernelGGL(k_best_gather, dim3(m), dim3(BEST_GATHER_T), 0, c.s, rb, first, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
+                                       rows_dev, entropy_dev, g + R.rows, g + R.ent);
+                    BBP_HIP_TRY(ctx, hipGetLastError());
+                }
+                if ((rc = verify_batch_agg_dev(ctx, VerifyRows::of_rounds(m, 1, &N, round_dev, nullptr), BBP_AGG_GROUP_DEFAULT, g + R.rows, g + R.ent,
+                                               tstat + first, c.s, nullptr)))
+                    return rc;
+            }
+            ty.examined += n;
+            if ((rc = best_mark_enqueue(c, n, tstat, status)) || (rc = best_settle_enqueue(c, n, tstat, status, ty.live() > 0))) return rc;
+            BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));  // rows examined and OK, identities settled, rows dropped
+            if (!ty.take(c, &why)) return ctx->err = why, BBP_ERR_INTERNAL;
+            if (ty.stop(K)) break;
+        }
+        if ((rc = best_distinct_finish_enqueue(c, nullptr, &room))) return rc;
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+        if ((rc = best_distinct_deliver(c, room, ty, cap, best_out, n_best, n_candidates, n_examined, n_duplicates, &why))) ctx->err = why;
+        return rc;
+    });
+}
+
+extern "C" int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* rows_dev, const void* entropy_dev,
+                                                      const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best,
+                                                      uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, void* status_dev, void* stream) {
+    if (!ctx || !round_dev || !rows_dev || !entropy_dev || !floor32 || !n_best || !n_candidates || !n_examined || !n_duplicates || !status_dev ||
+        (cap && !best_out))
+        return BBP_ERR_BAD_ARG;
+    *n_best = *n_candidates = *n_examined = *n_duplicates = 0;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_round_best_distinct_dev");
+    bool done;
+    if (int32_t rc = best_screen(ctx, "bbp_verify_round_best_distinct_dev", N, B, &done)) return rc;
+    if (done) return BBP_OK;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        return best_run_dev_distinct(ctx, N, (const u8*)round_dev, B, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, K, tranche, cap, best_out, n_best,
+                                     n_candidates, n_examined, n_duplicates, (int32_t*)status_dev, pick_stream(ctx, stream));
+    });
+}
+
 extern "C" int32_t bbp_set_prove_check(bbp_ctx* ctx, int32_t on) {
     if (!ctx) return BBP_ERR_BAD_ARG;
     for (bbp_ctx* m : ctx->members) bbp_set_prove_check(m, on);

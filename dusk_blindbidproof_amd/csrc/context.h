@@ -211,6 +211,8 @@ struct bbp_ctx {
     // candidate and winner records, statuses, one tranche's selection and verdicts on the device, a pinned mirror of what travels, and
     // -- the _dev form only -- the gathered rows of one tranche with their entropy rows.  All PUBLIC (secret_map.h), all grow on demand
     // (bbp_reserve does not size them); best_mu serialises the calls that use them, and is taken BEFORE the context lock.
+    // The one-per-bidder calls (bbp_verify_round_best_distinct, ...) use the same allocations: BestDistinctLayout puts the rows' z_img,
+    // the identity table and three counters behind BestLayout's state -- public for the same reason: what any verifier is handed.
     std::mutex best_mu;
     bbp::DevBuf best_dev, best_rows;
     void* best_h = nullptr;

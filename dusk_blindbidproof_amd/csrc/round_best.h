@@ -9,6 +9,13 @@
 //   k_best_pairs    (key, index) of the selected winners, for the host to put in rank order
 // The selection itself is round_select.h's, unchanged: over the candidate records with K = the tranche size, then once over the
 // winners' records with the call's K.
+// One per bidder (bbp_verify_round_best_distinct, its _dev form, bbp_debug_round_best_distinct): the same calls with at most one winner
+// per z_img.  Rules: round_best_distinct_host (tests/round_best_distinct_check.cpp, tests/test_gpu_round_best_distinct.py); on top of
+// the kernels above:
+//   k_best_ids      one lane per row: the 32 z_img bytes -> id[i], 8 words
+//   k_best_settle   a tranche's OK rows enter the identity table; per identity the first row in candidate order stays
+//   k_best_holders  the winner record of a tranche's OK row is open only when the row holds its identity
+//   k_best_drop     live candidates of a settled identity leave with BBP_ROW_DUPLICATE, unverified
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -134,6 +141,164 @@ struct BestRows {
     }
 };
 
+// ---- one per bidder (bbp_verify_round_best_distinct, its _dev form, bbp_debug_round_best_distinct; include/bbp.h "Best proofs of a
+// round, one per bidder") --------------------------------------------------------------------------------------------------------------
+// id[i] is the 32 raw z_img bytes of row i as 8 little-endian words; identities are compared as BYTES.  That is exact for every row that
+// can settle an identity: the verifier refuses a row whose z_img is not canonical with BBP_ERR_FORMAT (k_vparse, verifier_mixed.inc: the
+// parse of the row's scalars sets the format bit for any of them >= l) and so never reports BBP_OK for it; among canonical encodings
+// equal values are equal bytes.  tests/test_gpu_round_best_distinct.py holds it end to end (a row carrying z_img + l).
+//
+// The identity table: open addressing over row indices, 2^s slots, empty = BEST_EMPTY, linear probing that wraps.  A slot, once claimed,
+// keeps its identity for the rest of the call and holds the identity's holder so far: the first OK row in candidate order among those
+// inserted.  Hash, probe step, compare, insert and lookup are BBP_HD, so the host runs what the kernels run; only the compare-and-swap
+// differs (best_cas).  Every loop is bounded; a bound that is reached raises a bit of the flag word and the call ends BBP_ERR_INTERNAL.
+constexpr u32 BEST_EMPTY = 0xffffffffu;
+constexpr u32 BEST_TABLE_LOG2_MAX = 21;  // 2^21 slots >= 2 BBP_SELECT_MAX_BIDS: 8 MB
+enum : u32 { BEST_FLAG_PROBE = 1, BEST_FLAG_REPLACE = 2 };
+// the extra counters of a call, one word each
+enum : u32 { BEST_D_SETTLED = 0, BEST_D_DUPLICATES = 1, BEST_D_FLAG = 2, BEST_D_WORDS = 3 };
+
+// the least s with 2^s >= 2 B: sized from B alone
+BBP_HD u32 best_table_log2(u32 B) {
+    u32 s = 1;
+    while (s < BEST_TABLE_LOG2_MAX && (1ull << s) < 2ull * B) s++;
+    return s;
+}
+// all eight words decide the slot (FNV-1a over the words, then a finaliser that brings the high bits down: the slot is the low bits)
+BBP_HD u32 best_id_hash(const u32 id[8]) {
+    u32 h = 0x811c9dc5u;
+    for (int w = 0; w < 8; w++) h = (h ^ id[w]) * 0x01000193u;
+    h ^= h >> 15, h *= 0x2c1b3c6du, h ^= h >> 12, h *= 0x297a2d39u, h ^= h >> 15;
+    return h;
+}
+BBP_HD u32 best_probe_next(u32 p, u32 mask) { return (p + 1) & mask; }
+BBP_HD bool best_id_equal(const u32* a, const u32* b) {
+    u32 d = 0;
+    for (int w = 0; w < 8; w++) d |= a[w] ^ b[w];
+    return d == 0;
+}
+// a before b in the candidate order, keys at any stride (B x 8 words: stride 8; the selection's records: RS_WORDS, from RS_Q)
+BBP_HD bool best_before_at(const u32* keys, u32 stride, u32 a, u32 b) {
+    const int c = rs_cmp_top(keys + (size_t)stride * a, keys + (size_t)stride * b, 32);
+    return c ? c > 0 : a < b;
+}
+// *p == expect ? (*p = v, expect) : *p -- atomic on the device, plain on the host (which runs its rows one after the other)
+BBP_HD u32 best_cas(u32* p, u32 expect, u32 v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return atomicCAS(p, expect, v);
+#else
+    const u32 old = *p;
+    if (old == expect) *p = v;
+    return old;
+#endif
+}
+BBP_HD void best_flag_raise(u32* flag, u32 bit) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    atomicOr(flag, bit);
+#else
+    *flag |= bit;
+#endif
+}
+
+// Row i (OK) enters the table.  Returns 1 when it claimed an empty slot (a new identity is settled), else 0.  At a slot of its own identity
+// the row that comes first in candidate order stays: the holder is a minimum under a total order, whichever insert ran first.  At most
+// `slots` probe steps and `max_replace` exchanges (each failed exchange means another row of the identity, earlier in the order, got in).
+BBP_HD u32 best_table_insert(u32* table, u32 mask, const u32* ids, const u32* keys, u32 kstride, u32 i, u32 max_replace, u32* flag) {
+    const u32* id = ids + 8 * (size_t)i;
+    u32 p = best_id_hash(id) & mask;
+    for (u32 step = 0; step <= mask; step++, p = best_probe_next(p, mask)) {
+        u32 cur = best_cas(&table[p], BEST_EMPTY, i);
+        if (cur == BEST_EMPTY) return 1;
+        if (!best_id_equal(ids + 8 * (size_t)cur, id)) continue;
+        for (u32 r = 0; r <= max_replace; r++) {
+            if (!best_before_at(keys, kstride, i, cur)) return 0;
+            const u32 old = best_cas(&table[p], cur, i);
+            if (old == cur) return 0;
+            cur = old;  // (a slot keeps its identity: still a row of this one)
+        }
+        best_flag_raise(flag, BEST_FLAG_REPLACE);
+        return 0;
+    }
+    best_flag_raise(flag, BEST_FLAG_PROBE);
+    return 0;
+}
+// the holder of identity `id`, or BEST_EMPTY: the walk ends at the first empty slot, after `slots` steps at the latest
+BBP_HD u32 best_table_find(const u32* table, u32 mask, const u32* ids, const u32* id, u32* flag) {
+    u32 p = best_id_hash(id) & mask;
+    for (u32 step = 0; step <= mask; step++, p = best_probe_next(p, mask)) {
+        const u32 cur = table[p];
+        if (cur == BEST_EMPTY) return BEST_EMPTY;
+        if (best_id_equal(ids + 8 * (size_t)cur, id)) return cur;
+    }
+    best_flag_raise(flag, BEST_FLAG_PROBE);
+    return BEST_EMPTY;
+}
+
+// The rules, one per bidder.  As round_best_host, plus ids (B x 8 words) and n_duplicates.  An identity is settled once a row carrying it
+// has verified OK; its holder is the first such row in candidate order.  Tranche t is the next min(T_t, live) live candidates; all are
+// verified and keep their true status.  Stop after the first tranche that leaves >= K identities settled (K > 0) or when no live
+// candidate is left; otherwise every live candidate of a settled identity becomes BBP_ROW_DUPLICATE and leaves, before the next tranche.
+inline void round_best_distinct_host(u32 B, const u32* keys, const u32* ids, const int32_t* verdicts, const u32* floor, u32 K, u32 tranche, u32 cap,
+                                     u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status) {
+    std::vector<u32> live, holders;
+    for (u32 i = 0; i < B; i++) {
+        const int32_t s = best_screen_key(keys + 8 * (size_t)i, floor);
+        status[i] = s == BBP_ERR_FORMAT ? (int32_t)BBP_ERR_FORMAT : (int32_t)BBP_ROW_SKIPPED;
+        if (s == BBP_OK) live.push_back(i);
+    }
+    std::sort(live.begin(), live.end(), [&](u32 a, u32 b) { return best_before(keys, a, b); });
+    auto settled = [&](u32 i) {
+        for (u32 h : holders)
+            if (best_id_equal(ids + 8 * (size_t)h, ids + 8 * (size_t)i)) return true;
+        return false;
+    };
+    const u32 nc = (u32)live.size(), T0 = best_tranche0(K, tranche, nc);
+    u32 examined = 0, dups = 0;
+    for (u32 t = 0; !live.empty(); t++) {
+        const u32 n = best_tranche_rows(T0, t, (u32)live.size());
+        for (u32 j = 0; j < n; j++) {
+            const u32 i = live[j];
+            status[i] = verdicts[i];
+            if (verdicts[i] == BBP_OK && !settled(i)) holders.push_back(i);  // (candidate order: the first OK row of an identity)
+        }
+        live.erase(live.begin(), live.begin() + n);
+        examined += n;
+        if (K && holders.size() >= K) break;
+        std::vector<u32> keep;
+        for (u32 i : live) {
+            if (settled(i))
+                status[i] = BBP_ROW_DUPLICATE, dups++;
+            else
+                keep.push_back(i);
+        }
+        live.swap(keep);
+    }
+    const u32 nb = K && holders.size() > K ? K : (u32)holders.size();
+    for (u32 j = 0; j < nb && j < cap; j++) best_out[j] = holders[j];
+    *n_best = nb, *n_candidates = nc, *n_examined = examined, *n_duplicates = dups;
+}
+
+// The extra state of a one-per-bidder call, behind the state BestLayout(B, false) describes (same allocations: the context's best_dev and
+// its pinned mirror): the three counters, the ids, the table, and -- the host forms -- the staged score || z_img bytes, 64 per row.
+struct BestDistinctLayout {
+    u32 log2, slots;
+    size_t dctr, ids, table, kid, bytes;
+    size_t h_dctr, h_kid, h_bytes;
+    BestDistinctLayout(const BestLayout& L, u32 B, u32 table_log2, bool host_rows) {
+        const size_t b = B;
+        log2 = table_log2 ? table_log2 : best_table_log2(B);
+        slots = 1u << log2;
+        dctr = L.bytes;
+        ids = dctr + 256;
+        table = ids + align256(32 * b);
+        kid = table + align256(4 * (size_t)slots);
+        bytes = kid + (host_rows ? align256(64 * b) : 0);
+        h_dctr = L.h_bytes;
+        h_kid = h_dctr + 256;
+        h_bytes = h_kid + (host_rows ? align256(64 * b) : 0);
+    }
+};
+
 #ifdef __HIPCC__
 // One lane per row, 64-lane workgroups.  The key is read byte by byte at base + i stride + off: the _dev form's stride 1313 + 32 N is
 // odd, so every alignment occurs (the host forms: stride 32, offset 0).  Writes the candidate record (BBP_OK for a candidate), the
@@ -224,6 +389,59 @@ __global__ void __launch_bounds__(BEST_T) k_best_pairs(u32 cap, const u32* __res
 #pragma unroll
     for (int w = 0; w < 8; w++) p[w] = v[RS_Q + w];
     p[8] = i;
+}
+
+// ---- one per bidder ------------------------------------------------------------------------------------------------------------------
+// k_best_keys' sibling, launched beside it: id[i], the 32 bytes at base + i stride + off read byte by byte (any alignment), as 8 words.
+__global__ void __launch_bounds__(BEST_T) k_best_ids(u32 B, const u8* __restrict__ base, size_t stride, size_t off, u32* __restrict__ ids) {
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B) return;
+    const u8* p = base + stride * (size_t)i + off;
+    u32* d = ids + 8 * (size_t)i;
+#pragma unroll
+    for (int w = 0; w < 8; w++) d[w] = rb_le32(p + 4 * w);
+}
+
+// After a tranche's mark, one lane per row of the tranche: an OK row enters the identity table (best_table_insert: no lane waits for
+// another; the loops are bounded by the table's size and by the tranche's).  dctr[BEST_D_SETTLED] += the slots claimed from empty, one
+// addition per wave.  recs: the candidate records, whose keys order the rows.
+__global__ void __launch_bounds__(BEST_T) k_best_settle(u32 n, const u32* __restrict__ sel, const u32* __restrict__ counts, const int32_t* __restrict__ tstat,
+                                                        const u32* __restrict__ recs, const u32* __restrict__ ids, u32* table, u32 mask, u32* dctr) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    bool claimed = false;
+    if (j < n && j < counts[0] && tstat[j] == BBP_OK)
+        claimed = best_table_insert(table, mask, ids, recs + RS_Q, RS_WORDS, sel[j], n, &dctr[BEST_D_FLAG]) != 0;
+    const unsigned long long bc = __ballot(claimed);
+    if ((threadIdx.x & 63) == 0 && bc) atomicAdd(&dctr[BEST_D_SETTLED], (u32)__popcll(bc));
+}
+
+// A launch of its own behind k_best_settle (the table is final for this tranche), one lane per row of the tranche: the winner record of
+// an OK row is open exactly when the row is its identity's holder.  Only the current tranche needs it: a later row never displaces a
+// holder, because rows of a settled identity leave (k_best_drop) before the next selection.
+__global__ void __launch_bounds__(BEST_T) k_best_holders(u32 n, const u32* __restrict__ sel, const u32* __restrict__ counts, const int32_t* __restrict__ tstat,
+                                                         const u32* __restrict__ ids, const u32* __restrict__ table, u32 mask, u32* __restrict__ win, u32* dctr) {
+    const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n || j >= counts[0] || tstat[j] != BBP_OK) return;
+    const u32 i = sel[j];
+    const bool holder = best_table_find(table, mask, ids, ids + 8 * (size_t)i, &dctr[BEST_D_FLAG]) == i;
+    win[(size_t)RS_WORDS * i + RS_STATUS] = holder ? (u32)BBP_OK : BEST_OUT;
+}
+
+// Before each further selection, one lane per row: a candidate record that is still a member and whose identity is settled leaves with
+// BBP_ROW_DUPLICATE; dctr[BEST_D_DUPLICATES] += those rows, one addition per wave.  Enqueued behind k_best_holders, before the host has
+// read the count of settled identities: when the call stops here (K > 0 identities settled -- written by an earlier launch, every lane
+// reads the same) the launch does nothing, so no drop pass runs after the last tranche.
+__global__ void __launch_bounds__(BEST_T) k_best_drop(u32 B, u32 K, u32* __restrict__ recs, const u32* __restrict__ ids, const u32* __restrict__ table, u32 mask,
+                                                      int32_t* __restrict__ status, u32* dctr) {
+    if (K && dctr[BEST_D_SETTLED] >= K) return;
+    const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
+    bool dup = false;
+    if (i < B && recs[(size_t)RS_WORDS * i + RS_STATUS] == (u32)BBP_OK) {
+        dup = best_table_find(table, mask, ids, ids + 8 * (size_t)i, &dctr[BEST_D_FLAG]) != BEST_EMPTY;
+        if (dup) status[i] = BBP_ROW_DUPLICATE, recs[(size_t)RS_WORDS * i + RS_STATUS] = BEST_OUT;
+    }
+    const unsigned long long bd = __ballot(dup);
+    if ((threadIdx.x & 63) == 0 && bd) atomicAdd(&dctr[BEST_D_DUPLICATES], (u32)__popcll(bd));
 }
 #endif
 

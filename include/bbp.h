@@ -81,10 +81,12 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *   bbp_witness_batch, bbp_get_generator, bbp_get_mimc_constant, bbp_ubench   served by member 0
  *   bbp_prove_round_select  scoring and selection served by member 0, the selected bids proved as bbp_prove_round on the pool
  *   bbp_verify_round_best   keys, selection and marks served by member 0, every tranche verified as bbp_verify_rounds_aggregated on the pool
+ *   bbp_verify_round_best_distinct   the same: keys, identities, selection and marks on member 0, tranches verified on the pool
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
- * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_debug_round_best, bbp_set_profiling /
+ * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_debug_round_best,
+ * bbp_debug_round_best_distinct, bbp_set_profiling /
  * bbp_last_timings; the stream getters return NULL. */
 int32_t bbp_init_all(bbp_ctx** out);
 int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp_ctx** out);
@@ -423,6 +425,49 @@ int32_t bbp_verify_round_best_dev(bbp_ctx* ctx, uint32_t N, const void* round_de
 int32_t bbp_debug_round_best(bbp_ctx* ctx, uint32_t B, const uint8_t* keys, const int32_t* verdicts, const uint8_t floor32[32], uint32_t K,
                              uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined,
                              int32_t* status);
+
+/* Best proofs of a round, one per bidder.  z_img = mimc(seed, mimc(k, 0)) is the only per-bidder value a verifier sees: two valid rows
+ * of one round with equal z_img come from the same secret k.  The calls above treat every row as a bidder of its own, so with K > 1 a
+ * proof that was sent twice -- the same bytes, or the same bid proved again under fresh blindings -- takes two places and hides the real
+ * runners-up.  These calls return at most one row per z_img, and rows of an identity that already has a verified row leave the
+ * candidate set without being uploaded or verified.
+ * Inputs as bbp_verify_round_best, plus id[i]: the 32 raw z_img bytes of row i.  Identities are compared as BYTES; that is exact for
+ * every row that can win, because a row whose z_img is not canonical gets BBP_ERR_FORMAT from the verifier and never BBP_OK.
+ *   key, screening, order, n_candidates, T_0, T_t    as bbp_verify_round_best
+ *   settled       an identity is settled once a row carrying it has verified BBP_OK; its holder is the first such row in candidate order
+ *   tranches      tranche t is the next min(T_t, live) LIVE candidates in order; every one is verified and its status[i] is exactly what
+ *                 bbp_verify_rounds reports.  Rows of one identity inside one tranche are all verified and keep their true status; only
+ *                 the first OK one in candidate order becomes holder
+ *   stopping      after the first tranche that leaves at least K identities settled (K > 0), or when no live candidate is left
+ *   duplicates    otherwise, before the next tranche, every live candidate whose id is settled gets BBP_ROW_DUPLICATE ("could not have
+ *                 entered the result; not verified"; not a bbp_status) and leaves the candidate set; n_duplicates counts these rows.
+ *                 Once the call has stopped, rows never reached keep BBP_ROW_SKIPPED: no drop pass runs after the last tranche.  A
+ *                 forged row that borrows a victim's z_img under a higher claimed score fails verification and settles nothing: the
+ *                 victim's row stays live
+ *   best          the holders in candidate order, the first K of them (all when K == 0); n_best is the true length, best_out receives
+ *                 min(n_best, cap) entries
+ * n_examined + n_duplicates <= n_candidates; the bound on the tranches of bbp_verify_round_best holds; which rows are examined depends
+ * only on the inputs and `tranche`, never on timing.
+ * Argument screening and its order, the pool (the host form is accepted: state on member 0, tranches verified by the pool; the _dev form
+ * and the hook are refused), the serialisation of calls on one context, the synchronisation points of the _dev form (one more per
+ * tranche in the host form: the count of settled identities decides whether another tranche runs) and "bbp_reserve does not size the
+ * state" are those of the three calls above.  n_duplicates is a required pointer.
+ * The host form uploads 64 bytes per row, score || z_img (adjacent in a row: one gather per row); a tranche's rows come from the
+ * caller's memory exactly as above, and a duplicate row never crosses PCIe.  The _dev form reads both fields byte by byte at any
+ * alignment.
+ * bbp_debug_round_best_distinct, test hook: as bbp_debug_round_best, plus ids (B x 32 bytes, any values) and table_log2: 0 for the call's
+ * own sizing of the identity table (the least 2^s >= 2 B slots), or an explicit size of 2^table_log2 slots.  BBP_ERR_BAD_ARG, nothing
+ * launched, also when table_log2 > 21, or when table_log2 > 0 and 2^table_log2 is not greater than the number of BBP_OK verdicts. */
+#define BBP_ROW_DUPLICATE (-2)
+int32_t bbp_verify_round_best_distinct(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* rows, const uint8_t floor32[32],
+                                       uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates,
+                                       uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status);
+int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, const void* round_dev, uint32_t B, const void* rows_dev, const void* entropy_dev,
+                                           const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best,
+                                           uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, void* status_dev, void* stream);
+int32_t bbp_debug_round_best_distinct(bbp_ctx* ctx, uint32_t B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts,
+                                      const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t table_log2, uint32_t* best_out,
+                                      uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.

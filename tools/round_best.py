@@ -9,6 +9,15 @@ One JSON line per cell, to stdout and to --out (default profiles/r19_round_best.
           uploaded by the host forms, A / B.
   sweep   tranche in {16, 64, 256, 1024} on the honest and the 25 % traffic at B = 8192, host form: what picks BBP_BEST_TRANCHE_DEFAULT.
 
+  --distinct OUT   instead of the above: bbp_verify_round_best_distinct ("Best proofs of a round, one per bidder") at N = 8 / 202,
+          B = 8192, K = 4, default tranche, into OUT (profiles/r20_round_best_distinct.jsonl).  Traffic: (a) every bidder once at the top,
+          the rest of the rows claiming scores below them; (b) a flood: the top bidder's row 8000 times (byte-equal), the others once;
+          (c) the flood with the top 1 % by claimed score forged.  Arms: the new call (host, dev), the existing call (host, dev: under a
+          flood its answer holds one bidder K times -- here for cost only), bbp_verify_rounds_aggregated over everything with a
+          de-duplicating pick on the host.  Rows examined and dropped are asserted equal to the model of
+          tests/round_best_distinct_cases.py on the verdicts of the third arm; the tranche count is the model's.  Also traffic (a)
+          with K = 1, new call against existing call in the same run.
+
 Rows are 64 proved bids of the round repeated (byte-equal rows do occur in the protocol too); arms alternate in one process; every figure
 is the best of --calls calls, taken --runs times after a warm-up: median and range."""
 import argparse
@@ -131,14 +140,158 @@ def timed(arms, names, args):
     return {name: stats(v) for name, v in runs.items()}
 
 
+def model_tranches(dc, keys, ids, verdicts, K, tranche):
+    """the number of tranches the model of tests/round_best_distinct_cases.py runs (its loop, counting)"""
+    live = sorted(range(len(keys)), key=lambda i: (-keys[i], i))
+    T, settled, t = (max(tranche or 16, K) if K else len(live)), set(), 0
+    while live:
+        batch, live, T, t = live[:T], live[T:], 2 * T, t + 1
+        settled |= {ids[i] for i in batch if verdicts[i] == 0}
+        if K and len(settled) >= K:
+            break
+        live = [i for i in live if ids[i] not in settled]
+    return t
+
+
+def distinct_traffic(bbp, N, B, base_rows, kind):
+    """B rows as a bytearray: one row per bidder of base_rows (by z_img), then what `kind` says, then rows that claim scores below all"""
+    row = bbp.round_row_size(N)
+    key_off = bbp.record_size(N)
+    seen, uniq = set(), []
+    for i in range(len(base_rows) // row):
+        r = base_rows[row * i:row * (i + 1)]
+        if r[-32:] not in seen:
+            seen.add(r[-32:])
+            uniq.append(r)
+    uniq.sort(key=lambda r: -int.from_bytes(r[key_off:key_off + 32], "little"))
+    rows = list(uniq)
+    if kind != "no_duplicates":
+        rows += [uniq[0]] * (8000 - 1)
+    n_real = len(rows)
+    for i in range(B - n_real):  # the rest: a bidder's row under a claimed score below every real one (fails if it is ever verified)
+        r = uniq[i % len(uniq)]
+        rows.append(r[:key_off] + (i + 1).to_bytes(32, "little") + r[key_off + 32:])
+    if kind == "flood_top_1pct_forged":
+        order = sorted(range(B), key=lambda i: (-int.from_bytes(rows[i][key_off:key_off + 32], "little"), i))
+        for i in order[:B // 100]:
+            b = bytearray(rows[i])
+            b[T_X] ^= 0x01
+            rows[i] = bytes(b)
+    keys = [int.from_bytes(r[key_off:key_off + 32], "little") for r in rows]
+    ids = [r[-32:] for r in rows]
+    return bytearray(b"".join(rows)), keys, ids
+
+
+def distinct_main(args):
+    import numpy as np
+    import torch
+    torch.cuda.init()
+    import dusk_blindbidproof_amd as bbp
+    from tests import prove_round_cases as rc
+    from tests import round_best_distinct_cases as dc
+    box = box_id()
+    os.makedirs(os.path.dirname(os.path.abspath(args.distinct)), exist_ok=True)
+    B = 8192
+    unit = "ms of host time per call, best of %d, %d runs after a warm-up" % (args.calls, args.runs)
+    with open(args.distinct, "w") as f:
+        def emit(rec):
+            rec.update(box=box, commit=args.commit)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        ctx = bbp.Context(0)
+        lib, h = bbp.lib, ctx.handle
+        try:
+            for N in (8, 202):
+                r = rc.honest(N, 64, tag=20)
+                base_rows, _t, st = ctx.prove_round(N, r.table, r.bid_bytes)
+                assert st == [0] * 64
+                row = bbp.round_row_size(N)
+                table = (ctypes.c_uint8 * len(r.table)).from_buffer_copy(r.table)
+                d_table = torch.frombuffer(bytearray(r.table), dtype=torch.uint8).cuda()
+                Ns = (ctypes.c_uint32 * 1)(N)
+                floor = (ctypes.c_uint8 * 32)()
+                stream = torch.cuda.Stream()
+                for kind, Ks in (("no_duplicates", (4, 1)), ("flood", (4,)), ("flood_top_1pct_forged", (4,))):
+                    rows, keys, ids = distinct_traffic(bbp, N, B, base_rows, kind)
+                    host = (ctypes.c_uint8 * len(rows)).from_buffer(rows)
+                    d_rows = torch.frombuffer(rows, dtype=torch.uint8).cuda()
+                    d_ent = torch.randint(0, 256, (32 * B,), dtype=torch.uint8, device="cuda")
+                    d_status = torch.zeros(4 * B, dtype=torch.uint8, device="cuda")
+                    status = (ctypes.c_int32 * B)()
+                    nfb = ctypes.c_uint32()
+                    rc_ = lib.bbp_verify_rounds_aggregated(h, 1, Ns, table, B, None, host, status, 0, ctypes.byref(nfb))
+                    assert rc_ == 0
+                    verdicts = list(status)
+                    for K in Ks:
+                        best = (ctypes.c_uint32 * K)()
+                        n = [ctypes.c_uint32() for _ in range(4)]
+                        p = [ctypes.byref(x) for x in n]
+
+                        def new_host():
+                            assert lib.bbp_verify_round_best_distinct(h, N, table, B, host, floor, K, 0, K, best, p[0], p[1], p[2], p[3], status) == 0
+                            return list(best)[:n[0].value], n[0].value, n[1].value, n[2].value, n[3].value
+
+                        def new_dev():
+                            assert lib.bbp_verify_round_best_distinct_dev(h, N, d_table.data_ptr(), B, d_rows.data_ptr(), d_ent.data_ptr(), floor, K, 0, K, best,
+                                                                          p[0], p[1], p[2], p[3], d_status.data_ptr(), stream.cuda_stream) == 0
+                            stream.synchronize()
+                            return list(best)[:n[0].value], n[0].value, n[1].value, n[2].value, n[3].value
+
+                        def old_host():
+                            assert lib.bbp_verify_round_best(h, N, table, B, host, floor, K, 0, K, best, p[0], p[1], p[2], status) == 0
+                            return list(best)[:n[0].value]
+
+                        def old_dev():
+                            assert lib.bbp_verify_round_best_dev(h, N, d_table.data_ptr(), B, d_rows.data_ptr(), d_ent.data_ptr(), floor, K, 0, K, best, p[0], p[1],
+                                                                 p[2], d_status.data_ptr(), stream.cuda_stream) == 0
+                            stream.synchronize()
+                            return list(best)[:n[0].value]
+
+                        def all_then_pick():
+                            assert lib.bbp_verify_rounds_aggregated(h, 1, Ns, table, B, None, host, status, 0, ctypes.byref(nfb)) == 0
+                            ok = np.nonzero(np.frombuffer(status, dtype="<i4") == 0)[0].tolist()
+                            ok.sort(key=lambda i: (-keys[i], i))
+                            seen, out = set(), []
+                            for i in ok:
+                                if ids[i] not in seen:
+                                    seen.add(ids[i])
+                                    out.append(i)
+                                    if len(out) == K:
+                                        break
+                            return out
+                        arms = {"distinct_host": new_host, "distinct_dev": new_dev, "existing_host": old_host, "existing_dev": old_dev,
+                                "all_then_dedup_pick_host": all_then_pick}
+                        want = dc.model(keys, ids, verdicts, 0, K, 0)
+                        assert new_host() == want[:5] and new_dev() == want[:5], (new_host(), want[:5])  # nothing here is tuned: the model predicts it
+                        assert all_then_pick() == want[0]
+                        old = old_host()
+                        rec = {"section": "distinct", "N": N, "B": B, "traffic": kind, "K": K, "tranche": bbp.BEST_TRANCHE_DEFAULT, "bidders": len(set(ids)),
+                               "rows_examined": want[3], "rows_dropped": want[4], "tranches": model_tranches(dc, keys, ids, verdicts, K, 0),
+                               "existing_call_distinct_bidders_in_best": len({ids[i] for i in old}), "unit": unit}
+                        rec.update(timed(arms, list(arms), args))
+                        for form in ("host", "dev"):
+                            a, b = rec["distinct_" + form], rec["existing_" + form]
+                            rec["distinct_over_existing_" + form] = round(a["median"] / b["median"], 4)
+                            rec["distinct_above_existing_range_by_ms_" + form] = round(max(0.0, a["median"] - b["max"]), 3)
+                        emit(rec)
+            assert ctx.health() == 0
+        finally:
+            ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--distinct", default="", metavar="OUT", help="measure bbp_verify_round_best_distinct instead, into OUT")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19_round_best.jsonl"))
     ap.add_argument("--commit", default="")
     ap.add_argument("--runs", type=int, default=5)
     ap.add_argument("--calls", type=int, default=2)
     ap.add_argument("--sections", default="cells,sweep")
     args = ap.parse_args()
+    if args.distinct:
+        return distinct_main(args)
     import numpy as np
     import torch
     torch.cuda.init()
