@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <chrono>
 #include <functional>
+#include <optional>
 #include <thread>
 
 #include "batch.h"
@@ -1399,37 +1400,68 @@ extern "C" int32_t bbp_debug_round_select(bbp_ctx* ctx, uint32_t B, const uint8_
 }
 
 // ---- best valid proofs of a round (include/bbp.h; rules and kernels: round_best.h) ----------------------------------------------------
-// The launch sequence of one call, on ONE device's context and one stream (context lock held by every step):
-//   open      the state reserved, ctr zeroed
-//   keys      k_best_keys: records, winners' records, initial statuses
+// The launch sequence of one call, on ONE device's context and one stream (context lock held by every step).  [..]: what the
+// one-per-bidder calls add -- the same calls, plus an identity table (BestDistinctLayout behind BestLayout(B, false), same allocations):
+//   open      the state reserved, ctr [and dctr] zeroed [the table emptied]
+//   keys      k_best_keys: records, winners' records, initial statuses [k_best_ids]
 //   per tranche   select (the candidates' records, K = the tranche's size; 0: all) -> counts, sel;  [the rows verified];  mark
-//   finish    select (the winners' records, the call's K), k_best_pairs, then ctr, counts and pairs into the pinned mirror
+//                 [k_best_settle, k_best_holders, k_best_drop (which does nothing once the call stops), then ctr and dctr into the
+//                 mirror: settled identities and dropped rows decide the next tranche]
+//   finish    select (the winners' records, the call's K), k_best_pairs, then ctr, counts and pairs [and dctr] into the pinned mirror
 struct BestCall {
     bbp_ctx* ctx;
-    u32 B;
-    BestLayout L;
+    u32 B, K;
     hipStream_t s;
+    BestLayout L;
+    std::optional<BestDistinctLayout> D;  // one per bidder only
     u8 *d = nullptr, *h = nullptr;
-    BestCall(bbp_ctx* c, u32 B_, bool host_keys, hipStream_t s_) : ctx(c), B(B_), L(B_, host_keys), s(s_) {}
+    // host_rows: a host form, which stages bytes of every row -- the 32 key bytes (in L), one per bidder score || z_img (in D)
+    BestCall(bbp_ctx* c, u32 B_, u32 K_, hipStream_t s_, bool host_rows, bool distinct, u32 table_log2 = 0)
+        : ctx(c), B(B_), K(K_), s(s_), L(B_, host_rows && !distinct) {
+        if (distinct) D.emplace(L, B_, table_log2, host_rows);
+    }
     u32* at(size_t off) const { return (u32*)(d + off); }
+    u32 mask() const { return D->slots - 1; }
+    size_t bytes() const { return D ? D->bytes : L.bytes; }
+    size_t h_bytes() const { return D ? D->h_bytes : L.h_bytes; }
+    size_t staged_row() const { return D ? 64 : 32; }
+    size_t staged() const { return D ? D->kid : L.keys; }
+    size_t h_staged() const { return D ? D->h_kid : L.h_keys; }
+    std::string family() const { return D ? "best proofs, one per bidder: " : "best valid proofs: "; }
 };
 static const RsFloor BEST_NO_FLOOR = {};  // k_best_keys has applied the floor: a record is a member by its status alone
+// where a call's results go (n_duplicates: the one-per-bidder calls, otherwise null)
+struct BestOut {
+    u32 cap;
+    u32 *best, *n_best, *n_candidates, *n_examined, *n_duplicates;
+};
 
 static int32_t best_open(BestCall& c) {
     bbp_ctx* ctx = c.ctx;
     int32_t rc;
-    if ((rc = dev_reserve(ctx, ctx->best_dev, c.L.bytes)) || (rc = pinned_reserve(ctx, ctx->best_h, ctx->best_h_cap, c.L.h_bytes))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->best_dev, c.bytes())) || (rc = pinned_reserve(ctx, ctx->best_h, ctx->best_h_cap, c.h_bytes()))) return rc;
     if (!ctx->ev_best) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_best, hipEventDisableTiming));
     c.d = (u8*)ctx->best_dev.p, c.h = (u8*)ctx->best_h;
     BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.L.ctr, 0, 16, c.s));
+    if (c.D) {
+        BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.D->dctr, 0, 16, c.s));
+        BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.D->table, 0xff, 4 * (size_t)c.D->slots, c.s));
+    }
     return BBP_OK;
 }
 
-// keys at base + i stride + off (device memory), status: B x int32 (device memory)
+// keys at base + i stride + off (device memory) [ids 32 bytes behind them: score || z_img are adjacent in a row], status: B x int32
+// (device memory)
 static int32_t best_keys_enqueue(const BestCall& c, const u8* base, size_t stride, size_t off, const uint8_t* floor32, int32_t* status) {
+    const dim3 grid((c.B + BEST_T - 1) / BEST_T), block(BEST_T);
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_best_keys, grid, block, 0, c.s, c.B, base, stride, off, rs_floor_load(floor32), c.at(c.L.recs), c.at(c.L.win), status);
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    if (!c.D) return BBP_OK;
     ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
-    hipLaunchKernelGGL(k_best_keys, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, base, stride, off, rs_floor_load(floor32), c.at(c.L.recs),
-                       c.at(c.L.win), status);
+    hipLaunchKernelGGL(k_best_ids, grid, block, 0, c.s, c.B, base, stride, off + 32, c.at(c.D->ids));
     BBP_HIP_TRY(c.ctx, hipGetLastError());
     return BBP_OK;
 }
@@ -1448,12 +1480,73 @@ static int32_t best_mark_enqueue(const BestCall& c, u32 n, const int32_t* tstat,
     return BBP_OK;
 }
 
-// the K best winners (K == 0: all): selection, pairs, and everything the host reads into the mirror.  *room: pairs fetched at most.
-static int32_t best_finish_enqueue(const BestCall& c, u32 K, const int32_t* status_to_fetch, u32* room) {
+// Behind the mark of a tranche of n rows, for a caller that decides from the device's counters whether another tranche runs: ctr into
+// the mirror.  [Before that: identities settled, holders' winner records opened, duplicates dropped unless the call stops here (`drop`:
+// false when the host knows that no live candidate is left); dctr into the mirror as well.]
+static int32_t best_counters_enqueue(const BestCall& c, u32 n, const int32_t* tstat, int32_t* status, bool drop) {
     bbp_ctx* ctx = c.ctx;
-    const u32 n = K && K < c.B ? K : c.B;
+    if (c.D) {
+        const u32 *sel = c.at(c.L.sel), *counts = c.at(c.L.counts), *ids = c.at(c.D->ids);
+        u32 *table = c.at(c.D->table), *dctr = c.at(c.D->dctr);
+        ScopedEvent ev(ctx, TAG_SELECT, c.s);
+        const dim3 grid((n + BEST_T - 1) / BEST_T), block(BEST_T);
+        hipLaunchKernelGGL(k_best_settle, grid, block, 0, c.s, n, sel, counts, tstat, (const u32*)c.at(c.L.recs), ids, table, c.mask(), dctr);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_best_holders, grid, block, 0, c.s, n, sel, counts, tstat, ids, (const u32*)table, c.mask(), c.at(c.L.win), dctr);
+        BBP_HIP_TRY(ctx, hipGetLastError());
+        if (drop) {
+            hipLaunchKernelGGL(k_best_drop, dim3((c.B + BEST_T - 1) / BEST_T), block, 0, c.s, c.B, c.K, c.at(c.L.recs), ids, (const u32*)table, c.mask(), status,
+                               dctr);
+            BBP_HIP_TRY(ctx, hipGetLastError());
+        }
+    }
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
+    if (c.D) BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.D->h_dctr, c.d + c.D->dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+
+// What a call knows between tranches, and the checks that hold it to the device's counters.  reached: the rows found valid [the
+// identities settled]; dups: [the rows dropped as duplicates] 0.
+struct BestTally {
+    u32 T0 = 0, nc = 0, examined = 0, reached = 0, dups = 0;
+    u32 live() const { return nc - examined - dups; }
+    bool stop(u32 K) const { return live() == 0 || (K && reached >= K); }
+    // the counters that arrived behind a tranche's mark, or with the finish: false (with *why) when they are not what the call counted
+    bool take(const BestCall& c, std::string* why) {
+        u32 ctr[2], d[BEST_D_WORDS] = {};
+        memcpy(ctr, c.h + c.L.h_ctr, 8);
+        if (c.D)
+            memcpy(d, c.h + c.D->h_dctr, sizeof d);
+        else
+            d[BEST_D_SETTLED] = ctr[1];  // every valid row counts
+        if (d[BEST_D_FLAG]) return *why = c.family() + "a bounded loop of the identity table ran out (flag " + std::to_string(d[BEST_D_FLAG]) + ")", false;
+        if (ctr[0] != examined || d[BEST_D_SETTLED] < reached || d[BEST_D_SETTLED] > ctr[1] || d[BEST_D_DUPLICATES] < dups ||
+            (unsigned long long)examined + d[BEST_D_DUPLICATES] > nc)
+            return *why = c.family() + "the device counted " + std::to_string(ctr[0]) + " rows examined, " + std::to_string(ctr[1]) + " valid, " +
+                          std::to_string(d[BEST_D_SETTLED]) + " reached and " + std::to_string(d[BEST_D_DUPLICATES]) + " rows dropped; the call examined " +
+                          std::to_string(examined) + " of " + std::to_string(nc) + " candidates and had reached " + std::to_string(reached),
+                   false;
+        reached = d[BEST_D_SETTLED], dups = d[BEST_D_DUPLICATES];
+        return true;
+    }
+};
+// the rows to ask tranche t's selection for.  Tranche 0: its size needs the candidate count, which that selection delivers (0: every
+// candidate); a later one: the host knows it
+static u32 best_tranche_ask(u32 K, u32 tranche, u32 B, const BestTally& ty, u32 t) {
+    return t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(ty.T0, t, ty.live());
+}
+// counts = {n, live} of the selection of tranche t against the call's tally
+static bool best_tranche_ok(const u32* counts, u32 t, u32 K, u32 tranche, BestTally& ty) {
+    if (t == 0) ty.nc = counts[1], ty.T0 = best_tranche0(K, tranche, ty.nc);
+    return counts[1] == ty.live() && counts[0] == best_tranche_rows(ty.T0, t, counts[1]);
+}
+
+// the K best winners (K == 0: all): selection, pairs, and everything the host reads into the mirror.  *room: pairs fetched at most.
+static int32_t best_finish_enqueue(const BestCall& c, const int32_t* status_to_fetch, u32* room) {
+    bbp_ctx* ctx = c.ctx;
+    const u32 n = c.K && c.K < c.B ? c.K : c.B;
     *room = n;
-    if (int32_t rc = select_kernels_enqueue(ctx, c.B, c.at(c.L.win), BEST_NO_FLOOR, K, n, c.at(c.L.sel), c.at(c.L.counts), c.d + c.L.state, c.s)) return rc;
+    if (int32_t rc = select_kernels_enqueue(ctx, c.B, c.at(c.L.win), BEST_NO_FLOOR, c.K, n, c.at(c.L.sel), c.at(c.L.counts), c.d + c.L.state, c.s)) return rc;
     {
         ScopedEvent ev(ctx, TAG_SELECT, c.s);
         hipLaunchKernelGGL(k_best_pairs, dim3((n + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, n, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
@@ -1464,98 +1557,116 @@ static int32_t best_finish_enqueue(const BestCall& c, u32 K, const int32_t* stat
     BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
     BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_pairs, c.d + c.L.pairs, 4 * (size_t)BEST_PAIR_WORDS * n, hipMemcpyDeviceToHost, c.s));
     if (status_to_fetch) BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_status, status_to_fetch, 4 * (size_t)c.B, hipMemcpyDeviceToHost, c.s));
+    if (c.D) BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.D->h_dctr, c.d + c.D->dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
     return BBP_OK;
 }
 
-// after the finish has arrived: the host's tally against the device's counters, then the outputs
-static int32_t best_deliver(const BestCall& c, u32 room, u32 examined, u32 valid, u32 n_candidates, u32 cap, u32* best_out, u32* n_best, u32* n_cand_out,
-                            u32* n_examined, std::string* why) {
-    u32 ctr[2], counts[2];
-    memcpy(ctr, c.h + c.L.h_ctr, 8);
+// after the finish has arrived: the call's tally against the device's counters, which the finish must not have moved [and against the
+// winners' records the last selection counted], then the outputs
+static int32_t best_deliver(const BestCall& c, u32 room, BestTally& t, const BestOut& o, std::string* why) {
+    const u32 reached = t.reached, dups = t.dups;
+    if (!t.take(c, why)) return BBP_ERR_INTERNAL;
+    u32 counts[2];
     memcpy(counts, c.h + c.L.h_counts, 8);
-    if (ctr[0] != examined || ctr[1] != valid || counts[0] > room) {
-        *why = "best valid proofs: the device marked " + std::to_string(ctr[0]) + " rows examined and " + std::to_string(ctr[1]) + " valid, the call counted " +
-               std::to_string(examined) + " and " + std::to_string(valid);
+    bool ok = t.reached == reached && t.dups == dups && counts[0] <= room;
+    if (c.D) ok = ok && counts[1] == reached && counts[0] == (c.K && c.K < reached ? c.K : reached);
+    if (!ok) {
+        *why = c.family() + std::to_string(counts[1]) + " winner records are open and " + std::to_string(counts[0]) + " selected (room for " +
+               std::to_string(room) + "); the device counted " + std::to_string(t.reached) + " reached and " + std::to_string(t.dups) +
+               " rows dropped, the call " + std::to_string(reached) + " and " + std::to_string(dups);
         return BBP_ERR_INTERNAL;
     }
-    best_rank_pairs(counts[0], (const u32*)(c.h + c.L.h_pairs), cap, best_out);
-    *n_best = counts[0], *n_cand_out = n_candidates, *n_examined = examined;
+    best_rank_pairs(counts[0], (const u32*)(c.h + c.L.h_pairs), o.cap, o.best);
+    *o.n_best = counts[0], *o.n_candidates = t.nc, *o.n_examined = t.examined;
+    if (o.n_duplicates) *o.n_duplicates = t.dups;
     return BBP_OK;
 }
 
-// The host forms on ONE device's context.  fill_keys(dst): the B x 32 key bytes into the pinned staging area; verdicts(n, sel, st): the
-// statuses of the tranche's rows sel[0..n) -- called with no lock of `dev` held (the host form verifies through the caller's handle).
+// The host forms on ONE device's context (c.ctx).  fill(dst): the B x c.staged_row() bytes into the pinned staging area; verdicts(n, sel,
+// st): the statuses of the tranche's rows sel[0..n) -- called with no lock of the device held (the host form verifies through the
+// caller's handle).  Every submission is enqueued under the context lock and waited for with the lock released: one per tranche and one
+// for the finish [two per tranche: for the selection, and for the counters behind the settle].
 template <class Fill, class Verdicts>
-static int32_t best_run_host(bbp_ctx* dev, u32 B, Fill&& fill_keys, Verdicts&& verdicts, const uint8_t* floor32, u32 K, u32 tranche, u32 cap, u32* best_out,
-                             u32* n_best, u32* n_candidates, u32* n_examined, int32_t* status) {
+static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, const uint8_t* floor32, u32 tranche, const BestOut& out, int32_t* status) {
+    bbp_ctx* const dev = c.ctx;
     std::lock_guard<std::mutex> call(dev->best_mu);
-    BestCall c(dev, B, true, dev->stream);
-    u32 T0 = 0, nc = 0, examined = 0, valid = 0, pending = 0, room = 0;
+    const u32 B = c.B, K = c.K;
+    BestTally ty;
     std::vector<int32_t> st;
-    bool more = true;
-    for (u32 t = 0;; t++) {
-        const bool finish = !more;
-        const u32 rows = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(T0, t, nc - examined);
-        const u32 room_sel = rows ? rows : B;
+    u32 pending = 0, room = 0;
+    auto fail = [&](const std::string& why, int32_t rc) {
+        api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
+        return rc;
+    };
+    auto submit = [&](auto&& enqueue) -> int32_t {
         int32_t rc = api_guard(dev, [&]() -> int32_t {
-            int32_t rc;
             BBP_HIP_TRY(dev, hipSetDevice(dev->device));
-            if (t == 0 && (rc = best_open(c))) return rc;
-            int32_t* dstatus = (int32_t*)c.at(c.L.status);  // (the state's base is known once it is open)
-            if (t == 0) {
-                fill_keys(c.h + c.L.h_keys);
-                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.keys, c.h + c.L.h_keys, 32 * (size_t)B, hipMemcpyHostToDevice, c.s));
-                if ((rc = best_keys_enqueue(c, c.d + c.L.keys, 32, 0, floor32, dstatus))) return rc;
-            }
-            if (pending) {  // the tranche just verified: its statuses up, the rows marked
-                memcpy(c.h + c.L.h_tstat, st.data(), 4 * (size_t)pending);
-                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.tstat, c.h + c.L.h_tstat, 4 * (size_t)pending, hipMemcpyHostToDevice, c.s));
-                if ((rc = best_mark_enqueue(c, pending, (const int32_t*)c.at(c.L.tstat), dstatus))) return rc;
-            }
-            if (finish) {
-                if ((rc = best_finish_enqueue(c, K, dstatus, &room))) return rc;
-            } else {
-                if ((rc = best_select_enqueue(c, rows))) return rc;
-                BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 256 + 4 * (size_t)room_sel, hipMemcpyDeviceToHost, c.s));
-            }
+            if (int32_t r = enqueue()) return r;
             BBP_HIP_TRY(dev, hipEventRecord(dev->ev_best, c.s));
             return BBP_OK;
         });
         if (rc) return rc;
         const hipError_t e = wait_event_polling(dev->ev_best);
-        if (e != hipSuccess) {
-            api_guard(dev, [&]() -> int32_t { return dev->err = std::string("best valid proofs: ") + hipGetErrorString(e), BBP_ERR_DEVICE; });
-            return BBP_ERR_DEVICE;
-        }
+        return e == hipSuccess ? (int32_t)BBP_OK : fail(c.family() + hipGetErrorString(e), BBP_ERR_DEVICE);
+    };
+    auto dstatus = [&] { return (int32_t*)c.at(c.L.status); };  // (the state's base is known once it is open)
+    auto tstat = [&] { return (const int32_t*)c.at(c.L.tstat); };
+    auto mark = [&](u32 n) -> int32_t {  // the statuses of the tranche just verified up, its rows marked
+        memcpy(c.h + c.L.h_tstat, st.data(), 4 * (size_t)n);
+        BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.tstat, c.h + c.L.h_tstat, 4 * (size_t)n, hipMemcpyHostToDevice, c.s));
+        return best_mark_enqueue(c, n, tstat(), dstatus());
+    };
+    bool finish = false;
+    for (u32 t = 0;; t++) {
+        const u32 rows = best_tranche_ask(K, tranche, B, ty, t), room_sel = rows ? rows : B;
+        int32_t rc = submit([&]() -> int32_t {
+            int32_t r;
+            if (t == 0) {
+                if ((r = best_open(c))) return r;
+                fill(c.h + c.h_staged());
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.staged(), c.h + c.h_staged(), c.staged_row() * B, hipMemcpyHostToDevice, c.s));
+                if ((r = best_keys_enqueue(c, c.d + c.staged(), c.staged_row(), 0, floor32, dstatus()))) return r;
+            }
+            if (pending && (r = mark(pending))) return r;
+            if (finish) return best_finish_enqueue(c, dstatus(), &room);
+            if ((r = best_select_enqueue(c, rows))) return r;
+            BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 256 + 4 * (size_t)room_sel, hipMemcpyDeviceToHost, c.s));
+            return BBP_OK;
+        });
+        if (rc) return rc;
         if (finish) break;
         u32 counts[2];
         memcpy(counts, c.h + c.L.h_counts, 8);
-        if (t == 0) nc = counts[1], T0 = best_tranche0(K, tranche, nc);
+        if (!best_tranche_ok(counts, t, K, tranche, ty)) return fail(c.family() + "a tranche of unexpected size", BBP_ERR_INTERNAL);
         const u32 n = counts[0];
         pending = 0;
-        if (n != best_tranche_rows(T0, t, nc - examined)) {
-            api_guard(dev, [&]() -> int32_t { return dev->err = "best valid proofs: a tranche of unexpected size", BBP_ERR_INTERNAL; });
-            return BBP_ERR_INTERNAL;
-        }
         if (n) {
             st.assign(n, BBP_ERR_INTERNAL);
             if ((rc = verdicts(n, (const u32*)(c.h + c.L.h_sel), st.data()))) return rc;
-            examined += n, pending = n;
-            for (u32 j = 0; j < n; j++) valid += st[j] == BBP_OK;
+            ty.examined += n;
+            if (c.D) {  // the stop rule needs the device's counters: statuses, mark and settle at once, and a wait of their own
+                const bool drop = ty.live() > 0;
+                rc = submit([&]() -> int32_t {
+                    if (int32_t r = mark(n)) return r;
+                    return best_counters_enqueue(c, n, tstat(), dstatus(), drop);
+                });
+                if (rc) return rc;
+                std::string why;
+                if (!ty.take(c, &why)) return fail(why, BBP_ERR_INTERNAL);
+            } else {  // the host can count: the mark travels with the next submission
+                pending = n;
+                for (u32 j = 0; j < n; j++) ty.reached += st[j] == BBP_OK;
+            }
         }
-        more = n && examined < nc && !(K && valid >= K);
+        finish = n == 0 || ty.stop(K);
     }
     std::string why;
-    const int32_t rc = best_deliver(c, room, examined, valid, nc, cap, best_out, n_best, n_candidates, n_examined, &why);
-    if (rc) {
-        api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
-        return rc;
-    }
+    if (int32_t rc = best_deliver(c, room, ty, out, &why)) return fail(why, rc);
     memcpy(status, c.h + c.L.h_status, 4 * (size_t)B);
     return BBP_OK;
 }
 
-// screening shared by the three forms' numbers: N, then B (round_select.h round_select_screen: the same checks in the same order)
+// screening shared by every form's numbers: N, then B (round_select.h round_select_screen: the same checks in the same order)
 static int32_t best_screen(bbp_ctx* ctx, const char* what, u32 N, u32 B, bool* done) {
     const int32_t screened = round_select_screen(N, B, done);
     if (!screened) return BBP_OK;
@@ -1563,6 +1674,115 @@ static int32_t best_screen(bbp_ctx* ctx, const char* what, u32 N, u32 B, bool* d
         if (int32_t rc = check_n(ctx, N)) return rc;  // (names the list length)
         ctx->err = std::string(what) + ": more than BBP_SELECT_MAX_BIDS rows";
         return screened;
+    });
+}
+
+// The public host forms.  Staged: the score of every row [score || z_img: adjacent in a row, one gather per row]; a tranche comes from
+// the CALLER's memory, through the rounds verifier's own path.  On a pool, keys [identities], selection and marks are member 0's.
+static int32_t best_public_host(bbp_ctx* ctx, u32 N, const uint8_t* round, u32 B, const uint8_t* rows, const uint8_t* floor32, u32 K, u32 tranche,
+                                bool distinct, const BestOut& out, int32_t* status) {
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;
+        BestCall c(dev, B, K, dev->stream, true, distinct);
+        const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N), w = c.staged_row();
+        std::vector<uint8_t> picked;
+        auto fill = [&](u8* dst) {
+            for (u32 i = 0; i < B; i++) memcpy(dst + w * i, rows + rb * i + key_off, w);
+        };
+        auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
+            picked.resize(rb * n);
+            for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * sel[j], rb);
+            return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, round, nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
+        };
+        const int32_t rc = best_run_host(c, fill, verdicts, floor32, tranche, out, status);
+        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+        return rc;
+    });
+}
+
+// The test hooks: B, then the verdicts (*n_ok: how many are BBP_OK); a tranche's statuses are read from the caller's verdicts.
+static int32_t best_hook_refuse(bbp_ctx* ctx, const std::string& why) {
+    return api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
+}
+static int32_t best_hook_screen(bbp_ctx* ctx, const char* what, u32 B, const int32_t* verdicts, u32* n_ok) {
+    if (B == 0 || B > BBP_SELECT_MAX_BIDS) return best_hook_refuse(ctx, std::string(what) + ": B is 0 or above BBP_SELECT_MAX_BIDS");
+    *n_ok = 0;
+    for (u32 i = 0; i < B; i++) {
+        if (verdicts[i] != BBP_OK && verdicts[i] != BBP_ERR_VERIFY && verdicts[i] != BBP_ERR_FORMAT)
+            return best_hook_refuse(ctx, std::string(what) + ": a verdict is none of BBP_OK, BBP_ERR_VERIFY, BBP_ERR_FORMAT");
+        *n_ok += verdicts[i] == BBP_OK;
+    }
+    return BBP_OK;
+}
+static auto best_hook_read(const int32_t* verdicts) {
+    return [verdicts](u32 n, const u32* sel, int32_t* st) -> int32_t {
+        for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j]];
+        return BBP_OK;
+    };
+}
+
+// One tranche of n rows (in sel) on the device: the rows and their entropy rows packed, verified through the aggregated rounds path in
+// engine calls of at most BBP_HOST_CHUNK_VERIFY rows, as a host-pointer call's are (the packed rows of a part are read before the next
+// part's are written: one stream) -> tstat
+static int32_t best_verify_enqueue(const BestCall& c, u32 N, const u8* round_dev, const u8* rows_dev, const u8* entropy_dev, u32 n, int32_t* tstat) {
+    bbp_ctx* ctx = c.ctx;
+    const u32 rb = (u32)round_row_bytes(N), part = std::min(n, host_chunk_verify());
+    const BestRows R(part, N);
+    if (int32_t rc = dev_reserve(ctx, ctx->best_rows, R.bytes)) return rc;
+    u8* g = (u8*)ctx->best_rows.p;
+    for (u32 first = 0; first < n; first += part) {
+        const u32 m = std::min(part, n - first);
+        {
+            ScopedEvent ev(ctx, TAG_SELECT, c.s);
+            hipLaunchKernelGGL(k_best_gather, dim3(m), dim3(BEST_GATHER_T), 0, c.s, rb, first, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
+                               rows_dev, entropy_dev, g + R.rows, g + R.ent);
+            BBP_HIP_TRY(ctx, hipGetLastError());
+        }
+        if (int32_t rc = verify_batch_agg_dev(ctx, VerifyRows::of_rounds(m, 1, &N, round_dev, nullptr), BBP_AGG_GROUP_DEFAULT, g + R.rows, g + R.ent,
+                                              tstat + first, c.s, nullptr))
+            return rc;
+    }
+    return BBP_OK;
+}
+
+// The device forms, everything on c.s.  They synchronise c.s after the first selection (the candidate count), once per tranche (the
+// counters behind the mark [and the settle], which decide whether another tranche runs and size it) and once to deliver the results;
+// the context lock is held throughout, as by a _dev call that delivers n_fallback.
+static int32_t best_run_dev(BestCall& c, u32 N, const u8* round_dev, const u8* rows_dev, const u8* entropy_dev, const uint8_t* floor32, u32 tranche,
+                            const BestOut& out, int32_t* status) {
+    bbp_ctx* const ctx = c.ctx;
+    std::lock_guard<std::mutex> call(ctx->best_mu);
+    return api_guard(ctx, [&]() -> int32_t {
+        int32_t rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        if ((rc = best_open(c)) || (rc = best_keys_enqueue(c, rows_dev, round_row_bytes(N), proof_record_bytes(N), floor32, status))) return rc;
+        BestTally ty;
+        std::string why;
+        u32 room = 0;
+        for (u32 t = 0;; t++) {
+            u32 n = best_tranche_ask(c.K, tranche, c.B, ty, t);
+            if ((rc = best_select_enqueue(c, n))) return rc;
+            if (t == 0) {
+                BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
+                BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+                u32 counts[2];
+                memcpy(counts, c.h + c.L.h_counts, 8);
+                if (!best_tranche_ok(counts, 0, c.K, tranche, ty)) return ctx->err = c.family() + "a tranche of unexpected size", BBP_ERR_INTERNAL;
+                n = counts[0];
+            }
+            if (n == 0) break;
+            int32_t* tstat = (int32_t*)c.at(c.L.tstat);
+            if ((rc = best_verify_enqueue(c, N, round_dev, rows_dev, entropy_dev, n, tstat))) return rc;
+            ty.examined += n;
+            if ((rc = best_mark_enqueue(c, n, tstat, status)) || (rc = best_counters_enqueue(c, n, tstat, status, ty.live() > 0))) return rc;
+            BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));  // rows examined and OK [identities settled, rows dropped]
+            if (!ty.take(c, &why)) return ctx->err = why, BBP_ERR_INTERNAL;
+            if (ty.stop(c.K)) break;
+        }
+        if ((rc = best_finish_enqueue(c, nullptr, &room))) return rc;
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+        if ((rc = best_deliver(c, room, ty, out, &why))) ctx->err = why;
+        return rc;
     });
 }
 
@@ -1574,22 +1794,7 @@ extern "C" int32_t bbp_verify_round_best(bbp_ctx* ctx, uint32_t N, const uint8_t
     bool done;
     if (int32_t rc = best_screen(ctx, "bbp_verify_round_best", N, B, &done)) return rc;
     if (done) return BBP_OK;
-    return no_throw_ctx(ctx, [&]() -> int32_t {
-        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;  // keys, selection and marks: one device
-        const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
-        std::vector<uint8_t> picked;
-        auto fill = [&](u8* dst) {
-            for (u32 i = 0; i < B; i++) memcpy(dst + 32 * (size_t)i, rows + rb * i + key_off, 32);
-        };
-        auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // the tranche from the CALLER's memory, through the rounds verifier's own path
-            picked.resize(rb * n);
-            for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * sel[j], rb);
-            return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, round, nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
-        };
-        const int32_t rc = best_run_host(dev, B, fill, verdicts, floor32, K, tranche, cap, best_out, n_best, n_candidates, n_examined, status);
-        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
-        return rc;
-    });
+    return best_public_host(ctx, N, round, B, rows, floor32, K, tranche, false, BestOut{cap, best_out, n_best, n_candidates, n_examined, nullptr}, status);
 }
 
 // Test hook: the shipped key, selection, mark and ranking kernels on caller-made keys and verdicts.  Synchronises.
@@ -1599,82 +1804,11 @@ extern "C" int32_t bbp_debug_round_best(bbp_ctx* ctx, uint32_t B, const uint8_t*
     if (!ctx || !keys || !verdicts || !floor32 || !n_best || !n_candidates || !n_examined || !status || (cap && !best_out)) return BBP_ERR_BAD_ARG;
     if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_round_best");
     return no_throw_ctx(ctx, [&]() -> int32_t {
-        auto refuse = [&](const char* why) {
-            api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
-            return (int32_t)BBP_ERR_BAD_ARG;
-        };
-        if (B == 0 || B > BBP_SELECT_MAX_BIDS) return refuse("bbp_debug_round_best: B is 0 or above BBP_SELECT_MAX_BIDS");
-        for (u32 i = 0; i < B; i++)
-            if (verdicts[i] != BBP_OK && verdicts[i] != BBP_ERR_VERIFY && verdicts[i] != BBP_ERR_FORMAT)
-                return refuse("bbp_debug_round_best: a verdict is none of BBP_OK, BBP_ERR_VERIFY, BBP_ERR_FORMAT");
+        u32 n_ok;
+        if (int32_t rc = best_hook_screen(ctx, "bbp_debug_round_best", B, verdicts, &n_ok)) return rc;
         auto fill = [&](u8* dst) { memcpy(dst, keys, 32 * (size_t)B); };
-        auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
-            for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j]];
-            return BBP_OK;
-        };
-        return best_run_host(ctx, B, fill, read, floor32, K, tranche, cap, best_out, n_best, n_candidates, n_examined, status);
-    });
-}
-
-// The device form, everything on s.  It synchronises s after the first selection (the candidate count), once per tranche (the two
-// counters) and once to deliver the results; the context lock is held throughout, as by a _dev call that delivers n_fallback.
-static int32_t best_run_dev(bbp_ctx* ctx, u32 N, const u8* round_dev, u32 B, const u8* rows_dev, const u8* entropy_dev, const uint8_t* floor32, u32 K,
-                            u32 tranche, u32 cap, u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, int32_t* status, hipStream_t s) {
-    std::lock_guard<std::mutex> call(ctx->best_mu);
-    return api_guard(ctx, [&]() -> int32_t {
-        int32_t rc;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        BestCall c(ctx, B, false, s);
-        const u32 rb = (u32)round_row_bytes(N);
-        if ((rc = best_open(c)) || (rc = best_keys_enqueue(c, rows_dev, rb, proof_record_bytes(N), floor32, status))) return rc;
-        u32 T0 = 0, nc = 0, examined = 0, valid = 0, room = 0;
-        for (u32 t = 0;; t++) {
-            // tranche 0: its size needs the candidate count, which the selection delivers; a later one: the host knows it
-            u32 n = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(T0, t, nc - examined);
-            if ((rc = best_select_enqueue(c, n))) return rc;
-            if (t == 0) {
-                BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
-                BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
-                u32 counts[2];
-                memcpy(counts, c.h + c.L.h_counts, 8);
-                n = counts[0], nc = counts[1], T0 = best_tranche0(K, tranche, nc);
-                if (n != best_tranche_rows(T0, 0, nc)) return ctx->err = "best valid proofs: a tranche of unexpected size", BBP_ERR_INTERNAL;
-            }
-            if (n == 0) break;
-            // the tranche's rows and entropy rows, packed; verified through the aggregated rounds path in engine calls of at most
-            // BBP_HOST_CHUNK_VERIFY rows, as a host-pointer call's are (the packed rows of a part are read before the next part's are
-            // written: one stream); marked
-            const u32 part = std::min(n, host_chunk_verify());
-            const BestRows R(part, N);
-            if ((rc = dev_reserve(ctx, ctx->best_rows, R.bytes))) return rc;
-            u8* g = (u8*)ctx->best_rows.p;
-            int32_t* tstat = (int32_t*)c.at(c.L.tstat);
-            for (u32 first = 0; first < n; first += part) {
-                const u32 m = std::min(part, n - first);
-                {
-                    ScopedEvent ev(ctx, TAG_SELECT, c.s);
-                    hipLaunchKernelGGL(k_best_gather, dim3(m), dim3(BEST_GATHER_T), 0, c.s, rb, first, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
-                                       rows_dev, entropy_dev, g + R.rows, g + R.ent);
-                    BBP_HIP_TRY(ctx, hipGetLastError());
-                }
-                if ((rc = verify_batch_agg_dev(ctx, VerifyRows::of_rounds(m, 1, &N, round_dev, nullptr), BBP_AGG_GROUP_DEFAULT, g + R.rows, g + R.ent,
-                                               tstat + first, c.s, nullptr)))
-                    return rc;
-            }
-            if ((rc = best_mark_enqueue(c, n, tstat, status))) return rc;
-            BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
-            BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));  // the two counters: rows examined, rows OK
-            u32 ctr[2];
-            memcpy(ctr, c.h + c.L.h_ctr, 8);
-            examined += n, valid = ctr[1];
-            if (ctr[0] != examined) return ctx->err = "best valid proofs: the device's count of examined rows is not the call's", BBP_ERR_INTERNAL;
-            if (examined >= nc || (K && valid >= K)) break;
-        }
-        if ((rc = best_finish_enqueue(c, K, nullptr, &room))) return rc;
-        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
-        std::string why;
-        if ((rc = best_deliver(c, room, examined, valid, nc, cap, best_out, n_best, n_candidates, n_examined, &why))) ctx->err = why;
-        return rc;
+        BestCall c(ctx, B, K, ctx->stream, true, false);
+        return best_run_host(c, fill, best_hook_read(verdicts), floor32, tranche, BestOut{cap, best_out, n_best, n_candidates, n_examined, nullptr}, status);
     });
 }
 
@@ -1689,194 +1823,14 @@ extern "C" int32_t bbp_verify_round_best_dev(bbp_ctx* ctx, uint32_t N, const voi
     if (int32_t rc = best_screen(ctx, "bbp_verify_round_best_dev", N, B, &done)) return rc;
     if (done) return BBP_OK;
     return no_throw_ctx(ctx, [&]() -> int32_t {
-        return best_run_dev(ctx, N, (const u8*)round_dev, B, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, K, tranche, cap, best_out, n_best,
-                            n_candidates, n_examined, (int32_t*)status_dev, pick_stream(ctx, stream));
+        BestCall c(ctx, B, K, pick_stream(ctx, stream), false, false);
+        return best_run_dev(c, N, (const u8*)round_dev, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, tranche,
+                            BestOut{cap, best_out, n_best, n_candidates, n_examined, nullptr}, (int32_t*)status_dev);
     });
 }
 
 // ---- best proofs of a round, one per bidder (include/bbp.h; rules and kernels: round_best.h) ------------------------------------------
-// The launch sequence of one call, on ONE device's context and one stream:
-//   open      the state reserved (BestLayout(B, false) with BestDistinctLayout behind it), ctr and dctr zeroed, the table emptied
-//   keys      k_best_keys and k_best_ids
-//   per tranche   select -> counts, sel;  [the rows verified];  mark, k_best_settle, k_best_holders, k_best_drop (which does nothing once
-//                 the call stops), then ctr and dctr into the mirror: settled identities and dropped rows decide the next tranche
-//   finish    as the calls above, plus dctr
-struct BestDistinctCall : BestCall {
-    BestDistinctLayout D;
-    u32 K;
-    BestDistinctCall(bbp_ctx* c, u32 B_, u32 K_, u32 table_log2, bool host_rows, hipStream_t s_)
-        : BestCall(c, B_, false, s_), D(L, B_, table_log2, host_rows), K(K_) {}
-    u32 mask() const { return D.slots - 1; }
-};
-
-static int32_t best_distinct_open(BestDistinctCall& c) {
-    bbp_ctx* ctx = c.ctx;
-    int32_t rc;
-    if ((rc = dev_reserve(ctx, ctx->best_dev, c.D.bytes)) || (rc = pinned_reserve(ctx, ctx->best_h, ctx->best_h_cap, c.D.h_bytes))) return rc;
-    if (!ctx->ev_best) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_best, hipEventDisableTiming));
-    c.d = (u8*)ctx->best_dev.p, c.h = (u8*)ctx->best_h;
-    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.L.ctr, 0, 16, c.s));
-    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.D.dctr, 0, 16, c.s));
-    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + c.D.table, 0xff, 4 * (size_t)c.D.slots, c.s));
-    return BBP_OK;
-}
-
-// keys at base + i stride + off, ids 32 bytes behind them (score || z_img are adjacent in a row)
-static int32_t best_distinct_keys_enqueue(const BestDistinctCall& c, const u8* base, size_t stride, size_t off, const uint8_t* floor32, int32_t* status) {
-    if (int32_t rc = best_keys_enqueue(c, base, stride, off, floor32, status)) return rc;
-    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
-    hipLaunchKernelGGL(k_best_ids, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, base, stride, off + 32, c.at(c.D.ids));
-    BBP_HIP_TRY(c.ctx, hipGetLastError());
-    return BBP_OK;
-}
-
-// behind the mark of a tranche of n rows: identities settled, holders' winner records opened, duplicates dropped unless the call stops
-// here (`drop`: false when the host knows that no live candidate is left), the five counters into the mirror
-static int32_t best_settle_enqueue(const BestDistinctCall& c, u32 n, const int32_t* tstat, int32_t* status, bool drop) {
-    bbp_ctx* ctx = c.ctx;
-    const u32 *sel = c.at(c.L.sel), *counts = c.at(c.L.counts), *ids = c.at(c.D.ids);
-    u32 *table = c.at(c.D.table), *dctr = c.at(c.D.dctr);
-    {
-        ScopedEvent ev(ctx, TAG_SELECT, c.s);
-        const dim3 grid((n + BEST_T - 1) / BEST_T), block(BEST_T);
-        hipLaunchKernelGGL(k_best_settle, grid, block, 0, c.s, n, sel, counts, tstat, (const u32*)c.at(c.L.recs), ids, table, c.mask(), dctr);
-        BBP_HIP_TRY(ctx, hipGetLastError());
-        hipLaunchKernelGGL(k_best_holders, grid, block, 0, c.s, n, sel, counts, tstat, ids, (const u32*)table, c.mask(), c.at(c.L.win), dctr);
-        BBP_HIP_TRY(ctx, hipGetLastError());
-        if (drop) {
-            hipLaunchKernelGGL(k_best_drop, dim3((c.B + BEST_T - 1) / BEST_T), block, 0, c.s, c.B, c.K, c.at(c.L.recs), ids, (const u32*)table, c.mask(), status,
-                               dctr);
-            BBP_HIP_TRY(ctx, hipGetLastError());
-        }
-    }
-    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
-    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.D.h_dctr, c.d + c.D.dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
-    return BBP_OK;
-}
-
-// What a call knows between tranches, and the checks that hold it to the device's counters.
-struct BestDistinctTally {
-    u32 T0 = 0, nc = 0, examined = 0, settled = 0, dups = 0;
-    u32 live() const { return nc - examined - dups; }
-    // the counters that arrived behind tranche's settle: false (with *why) when they are not what the call counted
-    bool take(const BestDistinctCall& c, std::string* why) {
-        u32 ctr[2], d[BEST_D_WORDS];
-        memcpy(ctr, c.h + c.L.h_ctr, 8);
-        memcpy(d, c.h + c.D.h_dctr, sizeof d);
-        if (d[BEST_D_FLAG]) return *why = "best proofs, one per bidder: a bounded loop of the identity table ran out (flag " + std::to_string(d[BEST_D_FLAG]) + ")", false;
-        if (ctr[0] != examined || d[BEST_D_SETTLED] < settled || d[BEST_D_SETTLED] > ctr[1] || d[BEST_D_DUPLICATES] < dups ||
-            (unsigned long long)examined + d[BEST_D_DUPLICATES] > nc)
-            return *why = "best proofs, one per bidder: the device counted " + std::to_string(ctr[0]) + " rows examined, " + std::to_string(d[BEST_D_SETTLED]) +
-                          " identities settled and " + std::to_string(d[BEST_D_DUPLICATES]) + " rows dropped; the call examined " + std::to_string(examined) +
-                          " of " + std::to_string(nc) + " candidates",
-                   false;
-        settled = d[BEST_D_SETTLED], dups = d[BEST_D_DUPLICATES];
-        return true;
-    }
-    bool stop(u32 K) const { return live() == 0 || (K && settled >= K); }
-};
-
-static int32_t best_distinct_finish_enqueue(const BestDistinctCall& c, const int32_t* status_to_fetch, u32* room) {
-    if (int32_t rc = best_finish_enqueue(c, c.K, status_to_fetch, room)) return rc;
-    BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + c.D.h_dctr, c.d + c.D.dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
-    return BBP_OK;
-}
-
-// after the finish has arrived: examined, settled (against the winners' records the last selection counted) and duplicates, then the outputs
-static int32_t best_distinct_deliver(const BestDistinctCall& c, u32 room, BestDistinctTally& t, u32 cap, u32* best_out, u32* n_best, u32* n_candidates,
-                                     u32* n_examined, u32* n_duplicates, std::string* why) {
-    const u32 settled = t.settled, dups = t.dups;
-    if (!t.take(c, why)) return BBP_ERR_INTERNAL;
-    u32 counts[2];
-    memcpy(counts, c.h + c.L.h_counts, 8);
-    if (t.settled != settled || t.dups != dups || counts[1] != settled || counts[0] > room || counts[0] != (c.K && c.K < settled ? c.K : settled)) {
-        *why = "best proofs, one per bidder: " + std::to_string(counts[1]) + " winner records are open and " + std::to_string(counts[0]) + " selected for " +
-               std::to_string(settled) + " identities settled";
-        return BBP_ERR_INTERNAL;
-    }
-    best_rank_pairs(counts[0], (const u32*)(c.h + c.L.h_pairs), cap, best_out);
-    *n_best = counts[0], *n_candidates = t.nc, *n_examined = t.examined, *n_duplicates = t.dups;
-    return BBP_OK;
-}
-
-// counts = {n, live} of the selection of tranche t against the call's tally
-static bool best_distinct_tranche_ok(const u32* counts, u32 t, u32 K, u32 tranche, BestDistinctTally& ty) {
-    if (t == 0) ty.nc = counts[1], ty.T0 = best_tranche0(K, tranche, ty.nc);
-    return counts[1] == ty.live() && counts[0] == best_tranche_rows(ty.T0, t, counts[1]);
-}
-
-// The host forms on ONE device's context.  fill_rows(dst): the B x 64 bytes score || z_img into the pinned staging area; verdicts as in
-// best_run_host.  Two waits per tranche: for the selection, and for the counters behind the settle.
-template <class Fill, class Verdicts>
-static int32_t best_run_host_distinct(bbp_ctx* dev, u32 B, Fill&& fill_rows, Verdicts&& verdicts, const uint8_t* floor32, u32 K, u32 tranche, u32 cap,
-                                      u32 table_log2, u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status) {
-    std::lock_guard<std::mutex> call(dev->best_mu);
-    BestDistinctCall c(dev, B, K, table_log2, true, dev->stream);
-    BestDistinctTally ty;
-    std::vector<int32_t> st;
-    u32 room = 0;
-    auto fail = [&](const std::string& why, int32_t rc) {
-        api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
-        return rc;
-    };
-    // one submission under the context lock, then the wait for it with the lock released
-    auto submit = [&](auto&& enqueue) -> int32_t {
-        int32_t rc = api_guard(dev, [&]() -> int32_t {
-            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
-            if (int32_t r = enqueue()) return r;
-            BBP_HIP_TRY(dev, hipEventRecord(dev->ev_best, c.s));
-            return BBP_OK;
-        });
-        if (rc) return rc;
-        const hipError_t e = wait_event_polling(dev->ev_best);
-        return e == hipSuccess ? (int32_t)BBP_OK : fail(std::string("best proofs, one per bidder: ") + hipGetErrorString(e), BBP_ERR_DEVICE);
-    };
-    auto dstatus = [&] { return (int32_t*)c.at(c.L.status); };
-    for (u32 t = 0;; t++) {
-        const u32 rows = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(ty.T0, t, ty.live());
-        const u32 room_sel = rows ? rows : B;
-        int32_t rc = submit([&]() -> int32_t {
-            int32_t r;
-            if (t == 0) {
-                if ((r = best_distinct_open(c))) return r;
-                fill_rows(c.h + c.D.h_kid);
-                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.D.kid, c.h + c.D.h_kid, 64 * (size_t)B, hipMemcpyHostToDevice, c.s));
-                if ((r = best_distinct_keys_enqueue(c, c.d + c.D.kid, 64, 0, floor32, dstatus()))) return r;
-            }
-            if ((r = best_select_enqueue(c, rows))) return r;
-            BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 256 + 4 * (size_t)room_sel, hipMemcpyDeviceToHost, c.s));
-            return BBP_OK;
-        });
-        if (rc) return rc;
-        u32 counts[2];
-        memcpy(counts, c.h + c.L.h_counts, 8);
-        if (!best_distinct_tranche_ok(counts, t, K, tranche, ty)) return fail("best proofs, one per bidder: a tranche of unexpected size", BBP_ERR_INTERNAL);
-        const u32 n = counts[0];
-        if (n == 0) break;
-        st.assign(n, BBP_ERR_INTERNAL);
-        if ((rc = verdicts(n, (const u32*)(c.h + c.L.h_sel), st.data()))) return rc;
-        ty.examined += n;
-        const bool drop = ty.live() > 0;
-        rc = submit([&]() -> int32_t {  // the tranche's statuses up, the rows marked, identities settled
-            int32_t r;
-            memcpy(c.h + c.L.h_tstat, st.data(), 4 * (size_t)n);
-            BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.L.tstat, c.h + c.L.h_tstat, 4 * (size_t)n, hipMemcpyHostToDevice, c.s));
-            if ((r = best_mark_enqueue(c, n, (const int32_t*)c.at(c.L.tstat), dstatus()))) return r;
-            return best_settle_enqueue(c, n, (const int32_t*)c.at(c.L.tstat), dstatus(), drop);
-        });
-        if (rc) return rc;
-        std::string why;
-        if (!ty.take(c, &why)) return fail(why, BBP_ERR_INTERNAL);
-        if (ty.stop(K)) break;
-    }
-    int32_t rc = submit([&]() -> int32_t { return best_distinct_finish_enqueue(c, dstatus(), &room); });
-    if (rc) return rc;
-    std::string why;
-    if ((rc = best_distinct_deliver(c, room, ty, cap, best_out, n_best, n_candidates, n_examined, n_duplicates, &why))) return fail(why, rc);
-    memcpy(status, c.h + c.L.h_status, 4 * (size_t)B);
-    return BBP_OK;
-}
-
+// The calls above with an identity table: the same drivers over a BestCall that has one.
 extern "C" int32_t bbp_verify_round_best_distinct(bbp_ctx* ctx, uint32_t N, const uint8_t* round, uint32_t B, const uint8_t* rows, const uint8_t floor32[32],
                                                   uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates,
                                                   uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status) {
@@ -1885,23 +1839,7 @@ extern "C" int32_t bbp_verify_round_best_distinct(bbp_ctx* ctx, uint32_t N, cons
     bool done;
     if (int32_t rc = best_screen(ctx, "bbp_verify_round_best_distinct", N, B, &done)) return rc;
     if (done) return BBP_OK;
-    return no_throw_ctx(ctx, [&]() -> int32_t {
-        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;  // keys, identities, selection and marks: one device
-        const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
-        std::vector<uint8_t> picked;
-        auto fill = [&](u8* dst) {  // score || z_img: one gather per row
-            for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, rows + rb * i + key_off, 64);
-        };
-        auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // the tranche from the CALLER's memory, through the rounds verifier's own path
-            picked.resize(rb * n);
-            for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * sel[j], rb);
-            return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, round, nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
-        };
-        const int32_t rc =
-            best_run_host_distinct(dev, B, fill, verdicts, floor32, K, tranche, cap, 0, best_out, n_best, n_candidates, n_examined, n_duplicates, status);
-        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
-        return rc;
-    });
+    return best_public_host(ctx, N, round, B, rows, floor32, K, tranche, true, BestOut{cap, best_out, n_best, n_candidates, n_examined, n_duplicates}, status);
 }
 
 // Test hook: the shipped key, identity, selection, mark, settle, holder, drop and ranking kernels on caller-made keys, ids and verdicts.
@@ -1912,85 +1850,16 @@ extern "C" int32_t bbp_debug_round_best_distinct(bbp_ctx* ctx, uint32_t B, const
         return BBP_ERR_BAD_ARG;
     if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_round_best_distinct");
     return no_throw_ctx(ctx, [&]() -> int32_t {
-        auto refuse = [&](const char* why) {
-            api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
-            return (int32_t)BBP_ERR_BAD_ARG;
-        };
-        if (B == 0 || B > BBP_SELECT_MAX_BIDS) return refuse("bbp_debug_round_best_distinct: B is 0 or above BBP_SELECT_MAX_BIDS");
-        u32 n_ok = 0;
-        for (u32 i = 0; i < B; i++) {
-            if (verdicts[i] != BBP_OK && verdicts[i] != BBP_ERR_VERIFY && verdicts[i] != BBP_ERR_FORMAT)
-                return refuse("bbp_debug_round_best_distinct: a verdict is none of BBP_OK, BBP_ERR_VERIFY, BBP_ERR_FORMAT");
-            n_ok += verdicts[i] == BBP_OK;
-        }
+        u32 n_ok;
+        if (int32_t rc = best_hook_screen(ctx, "bbp_debug_round_best_distinct", B, verdicts, &n_ok)) return rc;
         if (table_log2 > BEST_TABLE_LOG2_MAX || (table_log2 && (1u << table_log2) <= n_ok))
-            return refuse("bbp_debug_round_best_distinct: table_log2 is above 21, or the table has no slot more than there are BBP_OK verdicts");
+            return best_hook_refuse(ctx, "bbp_debug_round_best_distinct: table_log2 is above 21, or the table has no slot more than there are BBP_OK verdicts");
         auto fill = [&](u8* dst) {
             for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, keys + 32 * (size_t)i, 32), memcpy(dst + 64 * (size_t)i + 32, ids + 32 * (size_t)i, 32);
         };
-        auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
-            for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j]];
-            return BBP_OK;
-        };
-        return best_run_host_distinct(ctx, B, fill, read, floor32, K, tranche, cap, table_log2, best_out, n_best, n_candidates, n_examined, n_duplicates, status);
-    });
-}
-
-// The device form, everything on s; the synchronisation points are best_run_dev's: after the first selection, once per tranche (the
-// counters behind the settle, which size the next tranche) and once to deliver the results.
-static int32_t best_run_dev_distinct(bbp_ctx* ctx, u32 N, const u8* round_dev, u32 B, const u8* rows_dev, const u8* entropy_dev, const uint8_t* floor32, u32 K,
-                                     u32 tranche, u32 cap, u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status,
-                                     hipStream_t s) {
-    std::lock_guard<std::mutex> call(ctx->best_mu);
-    return api_guard(ctx, [&]() -> int32_t {
-        int32_t rc;
-        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
-        BestDistinctCall c(ctx, B, K, 0, false, s);
-        const u32 rb = (u32)round_row_bytes(N);
-        if ((rc = best_distinct_open(c)) || (rc = best_distinct_keys_enqueue(c, rows_dev, rb, proof_record_bytes(N), floor32, status))) return rc;
-        BestDistinctTally ty;
-        std::string why;
-        u32 room = 0;
-        for (u32 t = 0;; t++) {
-            // tranche 0: its size needs the candidate count, which the selection delivers; a later one: the host knows it
-            u32 n = t == 0 ? (K ? std::min(best_tranche0(K, tranche, 0), B) : 0u) : best_tranche_rows(ty.T0, t, ty.live());
-            if ((rc = best_select_enqueue(c, n))) return rc;
-            if (t == 0) {
-                BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 8, hipMemcpyDeviceToHost, c.s));
-                BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
-                u32 counts[2];
-                memcpy(counts, c.h + c.L.h_counts, 8);
-                if (!best_distinct_tranche_ok(counts, 0, K, tranche, ty)) return ctx->err = "best proofs, one per bidder: a tranche of unexpected size", BBP_ERR_INTERNAL;
-                n = counts[0];
-            }
-            if (n == 0) break;
-            const u32 part = std::min(n, host_chunk_verify());
-            const BestRows R(part, N);
-            if ((rc = dev_reserve(ctx, ctx->best_rows, R.bytes))) return rc;
-            u8* g = (u8*)ctx->best_rows.p;
-            int32_t* tstat = (int32_t*)c.at(c.L.tstat);
-            for (u32 first = 0; first < n; first += part) {
-                const u32 m = std::min(part, n - first);
-                {
-                    ScopedEvent ev(ctx, TAG_SELECT, c.s);
-                    hipLaunchKernelGGL(k_best_gather, dim3(m), dim3(BEST_GATHER_T), 0, c.s, rb, first, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
-                                       rows_dev, entropy_dev, g + R.rows, g + R.ent);
-                    BBP_HIP_TRY(ctx, hipGetLastError());
-                }
-                if ((rc = verify_batch_agg_dev(ctx, VerifyRows::of_rounds(m, 1, &N, round_dev, nullptr), BBP_AGG_GROUP_DEFAULT, g + R.rows, g + R.ent,
-                                               tstat + first, c.s, nullptr)))
-                    return rc;
-            }
-            ty.examined += n;
-            if ((rc = best_mark_enqueue(c, n, tstat, status)) || (rc = best_settle_enqueue(c, n, tstat, status, ty.live() > 0))) return rc;
-            BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));  // rows examined and OK, identities settled, rows dropped
-            if (!ty.take(c, &why)) return ctx->err = why, BBP_ERR_INTERNAL;
-            if (ty.stop(K)) break;
-        }
-        if ((rc = best_distinct_finish_enqueue(c, nullptr, &room))) return rc;
-        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
-        if ((rc = best_distinct_deliver(c, room, ty, cap, best_out, n_best, n_candidates, n_examined, n_duplicates, &why))) ctx->err = why;
-        return rc;
+        BestCall c(ctx, B, K, ctx->stream, true, true, table_log2);
+        return best_run_host(c, fill, best_hook_read(verdicts), floor32, tranche, BestOut{cap, best_out, n_best, n_candidates, n_examined, n_duplicates},
+                             status);
     });
 }
 
@@ -2006,8 +1875,9 @@ extern "C" int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, 
     if (int32_t rc = best_screen(ctx, "bbp_verify_round_best_distinct_dev", N, B, &done)) return rc;
     if (done) return BBP_OK;
     return no_throw_ctx(ctx, [&]() -> int32_t {
-        return best_run_dev_distinct(ctx, N, (const u8*)round_dev, B, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, K, tranche, cap, best_out, n_best,
-                                     n_candidates, n_examined, n_duplicates, (int32_t*)status_dev, pick_stream(ctx, stream));
+        BestCall c(ctx, B, K, pick_stream(ctx, stream), false, true);
+        return best_run_dev(c, N, (const u8*)round_dev, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, tranche,
+                            BestOut{cap, best_out, n_best, n_candidates, n_examined, n_duplicates}, (int32_t*)status_dev);
     });
 }
 
