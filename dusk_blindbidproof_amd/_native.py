@@ -91,6 +91,9 @@ SIGNATURES = {
     "bbp_verify_round_best_distinct": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_round_best_distinct_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_round_best_distinct": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_rounds_best": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_rounds_best_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_rounds_best": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_set_prove_check": (_i32, [_vp, _i32]),
     "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -245,6 +248,19 @@ BEST_TRANCHE_DEFAULT = 16   # BBP_BEST_TRANCHE_DEFAULT
 RoundBest = collections.namedtuple("RoundBest", "best n_best n_candidates n_examined status raw")
 ROW_DUPLICATE = -2          # BBP_ROW_DUPLICATE: the row's identity (z_img) already had a verified row; not verified
 RoundBestDistinct = collections.namedtuple("RoundBestDistinct", "best n_best n_candidates n_examined n_duplicates status raw")
+BEST_MAX_ROUNDS = 1 << 16   # BBP_BEST_MAX_ROUNDS
+# per round: best (a list of row indices in rank order, at most cap), n_best, n_candidates, n_examined, raw (the round's cap entries as
+# the call left them); n_steps and the B statuses for the call
+RoundsBest = collections.namedtuple("RoundsBest", "best n_best n_candidates n_examined n_steps status raw")
+
+
+def rounds_floors(floors, R):
+    """floors of the many-rounds best calls: None (all zero), or R floors (ints or 32 bytes each) -> R x 32 bytes"""
+    if floors is None:
+        return None
+    if len(floors) != R:
+        raise ValueError("one floor per round")
+    return b"".join(select_floor(f) for f in floors)
 
 
 def select_floor(floor):
@@ -631,6 +647,64 @@ class Context:
                                                       ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
         return self._best_distinct_result(B, cap, best, status, counts, dups)
 
+    def verify_rounds_best(self, round_Ns, table, round_of, rows, floors=None, K=1, tranche=0, cap=None, fill=0, B=None):
+        """bbp_verify_rounds_best: verify_round_best for every round of a verify_rounds call at once -- step t of every round that still
+        runs is verified in one engine call.  round_Ns, table, round_of, rows as verify_rounds; floors: None or one per round.  Returns
+        a RoundsBest: per-round lists best, n_best, n_candidates, n_examined, then n_steps and the B statuses."""
+        R = len(round_Ns)
+        if B is None:
+            B = len(round_of) if round_of is not None else len(rows) // round_row_size(round_Ns[0])
+        cap, best, status, counts = self._bests_buffers(R, B, K, cap, fill)
+        fl = rounds_floors(floors, R)
+        self._check(lib.bbp_verify_rounds_best(self._h, R, _u32s(round_Ns), _buf(table), B, _u32s(round_of), _buf(rows) if B else best,
+                                               None if fl is None else _buf(fl), K, tranche, cap, best, counts[0], counts[1], counts[2],
+                                               ctypes.byref(counts[3]), status))
+        return self._bests_result(R, B, cap, best, status, counts)
+
+    def verify_rounds_best_dev(self, round_Ns, table_ptr, round_of, B, rows_ptr, ent_ptr, status_ptr, floors=None, K=1, tranche=0, cap=None, stream=None,
+                               fill=0):
+        """bbp_verify_rounds_best_dev: table, rows (any alignment) and B x 32 entropy bytes resident on the device; round_Ns, round_of and
+        floors are host values.  Synchronises `stream` once per step.  Returns a RoundsBest whose status is None: the B statuses are at
+        status_ptr, complete on `stream`."""
+        R = len(round_Ns)
+        cap, best, _, counts = self._bests_buffers(R, B, K, cap, fill)
+        fl = rounds_floors(floors, R)
+        self._check(lib.bbp_verify_rounds_best_dev(self._h, R, _u32s(round_Ns), table_ptr, B, _u32s(round_of), rows_ptr, ent_ptr,
+                                                   None if fl is None else _buf(fl), K, tranche, cap, best, counts[0], counts[1], counts[2],
+                                                   ctypes.byref(counts[3]), status_ptr, _stream(stream)))
+        return self._bests_result(R, B, cap, best, None, counts)
+
+    def debug_rounds_best(self, R, round_of, keys, verdicts, floors=None, K=1, tranche=0, cap=None, fill=0):
+        """bbp_debug_rounds_best (test hook): the shipped kernels of the many-rounds calls on made-up keys (B x 32 bytes) and verdicts;
+        nothing is verified.  Returns a RoundsBest."""
+        B = len(verdicts)
+        if len(keys) != 32 * B or (round_of is not None and len(round_of) != B):
+            raise ValueError("keys are 32 bytes and round_of one entry per verdict")
+        cap, best, status, counts = self._bests_buffers(R, B, K, cap, fill)
+        fl = rounds_floors(floors, R)
+        self._check(lib.bbp_debug_rounds_best(self._h, R, B, _u32s(round_of), _buf(keys) if B else best, (ctypes.c_int32 * max(1, B))(*verdicts),
+                                              None if fl is None else _buf(fl), K, tranche, cap, best, counts[0], counts[1], counts[2],
+                                              ctypes.byref(counts[3]), status))
+        return self._bests_result(R, B, cap, best, status, counts)
+
+    @staticmethod
+    def _bests_buffers(R, B, K, cap, fill):
+        if cap is None:
+            cap = K if K else B
+        best = (_u32 * max(1, R * cap))()
+        status = (ctypes.c_int32 * max(1, B))()
+        ctypes.memset(best, fill, ctypes.sizeof(best))
+        ctypes.memset(status, fill, ctypes.sizeof(status))
+        return cap, best, status, ((_u32 * max(1, R))(), (_u32 * max(1, R))(), (_u32 * max(1, R))(), _u32(0))
+
+    @staticmethod
+    def _bests_result(R, B, cap, best, status, counts):
+        raw = list(best)
+        raw = [raw[r * cap:(r + 1) * cap] for r in range(R)]
+        n_best = list(counts[0])[:R]
+        return RoundsBest([raw[r][:min(n_best[r], cap)] for r in range(R)], n_best, list(counts[1])[:R], list(counts[2])[:R], counts[3].value,
+                          None if status is None else list(status)[:B], raw)
+
     @staticmethod
     def _best_distinct_result(B, cap, best, status, counts, dups):
         r = Context._best_result(B, cap, best, status, counts)
@@ -859,7 +933,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best / verify_round_best_distinct (member 0 selects, the pool verifies); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best / verify_round_best_distinct / verify_rounds_best (member 0 selects, the pool verifies); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):
@@ -895,6 +969,11 @@ class Pool(Context):
         """bbp_verify_round_best on the pool: member 0 keeps the keys, selects and marks; every tranche is verified as
         verify_rounds_aggregated verifies it (block-split over the members)."""
         return super().verify_round_best(N, table, rows, floor, K, tranche, cap, fill)
+
+    def verify_rounds_best(self, round_Ns, table, round_of, rows, floors=None, K=1, tranche=0, cap=None, fill=0, B=None):
+        """bbp_verify_rounds_best on the pool: member 0 keeps the keys and segments, selects and marks; every step is verified as
+        verify_rounds_aggregated verifies it (block-split over the members)."""
+        return super().verify_rounds_best(round_Ns, table, round_of, rows, floors, K, tranche, cap, fill, B)
 
     def verify_round_best_distinct(self, N, table, rows, floor=0, K=1, tranche=0, cap=None, fill=0):
         """bbp_verify_round_best_distinct on the pool: member 0 keeps the keys and identities, selects, marks and drops; every tranche is

@@ -15,6 +15,7 @@
 #include "round_bids.h"
 #include "round_best.h"
 #include "round_select.h"
+#include "rounds_best.h"
 #include "secret_map.h"
 #include "submit.h"
 #include "witness_check.h"
@@ -1434,6 +1435,7 @@ static const RsFloor BEST_NO_FLOOR = {};  // k_best_keys has applied the floor: 
 struct BestOut {
     u32 cap;
     u32 *best, *n_best, *n_candidates, *n_examined, *n_duplicates;
+    u32* n_tranches = nullptr;  // the tranches that held at least one row (the many-rounds calls with one round report them)
 };
 
 static int32_t best_open(BestCall& c) {
@@ -1593,7 +1595,7 @@ static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, cons
     const u32 B = c.B, K = c.K;
     BestTally ty;
     std::vector<int32_t> st;
-    u32 pending = 0, room = 0;
+    u32 pending = 0, room = 0, tranches = 0;
     auto fail = [&](const std::string& why, int32_t rc) {
         api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
         return rc;
@@ -1641,6 +1643,7 @@ static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, cons
         const u32 n = counts[0];
         pending = 0;
         if (n) {
+            tranches++;
             st.assign(n, BBP_ERR_INTERNAL);
             if ((rc = verdicts(n, (const u32*)(c.h + c.L.h_sel), st.data()))) return rc;
             ty.examined += n;
@@ -1663,6 +1666,7 @@ static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, cons
     std::string why;
     if (int32_t rc = best_deliver(c, room, ty, out, &why)) return fail(why, rc);
     memcpy(status, c.h + c.L.h_status, 4 * (size_t)B);
+    if (out.n_tranches) *out.n_tranches = tranches;
     return BBP_OK;
 }
 
@@ -1758,7 +1762,7 @@ static int32_t best_run_dev(BestCall& c, u32 N, const u8* round_dev, const u8* r
         if ((rc = best_open(c)) || (rc = best_keys_enqueue(c, rows_dev, round_row_bytes(N), proof_record_bytes(N), floor32, status))) return rc;
         BestTally ty;
         std::string why;
-        u32 room = 0;
+        u32 room = 0, tranches = 0;
         for (u32 t = 0;; t++) {
             u32 n = best_tranche_ask(c.K, tranche, c.B, ty, t);
             if ((rc = best_select_enqueue(c, n))) return rc;
@@ -1771,6 +1775,7 @@ static int32_t best_run_dev(BestCall& c, u32 N, const u8* round_dev, const u8* r
                 n = counts[0];
             }
             if (n == 0) break;
+            tranches++;
             int32_t* tstat = (int32_t*)c.at(c.L.tstat);
             if ((rc = best_verify_enqueue(c, N, round_dev, rows_dev, entropy_dev, n, tstat))) return rc;
             ty.examined += n;
@@ -1782,6 +1787,7 @@ static int32_t best_run_dev(BestCall& c, u32 N, const u8* round_dev, const u8* r
         if ((rc = best_finish_enqueue(c, nullptr, &room))) return rc;
         BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
         if ((rc = best_deliver(c, room, ty, out, &why))) ctx->err = why;
+        if (!rc && out.n_tranches) *out.n_tranches = tranches;
         return rc;
     });
 }
@@ -1878,6 +1884,450 @@ extern "C" int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, 
         BestCall c(ctx, B, K, pick_stream(ctx, stream), false, true);
         return best_run_dev(c, N, (const u8*)round_dev, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, tranche,
                             BestOut{cap, best_out, n_best, n_candidates, n_examined, n_duplicates}, (int32_t*)status_dev);
+    });
+}
+
+// ---- best valid proofs of many rounds (include/bbp.h; rules and kernels: rounds_best.h) ---------------------------------------------
+// The launch sequence of one call with R > 1, on ONE device's context and one stream:
+//   open      the state reserved, the counters and sel zeroed; floors, round_of [the _dev form: row offsets and row sizes; the host
+//             forms: the keys] up
+//   segment   k_bests_keys, k_bests_scan (ncand -> seg), k_bests_place
+//   per step  k_bests_plan (take), k_bests_scan (take -> off), k_bests_select over the candidate records -> sel;  [the rows verified];
+//             k_bests_mark
+//   finish    k_bests_plan (winners), k_bests_scan, k_bests_select over the winner records, k_best_pairs; ctr, pairs [statuses] down
+struct BestsCall {
+    bbp_ctx* ctx;
+    u32 R, B, K, tranche;
+    hipStream_t s;
+    BestsLayout L;
+    u8 *d = nullptr, *h = nullptr;
+    BestsCall(bbp_ctx* c, u32 R_, u32 B_, u32 K_, u32 tranche_, hipStream_t s_, bool host_keys)
+        : ctx(c), R(R_), B(B_), K(K_), tranche(tranche_), s(s_), L(B_, R_, host_keys) {}
+    u32* at(size_t off) const { return (u32*)(d + off); }
+    u32* ctr(u32 word) const { return (u32*)(d + L.ctr) + word; }
+    const u32* mirror(u32 word) const { return (const u32*)(h + L.h_ctr) + word; }
+    unsigned long long* offb() const { return (unsigned long long*)(d + L.offb); }
+};
+static const char BESTS_FAMILY[] = "best valid proofs of many rounds: ";
+// where a call's results go: R x cap, R, R, R entries; n_steps may be null
+struct BestsOut {
+    u32 cap;
+    u32 *best, *n_best, *n_candidates, *n_examined, *n_steps;
+};
+
+// open: floors32 (R x 32 bytes or null), round_of (B, host), [rowoff (B u64) and rb (R): the _dev form] go up through the mirror
+static int32_t bests_open(BestsCall& c, const uint8_t* floors, const u32* round_of, const unsigned long long* rowoff, const u32* rb) {
+    bbp_ctx* ctx = c.ctx;
+    const BestsLayout& L = c.L;
+    int32_t rc;
+    if ((rc = dev_reserve(ctx, ctx->best_dev, L.bytes)) || (rc = pinned_reserve(ctx, ctx->best_h, ctx->best_h_cap, L.h_bytes))) return rc;
+    if (!ctx->ev_best) BBP_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_best, hipEventDisableTiming));
+    c.d = (u8*)ctx->best_dev.p, c.h = (u8*)ctx->best_h;
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + L.ctr, 0, 4 * (size_t)L.c_words, c.s));
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + L.sel, 0, 4 * (size_t)c.B, c.s));
+    if (floors) {
+        memcpy(c.h + L.h_floors, floors, 32 * (size_t)c.R);
+        BBP_HIP_TRY(ctx, hipMemcpyAsync(c.d + L.floors, c.h + L.h_floors, 32 * (size_t)c.R, hipMemcpyHostToDevice, c.s));
+    } else
+        BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + L.floors, 0, 32 * (size_t)c.R, c.s));
+    memcpy(c.h + L.h_round_of, round_of, 4 * (size_t)c.B);
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.d + L.round_of, c.h + L.h_round_of, 4 * (size_t)c.B, hipMemcpyHostToDevice, c.s));
+    if (rowoff) {
+        memcpy(c.h + L.h_rowoff, rowoff, 8 * (size_t)c.B);
+        memcpy(c.h + L.h_rb, rb, 4 * (size_t)c.R);
+        BBP_HIP_TRY(ctx, hipMemcpyAsync(c.d + L.rowoff, c.h + L.h_rowoff, 8 * (size_t)c.B, hipMemcpyHostToDevice, c.s));
+        BBP_HIP_TRY(ctx, hipMemcpyAsync(c.d + L.rb, c.h + L.h_rb, 4 * (size_t)c.R, hipMemcpyHostToDevice, c.s));
+    }
+    return BBP_OK;
+}
+
+static int32_t bests_scan_enqueue(const BestsCall& c, u32 in_word, u32 out_word, bool bytes) {
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_bests_scan, dim3(1), dim3(BESTS_T), 0, c.s, c.R, (const u32*)c.ctr(in_word), bytes ? (const u32*)c.at(c.L.rb) : (const u32*)nullptr,
+                       c.ctr(out_word), bytes ? c.offb() : (unsigned long long*)nullptr);
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// keys at base (the _dev form: the rows; else the staged keys) -> records, statuses, candidate counts, segments
+static int32_t bests_segment_enqueue(const BestsCall& c, const u8* base, bool dev_rows, int32_t* status) {
+    const BestsLayout& L = c.L;
+    const dim3 grid((c.B + BEST_T - 1) / BEST_T), block(BEST_T);
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_bests_keys, grid, block, 0, c.s, c.B, base, dev_rows ? (const unsigned long long*)(c.d + L.rowoff) : nullptr,
+                           (const u32*)c.at(L.rb), (const u32*)c.at(L.round_of), (const u32*)c.at(L.floors), c.at(L.recs), c.at(L.win), status, c.ctr(L.c_ncand));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    if (int32_t rc = bests_scan_enqueue(c, L.c_ncand, L.c_seg, false)) return rc;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_bests_place, grid, block, 0, c.s, c.B, (const u32*)c.at(L.recs), (const u32*)c.ctr(L.c_seg), c.ctr(L.c_fill), c.at(L.cand));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// take and off of step t (finish: of the winners), [the selection over `recs` -> sel], the counters into the mirror
+static int32_t bests_plan_enqueue(const BestsCall& c, u32 t, bool finish, bool bytes, bool select) {
+    const BestsLayout& L = c.L;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_bests_plan, dim3((c.R + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.R, t, c.K, c.tranche, finish ? 1u : 0u,
+                           (const u32*)c.ctr(L.c_ncand), (const u32*)c.ctr(L.c_examined), (const u32*)c.ctr(L.c_ok), c.ctr(L.c_take), c.ctr(L.c_tranches));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    if (int32_t rc = bests_scan_enqueue(c, L.c_take, L.c_off, bytes)) return rc;
+    if (select) {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_bests_select, dim3(c.R), dim3(BESTS_T), 0, c.s, (const u32*)c.at(finish ? L.win : L.recs), (const u32*)c.at(L.cand),
+                           (const u32*)c.ctr(L.c_seg), (const u32*)c.ctr(L.c_take), (const u32*)c.ctr(L.c_off), c.at(L.sel));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + L.h_ctr, c.d + L.ctr, 4 * (size_t)L.c_words, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+
+static int32_t bests_mark_enqueue(const BestsCall& c, u32 n, const int32_t* tstat, int32_t* status) {
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_bests_mark, dim3((n + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, n, (const u32*)c.at(c.L.sel), tstat, status, c.at(c.L.recs),
+                       c.at(c.L.win), c.ctr(c.L.c_examined), c.ctr(c.L.c_ok));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// the winners' pairs (nw of them, grouped by round as off says) and everything the host reads, into the mirror
+static int32_t bests_pairs_enqueue(const BestsCall& c, u32 nw, const int32_t* status_to_fetch) {
+    const BestsLayout& L = c.L;
+    if (nw) {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_best_pairs, dim3((nw + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, nw, (const u32*)c.at(L.sel), (const u32*)c.ctr(L.c_off + c.R),
+                           (const u32*)c.at(L.win), c.at(L.pairs));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+        BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + L.h_pairs, c.d + L.pairs, 4 * (size_t)BEST_PAIR_WORDS * nw, hipMemcpyDeviceToHost, c.s));
+    }
+    if (status_to_fetch) BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + L.h_status, status_to_fetch, 4 * (size_t)c.B, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+
+// What a call knows of every round between steps, held against the device's counters each time they arrive.
+struct BestsTally {
+    u32 R, K, tranche;
+    std::vector<u32> nc, examined, ok, take;
+    u32 n = 0;  // the rows of the step planned last
+    BestsTally(u32 R_, u32 K_, u32 tranche_) : R(R_), K(K_), tranche(tranche_), nc(R_), examined(R_), ok(R_), take(R_) {}
+    // step t (finish: the winners) from what the call has counted -> take, n
+    void plan(u32 t, bool finish) {
+        n = 0;
+        for (u32 r = 0; r < R; r++) n += take[r] = finish ? bests_winners(K, ok[r]) : bests_take(K, tranche, t, nc[r], examined[r], ok[r]);
+    }
+    // the first counters: the candidate counts are the device's; B bounds them
+    bool adopt_candidates(const BestsCall& c, std::string* why) {
+        unsigned long long total = 0;
+        for (u32 r = 0; r < R; r++) total += nc[r] = c.mirror(c.L.c_ncand)[r];
+        if (total <= c.B && c.mirror(c.L.c_seg)[R] == total) return true;
+        return *why = std::string(BESTS_FAMILY) + "the device counted " + std::to_string(total) + " candidates among " + std::to_string(c.B) + " rows", false;
+    }
+    // the counters that arrived with step t's plan (or the finish's).  ok_known: the host has counted the valid rows itself (the host
+    // forms); otherwise the device's count is taken over where it can be true, and the plan is made from it.
+    bool check(const BestsCall& c, u32 t, bool finish, bool ok_known, std::string* why) {
+        const BestsLayout& L = c.L;
+        bool good = true;
+        for (u32 r = 0; r < R && good; r++) {
+            const u32 dok = c.mirror(L.c_ok)[r];
+            good = c.mirror(L.c_ncand)[r] == nc[r] && c.mirror(L.c_examined)[r] == examined[r] && (ok_known ? dok == ok[r] : dok >= ok[r] && dok <= examined[r]);
+            ok[r] = dok;
+        }
+        if (good) {
+            plan(t, finish);
+            unsigned long long at = 0;
+            for (u32 r = 0; r < R && good; r++) good = c.mirror(L.c_take)[r] == take[r] && c.mirror(L.c_off)[r] == at, at += take[r];
+            good = good && c.mirror(L.c_off)[R] == n;
+        }
+        if (!good) *why = std::string(BESTS_FAMILY) + "the device's per-round counters at step " + std::to_string(t) + " are not what the call counted";
+        return good;
+    }
+};
+
+// after the finish has arrived (tally checked): every round's part of the pairs ranked, the counts delivered
+static int32_t bests_deliver(const BestsCall& c, const BestsTally& ty, const u32* round_of, u32 steps, const BestsOut& o, std::string* why) {
+    const u32* pairs = (const u32*)(c.h + c.L.h_pairs);
+    u32 at = 0;
+    for (u32 r = 0; r < c.R; r++) {
+        const u32 nw = ty.take[r];
+        for (u32 j = at; j < at + nw; j++) {
+            const u32 i = pairs[(size_t)BEST_PAIR_WORDS * j + 8];
+            if (i >= c.B || round_of[i] != r) return *why = std::string(BESTS_FAMILY) + "a winner of round " + std::to_string(r) + " is no row of it", BBP_ERR_INTERNAL;
+        }
+        best_rank_pairs(nw, pairs + (size_t)BEST_PAIR_WORDS * at, o.cap, o.best + (size_t)r * o.cap);
+        o.n_best[r] = nw, o.n_candidates[r] = ty.nc[r], o.n_examined[r] = ty.examined[r];
+        at += nw;
+    }
+    if (o.n_steps) *o.n_steps = steps;
+    return BBP_OK;
+}
+// a step cannot run more often than a tranche can double
+constexpr u32 BESTS_MAX_STEPS = 40;
+
+// The host forms with R > 1 on ONE device's context (c.ctx).  fill(dst): the B x 32 key bytes into the pinned staging area;
+// verdicts(n, sel, take, st): the statuses of the step's rows sel[0..n), grouped by round in ascending order, take[r] of round r --
+// called with no lock of the device held.  The host counts the valid rows itself, so it knows the next step's size before the device
+// has planned it: one submission per step carries the marks of the step before, the plan, the selection and the copies; one more in
+// front reads the candidate counts.
+template <class Fill, class Verdicts>
+static int32_t bests_run_host(BestsCall& c, const u32* round_of, Fill&& fill, Verdicts&& verdicts, const uint8_t* floors, const BestsOut& out, int32_t* status) {
+    bbp_ctx* const dev = c.ctx;
+    std::lock_guard<std::mutex> call(dev->best_mu);
+    const BestsLayout& L = c.L;
+    BestsTally ty(c.R, c.K, c.tranche);
+    std::vector<int32_t> st;
+    std::string why;
+    auto fail = [&](const std::string& w, int32_t rc) {
+        api_guard(dev, [&]() -> int32_t { return dev->err = w, rc; });
+        return rc;
+    };
+    auto submit = [&](auto&& enqueue) -> int32_t {
+        int32_t rc = api_guard(dev, [&]() -> int32_t {
+            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
+            if (int32_t r = enqueue()) return r;
+            BBP_HIP_TRY(dev, hipEventRecord(dev->ev_best, c.s));
+            return BBP_OK;
+        });
+        if (rc) return rc;
+        const hipError_t e = wait_event_polling(dev->ev_best);
+        return e == hipSuccess ? (int32_t)BBP_OK : fail(std::string(BESTS_FAMILY) + hipGetErrorString(e), BBP_ERR_DEVICE);
+    };
+    int32_t rc = submit([&]() -> int32_t {
+        if (int32_t r = bests_open(c, floors, round_of, nullptr, nullptr)) return r;
+        fill(c.h + L.h_keys);
+        BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + L.keys, c.h + L.h_keys, 32 * (size_t)c.B, hipMemcpyHostToDevice, c.s));
+        if (int32_t r = bests_segment_enqueue(c, c.d + L.keys, false, (int32_t*)c.at(L.status))) return r;
+        BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + L.h_ctr, c.d + L.ctr, 4 * (size_t)L.c_words, hipMemcpyDeviceToHost, c.s));
+        return BBP_OK;
+    });
+    if (rc) return rc;
+    if (!ty.adopt_candidates(c, &why)) return fail(why, BBP_ERR_INTERNAL);
+    u32 pending = 0, steps = 0;
+    for (u32 t = 0;; t++) {
+        ty.plan(t, false);
+        const bool finish = ty.n == 0 || t >= BESTS_MAX_STEPS;
+        if (finish) ty.plan(t, true);
+        const u32 n = ty.n;
+        rc = submit([&]() -> int32_t {
+            int32_t r;
+            if (pending) {
+                memcpy(c.h + L.h_tstat, st.data(), 4 * (size_t)pending);
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + L.tstat, c.h + L.h_tstat, 4 * (size_t)pending, hipMemcpyHostToDevice, c.s));
+                if ((r = bests_mark_enqueue(c, pending, (const int32_t*)c.at(L.tstat), (int32_t*)c.at(L.status)))) return r;
+            }
+            if ((r = bests_plan_enqueue(c, t, finish, false, n > 0))) return r;
+            if (finish) return bests_pairs_enqueue(c, n, (const int32_t*)c.at(L.status));
+            BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + L.h_sel, c.d + L.sel, 4 * (size_t)n, hipMemcpyDeviceToHost, c.s));
+            return BBP_OK;
+        });
+        if (rc) return rc;
+        if (!ty.check(c, t, finish, true, &why)) return fail(why, BBP_ERR_INTERNAL);
+        if (finish) break;
+        steps++;
+        st.assign(n, BBP_ERR_INTERNAL);
+        const u32* sel = (const u32*)(c.h + L.h_sel);
+        if ((rc = verdicts(n, sel, ty.take.data(), st.data()))) return rc;
+        u32 j = 0;
+        for (u32 r = 0; r < c.R; r++)
+            for (u32 e = j + ty.take[r]; j < e; j++) ty.examined[r]++, ty.ok[r] += st[j] == BBP_OK;
+        pending = n;
+    }
+    if ((rc = bests_deliver(c, ty, round_of, steps, out, &why))) return fail(why, rc);
+    memcpy(status, c.h + L.h_status, 4 * (size_t)c.B);
+    return BBP_OK;
+}
+
+// byte offset of every row of a rounds call (rows packed back to back in request order), the total at [B]
+static std::vector<unsigned long long> bests_row_offsets(const u32* round_Ns, u32 B, const u32* round_of) {
+    std::vector<unsigned long long> off((size_t)B + 1);
+    unsigned long long at = 0;
+    for (u32 i = 0; i < B; i++) off[i] = at, at += round_row_bytes(round_Ns[round_of[i]]);
+    off[B] = at;
+    return off;
+}
+// round_of of a step's rows: grouped by round in ascending order, take[r] of round r
+static void bests_step_rounds(u32 R, const u32* take, std::vector<u32>& step_round_of) {
+    step_round_of.clear();
+    for (u32 r = 0; r < R; r++) step_round_of.insert(step_round_of.end(), take[r], r);
+}
+
+// The _dev form with R > 1, everything on c.s, the context lock held throughout.  It synchronises c.s after the segments are built (the
+// candidate counts, and step 0's plan), once per step (the counters behind the mark, and the next step's plan: the host needs
+// take[] to build the step's round_of) and once to deliver.
+static int32_t bests_run_dev(BestsCall& c, const u32* round_Ns, const u8* rounds_dev, const u32* round_of, const u8* rows_dev, const u8* entropy_dev,
+                             const uint8_t* floors, const BestsOut& out, int32_t* status) {
+    bbp_ctx* const ctx = c.ctx;
+    std::lock_guard<std::mutex> call(ctx->best_mu);
+    return api_guard(ctx, [&]() -> int32_t {
+        const BestsLayout& L = c.L;
+        int32_t rc;
+        BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+        const std::vector<unsigned long long> rowoff = bests_row_offsets(round_Ns, c.B, round_of);
+        std::vector<u32> rb(c.R), step_round_of;
+        for (u32 r = 0; r < c.R; r++) rb[r] = (u32)round_row_bytes(round_Ns[r]);
+        if ((rc = bests_open(c, floors, round_of, rowoff.data(), rb.data())) || (rc = bests_segment_enqueue(c, rows_dev, true, status)) ||
+            (rc = bests_plan_enqueue(c, 0, false, true, false)))
+            return rc;
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+        BestsTally ty(c.R, c.K, c.tranche);
+        std::string why;
+        if (!ty.adopt_candidates(c, &why)) return ctx->err = why, BBP_ERR_INTERNAL;
+        u32 steps = 0;
+        int32_t* tstat = (int32_t*)c.at(L.tstat);
+        for (u32 t = 0; t < BESTS_MAX_STEPS; t++) {
+            if (!ty.check(c, t, false, false, &why)) return ctx->err = why, BBP_ERR_INTERNAL;
+            const u32 n = ty.n;
+            if (n == 0) break;
+            steps++;
+            {
+                ScopedEvent ev(ctx, TAG_SELECT, c.s);
+                hipLaunchKernelGGL(k_bests_select, dim3(c.R), dim3(BESTS_T), 0, c.s, (const u32*)c.at(L.recs), (const u32*)c.at(L.cand), (const u32*)c.ctr(L.c_seg),
+                                   (const u32*)c.ctr(L.c_take), (const u32*)c.ctr(L.c_off), c.at(L.sel));
+                BBP_HIP_TRY(ctx, hipGetLastError());
+            }
+            // the step's rows packed by round and verified, in engine calls of at most BBP_HOST_CHUNK_VERIFY rows
+            bests_step_rounds(c.R, ty.take.data(), step_round_of);
+            std::vector<unsigned long long> at((size_t)n + 1, 0);
+            for (u32 j = 0; j < n; j++) at[j + 1] = at[j] + rb[step_round_of[j]];
+            const u32 part = std::min(n, host_chunk_verify());
+            unsigned long long most = 0;
+            for (u32 first = 0; first < n; first += part) most = std::max(most, at[std::min(n, first + part)] - at[first]);
+            const size_t ent_off = align256((size_t)most + 4);
+            if ((rc = dev_reserve(ctx, ctx->best_rows, ent_off + align256(32 * (size_t)part)))) return rc;
+            u8* g = (u8*)ctx->best_rows.p;
+            for (u32 first = 0; first < n; first += part) {
+                const u32 m = std::min(part, n - first);
+                {
+                    ScopedEvent ev(ctx, TAG_SELECT, c.s);
+                    hipLaunchKernelGGL(k_bests_gather, dim3(m), dim3(BEST_GATHER_T), 0, c.s, n, first, at[first], (const u32*)c.at(L.sel), (const u32*)c.at(L.round_of),
+                                       (const u32*)c.at(L.rb), (const u32*)c.ctr(L.c_off), (const unsigned long long*)c.offb(),
+                                       (const unsigned long long*)(c.d + L.rowoff), rows_dev, entropy_dev, g, g + ent_off);
+                    BBP_HIP_TRY(ctx, hipGetLastError());
+                }
+                if ((rc = verify_batch_agg_dev(ctx, VerifyRows::of_rounds(m, c.R, round_Ns, rounds_dev, step_round_of.data() + first), BBP_AGG_GROUP_DEFAULT, g,
+                                               g + ent_off, tstat + first, c.s, nullptr)))
+                    return rc;
+            }
+            if ((rc = bests_mark_enqueue(c, n, tstat, status)) || (rc = bests_plan_enqueue(c, t + 1, false, true, false))) return rc;
+            BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+            for (u32 r = 0; r < c.R; r++) ty.examined[r] += ty.take[r];
+        }
+        // the last plan that arrived held no row (or the step bound is reached): the valid rows are known, the winners can be planned
+        for (u32 r = 0; r < c.R; r++) ty.ok[r] = std::min(c.mirror(L.c_ok)[r], ty.examined[r]);
+        ty.plan(0, true);
+        if ((rc = bests_plan_enqueue(c, 0, true, false, ty.n > 0)) || (rc = bests_pairs_enqueue(c, ty.n, nullptr))) return rc;
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(c.s));
+        if (!ty.check(c, 0, true, true, &why)) return ctx->err = why, BBP_ERR_INTERNAL;
+        if ((rc = bests_deliver(c, ty, round_of, steps, out, &why))) ctx->err = why;
+        return rc;
+    });
+}
+
+// screening of the numbers shared by the three forms (rounds_best.h rounds_best_screen: the same checks in the same order)
+static int32_t bests_screen(bbp_ctx* ctx, const char* what, u32 R, const u32* round_Ns, u32 B, const u32* round_of, bool* done) {
+    const int32_t screened = rounds_best_screen(R, round_Ns, B, round_of, done);
+    if (!screened) return BBP_OK;
+    return api_guard(ctx, [&]() -> int32_t {
+        for (u32 r = 0; r < R && R <= BBP_BEST_MAX_ROUNDS; r++)
+            if (round_Ns[r] == 0 || (screened == BBP_ERR_GENS_LEN && round_Ns[r] > BBP_MAX_ITEMS)) return check_n(ctx, round_Ns[r]);  // (names the list length)
+        ctx->err = std::string(what) + ": R is 0 or above BBP_BEST_MAX_ROUNDS, more than BBP_SELECT_MAX_BIDS rows, or round_of names no round";
+        return screened;
+    });
+}
+static void bests_zero(u32 R, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_steps) {
+    for (u32 r = 0; r < R && R <= BBP_BEST_MAX_ROUNDS; r++) n_best[r] = n_candidates[r] = n_examined[r] = 0;
+    if (n_steps) *n_steps = 0;
+}
+static const uint8_t BESTS_ZERO_FLOOR[32] = {};
+
+extern "C" int32_t bbp_verify_rounds_best(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                          const uint8_t* rows, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out,
+                                          uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_steps, int32_t* status) {
+    if (!ctx || !round_Ns || !rounds || !rows || !n_best || !n_candidates || !n_examined || !status || (cap && !best_out)) return BBP_ERR_BAD_ARG;
+    bests_zero(R, n_best, n_candidates, n_examined, n_steps);
+    bool done;
+    if (int32_t rc = bests_screen(ctx, "bbp_verify_rounds_best", R, round_Ns, B, round_of, &done)) return rc;
+    if (done) return BBP_OK;
+    if (R == 1)
+        return best_public_host(ctx, round_Ns[0], rounds, B, rows, floors ? floors : BESTS_ZERO_FLOOR, K, tranche, false,
+                                BestOut{cap, best_out, n_best, n_candidates, n_examined, nullptr, n_steps}, status);
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = is_pool(ctx) ? ctx->members[0] : ctx;
+        BestsCall c(dev, R, B, K, tranche, dev->stream, true);
+        const std::vector<unsigned long long> rowoff = bests_row_offsets(round_Ns, B, round_of);
+        std::vector<uint8_t> picked;
+        std::vector<u32> step_round_of;
+        auto fill = [&](u8* dst) {
+            for (u32 i = 0; i < B; i++) memcpy(dst + 32 * (size_t)i, rows + rowoff[i + 1] - 64, 32);  // the score: 64 bytes before the row's end
+        };
+        auto verdicts = [&](u32 n, const u32* sel, const u32* take, int32_t* st) -> int32_t {
+            bests_step_rounds(R, take, step_round_of);
+            picked.clear();
+            for (u32 j = 0; j < n; j++) {
+                if (sel[j] >= B || round_of[sel[j]] != step_round_of[j])
+                    return api_guard(ctx, [&]() -> int32_t { return ctx->err = std::string(BESTS_FAMILY) + "a selected row is no row of its round", BBP_ERR_INTERNAL; });
+                picked.insert(picked.end(), rows + rowoff[sel[j]], rows + rowoff[sel[j] + 1]);
+            }
+            return verify_host(ctx, VerifyRows::of_rounds(n, R, round_Ns, rounds, step_round_of.data()), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
+        };
+        const int32_t rc = bests_run_host(c, round_of, fill, verdicts, floors, BestsOut{cap, best_out, n_best, n_candidates, n_examined, n_steps}, status);
+        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+        return rc;
+    });
+}
+
+// Test hook: the shipped kernels of rounds_best.h on caller-made keys and verdicts.  Synchronises.
+extern "C" int32_t bbp_debug_rounds_best(bbp_ctx* ctx, uint32_t R, uint32_t B, const uint32_t* round_of, const uint8_t* keys, const int32_t* verdicts,
+                                         const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best,
+                                         uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_steps, int32_t* status) {
+    if (!ctx || !keys || !verdicts || !n_best || !n_candidates || !n_examined || !status || (cap && !best_out)) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_rounds_best");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        u32 n_ok;
+        if (R == 0 || R > BBP_BEST_MAX_ROUNDS) return best_hook_refuse(ctx, "bbp_debug_rounds_best: R is 0 or above BBP_BEST_MAX_ROUNDS");
+        if (int32_t rc = best_hook_screen(ctx, "bbp_debug_rounds_best", B, verdicts, &n_ok)) return rc;
+        if (!round_of && R > 1) return best_hook_refuse(ctx, "bbp_debug_rounds_best: round_of may be NULL with one round only");
+        for (u32 i = 0; round_of && i < B; i++)
+            if (round_of[i] >= R) return best_hook_refuse(ctx, "bbp_debug_rounds_best: round_of names a round beyond R");
+        bests_zero(R, n_best, n_candidates, n_examined, n_steps);
+        auto fill = [&](u8* dst) { memcpy(dst, keys, 32 * (size_t)B); };
+        if (R == 1) {
+            BestCall c(ctx, B, K, ctx->stream, true, false);
+            return best_run_host(c, fill, best_hook_read(verdicts), floors ? floors : BESTS_ZERO_FLOOR, tranche,
+                                 BestOut{cap, best_out, n_best, n_candidates, n_examined, nullptr, n_steps}, status);
+        }
+        BestsCall c(ctx, R, B, K, tranche, ctx->stream, true);
+        auto read = [&](u32 n, const u32* sel, const u32*, int32_t* st) -> int32_t {
+            for (u32 j = 0; j < n; j++) st[j] = sel[j] < B ? verdicts[sel[j]] : (int32_t)BBP_ERR_INTERNAL;
+            return BBP_OK;
+        };
+        return bests_run_host(c, round_of, fill, read, floors, BestsOut{cap, best_out, n_best, n_candidates, n_examined, n_steps}, status);
+    });
+}
+
+extern "C" int32_t bbp_verify_rounds_best_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B, const uint32_t* round_of,
+                                              const void* rows_dev, const void* entropy_dev, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap,
+                                              uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_steps,
+                                              void* status_dev, void* stream) {
+    if (!ctx || !round_Ns || !rounds_dev || !rows_dev || !entropy_dev || !n_best || !n_candidates || !n_examined || !status_dev || (cap && !best_out))
+        return BBP_ERR_BAD_ARG;
+    bests_zero(R, n_best, n_candidates, n_examined, n_steps);
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_verify_rounds_best_dev");
+    bool done;
+    if (int32_t rc = bests_screen(ctx, "bbp_verify_rounds_best_dev", R, round_Ns, B, round_of, &done)) return rc;
+    if (done) return BBP_OK;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        if (R == 1) {
+            BestCall c(ctx, B, K, pick_stream(ctx, stream), false, false);
+            return best_run_dev(c, round_Ns[0], (const u8*)rounds_dev, (const u8*)rows_dev, (const u8*)entropy_dev, floors ? floors : BESTS_ZERO_FLOOR, tranche,
+                                BestOut{cap, best_out, n_best, n_candidates, n_examined, nullptr, n_steps}, (int32_t*)status_dev);
+        }
+        BestsCall c(ctx, R, B, K, tranche, pick_stream(ctx, stream), false);
+        return bests_run_dev(c, round_Ns, (const u8*)rounds_dev, round_of, (const u8*)rows_dev, (const u8*)entropy_dev, floors,
+                             BestsOut{cap, best_out, n_best, n_candidates, n_examined, n_steps}, (int32_t*)status_dev);
     });
 }
 

@@ -213,6 +213,8 @@ struct bbp_ctx {
     // (bbp_reserve does not size them); best_mu serialises the calls that use them, and is taken BEFORE the context lock.
     // The one-per-bidder calls (bbp_verify_round_best_distinct, ...) use the same allocations: BestDistinctLayout puts the rows' z_img,
     // the identity table and three counters behind BestLayout's state -- public for the same reason: what any verifier is handed.
+    // The many-rounds calls (bbp_verify_rounds_best, ...) with R > 1 lay the same allocations out by rounds_best.h's BestsLayout:
+    // per-round counters, segments and floors, round_of and row offsets beside the keys, records and statuses.
     std::mutex best_mu;
     bbp::DevBuf best_dev, best_rows;
     void* best_h = nullptr;

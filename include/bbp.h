@@ -82,6 +82,7 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *   bbp_prove_round_select  scoring and selection served by member 0, the selected bids proved as bbp_prove_round on the pool
  *   bbp_verify_round_best   keys, selection and marks served by member 0, every tranche verified as bbp_verify_rounds_aggregated on the pool
  *   bbp_verify_round_best_distinct   the same: keys, identities, selection and marks on member 0, tranches verified on the pool
+ *   bbp_verify_rounds_best  the same over many rounds: keys, segments, selection and marks on member 0, every step verified on the pool
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
@@ -468,6 +469,59 @@ int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, const void*
 int32_t bbp_debug_round_best_distinct(bbp_ctx* ctx, uint32_t B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts,
                                       const uint8_t floor32[32], uint32_t K, uint32_t tranche, uint32_t cap, uint32_t table_log2, uint32_t* best_out,
                                       uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status);
+
+/* Best valid proofs of many rounds: bbp_verify_round_best for every round of a bbp_verify_rounds call at once.  A node that is catching
+ * up holds B candidate rows spread over R rounds and wants the winner, or the K best, of every round.  round_Ns, rounds, round_of and
+ * rows are exactly bbp_verify_rounds' arguments: rows packed back to back in request order, row i of bbp_round_row_size(round_Ns[
+ * round_of[i]]) bytes, any mix of sizes; R <= BBP_BEST_MAX_ROUNDS, B <= BBP_SELECT_MAX_BIDS.  floors: R x 32 bytes, one floor32 per
+ * round, or NULL for all zero.
+ * The rule: let I_r be the rows with round_of[i] == r in ascending index.  The outputs for round r -- status[i] for i in I_r, n_best[r],
+ * n_candidates[r], n_examined[r] and best_out[r * cap ..], which receives min(n_best[r], cap) entries (entries beyond are not written) --
+ * are exactly what bbp_verify_round_best reports for the rows of I_r, round r of the table, floor floors[r] and the call's K, tranche
+ * and cap, with local row indices mapped back to indices into the call's rows (ascending global index is ascending local index: ties
+ * break the same way).  A round that no row names reports zeros.
+ *   steps         at step t = 0, 1, ... every round that has not stopped under the single-round stopping rule contributes its tranche
+ *                 t; with K == 0 there is one step, and it holds every candidate of every round.  All the rows of a step are verified
+ *                 together, and every one gets exactly the status bbp_verify_rounds reports for it.  A round that has stopped
+ *                 contributes nothing to later steps.  n_steps (may be NULL) is the number of steps that held at least one row: the
+ *                 maximum, over the rounds, of the tranches each round ran.
+ * Which rows are examined depends only on the inputs and `tranche`, never on timing.
+ * Screening of the arguments, before anything runs, the first failing check decides: a NULL required pointer BBP_ERR_BAD_ARG (best_out may
+ * be NULL only when cap == 0; floors and n_steps may be NULL); R == 0 or R > BBP_BEST_MAX_ROUNDS BBP_ERR_BAD_ARG; a 0 in round_Ns
+ * BBP_ERR_BAD_ARG, otherwise an entry above BBP_MAX_ITEMS BBP_ERR_GENS_LEN; B > BBP_SELECT_MAX_BIDS BBP_ERR_BAD_ARG; B == 0 BBP_OK with
+ * every count of every round zero; round_of == NULL with R > 1, or round_of[i] >= R, BBP_ERR_BAD_ARG.
+ * With R == 1 every form runs the single-round call above it (one large round is what that call's many-workgroup selection is for) and
+ * reports its tranches as n_steps.  With R > 1 a round is selected by ONE workgroup, in time linear in the round's candidates per
+ * pass: the intended shape is many rounds of modest size.
+ *
+ * bbp_verify_rounds_best, the host form (a context or a pool): only the 32 score bytes of every row go up, with round_of and the floors;
+ * keys, segments, selection and marks live on one device -- the context, or member 0 of a pool.  Per step the selected indices come down
+ * grouped by round in ascending round order, the rows are gathered from the caller's memory and verified in one rounds call through
+ * bbp_verify_rounds_aggregated's own path (so the pool split, BBP_HOST_CHUNK_VERIFY, the entropy source, verify mixing and the health
+ * word hold as they do there; the whole round table travels with every step), and the statuses go back up to mark the rows.  A row that
+ * is never examined never crosses PCIe.  Serialised with the other best calls of the context; bbp_reserve does NOT size the state.
+ *
+ * bbp_verify_rounds_best_dev, table, rows and entropy resident in device memory; a pool refuses it.  rows_dev may have any alignment;
+ * entropy_dev holds B x 32 bytes, row i for row i, gathered with its row.  round_Ns, round_of and floors are host arrays.  The host
+ * computes the byte offset of every row once and uploads them; a step's rows, of mixed sizes, are packed on the device and verified
+ * through bbp_verify_rounds_aggregated_dev's path in engine calls of at most BBP_HOST_CHUNK_VERIFY rows.  The call SYNCHRONISES `stream`:
+ * once after the keys are segmented (the per-round candidate counts), once per step (the per-round rows of the next step), and once to
+ * deliver.  The host outputs are valid on return; status_dev (B x int32) is complete on `stream`.  No host screening of device data.
+ *
+ * bbp_debug_rounds_best, test hook (synchronises; a pool refuses it): the shipped kernels on caller-made keys (B x 32 bytes) and
+ * verdicts (B x int32, each BBP_OK, BBP_ERR_VERIFY or BBP_ERR_FORMAT); nothing is verified.  BBP_ERR_BAD_ARG, nothing launched, also for
+ * B == 0 and for a verdict outside the three. */
+#define BBP_BEST_MAX_ROUNDS (1u << 16)
+int32_t bbp_verify_rounds_best(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                               const uint8_t* rows, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best,
+                               uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_steps, int32_t* status);
+int32_t bbp_verify_rounds_best_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B, const uint32_t* round_of,
+                                   const void* rows_dev, const void* entropy_dev, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap,
+                                   uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_steps, void* status_dev,
+                                   void* stream);
+int32_t bbp_debug_rounds_best(bbp_ctx* ctx, uint32_t R, uint32_t B, const uint32_t* round_of, const uint8_t* keys, const int32_t* verdicts,
+                              const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates,
+                              uint32_t* n_examined, uint32_t* n_steps, int32_t* status);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.

@@ -18,6 +18,13 @@ One JSON line per cell, to stdout and to --out (default profiles/r19_round_best.
           tests/round_best_distinct_cases.py on the verdicts of the third arm; the tranche count is the model's.  Also traffic (a)
           with K = 1, new call against existing call in the same run.
 
+  --rounds OUT   instead of the above: bbp_verify_rounds_best ("Best valid proofs of many rounds") on 8192 rows over 202 rounds (row i in
+          round i mod 202), every round at N = 8, and rounds cycling through N = 8, 50, 120, 202; K = 1, tranche 16, into OUT
+          (profiles/r22_rounds_best.jsonl).  Traffic: honest / the top 1 % of each round (at least one row) forged / all forged.  Arms:
+          A the new call (host, dev); B a loop of bbp_verify_round_best calls, one per round (host, dev); C
+          bbp_verify_rounds_aggregated over everything, then the pick per round on the host.  Rows examined and steps are asserted
+          equal to what the rules predict; the three arms must name the same winners.  Rounds of one length reuse one proved table.
+
 Rows are 64 proved bids of the round repeated (byte-equal rows do occur in the protocol too); arms alternate in one process; every figure
 is the best of --calls calls, taken --runs times after a warm-up: median and range."""
 import argparse
@@ -281,8 +288,148 @@ def distinct_main(args):
             ctx.close()
 
 
+FOUR_LENGTHS = (8, 50, 120, 202)  # tools/verify_combine.py's four_values
+
+
+def rounds_main(args):
+    """--rounds: bbp_verify_rounds_best against the two routes a caller had before, 8192 rows over 202 rounds"""
+    import numpy as np
+    import torch
+    torch.cuda.init()
+    import dusk_blindbidproof_amd as bbp
+    from tests import prove_round_cases as rc
+    box = box_id()
+    os.makedirs(os.path.dirname(os.path.abspath(args.rounds)), exist_ok=True)
+    B, R, K, tranche, n_base = 8192, 202, 1, 16, 16
+    unit = "ms of host time per call, best of %d, %d runs after a warm-up" % (args.calls, args.runs)
+    with open(args.rounds, "w") as f:
+        def emit(rec):
+            rec.update(box=box, commit=args.commit)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        ctx = bbp.Context(0)
+        lib, h = bbp.lib, ctx.handle
+        try:
+            base = {}
+            for N in sorted(set(FOUR_LENGTHS)):
+                r = rc.honest(N, n_base, tag=22)
+                rows, _t, st = ctx.prove_round(N, r.table, r.bid_bytes)
+                assert st == [0] * n_base
+                size = bbp.round_row_size(N)
+                base[N] = ([rows[size * i:size * (i + 1)] for i in range(n_base)], r.table)
+            stream = torch.cuda.Stream()
+            for mix, lengths in (("n8", (8,)), ("four_lengths", FOUR_LENGTHS)):
+                Ns = [lengths[r % len(lengths)] for r in range(R)]  # (rounds of one length share the table's bytes: the cost is the same)
+                table = b"".join(base[N][1] for N in Ns)
+                round_of = [i % R for i in range(B)]
+                members = [[i for i in range(B) if i % R == r] for r in range(R)]
+                for tname, frac in (("honest", 0.0), ("top_1pct_of_each_round_forged", 0.01), ("all_forged", 1.0)):
+                    row_list = [base[Ns[i % R]][0][(i // R) % n_base] for i in range(B)]
+                    key_off = [bbp.record_size(Ns[i % R]) for i in range(B)]
+                    keys = [int.from_bytes(row_list[i][key_off[i]:key_off[i] + 32], "little") for i in range(B)]
+                    order = [sorted(m, key=lambda i: (-keys[i], i)) for m in members]
+                    forged = [0 if frac == 0 else max(1, int(round(frac * len(m)))) for m in members]
+                    for r in range(R):
+                        for i in order[r][:forged[r]]:
+                            b = bytearray(row_list[i])
+                            b[T_X] ^= 0x01
+                            row_list[i] = bytes(b)
+                    want_best = [order[r][forged[r]] if forged[r] < len(order[r]) else None for r in range(R)]
+                    pred = [predict(len(members[r]), forged[r], K, tranche) for r in range(R)]
+                    rows = bytearray(b"".join(row_list))
+                    c_rows = (ctypes.c_uint8 * len(rows)).from_buffer(rows)
+                    c_table = (ctypes.c_uint8 * len(table)).from_buffer_copy(table)
+                    c_ns, c_ro = (ctypes.c_uint32 * R)(*Ns), (ctypes.c_uint32 * B)(*round_of)
+                    d_rows = torch.frombuffer(rows, dtype=torch.uint8).cuda()
+                    d_table = torch.frombuffer(bytearray(table), dtype=torch.uint8).cuda()
+                    d_ent = torch.randint(0, 256, (32 * B,), dtype=torch.uint8, device="cuda")
+                    d_status = torch.zeros(4 * B, dtype=torch.uint8, device="cuda")
+                    status = (ctypes.c_int32 * B)()
+                    best, nb, nc, ne = ((ctypes.c_uint32 * R)() for _ in range(4))
+                    steps, nfb = ctypes.c_uint32(), ctypes.c_uint32()
+                    floor = (ctypes.c_uint8 * 32)()
+                    # arm B's inputs: every round's rows and table on their own, host and device
+                    per = []
+                    for r in range(R):
+                        blob = bytearray(b"".join(row_list[i] for i in members[r]))
+                        tab = base[Ns[r]][1]
+                        per.append(((ctypes.c_uint8 * len(blob)).from_buffer(blob), (ctypes.c_uint8 * len(tab)).from_buffer_copy(tab),
+                                    torch.frombuffer(blob, dtype=torch.uint8).cuda(), torch.frombuffer(bytearray(tab), dtype=torch.uint8).cuda(),
+                                    (ctypes.c_int32 * len(members[r]))()))
+                    one, n3 = (ctypes.c_uint32 * 1)(), [ctypes.c_uint32() for _ in range(3)]
+                    p3 = [ctypes.byref(x) for x in n3]
+
+                    def answer():
+                        return [best[r] if nb[r] else None for r in range(R)], list(ne), steps.value
+
+                    def a_host():
+                        rc_ = lib.bbp_verify_rounds_best(h, R, c_ns, c_table, B, c_ro, c_rows, None, K, tranche, 1, best, nb, nc, ne, ctypes.byref(steps), status)
+                        assert rc_ == 0, (rc_, lib.bbp_last_error(h))
+                        return answer()
+
+                    def a_dev():
+                        rc_ = lib.bbp_verify_rounds_best_dev(h, R, c_ns, d_table.data_ptr(), B, c_ro, d_rows.data_ptr(), d_ent.data_ptr(), None, K, tranche, 1, best,
+                                                             nb, nc, ne, ctypes.byref(steps), d_status.data_ptr(), stream.cuda_stream)
+                        assert rc_ == 0, (rc_, lib.bbp_last_error(h))
+                        stream.synchronize()
+                        return answer()
+
+                    def b_host():
+                        out, exam = [], []
+                        for r in range(R):
+                            hb, ht, _db, _dt, st_ = per[r]
+                            assert lib.bbp_verify_round_best(h, Ns[r], ht, len(members[r]), hb, floor, K, tranche, 1, one, p3[0], p3[1], p3[2], st_) == 0
+                            out.append(members[r][one[0]] if n3[0].value else None)
+                            exam.append(n3[2].value)
+                        return out, exam
+
+                    def b_dev():
+                        out, exam = [], []
+                        for r in range(R):
+                            _hb, _ht, db, dt, _st = per[r]
+                            assert lib.bbp_verify_round_best_dev(h, Ns[r], dt.data_ptr(), len(members[r]), db.data_ptr(), d_ent.data_ptr(), floor, K, tranche, 1, one,
+                                                                 p3[0], p3[1], p3[2], d_status.data_ptr(), stream.cuda_stream) == 0
+                            out.append(members[r][one[0]] if n3[0].value else None)
+                            exam.append(n3[2].value)
+                        stream.synchronize()
+                        return out, exam
+
+                    def c_host():
+                        assert lib.bbp_verify_rounds_aggregated(h, R, c_ns, c_table, B, c_ro, c_rows, status, 0, ctypes.byref(nfb)) == 0
+                        st_ = np.frombuffer(status, dtype="<i4")
+                        return [next((i for i in order[r] if st_[i] == 0), None) for r in range(R)]
+                    arms = {"rounds_best_host": a_host, "rounds_best_dev": a_dev, "loop_of_round_best_host": b_host, "loop_of_round_best_dev": b_dev,
+                            "all_then_pick_host": c_host}
+                    want = (want_best, [p[0] for p in pred], max(p[1] for p in pred))
+                    assert a_host() == want and a_dev() == want, (a_host()[1:], want[1:])  # nothing here is tuned: the rules predict it
+                    assert b_host() == want[:2] and b_dev() == want[:2] and c_host() == want_best
+                    examined = sum(want[1])
+                    row_bytes = [len(x) for x in row_list]
+                    up_rows = sum(row_bytes[i] + 32 + 4 for r in range(R) for i in order[r][:pred[r][0]])
+                    rec = {"section": "rounds", "mix": mix, "B": B, "R": R, "traffic": tname, "K": K, "tranche": tranche, "rows_examined": examined,
+                           "steps": want[2], "tranches_of_the_loop": sum(p[1] for p in pred), "unit": unit}
+                    rec.update(timed(arms, list(arms), args))
+                    rec["bytes_uploaded"] = {"rounds_best_host": 32 * B + 4 * B + up_rows + want[2] * len(table),
+                                             "loop_of_round_best_host": 32 * B + up_rows + sum(pred[r][1] * 32 * (1 + Ns[r]) for r in range(R)),
+                                             "all_then_pick_host": sum(row_bytes) + 32 * B + len(table)}
+                    for form in ("host", "dev"):
+                        a, b = rec["rounds_best_" + form], rec["loop_of_round_best_" + form]
+                        rec["A_over_B_" + form] = round(a["median"] / b["median"], 4)
+                        rec["A_beats_B_by_more_than_B_range_" + form] = b["median"] - a["median"] > b["max"] - b["min"]
+                    a, cc = rec["rounds_best_host"], rec["all_then_pick_host"]
+                    rec["A_over_C_host"] = round(a["median"] / cc["median"], 4)
+                    rec["A_beats_C_by_more_than_C_range_host"] = cc["median"] - a["median"] > cc["max"] - cc["min"]
+                    emit(rec)
+            assert ctx.health() == 0
+        finally:
+            ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", default="", metavar="OUT", help="measure bbp_verify_rounds_best instead, into OUT (profiles/r22_rounds_best.jsonl)")
     ap.add_argument("--distinct", default="", metavar="OUT", help="measure bbp_verify_round_best_distinct instead, into OUT")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19_round_best.jsonl"))
     ap.add_argument("--commit", default="")
@@ -290,6 +437,8 @@ def main():
     ap.add_argument("--calls", type=int, default=2)
     ap.add_argument("--sections", default="cells,sweep")
     args = ap.parse_args()
+    if args.rounds:
+        return rounds_main(args)
     if args.distinct:
         return distinct_main(args)
     import numpy as np
