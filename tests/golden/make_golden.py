@@ -3,7 +3,8 @@
 
 The reference holds no fixtures of its own and cannot be built here (no Rust toolchain,
 SURVEY.md F4), so these vectors are produced by the build's own restatement; the public KATs that pin the
-restatement's primitives live in tests/test_oracle_kat.py.  Usage:  python tests/golden/make_golden.py [--full]
+restatement's primitives live in tests/test_oracle_kat.py.  Usage:  python tests/golden/make_golden.py [--full | --noncanonical | --edge]
+(--edge: proofs_edge.json alone, three proofs, about a minute)
 """
 import hashlib
 import json
@@ -75,7 +76,48 @@ def case_noncanonical(name, N, toggle):
                 proof_len=len(pr.proof.to_bytes()), record=rec.hex(), trace=trace)
 
 
+class _BigIntWitness:
+    """oc.witness of the C oracle's loader, from the big-int oracle: d || k || seed -> m, x, y, y_inv, q, z_img"""
+
+    def __init__(self):
+        self.cons = bb.mimc_constants()
+
+    def witness(self, dks):
+        d, k, seed = (int.from_bytes(dks[32 * i:32 * i + 32], "little") for i in range(3))
+        w = bb.witness(d, k, seed, self.cons)
+        return b"".join(rs.sc_bytes(w[n]) for n in ("m", "x", "y", "y_inv", "q", "z_img"))
+
+
+def case_edge(r):
+    """One row of tests/edge_witness_cases.py (witness and blindings at their edges) in the fields of case().  `entropy` is the row as it
+    travels: blindings that are not reduced stay so in the fixture; the prover reduces them (sc_wide here, sc_reduce256 on the device)."""
+    from tests import edge_witness_cases as ew
+    d, k, y, y_inv, q, z_img, seed = r["f"]
+    w = bb.witness(d, k, seed)
+    assert (w["y"], w["y_inv"], w["q"], w["z_img"], w["x"]) == (y, y_inv, q, z_img, r["x"])
+    pub = [int.from_bytes(p, "little") for p in r["pub"]]
+    name = "edge_%s_n%d" % (r["name"], r["N"])
+    trace = {}
+    t0 = time.time()
+    pr = bb.prove(d, k, y, y_inv, q, z_img, seed, pub, r["toggle"], r["ent"], trace=trace)
+    t1 = time.time()
+    rec = pr.to_record()
+    assert bb.verify(bb.Proof.from_record(rec, r["N"]), q, z_img, seed, pub, bytes(32))
+    assert ew.identity_slots(rec, r["N"]) == set(r["identity_V"]) and (q == 0) == r["score_zero"]
+    print(name, "prove %.1fs verify %.1fs" % (t1 - t0, time.time() - t1), "identity V", sorted(r["identity_V"]))
+    sc = lambda v: rs.sc_bytes(v).hex()
+    return dict(name=name, case=r["name"], rounds=90, cap=2048, N=r["N"], toggle=r["toggle"],
+                d=sc(d), k=sc(k), seed=sc(seed), m=sc(w["m"]), x=sc(w["x"]), y=sc(y), y_inv=sc(y_inv),
+                q=sc(q), z_img=sc(z_img), pub_list=[p.hex() for p in r["pub"]], entropy=r["ent"].hex(),
+                proof_len=len(pr.proof.to_bytes()), record=rec.hex(), trace=trace)
+
+
 def main():
+    if "--edge" in sys.argv:
+        from tests import edge_witness_cases as ew
+        out = {"edge": [case_edge(r) for r in ew.golden_rows(_BigIntWitness())]}
+        json.dump(out, open(os.path.join(HERE, "proofs_edge.json"), "w"), indent=1)
+        return
     if "--noncanonical" in sys.argv:
         out = {"noncanonical": [case_noncanonical("noncanon_n7", 7, 4)]}
         json.dump(out, open(os.path.join(HERE, "proofs_noncanonical.json"), "w"), indent=1)
