@@ -94,6 +94,9 @@ SIGNATURES = {
     "bbp_verify_rounds_best": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_rounds_best_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_rounds_best": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_rounds_best_distinct": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_verify_rounds_best_distinct_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_rounds_best_distinct": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_set_prove_check": (_i32, [_vp, _i32]),
     "bbp_prove_check_stats": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_prove_batch_checked_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -252,6 +255,8 @@ BEST_MAX_ROUNDS = 1 << 16   # BBP_BEST_MAX_ROUNDS
 # per round: best (a list of row indices in rank order, at most cap), n_best, n_candidates, n_examined, raw (the round's cap entries as
 # the call left them); n_steps and the B statuses for the call
 RoundsBest = collections.namedtuple("RoundsBest", "best n_best n_candidates n_examined n_steps status raw")
+# ... one per bidder: n_duplicates per round as well
+RoundsBestDistinct = collections.namedtuple("RoundsBestDistinct", "best n_best n_candidates n_examined n_duplicates n_steps status raw")
 
 
 def rounds_floors(floors, R):
@@ -687,6 +692,53 @@ class Context:
                                               ctypes.byref(counts[3]), status))
         return self._bests_result(R, B, cap, best, status, counts)
 
+    def verify_rounds_best_distinct(self, round_Ns, table, round_of, rows, floors=None, K=1, tranche=0, cap=None, fill=0, B=None):
+        """bbp_verify_rounds_best_distinct: verify_round_best_distinct for every round of a verify_rounds call at once; identities (z_img)
+        belong to their round.  Arguments as verify_rounds_best.  Returns a RoundsBestDistinct (n_duplicates: per round)."""
+        R = len(round_Ns)
+        if B is None:
+            B = len(round_of) if round_of is not None else len(rows) // round_row_size(round_Ns[0])
+        cap, best, status, counts = self._bests_buffers(R, B, K, cap, fill)
+        dups = (_u32 * max(1, R))()
+        fl = rounds_floors(floors, R)
+        self._check(lib.bbp_verify_rounds_best_distinct(self._h, R, _u32s(round_Ns), _buf(table), B, _u32s(round_of), _buf(rows) if B else best,
+                                                        None if fl is None else _buf(fl), K, tranche, cap, best, counts[0], counts[1], counts[2], dups,
+                                                        ctypes.byref(counts[3]), status))
+        return self._bests_distinct_result(R, B, cap, best, status, counts, dups)
+
+    def verify_rounds_best_distinct_dev(self, round_Ns, table_ptr, round_of, B, rows_ptr, ent_ptr, status_ptr, floors=None, K=1, tranche=0, cap=None,
+                                        stream=None, fill=0):
+        """bbp_verify_rounds_best_distinct_dev: as verify_rounds_best_dev.  Returns a RoundsBestDistinct whose status is None: the B
+        statuses are at status_ptr, complete on `stream`."""
+        R = len(round_Ns)
+        cap, best, _, counts = self._bests_buffers(R, B, K, cap, fill)
+        dups = (_u32 * max(1, R))()
+        fl = rounds_floors(floors, R)
+        self._check(lib.bbp_verify_rounds_best_distinct_dev(self._h, R, _u32s(round_Ns), table_ptr, B, _u32s(round_of), rows_ptr, ent_ptr,
+                                                            None if fl is None else _buf(fl), K, tranche, cap, best, counts[0], counts[1], counts[2], dups,
+                                                            ctypes.byref(counts[3]), status_ptr, _stream(stream)))
+        return self._bests_distinct_result(R, B, cap, best, None, counts, dups)
+
+    def debug_rounds_best_distinct(self, R, round_of, keys, ids, verdicts, floors=None, K=1, tranche=0, cap=None, table_log2=0, fill=0):
+        """bbp_debug_rounds_best_distinct (test hook): the shipped kernels of the many-rounds one-per-bidder calls on made-up keys and ids
+        (B x 32 bytes each) and verdicts; nothing is verified.  table_log2: 0, or an explicit size of the identity table.  Returns a
+        RoundsBestDistinct."""
+        B = len(verdicts)
+        if len(keys) != 32 * B or len(ids) != 32 * B or (round_of is not None and len(round_of) != B):
+            raise ValueError("keys and ids are 32 bytes and round_of one entry per verdict")
+        cap, best, status, counts = self._bests_buffers(R, B, K, cap, fill)
+        dups = (_u32 * max(1, R))()
+        fl = rounds_floors(floors, R)
+        self._check(lib.bbp_debug_rounds_best_distinct(self._h, R, B, _u32s(round_of), _buf(keys) if B else best, _buf(ids) if B else best,
+                                                       (ctypes.c_int32 * max(1, B))(*verdicts), None if fl is None else _buf(fl), K, tranche, cap, table_log2,
+                                                       best, counts[0], counts[1], counts[2], dups, ctypes.byref(counts[3]), status))
+        return self._bests_distinct_result(R, B, cap, best, status, counts, dups)
+
+    @staticmethod
+    def _bests_distinct_result(R, B, cap, best, status, counts, dups):
+        r = Context._bests_result(R, B, cap, best, status, counts)
+        return RoundsBestDistinct(r.best, r.n_best, r.n_candidates, r.n_examined, list(dups)[:R], r.n_steps, r.status, r.raw)
+
     @staticmethod
     def _bests_buffers(R, B, K, cap, fill):
         if cap is None:
@@ -933,7 +985,7 @@ class Context:
 class Pool(Context):
     """A device pool (include/bbp.h "Device pool"): one handle, one engine context per GPU behind it.  Takes the host-pointer
     calls of Context -- prove / verify (combined and dealt to the least-loaded member), prove_batch / verify_batch /
-    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best / verify_round_best_distinct / verify_rounds_best (member 0 selects, the pool verifies); the device-pointer calls
+    verify_batch_aggregated / verify_batch_mixed[_aggregated] / verify_rounds[_aggregated] / verify_round / prove_round / msm_batch (block-split over the members, results in request order), prove_round_select (member 0 selects, the pool proves), verify_round_best / verify_round_best_distinct / verify_rounds_best / verify_rounds_best_distinct (member 0 selects, the pool verifies); the device-pointer calls
     need a member (`pool.member(i)`).  devices=None -> every visible GPU (bbp_init_all)."""
 
     def __init__(self, devices=None):
@@ -979,6 +1031,11 @@ class Pool(Context):
         """bbp_verify_round_best_distinct on the pool: member 0 keeps the keys and identities, selects, marks and drops; every tranche is
         verified as verify_rounds_aggregated verifies it (block-split over the members)."""
         return super().verify_round_best_distinct(N, table, rows, floor, K, tranche, cap, fill)
+
+    def verify_rounds_best_distinct(self, round_Ns, table, round_of, rows, floors=None, K=1, tranche=0, cap=None, fill=0, B=None):
+        """bbp_verify_rounds_best_distinct on the pool: member 0 keeps the keys, identities and segments, selects, marks and drops; every
+        step is verified as verify_rounds_aggregated verifies it (block-split over the members)."""
+        return super().verify_rounds_best_distinct(round_Ns, table, round_of, rows, floors, K, tranche, cap, fill, B)
 
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""

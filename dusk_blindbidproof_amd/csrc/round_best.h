@@ -238,8 +238,10 @@ BBP_HD u32 best_table_find(const u32* table, u32 mask, const u32* ids, const u32
 // has verified OK; its holder is the first such row in candidate order.  Tranche t is the next min(T_t, live) live candidates; all are
 // verified and keep their true status.  Stop after the first tranche that leaves >= K identities settled (K > 0) or when no live
 // candidate is left; otherwise every live candidate of a settled identity becomes BBP_ROW_DUPLICATE and leaves, before the next tranche.
+// n_tranches (may be null): the tranches that ran, counted.
 inline void round_best_distinct_host(u32 B, const u32* keys, const u32* ids, const int32_t* verdicts, const u32* floor, u32 K, u32 tranche, u32 cap,
-                                     u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status) {
+                                     u32* best_out, u32* n_best, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status,
+                                     u32* n_tranches = nullptr) {
     std::vector<u32> live, holders;
     for (u32 i = 0; i < B; i++) {
         const int32_t s = best_screen_key(keys + 8 * (size_t)i, floor);
@@ -253,9 +255,10 @@ inline void round_best_distinct_host(u32 B, const u32* keys, const u32* ids, con
         return false;
     };
     const u32 nc = (u32)live.size(), T0 = best_tranche0(K, tranche, nc);
-    u32 examined = 0, dups = 0;
+    u32 examined = 0, dups = 0, ran = 0;
     for (u32 t = 0; !live.empty(); t++) {
         const u32 n = best_tranche_rows(T0, t, (u32)live.size());
+        ran = t + 1;
         for (u32 j = 0; j < n; j++) {
             const u32 i = live[j];
             status[i] = verdicts[i];
@@ -276,6 +279,7 @@ inline void round_best_distinct_host(u32 B, const u32* keys, const u32* ids, con
     const u32 nb = K && holders.size() > K ? K : (u32)holders.size();
     for (u32 j = 0; j < nb && j < cap; j++) best_out[j] = holders[j];
     *n_best = nb, *n_candidates = nc, *n_examined = examined, *n_duplicates = dups;
+    if (n_tranches) *n_tranches = ran;
 }
 
 // The extra state of a one-per-bidder call, behind the state BestLayout(B, false) describes (same allocations: the context's best_dev and

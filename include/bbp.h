@@ -83,11 +83,12 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *   bbp_verify_round_best   keys, selection and marks served by member 0, every tranche verified as bbp_verify_rounds_aggregated on the pool
  *   bbp_verify_round_best_distinct   the same: keys, identities, selection and marks on member 0, tranches verified on the pool
  *   bbp_verify_rounds_best  the same over many rounds: keys, segments, selection and marks on member 0, every step verified on the pool
+ *   bbp_verify_rounds_best_distinct   the same, one per bidder: identities and drops on member 0 as well, every step verified on the pool
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
  * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_debug_round_best,
- * bbp_debug_round_best_distinct, bbp_set_profiling /
+ * bbp_debug_round_best_distinct, bbp_debug_rounds_best, bbp_debug_rounds_best_distinct, bbp_set_profiling /
  * bbp_last_timings; the stream getters return NULL. */
 int32_t bbp_init_all(bbp_ctx** out);
 int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp_ctx** out);
@@ -522,6 +523,55 @@ int32_t bbp_verify_rounds_best_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* rou
 int32_t bbp_debug_rounds_best(bbp_ctx* ctx, uint32_t R, uint32_t B, const uint32_t* round_of, const uint8_t* keys, const int32_t* verdicts,
                               const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates,
                               uint32_t* n_examined, uint32_t* n_steps, int32_t* status);
+
+/* Best proofs of many rounds, one per bidder: bbp_verify_round_best_distinct for every round of a bbp_verify_rounds call at once.  A node
+ * that gathers gossip from several peers holds resent proofs as a matter of course; with K > 1 bbp_verify_rounds_best lets the copies
+ * take the places of the real runners-up, and bbp_verify_round_best_distinct repairs that for one round per call only.  Inputs as
+ * bbp_verify_rounds_best; id[i] is the 32 raw z_img bytes of row i, as for bbp_verify_round_best_distinct.
+ * The rule: let I_r be the rows with round_of[i] == r in ascending index.  The outputs for round r -- status[i] for i in I_r, n_best[r],
+ * n_candidates[r], n_examined[r], n_duplicates[r] and best_out[r * cap ..], which receives min(n_best[r], cap) entries (entries beyond are
+ * not written) -- are exactly what bbp_verify_round_best_distinct reports for the rows of I_r, round r of the table, floor floors[r] and
+ * the call's K, tranche and cap, with local row indices mapped back to indices into the call's rows.  A round that no row names reports
+ * zeros.
+ *   identities    belong to a round: the same 32 z_img bytes in two rounds are two identities (z_img depends on the seed; and a table may
+ *                 list two rounds with equal seeds: still two rounds)
+ *   steps         step t holds tranche t of every round that has not stopped under the single-round one-per-bidder rule: K identities
+ *                 settled in it, or no live candidate left.  All the rows of a step are verified in one engine call, and every one gets
+ *                 exactly the status bbp_verify_rounds reports for it
+ *   drop pass     before round r's next tranche, live candidates of r whose identity is settled in r leave with BBP_ROW_DUPLICATE.  A
+ *                 round that has stopped runs no drop pass: its unreached rows keep BBP_ROW_SKIPPED even when their identity is settled,
+ *                 and even while other rounds go on for more steps
+ *   n_steps       (may be NULL) the largest number of tranches any round ran; under drops it is counted, not derived from n_examined
+ * n_examined[r] + n_duplicates[r] <= n_candidates[r].  Which rows are examined depends only on the inputs and `tranche`, never on timing.
+ * n_duplicates (R entries) is a required pointer; floors and n_steps may be NULL; screening of the arguments and its order are exactly
+ * bbp_verify_rounds_best's.  With R == 1 every form runs the single-round one-per-bidder call and reports its tranches as n_steps.
+ *
+ * bbp_verify_rounds_best_distinct, the host form (a context or a pool): 64 bytes of every row go up, score || z_img, with round_of and
+ * the floors; keys, identities, segments, selection, marks and drops live on one device -- the context, or member 0 of a pool.  The
+ * device plans every step from its own counters (the host knows the verdicts, not the identities): one submission per step carries the
+ * statuses of the step before up and brings the next step's rows down, which are gathered from the caller's memory and verified through
+ * bbp_verify_rounds_aggregated's own path, as for bbp_verify_rounds_best.  A row that is never examined and a duplicate row never cross
+ * PCIe.  Serialised with the other best calls of the context; bbp_reserve does NOT size the state.
+ *
+ * bbp_verify_rounds_best_distinct_dev: as bbp_verify_rounds_best_dev, the same synchronisation points; z_img is read byte by byte at any
+ * alignment.  status_dev is complete on `stream`.  No host screening of device data.  A pool refuses it.
+ *
+ * bbp_debug_rounds_best_distinct, test hook (synchronises; a pool refuses it): as bbp_debug_rounds_best, plus ids (B x 32 bytes, any
+ * values) and table_log2 under the rules of bbp_debug_round_best_distinct: 0 for the call's own sizing of the ONE identity table of the
+ * call (the least 2^s >= 2 B slots), or 2^table_log2 slots.  BBP_ERR_BAD_ARG, nothing launched, also when table_log2 > 21, or when
+ * table_log2 > 0 and 2^table_log2 is not greater than the number of BBP_OK verdicts. */
+int32_t bbp_verify_rounds_best_distinct(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const uint8_t* rounds, uint32_t B, const uint32_t* round_of,
+                                        const uint8_t* rows, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t* best_out,
+                                        uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, uint32_t* n_steps,
+                                        int32_t* status);
+int32_t bbp_verify_rounds_best_distinct_dev(bbp_ctx* ctx, uint32_t R, const uint32_t* round_Ns, const void* rounds_dev, uint32_t B,
+                                            const uint32_t* round_of, const void* rows_dev, const void* entropy_dev, const uint8_t* floors, uint32_t K,
+                                            uint32_t tranche, uint32_t cap, uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates,
+                                            uint32_t* n_examined, uint32_t* n_duplicates, uint32_t* n_steps, void* status_dev, void* stream);
+int32_t bbp_debug_rounds_best_distinct(bbp_ctx* ctx, uint32_t R, uint32_t B, const uint32_t* round_of, const uint8_t* keys, const uint8_t* ids,
+                                       const int32_t* verdicts, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t table_log2,
+                                       uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates,
+                                       uint32_t* n_steps, int32_t* status);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.

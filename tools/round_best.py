@@ -25,6 +25,16 @@ One JSON line per cell, to stdout and to --out (default profiles/r19_round_best.
           bbp_verify_rounds_aggregated over everything, then the pick per round on the host.  Rows examined and steps are asserted
           equal to what the rules predict; the three arms must name the same winners.  Rounds of one length reuse one proved table.
 
+  --rounds-distinct OUT   instead of the above: bbp_verify_rounds_best_distinct ("Best proofs of many rounds, one per bidder") on 8192
+          rows over 202 rounds (the --rounds shape: row i in round i mod 202), K = 3, tranche 16, into OUT
+          (profiles/r23_rounds_best_distinct.jsonl).  Every round holds 40 or 41 bidders, so every round is at N = 50: a list of 8 items
+          holds 8 bids.  Traffic: no duplicates / a flood: each round's best bidder resent eight times (byte-equal, in place
+          of the round's eight lowest claims) / a forged flood: those eight copies claim a raised score and fail.  Arms: the new call
+          (host, dev); one bbp_verify_round_best_distinct per round; the plain bbp_verify_rounds_best (under a flood its answer holds
+          the copies: here for cost); bbp_verify_rounds_aggregated over everything with a de-duplicating pick per round on the host.
+          The new call's outputs are asserted equal to the model of tests/rounds_best_distinct_cases.py on the verdicts of the last
+          arm, and to the loop's; without duplicates it must examine exactly the rows the plain call examines.
+
 Rows are 64 proved bids of the round repeated (byte-equal rows do occur in the protocol too); arms alternate in one process; every figure
 is the best of --calls calls, taken --runs times after a warm-up: median and range."""
 import argparse
@@ -427,8 +437,149 @@ def rounds_main(args):
             ctx.close()
 
 
+def rounds_distinct_main(args):
+    """--rounds-distinct: bbp_verify_rounds_best_distinct against the three routes a caller had before, 8192 rows over 202 rounds"""
+    import numpy as np
+    import torch
+    torch.cuda.init()
+    import dusk_blindbidproof_amd as bbp
+    from tests import prove_round_cases as rc
+    from tests import rounds_best_distinct_cases as mdc
+    box = box_id()
+    os.makedirs(os.path.dirname(os.path.abspath(args.rounds_distinct)), exist_ok=True)
+    B, R, K, tranche, N, n_base, copies = 8192, 202, 3, 16, 50, 41, 8
+    L = mdc.L
+    unit = "ms of host time per call, best of %d, %d runs after a warm-up" % (args.calls, args.runs)
+    with open(args.rounds_distinct, "w") as f:
+        def emit(rec):
+            rec.update(box=box, commit=args.commit)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        ctx = bbp.Context(0)
+        lib, h = bbp.lib, ctx.handle
+        try:
+            r0 = rc.honest(N, n_base, tag=23)
+            proved, _t, st = ctx.prove_round(N, r0.table, r0.bid_bytes)
+            assert st == [0] * n_base
+            size, key_off = bbp.round_row_size(N), bbp.record_size(N)
+            base = [proved[size * i:size * (i + 1)] for i in range(n_base)]
+            assert len({x[-32:] for x in base}) == n_base  # every bid a bidder of its own
+            score = lambda x: int.from_bytes(x[key_off:key_off + 32], "little")
+            Ns, table = [N] * R, r0.table * R  # (the rounds share the table's bytes: identities belong to a round all the same)
+            round_of = [i % R for i in range(B)]
+            members = [[i for i in range(B) if i % R == r] for r in range(R)]
+            stream = torch.cuda.Stream()
+            for tname in ("no_duplicates", "flood", "forged_flood"):
+                row_list = [base[i // R] for i in range(B)]
+                for r in range(R):
+                    order = sorted(members[r], key=lambda i: (-score(row_list[i]), i))
+                    if tname != "no_duplicates":
+                        top = row_list[order[0]]
+                        if tname == "forged_flood":
+                            top = top[:key_off] + (L - 1).to_bytes(32, "little") + top[key_off + 32:]
+                        for i in order[-copies:]:
+                            row_list[i] = top
+                keys, ids = [score(x) for x in row_list], [x[-32:] for x in row_list]
+                rows = bytearray(b"".join(row_list))
+                c_rows = (ctypes.c_uint8 * len(rows)).from_buffer(rows)
+                c_table = (ctypes.c_uint8 * len(table)).from_buffer_copy(table)
+                c_ns, c_ro = (ctypes.c_uint32 * R)(*Ns), (ctypes.c_uint32 * B)(*round_of)
+                d_rows = torch.frombuffer(rows, dtype=torch.uint8).cuda()
+                d_table = torch.frombuffer(bytearray(table), dtype=torch.uint8).cuda()
+                d_ent = torch.randint(0, 256, (32 * B,), dtype=torch.uint8, device="cuda")
+                d_status = torch.zeros(4 * B, dtype=torch.uint8, device="cuda")
+                status = (ctypes.c_int32 * B)()
+                best = (ctypes.c_uint32 * (R * K))()
+                nb, nc, ne, nd = ((ctypes.c_uint32 * R)() for _ in range(4))
+                steps, nfb = ctypes.c_uint32(), ctypes.c_uint32()
+                floor = (ctypes.c_uint8 * 32)()
+                per = []
+                for r in range(R):
+                    blob = bytearray(b"".join(row_list[i] for i in members[r]))
+                    per.append(((ctypes.c_uint8 * len(blob)).from_buffer(blob), (ctypes.c_uint8 * len(r0.table)).from_buffer_copy(r0.table),
+                                (ctypes.c_int32 * len(members[r]))()))
+                k3, n4 = (ctypes.c_uint32 * K)(), [ctypes.c_uint32() for _ in range(4)]
+                p4 = [ctypes.byref(x) for x in n4]
+
+                def answer(dups=True):
+                    return [list(best[r * K:r * K + min(nb[r], K)]) for r in range(R)], list(ne), list(nd) if dups else None, steps.value
+
+                def new_host():
+                    rc_ = lib.bbp_verify_rounds_best_distinct(h, R, c_ns, c_table, B, c_ro, c_rows, None, K, tranche, K, best, nb, nc, ne, nd, ctypes.byref(steps),
+                                                              status)
+                    assert rc_ == 0, (rc_, lib.bbp_last_error(h))
+                    return answer()
+
+                def new_dev():
+                    rc_ = lib.bbp_verify_rounds_best_distinct_dev(h, R, c_ns, d_table.data_ptr(), B, c_ro, d_rows.data_ptr(), d_ent.data_ptr(), None, K, tranche,
+                                                                  K, best, nb, nc, ne, nd, ctypes.byref(steps), d_status.data_ptr(), stream.cuda_stream)
+                    assert rc_ == 0, (rc_, lib.bbp_last_error(h))
+                    stream.synchronize()
+                    return answer()
+
+                def loop_host():
+                    out, exam, dups = [], [], []
+                    for r in range(R):
+                        hb, ht, st_ = per[r]
+                        assert lib.bbp_verify_round_best_distinct(h, N, ht, len(members[r]), hb, floor, K, tranche, K, k3, p4[0], p4[1], p4[2], p4[3], st_) == 0
+                        out.append([members[r][k3[j]] for j in range(min(n4[0].value, K))])
+                        exam.append(n4[2].value), dups.append(n4[3].value)
+                    return out, exam, dups
+
+                def plain_host():
+                    rc_ = lib.bbp_verify_rounds_best(h, R, c_ns, c_table, B, c_ro, c_rows, None, K, tranche, K, best, nb, nc, ne, ctypes.byref(steps), status)
+                    assert rc_ == 0, (rc_, lib.bbp_last_error(h))
+                    return answer(dups=False)
+
+                def all_host():
+                    assert lib.bbp_verify_rounds_aggregated(h, R, c_ns, c_table, B, c_ro, c_rows, status, 0, ctypes.byref(nfb)) == 0
+                    st_ = np.frombuffer(status, dtype="<i4")
+                    out = []
+                    for r in range(R):
+                        seen, mine = set(), []
+                        for i in sorted(members[r], key=lambda i: (-keys[i], i)):
+                            if st_[i] == 0 and ids[i] not in seen:
+                                seen.add(ids[i]), mine.append(i)
+                        out.append(mine[:K])
+                    return out
+                picked = all_host()
+                verdicts = [int(v) for v in np.frombuffer(status, dtype="<i4")]
+                w_best, _nb, _nc, w_exam, w_dups, w_steps, _st, ran = mdc.model(R, round_of, keys, ids, verdicts, None, K, tranche)
+                want = (w_best, w_exam, w_dups, w_steps)
+                assert new_host() == want and new_dev() == want, (new_host()[1:], want[1:])  # nothing here is tuned: the rules predict it
+                assert loop_host() == want[:3] and picked == w_best
+                p_best, p_exam, _none, p_steps = plain_host()
+                if tname == "no_duplicates":
+                    assert p_exam == w_exam and p_best == w_best and p_steps == w_steps  # exactly the rows the plain call examines
+                copies_in_plain = sum(len({ids[i] for i in b}) < len(b) for b in p_best)
+                arms = {"rounds_best_distinct_host": new_host, "rounds_best_distinct_dev": new_dev, "loop_of_round_best_distinct_host": loop_host,
+                        "rounds_best_host": plain_host, "all_then_pick_host": all_host}
+                rec = {"section": "rounds_distinct", "B": B, "R": R, "N": N, "traffic": tname, "K": K, "tranche": tranche, "rows_examined": sum(w_exam),
+                       "rows_dropped": sum(w_dups), "steps": w_steps, "tranches_of_the_loop": sum(ran), "rows_examined_by_rounds_best": sum(p_exam),
+                       "rounds_where_rounds_best_returns_copies": copies_in_plain, "unit": unit}
+                rec.update(timed(arms, list(arms), args))
+                tab = 32 * (1 + N)
+                rec["bytes_uploaded"] = {"rounds_best_distinct_host": 64 * B + 4 * B + sum(w_exam) * (size + 32 + 4) + w_steps * len(table),
+                                         "loop_of_round_best_distinct_host": 64 * B + sum(w_exam) * (size + 32 + 4) + sum(ran) * tab,
+                                         "rounds_best_host": 32 * B + 4 * B + sum(p_exam) * (size + 32 + 4) + p_steps * len(table),
+                                         "all_then_pick_host": B * (size + 32) + len(table)}
+                a = rec["rounds_best_distinct_host"]
+                for other in ("loop_of_round_best_distinct_host", "rounds_best_host", "all_then_pick_host"):
+                    o = rec[other]
+                    rec["new_over_" + other] = round(a["median"] / o["median"], 4)
+                rec["extra_ms_over_rounds_best_host"] = round(a["median"] - rec["rounds_best_host"]["median"], 3)
+                emit(rec)
+            assert ctx.health() == 0
+        finally:
+            ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds-distinct", default="", metavar="OUT",
+                    help="measure bbp_verify_rounds_best_distinct instead, into OUT (profiles/r23_rounds_best_distinct.jsonl)")
     ap.add_argument("--rounds", default="", metavar="OUT", help="measure bbp_verify_rounds_best instead, into OUT (profiles/r22_rounds_best.jsonl)")
     ap.add_argument("--distinct", default="", metavar="OUT", help="measure bbp_verify_round_best_distinct instead, into OUT")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r19_round_best.jsonl"))
@@ -437,6 +588,8 @@ def main():
     ap.add_argument("--calls", type=int, default=2)
     ap.add_argument("--sections", default="cells,sweep")
     args = ap.parse_args()
+    if args.rounds_distinct:
+        return rounds_distinct_main(args)
     if args.rounds:
         return rounds_main(args)
     if args.distinct:
