@@ -91,6 +91,12 @@ SIGNATURES = {
     "bbp_verify_round_best_distinct": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_round_best_distinct_dev": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_round_best_distinct": (_i32, [_vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_standing_open": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp]),
+    "bbp_standing_offer": (_i32, [_vp, _u32, _u32, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_standing_read": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_standing_close": (_i32, [_vp, _u32]),
+    "bbp_debug_standing_offer": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_standing_trip": (_i32, [_vp, _u32, _u32]),
     "bbp_verify_rounds_best": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_rounds_best_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_rounds_best": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -251,6 +257,12 @@ BEST_TRANCHE_DEFAULT = 16   # BBP_BEST_TRANCHE_DEFAULT
 RoundBest = collections.namedtuple("RoundBest", "best n_best n_candidates n_examined status raw")
 ROW_DUPLICATE = -2          # BBP_ROW_DUPLICATE: the row's identity (z_img) already had a verified row; not verified
 RoundBestDistinct = collections.namedtuple("RoundBestDistinct", "best n_best n_candidates n_examined n_duplicates status raw")
+STANDING_MAX_K = 1024       # BBP_STANDING_MAX_K
+STANDING_MAX_OPEN = 64      # BBP_STANDING_MAX_OPEN
+# an offer to a standing: entered (offer-local indices in rank order, the first min(n_entered, cap)), the counts, the B statuses, raw
+StandingOffer = collections.namedtuple("StandingOffer", "entered n_entered n_candidates n_examined n_duplicates status raw")
+# a standing's entries in rank order (the first min(n_entries, cap)): serials, 32-byte scores, 32-byte z_imgs; the true count; rows offered
+StandingEntries = collections.namedtuple("StandingEntries", "serials scores z_imgs n_entries n_offered")
 BEST_MAX_ROUNDS = 1 << 16   # BBP_BEST_MAX_ROUNDS
 # per round: best (a list of row indices in rank order, at most cap), n_best, n_candidates, n_examined, raw (the round's cap entries as
 # the call left them); n_steps and the B statuses for the call
@@ -652,6 +664,59 @@ class Context:
                                                       ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
         return self._best_distinct_result(B, cap, best, status, counts, dups)
 
+    def standing_open(self, N, table, floor=0, K=1):
+        """bbp_standing_open: a standing of one round (table: 32-byte seed and N 32-byte items, copied), one floor and one K in
+        1..STANDING_MAX_K.  Returns the handle."""
+        if len(table) != 32 * (1 + N):
+            raise ValueError("a round is a 32-byte seed and N 32-byte items")
+        h = _u32(0)
+        self._check(lib.bbp_standing_open(self._h, N, _buf(table), _buf(select_floor(floor)), K, ctypes.byref(h)))
+        return h.value
+
+    def standing_offer(self, standing, N, rows, tranche=0, cap=None, fill=0):
+        """bbp_standing_offer: offers rows (round_row_size(N) bytes each, N the standing's) to the standing.  cap: room in entered
+        (None: one per row).  Returns a StandingOffer."""
+        row = round_row_size(N)
+        if len(rows) % row:
+            raise ValueError("rows are round_row_size(N) bytes each")
+        B = len(rows) // row
+        cap, ent, status, counts = self._best_buffers(B, 0, cap, fill)
+        dups = _u32(0)
+        self._check(lib.bbp_standing_offer(self._h, standing, B, _buf(rows) if B else ent, tranche, cap, ent, ctypes.byref(counts[0]),
+                                           ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
+        return StandingOffer(*self._best_distinct_result(B, cap, ent, status, counts, dups))
+
+    def standing_read(self, standing, cap=STANDING_MAX_K):
+        """bbp_standing_read: the entries in rank order.  Returns a StandingEntries."""
+        serials = (ctypes.c_uint64 * max(1, cap))()
+        scores, z_imgs = ctypes.create_string_buffer(32 * max(1, cap)), ctypes.create_string_buffer(32 * max(1, cap))
+        n, offered = _u32(0), ctypes.c_uint64(0)
+        self._check(lib.bbp_standing_read(self._h, standing, cap, serials, scores, z_imgs, ctypes.byref(n), ctypes.byref(offered)))
+        m = min(n.value, cap)
+        return StandingEntries(list(serials)[:m], [scores.raw[32 * e:32 * e + 32] for e in range(m)], [z_imgs.raw[32 * e:32 * e + 32] for e in range(m)],
+                               n.value, offered.value)
+
+    def standing_close(self, standing):
+        """bbp_standing_close: closes the standing and frees its state."""
+        self._check(lib.bbp_standing_close(self._h, standing))
+
+    def debug_standing_offer(self, standing, keys, ids, verdicts, tranche=0, cap=None, fill=0):
+        """bbp_debug_standing_offer (test hook): an offer of made-up keys and ids (B x 32 bytes each) and verdicts through the shipped
+        kernels against the standing's state; nothing is verified.  Returns a StandingOffer."""
+        B = len(verdicts)
+        if len(keys) != 32 * B or len(ids) != 32 * B:
+            raise ValueError("keys and ids are 32 bytes per verdict")
+        cap, ent, status, counts = self._best_buffers(B, 0, cap, fill)
+        dups = _u32(0)
+        self._check(lib.bbp_debug_standing_offer(self._h, standing, B, _buf(keys) if B else ent, _buf(ids) if B else ent,
+                                                 (ctypes.c_int32 * max(1, B))(*verdicts), tranche, cap, ent, ctypes.byref(counts[0]),
+                                                 ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
+        return StandingOffer(*self._best_distinct_result(B, cap, ent, status, counts, dups))
+
+    def debug_standing_trip(self, standing, after=1):
+        """bbp_debug_standing_trip (test hook): the next offer to the standing fails with ERR_INTERNAL behind its after-th merge."""
+        self._check(lib.bbp_debug_standing_trip(self._h, standing, after))
+
     def verify_rounds_best(self, round_Ns, table, round_of, rows, floors=None, K=1, tranche=0, cap=None, fill=0, B=None):
         """bbp_verify_rounds_best: verify_round_best for every round of a verify_rounds call at once -- step t of every round that still
         runs is verified in one engine call.  round_Ns, table, round_of, rows as verify_rounds; floors: None or one per round.  Returns
@@ -1036,6 +1101,23 @@ class Pool(Context):
         """bbp_verify_rounds_best_distinct on the pool: member 0 keeps the keys, identities and segments, selects, marks and drops; every
         step is verified as verify_rounds_aggregated verifies it (block-split over the members)."""
         return super().verify_rounds_best_distinct(round_Ns, table, round_of, rows, floors, K, tranche, cap, fill, B)
+
+    def standing_open(self, N, table, floor=0, K=1):
+        """bbp_standing_open on the pool: the standing's state lives on member 0."""
+        return super().standing_open(N, table, floor, K)
+
+    def standing_offer(self, standing, N, rows, tranche=0, cap=None, fill=0):
+        """bbp_standing_offer on the pool: member 0 screens, selects, merges and commits; every tranche is verified as
+        verify_rounds_aggregated verifies it (block-split over the members)."""
+        return super().standing_offer(standing, N, rows, tranche, cap, fill)
+
+    def standing_read(self, standing, cap=STANDING_MAX_K):
+        """bbp_standing_read on the pool: from member 0."""
+        return super().standing_read(standing, cap)
+
+    def standing_close(self, standing):
+        """bbp_standing_close on the pool."""
+        super().standing_close(standing)
 
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""

@@ -15,6 +15,7 @@
 #include "round_bids.h"
 #include "round_best.h"
 #include "round_select.h"
+#include "round_standing.h"
 #include "rounds_best.h"
 #include "rounds_best_distinct.h"
 #include "secret_map.h"
@@ -1416,6 +1417,7 @@ struct BestCall {
     hipStream_t s;
     BestLayout L;
     std::optional<BestDistinctLayout> D;  // one per bidder only
+    struct StandCall* stand = nullptr;    // an offer to a standing only (below): B is K + the offer's rows, the working rows
     u8 *d = nullptr, *h = nullptr;
     // host_rows: a host form, which stages bytes of every row -- the 32 key bytes (in L), one per bidder score || z_img (in D)
     BestCall(bbp_ctx* c, u32 B_, u32 K_, hipStream_t s_, bool host_rows, bool distinct, u32 table_log2 = 0)
@@ -1424,13 +1426,28 @@ struct BestCall {
     }
     u32* at(size_t off) const { return (u32*)(d + off); }
     u32 mask() const { return D->slots - 1; }
-    size_t bytes() const { return D ? D->bytes : L.bytes; }
-    size_t h_bytes() const { return D ? D->h_bytes : L.h_bytes; }
+    size_t bytes() const;
+    size_t h_bytes() const;
+    u32 first() const;  // the working rows in front of the call's own: a standing's K entry slots, otherwise none
     size_t staged_row() const { return D ? 64 : 32; }
     size_t staged() const { return D ? D->kid : L.keys; }
     size_t h_staged() const { return D ? D->h_kid : L.h_keys; }
-    std::string family() const { return D ? "best proofs, one per bidder: " : "best valid proofs: "; }
+    std::string family() const { return stand ? "standing of a round: " : D ? "best proofs, one per bidder: " : "best valid proofs: "; }
 };
+// What an offer to a standing adds to a one-per-bidder call (round_standing.h): the standing's own allocation and the host's record of
+// it, the scratch behind the call's, and the launches between the family's.
+struct StandCall {
+    bbp_ctx::Standing* meta;
+    u8* st;        // the standing's allocation
+    u32 K, rows;   // rows: the offer's
+    StandingLayout SL;
+    StandingWork W;
+    u32 merges = 0;
+    StandCall(bbp_ctx::Standing* m, u8* st_, u32 rows_, const BestDistinctLayout& D) : meta(m), st(st_), K(m->K), rows(rows_), SL(m->K), W(D, m->K) {}
+};
+size_t BestCall::bytes() const { return stand ? stand->W.bytes : D ? D->bytes : L.bytes; }
+size_t BestCall::h_bytes() const { return stand ? stand->W.h_bytes : D ? D->h_bytes : L.h_bytes; }
+u32 BestCall::first() const { return stand ? stand->K : 0; }
 static const RsFloor BEST_NO_FLOOR = {};  // k_best_keys has applied the floor: a record is a member by its status alone
 // where a call's results go (n_duplicates: the one-per-bidder calls, otherwise null)
 struct BestOut {
@@ -1456,15 +1473,17 @@ static int32_t best_open(BestCall& c) {
 // keys at base + i stride + off (device memory) [ids 32 bytes behind them: score || z_img are adjacent in a row], status: B x int32
 // (device memory)
 static int32_t best_keys_enqueue(const BestCall& c, const u8* base, size_t stride, size_t off, const uint8_t* floor32, int32_t* status) {
-    const dim3 grid((c.B + BEST_T - 1) / BEST_T), block(BEST_T);
+    const u32 f = c.first(), n = c.B - f;  // (an offer to a standing: base is the offer's row 0, which is working row f)
+    const dim3 grid((n + BEST_T - 1) / BEST_T), block(BEST_T);
     {
         ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
-        hipLaunchKernelGGL(k_best_keys, grid, block, 0, c.s, c.B, base, stride, off, rs_floor_load(floor32), c.at(c.L.recs), c.at(c.L.win), status);
+        hipLaunchKernelGGL(k_best_keys, grid, block, 0, c.s, n, base, stride, off, rs_floor_load(floor32), c.at(c.L.recs) + (size_t)RS_WORDS * f,
+                           c.at(c.L.win) + (size_t)RS_WORDS * f, status + f);
         BBP_HIP_TRY(c.ctx, hipGetLastError());
     }
     if (!c.D) return BBP_OK;
     ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
-    hipLaunchKernelGGL(k_best_ids, grid, block, 0, c.s, c.B, base, stride, off + 32, c.at(c.D->ids));
+    hipLaunchKernelGGL(k_best_ids, grid, block, 0, c.s, n, base, stride, off + 32, c.at(c.D->ids) + 8 * (size_t)f);
     BBP_HIP_TRY(c.ctx, hipGetLastError());
     return BBP_OK;
 }
@@ -1483,6 +1502,65 @@ static int32_t best_mark_enqueue(const BestCall& c, u32 n, const int32_t* tstat,
     return BBP_OK;
 }
 
+// An offer to a standing, on c.s.  Seed: behind best_open, before the keys.  Leave: the leave pass.  Merge: behind a tranche's holders --
+// displaced entries closed, the selection over the winner records with the call's K, the merge, then the leave pass unless no live
+// candidate is left.  Finish: everything the host reads into the mirror.  Commit: a submission of its own, after the host's checks.
+static int32_t stand_seed_enqueue(const BestCall& c, int32_t* status) {
+    const StandCall& S = *c.stand;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stand_seed, dim3((S.K + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.K, (const u32*)(S.st + S.SL.hdr), (const u32*)(S.st + S.SL.keys),
+                       (const u32*)(S.st + S.SL.ids), (const u32*)(S.st + S.SL.serials), c.at(c.L.recs), c.at(c.L.win), c.at(c.D->ids), status,
+                       c.at(c.D->table), c.mask(), c.at(S.W.whdr), c.at(S.W.wserial), c.at(S.W.order), c.at(c.D->dctr));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+static int32_t stand_leave_enqueue(const BestCall& c, int32_t* status) {
+    const StandCall& S = *c.stand;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stand_leave, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, S.K, c.at(c.L.recs), (const u32*)c.at(c.D->ids),
+                       (const u32*)c.at(c.D->table), c.mask(), (const u32*)c.at(S.W.whdr), status, c.at(c.D->dctr));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+static int32_t stand_merge_enqueue(const BestCall& c, int32_t* status, bool leave) {
+    StandCall& S = *c.stand;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_stand_displace, dim3((S.K + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.K, (const u32*)c.at(c.D->ids),
+                           (const u32*)c.at(c.D->table), c.mask(), c.at(c.L.win), c.at(c.D->dctr));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    if (int32_t rc = select_kernels_enqueue(c.ctx, c.B, c.at(c.L.win), BEST_NO_FLOOR, S.K, S.K, c.at(c.L.sel), c.at(c.L.counts), c.d + c.L.state, c.s)) return rc;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        const u32 trip = S.meta->trip && S.meta->trip == ++S.merges;  // (bbp_debug_standing_trip: once)
+        if (trip) S.meta->trip = 0;
+        hipLaunchKernelGGL(k_stand_merge, dim3(1), dim3(STAND_MERGE_T), 0, c.s, S.K, (const u32*)c.at(c.L.sel), (const u32*)c.at(c.L.counts),
+                           (const u32*)c.at(c.L.win), c.at(S.W.whdr), c.at(S.W.order), trip, c.at(c.D->dctr));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    return leave ? stand_leave_enqueue(c, status) : (int32_t)BBP_OK;
+}
+static int32_t stand_finish_enqueue(const BestCall& c, const int32_t* status) {
+    bbp_ctx* ctx = c.ctx;
+    const StandCall& S = *c.stand;
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 8, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.D->h_dctr, c.d + c.D->dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + S.W.h_whdr, c.d + S.W.whdr, 4 * STAND_H_WORDS, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + S.W.h_order, c.d + S.W.order, 4 * (size_t)S.K, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_status, status + S.K, 4 * (size_t)S.rows, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+static int32_t stand_commit_enqueue(const BestCall& c) {
+    const StandCall& S = *c.stand;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stand_commit, dim3((S.K + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.K, S.rows, (const u32*)c.at(S.W.whdr),
+                       (const u32*)c.at(S.W.order), (const u32*)c.at(c.L.win), (const u32*)c.at(c.D->ids), (const u32*)c.at(S.W.wserial),
+                       (u32*)(S.st + S.SL.hdr), (u32*)(S.st + S.SL.keys), (u32*)(S.st + S.SL.ids), (u32*)(S.st + S.SL.serials));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
 // Behind the mark of a tranche of n rows, for a caller that decides from the device's counters whether another tranche runs: ctr into
 // the mirror.  [Before that: identities settled, holders' winner records opened, duplicates dropped unless the call stops here (`drop`:
 // false when the host knows that no live candidate is left); dctr into the mirror as well.]
@@ -1497,7 +1575,9 @@ static int32_t best_counters_enqueue(const BestCall& c, u32 n, const int32_t* ts
         BBP_HIP_TRY(ctx, hipGetLastError());
         hipLaunchKernelGGL(k_best_holders, grid, block, 0, c.s, n, sel, counts, tstat, ids, (const u32*)table, c.mask(), c.at(c.L.win), dctr);
         BBP_HIP_TRY(ctx, hipGetLastError());
-        if (drop) {
+        if (c.stand) {  // (an offer to a standing: the merge, and the leave pass in the drop pass's place)
+            if (int32_t rc = stand_merge_enqueue(c, status, drop)) return rc;
+        } else if (drop) {
             hipLaunchKernelGGL(k_best_drop, dim3((c.B + BEST_T - 1) / BEST_T), block, 0, c.s, c.B, c.K, c.at(c.L.recs), ids, (const u32*)table, c.mask(), status,
                                dctr);
             BBP_HIP_TRY(ctx, hipGetLastError());
@@ -1511,8 +1591,16 @@ static int32_t best_counters_enqueue(const BestCall& c, u32 n, const int32_t* ts
 // What a call knows between tranches, and the checks that hold it to the device's counters.  reached: the rows found valid [the
 // identities settled]; dups: [the rows dropped as duplicates] 0.
 struct BestTally {
-    u32 T0 = 0, nc = 0, examined = 0, reached = 0, dups = 0;
-    u32 live() const { return nc - examined - dups; }
+    u32 T0 = 0, nc = 0, examined = 0, reached = 0, dups = 0, left = 0;  // left: an offer to a standing -- candidates that left by the bar
+    u32 live() const { return nc - examined - dups - left; }
+    // an offer to a standing, before tranche 0: the leave pass that ran in front of the first selection (the candidate count follows)
+    bool pre(const BestCall& c, std::string* why) {
+        u32 d[BEST_D_WORDS];
+        memcpy(d, c.h + c.D->h_dctr, sizeof d);
+        if (d[BEST_D_FLAG]) return *why = c.family() + "a bounded loop of the identity table ran out (flag " + std::to_string(d[BEST_D_FLAG]) + ")", false;
+        dups = d[BEST_D_DUPLICATES], left = d[STAND_D_LEFT];
+        return true;
+    }
     bool stop(u32 K) const { return live() == 0 || (K && reached >= K); }
     // the counters that arrived behind a tranche's mark, or with the finish: false (with *why) when they are not what the call counted
     bool take(const BestCall& c, std::string* why) {
@@ -1523,13 +1611,13 @@ struct BestTally {
         else
             d[BEST_D_SETTLED] = ctr[1];  // every valid row counts
         if (d[BEST_D_FLAG]) return *why = c.family() + "a bounded loop of the identity table ran out (flag " + std::to_string(d[BEST_D_FLAG]) + ")", false;
-        if (ctr[0] != examined || d[BEST_D_SETTLED] < reached || d[BEST_D_SETTLED] > ctr[1] || d[BEST_D_DUPLICATES] < dups ||
-            (unsigned long long)examined + d[BEST_D_DUPLICATES] > nc)
+        if (ctr[0] != examined || d[BEST_D_SETTLED] < reached || d[BEST_D_SETTLED] > ctr[1] || d[BEST_D_DUPLICATES] < dups || d[STAND_D_LEFT] < left ||
+            (unsigned long long)examined + d[BEST_D_DUPLICATES] + d[STAND_D_LEFT] > nc)
             return *why = c.family() + "the device counted " + std::to_string(ctr[0]) + " rows examined, " + std::to_string(ctr[1]) + " valid, " +
                           std::to_string(d[BEST_D_SETTLED]) + " reached and " + std::to_string(d[BEST_D_DUPLICATES]) + " rows dropped; the call examined " +
                           std::to_string(examined) + " of " + std::to_string(nc) + " candidates and had reached " + std::to_string(reached),
                    false;
-        reached = d[BEST_D_SETTLED], dups = d[BEST_D_DUPLICATES];
+        reached = d[BEST_D_SETTLED], dups = d[BEST_D_DUPLICATES], left = d[STAND_D_LEFT];
         return true;
     }
 };
@@ -1540,7 +1628,7 @@ static u32 best_tranche_ask(u32 K, u32 tranche, u32 B, const BestTally& ty, u32 
 }
 // counts = {n, live} of the selection of tranche t against the call's tally
 static bool best_tranche_ok(const u32* counts, u32 t, u32 K, u32 tranche, BestTally& ty) {
-    if (t == 0) ty.nc = counts[1], ty.T0 = best_tranche0(K, tranche, ty.nc);
+    if (t == 0) ty.nc = counts[1] + ty.dups + ty.left, ty.T0 = best_tranche0(K, tranche, ty.nc);
     return counts[1] == ty.live() && counts[0] == best_tranche_rows(ty.T0, t, counts[1]);
 }
 
@@ -1585,6 +1673,41 @@ static int32_t best_deliver(const BestCall& c, u32 room, BestTally& t, const Bes
     return BBP_OK;
 }
 
+// An offer to a standing, after its finish has arrived: the tally against the device's counters, the working standing against the call
+// (no live candidate left, at most K entries, every one a working row), then the outputs: the offer's rows among the entries, in rank order.
+static int32_t stand_deliver(const BestCall& c, BestTally& t, const BestOut& o, std::string* why) {
+    const StandCall& S = *c.stand;
+    const u32 dups = t.dups, left = t.left;
+    if (!t.take(c, why)) return BBP_ERR_INTERNAL;
+    const u32 *whdr = (const u32*)(c.h + S.W.h_whdr), *order = (const u32*)(c.h + S.W.h_order), count = whdr[STAND_H_COUNT];
+    bool ok = t.dups == dups && t.left == left && t.live() == 0 && count <= S.K;
+    for (u32 e = 0; ok && e < count; e++) ok = order[e] < c.B;
+    if (!ok) {
+        *why = c.family() + "the working standing holds " + std::to_string(count) + " entries; the device counted " + std::to_string(t.dups) +
+               " duplicates and " + std::to_string(t.left) + " rows below the bar, the call " + std::to_string(dups) + " and " + std::to_string(left) + "; " +
+               std::to_string(t.live()) + " candidates are live";
+        return BBP_ERR_INTERNAL;
+    }
+    u32 ne = 0;
+    for (u32 e = 0; e < count; e++)
+        if (order[e] >= S.K) {
+            if (ne < o.cap) o.best[ne] = order[e] - S.K;
+            ne++;
+        }
+    *o.n_best = ne, *o.n_candidates = t.nc, *o.n_examined = t.examined, *o.n_duplicates = t.dups;
+    return BBP_OK;
+}
+// ... and after its commit has run: what the host keeps of the header
+static void stand_committed(const BestCall& c) {
+    const StandCall& S = *c.stand;
+    const u32* whdr = (const u32*)(c.h + S.W.h_whdr);
+    bbp_ctx::Standing& m = *S.meta;
+    m.count = whdr[STAND_H_COUNT];
+    memcpy(m.bar, whdr + STAND_H_BAR, 32);
+    m.offered += S.rows;
+    m.trip = 0;
+}
+
 // The host forms on ONE device's context (c.ctx).  fill(dst): the B x c.staged_row() bytes into the pinned staging area; verdicts(n, sel,
 // st): the statuses of the tranche's rows sel[0..n) -- called with no lock of the device held (the host form verifies through the
 // caller's handle).  Every submission is enqueued under the context lock and waited for with the lock released: one per tranche and one
@@ -1593,10 +1716,18 @@ template <class Fill, class Verdicts>
 static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, const uint8_t* floor32, u32 tranche, const BestOut& out, int32_t* status) {
     bbp_ctx* const dev = c.ctx;
     std::lock_guard<std::mutex> call(dev->best_mu);
-    const u32 B = c.B, K = c.K;
+    const u32 B = c.B, K = c.K, first = c.first(), stop_K = c.stand ? 0 : K;  // (an offer to a standing stops when nothing is live)
     BestTally ty;
     std::vector<int32_t> st;
     u32 pending = 0, room = 0, tranches = 0;
+    uint8_t stand_floor[32];
+    if (c.stand) {  // the floor an offer screens by, from the standing as the last commit left it
+        const bbp_ctx::Standing& m = *c.stand->meta;
+        u32 f[8];
+        stand_screen_floor(m.floor, m.count == m.K, m.bar, f);
+        for (int b = 0; b < 32; b++) stand_floor[b] = (uint8_t)(f[b >> 2] >> (8 * (b & 3)));
+        floor32 = stand_floor;
+    }
     auto fail = [&](const std::string& why, int32_t rc) {
         api_guard(dev, [&]() -> int32_t { return dev->err = why, rc; });
         return rc;
@@ -1626,12 +1757,18 @@ static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, cons
             int32_t r;
             if (t == 0) {
                 if ((r = best_open(c))) return r;
-                fill(c.h + c.h_staged());
-                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.staged(), c.h + c.h_staged(), c.staged_row() * B, hipMemcpyHostToDevice, c.s));
-                if ((r = best_keys_enqueue(c, c.d + c.staged(), c.staged_row(), 0, floor32, dstatus()))) return r;
+                if (c.stand && (r = stand_seed_enqueue(c, dstatus()))) return r;
+                const size_t skip = c.staged_row() * first;  // (the entry slots of a standing are not staged: the seed wrote them)
+                fill(c.h + c.h_staged() + skip);
+                BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.staged() + skip, c.h + c.h_staged() + skip, c.staged_row() * (B - first), hipMemcpyHostToDevice, c.s));
+                if ((r = best_keys_enqueue(c, c.d + c.staged() + skip, c.staged_row(), 0, floor32, dstatus()))) return r;
+                if (c.stand) {  // the leave pass in front of tranche 0; its counts come down with the selection's
+                    if ((r = stand_leave_enqueue(c, dstatus()))) return r;
+                    BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.D->h_dctr, c.d + c.D->dctr, 4 * BEST_D_WORDS, hipMemcpyDeviceToHost, c.s));
+                }
             }
             if (pending && (r = mark(pending))) return r;
-            if (finish) return best_finish_enqueue(c, dstatus(), &room);
+            if (finish) return c.stand ? stand_finish_enqueue(c, dstatus()) : best_finish_enqueue(c, dstatus(), &room);
             if ((r = best_select_enqueue(c, rows))) return r;
             BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + c.L.h_counts, c.d + c.L.counts, 256 + 4 * (size_t)room_sel, hipMemcpyDeviceToHost, c.s));
             return BBP_OK;
@@ -1640,6 +1777,10 @@ static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, cons
         if (finish) break;
         u32 counts[2];
         memcpy(counts, c.h + c.L.h_counts, 8);
+        if (c.stand && t == 0) {
+            std::string why;
+            if (!ty.pre(c, &why)) return fail(why, BBP_ERR_INTERNAL);
+        }
         if (!best_tranche_ok(counts, t, K, tranche, ty)) return fail(c.family() + "a tranche of unexpected size", BBP_ERR_INTERNAL);
         const u32 n = counts[0];
         pending = 0;
@@ -1662,11 +1803,16 @@ static int32_t best_run_host(BestCall& c, Fill&& fill, Verdicts&& verdicts, cons
                 for (u32 j = 0; j < n; j++) ty.reached += st[j] == BBP_OK;
             }
         }
-        finish = n == 0 || ty.stop(K);
+        finish = n == 0 || ty.stop(stop_K);
     }
     std::string why;
-    if (int32_t rc = best_deliver(c, room, ty, out, &why)) return fail(why, rc);
-    memcpy(status, c.h + c.L.h_status, 4 * (size_t)B);
+    if (c.stand) {  // the host's checks first, then the one commit, then the host's record of what was committed
+        if (int32_t rc = stand_deliver(c, ty, out, &why)) return fail(why, rc);
+        if (int32_t rc = submit([&]() -> int32_t { return stand_commit_enqueue(c); })) return rc;
+        stand_committed(c);
+    } else if (int32_t rc = best_deliver(c, room, ty, out, &why))
+        return fail(why, rc);
+    memcpy(status, c.h + c.L.h_status, 4 * (size_t)(B - first));
     if (out.n_tranches) *out.n_tranches = tranches;
     return BBP_OK;
 }
@@ -1885,6 +2031,210 @@ extern "C" int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, 
         BestCall c(ctx, B, K, pick_stream(ctx, stream), false, true);
         return best_run_dev(c, N, (const u8*)round_dev, (const u8*)rows_dev, (const u8*)entropy_dev, floor32, tranche,
                             BestOut{cap, best_out, n_best, n_candidates, n_examined, n_duplicates}, (int32_t*)status_dev);
+    });
+}
+
+// ---- standing of a round (include/bbp.h; rules and kernels: round_standing.h) ---------------------------------------------------------
+// An offer is a one-per-bidder host call over K + B working rows with a StandCall: the same driver.  The standings of a handle live on
+// ONE device's context (a pool: member 0), found and changed under its best_mu.
+static bbp_ctx* stand_dev(bbp_ctx* ctx) { return is_pool(ctx) ? ctx->members[0] : ctx; }
+static int32_t stand_refuse(bbp_ctx* ctx, const std::string& why) {
+    return api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
+}
+// the open standing behind a handle, or null (caller holds dev->best_mu)
+static bbp_ctx::Standing* stand_find(bbp_ctx* dev, u32 handle) {
+    return dev->stand_handles.is_open(handle) ? &dev->stand_meta[handle] : nullptr;
+}
+
+extern "C" int32_t bbp_standing_open(bbp_ctx* ctx, uint32_t N, const uint8_t* round, const uint8_t floor32[32], uint32_t K, uint32_t* standing) {
+    if (!ctx || !round || !floor32 || !standing) return BBP_ERR_BAD_ARG;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        if (N == 0 || N > BBP_MAX_ITEMS) return api_guard(ctx, [&]() -> int32_t { return check_n(ctx, N); });
+        if (K == 0 || K > BBP_STANDING_MAX_K) return stand_refuse(ctx, "bbp_standing_open: K is 0 or above BBP_STANDING_MAX_K");
+        bbp_ctx* const dev = stand_dev(ctx);
+        std::lock_guard<std::mutex> call(dev->best_mu);
+        const u32 h = dev->stand_handles.take();
+        if (h == BBP_STANDING_MAX_OPEN) return stand_refuse(ctx, "bbp_standing_open: BBP_STANDING_MAX_OPEN standings are open on this handle");
+        bbp_ctx::Standing m;
+        m.N = N, m.K = K;
+        const RsFloor f = rs_floor_load(floor32);
+        memcpy(m.floor, f.w, 32);
+        m.round.assign(round, round + round_table_bytes(N));
+        const int32_t rc = api_guard(dev, [&]() -> int32_t {
+            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
+            const StandingLayout SL(K);
+            if (int32_t r = dev_reserve(dev, dev->stand[h], SL.bytes)) return r;
+            BBP_HIP_TRY(dev, hipMemsetAsync(dev->stand[h].p, 0, SL.bytes, dev->stream));  // count 0, offered 0
+            BBP_HIP_TRY(dev, hipStreamSynchronize(dev->stream));
+            return BBP_OK;
+        });
+        if (rc) {
+            dev->stand_handles.release(h);
+            if (dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+            return rc;
+        }
+        dev->stand_meta[h] = std::move(m);
+        *standing = h;
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_standing_close(bbp_ctx* ctx, uint32_t standing) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = stand_dev(ctx);
+        std::lock_guard<std::mutex> call(dev->best_mu);
+        if (!dev->stand_handles.release(standing)) return stand_refuse(ctx, "bbp_standing_close: no open standing has this handle");
+        dev->stand_meta[standing] = bbp_ctx::Standing{};
+        return api_guard(dev, [&]() -> int32_t {
+            DevBuf& b = dev->stand[standing];
+            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
+            if (b.p) {
+                BBP_HIP_TRY(dev, hipFree(b.p));  // (waits for the device: no offer is in flight, best_mu is held)
+                dev->scratch_bytes -= b.cap;
+            }
+            b = DevBuf{};
+            return BBP_OK;
+        });
+    });
+}
+
+extern "C" int32_t bbp_standing_read(bbp_ctx* ctx, uint32_t standing, uint32_t cap, uint64_t* serials_out, uint8_t* scores_out, uint8_t* z_imgs_out,
+                                     uint32_t* n_entries, uint64_t* n_offered) {
+    if (!ctx || !n_entries) return BBP_ERR_BAD_ARG;
+    *n_entries = 0;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        bbp_ctx* const dev = stand_dev(ctx);
+        std::lock_guard<std::mutex> call(dev->best_mu);
+        const bbp_ctx::Standing* m = stand_find(dev, standing);
+        if (!m) return stand_refuse(ctx, "bbp_standing_read: no open standing has this handle");
+        const int32_t rc = api_guard(dev, [&]() -> int32_t {
+            BBP_HIP_TRY(dev, hipSetDevice(dev->device));
+            const StandingLayout SL(m->K);
+            const u8* st = (const u8*)dev->stand[standing].p;
+            u32 hdr[STAND_H_WORDS];
+            BBP_HIP_TRY(dev, hipMemcpy(hdr, st + SL.hdr, sizeof hdr, hipMemcpyDeviceToHost));  // (the device's own record, not the host's shadow)
+            const u32 count = hdr[STAND_H_COUNT];
+            if (count > m->K) return dev->err = "standing of a round: the state holds more than K entries", BBP_ERR_INTERNAL;
+            const u32 n = count < cap ? count : cap;
+            std::vector<u32> w(8 * (size_t)n);
+            auto words_out = [&](size_t off, uint8_t* out) -> int32_t {  // n x 8 words -> n x 32 little-endian bytes
+                if (!out || !n) return BBP_OK;
+                BBP_HIP_TRY(dev, hipMemcpy(w.data(), st + off, 32 * (size_t)n, hipMemcpyDeviceToHost));
+                for (size_t b = 0; b < 32 * (size_t)n; b++) out[b] = (uint8_t)(w[b >> 2] >> (8 * (b & 3)));
+                return BBP_OK;
+            };
+            if (int32_t r = words_out(SL.keys, scores_out)) return r;
+            if (int32_t r = words_out(SL.ids, z_imgs_out)) return r;
+            if (serials_out && n) {
+                BBP_HIP_TRY(dev, hipMemcpy(w.data(), st + SL.serials, 8 * (size_t)n, hipMemcpyDeviceToHost));
+                for (u32 e = 0; e < n; e++) serials_out[e] = ((uint64_t)w[2 * (size_t)e + 1] << 32) | w[2 * (size_t)e];
+            }
+            *n_entries = count;
+            if (n_offered) *n_offered = ((uint64_t)hdr[STAND_H_OFFERED + 1] << 32) | hdr[STAND_H_OFFERED];
+            return BBP_OK;
+        });
+        if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+        return rc;
+    });
+}
+
+// Both forms of an offer behind their screening: the standing looked up, the one-per-bidder call over K + B working rows built, run by
+// the host driver.  run(c, m): the form's fill and verdicts for the standing m, handed to best_run_host with the call c.
+template <class Run>
+static int32_t stand_offer(bbp_ctx* ctx, const char* what, u32 standing, u32 B, Run&& run) {
+    bbp_ctx* const dev = stand_dev(ctx);
+    bbp_ctx::Standing* m;
+    {
+        std::lock_guard<std::mutex> call(dev->best_mu);
+        m = stand_find(dev, standing);
+    }
+    if (!m) return stand_refuse(ctx, std::string(what) + ": no open standing has this handle");
+    BestCall c(dev, m->K + B, m->K, dev->stream, true, true);
+    StandCall S(m, (u8*)dev->stand[standing].p, B, *c.D);
+    c.stand = &S;
+    const int32_t rc = run(c, *m);
+    if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+    return rc;
+}
+
+extern "C" int32_t bbp_standing_offer(bbp_ctx* ctx, uint32_t standing, uint32_t B, const uint8_t* rows, uint32_t tranche, uint32_t cap, uint32_t* entered_out,
+                                      uint32_t* n_entered, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        {
+            bbp_ctx* const dev = stand_dev(ctx);
+            std::lock_guard<std::mutex> call(dev->best_mu);
+            if (!stand_find(dev, standing)) return stand_refuse(ctx, "bbp_standing_offer: no open standing has this handle");
+        }
+        if (!rows || !n_entered || !n_candidates || !n_examined || !n_duplicates || !status || (cap && !entered_out))
+            return stand_refuse(ctx, "bbp_standing_offer: a NULL pointer");
+        *n_entered = *n_candidates = *n_examined = *n_duplicates = 0;
+        if (B > BBP_SELECT_MAX_BIDS) return stand_refuse(ctx, "bbp_standing_offer: more than BBP_SELECT_MAX_BIDS rows");
+        if (B == 0) return BBP_OK;
+        return stand_offer(ctx, "bbp_standing_offer", standing, B,
+                           [&](BestCall& c, const bbp_ctx::Standing& m) -> int32_t {
+                               const u32 N = m.N, K = m.K;
+                               const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
+                               std::vector<uint8_t> picked;
+                               auto fill = [&](u8* dst) {
+                                   for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, rows + rb * i + key_off, 64);
+                               };
+                               auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // (sel: working rows; row sel[j] - K of the offer)
+                                   picked.resize(rb * n);
+                                   for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * (sel[j] - K), rb);
+                                   return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, m.round.data(), nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT,
+                                                      nullptr);
+                               };
+                               return best_run_host(c, fill, verdicts, nullptr, tranche,
+                                                    BestOut{cap, entered_out, n_entered, n_candidates, n_examined, n_duplicates}, status);
+                           });
+    });
+}
+
+// Test hook: an offer of caller-made keys, ids and verdicts through the shipped kernels against the standing's state.
+extern "C" int32_t bbp_debug_standing_offer(bbp_ctx* ctx, uint32_t standing, uint32_t B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts,
+                                            uint32_t tranche, uint32_t cap, uint32_t* entered_out, uint32_t* n_entered, uint32_t* n_candidates,
+                                            uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_standing_offer");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        {
+            std::lock_guard<std::mutex> call(ctx->best_mu);
+            if (!stand_find(ctx, standing)) return stand_refuse(ctx, "bbp_debug_standing_offer: no open standing has this handle");
+        }
+        if (!keys || !ids || !verdicts || !n_entered || !n_candidates || !n_examined || !n_duplicates || !status || (cap && !entered_out))
+            return stand_refuse(ctx, "bbp_debug_standing_offer: a NULL pointer");
+        *n_entered = *n_candidates = *n_examined = *n_duplicates = 0;
+        if (B == 0) return BBP_OK;  // (as the offer itself: zero counts, the standing unchanged)
+        u32 n_ok;
+        if (int32_t rc = best_hook_screen(ctx, "bbp_debug_standing_offer", B, verdicts, &n_ok)) return rc;
+        return stand_offer(ctx, "bbp_debug_standing_offer", standing, B,
+                           [&](BestCall& c, const bbp_ctx::Standing& m) -> int32_t {
+                               const u32 K = m.K;
+                               auto fill = [&](u8* dst) {
+                                   for (u32 i = 0; i < B; i++)
+                                       memcpy(dst + 64 * (size_t)i, keys + 32 * (size_t)i, 32), memcpy(dst + 64 * (size_t)i + 32, ids + 32 * (size_t)i, 32);
+                               };
+                               auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
+                                   for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j] - K];
+                                   return BBP_OK;
+                               };
+                               return best_run_host(c, fill, read, nullptr, tranche, BestOut{cap, entered_out, n_entered, n_candidates, n_examined, n_duplicates},
+                                                    status);
+                           });
+    });
+}
+
+extern "C" int32_t bbp_debug_standing_trip(bbp_ctx* ctx, uint32_t standing, uint32_t after) {
+    if (!ctx) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_standing_trip");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        std::lock_guard<std::mutex> call(ctx->best_mu);
+        bbp_ctx::Standing* m = stand_find(ctx, standing);
+        if (!m || after == 0) return stand_refuse(ctx, "bbp_debug_standing_trip: no open standing has this handle, or after is 0");
+        m->trip = after;
+        return BBP_OK;
     });
 }
 

@@ -22,6 +22,7 @@
 #include "prove_io.h"
 #include "prove_plan.h"
 #include "scalar.h"
+#include "standing_handles.h"
 #include "verify_plan.h"
 #include "verify_rows.h"
 
@@ -220,6 +221,20 @@ struct bbp_ctx {
     void* best_h = nullptr;
     size_t best_h_cap = 0;
     hipEvent_t ev_best = nullptr;
+    // Standings (bbp_standing_open, ...; capi_prove.hip; round_standing.h's StandingLayout): per open standing a device allocation of
+    // its OWN -- header, K keys, ids and serials -- that lives from open to close, PUBLIC like the state above, and what the host knows
+    // of it: the round, the floor, and a shadow of the header as of the last commit.  An offer works in best_dev and commits at its end.
+    // Guarded by best_mu; a pool keeps its standings on member 0.
+    struct Standing {
+        uint32_t N = 0, K = 0, count = 0, trip = 0;  // trip: bbp_debug_standing_trip (0: none)
+        uint32_t floor[8] = {}, bar[8] = {};
+        uint64_t offered = 0;
+        std::vector<uint8_t> round;
+    };
+    static constexpr int STANDINGS = BBP_STANDING_MAX_OPEN;
+    bbp::StandingHandles stand_handles;  // which are open (standing_handles.h)
+    Standing stand_meta[STANDINGS];
+    bbp::DevBuf stand[STANDINGS];
     // resident tables
     bbp::ge* gens = nullptr;           // [TAB_BASES] extended points: B_blinding, G[2048], H[2048], B, then the PAD_BASES range sums and the MRG_BASES merged bases
     bbp::niels_row* ptable = nullptr;      // [TAB_BASES * MSM_POS] affine cached 2^b * P_i, 128-byte limb rows (275 MB)

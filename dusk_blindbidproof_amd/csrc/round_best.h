@@ -155,8 +155,8 @@ struct BestRows {
 constexpr u32 BEST_EMPTY = 0xffffffffu;
 constexpr u32 BEST_TABLE_LOG2_MAX = 21;  // 2^21 slots >= 2 BBP_SELECT_MAX_BIDS: 8 MB
 enum : u32 { BEST_FLAG_PROBE = 1, BEST_FLAG_REPLACE = 2 };
-// the extra counters of a call, one word each
-enum : u32 { BEST_D_SETTLED = 0, BEST_D_DUPLICATES = 1, BEST_D_FLAG = 2, BEST_D_WORDS = 3 };
+// the extra counters of a call, one word each (word 3 is round_standing.h's: zero in every other call)
+enum : u32 { BEST_D_SETTLED = 0, BEST_D_DUPLICATES = 1, BEST_D_FLAG = 2, BEST_D_WORDS = 4 };
 
 // the least s with 2^s >= 2 B: sized from B alone
 BBP_HD u32 best_table_log2(u32 B) {

@@ -384,6 +384,8 @@ extern "C" void bbp_free(bbp_ctx* ctx) {
     if (ctx->sel_h) (void)hipHostFree(ctx->sel_h);
     for (bbp::DevBuf* b : {&ctx->best_dev, &ctx->best_rows})
         if (b->p) (void)hipFree(b->p);
+    for (bbp::DevBuf& b : ctx->stand)  // standings still open
+        if (b.p) (void)hipFree(b.p);
     if (ctx->best_h) (void)hipHostFree(ctx->best_h);
     for (hipEvent_t e : {ctx->ev_chk_fork, ctx->ev_chk_join, ctx->ev_round, ctx->ev_sel, ctx->ev_best})
         if (e) (void)hipEventDestroy(e);

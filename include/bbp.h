@@ -84,11 +84,12 @@ int32_t bbp_init(int32_t device, bbp_ctx** out);
  *   bbp_verify_round_best_distinct   the same: keys, identities, selection and marks on member 0, tranches verified on the pool
  *   bbp_verify_rounds_best  the same over many rounds: keys, segments, selection and marks on member 0, every step verified on the pool
  *   bbp_verify_rounds_best_distinct   the same, one per bidder: identities and drops on member 0 as well, every step verified on the pool
+ *   bbp_standing_open / _offer / _read / _close   a standing's state lives on member 0, an offer's tranches are verified on the pool
  *   bbp_check_health        the members' flags OR-ed;  bbp_set_batching / bbp_batching_stats: the pool's combiner
  *   bbp_free                frees the members too
  * What it refuses (BBP_ERR_BAD_ARG; device pointers and streams belong to one device -- take a member with bbp_pool_member and
  * call it directly): every *_dev entry point, bbp_debug_challenges, bbp_debug_table, bbp_debug_varbase, bbp_debug_round_select, bbp_debug_round_best,
- * bbp_debug_round_best_distinct, bbp_debug_rounds_best, bbp_debug_rounds_best_distinct, bbp_set_profiling /
+ * bbp_debug_round_best_distinct, bbp_debug_standing_offer, bbp_debug_standing_trip, bbp_debug_rounds_best, bbp_debug_rounds_best_distinct, bbp_set_profiling /
  * bbp_last_timings; the stream getters return NULL. */
 int32_t bbp_init_all(bbp_ctx** out);
 int32_t bbp_pool_init(const int32_t* devices, uint32_t n_devices, bbp_ctx** out);
@@ -572,6 +573,75 @@ int32_t bbp_debug_rounds_best_distinct(bbp_ctx* ctx, uint32_t R, uint32_t B, con
                                        const int32_t* verdicts, const uint8_t* floors, uint32_t K, uint32_t tranche, uint32_t cap, uint32_t table_log2,
                                        uint32_t* best_out, uint32_t* n_best, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates,
                                        uint32_t* n_steps, int32_t* status);
+
+/* Standing of a round: the K best valid rows of a round SO FAR, one per z_img, kept on the device while candidates arrive.  The calls
+ * above are one-shot: the caller holds all B rows of a round and hands them over together.  A node receives a round by gossip, in
+ * bursts, from several peers, with resends; re-running bbp_verify_round_best_distinct over everything received verifies examined rows
+ * again, and calling it on a burst alone loses the identity table between calls.  A standing is the state that outlives a call.
+ * It belongs to one round (seed || pub_list, N items; copied by bbp_standing_open, the caller's buffer is free on return), one floor32
+ * and one K in 1..BBP_STANDING_MAX_K (K == 0, "every valid row", is refused: nothing would ever leave).
+ *   entries       at most K of (key, z_img, serial); key as bbp_verify_round_best's; serial (u64) is the number of rows offered to this
+ *                 standing before that row: row j of an offer has serial offered + j.  Kept in RANK ORDER: key descending, then serial
+ *                 ascending.  bar is the key of entry K-1 once the standing is full; it never falls
+ * An offer of B rows (bbp_verify_round_best's row layout: record || score || z_img, bbp_round_row_size(N) bytes each):
+ *   screening     in this order: key >= l BBP_ERR_FORMAT, never verified; key < floor BBP_ROW_SKIPPED; the standing is full and (key,
+ *                 serial) does not come before entry K-1 in rank order BBP_ROW_SKIPPED (at the start of an offer: key <= bar); every
+ *                 other row is a candidate, n_candidates counts them
+ *   leave pass    before tranche 0 and after every tranche, over the live candidates: a row that no longer passes the third screening
+ *                 test leaves, its status stays BBP_ROW_SKIPPED; otherwise a row whose z_img is held by an entry that comes BEFORE it in
+ *                 rank order leaves with BBP_ROW_DUPLICATE, n_duplicates counts these.  A row whose identity is held with a LOWER key stays
+ *                 live: a bidder may improve
+ *   tranches      T_0 = max(tranche, K) (tranche == 0: BBP_BEST_TRANCHE_DEFAULT), T_t = T_0 2^t; tranche t is the next min(T_t, live)
+ *                 live candidates in candidate order (key descending, index ascending); every one is verified, its status is exactly
+ *                 what bbp_verify_rounds reports, n_examined counts them
+ *   merge         after each tranche every BBP_OK row enters; one whose identity is already held replaces that entry only if it comes
+ *                 before it in rank order; the standing is cut to its first K entries, and what falls out is forgotten
+ *   stop          when no live candidate is left
+ *   entered       the offer's rows that are entries after it, offer-local indices in rank order; n_entered is the true length,
+ *                 entered_out receives min(n_entered, cap) of them, entries beyond are not written.  The standing keeps no row bytes: the
+ *                 caller keeps the rows that entered_out names
+ *   failure       an offer that fails with BBP_ERR_DEVICE or BBP_ERR_INTERNAL leaves the standing and its offered count exactly as they
+ *                 were: the call works on a copy in its own scratch and commits once, at the end
+ * What follows: an offer to a fresh standing reports what bbp_verify_round_best_distinct reports for the same rows, floor, K and tranche
+ * (status, n_candidates, n_examined, n_duplicates, entered == best).  After any sequence of offers the entries are the first K, in rank
+ * order, of: per z_img the first BBP_OK row at or above the floor in rank order, over ALL rows offered so far -- whatever the cuts
+ * between bursts and whatever `tranche`.  A valid row that is offered again is never verified again (BBP_ROW_SKIPPED or
+ * BBP_ROW_DUPLICATE) and is not uploaded.  A forged row with a high claimed score costs one failed check each time it is sent: rejected
+ * rows are not remembered.  n_examined + n_duplicates <= n_candidates; which rows are examined depends only on the inputs, never on timing.
+ *
+ * bbp_standing_open: screening, the first failing check decides: a NULL pointer BBP_ERR_BAD_ARG; N == 0 BBP_ERR_BAD_ARG; N > BBP_MAX_ITEMS
+ * BBP_ERR_GENS_LEN; K == 0 or K > BBP_STANDING_MAX_K BBP_ERR_BAD_ARG; BBP_STANDING_MAX_OPEN standings already open on the handle
+ * BBP_ERR_BAD_ARG.  *standing is the handle of the new standing.  Its state is a device allocation of its OWN (a header -- count, bar,
+ * offered -- and K x (8 + 8 + 2) words; on a pool: on member 0), not part of the scratch the best calls share: other best calls, and
+ * offers to other standings, may run between two offers.  bbp_reserve does not size it.
+ * bbp_standing_offer, the host form (a context or a pool): screening: an unknown or closed handle BBP_ERR_BAD_ARG; a NULL pointer
+ * BBP_ERR_BAD_ARG (entered_out may be NULL only when cap == 0); B > BBP_SELECT_MAX_BIDS BBP_ERR_BAD_ARG; B == 0 BBP_OK with zero counts
+ * and the standing unchanged.  64 bytes per row go up, score || z_img; a tranche's rows are gathered from the caller's memory and
+ * verified through bbp_verify_rounds_aggregated's own path exactly as bbp_verify_round_best_distinct does it (entropy source,
+ * BBP_HOST_CHUNK_VERIFY, the health word, verify mixing and the pool split hold as they do there); one more wait than that call: the
+ * commit.  Serialised with the other best calls of the context.
+ * bbp_standing_read: the entries in rank order: serials_out (u64 each), scores_out and z_imgs_out (32 bytes each) receive min(count,
+ * cap) entries; any output except n_entries may be NULL; n_entries is the true count, n_offered the rows offered so far.
+ * bbp_standing_close: closes the standing and frees its state; the handle may be handed out again.  bbp_free closes what is still open.
+ * bbp_debug_standing_offer, test hook (synchronises; a pool refuses it): an offer of made-up keys, ids (B x 32 bytes each) and verdicts
+ * (B x int32) through the shipped kernels against a real standing's state; nothing is verified.  Screening as the offer's (B == 0 is
+ * BBP_OK with zero counts); beyond that it refuses what bbp_debug_round_best_distinct refuses: a verdict outside the three.
+ * bbp_debug_standing_trip, test hook: the next offer to the standing raises the offer's internal flag word on the device behind its
+ * after-th merge (after >= 1) and so ends with BBP_ERR_INTERNAL, as an offer whose bounded loops ran out does; no device fault is involved.
+ * Out of scope: a _dev form of the offer; standings over many rounds in one call; a server opcode; keeping the winning rows' bytes; a
+ * memory of rejected rows; a round table resident across offers (the round travels with every tranche, as in the one-shot calls). */
+#define BBP_STANDING_MAX_K 1024u
+#define BBP_STANDING_MAX_OPEN 64u
+int32_t bbp_standing_open(bbp_ctx* ctx, uint32_t N, const uint8_t* round, const uint8_t floor32[32], uint32_t K, uint32_t* standing);
+int32_t bbp_standing_offer(bbp_ctx* ctx, uint32_t standing, uint32_t B, const uint8_t* rows, uint32_t tranche, uint32_t cap, uint32_t* entered_out,
+                           uint32_t* n_entered, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status);
+int32_t bbp_standing_read(bbp_ctx* ctx, uint32_t standing, uint32_t cap, uint64_t* serials_out, uint8_t* scores_out, uint8_t* z_imgs_out,
+                          uint32_t* n_entries, uint64_t* n_offered);
+int32_t bbp_standing_close(bbp_ctx* ctx, uint32_t standing);
+int32_t bbp_debug_standing_offer(bbp_ctx* ctx, uint32_t standing, uint32_t B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts,
+                                 uint32_t tranche, uint32_t cap, uint32_t* entered_out, uint32_t* n_entered, uint32_t* n_candidates,
+                                 uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status);
+int32_t bbp_debug_standing_trip(bbp_ctx* ctx, uint32_t standing, uint32_t after);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.

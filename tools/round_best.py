@@ -35,6 +35,13 @@ One JSON line per cell, to stdout and to --out (default profiles/r19_round_best.
           The new call's outputs are asserted equal to the model of tests/rounds_best_distinct_cases.py on the verdicts of the last
           arm, and to the loop's; without duplicates it must examine exactly the rows the plain call examines.
 
+  --standing [OUT]   instead of the above: a standing ("Standing of a round") of one round at N = 50, K = 3, default tranche; 8192 rows
+          arrive as 32 offers of 256, into OUT (profiles/r24_round_standing.jsonl).  Traffic: every valid row sent once / the second half of
+          every offer resends earlier rows / a forged flood on top (16 rows per offer under the best bidder's z_img and a forged score).
+          Arms: offers to a standing; bbp_verify_round_best_distinct over all rows so far after each burst; the same call on each burst
+          alone.  Per arm ms per burst, bytes uploaded, rows verified; every output of every offer is asserted equal to the model of
+          tests/round_standing_cases.py.
+
 Rows are 64 proved bids of the round repeated (byte-equal rows do occur in the protocol too); arms alternate in one process; every figure
 is the best of --calls calls, taken --runs times after a warm-up: median and range."""
 import argparse
@@ -576,8 +583,132 @@ def rounds_distinct_main(args):
             ctx.close()
 
 
+def standing_traffic(bbp, N, base_rows, kind, n_offers, per_offer):
+    """n_offers x per_offer rows of one round as a list: every bidder of base_rows once, in ascending score (so the standing keeps
+    changing), spread evenly over the first half of the stream; the other rows claim scores below every real one.  half_resent: the
+    second half of every offer resends rows of earlier offers (offer 0: of its own first half), byte-equal.  forged_flood: on top of that
+    16 rows of every offer carry the best bidder's row under a forged score near l, each a different one."""
+    import random
+    row, key_off = bbp.round_row_size(N), bbp.record_size(N)
+    score = lambda r: int.from_bytes(r[key_off:key_off + 32], "little")
+    uniq = sorted({base_rows[row * i:row * (i + 1)][-32:]: base_rows[row * i:row * (i + 1)] for i in range(len(base_rows) // row)}.values(), key=score)
+    B = n_offers * per_offer
+    step = (B // 2) // len(uniq)
+    L = (1 << 252) + 27742317777372353535851937790883648493
+    rnd = random.Random(24)
+    rows = []
+    for i in range(B):
+        o, j = divmod(i, per_offer)
+        if kind != "no_resends" and j >= per_offer // 2:
+            rows.append(rows[rnd.randrange(per_offer // 2)] if o == 0 else rows[rnd.randrange(o * per_offer)])
+        elif kind == "forged_flood" and j < 16:
+            rows.append(uniq[-1][:key_off] + (L - 1 - i).to_bytes(32, "little") + uniq[-1][key_off + 32:])
+        elif i % step == 0 and i // step < len(uniq):
+            rows.append(uniq[i // step])
+        else:
+            r = uniq[i % len(uniq)]
+            rows.append(r[:key_off] + (i + 1).to_bytes(32, "little") + r[key_off + 32:])
+    return rows, [score(r) for r in rows], [r[-32:] for r in rows]
+
+
+def standing_main(args):
+    """--standing: one round at N = 50, K = 3; 8192 rows arrive as 32 offers of 256.  Arms, alternated: (a) offers to a standing; (b)
+    bbp_verify_round_best_distinct over all rows so far after each burst; (c) the same call on each burst alone, floor 0 (its answers
+    would still have to be merged by hand: here for cost).  Per arm ms per burst, bytes uploaded and rows verified; arm (a)'s rows
+    verified are asserted equal to the model's of tests/round_standing_cases.py on the verdicts of bbp_verify_rounds_aggregated."""
+    import torch
+    torch.cuda.init()
+    import dusk_blindbidproof_amd as bbp
+    from tests import prove_round_cases as rc
+    from tests import round_standing_cases as sc
+    box = box_id()
+    os.makedirs(os.path.dirname(os.path.abspath(args.standing)), exist_ok=True)
+    N, K, tranche, n_offers, per, n_base = 50, 3, 0, 32, 256, 41
+    B = n_offers * per
+    unit = "ms of host time per burst (a run is the %d bursts of the round in order), %d runs after a warm-up, arms alternated" % (n_offers, args.runs)
+    with open(args.standing, "w") as f:
+        def emit(rec):
+            rec.update(box=box, commit=args.commit)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        ctx = bbp.Context(0)
+        lib, h = bbp.lib, ctx.handle
+        try:
+            r0 = rc.honest(N, n_base, tag=24)
+            proved, _t, st = ctx.prove_round(N, r0.table, r0.bid_bytes)
+            assert st == [0] * n_base
+            size, tab = bbp.round_row_size(N), 32 * (1 + N)
+            table = (ctypes.c_uint8 * len(r0.table)).from_buffer_copy(r0.table)
+            Ns, floor, nfb = (ctypes.c_uint32 * 1)(N), (ctypes.c_uint8 * 32)(), ctypes.c_uint32()
+            for kind in ("no_resends", "half_resent", "forged_flood"):
+                row_list, keys, ids = standing_traffic(bbp, N, proved, kind, n_offers, per)
+                blob = bytearray(b"".join(row_list))
+                host = (ctypes.c_uint8 * len(blob)).from_buffer(blob)
+                status = (ctypes.c_int32 * B)()
+                assert lib.bbp_verify_rounds_aggregated(h, 1, Ns, table, B, None, host, status, 0, ctypes.byref(nfb)) == 0
+                verdicts = list(status)
+                model, want, m_bytes = sc.Standing(0, K), [], 0
+                for o in range(n_offers):
+                    sl = slice(o * per, (o + 1) * per)
+                    want.append(model.offer(keys[sl], ids[sl], verdicts[sl], tranche))
+                    m_bytes += 64 * per + want[-1][3] * (size + 32 + 4) + model.tranches * tab
+                assert [(k, i) for k, i, _ in model.entries] == [(k, i) for k, i, _ in sc.truth(keys, ids, verdicts, 0, K)]
+                ent = (ctypes.c_uint32 * K)()
+                n = [ctypes.c_uint32() for _ in range(4)]
+                p = [ctypes.byref(x) for x in n]
+                at = lambda first: ctypes.byref(host, size * first)
+                seen = {}
+
+                def a_standing():
+                    hs = ctx.standing_open(N, r0.table, 0, K)
+                    got = []
+                    for o in range(n_offers):
+                        assert lib.bbp_standing_offer(h, hs, per, at(o * per), tranche, K, ent, p[0], p[1], p[2], p[3], status) == 0, lib.bbp_last_error(h)
+                        got.append((list(ent)[:n[0].value], n[0].value, n[1].value, n[2].value, n[3].value, list(status)[:per]))
+                    seen["entries"] = ctx.standing_read(hs)
+                    ctx.standing_close(hs)
+                    return got
+
+                def one_shot(first, rows):
+                    assert lib.bbp_verify_round_best_distinct(h, N, table, rows, at(first), floor, K, tranche, K, ent, p[0], p[1], p[2], p[3], status) == 0
+                    return n[2].value, 64 * rows + n[2].value * (size + 32 + 4)
+
+                def b_all_so_far():
+                    return [one_shot(0, (o + 1) * per) for o in range(n_offers)]
+
+                def c_burst_alone():
+                    return [one_shot(o * per, per) for o in range(n_offers)]
+                got = a_standing()
+                assert got == want, "an offer differs from the model"  # nothing here is tuned: the rules predict every output
+                examined = sum(g[3] for g in got)
+                assert examined == sum(w[3] for w in want)
+                assert list(zip(seen["entries"].scores, seen["entries"].z_imgs)) == [(k.to_bytes(32, "little"), i) for k, i, _ in model.entries]
+                arms = {"standing_offers": a_standing, "best_distinct_over_all_so_far": b_all_so_far, "best_distinct_on_each_burst_alone": c_burst_alone}
+                b_out, c_out = b_all_so_far(), c_burst_alone()
+                args.calls = 1
+                rec = {"section": "standing", "N": N, "K": K, "tranche": "default", "rows": B, "offers": n_offers, "rows_per_offer": per, "traffic": kind,
+                       "valid_rows": verdicts.count(0), "unit": unit}
+                for name, v in timed(arms, list(arms), args).items():
+                    rec[name] = {k: round(x / n_offers, 4) for k, x in v.items()}
+                rec["rows_verified"] = {"standing_offers": examined, "best_distinct_over_all_so_far": sum(x for x, _ in b_out),
+                                        "best_distinct_on_each_burst_alone": sum(x for x, _ in c_out)}
+                # score || z_img of every row handed over, the examined rows with their entropy and status words, a round table per tranche
+                # (arms b and c: the table counted once per call -- a lower bound)
+                rec["bytes_uploaded"] = {"standing_offers": m_bytes, "best_distinct_over_all_so_far": sum(y for _, y in b_out) + n_offers * tab,
+                                         "best_distinct_on_each_burst_alone": sum(y for _, y in c_out) + n_offers * tab}
+                rec["duplicates_left_unverified_by_standing"] = sum(g[4] for g in got)
+                emit(rec)
+            assert ctx.health() == 0
+        finally:
+            ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--standing", nargs="?", const=os.path.join(ROOT, "profiles", "r24_round_standing.jsonl"), default="", metavar="OUT",
+                    help="measure offers to a standing instead, into OUT (default profiles/r24_round_standing.jsonl)")
     ap.add_argument("--rounds-distinct", default="", metavar="OUT",
                     help="measure bbp_verify_rounds_best_distinct instead, into OUT (profiles/r23_rounds_best_distinct.jsonl)")
     ap.add_argument("--rounds", default="", metavar="OUT", help="measure bbp_verify_rounds_best instead, into OUT (profiles/r22_rounds_best.jsonl)")
@@ -588,6 +719,8 @@ def main():
     ap.add_argument("--calls", type=int, default=2)
     ap.add_argument("--sections", default="cells,sweep")
     args = ap.parse_args()
+    if args.standing:
+        return standing_main(args)
     if args.rounds_distinct:
         return rounds_distinct_main(args)
     if args.rounds:
