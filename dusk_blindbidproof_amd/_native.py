@@ -116,6 +116,7 @@ SIGNATURES = {
     "bbp_debug_secret_residue": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u32]),
     "bbp_debug_secret_scan": (_i32, [_vp, _vp, _u32, ctypes.POINTER(_u64), ctypes.POINTER(_u64)]),
     "bbp_debug_wipe_cost": (_i32, [_vp, _i32, ctypes.POINTER(_u64), ctypes.POINTER(_u32), ctypes.POINTER(ctypes.c_float)]),
+    "bbp_debug_poison_scratch": (_i32, [_vp, _u32, _i32, ctypes.POINTER(_u64), ctypes.POINTER(_u64), ctypes.POINTER(_u32)]),
     "bbp_debug_challenges": (_i32, [_vp, _u32, _u32, _u32, _vp]),
     "bbp_debug_table": (_i32, [_vp, _u32, ctypes.POINTER(_vp), ctypes.POINTER(_u64)]),
     "bbp_debug_varbase": (_i32, [_vp, _u32, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -991,6 +992,14 @@ class Context:
         nbytes, launches, us = ctypes.c_uint64(), ctypes.c_uint32(), ctypes.c_float()
         self._check(lib.bbp_debug_wipe_cost(self._h, 1 if clear else 0, ctypes.byref(nbytes), ctypes.byref(launches), ctypes.byref(us)))
         return nbytes.value, launches.value, us.value
+
+    def debug_poison_scratch(self, word, sticky=False):
+        """Test hook: fill every scratch buffer, ring, staging slot and pinned mirror of the context with the 32-bit `word`, except the
+        state csrc/secret_map.h exempts (bbp_debug_poison_scratch); sticky: buffers allocated later start out filled too, until a call
+        without it.  Returns (device bytes, pinned host bytes, device buffers) filled; synchronises.  No call may be in flight."""
+        dev, host, n = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint32()
+        self._check(lib.bbp_debug_poison_scratch(self._h, word, 1 if sticky else 0, ctypes.byref(dev), ctypes.byref(host), ctypes.byref(n)))
+        return dev.value, host.value, n.value
 
     def debug_challenges(self, B, N, proof):
         out = (ctypes.c_uint8 * (32 * 32))()

@@ -508,7 +508,7 @@ static int32_t pinned_reserve(bbp_ctx* ctx, void*& p, size_t& cap, size_t bytes)
     if (p) BBP_HIP_TRY(ctx, hipHostFree(p));
     p = nullptr;
     cap = 0;
-    const size_t want = bytes + (bytes >> 3) + 4096;
+    const size_t want = (bytes + (bytes >> 3) + 4096 + 15) & ~(size_t)15;  // whole 16-byte grains, like dev_reserve's
     BBP_HIP_TRY(ctx, hipHostMalloc(&p, want, hipHostMallocDefault));
     if (wipe_on(ctx)) memset(p, 0, want);  // ... and a new one starts out zero: a call erases what it wrote, not the capacity
     cap = want;

@@ -171,6 +171,10 @@ struct bbp_ctx {
     // Secret wiping (bbp_set_secret_wipe, wipe.hip; the classes are secret_map.h's): while on, every SECRET buffer reads zero whenever
     // no prove-side call is in flight -- each call erases what it wrote, at the end of the stream that guards the buffer
     std::atomic<int> secret_wipe{0};
+    // bbp_debug_poison_scratch(.., sticky != 0) (wipe.hip; tests): while set, dev_reserve fills every buffer it newly allocates with
+    // poison_word, the way it fills with zero under wiping -- the first call of a fresh context and every regrowth run over poison too
+    std::atomic<int> poison_sticky{0};
+    uint32_t poison_word = 0;
     struct WipeLog {  // the wipes enqueued since the log was cleared (bbp_debug_wipe_cost): how many bytes in how many launches, over which buffers
         static constexpr int CAP = 24;  // = WIPE_SPANS: what one lone launch replays
         uint64_t bytes = 0;
@@ -328,8 +332,12 @@ inline int32_t dev_reserve(bbp_ctx* ctx, DevBuf& b, size_t bytes) {
     }
     b.p = nullptr;
     b.cap = 0;
-    size_t want = bytes + (bytes >> 3) + 4096;
+    size_t want = (bytes + (bytes >> 3) + 4096 + 15) & ~(size_t)15;  // whole 16-byte grains: a wipe, a fill and a scan cover all of it
     BBP_HIP_TRY(ctx, hipMalloc(&b.p, want));
+    if (ctx->poison_sticky.load(std::memory_order_relaxed) != 0 && !wipe) {  // test hook: a new buffer starts out as the poison word
+        BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)b.p, (int)ctx->poison_word, want / 4, nullptr));
+        BBP_HIP_TRY(ctx, hipStreamSynchronize(nullptr));
+    }
     if (wipe) {  // ... and a new one starts out zero (the driver hands out whatever was freed last): a call erases what it wrote, not the capacity
         BBP_HIP_TRY(ctx, hipMemsetAsync(b.p, 0, want, nullptr));
         BBP_HIP_TRY(ctx, hipStreamSynchronize(nullptr));  // the context's streams do not wait for the null stream

@@ -160,6 +160,21 @@ inline bool batch_spans(u32 B, const BatchDims& d, int cls, BatchSpans& out) {
     X("io.h_out", c->io[i].h_out, c->io[i].h_cap, S + bbp_ctx::IO_VSLOTS, i < S)                                                        \
     X("sel.h", c->sel_h, c->sel_h_cap, 1, true)              /* ... and its mirror: the bids going up, scores and selection coming down */ \
     X("best.h", c->best_h, c->best_h_cap, 1, false)          /* bbp_verify_round_best's mirror: claimed scores up, verdicts and ranks down (public) */
+// Scratch discipline: a call reads only what it wrote itself, the resident tables, or state named here.  The test hook
+// bbp_debug_poison_scratch fills every buffer of the two lists above EXCEPT these, so a buffer is poisoned unless it is exempt, and
+// exempting one is a line here with the reason its contents outlive a call.  X(name, reason): `name` as in the lists above.
+#define BBP_POISON_EXEMPT(X)                                                                                                            \
+    X("stand", "a standing's entries live from bbp_standing_open to bbp_standing_close: every offer reads what the offers before it committed")
+inline bool poison_exempt(const char* name) {
+    auto same = [](const char* a, const char* b) {
+        while (*a && *a == *b) a++, b++;
+        return *a == *b;
+    };
+#define X(n, reason) if (same(name, n)) return true;
+    BBP_POISON_EXEMPT(X)
+#undef X
+    return false;
+}
 // Not DevBufs, all PUBLIC, walked by the scan from wipe.hip: the resident tables gens, ptable, btab, comb, mimc_c (functions of public
 // constants) and the verifier lanes' pinned ns_ring.  Not walked: the compiled circuits' lists and vctab (uploaded from host tables that
 // are functions of N), and the counter words health, chk_counts, agg_count and the pinned h_flag.

@@ -764,7 +764,7 @@ static int32_t stage_host(bbp_ctx* ctx, bbp_ctx::VLane& L, const void* a, size_t
         if (st->h) BBP_HIP_TRY(ctx, hipHostFree(st->h));
         st->h = nullptr;
         st->cap = 0;
-        const size_t want = std::max(bytes + bytes / 2, (size_t)65536);
+        const size_t want = (std::max(bytes + bytes / 2, (size_t)65536) + 15) & ~(size_t)15;  // whole 16-byte grains, like dev_reserve's
         BBP_HIP_TRY(ctx, hipHostMalloc(&st->h, want, hipHostMallocDefault));
         st->cap = want;
     }

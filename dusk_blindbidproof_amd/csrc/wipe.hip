@@ -164,6 +164,37 @@ int32_t wipe_all(bbp_ctx* ctx) {
     return BBP_OK;
 }
 
+// Test hook (bbp_debug_poison_scratch): wipe_all with another fill value and over both classes.  Every DevBuf of the table over its whole
+// capacity and every pinned mirror, except what secret_map.h exempts (state that outlives a call); the resident tables, the compiled
+// circuits and the counter words are not in the walk.  `dirty` stays: what a wiping call owes is not changed by a fill.
+static void fill_words(void* p, size_t bytes, uint32_t word) {  // host memory: whole words, then the ragged end from the word's low bytes
+    uint8_t* q = static_cast<uint8_t*>(p);
+    size_t i = 0;
+    for (; i + 4 <= bytes; i += 4) memcpy(q + i, &word, 4);
+    if (i < bytes) memcpy(q + i, &word, bytes - i);
+}
+int32_t poison_all(bbp_ctx* ctx, uint32_t word, uint64_t* dev_bytes, uint64_t* host_bytes, uint32_t* n_buffers) {
+    BBP_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    BBP_HIP_TRY(ctx, hipDeviceSynchronize());
+    std::vector<MemRef> dev, host;
+    device_buffers(ctx, dev);
+    pinned_buffers(ctx, host);
+    *dev_bytes = 0, *host_bytes = 0, *n_buffers = 0;
+    for (const MemRef& m : dev) {
+        if (!m.buf || poison_exempt(m.name)) continue;  // (no DevBuf behind it: a resident table)
+        BBP_HIP_TRY(ctx, hipMemsetD32Async((hipDeviceptr_t)m.p, (int)word, m.cap / 4, ctx->stream));
+        if (m.cap % 4) BBP_HIP_TRY(ctx, hipMemcpyAsync(static_cast<uint8_t*>(m.p) + m.cap / 4 * 4, &word, m.cap % 4, hipMemcpyHostToDevice, ctx->stream));
+        *dev_bytes += m.cap, ++*n_buffers;
+    }
+    BBP_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (const MemRef& m : host) {
+        if (poison_exempt(m.name)) continue;
+        fill_words(m.p, m.cap, word);
+        *host_bytes += m.cap;
+    }
+    return BBP_OK;
+}
+
 // A host-pointer prove call whose enqueue step failed half-way: what it reserved and did not get to wipe -- every SECRET buffer that is
 // still `dirty` (a call that was enqueued whole has reset its own) and its staging slot with the slot's mirrors -- behind a device
 // synchronise, since streams may still read them.  Other calls' staging slots are theirs: a caller that is collecting its results with
@@ -298,6 +329,16 @@ extern "C" int32_t bbp_debug_secret_scan(bbp_ctx* ctx, const uint8_t* pattern, u
                 if (!memcmp(q + i, pattern, len)) ++*host_hits;
         }
         return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_debug_poison_scratch(bbp_ctx* ctx, uint32_t word, int32_t sticky, uint64_t* dev_bytes, uint64_t* host_bytes, uint32_t* n_buffers) {
+    if (!ctx || !dev_bytes || !host_bytes || !n_buffers) return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_poison_scratch");
+    return api_guard(ctx, [&]() -> int32_t {
+        ctx->poison_word = word;
+        ctx->poison_sticky.store(sticky != 0, std::memory_order_relaxed);
+        return poison_all(ctx, word, dev_bytes, host_bytes, n_buffers);
     });
 }
 

@@ -865,6 +865,20 @@ int32_t bbp_wipe_secrets(bbp_ctx* ctx);
 int32_t bbp_debug_secret_residue(bbp_ctx* ctx, uint64_t* dev_bytes, uint64_t* host_bytes, char* where, uint32_t cap);
 int32_t bbp_debug_secret_scan(bbp_ctx* ctx, const uint8_t* pattern, uint32_t len, uint64_t* dev_hits, uint64_t* host_hits);
 int32_t bbp_debug_wipe_cost(bbp_ctx* ctx, int32_t clear, uint64_t* bytes, uint32_t* launches, float* lone_us);
+/* Test hook only -- scratch discipline: a call reads only what it wrote itself, the resident tables, or state that outlives a call by
+ * contract.  The hook fills everything else with `word`, so that a kernel that reads a row, counter or bucket of an earlier call, or
+ * one that it should have cleared first, computes a wrong byte instead of a plausible one.
+ * It takes the context lock, synchronises the device and fills, over their whole capacity (the allocation slack included), every
+ * grow-only device buffer, ring and staging slot of the context with the 32-bit `word`, and on the host every pinned mirror and the
+ * verifier lanes' pinned N staging; then it synchronises again.  Not filled: the buffers csrc/secret_map.h exempts with a reason
+ * (BBP_POISON_EXEMPT: an open standing's entries), the resident tables, the compiled circuits and the counter words (health, check
+ * counts, aggregation counts, the pinned health mirror).  What a wiping call owes is left as it is.  *dev_bytes / *host_bytes: the
+ * bytes filled; *n_buffers: the device buffers filled.
+ * sticky != 0: the context remembers `word`, and until a call with sticky == 0 every buffer the context newly allocates -- the first
+ * call of a fresh context, every regrowth -- starts out filled with it (with secret wiping on it starts out zero, as always).
+ * Use small words (the tests use 1 and 3): an index or count read from the fill then stays inside the allocation slack, a status is a
+ * real error code, a scalar is canonical and non-zero.  No call of the context may be in flight; a pool refuses it (take a member). */
+int32_t bbp_debug_poison_scratch(bbp_ctx* ctx, uint32_t word, int32_t sticky, uint64_t* dev_bytes, uint64_t* host_bytes, uint32_t* n_buffers);
 
 /* Parity hook: the 32-scalar challenge block of proof `proof` of the LAST batch call of geometry (B, N):
  * y z u x w y^-1 t1..t6 tb1..tb6 t_x t_x~ e~ ... (MiscSlot order in csrc/batch_layout.h), 32 x 32 bytes. */

@@ -120,6 +120,35 @@ int main() {
                  B, N, sec.n, gap, overlap, outside, on_public, any_gap);
         expect(ok, buf);
     }
+    // scratch discipline: what bbp_debug_poison_scratch leaves alone.  Every exempt name is a buffer of the context, named exactly once
+    // in the two buffer lists, with a reason; the list itself is printed for the Python tier to hold against its literal.
+    {
+        std::vector<std::string> buffers, exempt;
+#define X(name, field, count, secret) buffers.push_back(name);
+        BBP_CTX_DEVICE_BUFFERS(X, 0, 0, 0)
+#undef X
+#define X(name, ptr, cap, count, secret) buffers.push_back(name);
+        BBP_CTX_PINNED_BUFFERS(X, 0)
+#undef X
+        bool ok = true, reasons = true;
+        std::string list;
+#define X(name, reason) exempt.push_back(name), reasons = reasons && strlen(reason) >= 20;
+        BBP_POISON_EXEMPT(X)
+#undef X
+        for (const std::string& e : exempt) {
+            const long n = std::count(buffers.begin(), buffers.end(), e);
+            if (n != 1) ok = false, printf("  exempt buffer %s is named %ld times in the buffer lists\n", e.c_str(), n);
+            if (std::count(exempt.begin(), exempt.end(), e) != 1) ok = false, printf("  %s is exempted more than once\n", e.c_str());
+            if (!poison_exempt(e.c_str())) ok = false;
+            list += (list.empty() ? "" : " ") + e;
+        }
+        size_t n_poisoned = 0;
+        for (const std::string& b : buffers) n_poisoned += !poison_exempt(b.c_str());
+        ok = ok && !poison_exempt("nosuch") && !poison_exempt("") && !poison_exempt("stan") && n_poisoned + exempt.size() == buffers.size();
+        expect(ok && reasons, "every poison-exempt buffer is one buffer of the context, exempted once, with a reason (" + std::to_string(n_poisoned) + " of " +
+                                  std::to_string(buffers.size()) + " buffers are poisoned)");
+        printf("poison exempt: [%s]\n", list.c_str());
+    }
     if (g_fail) return 1;
     printf("secret_map_check ok\n");
     return 0;

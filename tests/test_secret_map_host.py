@@ -46,6 +46,26 @@ def test_every_batch_array_of_the_issue_is_secret():
     assert sorted(public) == sorted("zpow ypow yipow wl wr wo enc".split())
 
 
+POISON_EXEMPT = ["stand"]  # what bbp_debug_poison_scratch leaves alone: a new buffer is poisoned by default, exempting one changes this line
+
+
+def test_poison_exempt_list_is_the_expected_one_and_names_real_buffers(ge):
+    """BBP_POISON_EXEMPT (csrc/secret_map.h): every name occurs exactly once in the context's buffer lists (the stand-alone program
+    expands the macros), and the list is the literal above, both as compiled and as written."""
+    r = subprocess.run([ge.build_secret_map_check()], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    assert "ok: every poison-exempt buffer is one buffer of the context, exempted once, with a reason" in r.stdout
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("poison exempt: ")]
+    assert len(line) == 1 and line[0] == "poison exempt: [%s]" % " ".join(POISON_EXEMPT), line
+    src = open(os.path.join(ROOT, "dusk_blindbidproof_amd", "csrc", "secret_map.h")).read()
+    body = src.split("#define BBP_POISON_EXEMPT(X)")[1].split("\ninline")[0]
+    assert re.findall(r'X\("([\w.]+)",', body) == POISON_EXEMPT
+    buffers = re.findall(r'^\s*X\("([\w.]+)",', src.split("#define BBP_POISON_EXEMPT(X)")[0], flags=re.M)
+    assert len(buffers) >= 30 and all(buffers.count(n) == 1 for n in POISON_EXEMPT)
+    hdr = open(os.path.join(ROOT, "include", "bbp.h")).read()
+    assert re.search(r"\bbbp_debug_poison_scratch\s*\(", hdr) and "BBP_POISON_EXEMPT" in hdr and "No call of the context may be in flight" in hdr
+
+
 def test_header_and_binding_name_the_entry_points():
     """The four entry points of the contract and the cost hook that goes with them (bbp_debug_wipe_cost)"""
     hdr = open(os.path.join(ROOT, "include", "bbp.h")).read()
