@@ -212,7 +212,7 @@ struct bbp_ctx {
     void* sel_h = nullptr;
     size_t sel_h_cap = 0;
     hipEvent_t ev_sel = nullptr;
-    // bbp_verify_round_best, its _dev form and bbp_debug_round_best (capi_prove.hip; the layout is round_best.h's BestLayout): keys,
+    // bbp_verify_round_best, its _dev form and bbp_debug_round_best (capi_best.hip; the layout is round_best.h's BestLayout): keys,
     // candidate and winner records, statuses, one tranche's selection and verdicts on the device, a pinned mirror of what travels, and
     // -- the _dev form only -- the gathered rows of one tranche with their entropy rows.  All PUBLIC (secret_map.h), all grow on demand
     // (bbp_reserve does not size them); best_mu serialises the calls that use them, and is taken BEFORE the context lock.
@@ -225,7 +225,7 @@ struct bbp_ctx {
     void* best_h = nullptr;
     size_t best_h_cap = 0;
     hipEvent_t ev_best = nullptr;
-    // Standings (bbp_standing_open, ...; capi_prove.hip; round_standing.h's StandingLayout): per open standing a device allocation of
+    // Standings (bbp_standing_open, ...; capi_best.hip; round_standing.h's StandingLayout): per open standing a device allocation of
     // its OWN -- header, K keys, ids and serials -- that lives from open to close, PUBLIC like the state above, and what the host knows
     // of it: the round, the floor, and a shadow of the header as of the last commit.  An offer works in best_dev and commits at its end.
     // Guarded by best_mu; a pool keeps its standings on member 0.
@@ -487,7 +487,7 @@ int32_t pool_prove_round(bbp_ctx* pool, uint32_t N, const uint8_t* round, uint32
                          uint64_t* toggles_out, int32_t* status);
 // every verify form on a pool handle: the rows block-split over the members (VerifyRows::slice); group == 0: the plain entry point
 int32_t pool_verify(bbp_ctx* pool, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback);
-// capi_prove.hip: the host-pointer verify path of a context or a pool, after the entry point's screening (what a pool runs on its members)
+// capi_verify.hip: the host-pointer verify path of a context or a pool, after the entry point's screening (what a pool runs on its members)
 int32_t verify_host(bbp_ctx* ctx, const VerifyRows& rows, const uint8_t* in, int32_t* status, uint32_t group, uint32_t* n_fallback);
 int32_t pool_msm_batch(bbp_ctx* pool, uint32_t B, uint32_t n_terms, const uint8_t* scalars, uint32_t layout, uint8_t* out32);
 int32_t pool_reject(bbp_ctx* pool, const char* what);  // BBP_ERR_BAD_ARG + message: entry points that need ONE device

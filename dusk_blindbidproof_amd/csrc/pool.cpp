@@ -9,7 +9,7 @@
 //   * bbp_prove_batch / bbp_verify_batch* / bbp_verify_rounds* / bbp_msm_batch: contiguous block split by index over the members, sizes
 //     differing by at most one (= sharding.shard_range), one host thread per member, results land in request order
 //     because every member writes straight into its slice of the caller's buffers;
-//   * bbp_verify_round_best / bbp_verify_round_best_distinct / bbp_verify_rounds_best (capi_prove.hip): keys, selection and marks on
+//   * bbp_verify_round_best / bbp_verify_round_best_distinct / bbp_verify_rounds_best (capi_best.hip, capi_bests.hip): keys, selection and marks on
 //     member 0; every tranche or step is a rounds call split as above;
 //   * no data crosses between GPUs (proofs are independent units; tables are replicated per member at init).
 // Host-only C++ (no kernels); everything that touches a device goes through the members' own entry points.

@@ -1,7 +1,7 @@
 // What the rows of a prove call are and where a call keeps them: the row sizes of the prove side, named once, and the staging layout
 // of one host-pointer prove call (bbp_prove_batch, bbp_prove_round) with its two siblings for the device forms' scratch rings.
-// capi_prove.hip lays its buffers out by these values and bbp_reserve sizes them by the same values (DESIGN.md "The host prove call").
-// Plain arithmetic, no HIP calls: pool.cpp, prover.hip, capi_prove.hip, round_bids.h and the CPU test tier (tests/host_check.cpp)
+// capi_prove.hip lays its buffers out by these values and bbp_reserve (capi_ctx.hip) sizes them by the same values (DESIGN.md "The host prove call").
+// Plain arithmetic, no HIP calls: pool.cpp, prover.hip, the capi_*.hip units, round_bids.h and the CPU test tier (tests/host_check.cpp)
 // include it; the helpers that kernels use are BBP_HD.
 #pragma once
 #include <stddef.h>

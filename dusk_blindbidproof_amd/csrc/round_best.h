@@ -303,11 +303,12 @@ struct BestDistinctLayout {
     }
 };
 
-#ifdef __HIPCC__
+constexpr u32 BEST_T = 64, BEST_GATHER_T = 256;  // workgroup sizes: the per-row kernels (rounds_best.h's too), the two gathers
+
+#if defined(__HIPCC__) && defined(BBP_ROUND_BEST_KERNELS)  // the kernels: compiled by the one unit that launches them (capi.h)
 // One lane per row, 64-lane workgroups.  The key is read byte by byte at base + i stride + off: the _dev form's stride 1313 + 32 N is
 // odd, so every alignment occurs (the host forms: stride 32, offset 0).  Writes the candidate record (BBP_OK for a candidate), the
 // winner record (not a member yet) and the row's initial status: BBP_ERR_FORMAT for a key >= l, BBP_ROW_SKIPPED for every other row.
-constexpr u32 BEST_T = 64;
 __global__ void __launch_bounds__(BEST_T) k_best_keys(u32 B, const u8* __restrict__ base, size_t stride, size_t off, RsFloor floor, u32* __restrict__ recs,
                                                       u32* __restrict__ win, int32_t* __restrict__ status) {
     const u32 i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -330,7 +331,6 @@ __global__ void __launch_bounds__(BEST_T) k_best_keys(u32 B, const u8* __restric
 // j of out_rows, its 32 entropy bytes -> row j of out_ent.  Aligned 32-bit stores; a stored word is put together from the two aligned source words that hold
 // it, or -- where those would reach outside the source row -- from its four bytes, so nothing outside [row, row + rb) is read.
 // Workgroups at or beyond the device-side count leave at once.
-constexpr u32 BEST_GATHER_T = 256;
 __global__ void __launch_bounds__(BEST_GATHER_T) k_best_gather(u32 rb, u32 first, const u32* __restrict__ sel, const u32* __restrict__ counts,
                                                                const u8* __restrict__ rows, const u8* __restrict__ ent, u8* __restrict__ out_rows,
                                                                u8* __restrict__ out_ent) {

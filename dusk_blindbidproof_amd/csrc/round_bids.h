@@ -86,7 +86,7 @@ BBP_HD u8 round_row_byte(u32 N, u32 o, const u8* record, const u32* rb) {
 
 // (the scratch of one device pass, RoundScratch / round_scratch: prove_io.h)
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && defined(BBP_ROUND_BIDS_KERNELS)  // the kernels: compiled by the one unit that launches them (capi.h)
 // One lane per bid; the four chains are 1440 dependent Montgomery products, so the wave lives for milliseconds and is fenced onto
 // CUs of its own by its launch (serial_lds_bytes), like k_prepare_bids.  Writes the bid's RB_WORDS words, nothing else.
 // n_dev (NULL: all B): a device-side count -- only the first min(B, *n_dev) bids exist (bbp_select_round_dev sizes the launch by its cap).

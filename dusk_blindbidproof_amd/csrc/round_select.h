@@ -111,7 +111,7 @@ BBP_HD void round_score_eval(u32 N, const u8* bid, const sc* rblk, int32_t seed_
     out[RS_STATUS] = (u32)BBP_OK;
 }
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && defined(BBP_ROUND_SELECT_KERNELS)  // the kernels: compiled by the one unit that launches them (capi.h)
 // One lane per bid, 64-lane workgroups so that a small call still spreads over the CUs, no LDS: the waves of several workgroups share
 // a SIMD and hide each other's multiply latency (DESIGN.md "Selecting a round's bids" has the register and occupancy figures).
 // Writes the bid's record, its status and -- unless NULL -- its score.
@@ -167,7 +167,7 @@ struct RsState {
 };
 static_assert(sizeof(RsState) <= RS_STATE_BYTES, "prove_io.h reserves RS_STATE_BYTES for the selection's state");
 
-#ifdef __HIPCC__
+#if defined(__HIPCC__) && defined(BBP_ROUND_SELECT_KERNELS)
 // true in exactly one workgroup of the launch: the one whose lanes arrive here last.  Everything the others wrote before is visible to it.
 __device__ inline bool rs_last_workgroup(RsState* st) {
     __shared__ u32 s_last;

@@ -91,7 +91,7 @@ inline uint64_t hash_bytes(const uint8_t* p, size_t n) {
     return h ^ (h >> 32);
 }
 
-// what a combined call runs (capi_prove.hip); both take the context lock themselves
+// what a combined call runs (capi_prove.hip, capi_verify.hip); both take the context lock themselves
 int32_t prove_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, const uint8_t* in, const uint8_t* entropy, uint8_t* out, int32_t* status,
                            std::string* err);
 int32_t verify_batch_locked(bbp_ctx* ctx, uint32_t B, uint32_t N, uint32_t rec_ver, const uint8_t* in, int32_t* status, std::string* err);

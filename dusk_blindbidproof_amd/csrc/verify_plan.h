@@ -1,6 +1,6 @@
 // How one verify call is laid out and launched: the knobs, what the plan needs of the circuits, the plan that plan_verify decides
 // from them (front end, launch geometry, round offsets, the three scratch layouts) and the staging layout of one host-pointer call.
-// verifier.inc and capi_prove.hip execute these values; nothing else decides (DESIGN.md section 4 "The plan of a verify call").
+// verifier.inc and capi_verify.hip execute these values; nothing else decides (DESIGN.md section 4 "The plan of a verify call").
 // Host arithmetic only, no HIP calls: the CPU test tier compiles it too (tests/host_check.cpp).
 #pragma once
 #include <stdint.h>

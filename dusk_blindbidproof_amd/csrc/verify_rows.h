@@ -1,6 +1,6 @@
 // What the rows of one verify call are: the one descriptor every verify path passes along, from the extern "C" entry points
 // through the pool split and the host chunk loop down to the launches (include/bbp.h "bbp_verify_batch", "_mixed", "bbp_verify_rounds").
-// Host-only, no HIP types: pool.cpp, capi_prove.hip, verifier.inc and the CPU test tier (tests/host_check.cpp) include it.
+// Host-only, no HIP types: pool.cpp, the capi_*.hip units, verifier.inc and the CPU test tier (tests/host_check.cpp) include it.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>

@@ -167,6 +167,6 @@ def test_header_binding_pool_surface_and_screening_without_a_device(bbp):
     assert lib.bbp_verify_rounds_best_distinct_dev(None, 1, 1, 1, 1, 1, 1, 1, None, 1, 1, 0, None, 1, 1, 1, 1, None, 1, None) == BAD_ARG
     assert lib.bbp_debug_rounds_best_distinct(None, 1, 1, 1, 1, 1, 1, None, 1, 1, 0, 0, None, 1, 1, 1, 1, None, 1) == BAD_ARG
     # ... the entry points screen the numbers with rounds_best.h's rounds_best_screen, whose order tests/test_rounds_best_host.py holds
-    src = open(bbp.lib_path.rsplit("/", 1)[0] + "/csrc/capi_prove.hip").read()
+    src = open(bbp.lib_path.rsplit("/", 1)[0] + "/csrc/capi_bests.hip").read()
     for name in ("bbp_verify_rounds_best_distinct", "bbp_verify_rounds_best_distinct_dev"):
         assert 'bests_screen(ctx, "%s", R, round_Ns, B, round_of, &done)' % name in src, name
