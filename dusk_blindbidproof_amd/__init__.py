@@ -10,7 +10,7 @@ from ._native import (Context, Pool, BbpError, lib, lib_path, STATUS, SIGNATURES
                       ROUND_BID_BYTES, TABLE_GENS, TABLE_PTABLE, TABLE_COMB, TABLE_BTAB, TABLE_IDX_AI, TABLE_IDX_AO, TABLE_IDX_S1,
                       TABLE_IDX_IPA, TABLE_IDX_VER, VARBASE_LANES, VARBASE_PREP_SUM, VARBASE_MX_LANES, VARBASE_MX_PREP_SUM,
                       varbase_points, SELECT_MAX_BIDS, RoundSelection, select_floor, ROW_SKIPPED, BEST_TRANCHE_DEFAULT, RoundBest, ROW_DUPLICATE, RoundBestDistinct,
-                      BEST_MAX_ROUNDS, RoundsBest, RoundsBestDistinct, rounds_floors, STANDING_MAX_K, STANDING_MAX_OPEN, StandingOffer, StandingEntries)
+                      BEST_MAX_ROUNDS, RoundsBest, RoundsBestDistinct, rounds_floors, STANDING_MAX_K, STANDING_MAX_OPEN, StandingOffer, StandingEntries, StandingsOffer)
 
 __all__ = ["Context", "Pool", "BbpError", "lib", "lib_path", "STATUS", "SIGNATURES", "record_size", "entropy_size",
            "LAYOUT_BLIND_G_H", "LAYOUT_BLIND_G", "BASE_BBLIND", "BASE_G0", "BASE_H0", "BASE_B", "NUM_BASES", "STREAM_CONTEXT", "compile_circuit",
@@ -20,4 +20,4 @@ __all__ = ["Context", "Pool", "BbpError", "lib", "lib_path", "STATUS", "SIGNATUR
            "TABLE_IDX_VER", "VARBASE_LANES", "VARBASE_PREP_SUM", "VARBASE_MX_LANES", "VARBASE_MX_PREP_SUM", "varbase_points",
            "SELECT_MAX_BIDS", "RoundSelection", "select_floor", "ROW_SKIPPED", "BEST_TRANCHE_DEFAULT", "RoundBest", "ROW_DUPLICATE",
            "RoundBestDistinct", "BEST_MAX_ROUNDS", "RoundsBest", "RoundsBestDistinct", "rounds_floors",
-           "STANDING_MAX_K", "STANDING_MAX_OPEN", "StandingOffer", "StandingEntries"]
+           "STANDING_MAX_K", "STANDING_MAX_OPEN", "StandingOffer", "StandingEntries", "StandingsOffer"]

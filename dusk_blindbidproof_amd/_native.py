@@ -97,6 +97,8 @@ SIGNATURES = {
     "bbp_standing_close": (_i32, [_vp, _u32]),
     "bbp_debug_standing_offer": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_standing_trip": (_i32, [_vp, _u32, _u32]),
+    "bbp_standings_offer": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "bbp_debug_standings_offer": (_i32, [_vp, _u32, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_rounds_best": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_verify_rounds_best_dev": (_i32, [_vp, _u32, _vp, _vp, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "bbp_debug_rounds_best": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp]),
@@ -264,6 +266,9 @@ STANDING_MAX_OPEN = 64      # BBP_STANDING_MAX_OPEN
 StandingOffer = collections.namedtuple("StandingOffer", "entered n_entered n_candidates n_examined n_duplicates status raw")
 # a standing's entries in rank order (the first min(n_entries, cap)): serials, 32-byte scores, 32-byte z_imgs; the true count; rows offered
 StandingEntries = collections.namedtuple("StandingEntries", "serials scores z_imgs n_entries n_offered")
+# one offer to S standings: per-standing lists entered (CALL indices in rank order), n_entered, n_candidates, n_examined, n_duplicates; the
+# largest number of tranches any standing ran; the B statuses; raw (S x cap entries as the call left them)
+StandingsOffer = collections.namedtuple("StandingsOffer", "entered n_entered n_candidates n_examined n_duplicates n_steps status raw")
 BEST_MAX_ROUNDS = 1 << 16   # BBP_BEST_MAX_ROUNDS
 # per round: best (a list of row indices in rank order, at most cap), n_best, n_candidates, n_examined, raw (the round's cap entries as
 # the call left them); n_steps and the B statuses for the call
@@ -714,6 +719,33 @@ class Context:
                                                  ctypes.byref(counts[1]), ctypes.byref(counts[2]), ctypes.byref(dups), status))
         return StandingOffer(*self._best_distinct_result(B, cap, ent, status, counts, dups))
 
+    def standings_offer(self, standings, Ns, standing_of, rows, tranche=0, cap=None, fill=0):
+        """bbp_standings_offer: one offer to the open standings `standings` at once.  Ns: the N of every standing; standing_of: per row
+        the index into `standings` (None with one standing only); rows: round_row_size(Ns[standing_of[i]]) bytes each, back to back.
+        cap: room in entered per standing (None: one per row).  Returns a StandingsOffer."""
+        S = len(standings)
+        B = len(standing_of) if standing_of is not None else len(rows) // round_row_size(Ns[0])
+        if len(Ns) != S or len(rows) != sum(round_row_size(Ns[s]) for s in (standing_of if standing_of is not None else [0] * B)):
+            raise ValueError("one N per standing; rows are round_row_size(N of the row's standing) bytes each")
+        cap, ent, status, counts = self._bests_buffers(S, B, 0, cap, fill)
+        dups = (_u32 * max(1, S))()
+        self._check(lib.bbp_standings_offer(self._h, S, _u32s(standings), B, _u32s(standing_of), _buf(rows) if B else ent, tranche, cap, ent, counts[0],
+                                            counts[1], counts[2], dups, ctypes.byref(counts[3]), status))
+        return StandingsOffer(*self._bests_distinct_result(S, B, cap, ent, status, counts, dups))
+
+    def debug_standings_offer(self, standings, standing_of, keys, ids, verdicts, tranche=0, cap=None, fill=0):
+        """bbp_debug_standings_offer (test hook): one offer of made-up keys and ids (B x 32 bytes each) and verdicts to the open standings
+        `standings` through the shipped kernels; nothing is verified.  Returns a StandingsOffer."""
+        S, B = len(standings), len(verdicts)
+        if len(keys) != 32 * B or len(ids) != 32 * B or (standing_of is not None and len(standing_of) != B):
+            raise ValueError("keys and ids are 32 bytes and standing_of one entry per verdict")
+        cap, ent, status, counts = self._bests_buffers(S, B, 0, cap, fill)
+        dups = (_u32 * max(1, S))()
+        self._check(lib.bbp_debug_standings_offer(self._h, S, _u32s(standings), B, _u32s(standing_of), _buf(keys) if B else ent, _buf(ids) if B else ent,
+                                                  (ctypes.c_int32 * max(1, B))(*verdicts), tranche, cap, ent, counts[0], counts[1], counts[2], dups,
+                                                  ctypes.byref(counts[3]), status))
+        return StandingsOffer(*self._bests_distinct_result(S, B, cap, ent, status, counts, dups))
+
     def debug_standing_trip(self, standing, after=1):
         """bbp_debug_standing_trip (test hook): the next offer to the standing fails with ERR_INTERNAL behind its after-th merge."""
         self._check(lib.bbp_debug_standing_trip(self._h, standing, after))
@@ -1119,6 +1151,11 @@ class Pool(Context):
         """bbp_standing_offer on the pool: member 0 screens, selects, merges and commits; every tranche is verified as
         verify_rounds_aggregated verifies it (block-split over the members)."""
         return super().standing_offer(standing, N, rows, tranche, cap, fill)
+
+    def standings_offer(self, standings, Ns, standing_of, rows, tranche=0, cap=None, fill=0):
+        """bbp_standings_offer on the pool: member 0 screens, selects, merges and commits; every step is verified as
+        verify_rounds_aggregated verifies it (block-split over the members)."""
+        return super().standings_offer(standings, Ns, standing_of, rows, tranche, cap, fill)
 
     def standing_read(self, standing, cap=STANDING_MAX_K):
         """bbp_standing_read on the pool: from member 0."""

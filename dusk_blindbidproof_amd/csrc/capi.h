@@ -1,13 +1,13 @@
 // What the five C-API units share (DESIGN.md "C API units"); included by them and by nothing else:
 //   capi_prove.hip   everything that proves: witness, entropy, checked proving, the host and device prove calls, rounds, selection
 //   capi_best.hip    best proofs of one round, plain and one per bidder; standings
-//   capi_bests.hip   best proofs of many rounds
+//   capi_bests.hip   best proofs of many rounds; one offer to many standings
 //   capi_verify.hip  every verify entry point and the host verify path
 //   capi_ctx.hip     error slots, sizes, bbp_reserve, settings, debug hooks, profiling
 // Declarations only -- each function is defined once, in the unit named above it -- except the two exception barriers, SlotLease and
 // one-line accessors.  A helper that one unit alone uses is a `static` of that unit and does not appear here.
 // Kernels: every kernel is compiled by exactly one unit.  round_bids.h, round_select.h and round_best.h are also read by other units
-// for their host-side rules, so their kernels sit behind BBP_ROUND_BIDS_KERNELS / BBP_ROUND_SELECT_KERNELS / BBP_ROUND_BEST_KERNELS,
+// for their host-side rules (round_standing.h: with round_best.h's), so their kernels sit behind BBP_ROUND_BIDS_KERNELS / BBP_ROUND_SELECT_KERNELS / BBP_ROUND_BEST_KERNELS,
 // which the owning unit defines before it includes anything.  A unit that needs another unit's launch calls a host function below.
 #pragma once
 #include <mutex>
@@ -119,5 +119,16 @@ int32_t best_public_dev(bbp_ctx* ctx, u32 N, const void* round_dev, u32 B, const
                         u32 tranche, bool distinct, const BestOut& out, void* status_dev, void* stream);
 // the k_best_pairs launch: the winners' pairs of the n rows in sel (counts: the device-side count) out of the winner records
 int32_t best_pairs_enqueue(bbp_ctx* ctx, u32 n, const u32* sel, const u32* counts, const u32* win, u32* pairs, hipStream_t s);
+// standings, as the many-standings call (capi_bests.hip) needs them: the context that holds a handle's standings (a pool: member 0); a
+// refusal; the open standing behind a handle, or null (caller holds dev->best_mu); what the host keeps of a committed working header
+// (STAND_H_* words) after an offer of `rows` rows; the two single-standing offers behind their screening, as the entry points of one
+// standing and the many-standings calls with S == 1 run them (out.n_tranches: the tranches that ran)
+bbp_ctx* stand_dev(bbp_ctx* ctx);
+int32_t stand_refuse(bbp_ctx* ctx, const std::string& why);
+bbp_ctx::Standing* stand_find(bbp_ctx* dev, u32 handle);
+void stand_record_commit(bbp_ctx::Standing& m, const u32* whdr, u32 rows);
+int32_t stand_public_host(bbp_ctx* ctx, const char* what, u32 standing, u32 B, const uint8_t* rows, u32 tranche, const BestOut& out, int32_t* status);
+int32_t stand_hook_host(bbp_ctx* ctx, const char* what, u32 standing, u32 B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts, u32 tranche,
+                        const BestOut& out, int32_t* status);
 
 }  // namespace bbp

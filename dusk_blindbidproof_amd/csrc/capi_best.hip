@@ -304,14 +304,15 @@ static int32_t stand_deliver(const BestCall& c, BestTally& t, const BestOut& o, 
     return BBP_OK;
 }
 // ... and after its commit has run: what the host keeps of the header
-static void stand_committed(const BestCall& c) {
-    const StandCall& S = *c.stand;
-    const u32* whdr = (const u32*)(c.h + S.W.h_whdr);
-    bbp_ctx::Standing& m = *S.meta;
+void bbp::stand_record_commit(bbp_ctx::Standing& m, const u32* whdr, u32 rows) {
     m.count = whdr[STAND_H_COUNT];
     memcpy(m.bar, whdr + STAND_H_BAR, 32);
-    m.offered += S.rows;
+    m.offered += rows;
     m.trip = 0;
+}
+static void stand_committed(const BestCall& c) {
+    const StandCall& S = *c.stand;
+    stand_record_commit(*S.meta, (const u32*)(c.h + S.W.h_whdr), S.rows);
 }
 
 // The host forms on ONE device's context (c.ctx).  fill(dst): the B x c.staged_row() bytes into the pinned staging area; verdicts(n, sel,
@@ -654,12 +655,12 @@ extern "C" int32_t bbp_verify_round_best_distinct_dev(bbp_ctx* ctx, uint32_t N, 
 // ---- standing of a round (include/bbp.h; rules and kernels: round_standing.h) ---------------------------------------------------------
 // An offer is a one-per-bidder host call over K + B working rows with a StandCall: the same driver.  The standings of a handle live on
 // ONE device's context (a pool: member 0), found and changed under its best_mu.
-static bbp_ctx* stand_dev(bbp_ctx* ctx) { return is_pool(ctx) ? ctx->members[0] : ctx; }
-static int32_t stand_refuse(bbp_ctx* ctx, const std::string& why) {
+bbp_ctx* bbp::stand_dev(bbp_ctx* ctx) { return is_pool(ctx) ? ctx->members[0] : ctx; }
+int32_t bbp::stand_refuse(bbp_ctx* ctx, const std::string& why) {
     return api_guard(ctx, [&]() -> int32_t { return ctx->err = why, BBP_ERR_BAD_ARG; });
 }
 // the open standing behind a handle, or null (caller holds dev->best_mu)
-static bbp_ctx::Standing* stand_find(bbp_ctx* dev, u32 handle) {
+bbp_ctx::Standing* bbp::stand_find(bbp_ctx* dev, u32 handle) {
     return dev->stand_handles.is_open(handle) ? &dev->stand_meta[handle] : nullptr;
 }
 
@@ -789,24 +790,28 @@ extern "C" int32_t bbp_standing_offer(bbp_ctx* ctx, uint32_t standing, uint32_t 
         *n_entered = *n_candidates = *n_examined = *n_duplicates = 0;
         if (B > BBP_SELECT_MAX_BIDS) return stand_refuse(ctx, "bbp_standing_offer: more than BBP_SELECT_MAX_BIDS rows");
         if (B == 0) return BBP_OK;
-        return stand_offer(ctx, "bbp_standing_offer", standing, B,
-                           [&](BestCall& c, const bbp_ctx::Standing& m) -> int32_t {
-                               const u32 N = m.N, K = m.K;
-                               const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
-                               std::vector<uint8_t> picked;
-                               auto fill = [&](u8* dst) {
-                                   for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, rows + rb * i + key_off, 64);
-                               };
-                               auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // (sel: working rows; row sel[j] - K of the offer)
-                                   picked.resize(rb * n);
-                                   for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * (sel[j] - K), rb);
-                                   return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, m.round.data(), nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT,
-                                                      nullptr);
-                               };
-                               return best_run_host(c, fill, verdicts, nullptr, tranche,
-                                                    BestOut{cap, entered_out, n_entered, n_candidates, n_examined, n_duplicates}, status);
-                           });
+        return stand_public_host(ctx, "bbp_standing_offer", standing, B, rows, tranche,
+                                 BestOut{cap, entered_out, n_entered, n_candidates, n_examined, n_duplicates}, status);
     });
+}
+// ... and behind that screening (the many-standings call with one standing runs it too; out.n_tranches: the tranches that ran)
+int32_t bbp::stand_public_host(bbp_ctx* ctx, const char* what, u32 standing, u32 B, const uint8_t* rows, u32 tranche, const BestOut& out, int32_t* status) {
+    return stand_offer(ctx, what, standing, B,
+                       [&](BestCall& c, const bbp_ctx::Standing& m) -> int32_t {
+                           const u32 N = m.N, K = m.K;
+                           const size_t rb = round_row_bytes(N), key_off = proof_record_bytes(N);
+                           std::vector<uint8_t> picked;
+                           auto fill = [&](u8* dst) {
+                               for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, rows + rb * i + key_off, 64);
+                           };
+                           auto verdicts = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {  // (sel: working rows; row sel[j] - K of the offer)
+                               picked.resize(rb * n);
+                               for (u32 j = 0; j < n; j++) memcpy(&picked[rb * j], rows + rb * (sel[j] - K), rb);
+                               return verify_host(ctx, VerifyRows::of_rounds(n, 1, &N, m.round.data(), nullptr), picked.data(), st, BBP_AGG_GROUP_DEFAULT,
+                                                  nullptr);
+                           };
+                           return best_run_host(c, fill, verdicts, nullptr, tranche, out, status);
+                       });
 }
 
 // Test hook: an offer of caller-made keys, ids and verdicts through the shipped kernels against the standing's state.
@@ -826,21 +831,25 @@ extern "C" int32_t bbp_debug_standing_offer(bbp_ctx* ctx, uint32_t standing, uin
         if (B == 0) return BBP_OK;  // (as the offer itself: zero counts, the standing unchanged)
         u32 n_ok;
         if (int32_t rc = best_hook_screen(ctx, "bbp_debug_standing_offer", B, verdicts, &n_ok)) return rc;
-        return stand_offer(ctx, "bbp_debug_standing_offer", standing, B,
-                           [&](BestCall& c, const bbp_ctx::Standing& m) -> int32_t {
-                               const u32 K = m.K;
-                               auto fill = [&](u8* dst) {
-                                   for (u32 i = 0; i < B; i++)
-                                       memcpy(dst + 64 * (size_t)i, keys + 32 * (size_t)i, 32), memcpy(dst + 64 * (size_t)i + 32, ids + 32 * (size_t)i, 32);
-                               };
-                               auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
-                                   for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j] - K];
-                                   return BBP_OK;
-                               };
-                               return best_run_host(c, fill, read, nullptr, tranche, BestOut{cap, entered_out, n_entered, n_candidates, n_examined, n_duplicates},
-                                                    status);
-                           });
+        return stand_hook_host(ctx, "bbp_debug_standing_offer", standing, B, keys, ids, verdicts, tranche,
+                               BestOut{cap, entered_out, n_entered, n_candidates, n_examined, n_duplicates}, status);
     });
+}
+int32_t bbp::stand_hook_host(bbp_ctx* ctx, const char* what, u32 standing, u32 B, const uint8_t* keys, const uint8_t* ids, const int32_t* verdicts, u32 tranche,
+                             const BestOut& out, int32_t* status) {
+    return stand_offer(ctx, what, standing, B,
+                       [&](BestCall& c, const bbp_ctx::Standing& m) -> int32_t {
+                           const u32 K = m.K;
+                           auto fill = [&](u8* dst) {
+                               for (u32 i = 0; i < B; i++)
+                                   memcpy(dst + 64 * (size_t)i, keys + 32 * (size_t)i, 32), memcpy(dst + 64 * (size_t)i + 32, ids + 32 * (size_t)i, 32);
+                           };
+                           auto read = [&](u32 n, const u32* sel, int32_t* st) -> int32_t {
+                               for (u32 j = 0; j < n; j++) st[j] = verdicts[sel[j] - K];
+                               return BBP_OK;
+                           };
+                           return best_run_host(c, fill, read, nullptr, tranche, out, status);
+                       });
 }
 
 extern "C" int32_t bbp_debug_standing_trip(bbp_ctx* ctx, uint32_t standing, uint32_t after) {

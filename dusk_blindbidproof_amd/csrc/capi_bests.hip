@@ -1,5 +1,5 @@
-// C-ABI, best proofs of MANY rounds, plain and one per bidder, with their hooks and _dev forms -- see include/bbp.h.  A call with one
-// round runs the single-round calls of capi_best.hip (capi.h).
+// C-ABI, best proofs of MANY rounds, plain and one per bidder, with their hooks and _dev forms, and an offer to MANY standings -- see
+// include/bbp.h.  A call with one round, or one standing, runs the single-round calls of capi_best.hip (capi.h).
 #include <string.h>
 
 #include <algorithm>
@@ -8,6 +8,7 @@
 #include "capi.h"
 #include "rounds_best.h"
 #include "rounds_best_distinct.h"
+#include "standings.h"
 
 using namespace bbp;
 
@@ -22,12 +23,19 @@ using namespace bbp;
 //             stopped)}
 //   finish    k_bests_plan {k_bests_plan_distinct} (winners {the settled identities}), k_bests_scan, k_bests_select over the winner
 //             records, k_best_pairs; ctr, pairs [statuses] down
+// <..>: an offer to many standings (standings.h), a one-per-bidder host call over the working rows with the standings as its rounds:
+//   open      <sctr zeroed, the parameter table and the local indices up, k_stands_seed>
+//   segment   the ids and keys of the OFFER rows; <k_stands_plan: the segment sizes;> scan, place <k_stands_enter, k_stands_leave>
+//   per step  <k_stands_plan in k_bests_plan_distinct's place>; behind settle and holders, in k_bests_drop's place: <k_stands_displace,
+//             k_stands_plan (the winners to keep), scan, k_bests_select over the winner records, k_stands_merge, k_stands_leave>
+//   finish    <no selection: the working headers, order and statuses down; after the host's checks k_stands_commit, a submission of its own>
 struct BestsCall {
     bbp_ctx* ctx;
     u32 R, B, K, tranche;
     hipStream_t s;
     BestsLayout L;
     std::optional<BestsDistinctLayout> D;  // one per bidder only (rounds_best_distinct.h)
+    struct StandsCall* stands = nullptr;   // an offer to many standings only (below): B is the working rows, R the standings
     u8 *d = nullptr, *h = nullptr;
     // host_rows: a host form, which stages bytes of every row -- the 32 key bytes (in L), one per bidder score || z_img (in D)
     BestsCall(bbp_ctx* c, u32 R_, u32 B_, u32 K_, u32 tranche_, hipStream_t s_, bool host_rows, bool distinct = false, u32 table_log2 = 0)
@@ -39,14 +47,43 @@ struct BestsCall {
     const u32* mirror(u32 word) const { return (const u32*)(h + L.h_ctr) + word; }
     u32* dctr(u32 word) const { return (u32*)(d + D->dctr) + word; }
     const u32* dmirror(u32 word) const { return (const u32*)(h + D->h_dctr) + word; }
-    size_t bytes() const { return D ? D->bytes : L.bytes; }
-    size_t h_bytes() const { return D ? D->h_bytes : L.h_bytes; }
+    size_t bytes() const;
+    size_t h_bytes() const;
+    u32 first() const;  // the working rows in front of the call's own: the standings' entry slots, otherwise none
     size_t staged_row() const { return D ? 64 : 32; }
     size_t staged() const { return D ? D->kid : L.keys; }
     size_t h_staged() const { return D ? D->h_kid : L.h_keys; }
-    const char* family() const { return D ? "best proofs of many rounds, one per bidder: " : "best valid proofs of many rounds: "; }
+    const char* family() const {
+        return stands ? "standings of many rounds: " : D ? "best proofs of many rounds, one per bidder: " : "best valid proofs of many rounds: ";
+    }
     unsigned long long* offb() const { return (unsigned long long*)(d + L.offb); }
 };
+// What an offer to many standings adds (standings.h): the standings' own allocations and the host's records of them, the scratch behind
+// the call's, and what the host counts between the steps.
+struct StandsCall {
+    u32 S, sumK = 0, rows;  // rows: the call's
+    std::vector<bbp_ctx::Standing*> meta;
+    std::vector<u8*> st;
+    std::vector<u32> K, E, n_rows, merges, local;
+    std::optional<StandingsLayout> W;
+    StandsCall(bbp_ctx* dev, u32 S_, const u32* handles, u32 B, const u32* standing_of) : S(S_), rows(B), meta(S_), st(S_), K(S_), E(S_), n_rows(S_, 0), merges(S_, 0), local(B) {
+        for (u32 s = 0; s < S; s++) {
+            meta[s] = &dev->stand_meta[handles[s]], st[s] = (u8*)dev->stand[handles[s]].p;
+            K[s] = meta[s]->K, E[s] = sumK, sumK += K[s];
+        }
+        for (u32 i = 0; i < B; i++) local[i] = n_rows[standing_of[i]]++;
+    }
+    // the standings whose merge behind a step with these rows is the one bbp_debug_standing_trip asked for (once)
+    unsigned long long trips(const u32* take) {
+        unsigned long long mask = 0;
+        for (u32 s = 0; s < S; s++)
+            if (take[s] && meta[s]->trip && meta[s]->trip == ++merges[s]) mask |= 1ull << s, meta[s]->trip = 0;
+        return mask;
+    }
+};
+size_t BestsCall::bytes() const { return stands ? stands->W->bytes : D ? D->bytes : L.bytes; }
+size_t BestsCall::h_bytes() const { return stands ? stands->W->h_bytes : D ? D->h_bytes : L.h_bytes; }
+u32 BestsCall::first() const { return stands ? stands->sumK : 0; }
 // where a call's results go: R x cap, R, R, R entries; n_steps may be null
 struct BestsOut {
     u32 cap;
@@ -101,8 +138,112 @@ static int32_t bests_ids_enqueue(const BestsCall& c, const u8* base, bool dev_ro
     ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
     if (!dev_rows) BBP_HIP_TRY(c.ctx, hipMemsetD32Async((hipDeviceptr_t)c.at(L.rb), 64, c.R, c.s));  // a staged row: 64 bytes in every round
     auto* rowoff = (unsigned long long*)(c.d + L.rowoff);
-    hipLaunchKernelGGL(k_bests_ids, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, base, dev_rows ? (const unsigned long long*)rowoff : nullptr,
-                       (const u32*)c.at(L.rb), (const u32*)c.at(L.round_of), c.at(c.D->ids), dev_rows ? nullptr : rowoff);
+    const u32 f = c.first(), n = c.B - f;  // <base is the staged row of the offer's row 0, which is working row f>
+    hipLaunchKernelGGL(k_bests_ids, dim3((n + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, n, base, dev_rows ? (const unsigned long long*)rowoff : nullptr,
+                       (const u32*)c.at(L.rb), (const u32*)c.at(L.round_of) + f, c.at(c.D->ids) + 8 * (size_t)f, dev_rows ? nullptr : rowoff);
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+
+// <an offer to many standings, on c.s>  Seed: behind bests_open, before the keys.  Plan: k_stands_plan in one of its modes, into take.
+// Enter: behind the segment starts -- the entry slots into their segments and the identity table -- then the leave pass in front of
+// step 0.  Merge: behind a step's holders.  Finish: everything the host reads.  Commit: a submission of its own, after the host's checks.
+static int32_t stands_seed_enqueue(const BestsCall& c, int32_t* status) {
+    bbp_ctx* ctx = c.ctx;
+    const StandsCall& S = *c.stands;
+    const StandingsLayout& W = *S.W;
+    u32* par = (u32*)(c.h + W.h_par);
+    for (u32 s = 0; s < S.S; s++) {
+        const StandingLayout SL(S.K[s]);
+        u32* p = par + (size_t)STANDS_P_WORDS * s;
+        const unsigned long long ptr = (unsigned long long)(uintptr_t)S.st[s];
+        p[STANDS_P_PTR] = (u32)ptr, p[STANDS_P_PTR + 1] = (u32)(ptr >> 32), p[STANDS_P_K] = S.K[s], p[STANDS_P_E] = S.E[s], p[STANDS_P_ROWS] = S.n_rows[s];
+        p[STANDS_P_KEYS] = (u32)SL.keys, p[STANDS_P_IDS] = (u32)SL.ids, p[STANDS_P_SERIALS] = (u32)SL.serials;
+    }
+    memcpy(c.h + W.h_local, S.local.data(), 4 * (size_t)S.rows);
+    BBP_HIP_TRY(ctx, hipMemsetAsync(c.d + W.sctr, 0, 4 * (size_t)S.S, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.d + W.par, c.h + W.h_par, 4 * (size_t)STANDS_P_WORDS * S.S, hipMemcpyHostToDevice, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.d + W.local, c.h + W.h_local, 4 * (size_t)S.rows, hipMemcpyHostToDevice, c.s));
+    ScopedEvent ev(ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stands_seed, dim3((S.sumK + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.S, S.sumK, (const u32*)c.at(W.par), c.at(c.L.recs), c.at(c.L.win),
+                       c.at(c.D->ids), status, c.at(W.whdr), c.at(W.wserial), c.at(W.order));
+    BBP_HIP_TRY(ctx, hipGetLastError());
+    return BBP_OK;
+}
+static int32_t stands_plan_enqueue(const BestsCall& c, u32 mode, u32 t) {
+    const BestsLayout& L = c.L;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stands_plan, dim3((c.R + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.R, mode, t, c.tranche, (const u32*)c.at(c.stands->W->par),
+                       (const u32*)c.ctr(L.c_ncand), (const u32*)c.ctr(L.c_examined), (const u32*)c.dctr(c.D->d_dups), (const u32*)c.at(c.stands->W->sctr),
+                       c.ctr(L.c_take), c.ctr(L.c_tranches));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+static int32_t stands_leave_enqueue(const BestsCall& c, int32_t* status) {
+    const StandingsLayout& W = *c.stands->W;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stands_leave, dim3((c.B + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.B, (const u32*)c.at(W.par), c.at(c.L.recs),
+                       (const u32*)c.at(c.D->ids), (const u32*)c.at(c.L.round_of), (const u32*)c.at(c.D->table), c.D->slots - 1, (const u32*)c.at(W.whdr), status,
+                       c.at(W.sctr), c.dctr(c.D->d_dups), c.dctr(c.D->d_flag));
+    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    return BBP_OK;
+}
+static int32_t stands_enter_enqueue(const BestsCall& c, int32_t* status) {
+    const StandsCall& S = *c.stands;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_stands_enter, dim3((S.sumK + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.S, S.sumK, (const u32*)c.at(S.W->par), (const u32*)c.at(c.L.win),
+                           (const u32*)c.at(c.D->ids), (const u32*)c.at(c.L.round_of), (const u32*)c.ctr(c.L.c_ncand), (const u32*)c.ctr(c.L.c_seg), c.at(c.L.cand),
+                           c.at(c.D->table), c.D->slots - 1, c.dctr(c.D->d_flag));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    return stands_leave_enqueue(c, status);
+}
+static int32_t bests_select_enqueue(const BestsCall& c, bool finish);
+static int32_t bests_scan_enqueue(const BestsCall& c, u32 in_word, u32 out_word, bool bytes);
+// behind the holders of step t, whose rows were take[s] of standing s
+static int32_t stands_merge_enqueue(const BestsCall& c, u32 t, const u32* take, int32_t* status) {
+    StandsCall& S = *c.stands;
+    const BestsLayout& L = c.L;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_stands_displace, dim3((S.sumK + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.sumK, (const u32*)c.at(c.D->ids), (const u32*)c.at(L.round_of),
+                           (const u32*)c.at(c.D->table), c.D->slots - 1, c.at(L.win), c.at(L.sel), c.dctr(c.D->d_flag));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    int32_t rc;
+    if ((rc = stands_plan_enqueue(c, STANDS_PLAN_WINNERS, t)) || (rc = bests_scan_enqueue(c, L.c_take, L.c_off, false)) || (rc = bests_select_enqueue(c, true))) return rc;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_stands_merge, dim3(S.S), dim3(STAND_MERGE_T), 0, c.s, c.B, (const u32*)c.at(S.W->par), (const u32*)c.ctr(L.c_take), (const u32*)c.ctr(L.c_off),
+                           (const u32*)c.at(L.sel), (const u32*)c.at(L.win), c.at(S.W->whdr), c.at(S.W->order), S.trips(take), c.dctr(c.D->d_flag));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    return stands_leave_enqueue(c, status);
+}
+static int32_t stands_counters_fetch(const BestsCall& c) {
+    const StandingsLayout& W = *c.stands->W;
+    BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + W.h_sctr, c.d + W.sctr, 4 * (size_t)c.R, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+static int32_t stands_finish_enqueue(const BestsCall& c, const int32_t* status) {
+    bbp_ctx* ctx = c.ctx;
+    const StandsCall& S = *c.stands;
+    const StandingsLayout& W = *S.W;
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_ctr, c.d + c.L.ctr, 4 * (size_t)c.L.c_words, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.D->h_dctr, c.d + c.D->dctr, 4 * (size_t)c.D->d_words, hipMemcpyDeviceToHost, c.s));
+    if (int32_t rc = stands_counters_fetch(c)) return rc;
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + W.h_whdr, c.d + W.whdr, 4 * (size_t)STANDS_H_STRIDE * S.S, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + W.h_order, c.d + W.order, 4 * (size_t)S.sumK, hipMemcpyDeviceToHost, c.s));
+    BBP_HIP_TRY(ctx, hipMemcpyAsync(c.h + c.L.h_status, status + S.sumK, 4 * (size_t)S.rows, hipMemcpyDeviceToHost, c.s));
+    return BBP_OK;
+}
+static int32_t stands_commit_enqueue(const BestsCall& c) {
+    const StandsCall& S = *c.stands;
+    const StandingsLayout& W = *S.W;
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+    hipLaunchKernelGGL(k_stands_commit, dim3((S.sumK + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, S.S, S.sumK, c.B, (const u32*)c.at(W.par), (const u32*)c.at(W.whdr),
+                       (const u32*)c.at(W.order), (const u32*)c.at(c.L.win), (const u32*)c.at(c.D->ids), (const u32*)c.at(W.wserial), (const u32*)c.at(W.local));
     BBP_HIP_TRY(c.ctx, hipGetLastError());
     return BBP_OK;
 }
@@ -110,18 +251,25 @@ static int32_t bests_ids_enqueue(const BestsCall& c, const u8* base, bool dev_ro
 // keys at base (the _dev form: the rows; else the staged keys {rows}) -> records, statuses, candidate counts, segments
 static int32_t bests_segment_enqueue(const BestsCall& c, const u8* base, bool dev_rows, int32_t* status) {
     const BestsLayout& L = c.L;
+    const u32 f = c.first(), n = c.B - f;  // <the keys of the offer's rows: the seed wrote the entry slots>
     const dim3 grid((c.B + BEST_T - 1) / BEST_T), block(BEST_T);
     {
         ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
-        hipLaunchKernelGGL(k_bests_keys, grid, block, 0, c.s, c.B, base, dev_rows ? (const unsigned long long*)(c.d + L.rowoff) : nullptr,
-                           (const u32*)c.at(L.rb), (const u32*)c.at(L.round_of), (const u32*)c.at(L.floors), c.at(L.recs), c.at(L.win), status, c.ctr(L.c_ncand));
+        hipLaunchKernelGGL(k_bests_keys, dim3((n + BEST_T - 1) / BEST_T), block, 0, c.s, n, base, dev_rows ? (const unsigned long long*)(c.d + L.rowoff) : nullptr,
+                           (const u32*)c.at(L.rb), (const u32*)c.at(L.round_of) + f, (const u32*)c.at(L.floors), c.at(L.recs) + (size_t)RS_WORDS * f,
+                           c.at(L.win) + (size_t)RS_WORDS * f, status + f, c.ctr(L.c_ncand));
         BBP_HIP_TRY(c.ctx, hipGetLastError());
     }
-    if (int32_t rc = bests_scan_enqueue(c, L.c_ncand, L.c_seg, false)) return rc;
-    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
-    hipLaunchKernelGGL(k_bests_place, grid, block, 0, c.s, c.B, (const u32*)c.at(L.recs), (const u32*)c.ctr(L.c_seg), c.ctr(L.c_fill), c.at(L.cand));
-    BBP_HIP_TRY(c.ctx, hipGetLastError());
-    return BBP_OK;
+    if (c.stands) {  // <a segment holds the candidates and the entry slots: its size into take, which the first plan overwrites>
+        if (int32_t rc = stands_plan_enqueue(c, STANDS_PLAN_SEGMENTS, 0)) return rc;
+    }
+    if (int32_t rc = bests_scan_enqueue(c, c.stands ? L.c_take : L.c_ncand, L.c_seg, false)) return rc;
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+        hipLaunchKernelGGL(k_bests_place, grid, block, 0, c.s, c.B, (const u32*)c.at(L.recs), (const u32*)c.ctr(L.c_seg), c.ctr(L.c_fill), c.at(L.cand));
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    return c.stands ? stands_enter_enqueue(c, status) : (int32_t)BBP_OK;
 }
 
 // the rows that take and off plan, out of the candidate records (finish: the winner records) -> sel
@@ -137,7 +285,9 @@ static int32_t bests_select_enqueue(const BestsCall& c, bool finish) {
 // take and off of step t (finish: of the winners), [the selection -> sel], the counters into the mirror
 static int32_t bests_plan_enqueue(const BestsCall& c, u32 t, bool finish, bool bytes, bool select) {
     const BestsLayout& L = c.L;
-    {
+    if (c.stands) {
+        if (int32_t rc = stands_plan_enqueue(c, STANDS_PLAN_STEP, t)) return rc;
+    } else {
         ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
         if (c.D)
             hipLaunchKernelGGL(k_bests_plan_distinct, dim3((c.R + BEST_T - 1) / BEST_T), dim3(BEST_T), 0, c.s, c.R, t, c.K, c.tranche, finish ? 1u : 0u,
@@ -153,7 +303,7 @@ static int32_t bests_plan_enqueue(const BestsCall& c, u32 t, bool finish, bool b
         if (int32_t rc = bests_select_enqueue(c, finish)) return rc;
     BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + L.h_ctr, c.d + L.ctr, 4 * (size_t)L.c_words, hipMemcpyDeviceToHost, c.s));
     if (c.D) BBP_HIP_TRY(c.ctx, hipMemcpyAsync(c.h + c.D->h_dctr, c.d + c.D->dctr, 4 * (size_t)c.D->d_words, hipMemcpyDeviceToHost, c.s));
-    return BBP_OK;
+    return c.stands ? stands_counters_fetch(c) : (int32_t)BBP_OK;
 }
 
 static int32_t bests_mark_enqueue(const BestsCall& c, u32 n, const int32_t* tstat, int32_t* status) {
@@ -165,18 +315,22 @@ static int32_t bests_mark_enqueue(const BestsCall& c, u32 n, const int32_t* tsta
 }
 
 // {one per bidder} behind the mark of a step of n rows: identities settled, holders' winner records opened, duplicates of running
-// rounds dropped
-static int32_t bests_settle_enqueue(const BestsCall& c, u32 n, const int32_t* tstat, int32_t* status) {
+// rounds dropped <the merge and the leave pass in the drop pass's place; t: the step, take: its rows per standing>
+static int32_t bests_settle_enqueue(const BestsCall& c, u32 n, const int32_t* tstat, int32_t* status, u32 t = 0, const u32* take = nullptr) {
     const BestsLayout& L = c.L;
     const BestsDistinctLayout& D = *c.D;
     const u32 *sel = c.at(L.sel), *ids = c.at(D.ids), *round_of = c.at(L.round_of), mask = D.slots - 1;
     u32 *table = c.at(D.table), *flag = c.dctr(D.d_flag);
-    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
     const dim3 grid((n + BEST_T - 1) / BEST_T), block(BEST_T);
-    hipLaunchKernelGGL(k_bests_settle, grid, block, 0, c.s, n, c.B, sel, tstat, (const u32*)c.at(L.recs), ids, round_of, table, mask, c.dctr(D.d_settled), flag);
-    BBP_HIP_TRY(c.ctx, hipGetLastError());
-    hipLaunchKernelGGL(k_bests_holders, grid, block, 0, c.s, n, c.B, sel, tstat, ids, round_of, (const u32*)table, mask, c.at(L.win), flag);
-    BBP_HIP_TRY(c.ctx, hipGetLastError());
+    {
+        ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
+            hipLaunchKernelGGL(k_bests_settle, grid, block, 0, c.s, n, c.B, sel, tstat, (const u32*)c.at(L.recs), ids, round_of, table, mask, c.dctr(D.d_settled), flag);
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+        hipLaunchKernelGGL(k_bests_holders, grid, block, 0, c.s, n, c.B, sel, tstat, ids, round_of, (const u32*)table, mask, c.at(L.win), flag);
+        BBP_HIP_TRY(c.ctx, hipGetLastError());
+    }
+    if (c.stands) return stands_merge_enqueue(c, t, take, status);
+    ScopedEvent ev(c.ctx, TAG_SELECT, c.s);
     hipLaunchKernelGGL(k_bests_drop, dim3((c.B + BEST_T - 1) / BEST_T), block, 0, c.s, c.B, c.K, c.at(L.recs), ids, round_of, (const u32*)table, mask, status,
                        (const u32*)c.dctr(D.d_settled), c.dctr(D.d_dups), flag);
     BBP_HIP_TRY(c.ctx, hipGetLastError());
@@ -201,13 +355,18 @@ struct BestsTally {
     u32 R, K, tranche;
     bool distinct;
     std::vector<u32> nc, examined, ok, take, settled, dups;  // (settled, dups, running: the one-per-bidder calls only, otherwise empty)
+    std::vector<u32> Ks, left;  // <an offer to many standings only: every standing's K, and the candidates that left by the bar>
     std::vector<char> running;  // round r contributed to the step planned last (all of them before step 0); a round that stopped stays stopped
     u32 n = 0;                  // the rows of the step planned last
     explicit BestsTally(const BestsCall& c)
         : R(c.R), K(c.K), tranche(c.tranche), distinct(c.D.has_value()), nc(R), examined(R), ok(R), take(R), settled(distinct ? R : 0),
-          dups(settled.size()), running(settled.size(), 1) {}
+          dups(settled.size()), running(settled.size(), 1) {
+        if (c.stands) Ks = c.stands->K, left.assign(R, 0);
+    }
+    bool stands() const { return !Ks.empty(); }
     // the rows round r contributes to step t (finish: the winners it reports), from what the call holds of the device's counters
     u32 rows_of(u32 r, u32 t, bool finish) const {
+        if (stands()) return finish ? 0 : stands_take(Ks[r], tranche, t, nc[r], examined[r], dups[r], left[r]);  // <no stop at K, no winners' selection>
         if (distinct) return finish ? bests_winners(K, settled[r]) : bests_take_distinct(K, tranche, t, nc[r], examined[r], dups[r], settled[r]);
         return finish ? bests_winners(K, ok[r]) : bests_take(K, tranche, t, nc[r], examined[r], ok[r]);
     }
@@ -215,7 +374,7 @@ struct BestsTally {
     bool adopt_candidates(const BestsCall& c, std::string* why) {
         unsigned long long total = 0;
         for (u32 r = 0; r < R; r++) total += nc[r] = c.mirror(c.L.c_ncand)[r];
-        if (total <= c.B && c.mirror(c.L.c_seg)[R] == total) return true;
+        if (total <= c.B - c.first() && c.mirror(c.L.c_seg)[R] == total + c.first()) return true;  // <a segment holds the entry slots too>
         return *why = std::string(c.family()) + "the device counted " + std::to_string(total) + " candidates among " + std::to_string(c.B) + " rows", false;
     }
     // The most rows step t can hold, from what a host form knows before the device has planned it.  It has counted the valid rows, so
@@ -224,8 +383,8 @@ struct BestsTally {
     u32 bound(u32 t) const {
         unsigned long long sum = 0;
         for (u32 r = 0; r < R; r++) {
-            if (!distinct)
-                sum += rows_of(r, t, false);
+            if (!distinct || stands())  // <dups and left as mirrored are lower bounds>
+                sum += !distinct || running[r] ? rows_of(r, t, false) : 0;
             else if (running[r] && !(K && std::max(settled[r], ok[r] ? 1u : 0u) >= K))
                 sum += bests_take_distinct(K, tranche, t, nc[r], examined[r], dups[r], 0);
         }
@@ -257,11 +416,19 @@ struct BestsTally {
             if (good && c.D) {
                 const u32 ds = c.dmirror(c.D->d_settled)[r], dd = c.dmirror(c.D->d_dups)[r];
                 good = ds >= settled[r] && ds <= dok && dd >= dups[r] && (unsigned long long)examined[r] + dd <= nc[r];
+                if (good && stands()) {
+                    const u32 dl = ((const u32*)(c.h + c.stands->W->h_sctr))[r];
+                    good = dl >= left[r] && (unsigned long long)examined[r] + dd + dl <= nc[r];
+                    if (good) left[r] = dl;
+                }
                 if (good) settled[r] = ds, dups[r] = dd;
             }
             if (good) ok[r] = dok;
         }
-        if (good) {
+        if (good && stands() && finish) {  // <nothing was planned: every standing has stopped, no candidate is live>
+            n = 0;
+            for (u32 r = 0; r < R && good; r++) good = rows_of(r, 0, false) == 0, take[r] = 0;
+        } else if (good) {
             n = 0;
             unsigned long long at = 0;
             for (u32 r = 0; r < R && good; r++) {
@@ -295,6 +462,31 @@ static int32_t bests_deliver(const BestsCall& c, const BestsTally& ty, const u32
     if (o.n_steps) *o.n_steps = steps;
     return BBP_OK;
 }
+// <an offer to many standings, after its finish has arrived (tally checked): every working standing against the call -- at most K
+// entries, every one a working row of that standing -- then the outputs: the call's rows among the entries, in rank order>
+static int32_t stands_deliver(const BestsCall& c, const BestsTally& ty, const u32* round_of, u32 steps, const BestsOut& o, std::string* why) {
+    const StandsCall& S = *c.stands;
+    const u32 *whdr = (const u32*)(c.h + S.W->h_whdr), *order = (const u32*)(c.h + S.W->h_order);
+    for (u32 s = 0; s < S.S; s++) {
+        const u32 count = whdr[(size_t)STANDS_H_STRIDE * s + STAND_H_COUNT];
+        bool ok = count <= S.K[s];
+        for (u32 e = 0; ok && e < count; e++) {
+            const u32 i = order[S.E[s] + e];
+            ok = i < c.B && round_of[i] == s && (i >= S.sumK || (i >= S.E[s] && i - S.E[s] < S.K[s]));
+        }
+        if (!ok) return *why = std::string(c.family()) + "the working standing " + std::to_string(s) + " holds what is no row of it", BBP_ERR_INTERNAL;
+        u32 ne = 0;
+        for (u32 e = 0; e < count; e++) {
+            const u32 i = order[S.E[s] + e];
+            if (i < S.sumK) continue;
+            if (ne < o.cap) o.best[(size_t)s * o.cap + ne] = i - S.sumK;
+            ne++;
+        }
+        o.n_best[s] = ne, o.n_candidates[s] = ty.nc[s], o.n_examined[s] = ty.examined[s], o.n_duplicates[s] = ty.dups[s];
+    }
+    if (o.n_steps) *o.n_steps = steps;
+    return BBP_OK;
+}
 // a step cannot run more often than a tranche can double
 constexpr u32 BESTS_MAX_STEPS = 40;
 
@@ -314,6 +506,18 @@ static int32_t bests_run_host(BestsCall& c, const u32* round_of, Fill&& fill, Ve
     BestsTally ty(c);
     std::vector<int32_t> st;
     std::string why;
+    const u32 first = c.first();
+    std::vector<uint8_t> stand_floors;
+    if (c.stands) {  // <the floor every standing screens by, from the standing as its last commit left it>
+        stand_floors.resize(32 * (size_t)c.R);
+        for (u32 s = 0; s < c.R; s++) {
+            const bbp_ctx::Standing& m = *c.stands->meta[s];
+            u32 f[8];
+            stand_screen_floor(m.floor, m.count == m.K, m.bar, f);
+            for (int b = 0; b < 32; b++) stand_floors[32 * (size_t)s + b] = (uint8_t)(f[b >> 2] >> (8 * (b & 3)));
+        }
+        floors = stand_floors.data();
+    }
     auto fail = [&](const std::string& w, int32_t rc) {
         api_guard(dev, [&]() -> int32_t { return dev->err = w, rc; });
         return rc;
@@ -332,10 +536,12 @@ static int32_t bests_run_host(BestsCall& c, const u32* round_of, Fill&& fill, Ve
     int32_t rc = submit([&]() -> int32_t {
         int32_t r;
         if ((r = bests_open(c, floors, round_of, nullptr, nullptr))) return r;
-        fill(c.h + c.h_staged());
-        BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.staged(), c.h + c.h_staged(), c.staged_row() * c.B, hipMemcpyHostToDevice, c.s));
-        if (c.D && (r = bests_ids_enqueue(c, c.d + c.staged(), false))) return r;  // (which says where each staged row starts)
-        if ((r = bests_segment_enqueue(c, c.d + c.staged(), c.D.has_value(), (int32_t*)c.at(L.status)))) return r;
+        if (c.stands && (r = stands_seed_enqueue(c, (int32_t*)c.at(L.status)))) return r;
+        const size_t skip = c.staged_row() * first;  // <the entry slots are not staged: the seed wrote them>
+        fill(c.h + c.h_staged() + skip);
+        BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + c.staged() + skip, c.h + c.h_staged() + skip, c.staged_row() * (c.B - first), hipMemcpyHostToDevice, c.s));
+        if (c.D && (r = bests_ids_enqueue(c, c.d + c.staged() + skip, false))) return r;  // (which says where each staged row starts)
+        if ((r = bests_segment_enqueue(c, c.d + c.staged() + skip, c.D.has_value(), (int32_t*)c.at(L.status)))) return r;  // <and the leave pass in front of step 0>
         BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + L.h_ctr, c.d + L.ctr, 4 * (size_t)L.c_words, hipMemcpyDeviceToHost, c.s));
         return BBP_OK;
     });
@@ -346,7 +552,7 @@ static int32_t bests_run_host(BestsCall& c, const u32* round_of, Fill&& fill, Ve
     for (u32 t = 0;; t++) {
         const u32 room = std::min(ty.bound(t), c.B);
         finish = finish || room == 0 || t >= BESTS_MAX_STEPS;
-        const u32 nw = finish ? std::min(ty.winners_bound(), c.B) : 0;
+        const u32 nw = finish && !c.stands ? std::min(ty.winners_bound(), c.B) : 0;
         rc = submit([&]() -> int32_t {
             int32_t r;
             if (pending) {
@@ -354,8 +560,9 @@ static int32_t bests_run_host(BestsCall& c, const u32* round_of, Fill&& fill, Ve
                 memcpy(c.h + L.h_tstat, st.data(), 4 * (size_t)pending);
                 BBP_HIP_TRY(dev, hipMemcpyAsync(c.d + L.tstat, c.h + L.h_tstat, 4 * (size_t)pending, hipMemcpyHostToDevice, c.s));
                 if ((r = bests_mark_enqueue(c, pending, tstat, (int32_t*)c.at(L.status)))) return r;
-                if (c.D && (r = bests_settle_enqueue(c, pending, tstat, (int32_t*)c.at(L.status)))) return r;
+                if (c.D && (r = bests_settle_enqueue(c, pending, tstat, (int32_t*)c.at(L.status), t - 1, ty.take.data()))) return r;
             }
+            if (c.stands && finish) return stands_finish_enqueue(c, (const int32_t*)c.at(L.status));
             if ((r = bests_plan_enqueue(c, t, finish, false, finish ? nw > 0 : true))) return r;
             if (finish) return bests_pairs_enqueue(c, nw, (const int32_t*)c.at(L.status));
             BBP_HIP_TRY(dev, hipMemcpyAsync(c.h + L.h_sel, c.d + L.sel, 4 * (size_t)room, hipMemcpyDeviceToHost, c.s));
@@ -382,8 +589,14 @@ static int32_t bests_run_host(BestsCall& c, const u32* round_of, Fill&& fill, Ve
             for (u32 e = j + ty.take[r]; j < e; j++) ty.examined[r]++, ty.ok[r] += st[j] == BBP_OK;
         pending = n;
     }
-    if ((rc = bests_deliver(c, ty, round_of, steps, out, &why))) return fail(why, rc);
-    memcpy(status, c.h + L.h_status, 4 * (size_t)c.B);
+    if (c.stands) {  // <the host's checks first, then the one commit, then the host's records of what was committed>
+        if ((rc = stands_deliver(c, ty, round_of, steps, out, &why))) return fail(why, rc);
+        if ((rc = submit([&]() -> int32_t { return stands_commit_enqueue(c); }))) return rc;
+        for (u32 s = 0; s < c.R; s++)
+            stand_record_commit(*c.stands->meta[s], (const u32*)(c.h + c.stands->W->h_whdr) + (size_t)STANDS_H_STRIDE * s, c.stands->n_rows[s]);
+    } else if ((rc = bests_deliver(c, ty, round_of, steps, out, &why)))
+        return fail(why, rc);
+    memcpy(status, c.h + L.h_status, 4 * (size_t)(c.B - first));
     return BBP_OK;
 }
 
@@ -513,13 +726,15 @@ struct BestsHostRows {
     std::vector<unsigned long long> rowoff;
     std::vector<uint8_t> picked;
     std::vector<u32> step_round_of;
+    u32 first = 0;  // <sel holds working rows: row sel[j] - first of the call>
     int32_t verify(u32 n, const u32* sel, const u32* take, int32_t* st) {
         bests_step_rounds(R, take, step_round_of);
         picked.clear();
         for (u32 j = 0; j < n; j++) {
-            if (sel[j] >= B || round_of[sel[j]] != step_round_of[j])
+            const u32 i = sel[j] - first;
+            if (sel[j] < first || i >= B || round_of[i] != step_round_of[j])
                 return api_guard(ctx, [&]() -> int32_t { return ctx->err = std::string(family) + "a selected row is no row of its round", BBP_ERR_INTERNAL; });
-            picked.insert(picked.end(), rows + rowoff[sel[j]], rows + rowoff[sel[j] + 1]);
+            picked.insert(picked.end(), rows + rowoff[i], rows + rowoff[i + 1]);
         }
         return verify_host(ctx, VerifyRows::of_rounds(n, R, round_Ns, rounds, step_round_of.data()), picked.data(), st, BBP_AGG_GROUP_DEFAULT, nullptr);
     }
@@ -667,4 +882,105 @@ extern "C" int32_t bbp_verify_rounds_best_distinct_dev(bbp_ctx* ctx, uint32_t R,
     if (int32_t rc = bests_screen(ctx, "bbp_verify_rounds_best_distinct_dev", R, round_Ns, B, round_of, &done)) return rc;
     if (done) return BBP_OK;
     return bests_public_dev(ctx, R, round_Ns, rounds_dev, B, round_of, rows_dev, entropy_dev, floors, K, tranche, true, out, status_dev, stream);
+}
+
+// ---- standings of many rounds (include/bbp.h; rules and kernels: standings.h) -----------------------------------------------------------
+// One offer to S open standings: the host driver above over the W = sum K + B working rows, the standings as its rounds.  The standings
+// of a handle live on ONE device's context (a pool: member 0).  One standing: the single-standing driver of capi_best.hip.
+static void stands_zero(u32 S, const BestsOut& o) {
+    for (u32 s = 0; s < S && S <= BBP_STANDING_MAX_OPEN; s++) o.n_best[s] = o.n_candidates[s] = o.n_examined[s] = o.n_duplicates[s] = 0;
+    if (o.n_steps) *o.n_steps = 0;
+}
+// the screening both forms share, in the header's order behind the NULL checks; *done: the call ends here with BBP_OK
+static int32_t stands_screen(bbp_ctx* ctx, const char* what, u32 S, const u32* standings, u32 B, const u32* standing_of, bool* done) {
+    const std::string name(what);
+    *done = false;
+    if (S == 0 || S > BBP_STANDING_MAX_OPEN) return stand_refuse(ctx, name + ": S is 0 or above BBP_STANDING_MAX_OPEN");
+    {
+        bbp_ctx* const dev = stand_dev(ctx);
+        std::lock_guard<std::mutex> call(dev->best_mu);
+        for (u32 s = 0; s < S; s++)
+            if (!stand_find(dev, standings[s])) return stand_refuse(ctx, name + ": no open standing has the handle standings[" + std::to_string(s) + "]");
+    }
+    for (u32 s = 0; s < S; s++)
+        for (u32 q = 0; q < s; q++)
+            if (standings[q] == standings[s]) return stand_refuse(ctx, name + ": a standing is named twice");
+    if (B > BBP_SELECT_MAX_BIDS) return stand_refuse(ctx, name + ": more than BBP_SELECT_MAX_BIDS rows");
+    if (B == 0) return *done = true, BBP_OK;
+    for (u32 i = 0; standing_of && i < B; i++)
+        if (standing_of[i] >= S) return stand_refuse(ctx, name + ": standing_of names a standing beyond S");
+    return BBP_OK;
+}
+// both forms behind their screening, S > 1: the call built and run.  run(c, S): the form's fill and verdicts, handed to bests_run_host.
+template <class Run>
+static int32_t stands_offer(bbp_ctx* ctx, u32 S, const u32* standings, u32 B, const u32* standing_of, u32 tranche, Run&& run) {
+    bbp_ctx* const dev = stand_dev(ctx);
+    StandsCall SC(dev, S, standings, B, standing_of);
+    const u32 W = SC.sumK + B;
+    BestsCall c(dev, S, W, 0, tranche, dev->stream, true, true);
+    SC.W.emplace(*c.D, S, SC.sumK, B);
+    c.stands = &SC;
+    std::vector<u32> round_of(W);  // the working round_of
+    for (u32 s = 0; s < S; s++) std::fill(round_of.begin() + SC.E[s], round_of.begin() + SC.E[s] + SC.K[s], s);
+    std::copy(standing_of, standing_of + B, round_of.begin() + SC.sumK);
+    const int32_t rc = run(c, SC, round_of.data());
+    if (rc && dev != ctx) api_guard(ctx, [&]() -> int32_t { return ctx->err = tls_error(), rc; });
+    return rc;
+}
+
+extern "C" int32_t bbp_standings_offer(bbp_ctx* ctx, uint32_t S, const uint32_t* standings, uint32_t B, const uint32_t* standing_of, const uint8_t* rows,
+                                       uint32_t tranche, uint32_t cap, uint32_t* entered_out, uint32_t* n_entered, uint32_t* n_candidates, uint32_t* n_examined,
+                                       uint32_t* n_duplicates, uint32_t* n_steps, int32_t* status) {
+    if (!ctx || !standings || !rows || !n_entered || !n_candidates || !n_examined || !n_duplicates || !status || (cap && !entered_out) || (!standing_of && S != 1))
+        return BBP_ERR_BAD_ARG;
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        const BestsOut out{cap, entered_out, n_entered, n_candidates, n_examined, n_steps, n_duplicates};
+        stands_zero(S, out);
+        bool done;
+        if (int32_t rc = stands_screen(ctx, "bbp_standings_offer", S, standings, B, standing_of, &done)) return rc;
+        if (done) return BBP_OK;
+        if (S == 1) return stand_public_host(ctx, "bbp_standings_offer", standings[0], B, rows, tranche, out.one_round(), status);
+        return stands_offer(ctx, S, standings, B, standing_of, tranche, [&](BestsCall& c, StandsCall& SC, const u32* round_of) -> int32_t {
+            std::vector<u32> Ns(S);
+            std::vector<uint8_t> rounds;
+            for (u32 s = 0; s < S; s++) Ns[s] = SC.meta[s]->N, rounds.insert(rounds.end(), SC.meta[s]->round.begin(), SC.meta[s]->round.end());
+            BestsHostRows hr{ctx, c.family(), S, B, Ns.data(), standing_of, rounds.data(), rows, bests_row_offsets(Ns.data(), B, standing_of), {}, {}, SC.sumK};
+            auto fill = [&](u8* dst) {
+                for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, rows + hr.rowoff[i + 1] - 64, 64);
+            };
+            auto verdicts = [&](u32 n, const u32* sel, const u32* take, int32_t* st) -> int32_t { return hr.verify(n, sel, take, st); };
+            return bests_run_host(c, round_of, fill, verdicts, nullptr, out, status);
+        });
+    });
+}
+
+// Test hook: an offer of caller-made keys, ids and verdicts through the shipped kernels against the standings' states.  Synchronises.
+extern "C" int32_t bbp_debug_standings_offer(bbp_ctx* ctx, uint32_t S, const uint32_t* standings, uint32_t B, const uint32_t* standing_of, const uint8_t* keys,
+                                             const uint8_t* ids, const int32_t* verdicts, uint32_t tranche, uint32_t cap, uint32_t* entered_out,
+                                             uint32_t* n_entered, uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, uint32_t* n_steps,
+                                             int32_t* status) {
+    if (!ctx || !standings || !keys || !ids || !verdicts || !n_entered || !n_candidates || !n_examined || !n_duplicates || !status || (cap && !entered_out) ||
+        (!standing_of && S != 1))
+        return BBP_ERR_BAD_ARG;
+    if (is_pool(ctx)) return pool_reject(ctx, "bbp_debug_standings_offer");
+    return no_throw_ctx(ctx, [&]() -> int32_t {
+        const BestsOut out{cap, entered_out, n_entered, n_candidates, n_examined, n_steps, n_duplicates};
+        stands_zero(S, out);
+        bool done;
+        if (int32_t rc = stands_screen(ctx, "bbp_debug_standings_offer", S, standings, B, standing_of, &done)) return rc;
+        if (done) return BBP_OK;
+        u32 n_ok;
+        if (int32_t rc = best_hook_screen(ctx, "bbp_debug_standings_offer", B, verdicts, &n_ok)) return rc;
+        if (S == 1) return stand_hook_host(ctx, "bbp_debug_standings_offer", standings[0], B, keys, ids, verdicts, tranche, out.one_round(), status);
+        return stands_offer(ctx, S, standings, B, standing_of, tranche, [&](BestsCall& c, StandsCall& SC, const u32* round_of) -> int32_t {
+            auto fill = [&](u8* dst) {
+                for (u32 i = 0; i < B; i++) memcpy(dst + 64 * (size_t)i, keys + 32 * (size_t)i, 32), memcpy(dst + 64 * (size_t)i + 32, ids + 32 * (size_t)i, 32);
+            };
+            auto read = [&](u32 n, const u32* sel, const u32*, int32_t* st) -> int32_t {
+                for (u32 j = 0; j < n; j++) st[j] = sel[j] >= SC.sumK && sel[j] - SC.sumK < B ? verdicts[sel[j] - SC.sumK] : (int32_t)BBP_ERR_INTERNAL;
+                return BBP_OK;
+            };
+            return bests_run_host(c, round_of, fill, read, nullptr, out, status);
+        });
+    });
 }

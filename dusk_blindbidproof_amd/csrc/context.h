@@ -220,6 +220,7 @@ struct bbp_ctx {
     // the identity table and three counters behind BestLayout's state -- public for the same reason: what any verifier is handed.
     // The many-rounds calls (bbp_verify_rounds_best, ...) with R > 1 lay the same allocations out by rounds_best.h's BestsLayout:
     // per-round counters, segments and floors, round_of and row offsets beside the keys, records and statuses.
+    // An offer to many standings (bbp_standings_offer; standings.h's StandingsLayout) works behind that state, in the same allocations.
     std::mutex best_mu;
     bbp::DevBuf best_dev, best_rows;
     void* best_h = nullptr;

@@ -88,11 +88,13 @@ struct StandingState {
 
 // The rules.  keys, ids: B x 8 words; verdicts: what verification says of row i (read for examined rows only); entered_out: room for cap
 // entries; status: B entries.  table_log2: 0 for the call's own sizing (from K + B working rows), or an explicit size.  Returns BBP_OK,
-// or BBP_ERR_INTERNAL with S untouched when a bounded loop of the identity table ran out.
+// or BBP_ERR_INTERNAL with S untouched when a bounded loop of the identity table ran out.  ran (may be null): the tranches that ran.
 inline int32_t standing_offer_host(StandingState& S, u32 B, const u32* keys, const u32* ids, const int32_t* verdicts, u32 tranche, u32 cap, u32* entered_out,
-                                   u32* n_entered, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status, u32 table_log2 = 0) {
+                                   u32* n_entered, u32* n_candidates, u32* n_examined, u32* n_duplicates, int32_t* status, u32 table_log2 = 0,
+                                   u32* ran = nullptr) {
     const u32 K = S.K, n0 = S.count(), W = K + B;
     *n_entered = *n_candidates = *n_examined = *n_duplicates = 0;
+    if (ran) *ran = 0;
     if (B == 0) return BBP_OK;
     std::vector<u32> wk(8 * (size_t)W, 0), wid(8 * (size_t)W, 0);
     std::copy(S.keys.begin(), S.keys.end(), wk.begin());
@@ -145,6 +147,7 @@ inline int32_t standing_offer_host(StandingState& S, u32 B, const u32* keys, con
         std::sort(held.begin(), held.end(), before);
         if (held.size() > K) held.resize(K);
         leave();
+        if (ran) *ran = t + 1;
     }
     if (flag) return BBP_ERR_INTERNAL;
     StandingState N = S;
@@ -165,7 +168,9 @@ inline int32_t standing_offer_host(StandingState& S, u32 B, const u32* keys, con
     return BBP_OK;
 }
 
-#ifdef __HIPCC__
+// k_stand_merge's workgroup; standings.h's merge has the same
+constexpr u32 STAND_MERGE_T = 256;
+#if defined(__HIPCC__) && defined(BBP_ROUND_BEST_KERNELS)  // the kernels: compiled by the one unit that launches them (capi.h)
 // One lane per entry slot e < K.  st_*: the standing's own allocation (read only).  An entry's working index is its slot; it enters the
 // table through the standing's own arrays (stride 8, the same indices), so no lane reads what another lane of this launch writes.
 // Entries have distinct identities: every insert claims an empty slot.
@@ -206,7 +211,6 @@ __global__ void __launch_bounds__(BEST_T) k_stand_displace(u32 K, const u32* __r
 // ONE workgroup, behind the selection over the winner records with the call's K: sel holds the at most K winners that stay, in ascending
 // index.  Their keys go to LDS; every winner counts the winners that come before it in rank order (key descending, index ascending: a
 // total order, so the counts are a permutation) and writes its index there.  At most K^2 / STAND_MERGE_T comparisons per lane.
-constexpr u32 STAND_MERGE_T = 256;
 __global__ void __launch_bounds__(STAND_MERGE_T) k_stand_merge(u32 K, const u32* __restrict__ sel, const u32* __restrict__ counts, const u32* __restrict__ win,
                                                                u32* __restrict__ whdr, u32* __restrict__ order, u32 trip, u32* dctr) {
     __shared__ u32 key[8 * BBP_STANDING_MAX_K];

@@ -151,7 +151,7 @@ inline bool batch_spans(u32 B, const BatchDims& d, int cls, BatchSpans& out) {
     X("vl.agg", c->vl[i].agg, bbp_ctx::VLANES, false)                                                                                   \
     X("vl.agg_io", c->vl[i].agg_io, bbp_ctx::VLANES, false)                                                                             \
     /* bbp_verify_round_best: proof rows, their claimed scores and the verifier's verdicts are what any verifier is handed or tells */   \
-    X("best", c->best_dev, 1, false)                         /* keys, candidate and winner records, statuses, selections; the one-per-bidder calls: z_img of every row, the identity table (row indices), three counters; the many-rounds calls: round_of, row offsets, floors, per-round counters and segments */ \
+    X("best", c->best_dev, 1, false)                         /* keys, candidate and winner records, statuses, selections; the one-per-bidder calls: z_img of every row, the identity table (row indices), three counters; the many-rounds calls: round_of, row offsets, floors, per-round counters and segments; an offer to many standings (StandingsLayout): per-standing counters, the table of the standings' base pointers and K, working headers, serials, rank orders and the rows' local indices -- copies of standings' entries and addresses, nothing of a prover */ \
     X("best.rows", c->best_rows, 1, false)                   /* the _dev form's gathered rows and verifier entropy rows of one tranche */ \
     X("stand", c->stand[i], bbp_ctx::STANDINGS, false)       /* a standing's entries: claimed scores, z_img, serials of rows that verified -- verify-side data only */
 // X(name, pointer, capacity, count, secret): the pinned mirrors of the staging slots

@@ -628,7 +628,7 @@ int32_t bbp_debug_rounds_best_distinct(bbp_ctx* ctx, uint32_t R, uint32_t B, con
  * BBP_OK with zero counts); beyond that it refuses what bbp_debug_round_best_distinct refuses: a verdict outside the three.
  * bbp_debug_standing_trip, test hook: the next offer to the standing raises the offer's internal flag word on the device behind its
  * after-th merge (after >= 1) and so ends with BBP_ERR_INTERNAL, as an offer whose bounded loops ran out does; no device fault is involved.
- * Out of scope: a _dev form of the offer; standings over many rounds in one call; a server opcode; keeping the winning rows' bytes; a
+ * Out of scope: a _dev form of the offer; a server opcode; keeping the winning rows' bytes; a
  * memory of rejected rows; a round table resident across offers (the round travels with every tranche, as in the one-shot calls). */
 #define BBP_STANDING_MAX_K 1024u
 #define BBP_STANDING_MAX_OPEN 64u
@@ -642,6 +642,47 @@ int32_t bbp_debug_standing_offer(bbp_ctx* ctx, uint32_t standing, uint32_t B, co
                                  uint32_t tranche, uint32_t cap, uint32_t* entered_out, uint32_t* n_entered, uint32_t* n_candidates,
                                  uint32_t* n_examined, uint32_t* n_duplicates, int32_t* status);
 int32_t bbp_debug_standing_trip(bbp_ctx* ctx, uint32_t standing, uint32_t after);
+
+/* Standings of many rounds: one offer to S open standings at once.  A node that follows several rounds receives each gossip burst with
+ * rows of all of them mixed; cut by round and offered one standing at a time, every bbp_standing_offer pays the floor of a small call --
+ * seed, keys, leave pass, at least one tranche, finish, commit, several host waits each -- and they are serialised.  Here step t of every
+ * standing that still runs rides ONE engine call, as in bbp_verify_rounds_best_distinct.
+ * standings[s] are S handles of open standings of this context or pool, all different; standing_of[i] < S names the standing that row i
+ * is offered to (NULL only when S == 1: every row to standings[0]); rows as bbp_verify_rounds_best takes the rows of rounds with
+ * different N: row i is bbp_round_row_size(N of its standing) bytes, rows back to back.  A standing of the call may receive no row.
+ * The rule: for every s the call reports what bbp_standing_offer(standings[s], the rows with standing_of[i] == s in ascending call index,
+ * tranche, cap) would report -- n_entered[s], n_candidates[s], n_examined[s], n_duplicates[s] (S entries each), the statuses of its rows
+ * (status: B entries) and entered_out[s * cap ..], which receives min(n_entered[s], cap) CALL indices in rank order (entries beyond are
+ * not written) -- and afterwards bbp_standing_read of standings[s] returns what it would return after that single offer, serials
+ * included: the j-th row of standing s in call order has serial offered_s + j.
+ *   per standing  each standing keeps its own N, round, floor and K from bbp_standing_open; T_0 of standing s is max(tranche, K_s)
+ *   steps         step t holds tranche t of every standing that still has a live candidate; a standing stops when it has none, and one
+ *                 that still runs has run every step so far.  All the rows of a step are gathered by standing and verified in one
+ *                 call through bbp_verify_rounds_aggregated's own path, the round table made of the S standings' stored rounds; entropy
+ *                 source, BBP_HOST_CHUNK_VERIFY, the health word, verify mixing and the pool split hold as they do for
+ *                 bbp_verify_rounds_best_distinct
+ *   n_steps       (may be NULL) the largest number of tranches any standing ran
+ *   identities    never meet across standings: one z_img resent to every standing is S identities
+ *   one commit    the call works on copies in its own scratch and commits all S standings with one launch at the end, after the host's
+ *                 checks.  A call that ends with BBP_ERR_DEVICE or BBP_ERR_INTERNAL leaves EVERY standing of the call and its offered
+ *                 count exactly as before -- also when the flag word was raised for one standing only, as bbp_debug_standing_trip set on
+ *                 any one of them does (the trip is consumed by the next offer of either kind)
+ * Only score || z_img (64 bytes per row) go up for screening; a row's full bytes go up only in the step that verifies it.
+ * Screening, the first failing check decides: a NULL pointer BBP_ERR_BAD_ARG (entered_out may be NULL only when cap == 0, standing_of only
+ * when S == 1, n_steps always); S == 0 or S > BBP_STANDING_MAX_OPEN BBP_ERR_BAD_ARG; a handle that is unknown or closed BBP_ERR_BAD_ARG;
+ * the same handle twice BBP_ERR_BAD_ARG; B > BBP_SELECT_MAX_BIDS BBP_ERR_BAD_ARG; B == 0 BBP_OK with zero counts and nothing changed;
+ * standing_of[i] >= S BBP_ERR_BAD_ARG.  S == 1 runs bbp_standing_offer's own driver, as R == 1 does in the many-rounds best calls.
+ * Serialised with the other best calls of the context; on a pool the standings live on member 0; bbp_reserve does NOT size the state.
+ * bbp_debug_standings_offer, test hook (synchronises; a pool refuses it): the same with made-up keys, ids (B x 32 bytes each) and
+ * verdicts (B x int32) in place of rows, through the shipped kernels; nothing is verified.  Beyond the screening above it refuses what
+ * bbp_debug_standing_offer refuses: a verdict outside the three.
+ * Out of scope: a _dev form; a server opcode; more than BBP_STANDING_MAX_OPEN standings in one call. */
+int32_t bbp_standings_offer(bbp_ctx* ctx, uint32_t S, const uint32_t* standings, uint32_t B, const uint32_t* standing_of, const uint8_t* rows,
+                            uint32_t tranche, uint32_t cap, uint32_t* entered_out, uint32_t* n_entered, uint32_t* n_candidates, uint32_t* n_examined,
+                            uint32_t* n_duplicates, uint32_t* n_steps, int32_t* status);
+int32_t bbp_debug_standings_offer(bbp_ctx* ctx, uint32_t S, const uint32_t* standings, uint32_t B, const uint32_t* standing_of, const uint8_t* keys,
+                                  const uint8_t* ids, const int32_t* verdicts, uint32_t tranche, uint32_t cap, uint32_t* entered_out, uint32_t* n_entered,
+                                  uint32_t* n_candidates, uint32_t* n_examined, uint32_t* n_duplicates, uint32_t* n_steps, int32_t* status);
 
 /* Optional, once after bbp_init (or whenever a new list length N shows up): grow every per-batch buffer of the context (every member
  * of a pool) to what batches of up to max_batch proofs / verifications of list length N need, and compile the circuit for N.

@@ -42,6 +42,13 @@ One JSON line per cell, to stdout and to --out (default profiles/r19_round_best.
           alone.  Per arm ms per burst, bytes uploaded, rows verified; every output of every offer is asserted equal to the model of
           tests/round_standing_cases.py.
 
+  --standings [OUT]   instead of the above: one offer to many standings ("Standings of many rounds"): 64 standings at N = 50, K = 3,
+          default tranche; 8192 rows arrive as 32 bursts of 256, every burst carrying 4 rows of each of the 64 rounds, interleaved, the
+          second half of a round's rows of a burst resending earlier ones, into OUT (profiles/r25_standings.jsonl).  Arms: (a) one
+          bbp_standings_offer per burst; (b) one bbp_standing_offer per standing per burst.  Per arm ms per burst, rows verified, bytes
+          uploaded; every output of arm (a) is asserted equal to the model of tests/standings_cases.py, and the two arms must leave equal
+          standings.
+
 Rows are 64 proved bids of the round repeated (byte-equal rows do occur in the protocol too); arms alternate in one process; every figure
 is the best of --calls calls, taken --runs times after a warm-up: median and range."""
 import argparse
@@ -705,8 +712,122 @@ def standing_main(args):
             ctx.close()
 
 
+def standings_main(args):
+    """--standings: 64 rounds at N = 50, K = 3, one standing each; 8192 rows arrive as 32 bursts of 256, 4 rows of every round in every
+    burst.  Arms, alternated: (a) one bbp_standings_offer per burst; (b) one bbp_standing_offer per standing per burst."""
+    import torch
+    torch.cuda.init()
+    import dusk_blindbidproof_amd as bbp
+    from tests import prove_round_cases as rc
+    from tests import round_standing_cases as sc
+    from tests import standings_cases as mc
+    box = box_id()
+    os.makedirs(os.path.dirname(os.path.abspath(args.standings)), exist_ok=True)
+    N, K, tranche, S, n_bursts, per_round, n_base = 50, 3, 0, 64, 32, 4, 8
+    per = S * per_round
+    B = n_bursts * per
+    unit = "ms of host time per burst (a run is the %d bursts in order, the standings opened before and read and closed after), %d runs after a warm-up, arms alternated" % (n_bursts, args.runs)
+    with open(args.standings, "w") as f:
+        def emit(rec):
+            rec.update(box=box, commit=args.commit)
+            line = json.dumps(rec)
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        ctx = bbp.Context(0)
+        lib, h = bbp.lib, ctx.handle
+        try:
+            size, tab = bbp.round_row_size(N), 32 * (1 + N)
+            tables, rows, keys, ids, verdicts = [], [], [], [], []
+            for r in range(S):  # every round: its own seed and list, eight proved bidders, a stream of 128 rows with resends
+                r0 = rc.honest(N, n_base, tag=250 + r)
+                proved, _t, st = ctx.prove_round(N, r0.table, r0.bid_bytes)
+                assert st == [0] * n_base
+                rl, k, i = standing_traffic(bbp, N, proved, "half_resent", n_bursts, per_round)
+                tables.append(r0.table), rows.append(rl), keys.append(k), ids.append(i)
+                verdicts.append(ctx.verify_rounds([N], r0.table, None, b"".join(rl)))
+            # burst o: row j of every round, then row j + 1: a wavefront holds rows of all rounds
+            idx = [[(r, o * per_round + j) for j in range(per_round) for r in range(S)] for o in range(n_bursts)]
+            so = (ctypes.c_uint32 * per)(*[r for r, _ in idx[0]])
+            mixed = [(ctypes.c_uint8 * (size * per)).from_buffer_copy(b"".join(rows[r][x] for r, x in burst)) for burst in idx]
+            alone = [[(ctypes.c_uint8 * (size * per_round)).from_buffer_copy(b"".join(rows[r][o * per_round:(o + 1) * per_round])) for r in range(S)]
+                     for o in range(n_bursts)]
+            models, want, bytes_a, bytes_b = [sc.Standing(0, K) for _ in range(S)], [], 0, 0
+            for burst in idx:
+                w = mc.offer(models, [r for r, _ in burst], [keys[r][x] for r, x in burst], [ids[r][x] for r, x in burst], [verdicts[r][x] for r, x in burst],
+                             tranche)
+                want.append(w)
+                examined = sum(p[3] for p in w[0])
+                # score || z_img of every row handed over, the examined rows with their entropy and status words, and the round tables: arm
+                # (a) one table of S rounds per step, arm (b) one round per tranche of every standing
+                bytes_a += 64 * per + examined * (size + 32 + 4) + w[1] * S * tab
+                bytes_b += 64 * per + examined * (size + 32 + 4) + sum(m.tranches for m in models) * tab
+            for r in range(S):
+                assert [(k, i) for k, i, _ in models[r].entries] == [(k, i) for k, i, _ in sc.truth(keys[r], ids[r], verdicts[r], 0, K)]
+            ent, status = (ctypes.c_uint32 * (S * K))(), (ctypes.c_int32 * per)()
+            cnt = [(ctypes.c_uint32 * S)() for _ in range(4)]
+            steps = ctypes.c_uint32()
+            one = [ctypes.c_uint32() for _ in range(4)]
+            p1 = [ctypes.byref(x) for x in one]
+            seen = {}
+
+            def opened():
+                return [ctx.standing_open(N, tables[r], 0, K) for r in range(S)]
+
+            def closed(hs, arm):
+                seen[arm] = [ctx.standing_read(x) for x in hs]
+                for x in hs:
+                    ctx.standing_close(x)
+
+            def a_one_call_per_burst():
+                hs = opened()
+                handles = (ctypes.c_uint32 * S)(*hs)
+                got = []
+                for o in range(n_bursts):
+                    assert lib.bbp_standings_offer(h, S, handles, per, so, mixed[o], tranche, K, ent, cnt[0], cnt[1], cnt[2], cnt[3], ctypes.byref(steps),
+                                                   status) == 0, lib.bbp_last_error(h)
+                    e = list(ent)
+                    got.append(([[e[K * r:K * r + min(cnt[0][r], K)], cnt[0][r], cnt[1][r], cnt[2][r], cnt[3][r]] for r in range(S)], steps.value,
+                                list(status)))
+                closed(hs, "a")
+                return got
+
+            def b_one_call_per_standing():
+                hs = opened()
+                examined = 0
+                for o in range(n_bursts):
+                    for r in range(S):
+                        assert lib.bbp_standing_offer(h, hs[r], per_round, alone[o][r], tranche, K, ent, p1[0], p1[1], p1[2], p1[3], status) == 0
+                        examined += one[2].value
+                closed(hs, "b")
+                return examined
+            got = a_one_call_per_burst()
+            assert got == [(w[0], w[1], w[2]) for w in want], "an offer differs from the model"  # nothing here is tuned: the rules predict every output
+            examined_a = sum(p[3] for g in got for p in g[0])
+            examined_b = b_one_call_per_standing()
+            assert seen["a"] == seen["b"], "the two arms leave different standings"
+            assert examined_a == examined_b
+            arms = {"one_standings_offer_per_burst": a_one_call_per_burst, "one_standing_offer_per_standing_per_burst": b_one_call_per_standing}
+            args.calls = 1
+            rec = {"section": "standings", "N": N, "K": K, "tranche": "default", "standings": S, "rows": B, "bursts": n_bursts, "rows_per_burst": per,
+                   "rows_per_standing_per_burst": per_round, "traffic": "half_resent", "valid_rows": sum(v.count(0) for v in verdicts), "unit": unit}
+            for name, v in timed(arms, list(arms), args).items():
+                rec[name] = {k: round(x / n_bursts, 4) for k, x in v.items()}
+            assert seen["a"] == seen["b"]
+            rec["rows_verified"] = {"one_standings_offer_per_burst": examined_a, "one_standing_offer_per_standing_per_burst": examined_b}
+            rec["bytes_uploaded"] = {"one_standings_offer_per_burst": bytes_a, "one_standing_offer_per_standing_per_burst": bytes_b}
+            rec["steps"] = sum(g[1] for g in got)
+            rec["engine_calls"] = {"one_standings_offer_per_burst": sum(g[1] for g in got), "one_standing_offer_per_standing_per_burst": "one per tranche of every standing"}
+            emit(rec)
+            assert ctx.health() == 0
+        finally:
+            ctx.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--standings", nargs="?", const=os.path.join(ROOT, "profiles", "r25_standings.jsonl"), default="", metavar="OUT",
+                    help="measure one offer to many standings instead, into OUT (default profiles/r25_standings.jsonl)")
     ap.add_argument("--standing", nargs="?", const=os.path.join(ROOT, "profiles", "r24_round_standing.jsonl"), default="", metavar="OUT",
                     help="measure offers to a standing instead, into OUT (default profiles/r24_round_standing.jsonl)")
     ap.add_argument("--rounds-distinct", default="", metavar="OUT",
@@ -719,6 +840,8 @@ def main():
     ap.add_argument("--calls", type=int, default=2)
     ap.add_argument("--sections", default="cells,sweep")
     args = ap.parse_args()
+    if args.standings:
+        return standings_main(args)
     if args.standing:
         return standing_main(args)
     if args.rounds_distinct:
