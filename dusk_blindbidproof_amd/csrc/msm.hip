@@ -640,6 +640,34 @@ void k_msm_acc(const niels_row* __restrict__ ptable, const u32* __restrict__ sor
 #endif
 }
 
+// p + q where p2d = 2 d * p.T is already known (an operand that takes part in several additions pays that product once): 8M
+__device__ __forceinline__ ge ge_add_t2d(const ge& p, const fe& p2d, const ge& q) {
+    fe a = fe_mul(fe_sub(p.Y, p.X), fe_sub(q.Y, q.X));
+    fe b = fe_mul(fe_add(p.Y, p.X), fe_add(q.Y, q.X));
+    fe c = fe_mul(p2d, q.T);
+    fe zz = fe_mul(p.Z, q.Z);
+    fe d = fe_add(zz, zz);
+    fe e = fe_sub(b, a), f = fe_sub(d, c), g = fe_add(d, c), h = fe_add(b, a);
+    ge r;
+    r.X = fe_mul(e, f);
+    r.Y = fe_mul(g, h);
+    r.Z = fe_mul(g, f);  // (g first: the four products then share 2 x {e, g} and 19 x {f, h})
+    r.T = fe_mul(e, h);
+    return r;
+}
+
+__device__ __forceinline__ ge ld_ge(const ge* p) {
+    ge r;
+    const uint4* s = reinterpret_cast<const uint4*>(p);
+    u32* o = reinterpret_cast<u32*>(&r);
+#pragma unroll
+    for (int i = 0; i < GE_WORDS / 4; i++) {
+        const uint4 v = s[i];
+        o[4 * i] = v.x, o[4 * i + 1] = v.y, o[4 * i + 2] = v.z, o[4 * i + 3] = v.w;
+    }
+    return r;
+}
+
 // The cold half of an MSM as a kernel of its own: chunk-leading partial sums into their buckets (P), running-sum fold over each
 // lane's G buckets (D2), cross-lane fold (E).  It used to be the tail of k_msm_acc, where every point addition had to go through
 // ONE out-of-line copy (operands through the stack: 35 calls per lane and MSM, ~19 GB of scratch writes per 1024-proof batch) to
@@ -683,15 +711,29 @@ __global__ __launch_bounds__(MSM_T) void k_msm_fold(const u32* __restrict__ curs
         const bool inside = cursor[lo - 1] < c0;
         const bool last_of_run = inside && !(c1 < E && c1 > cursor[k_first - 1] && c1 < cursor[k_first]);
         if (last_of_run) {
-            ge part = psum[ch];
-            for (int u = (int)ch - 1; u >= 0; u--) {  // earlier chunks that also start strictly inside this bucket (skewed inputs only)
-                const u32 cu = (u32)(((u64)u * E) / ACC_T), cu1 = (u32)(((u64)(u + 1) * E) / ACC_T);
-                if (cu <= cursor[k_first - 1]) break;
-                if (cu1 > cu) ge_add_nc(part, part, psum[u]);
+            if constexpr (MODE == 1) {  // (inlined: the composite fold keeps nothing on the stack)
+                ge part = ld_ge(&psum[ch]);
+                for (int u = (int)ch - 1; u >= 0; u--) {
+                    const u32 cu = (u32)(((u64)u * E) / ACC_T), cu1 = (u32)(((u64)(u + 1) * E) / ACC_T);
+                    if (cu <= cursor[k_first - 1]) break;
+                    if (cu1 > cu) {
+                        const ge more = ld_ge(&psum[u]);
+                        part = ge_add(part, more);
+                    }
+                }
+                const ge head = ld_ge(&bsum[k_first - 1]);
+                bsum[k_first - 1] = ge_add(head, part);
+            } else {
+                ge part = psum[ch];
+                for (int u = (int)ch - 1; u >= 0; u--) {  // earlier chunks that also start strictly inside this bucket (skewed inputs only)
+                    const u32 cu = (u32)(((u64)u * E) / ACC_T), cu1 = (u32)(((u64)(u + 1) * E) / ACC_T);
+                    if (cu <= cursor[k_first - 1]) break;
+                    if (cu1 > cu) ge_add_nc(part, part, psum[u]);
+                }
+                ge head = bsum[k_first - 1];
+                ge_add_nc(head, head, part);
+                bsum[k_first - 1] = head;
             }
-            ge head = bsum[k_first - 1];
-            ge_add_nc(head, head, part);
-            bsum[k_first - 1] = head;
         }
     }
     __threadfence_block();
@@ -702,6 +744,26 @@ __global__ __launch_bounds__(MSM_T) void k_msm_fold(const u32* __restrict__ curs
     if constexpr (G == 1) {  // one bucket per lane: nothing to run over (two additions to the identity were 13 us of a 122 us fold)
         if (cursor[tid + 1] != cursor[tid]) running = bsum[tid];
         total = running;
+    } else if constexpr (MODE == 1) {
+        // ONE inlined addition site for both additions of a bucket: `running` is the first operand of either, so its 2d T product is
+        // computed once per change and shared (8 + 8 + 1 multiplications per bucket instead of 9 + 9, as in k_msm_fold_half)
+        fe r2d = fe_zero();  // 2 d * running.T
+#pragma unroll 1
+        for (int st = 2 * G - 1; st >= 0; st--) {  // odd: running += bucket r (when it is not empty); even: total += running
+            const u32 k = tid * G + (u32)(st >> 1) + 1;
+            const bool into_total = !(st & 1);
+            if (into_total || cursor[k] != cursor[k - 1]) {
+                ge q = total;
+                if (!into_total) q = ld_ge(&bsum[k - 1]);
+                const ge sum = ge_add_t2d(running, r2d, q);
+                if (into_total) {
+                    total = sum;
+                } else {
+                    running = sum;
+                    r2d = fe_mul(running.T, fe_d2());
+                }
+            }
+        }
     } else {
 #pragma unroll 1
         for (int r = G; r >= 1; r--) {
@@ -761,29 +823,39 @@ __global__ __launch_bounds__(MSM_T) void k_msm_fold(const u32* __restrict__ curs
         // class (LPC lanes x G keys): W = sum_q total_q + G * sum_{q>=1} suffix_q, S = suffix_0; result = 2 W - S
         constexpr int LPC = FOLD_M / G, LOG_G2 = G == 32 ? 5 : 6;
         static_assert(G == 32 || G == 64, "class reduction written for 4 or 2 lanes per class");
+        // ONE loop with one inlined addition and one inlined doubling, as phase E of k_msm_fold_half: steps 0 .. LOG_LPC - 1 are the
+        // suffix scan of `running` inside the class; step LOG_LPC is x = total + G * suffix (the suffix -- lane 0's is S -- is kept);
+        // the next LOG_LPC steps are the tree sum of x; the last one is 2 x - S, taken as (-S) + 2 x so that the doubling is the same site.
+        constexpr int LOG_LPC = LPC == 4 ? 2 : 1;
+        static_assert((1 << LOG_LPC) == LPC, "lanes per class");
         const int q = tid & (LPC - 1);
-        ge suf = running;
-        for (int d = 1; d < LPC; d++) {
-            ge other = ge_shfl_down(running, d);
-            if (q + d < LPC) ge_add_nc(suf, suf, other);
+        ge v = running, keep = total;
+#pragma unroll 1
+        for (int it = 0; it < 2 * LOG_LPC + 2; it++) {
+            ge o;
+            bool take;
+            int n_dbl = 0;
+            if (it == LOG_LPC) {
+                o = v;
+                v = keep;
+                keep = o;
+                n_dbl = LOG_G2;
+                take = q >= 1;
+            } else if (it == 2 * LOG_LPC + 1) {
+                o = v;
+                v = ge_neg(keep);
+                n_dbl = 1;
+                take = true;
+            } else {
+                const int d = it < LOG_LPC ? (1 << it) : ((LPC / 2) >> (it - LOG_LPC - 1));
+                o = ge_shfl_down(v, d);
+                take = it < LOG_LPC ? (q + d < LPC) : (q < d);
+            }
+#pragma unroll 1
+            for (int i = 0; i < n_dbl; i++) o = ge_dbl(o);
+            if (take) v = ge_add(v, o);
         }
-        ge x = total;
-        if (q >= 1) {
-            ge sg = suf;
-            for (int i = 0; i < LOG_G2; i++) ge_dbl_nc(sg, sg);
-            ge_add_nc(x, x, sg);
-        }
-        ge accq = x;
-        for (int d = 1; d < LPC; d++) {
-            ge other = ge_shfl_down(x, d);
-            if (q == 0) ge_add_nc(accq, accq, other);
-        }
-        if (q == 0) {
-            ge_dbl_nc(accq, accq);
-            ge other = ge_neg(suf);
-            ge_add_nc(accq, accq, other);
-            out[msm * FOLD_CLS + (tid / LPC)] = accq;
-        }
+        if (q == 0) out[msm * FOLD_CLS + (tid / LPC)] = v;
     }
 }
 
@@ -806,22 +878,6 @@ __device__ __forceinline__ ge ge_shfl_down32(const ge& p, int d) {  // within ea
     return r;
 }
 
-// p + q where p2d = 2 d * p.T is already known (an operand that takes part in several additions pays that product once): 8M
-__device__ __forceinline__ ge ge_add_t2d(const ge& p, const fe& p2d, const ge& q) {
-    fe a = fe_mul(fe_sub(p.Y, p.X), fe_sub(q.Y, q.X));
-    fe b = fe_mul(fe_add(p.Y, p.X), fe_add(q.Y, q.X));
-    fe c = fe_mul(p2d, q.T);
-    fe zz = fe_mul(p.Z, q.Z);
-    fe d = fe_add(zz, zz);
-    fe e = fe_sub(b, a), f = fe_sub(d, c), g = fe_add(d, c), h = fe_add(b, a);
-    ge r;
-    r.X = fe_mul(e, f);
-    r.Y = fe_mul(g, h);
-    r.Z = fe_mul(g, f);  // (g first: the four products then share 2 x {e, g} and 19 x {f, h})
-    r.T = fe_mul(e, h);
-    return r;
-}
-
 __device__ __forceinline__ void park_put(u32* park, int tid, const ge& p) {
     const u32* w = reinterpret_cast<const u32*>(&p);
 #pragma unroll
@@ -834,18 +890,6 @@ __device__ __forceinline__ ge park_get(const u32* park, int tid) {
 #pragma unroll
     for (int i = 0; i < GE_WORDS; i++) w[i] = park[i * 64 + tid];
     return p;
-}
-
-__device__ __forceinline__ ge ld_ge(const ge* p) {
-    ge r;
-    const uint4* s = reinterpret_cast<const uint4*>(p);
-    u32* o = reinterpret_cast<u32*>(&r);
-#pragma unroll
-    for (int i = 0; i < GE_WORDS / 4; i++) {
-        const uint4 v = s[i];
-        o[4 * i] = v.x, o[4 * i + 1] = v.y, o[4 * i + 2] = v.z, o[4 * i + 3] = v.w;
-    }
-    return r;
 }
 
 #ifndef BBP_FOLD_WAVES

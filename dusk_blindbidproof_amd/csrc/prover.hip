@@ -1063,139 +1063,102 @@ __global__ void k_tail_init(u32 B, sc* __restrict__ g_all, sc* __restrict__ h_al
 // L and R of a tail round (half length n <= 16) over the 32 + 32 materialised generators: one lane per (side, term), 33 terms a side.
 //   L = sum_{hi k} a[io] gg[k] F_G[k] + sum_{lo k} b[n+io] hh[k] F_H[k] + c_L w B      (k = blk 2n + {0, n} + io, rank = blk n + io)
 //   R = sum_{lo k} a[n+io] gg[k] F_G[k] + sum_{hi k} b[io] hh[k] F_H[k] + c_R w B
-// With `prev_round` != 0 the block first finishes the previous round: the first lane of each proof absorbs L, R of that round,
-// draws u and inverts it (the other lanes wait), then the proof's lanes fold a, b to length 2n and update gg, hh in parallel.
-// Three proofs share a 256-lane block (66 lanes each: 33 terms a side), 77 % of the lanes doing scalar multiplications instead of
-// the 52 % of one proof per 128 lanes.  A term can be SPLIT over TAIL_SPLIT lanes, each taking a share of the table's pieces (a shorter
-// chain per lane, the doublings paid once per share): with two shares measured 52.2 instead of 50.2 ms per batch -- the tail is bound
-// by its work like everything else, not by its chain -- and TWO terms per lane on one doubling chain (-DBBP_TAIL_MERGE=2: 13 % less work,
-// a 74 % longer chain) 53.8 instead of 49.3 ms: one lane per term is the optimum from both sides.
-#ifndef BBP_TAIL_SPLIT
-#define BBP_TAIL_SPLIT 1
-#endif
-#ifndef BBP_TAIL_MERGE  // 2: a lane takes TWO terms of its side and runs one doubling chain for both (17 lanes a side, seven proofs per block)
-#define BBP_TAIL_MERGE 1
-#endif
-#ifndef BBP_TAIL_BLK
-#define BBP_TAIL_BLK (BBP_TAIL_SPLIT == 1 ? 256 : 320)
-#endif
-constexpr int TAIL_SPLIT = BBP_TAIL_SPLIT, TAIL_MERGE = BBP_TAIL_MERGE, TAIL_LS = TAIL_MERGE == 2 ? 17 : 33 * TAIL_SPLIT, TAIL_BLK = BBP_TAIL_BLK, TAIL_LP = 2 * TAIL_LS, TAIL_PPB = TAIL_BLK / TAIL_LP;
-static_assert(TAIL_PIECES % TAIL_SPLIT == 0 && TAIL_PPB >= 1 && (TAIL_MERGE == 1 || (TAIL_MERGE == 2 && TAIL_SPLIT == 1)), "tail kernel geometry");
+// ONE WAVEFRONT per proof, in a workgroup of its own: lanes 0..31 are the G/H terms of L, lanes 32..63 those of R (scalarmul.h
+// TAIL_SIDE), and the B term rides along -- the 64 digits of c w are dealt to the side's lanes, two each (scalarmul.h tail_share), so
+// no lane and no wavefront exists for the 33rd term.  A side is summed by five shuffle steps: no staging array, no barrier of the kernel's own.
+// With `prev_round` != 0 the wavefront first finishes the previous round: all lanes absorb L, R of that round in lockstep and draw u
+// (the wavefront form of the permutation, keccak_wave.h), lane 0 inverts it, then the lanes fold a, b to length 2n and update gg, hh.
+// (Before: three proofs to a 256-lane block, 66 lanes each -- four wavefronts for three proofs, the fourth with 6 live lanes on the
+// whole chain, 40 KB of LDS for the tree sums, and all four waiting at a barrier for the one-lane challenge.  Measured out earlier,
+// a term split over two lanes, and two terms per lane on one doubling chain.)
+__device__ __forceinline__ sc sc_shfl(const sc& s, int src) {
+    sc r;
+#pragma unroll
+    for (int w = 0; w < 8; w++) r.v[w] = (u32)__shfl((int)s.v[w], src, 64);
+    return r;
+}
+__device__ __forceinline__ sc sc_shfl_xor(const sc& s, int mask) {
+    sc r;
+#pragma unroll
+    for (int w = 0; w < 8; w++) r.v[w] = (u32)__shfl_xor((int)s.v[w], mask, 64);
+    return r;
+}
+constexpr int TAIL_BLK = 2 * TAIL_SIDE;
+static_assert(TAIL_BLK == 64 && TAIL_SIDE == FOLD_CLS, "k_tail_lr: one wavefront per proof, one lane per (side, G/H term)");
 __global__ __launch_bounds__(TAIL_BLK) void k_tail_lr(u32 B, u32 n, u32 prev_round, u32 m, const u32* __restrict__ enc, merlin_transcript* __restrict__ tr,
                                                        const sc* __restrict__ misc, sc* __restrict__ a_all, sc* __restrict__ b_all,
                                                        sc* __restrict__ g_all, sc* __restrict__ h_all, const ge* __restrict__ ftab,
                                                        const ge* __restrict__ btab, ge* __restrict__ lrpts) {
     BBP_THIN_PRIO();
-    __shared__ u32 stage[GE_WORDS * TAIL_BLK];
-    __shared__ u32 uu_w[TAIL_PPB * 2 * 8];
-    const u32 tid = threadIdx.x;
-    const u32 pj = tid / TAIL_LP, l = tid % TAIL_LP;        // proof slot in the block, lane within the proof
-    const u32 p = blockIdx.x * TAIL_PPB + pj;
-    const bool live = pj < TAIL_PPB && p < B;
-    const u32 side = l / TAIL_LS, rem = l % TAIL_LS;        // lane `rem` of its side: share rem % TAIL_SPLIT of term j
-    const u32 j = TAIL_MERGE == 2 ? 2 * rem : rem / TAIL_SPLIT, share = rem % TAIL_SPLIT;  // j: 0..15 G terms, 16..31 H terms, 32 the B term (merged: terms j and j + 1)
-    const size_t po = live ? (size_t)p : 0;
-    sc *a = a_all + po * IPA_N, *b = b_all + po * IPA_N, *gg = g_all + po * IPA_N, *hh = h_all + po * IPA_N;
+    const u32 p = blockIdx.x, l = threadIdx.x;
+    if (p >= B) return;
+    const u32 side = l / TAIL_SIDE, j = l % TAIL_SIDE;     // j: 0..15 G terms, 16..31 H terms of the side
+    sc *a = a_all + (size_t)p * IPA_N, *b = b_all + (size_t)p * IPA_N, *gg = g_all + (size_t)p * IPA_N, *hh = h_all + (size_t)p * IPA_N;
     if (prev_round) {
-        if (live && l == 0) {
-            merlin_transcript t = tr[p];
-            const u32* e = enc + (size_t)p * enc_words(m) + enc_LR(m, prev_round);
-            tr_append_words(t, LBL("L"), e);
-            tr_append_words(t, LBL("R"), e + 8);
-            const sc u = tr_challenge_sc(t, LBL("u")), ui = sc_invert(u);
-#pragma unroll
-            for (int w = 0; w < 8; w++) {
-                uu_w[(pj * 2) * 8 + w] = u.v[w];
-                uu_w[(pj * 2 + 1) * 8 + w] = ui.v[w];
-            }
+        merlin_transcript t = tr[p];
+        t.wave = 1;  // every lane holds the transcript (keccak_wave.h keccak_f1600_wave: the workgroup is exactly one wavefront)
+        const u32* e = enc + (size_t)p * enc_words(m) + enc_LR(m, prev_round);
+        tr_append_words(t, LBL("L"), e);
+        tr_append_words(t, LBL("R"), e + 8);
+        const sc u = tr_challenge_sc(t, LBL("u"));
+        sc ui = sc_zero();
+        if (l == 0) {
+            ui = sc_invert(u);
+            t.wave = 0;  // (memory never holds the flag: every kernel sets it for itself)
             tr[p] = t;
         }
-        __syncthreads();
-        if (live) {
-            sc u, ui;
-#pragma unroll
-            for (int w = 0; w < 8; w++) {
-                u.v[w] = uu_w[(pj * 2) * 8 + w];
-                ui.v[w] = uu_w[(pj * 2 + 1) * 8 + w];
-            }
-            const u32 n2 = 2 * n;
-            // work items of one proof: n2 folds of a, n2 folds of b, 32 factors gg, 32 factors hh
-            for (u32 w = l; w < 2 * n2 + 2 * FOLD_CLS; w += TAIL_LP) {
-                if (w < n2) {
-                    st_sc(&a[w], sc_add(sc_mul(ld_sc(&a[w]), u), sc_mul(ui, ld_sc(&a[n2 + w]))));
-                } else if (w < 2 * n2) {
-                    const u32 i = w - n2;
-                    st_sc(&b[i], sc_add(sc_mul(ld_sc(&b[i]), ui), sc_mul(u, ld_sc(&b[n2 + i]))));
-                } else {
-                    const u32 k = (w - 2 * n2) % FOLD_CLS;
-                    const bool hi = (k & (2 * n2 - 1)) >= n2;
-                    if (w - 2 * n2 < FOLD_CLS) st_sc(&gg[k], sc_mul(ld_sc(&gg[k]), hi ? u : ui));
-                    else st_sc(&hh[k], sc_mul(ld_sc(&hh[k]), hi ? ui : u));
-                }
+        ui = sc_shfl(ui, 0);
+        const u32 n2 = 2 * n;
+        // work items of one proof: n2 folds of a, n2 folds of b, 32 factors gg, 32 factors hh
+        for (u32 w = l; w < 2 * n2 + 2 * FOLD_CLS; w += TAIL_BLK) {
+            if (w < n2) {
+                st_sc(&a[w], sc_add(sc_mul(ld_sc(&a[w]), u), sc_mul(ui, ld_sc(&a[n2 + w]))));
+            } else if (w < 2 * n2) {
+                const u32 i = w - n2;
+                st_sc(&b[i], sc_add(sc_mul(ld_sc(&b[i]), ui), sc_mul(u, ld_sc(&b[n2 + i]))));
+            } else {
+                const u32 k = (w - 2 * n2) % FOLD_CLS;
+                const bool hi = (k & (2 * n2 - 1)) >= n2;
+                if (w - 2 * n2 < FOLD_CLS) st_sc(&gg[k], sc_mul(ld_sc(&gg[k]), hi ? u : ui));
+                else st_sc(&hh[k], sc_mul(ld_sc(&hh[k]), hi ? ui : u));
             }
         }
-        __threadfence_block();
-        __syncthreads();
+        __threadfence_block();  // the lanes below read what other lanes of this wavefront stored above
+        __builtin_amdgcn_wave_barrier();
     }
-    const ge *FG = ftab + po * 2 * FOLD_CLS * TAIL_TAB, *FH = FG + (size_t)FOLD_CLS * TAIL_TAB;  // tables of F_G[32], F_H[32]
+    const ge *FG = ftab + (size_t)p * 2 * FOLD_CLS * TAIL_TAB, *FH = FG + (size_t)FOLD_CLS * TAIL_TAB;  // tables of F_G[32], F_H[32]
     constexpr u32 HALF = FOLD_CLS / 2;  // 16 G-terms and 16 H-terms per side
-    // scalar and table of term jt of this lane's side
-    auto term = [&](u32 jt, sc& s, const ge*& T) {
-        if (jt < 2 * HALF) {
-            const u32 rank = jt % HALF, blk = rank / n, io = rank % n;
-            const u32 k_lo = blk * 2 * n + io, k_hi = k_lo + n;
-            if (jt < HALF) {  // G term
-                const u32 k = side == 0 ? k_hi : k_lo;
-                s = sc_mul(ld_sc(&a[side == 0 ? io : n + io]), ld_sc(&gg[k]));
-                T = FG + (size_t)k * TAIL_TAB;
-            } else {  // H term
-                const u32 k = side == 0 ? k_lo : k_hi;
-                s = sc_mul(ld_sc(&b[side == 0 ? n + io : io]), ld_sc(&hh[k]));
-                T = FH + (size_t)k * TAIL_TAB;
-            }
-        } else {
-            sc c = sc_zero();
-            for (u32 i = 0; i < n; i++)
-                c = sc_add(c, side == 0 ? sc_mul(ld_sc(&a[i]), ld_sc(&b[n + i])) : sc_mul(ld_sc(&a[n + i]), ld_sc(&b[i])));
-            s = sc_mul(c, ld_sc(&misc[(size_t)p * MS_COUNT + MS_W]));  // Q = w B
-            T = btab;
+    // scalar and table of this lane's term
+    sc s;
+    const ge* T;
+    {
+        const u32 rank = j % HALF, blk = rank / n, io = rank % n;
+        const u32 k_lo = blk * 2 * n + io, k_hi = k_lo + n;
+        if (j < HALF) {  // G term
+            const u32 k = side == 0 ? k_hi : k_lo;
+            s = sc_mul(ld_sc(&a[side == 0 ? io : n + io]), ld_sc(&gg[k]));
+            T = FG + (size_t)k * TAIL_TAB;
+        } else {  // H term
+            const u32 k = side == 0 ? k_lo : k_hi;
+            s = sc_mul(ld_sc(&b[side == 0 ? n + io : io]), ld_sc(&hh[k]));
+            T = FH + (size_t)k * TAIL_TAB;
         }
-    };
-    ge q = ge_identity();
-    if (live) {
-        sc s;
-        const ge* T;
-        term(j, s, T);
+    }
+    // the B term's scalar c w of this side (Q = w B): lane i < n of the side takes one product of c, an exchange tree inside the
+    // side's 32 lanes leaves the sum in all of them
+    sc c = sc_zero();
+    if (j < n) c = side == 0 ? sc_mul(ld_sc(&a[j]), ld_sc(&b[n + j])) : sc_mul(ld_sc(&a[n + j]), ld_sc(&b[j]));
+#pragma unroll 1
+    for (int d = TAIL_SIDE / 2; d >= 1; d >>= 1) c = sc_add(c, sc_shfl_xor(c, d));
+    const sc sB = sc_mul(c, ld_sc(&misc[(size_t)p * MS_COUNT + MS_W]));
 #ifndef BBP_KO_TAIL  // (timing experiment, wrong results, when defined)
-        if (TAIL_MERGE == 2 && j + 1 < 2 * HALF + 1) {
-            sc s2;
-            const ge* T2;
-            term(j + 1, s2, T2);
-            q = ge_scalarmul_pieces_pair(s, T, s2, T2);
-        } else {
-            constexpr int PPS = TAIL_PIECES / TAIL_SPLIT;
-            q = ge_scalarmul_pieces(s, T, (int)share * PPS, (int)share * PPS + PPS);
-        }
+    ge q = ge_scalarmul_pieces_shared(s, T, tail_share_of(sB, j), btab);
 #else
-        q = T[0];
-        q.X.v[0] += (i32)(s.v[0] & 1u);
+    ge q = T[0];
+    q.X.v[0] += (i32)((s.v[0] ^ sB.v[0]) & 1u);
 #endif
-    }
-    const u32* w = reinterpret_cast<const u32*>(&q);
-    for (int k = 0; k < GE_WORDS; k++) stage[k * TAIL_BLK + tid] = w[k];
-    __syncthreads();
-    // tree sum inside each group of TAIL_LS consecutive lanes (one group per proof and side)
-    for (int d = 64; d >= 1; d >>= 1) {
-        if (live && rem < (u32)d && rem + d < (u32)TAIL_LS) {
-            ge o;
-            u32* ow = reinterpret_cast<u32*>(&o);
-            for (int k = 0; k < GE_WORDS; k++) ow[k] = stage[k * TAIL_BLK + tid + d];
-            q = ge_add(q, o);
-            for (int k = 0; k < GE_WORDS; k++) stage[k * TAIL_BLK + tid] = reinterpret_cast<const u32*>(&q)[k];
-        }
-        __syncthreads();
-    }
-    if (live && rem == 0) lrpts[(size_t)p * 2 + side] = q;
+    q = tail_side_sum(q);
+    if (j == 0) lrpts[(size_t)p * 2 + side] = q;
 }
 
 __global__ BBP_LANE_KERNEL void k_ipa_final(u32 B, u32 m, const u32* __restrict__ enc, merlin_transcript* __restrict__ tr, sc* __restrict__ misc,
@@ -1415,7 +1378,7 @@ static int32_t prove_heavy(bbp_ctx* ctx, const HeavyPlan& hp, const CircuitDev& 
         LAUNCH(ctx, TAG_VARBASE, k_tail_tables, cdiv(B * 2 * FOLD_CLS, 64), 64, s, B * 2 * FOLD_CLS, bd.fpts, ftab);
         for (u32 r = tail_from; r <= IPA_ROUNDS; r++) {
             const u32 n = IPA_HALF >> (r - 1);
-            LAUNCH(ctx, TAG_VARBASE, k_tail_lr, cdiv(B, TAIL_PPB), TAIL_BLK, s, B, n, r > tail_from ? r - 1 : 0u, m, bd.enc, bd.tr, bd.misc, bd.a, bd.b, bd.g, bd.h, ftab,
+            LAUNCH(ctx, TAG_VARBASE, k_tail_lr, B, TAIL_BLK, s, B, n, r > tail_from ? r - 1 : 0u, m, bd.enc, bd.tr, bd.misc, bd.a, bd.b, bd.g, bd.h, ftab,
                    ctx->btab, bd.lrpts);
             LAUNCH(ctx, TAG_ENCODE, k_encode_strided, cdiv(2 * B, 64), 64, s, 2 * B, 2u, bd.lrpts, st.lrpts, bd.enc, st.enc, enc_LR(m, r), 1u);
         }

@@ -195,7 +195,7 @@ BBP_HD ge ge_scalarmul_pieces(const sc& s, const ge* __restrict__ T, int k_lo = 
     return acc;
 }
 
-// s1 * P1 + s2 * P2 over tail tables T1, T2 with ONE doubling chain (the merged form of k_tail_lr: two terms per lane)
+// s1 * P1 + s2 * P2 over tail tables T1, T2 with ONE doubling chain (two terms per lane: measured out of k_tail_lr)
 BBP_HD ge ge_scalarmul_pieces_pair(const sc& s1, const ge* __restrict__ T1, const sc& s2, const ge* __restrict__ T2) {
     u64 cm1 = 0, cm2 = 0;
     u32 c1 = 0, c2 = 0;
@@ -233,6 +233,95 @@ BBP_HD ge ge_scalarmul_pieces_pair(const sc& s1, const ge* __restrict__ T1, cons
     }
     return acc;
 }
+
+// k_tail_lr puts one side of a proof (L or R) on TAIL_SIDE lanes: lane j walks G/H term j, and the B term sB * B has no lane of its
+// own -- btab has the geometry of every other table, so the TAIL_PIECES x TAIL_DIGITS signed digits of sB are dealt to the side's
+// lanes, TAIL_SHARE_DIGITS each: lane j takes piece j % TAIL_PIECES, digits r0 .. r0 + TAIL_SHARE_DIGITS - 1 with
+// r0 = TAIL_SHARE_DIGITS * (j / TAIL_PIECES).  A lane adds its share into its own accumulator in the iteration that handles digit r
+// (every lane's doubling chain passes through every r, so the weight 16^r * 2^(w k) comes out right); the side's sum is then
+// sum_j s_j P_j + sB B.
+constexpr int TAIL_SIDE = 32, TAIL_SHARE_DIGITS = TAIL_PIECES * TAIL_DIGITS / TAIL_SIDE;
+static_assert(TAIL_SHARE_DIGITS >= 1 && TAIL_SHARE_DIGITS * TAIL_SIDE == TAIL_PIECES * TAIL_DIGITS && TAIL_DIGITS % TAIL_SHARE_DIGITS == 0 &&
+                  (TAIL_DIGITS / TAIL_SHARE_DIGITS) * TAIL_PIECES == TAIL_SIDE,
+              "the shares of the B term tile its digits: every (piece, digit) belongs to exactly one lane of the side");
+
+// carry mask of the signed radix-16 recoding (carry form): bit j = carry INTO digit j (a canonical scalar never carries out of digit 63)
+BBP_HD u64 tail_carry_mask(const sc& s) {
+    u64 cm = 0;
+    u32 c = 0;
+    for (int j = 0; j < 64; j++) {
+        u32 v = ((s.v[j >> 3] >> (4 * (j & 7))) & 15u) + c;
+        c = v > 8u;
+        if (j < 63) cm |= (u64)c << (j + 1);
+    }
+    return cm;
+}
+// digit j of s, in [-7, 8]
+BBP_HD int tail_digit(const sc& s, u64 cm, int j) {
+    u32 word = s.v[0];  // (selects, not an indexed read: the scalar stays in registers when j is not known at compile time)
+#pragma unroll
+    for (int w = 1; w < 8; w++) word = (j >> 3) == w ? s.v[w] : word;
+    return (int)((word >> (4 * (j & 7))) & 15u) +(int)((cm >> j) & 1u) - 16 * (int)((j < 63) ? ((cm >> (j + 1)) & 1u) : 0u);
+}
+
+struct tail_share {
+    int k, r0;                  // piece, first digit position within the piece
+    int d[TAIL_SHARE_DIGITS];   // digits r0, r0 + 1, .. of piece k
+};
+BBP_HD tail_share tail_share_of(const sc& sB, u32 lane /* of the side, < TAIL_SIDE */) {
+    const u64 cm = tail_carry_mask(sB);
+    tail_share sh;
+    sh.k = (int)(lane % TAIL_PIECES);
+    sh.r0 = TAIL_SHARE_DIGITS * (int)(lane / TAIL_PIECES);
+    for (int i = 0; i < TAIL_SHARE_DIGITS; i++) sh.d[i] = tail_digit(sB, cm, TAIL_DIGITS * sh.k + sh.r0 + i);
+    return sh;
+}
+
+// s * P over P's table T, plus the share `sh` of the B term over B's table TB: ge_scalarmul_pieces with one more slot per digit
+// position, taken by the lanes whose share holds that position.  ONE addition site for the table's pieces and the share.
+BBP_HD ge ge_scalarmul_pieces_shared(const sc& s, const ge* __restrict__ T, const tail_share& sh, const ge* __restrict__ TB) {
+    const u64 cm = tail_carry_mask(s);
+    ge acc = ge_identity();
+    for (int r = TAIL_DIGITS - 1; r >= 0; r--) {
+        if (r != TAIL_DIGITS - 1) {
+            acc = ge_dbl(acc);
+            acc = ge_dbl(acc);
+            acc = ge_dbl(acc);
+            acc = ge_dbl(acc);
+        }
+        const int i = r - sh.r0;
+        const bool mine = i >= 0 && i < TAIL_SHARE_DIGITS;
+        int dB = 0;
+        for (int q = 0; q < TAIL_SHARE_DIGITS; q++) dB = q == i ? sh.d[q] : dB;
+#pragma unroll 1
+        for (int kk = 0; kk < TAIL_PIECES + 1; kk++) {  // pieces 0 .. TAIL_PIECES - 1 of s, then the share's digit
+            const bool own = kk < TAIL_PIECES;
+            if (!own && !mine) break;
+            const int k = own ? kk : sh.k;
+            const int d = own ? tail_digit(s, cm, TAIL_DIGITS * k + r) : dB;
+            if (d != 0) {
+                ge q = (own ? T : TB)[8 * k + (d > 0 ? d : -d) - 1];
+                if (d < 0) q = ge_neg(q);
+                acc = ge_add(acc, q);
+            }
+        }
+    }
+    return acc;
+}
+#if defined(__HIPCC__)
+__device__ __forceinline__ ge tail_side_sum(ge acc) {  // the first lane of each TAIL_SIDE-lane half of the wavefront ends up with the half's sum
+#pragma unroll 1
+    for (int d = TAIL_SIDE / 2; d >= 1; d >>= 1) {
+        ge other;
+        const u32* w = reinterpret_cast<const u32*>(&acc);
+        u32* o = reinterpret_cast<u32*>(&other);
+#pragma unroll
+        for (int i = 0; i < (int)(sizeof(ge) / 4); i++) o[i] = (u32)__shfl_down((int)w[i], d, TAIL_SIDE);
+        acc = ge_add(acc, other);  // (lanes whose partner lies past the half add something nobody reads)
+    }
+    return acc;
+}
+#endif
 
 // ---------------------------------------------------------------------------------------------------------------
 // K9: the data-dependent steps of the verifier's Straus sums (each kernel keeps its own loops over points, digits and lanes)
