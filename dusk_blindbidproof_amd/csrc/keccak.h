@@ -11,8 +11,8 @@
 namespace bbp {
 
 // 64-bit rotate left.  On the device a rotation by a constant is two v_alignbit_b32 (the compiler's own lowering of the shift /
-// or form costs three instructions: 64-bit shift, 32-bit shift, or) -- 27 of the ~300 instructions of a Keccak round, and the
-// prover's 2935-permutation rng chain runs at exactly the single-wave issue limit.
+// or form costs three instructions: 64-bit shift, 32-bit shift, or) -- 29 rotations, 58 of the 180 vector instructions of a Keccak
+// round (keccak_f1600_body below), and the prover's 2935-permutation rng chain runs at exactly the single-wave issue limit.
 // n is taken mod 64 and a rotation by 0 returns x: v_alignbit_b32 reads its shift mod 32, so s = 32 would select b and swap the
 // halves, and the host's x >> 64 is undefined.  For the literal amounts of keccak_f1600_body both checks fold away.
 BBP_HD u64 rotl64(u64 x, int n) {
@@ -30,6 +30,30 @@ BBP_HD u64 rotl64(u64 x, int n) {
 #endif
 }
 
+// The two Boolean steps of a round on three 64-bit lanes.  gfx950 has v_bitop3_b32 (any function of three inputs, result bit =
+// table[(s0 << 2) | (s1 << 1) | s2] per bit position): one instruction per 32-bit half where plain ^ ~ & compile to two (v_xor_b32
+// twice, or v_bfi_b32 + v_xor_b32), and the one-lane chain's time is its instruction count.  Tables as in keccak_wave.h's BBP_KW_ROUND.
+#define BBP_BITOP3_XOR3 0x96  // s0 ^ s1 ^ s2
+#define BBP_BITOP3_CHI 0xd2   // s0 ^ (~s1 & s2)
+BBP_HD u64 keccak_xor3(u64 a, u64 b, u64 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const u32 lo = __builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, BBP_BITOP3_XOR3);
+    const u32 hi = __builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), BBP_BITOP3_XOR3);
+    return ((u64)hi << 32) | lo;
+#else
+    return a ^ b ^ c;
+#endif
+}
+BBP_HD u64 keccak_chi(u64 a, u64 b, u64 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const u32 lo = __builtin_amdgcn_bitop3_b32((u32)a, (u32)b, (u32)c, BBP_BITOP3_CHI);
+    const u32 hi = __builtin_amdgcn_bitop3_b32((u32)(a >> 32), (u32)(b >> 32), (u32)(c >> 32), BBP_BITOP3_CHI);
+    return ((u64)hi << 32) | lo;
+#else
+    return a ^ (~b & c);
+#endif
+}
+
 // forceinline body: with `s` a local array indexed statically the 25 lanes live in registers across calls
 BBP_HD void keccak_f1600_body(u64* s) {
     const u64 RC[24] = {0x0000000000000001ull, 0x0000000000008082ull, 0x800000000000808Aull, 0x8000000080008000ull,
@@ -44,19 +68,18 @@ BBP_HD void keccak_f1600_body(u64* s) {
     u64 a15 = s[15], a16 = s[16], a17 = s[17], a18 = s[18], a19 = s[19];
     u64 a20 = s[20], a21 = s[21], a22 = s[22], a23 = s[23], a24 = s[24];
     for (int r = 0; r < 24; r++) {
-        // theta
-        u64 c0 = a00 ^ a05 ^ a10 ^ a15 ^ a20;
-        u64 c1 = a01 ^ a06 ^ a11 ^ a16 ^ a21;
-        u64 c2 = a02 ^ a07 ^ a12 ^ a17 ^ a22;
-        u64 c3 = a03 ^ a08 ^ a13 ^ a18 ^ a23;
-        u64 c4 = a04 ^ a09 ^ a14 ^ a19 ^ a24;
-        u64 d0 = c4 ^ rotl64(c1, 1), d1 = c0 ^ rotl64(c2, 1), d2 = c1 ^ rotl64(c3, 1);
-        u64 d3 = c2 ^ rotl64(c4, 1), d4 = c3 ^ rotl64(c0, 1);
-        a00 ^= d0; a05 ^= d0; a10 ^= d0; a15 ^= d0; a20 ^= d0;
-        a01 ^= d1; a06 ^= d1; a11 ^= d1; a16 ^= d1; a21 ^= d1;
-        a02 ^= d2; a07 ^= d2; a12 ^= d2; a17 ^= d2; a22 ^= d2;
-        a03 ^= d3; a08 ^= d3; a13 ^= d3; a18 ^= d3; a23 ^= d3;
-        a04 ^= d4; a09 ^= d4; a14 ^= d4; a19 ^= d4; a24 ^= d4;
+        // theta: column parities, then a ^= c[x - 1] ^ rot(c[x + 1], 1) in one step (d is never formed)
+        const u64 c0 = keccak_xor3(keccak_xor3(a00, a05, a10), a15, a20);
+        const u64 c1 = keccak_xor3(keccak_xor3(a01, a06, a11), a16, a21);
+        const u64 c2 = keccak_xor3(keccak_xor3(a02, a07, a12), a17, a22);
+        const u64 c3 = keccak_xor3(keccak_xor3(a03, a08, a13), a18, a23);
+        const u64 c4 = keccak_xor3(keccak_xor3(a04, a09, a14), a19, a24);
+        const u64 r0 = rotl64(c0, 1), r1 = rotl64(c1, 1), r2 = rotl64(c2, 1), r3 = rotl64(c3, 1), r4 = rotl64(c4, 1);
+        a00 = keccak_xor3(a00, c4, r1); a05 = keccak_xor3(a05, c4, r1); a10 = keccak_xor3(a10, c4, r1); a15 = keccak_xor3(a15, c4, r1); a20 = keccak_xor3(a20, c4, r1);
+        a01 = keccak_xor3(a01, c0, r2); a06 = keccak_xor3(a06, c0, r2); a11 = keccak_xor3(a11, c0, r2); a16 = keccak_xor3(a16, c0, r2); a21 = keccak_xor3(a21, c0, r2);
+        a02 = keccak_xor3(a02, c1, r3); a07 = keccak_xor3(a07, c1, r3); a12 = keccak_xor3(a12, c1, r3); a17 = keccak_xor3(a17, c1, r3); a22 = keccak_xor3(a22, c1, r3);
+        a03 = keccak_xor3(a03, c2, r4); a08 = keccak_xor3(a08, c2, r4); a13 = keccak_xor3(a13, c2, r4); a18 = keccak_xor3(a18, c2, r4); a23 = keccak_xor3(a23, c2, r4);
+        a04 = keccak_xor3(a04, c3, r0); a09 = keccak_xor3(a09, c3, r0); a14 = keccak_xor3(a14, c3, r0); a19 = keccak_xor3(a19, c3, r0); a24 = keccak_xor3(a24, c3, r0);
         // rho + pi : B[y][2x+3y] = rot(A[x][y])
         u64 b00 = a00;
         u64 b10 = rotl64(a01, 1), b20 = rotl64(a02, 62), b05 = rotl64(a03, 28), b15 = rotl64(a04, 27);
@@ -65,11 +88,11 @@ BBP_HD void keccak_f1600_body(u64* s) {
         u64 b23 = rotl64(a15, 41), b08 = rotl64(a16, 45), b18 = rotl64(a17, 15), b03 = rotl64(a18, 21), b13 = rotl64(a19, 8);
         u64 b14 = rotl64(a20, 18), b24 = rotl64(a21, 2), b09 = rotl64(a22, 61), b19 = rotl64(a23, 56), b04 = rotl64(a24, 14);
         // chi
-        a00 = b00 ^ (~b01 & b02); a01 = b01 ^ (~b02 & b03); a02 = b02 ^ (~b03 & b04); a03 = b03 ^ (~b04 & b00); a04 = b04 ^ (~b00 & b01);
-        a05 = b05 ^ (~b06 & b07); a06 = b06 ^ (~b07 & b08); a07 = b07 ^ (~b08 & b09); a08 = b08 ^ (~b09 & b05); a09 = b09 ^ (~b05 & b06);
-        a10 = b10 ^ (~b11 & b12); a11 = b11 ^ (~b12 & b13); a12 = b12 ^ (~b13 & b14); a13 = b13 ^ (~b14 & b10); a14 = b14 ^ (~b10 & b11);
-        a15 = b15 ^ (~b16 & b17); a16 = b16 ^ (~b17 & b18); a17 = b17 ^ (~b18 & b19); a18 = b18 ^ (~b19 & b15); a19 = b19 ^ (~b15 & b16);
-        a20 = b20 ^ (~b21 & b22); a21 = b21 ^ (~b22 & b23); a22 = b22 ^ (~b23 & b24); a23 = b23 ^ (~b24 & b20); a24 = b24 ^ (~b20 & b21);
+        a00 = keccak_chi(b00, b01, b02); a01 = keccak_chi(b01, b02, b03); a02 = keccak_chi(b02, b03, b04); a03 = keccak_chi(b03, b04, b00); a04 = keccak_chi(b04, b00, b01);
+        a05 = keccak_chi(b05, b06, b07); a06 = keccak_chi(b06, b07, b08); a07 = keccak_chi(b07, b08, b09); a08 = keccak_chi(b08, b09, b05); a09 = keccak_chi(b09, b05, b06);
+        a10 = keccak_chi(b10, b11, b12); a11 = keccak_chi(b11, b12, b13); a12 = keccak_chi(b12, b13, b14); a13 = keccak_chi(b13, b14, b10); a14 = keccak_chi(b14, b10, b11);
+        a15 = keccak_chi(b15, b16, b17); a16 = keccak_chi(b16, b17, b18); a17 = keccak_chi(b17, b18, b19); a18 = keccak_chi(b18, b19, b15); a19 = keccak_chi(b19, b15, b16);
+        a20 = keccak_chi(b20, b21, b22); a21 = keccak_chi(b21, b22, b23); a22 = keccak_chi(b22, b23, b24); a23 = keccak_chi(b23, b24, b20); a24 = keccak_chi(b24, b20, b21);
         a00 ^= RC[r];
     }
     s[0] = a00; s[1] = a01; s[2] = a02; s[3] = a03; s[4] = a04;
