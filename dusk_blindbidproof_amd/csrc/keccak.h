@@ -285,4 +285,189 @@ BBP_HD bool merlin_rng_fill64_bulk(merlin_transcript& t, u32 count, u32* out_wor
     return true;
 }
 
+// ---- pair form: half a state per lane ---------------------------------------------------------------
+// The only operations of Keccak-f[1600] that mix the two 32-bit halves of a 64-bit lane are its 29 rotations per round (theta: 5 by 1;
+// rho: 24, none by 0 or 32); theta's XORs, chi and iota are bitwise.  Two adjacent GPU lanes share a state: the even one holds the 25 low
+// words, the odd one the 25 high words.  Each then runs 60 three-input operations per round instead of 120, and per rotation one partner
+// fetch (a DPP move inside the quad, no LDS) plus ONE v_alignbit_b32, the same instruction in both lanes:
+//   rotl by r < 32:  own' = alignbit(own, partner, 32 - r)        rotl by r > 32:  own' = alignbit(partner, own, 64 - r)
+// A round is three phases between two partner reads (the column parities; the 24 words rho rotates), so the same phase functions serve
+// the device, where the read is keccak_pair_partner, and the host model, which keeps a pair as two arrays of 25 words and reads the
+// other array (keccak_f1600_pair_model: what the CPU tier checks the split with).
+BBP_HD u32 keccak_alignbit(u32 a, u32 b, u32 s) {  // low word of {a:b} >> s, 0 < s < 32
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_alignbit(a, b, s);
+#else
+    return (u32)(((((u64)a) << 32) | b) >> s);
+#endif
+}
+BBP_HD u32 keccak_xor3_32(u32 a, u32 b, u32 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, BBP_BITOP3_XOR3);
+#else
+    return (u32)keccak_xor3(a, b, c);
+#endif
+}
+BBP_HD u32 keccak_chi_32(u32 a, u32 b, u32 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, BBP_BITOP3_CHI);
+#else
+    return (u32)keccak_chi(a, b, c);
+#endif
+}
+#define BBP_PAIR_IOTA_TABLE 0x78  // s0 ^ (s1 & s2)
+BBP_HD u32 keccak_xorand_32(u32 a, u32 b, u32 c) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_bitop3_b32(a, b, c, BBP_PAIR_IOTA_TABLE);
+#else
+    return a ^ (b & c);
+#endif
+}
+// this half of rotl64 by the literal r (not 0, not 32): `own` and `partner` are the two halves of the word
+BBP_HD u32 keccak_pair_rotl(u32 own, u32 partner, int r) { return r < 32 ? keccak_alignbit(own, partner, 32u - (u32)r) : keccak_alignbit(partner, own, 64u - (u32)r); }
+
+// phase 1: the five column parities of this half
+BBP_HD void keccak_pair_parity(const u32* a, u32* c) {
+#pragma unroll
+    for (int x = 0; x < 5; x++) c[x] = keccak_xor3_32(keccak_xor3_32(a[x], a[x + 5], a[x + 10]), a[x + 15], a[x + 20]);
+}
+// phase 2: a[x + 5y] ^= c[x - 1] ^ rotl(C[x + 1], 1); pc = the partner's parities
+BBP_HD void keccak_pair_theta(u32* a, const u32* c, const u32* pc) {
+#pragma unroll
+    for (int x = 0; x < 5; x++) {
+        const u32 cm = c[(x + 4) % 5], rp = keccak_pair_rotl(c[(x + 1) % 5], pc[(x + 1) % 5], 1);
+#pragma unroll
+        for (int y = 0; y < 5; y++) a[x + 5 * y] = keccak_xor3_32(a[x + 5 * y], cm, rp);
+    }
+}
+// phase 3: rho + pi + chi; pa[1..24] = the partner's halves of the words that rho rotates (pa[0] is not read)
+BBP_HD void keccak_pair_rho_pi_chi(u32* a, const u32* pa) {
+    u32 b[25];
+    b[0] = a[0];
+#define BBP_KP_RHO(dst, src, r) b[dst] = keccak_pair_rotl(a[src], pa[src], r)
+    BBP_KP_RHO(10, 1, 1); BBP_KP_RHO(20, 2, 62); BBP_KP_RHO(5, 3, 28); BBP_KP_RHO(15, 4, 27);
+    BBP_KP_RHO(16, 5, 36); BBP_KP_RHO(1, 6, 44); BBP_KP_RHO(11, 7, 6); BBP_KP_RHO(21, 8, 55); BBP_KP_RHO(6, 9, 20);
+    BBP_KP_RHO(7, 10, 3); BBP_KP_RHO(17, 11, 10); BBP_KP_RHO(2, 12, 43); BBP_KP_RHO(12, 13, 25); BBP_KP_RHO(22, 14, 39);
+    BBP_KP_RHO(23, 15, 41); BBP_KP_RHO(8, 16, 45); BBP_KP_RHO(18, 17, 15); BBP_KP_RHO(3, 18, 21); BBP_KP_RHO(13, 19, 8);
+    BBP_KP_RHO(14, 20, 18); BBP_KP_RHO(24, 21, 2); BBP_KP_RHO(9, 22, 61); BBP_KP_RHO(19, 23, 56); BBP_KP_RHO(4, 24, 14);
+#undef BBP_KP_RHO
+#pragma unroll
+    for (int y = 0; y < 25; y += 5) {
+#pragma unroll
+        for (int x = 0; x < 5; x++) a[y + x] = keccak_chi_32(b[y + x], b[y + (x + 1) % 5], b[y + (x + 2) % 5]);
+    }
+}
+// iota.  Round constants as (low word, low ^ high): with sel = 0 in the low-word lane and ~0 in the high-word lane, the lane's constant
+// is low ^ (sel & (low ^ high)) -- chosen by parity once per round in two operations, no select
+BBP_HD void keccak_pair_iota(u32* a, u32 sel, int r) {
+#define BBP_KP_RC(hi, lo) (((u64)((hi) ^ (lo)) << 32) | (lo))
+    const u64 RC[24] = {BBP_KP_RC(0x00000000u, 0x00000001u), BBP_KP_RC(0x00000000u, 0x00008082u), BBP_KP_RC(0x80000000u, 0x0000808Au),
+                        BBP_KP_RC(0x80000000u, 0x80008000u), BBP_KP_RC(0x00000000u, 0x0000808Bu), BBP_KP_RC(0x00000000u, 0x80000001u),
+                        BBP_KP_RC(0x80000000u, 0x80008081u), BBP_KP_RC(0x80000000u, 0x00008009u), BBP_KP_RC(0x00000000u, 0x0000008Au),
+                        BBP_KP_RC(0x00000000u, 0x00000088u), BBP_KP_RC(0x00000000u, 0x80008009u), BBP_KP_RC(0x00000000u, 0x8000000Au),
+                        BBP_KP_RC(0x00000000u, 0x8000808Bu), BBP_KP_RC(0x80000000u, 0x0000008Bu), BBP_KP_RC(0x80000000u, 0x00008089u),
+                        BBP_KP_RC(0x80000000u, 0x00008003u), BBP_KP_RC(0x80000000u, 0x00008002u), BBP_KP_RC(0x80000000u, 0x00000080u),
+                        BBP_KP_RC(0x00000000u, 0x0000800Au), BBP_KP_RC(0x80000000u, 0x8000000Au), BBP_KP_RC(0x80000000u, 0x80008081u),
+                        BBP_KP_RC(0x80000000u, 0x00008080u), BBP_KP_RC(0x00000000u, 0x80000001u), BBP_KP_RC(0x80000000u, 0x80008008u)};
+#undef BBP_KP_RC
+    const u64 k = RC[r];
+    a[0] = keccak_xorand_32(a[0], sel, (u32)(k >> 32)) ^ (u32)k;
+}
+
+#if defined(__HIPCC__)
+// the other lane of the pair: lane ^ 1, DPP quad_perm:[1,0,3,2].  Both lanes of a pair must be active.
+__device__ __forceinline__ u32 keccak_pair_partner(u32 v) { return (u32)__builtin_amdgcn_update_dpp(0, (int)v, 0xb1, 0xf, 0xf, true); }
+
+// Keccak-f[1600] on this lane's 25 half-words; sel = 0 in the even (low-word) lane, ~0 in the odd (high-word) lane
+__device__ __forceinline__ void keccak_f1600_pair(u32* a, u32 sel) {
+    for (int r = 0; r < 24; r++) {
+        u32 c[5], pc[5], pa[25];
+        keccak_pair_parity(a, c);
+#pragma unroll
+        for (int x = 0; x < 5; x++) pc[x] = keccak_pair_partner(c[x]);
+        keccak_pair_theta(a, c, pc);
+        pa[0] = 0;
+#pragma unroll
+        for (int i = 1; i < 25; i++) pa[i] = keccak_pair_partner(a[i]);
+        keccak_pair_rho_pi_chi(a, pa);
+        keccak_pair_iota(a, sel, r);
+    }
+}
+#endif
+
+// The plain-C model of a pair: lo[] is what the even lane holds, hi[] the odd lane; every partner read is a read of the other array
+// as it stood when the phase began.
+inline void keccak_f1600_pair_model(u32* lo, u32* hi) {
+    for (int r = 0; r < 24; r++) {
+        u32 cl[5], ch[5], pl[25], ph[25];
+        keccak_pair_parity(lo, cl);
+        keccak_pair_parity(hi, ch);
+        keccak_pair_theta(lo, cl, ch);
+        keccak_pair_theta(hi, ch, cl);
+        for (int i = 0; i < 25; i++) pl[i] = lo[i], ph[i] = hi[i];
+        keccak_pair_rho_pi_chi(lo, ph);
+        keccak_pair_rho_pi_chi(hi, pl);
+        keccak_pair_iota(lo, 0u, r);
+        keccak_pair_iota(hi, ~0u, r);
+    }
+}
+
+// The framing of one steady-state draw (merlin_rng_fill64_bulk's three lane XORs) on the words one lane of a pair owns
+BBP_HD void merlin_pair_draw_framing(u32* a, u32 sel) {
+    a[8] ^= sel ? 0x07410000u : 0x00401200u;
+    a[9] ^= sel ? 0u : 0x00000447u;
+    a[20] ^= sel ? 0x80000000u : 0u;
+}
+
+#if defined(__HIPCC__)
+// Pair form of merlin_rng_fill64_bulk.  Both lanes of the pair enter with the same full transcript and the same arguments; each keeps
+// its half, runs `count` draws, writes its own eight words of every draw (word 2i low, word 2i + 1 high: the one-lane layout), and one
+// exchange at the end leaves the same full state in both.  `odd` = this lane holds the high words.
+__device__ __forceinline__ bool merlin_rng_fill64_bulk_pair(merlin_transcript& t, u32 count, u32* out_words /* count * 16 */, u32 odd) {
+    if (t.pos != 64 || t.pos_begin != 0) return false;
+    const u32 sel = odd ? ~0u : 0u;
+    u32 a[25];
+#pragma unroll
+    for (int i = 0; i < 25; i++) a[i] = odd ? (u32)(t.st[i] >> 32) : (u32)t.st[i];
+    for (u32 c = 0; c < count; c++) {
+        merlin_pair_draw_framing(a, sel);  // (the lane's three words are loop invariants)
+        keccak_f1600_pair(a, sel);
+        u32* o = out_words + (size_t)c * 16 + odd;
+#pragma unroll
+        for (int i = 0; i < 8; i++) {
+            o[2 * i] = a[i];
+            a[i] = 0;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 25; i++) {
+        const u32 q = keccak_pair_partner(a[i]);
+        t.st[i] = odd ? ((u64)a[i] << 32) | q : ((u64)q << 32) | a[i];
+    }
+    t.cur_flags = BBP_FLAG_I | BBP_FLAG_A | BBP_FLAG_C;
+    return true;
+}
+#endif
+
+// ... and its model: the pair as two arrays, entered from and left to a full state
+inline bool merlin_rng_fill64_bulk_pair_model(merlin_transcript& t, u32 count, u32* out_words /* count * 16 */) {
+    if (t.pos != 64 || t.pos_begin != 0) return false;
+    u32 lo[25], hi[25];
+    for (int i = 0; i < 25; i++) lo[i] = (u32)t.st[i], hi[i] = (u32)(t.st[i] >> 32);
+    for (u32 c = 0; c < count; c++) {
+        merlin_pair_draw_framing(lo, 0u);
+        merlin_pair_draw_framing(hi, ~0u);
+        keccak_f1600_pair_model(lo, hi);
+        u32* o = out_words + (size_t)c * 16;
+        for (int i = 0; i < 8; i++) {
+            o[2 * i] = lo[i];      // what the even lane stores
+            o[2 * i + 1] = hi[i];  // what the odd lane stores
+            lo[i] = hi[i] = 0;
+        }
+    }
+    for (int i = 0; i < 25; i++) t.st[i] = ((u64)hi[i] << 32) | lo[i];
+    t.cur_flags = BBP_FLAG_I | BBP_FLAG_A | BBP_FLAG_C;
+    return true;
+}
+
 }  // namespace bbp

@@ -17,6 +17,12 @@ constexpr int PROVE_MAX_SLICES = 4;  // heavy-stage slices of one call, one stre
 #define BBP_PROVE_BUFS 5
 #endif
 constexpr int PROVE_BUFS = BBP_PROVE_BUFS;  // batch buffers: a dual-opening call uses buffer call % PROVE_BUFS, any other call & 1
+// -DBBP_SERIAL_PAIR=0 (experiment): the whole-chain form of k_open_serial on one lane per proof, as before round 27.  Shipped: two
+// adjacent lanes per proof, half a Keccak state each (keccak.h "pair form").
+#ifndef BBP_SERIAL_PAIR
+#define BBP_SERIAL_PAIR 1
+#endif
+constexpr uint32_t SERIAL_CHAIN_LANES = BBP_SERIAL_PAIR ? 2 : 1;  // lanes per proof of the whole serial draw chain
 
 struct ProveKnobs {
     int slices = 3;                   // BBP_SLICES (1..4): heavy-stage slices of a call that is not rotated
@@ -30,7 +36,10 @@ struct ProveKnobs {
     int rng_coop_idle_below = 2300;   // BBP_RNG_COOP_IDLE_BELOW: ... and up to this many when no earlier prove call is in flight; 0 = never
     int rng_dpp = 2;                  // BBP_RNG_DPP: cooperative chain 2 = half-word per lane (k_open_bulk50), 1 = word per lane (k_open_bulk8), 0 = 25 lanes (k_open_bulk)
     int rng_block = 0;                // BBP_RNG_BLOCK (64..1024, power of two): threads per cooperative workgroup; 0 = by size: 64 up to 128 proofs, 128 up to 256, 256 above
-    int serial_block = 64;            // BBP_SERIAL_BLOCK (64, 128 or 256): threads per workgroup of the one-lane-per-proof opening kernels
+    int serial_block = 64;            // BBP_SERIAL_BLOCK (64, 128 or 256): PROOFS per workgroup of the serial opening kernels.  The whole draw chain puts
+                                      // SERIAL_CHAIN_LANES lanes on a proof (ProvePlan::serial_chain_lanes()), so by default its workgroup is 128 lanes = two
+                                      // wavefronts, which a CU places on two SIMDs: a lone wavefront each, as before, and a 1024-proof call still fences
+                                      // 16 CUs (8 / 16 / 32 fenced CUs measured alike).  Counting lanes would have fenced 32.
     int serial_lds = 160 * 1024;      // BBP_SERIAL_LDS (0..160 KiB): LDS those kernels reserve to keep their CU to themselves; 0 = off
     int tr_wave_below = 32;           // BBP_TR_WAVE_BELOW: launches of at most this many proofs run the transcript kernels one proof per wavefront; 0 = never
     int ipa_wide_below = 32;          // BBP_IPA_WIDE_BELOW: launches of at most this many proofs run k_ipa_round on 1024 lanes per proof; 0 = never
@@ -150,7 +159,7 @@ struct ProvePlan {
     bool coop = false;           // the draw chain runs on a wavefront (or half of one) per proof
     Chain chain = SERIAL;
     uint32_t prefix_form = 0;    // k_open_serial's last argument: 0 the whole chain, 1 / 2 the prefix of a cooperative chain on a lane / a wavefront per proof
-    uint32_t serial_blk = 64;    // workgroup of the serial chain
+    uint32_t serial_blk = 64;    // proofs per workgroup of the serial chain (and its witness workgroups); its lanes: serial_chain_lanes()
     uint32_t cblk = 64;          // workgroup of k_open_bulk; the wavefront-per-proof chains take cblk_wave()
     bool rotate = false;         // the heavy stage runs unsliced on lane[heavy_stream]
     int heavy_stream = 0;
@@ -172,6 +181,7 @@ struct ProvePlan {
     // the draw buffer (bbp_ctx::raw) of the opening stage: one per stream that opens, so that stream order alone guards it
     int raw_index() const { return !open_on_chain ? open_stream : chain_stream == ROLE_SIDE ? 0 : 1 + heavy_stream; }
     uint32_t cblk_wave() const { return 2 * cblk > 1024u ? 1024u : 2 * cblk; }
+    uint32_t serial_chain_lanes() const { return SERIAL_CHAIN_LANES * serial_blk; }  // threads per workgroup of the whole-chain launch (at most 512)
     // slice i of a call of B proofs is [slice_first(B, i), slice_first(B, i + 1))
     uint32_t slice_first(uint32_t B, uint32_t i) const { return (uint32_t)(((uint64_t)B * i) / slices); }
 

@@ -259,7 +259,11 @@ __global__ BBP_LANE_KERNEL BBP_ENCODE_ATTR void k_encode_strided(u32 count, u32 
 
 __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& prefix, const u32* __restrict__ enc, const u8* __restrict__ entropy,
                              const sc* __restrict__ vb_all, u32* __restrict__ raw, merlin_transcript* __restrict__ tr_out,
-                             merlin_transcript* __restrict__ rng_out, bool coop, u32 wave) {
+                             merlin_transcript* __restrict__ rng_out, bool coop, u32 wave, u32 pair_lane) {
+    // pair_lane (whole chain only, prove_plan.h BBP_SERIAL_PAIR): 0 = this lane alone has proof p; 1 / 2 = the even / odd lane of the two
+    // that have it.  The two run everything up to the draw loop in lockstep on the same data, split the state there (keccak.h "pair
+    // form"), and the even one alone writes.
+    const bool writer = pair_lane != 2;
     merlin_transcript t = prefix;  // Transcript::new(b"BlindBidProofGadget") + r1cs_domain_sep (A.4)
     t.wave = wave;
     const u32* e = enc + (size_t)p * enc_words(m);
@@ -283,11 +287,16 @@ __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& pref
     {
         uint8_t b[64];
         merlin_rng_fill(r, b, 64);  // first draw leaves the sponge in the steady state the bulk path needs
-        bytes_to_words(rw, b, 16);
+        if (writer) bytes_to_words(rw, b, 16);
     }
     // the remaining 2 + 2 n1 draws: BBP_RNG_COOP (default) leaves them to the cooperative kernel (k_open_bulk, 25 lanes per sponge)
+#if BBP_SERIAL_PAIR
+    if (!coop) merlin_rng_fill64_bulk_pair(r, 2 + 2 * n1, rw + 16, pair_lane == 2 ? 1u : 0u);  // both lanes of the pair are here: p < B holds for both or neither
+#else
     if (!coop) merlin_rng_fill64_bulk(r, 2 + 2 * n1, rw + 16);
+#endif
     t.wave = r.wave = 0;  // (memory never holds the flag: every kernel sets it for itself)
+    if (!writer) return;
     tr_out[p] = t;
     rng_out[p] = r;
 }
@@ -295,8 +304,10 @@ __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& pref
 // The two strictly serial jobs of the opening stage in ONE launch: the first `rng_blocks` workgroups run the transcript opening +
 // the 2935 sequential rng draws of their proofs, the others interpret the gadget program of theirs.  Neither needs the other
 // (the V commitments only need k_witness_head), so the opening stage lasts max(36 ms, 6 ms) instead of their sum.
-// (BBP_RNG_COOP=0 path: one lane per proof does everything.  Default path: this kernel is launched with rng lanes only for the
-// transcript prefix -- V x m, "m", rng rekeys, first draw -- and k_open_bulk does the bulk of the draws and the witness.)
+// (BBP_RNG_COOP=0 path: the rng lanes of a proof do everything -- two adjacent lanes per proof, half a Keccak state each in the draw
+// loop (prove_plan.h BBP_SERIAL_PAIR, keccak.h "pair form"), so a workgroup of plan.serial_chain_lanes() lanes has serial_blk proofs.
+// Default path: this kernel is launched with rng lanes only, one per proof, for the transcript prefix -- V x m, "m", rng rekeys,
+// first draw -- and k_open_bulk does the bulk of the draws and the witness.)
 __global__ void k_open_serial(u32 B, u32 rng_blocks, u32 m, u32 n1, merlin_transcript prefix, const u32* __restrict__ enc,
                               const u8* __restrict__ entropy, const sc* __restrict__ vb_all, u32* __restrict__ raw,
                               merlin_transcript* __restrict__ tr_out, merlin_transcript* __restrict__ rng_out, u32 n_cst,
@@ -306,8 +317,10 @@ __global__ void k_open_serial(u32 B, u32 rng_blocks, u32 m, u32 n1, merlin_trans
     if (blockIdx.x < rng_blocks) {
         // coop: 0 = the whole draw chain here; 1 = the transcript prefix and the first draw only (the chain follows in k_open_bulk*);
         // 2 = the same with one proof per WAVEFRONT, every lane in lockstep, the permutations spread over the lanes
-        const u32 t = blockIdx.x * blockDim.x + threadIdx.x, p = coop == 2 ? t >> 6 : t;
-        if (p < B) tr_open_lane(p, m, n1, prefix, enc, entropy, vb_all, raw, tr_out, rng_out, coop != 0, coop == 2);
+        // (the whole chain, BBP_SERIAL_PAIR: two adjacent lanes per proof, live or dead together, so a pair's DPP reads always find their partner)
+        const u32 t = blockIdx.x * blockDim.x + threadIdx.x, pair = BBP_SERIAL_PAIR && coop == 0 ? 1u + (t & 1u) : 0u;
+        const u32 p = coop == 2 ? t >> 6 : pair ? t >> 1 : t;
+        if (p < B) tr_open_lane(p, m, n1, prefix, enc, entropy, vb_all, raw, tr_out, rng_out, coop != 0, coop == 2, pair);
     } else {
         const u32 p = (blockIdx.x - rng_blocks) * blockDim.x + threadIdx.x;
         if (p < B) witness_gates_lane(p, m, n1, n_cst, w_terms, w_loff, w_roff, cst_all, v_all, ai1_all, ao1_all);
@@ -1522,10 +1535,13 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
         return BBP_OK;
     };
     switch (plan.chain) {
-        case ProvePlan::SERIAL:
-            LAUNCH_LDS(ctx, TAG_RNG, k_open_serial, 2 * cdiv(B, plan.serial_blk), plan.serial_blk, hog, os, B, cdiv(B, plan.serial_blk), m, n1, prefix,
-                       bd.enc, ent_dev, bd.vb, raw, bd.tr, bd.rng, c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 0u);
+        case ProvePlan::SERIAL: {
+            // draw-chain workgroups of serial_blk proofs on SERIAL_CHAIN_LANES lanes each, then witness workgroups of one lane per proof
+            const u32 blk = plan.serial_chain_lanes(), nb_rng = cdiv(B, plan.serial_blk), nb_wit = cdiv(B, blk);
+            LAUNCH_LDS(ctx, TAG_RNG, k_open_serial, nb_rng + nb_wit, blk, hog, os, B, nb_rng, m, n1, prefix, bd.enc, ent_dev, bd.vb, raw, bd.tr, bd.rng,
+                       c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 0u);
             break;
+        }
         case ProvePlan::LANES25: rc = bulk(k_open_bulk, 32, plan.cblk); break;
         case ProvePlan::WORD: rc = bulk(k_open_bulk8, 64, plan.cblk_wave()); break;
         case ProvePlan::HALFWORD: rc = bulk(k_open_bulk50, 64, plan.cblk_wave()); break;
