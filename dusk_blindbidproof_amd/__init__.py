@@ -5,7 +5,7 @@ The library has no CPU compute path: importing works anywhere (so the C-ABI surf
 """
 from ._native import (Context, Pool, BbpError, lib, lib_path, STATUS, SIGNATURES, record_size, entropy_size,
                       LAYOUT_BLIND_G_H, LAYOUT_BLIND_G, BASE_BBLIND, BASE_G0, BASE_H0, BASE_B, NUM_BASES, STREAM_CONTEXT,
-                      compile_circuit, ENTROPY_PROVE, ENTROPY_VERIFY, ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE, ENTROPY_SOURCE_HEDGED, prove_row_size, verify_row_size,
+                      compile_circuit, ENTROPY_PROVE, ENTROPY_VERIFY, ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE, ENTROPY_SOURCE_HEDGED, BLINDING_DRAW_MERLIN, BLINDING_DRAW_EXPANDED, prove_row_size, verify_row_size,
                       mixed_row_offsets, pack_mixed_rows, round_row_size, round_table_offsets, pack_rounds, expand_round_rows, pack_round_bids,
                       ROUND_BID_BYTES, TABLE_GENS, TABLE_PTABLE, TABLE_COMB, TABLE_BTAB, TABLE_IDX_AI, TABLE_IDX_AO, TABLE_IDX_S1,
                       TABLE_IDX_IPA, TABLE_IDX_VER, VARBASE_LANES, VARBASE_PREP_SUM, VARBASE_MX_LANES, VARBASE_MX_PREP_SUM,
@@ -14,7 +14,7 @@ from ._native import (Context, Pool, BbpError, lib, lib_path, STATUS, SIGNATURES
 
 __all__ = ["Context", "Pool", "BbpError", "lib", "lib_path", "STATUS", "SIGNATURES", "record_size", "entropy_size",
            "LAYOUT_BLIND_G_H", "LAYOUT_BLIND_G", "BASE_BBLIND", "BASE_G0", "BASE_H0", "BASE_B", "NUM_BASES", "STREAM_CONTEXT", "compile_circuit",
-           "ENTROPY_PROVE", "ENTROPY_VERIFY", "ENTROPY_SOURCE_OS", "ENTROPY_SOURCE_DEVICE", "ENTROPY_SOURCE_HEDGED", "prove_row_size", "verify_row_size", "mixed_row_offsets",
+           "ENTROPY_PROVE", "ENTROPY_VERIFY", "ENTROPY_SOURCE_OS", "ENTROPY_SOURCE_DEVICE", "ENTROPY_SOURCE_HEDGED", "BLINDING_DRAW_MERLIN", "BLINDING_DRAW_EXPANDED", "prove_row_size", "verify_row_size", "mixed_row_offsets",
            "pack_mixed_rows", "round_row_size", "round_table_offsets", "pack_rounds", "expand_round_rows", "pack_round_bids", "ROUND_BID_BYTES",
            "TABLE_GENS", "TABLE_PTABLE", "TABLE_COMB", "TABLE_BTAB", "TABLE_IDX_AI", "TABLE_IDX_AO", "TABLE_IDX_S1", "TABLE_IDX_IPA",
            "TABLE_IDX_VER", "VARBASE_LANES", "VARBASE_PREP_SUM", "VARBASE_MX_LANES", "VARBASE_MX_PREP_SUM", "varbase_points",

@@ -19,6 +19,7 @@ BASE_BBLIND, BASE_G0, BASE_H0, BASE_B, NUM_BASES = 0, 1, 2049, 4097, 4098
 R1CS_PROOF_BYTES = 1121
 ENTROPY_PROVE, ENTROPY_VERIFY = 0, 1            # bbp_draw_entropy_dev kinds
 ENTROPY_SOURCE_OS, ENTROPY_SOURCE_DEVICE, ENTROPY_SOURCE_HEDGED = 0, 1, 2  # bbp_set_entropy_source
+BLINDING_DRAW_MERLIN, BLINDING_DRAW_EXPANDED = 0, 1  # bbp_set_blinding_draw
 TABLE_GENS, TABLE_PTABLE, TABLE_COMB, TABLE_BTAB = 0, 1, 2, 3  # bbp_debug_table
 TABLE_IDX_AI, TABLE_IDX_AO, TABLE_IDX_S1, TABLE_IDX_IPA, TABLE_IDX_VER = 4, 5, 6, 7, 8  # ... its index lists: which = list | N << 8
 VARBASE_LANES, VARBASE_PREP_SUM, VARBASE_MX_LANES, VARBASE_MX_PREP_SUM = 0, 1, 2, 3  # bbp_debug_varbase forms
@@ -113,6 +114,8 @@ SIGNATURES = {
     "bbp_draw_entropy_hedged_dev": (_i32, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "bbp_set_entropy_source": (_i32, [_vp, _i32]),
     "bbp_debug_next_entropy_key": (_i32, [_vp, _vp]),
+    "bbp_set_blinding_draw": (_i32, [_vp, _i32]),
+    "bbp_blinding_draw": (_i32, [_vp]),
     "bbp_set_secret_wipe": (_i32, [_vp, _i32]),
     "bbp_wipe_secrets": (_i32, [_vp]),
     "bbp_debug_secret_residue": (_i32, [_vp, ctypes.POINTER(_u64), ctypes.POINTER(_u64), _vp, _u32]),
@@ -986,6 +989,20 @@ class Context:
         src = {"os": ENTROPY_SOURCE_OS, "device": ENTROPY_SOURCE_DEVICE, "hedged": ENTROPY_SOURCE_HEDGED}.get(source, source)
         self._check(lib.bbp_set_entropy_source(self._h, src))
 
+    def set_blinding_draw(self, mode):
+        """How every proof's 3 + 2 n1 blinding scalars are drawn (bbp_set_blinding_draw): "merlin" / BLINDING_DRAW_MERLIN (default, one
+        Keccak permutation per draw, the oracles' bytes under injected entropy) or "expanded" / BLINDING_DRAW_EXPANDED (one key per proof
+        from its TranscriptRng, the draws from ChaCha20 blocks under it: other bytes, accepted by every verifier).  Holds for prove calls
+        made after it returns.  A pool: every member."""
+        m = {"merlin": BLINDING_DRAW_MERLIN, "expanded": BLINDING_DRAW_EXPANDED}.get(mode, mode)
+        if isinstance(m, bool) or not isinstance(m, int):
+            raise ValueError("blinding draw must be \"merlin\", \"expanded\" or one of the BLINDING_DRAW_* values")
+        self._check(lib.bbp_set_blinding_draw(self._h, m))
+
+    def blinding_draw(self):
+        """The setting of set_blinding_draw: BLINDING_DRAW_MERLIN or BLINDING_DRAW_EXPANDED (bbp_blinding_draw)."""
+        return lib.bbp_blinding_draw(self._h)
+
     def debug_next_entropy_key(self, key):
         """Test hook: the key of the next host-pointer call that draws on the device (bbp_debug_next_entropy_key)."""
         if len(key) != 32:
@@ -1168,6 +1185,10 @@ class Pool(Context):
     def set_entropy_source(self, source):
         """bbp_set_entropy_source on the pool: every member takes the setting."""
         super().set_entropy_source(source)
+
+    def set_blinding_draw(self, mode):
+        """bbp_set_blinding_draw on the pool: every member takes the setting."""
+        super().set_blinding_draw(mode)
 
     def set_secret_wipe(self, on):
         """bbp_set_secret_wipe on the pool: every member takes the setting, and the pool's combiner erases its gathered rows."""

@@ -110,11 +110,35 @@ extern "C" int32_t bbp_reserve(bbp_ctx* ctx, uint32_t max_batch, uint32_t N) {
                     const uint32_t dual_max = std::max((uint32_t)std::max(ctx->knobs.dual_open_below - 1, 0), ctx->knobs.deep_eligible(1) ? (uint32_t)ctx->knobs.rotate_deep_max : 0u);
                     for (auto& r : ctx->raw)
                         if (rc == BBP_OK) rc = dev_reserve(ctx, r, (size_t)std::min(B, dual_max) * (3 + 2 * (size_t)c->n_mul) * 64);
+                    // ... at the merlin draw's size whatever bbp_set_blinding_draw says (the expanded draw keeps 32 bytes per proof there: a
+                    // subset), side's too: a context reserved in one mode allocates nothing in the other
+                    if (rc == BBP_OK) rc = dev_reserve(ctx, ctx->raw[0], (size_t)B * (3 + 2 * (size_t)c->n_mul) * 64);
                 }
                 return rc;
             });
         return rc;
     });
+}
+
+// The blinding draw of prove calls (include/bbp.h "Expanded blinding draw"): the setting lives in the prove knobs, where plan_prove reads it.
+extern "C" int32_t bbp_set_blinding_draw(bbp_ctx* ctx, int32_t mode) {
+    if (!ctx || (mode != BBP_BLINDING_DRAW_MERLIN && mode != BBP_BLINDING_DRAW_EXPANDED)) return BBP_ERR_BAD_ARG;
+    for (bbp_ctx* m : ctx->members)
+        if (int32_t rc = bbp_set_blinding_draw(m, mode)) return rc;
+    return api_guard(ctx, [&]() -> int32_t {
+        ctx->knobs.blinding_draw = mode;
+        return BBP_OK;
+    });
+}
+
+extern "C" int32_t bbp_blinding_draw(bbp_ctx* ctx) {
+    if (!ctx) return -1;  // (the modes are 0 and 1: no status code fits here)
+    int32_t mode = -1;
+    api_guard(ctx, [&]() -> int32_t {
+        mode = ctx->knobs.blinding_draw;
+        return BBP_OK;
+    });
+    return mode;
 }
 
 extern "C" int32_t bbp_set_batching(bbp_ctx* ctx, uint32_t window_us, uint32_t max_batch) {

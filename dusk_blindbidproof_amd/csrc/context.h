@@ -87,6 +87,7 @@ struct bbp_ctx {
     hipStream_t copy = nullptr;            // the caller's ingest stream (bbp_context_copy_stream): never used by the engine
     hipStream_t side2 = nullptr;           // second opening stream: batches too small to fill three heavy slices alternate between the two
     bbp::ProveKnobs knobs;                 // how prove calls are scheduled (prove_plan.h): read from the environment by bbp_init ...
+                                           // (knobs.blinding_draw is no environment knob: bbp_set_blinding_draw writes it under the lock, capi_ctx.hip)
     bbp::ProveRuleState prove_state;       // ... and what the rules remember from call to call; prover.hip plans every call from the two
     bbp::VerifyKnobs vknobs;               // how verify calls are laid out and launched (verify_plan.h): read from the environment by bbp_init
     std::vector<hipStream_t> spare_streams;  // (experiment BBP_VL_SKIP: placeholders in the hardware-queue round-robin)

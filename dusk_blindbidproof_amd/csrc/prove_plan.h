@@ -51,6 +51,7 @@ struct ProveKnobs {
     int trace_prove = 0;              // BBP_TRACE_PROVE (present = on): one stderr line per prove call with its plan
     int open_on_chain = -1;           // BBP_OPEN_ON_CHAIN: a rotating call's opening stage runs on the stream of its heavy stage: 0 never, 1 every rotating call, unset (-1) = the calls of a deep pipeline, by hw_queues
     int hw_queues = 4;                // no environment name of its own: the hardware queues the process's HIP runtime was given, filled in by bbp_init (HIP's default)
+    int blinding_draw = 0;            // no environment name: the context's bbp_set_blinding_draw setting (include/bbp.h), 0 = MERLIN, 1 = EXPANDED
 
     // the one list of environment names; a null clamp takes the number as it is
     struct Env {
@@ -149,7 +150,10 @@ inline HeavyPlan plan_heavy(const ProveKnobs& k, uint32_t B) {
 enum StreamRole { ROLE_CALLER = 0, ROLE_SIDE, ROLE_LANE1, ROLE_LANE2, ROLE_LANE3, ROLE_COPY, ROLE_SIDE2, ROLE_COUNT };
 
 struct ProvePlan {
-    enum Chain { SERIAL, LANES25, WORD, HALFWORD };  // the draw chain: k_open_serial alone | k_open_bulk | k_open_bulk8 | k_open_bulk50
+    // the draw chain: k_open_serial alone | k_open_bulk | k_open_bulk8 | k_open_bulk50 | none: k_open_key, k_expand_draws, k_witness_gates
+    // (bbp_set_blinding_draw(EXPANDED): coop, serial_blk, cblk and the rng_coop* knobs then play no part, and prefix_form is k_open_key's:
+    // 2 = a wavefront per proof up to tr_wave_below proofs, 1 = a lane per proof)
+    enum Chain { SERIAL, LANES25, WORD, HALFWORD, EXPANDED };
     uint32_t call = 0;           // this call's index
     bool deep = false;           // taken as a call of a caller in deep mode
     bool behind_sliced = false;  // not small, and the last call's slices are still on the device: sliced and stream-ordered behind them
@@ -180,15 +184,17 @@ struct ProvePlan {
     }
     // the draw buffer (bbp_ctx::raw) of the opening stage: one per stream that opens, so that stream order alone guards it
     int raw_index() const { return !open_on_chain ? open_stream : chain_stream == ROLE_SIDE ? 0 : 1 + heavy_stream; }
+    // ... and its bytes for B proofs of n1 multipliers: every raw 64-byte draw, or under EXPANDED one 32-byte key per proof
+    size_t raw_bytes(uint32_t B, uint32_t n1) const { return chain == EXPANDED ? (size_t)32 * B : (size_t)64 * B * (3 + 2 * (size_t)n1); }
     uint32_t cblk_wave() const { return 2 * cblk > 1024u ? 1024u : 2 * cblk; }
     uint32_t serial_chain_lanes() const { return SERIAL_CHAIN_LANES * serial_blk; }  // threads per workgroup of the whole-chain launch (at most 512)
     // slice i of a call of B proofs is [slice_first(B, i), slice_first(B, i + 1))
     uint32_t slice_first(uint32_t B, uint32_t i) const { return (uint32_t)(((uint64_t)B * i) / slices); }
 
     std::string trace_line(uint32_t call_, uint32_t B, int inflight) const {
-        char buf[160];
-        snprintf(buf, sizeof buf, "prove call %u: B %u inflight %d deep %d behind_sliced %d dual %d rotate %d par %d coop %d\n", call_, B, inflight,
-                 (int)deep, (int)behind_sliced, (int)dual, (int)rotate, par, (int)coop);
+        char buf[176];
+        snprintf(buf, sizeof buf, "prove call %u: B %u inflight %d deep %d behind_sliced %d dual %d rotate %d par %d coop %d%s\n", call_, B, inflight,
+                 (int)deep, (int)behind_sliced, (int)dual, (int)rotate, par, (int)coop, chain == EXPANDED ? " draw expanded" : "");
         return buf;
     }
 };
@@ -223,6 +229,11 @@ ProvePlan plan_prove(const ProveKnobs& k, ProveRuleState& st, uint32_t B, int in
     if (p.rotate) p.slices = 0;
     p.open_on_chain = p.rotate && k.chain_rule(p.deep);
     p.chain_stream = !p.open_on_chain ? -1 : p.heavy_stream == 3 ? (int)ROLE_SIDE : (int)ROLE_LANE1 + p.heavy_stream - 1;
+    if (k.blinding_draw) {  // no draw chain: nothing of its form is decided; streams, rotation, slices, par and raw_index() stay as above
+        p.chain = ProvePlan::EXPANDED;
+        p.coop = false;
+        p.prefix_form = B <= (uint32_t)k.tr_wave_below ? 2u : 1u;
+    }
     return p;
 }
 

@@ -30,6 +30,7 @@
 #include <functional>
 
 #include "batch.h"
+#include "blinding_expand.h"
 #include "hosthash.h"
 #include "keccak_wave.h"
 #include "scalarmul.h"
@@ -257,6 +258,10 @@ __global__ BBP_LANE_KERNEL BBP_ENCODE_ATTR void k_encode_strided(u32 count, u32 
 // ---------------------------------------------------------------------------------------------------------------
 // (the enc block of a proof -- enc_words, enc_V, enc_A, enc_T, enc_LR -- is batch_layout.h's)
 
+// KEY (k_open_key, the EXPANDED blinding draw of blinding_expand.h): in place of the first draw, the 32-byte key of the proof's draws goes
+// to raw + 8 p, and no draw follows; coop and pair_lane play no part.  An instantiation of its own: k_open_serial's is KEY = false, the code it
+// had before there was a KEY.
+template <bool KEY>
 __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& prefix, const u32* __restrict__ enc, const u8* __restrict__ entropy,
                              const sc* __restrict__ vb_all, u32* __restrict__ raw, merlin_transcript* __restrict__ tr_out,
                              merlin_transcript* __restrict__ rng_out, bool coop, u32 wave, u32 pair_lane) {
@@ -281,6 +286,16 @@ __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& pref
     uint8_t seed[32];
     for (int i = 0; i < 32; i++) seed[i] = ent[i];
     merlin_rng_finalize(r, seed);
+    if constexpr (KEY) {
+        const ChachaKey key = blinding_key_squeeze(r);  // the rng goes on from here: k_tr_tblind's five draws
+        u32* kw = raw + 8 * (size_t)p;
+#pragma unroll
+        for (int i = 0; i < 8; i++) kw[i] = key.w[i];
+        t.wave = r.wave = 0;
+        tr_out[p] = t;
+        rng_out[p] = r;
+        return;
+    }
     // draws, in order: i_blinding1, o_blinding1, s_blinding1, s_L1[n1], s_R1[n1] (A.5 step 3).  Raw 64-byte outputs go
     // to `raw`; the wide reductions mod l run afterwards in k_reduce_draws, off this strictly sequential chain.
     u32* rw = raw + (size_t)p * (3 + 2 * (size_t)n1) * 16;
@@ -300,6 +315,10 @@ __device__ void tr_open_lane(u32 p, u32 m, u32 n1, const merlin_transcript& pref
     tr_out[p] = t;
     rng_out[p] = r;
 }
+// (instantiated here, where the function stood before it had a parameter: the compiler numbers its string constants in this order, and
+// tools/asm_functions_diff.py then finds every older kernel of this file unchanged)
+template __device__ void tr_open_lane<false>(u32, u32, u32, const merlin_transcript&, const u32* __restrict__, const u8* __restrict__, const sc* __restrict__,
+                                             u32* __restrict__, merlin_transcript* __restrict__, merlin_transcript* __restrict__, bool, u32, u32);
 
 // The two strictly serial jobs of the opening stage in ONE launch: the first `rng_blocks` workgroups run the transcript opening +
 // the 2935 sequential rng draws of their proofs, the others interpret the gadget program of theirs.  Neither needs the other
@@ -320,11 +339,21 @@ __global__ void k_open_serial(u32 B, u32 rng_blocks, u32 m, u32 n1, merlin_trans
         // (the whole chain, BBP_SERIAL_PAIR: two adjacent lanes per proof, live or dead together, so a pair's DPP reads always find their partner)
         const u32 t = blockIdx.x * blockDim.x + threadIdx.x, pair = BBP_SERIAL_PAIR && coop == 0 ? 1u + (t & 1u) : 0u;
         const u32 p = coop == 2 ? t >> 6 : pair ? t >> 1 : t;
-        if (p < B) tr_open_lane(p, m, n1, prefix, enc, entropy, vb_all, raw, tr_out, rng_out, coop != 0, coop == 2, pair);
+        if (p < B) tr_open_lane<false>(p, m, n1, prefix, enc, entropy, vb_all, raw, tr_out, rng_out, coop != 0, coop == 2, pair);
     } else {
         const u32 p = (blockIdx.x - rng_blocks) * blockDim.x + threadIdx.x;
         if (p < B) witness_gates_lane(p, m, n1, n_cst, w_terms, w_loff, w_roff, cst_all, v_all, ai1_all, ao1_all);
     }
+}
+
+// The EXPANDED blinding draw (bbp_set_blinding_draw, blinding_expand.h): k_open_serial's two prefix forms -- wave = 0 one lane per
+// proof, 1 one proof per wavefront in lockstep -- with the 32-byte key squeeze in place of the first 64-byte draw.  keys: 8 words per
+// proof at the front of the opening stream's draw buffer; k_expand_draws reads them.
+__global__ BBP_LANE_KERNEL void k_open_key(u32 B, u32 m, u32 n1, merlin_transcript prefix, const u32* __restrict__ enc, const u8* __restrict__ entropy,
+                                           const sc* __restrict__ vb_all, u32* __restrict__ keys, merlin_transcript* __restrict__ tr_out,
+                                           merlin_transcript* __restrict__ rng_out, u32 wave) {
+    const u32 t = blockIdx.x * blockDim.x + threadIdx.x, p = wave ? t >> 6 : t;
+    if (p < B) tr_open_lane<true>(p, m, n1, prefix, enc, entropy, vb_all, keys, tr_out, rng_out, true, wave, 0u);
 }
 
 // ---- cooperative Keccak: the TranscriptRng draw chain with 25 lanes per sponge --------------------------------------------------
@@ -612,6 +641,30 @@ __global__ void k_reduce_draws(u32 B, u32 n1, const u32* __restrict__ raw, sc* _
     sc v = sc_from_wide(w);
     sc* dst = j == 0 ? &ai1[(size_t)p * (1 + 2 * n1)] : j == 1 ? &ao1[(size_t)p * (1 + n1)] : &s1[(size_t)p * (1 + 2 * n1) + (j - 2)];
     st_sc(dst, v);
+}
+
+// EXPANDED: every draw of the launch is one ChaCha20 block under its proof's key, reduced and stored where k_reduce_draws puts the
+// merlin draw of that number (blinding_expand.h blinding_slot).  One lane per draw, consecutive lanes on consecutive draws of a proof
+// (k_draw_entropy's shape); no raw bytes in memory, no LDS, no atomics.
+__global__ void __launch_bounds__(64) k_expand_draws(u32 n_total, u32 n1, const u32* __restrict__ keys, sc* __restrict__ ai1, sc* __restrict__ ao1,
+                                                     sc* __restrict__ s1) {
+    const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g >= n_total) return;
+    const u32 per = blinding_draws(n1), p = g / per, j = g - p * per;
+    const uint4* kp = reinterpret_cast<const uint4*>(keys + 8 * (size_t)p);
+    const uint4 lo = kp[0], hi = kp[1];
+    const ChachaKey key = {{lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w}};
+    const BlindingSlot slot = blinding_slot(p, j, n1);
+    st_sc((slot.which == 0 ? ai1 : slot.which == 1 ? ao1 : s1) + slot.index, blinding_expand_draw(key, j));
+}
+
+// EXPANDED: the gates a_L, a_R, a_O in a launch of their own, one lane per proof (with a draw chain they run beside it, in its launch).
+// lds_bytes: the dynamic LDS the interpreter (native = 0) may stage its program in; the launch gives it none, so it reads the program
+// from global memory, and reserves no CU.
+__global__ BBP_LANE_KERNEL void k_witness_gates(u32 B, u32 m, u32 n1, u32 n_cst, const u32* __restrict__ w_terms, const u32* __restrict__ w_loff,
+                                                const u32* __restrict__ w_roff, const sc* __restrict__ cst_all, const sc* __restrict__ v_all,
+                                                sc* __restrict__ ai1_all, sc* __restrict__ ao1_all, u32 lds_bytes, u32 native) {
+    witness_gates_block(blockIdx.x * blockDim.x, B, m, n1, n_cst, w_terms, w_loff, w_roff, cst_all, v_all, ai1_all, ao1_all, lds_bytes, native);
 }
 
 // blindings from the entropy block: (4+N) 32-byte values, reduced
@@ -1489,7 +1542,7 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
     const u32 m = c.m, n1 = c.n_mul;
     const merlin_transcript prefix = prover_prefix();
     const size_t n_draws = 3 + 2 * (size_t)n1;
-    if ((rc = dev_reserve(ctx, ctx->raw[ridx], (size_t)B * n_draws * 64))) return rc;
+    if ((rc = dev_reserve(ctx, ctx->raw[ridx], plan.raw_bytes(B, n1)))) return rc;
     u32* const raw = (u32*)ctx->raw[ridx].p;
     BBP_HIP_TRY(ctx, hipEventRecord(ctx->ev_entry[par], s));
     // 3. OPENING stage, on `os`.  It does NOT wait for the caller's stream: in_dev / ent_dev must be complete when the call is made
@@ -1545,11 +1598,23 @@ int32_t prove_batch_dev(bbp_ctx* ctx, u32 B, u32 N, const u8* in_dev, const u8* 
         case ProvePlan::LANES25: rc = bulk(k_open_bulk, 32, plan.cblk); break;
         case ProvePlan::WORD: rc = bulk(k_open_bulk8, 64, plan.cblk_wave()); break;
         case ProvePlan::HALFWORD: rc = bulk(k_open_bulk50, 64, plan.cblk_wave()); break;
+        case ProvePlan::EXPANDED: {
+            // no chain (bbp_set_blinding_draw, blinding_expand.h): the prefix squeezes a key per proof into the front of the draw buffer,
+            // one flat launch expands and reduces every draw into its slot, and the gates get a launch of their own -- nothing here runs
+            // long enough to fence a CU for
+            const u32 pgrid = plan.prefix_form == 2 ? B : cdiv(B, 64);
+            LAUNCH(ctx, TAG_RNG, k_open_key, pgrid, 64, os, B, m, n1, prefix, bd.enc, ent_dev, bd.vb, raw, bd.tr, bd.rng, plan.prefix_form == 2 ? 1u : 0u);
+            LAUNCH(ctx, TAG_RNG, k_expand_draws, cdiv((u32)(B * n_draws), 64), 64, os, (u32)(B * n_draws), n1, (const u32*)raw, bd.ai1, bd.ao1, bd.s1);
+            LAUNCH(ctx, TAG_WITNESS, k_witness_gates, cdiv(B, 64), 64, os, B, m, n1, c.n_cst, c.w_terms, c.w_loff, c.w_roff, bd.cst, bd.v, bd.ai1, bd.ao1, 0u,
+                   (u32)ctx->knobs.witness_native);
+            break;
+        }
     }
     if (rc) return rc;
     // (k_open_bulk50 writes the draws as bit-interleaved halves)
-    LAUNCH(ctx, TAG_RNG, k_reduce_draws, cdiv((u32)(B * n_draws), 128), 128, os, B, n1, (const u32*)raw, bd.ai1, bd.ao1, bd.s1,
-           plan.chain == ProvePlan::HALFWORD ? 1u : 0u);
+    if (plan.chain != ProvePlan::EXPANDED)
+        LAUNCH(ctx, TAG_RNG, k_reduce_draws, cdiv((u32)(B * n_draws), 128), 128, os, B, n1, (const u32*)raw, bd.ai1, bd.ao1, bd.s1,
+               plan.chain == ProvePlan::HALFWORD ? 1u : 0u);
     if (wipe_on(ctx)) {  // secret wiping: the draws are reduced; their buffer is the opening stream's own, stream order guards it
         WipeList wl;
         wipe_take(wl, ctx->raw[ridx]);

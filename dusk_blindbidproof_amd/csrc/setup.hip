@@ -523,6 +523,11 @@ extern "C" int32_t bbp_describe(bbp_ctx* ctx, char* buf, uint32_t cap) {
                                       : ctx->entropy_source == BBP_ENTROPY_SOURCE_DEVICE
                                           ? "device (one 32-byte OS key per call, expanded with ChaCha20 on the device)"
                                           : "os (the calling thread reads /dev/urandom and reduces the blindings on the host)");
+        if (off + 1 < cap)
+            off += (uint32_t)snprintf(buf + off, cap - off, "blinding draw: %s\n",
+                                      ctx->knobs.blinding_draw == BBP_BLINDING_DRAW_EXPANDED
+                                          ? "expanded (one 32-byte key per proof from its TranscriptRng, the 3 + 2 n1 blinding scalars from ChaCha20 blocks under it)"
+                                          : "merlin (every blinding scalar from the TranscriptRng, one Keccak permutation per draw)");
         if (free_b < ((size_t)6 << 30) && off + 1 < cap)
             off += (uint32_t)snprintf(buf + off, cap - off, "WARNING: less than 6 GiB of device memory free: a 1024-proof batch needs ~14 GiB of scratch\n");
         return BBP_OK;

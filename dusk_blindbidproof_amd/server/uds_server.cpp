@@ -647,7 +647,7 @@ static void usage(const char* argv0) {
             "usage: %s [-b|--bind-path PATH] [-l|--log-level error|warn|info|debug|trace] [--engine LIB.so] [--device N | --devices 0,1,.. | --devices all]\n"
             "          [--window-us US] [--max-batch B] [--max-connections C] [--io-threads T] [--reserve N[,N..]] [--verify-aggregate G]\n"
             "          [--check-proofs] [--entropy os|device|hedged] [--verify-mixing on|off] [--verify-rounds on|off]\n"
-            "          [--pipeline-depth D] [--max-inflight M] [--wipe-secrets]\n"
+            "          [--pipeline-depth D] [--max-inflight M] [--wipe-secrets] [--blinding-draw merlin|expanded]\n"
             "  --pipeline-depth D  requests of ONE connection with the engine at once, replies in request order (1..4096, default 64;\n"
             "                      1 = one request per connection at a time)\n"
             "  --max-inflight M    beyond each connection's first request, requests are admitted only while fewer than M are with\n"
@@ -670,6 +670,7 @@ int main(int argc, char** argv) {
     bool wipe_secrets = false;  // --wipe-secrets: no witness, blinding or key outlives its call in engine memory (bbp_set_secret_wipe); the SIGTERM path erases through bbp_free
     int verify_mixing = -1;  // --verify-mixing on|off: opcode-2 requests share device calls across bid-list lengths (bbp_set_verify_mixing); -1 = not given, the engine's default (on)
     int verify_rounds = -1;  // --verify-rounds on|off: opcode-2 requests with a byte-equal seed and bid list share one rounds call (bbp_set_verify_round_sharing); -1 = not given, no call is made (the engine's default: off)
+    int blinding_draw = -1;  // --blinding-draw merlin|expanded: how every proof's blinding scalars are drawn (bbp_set_blinding_draw); -1 = not given, no call is made (the engine's default: merlin)
     for (int i = 1; i < argc; i++) {
         std::string a = argv[i];
         auto val = [&]() -> const char* {
@@ -732,6 +733,14 @@ int main(int argc, char** argv) {
                 return 2;
             }
             verify_rounds = v == "on";
+        }
+        else if (a == "--blinding-draw") {
+            const std::string v = val();
+            if (v != "merlin" && v != "expanded") {
+                usage(argv[0]);
+                return 2;
+            }
+            blinding_draw = v == "expanded" ? BBP_BLINDING_DRAW_EXPANDED : BBP_BLINDING_DRAW_MERLIN;
         }
         else if (a == "--reserve") {
             for (const char* p = val(); *p;) {
@@ -842,6 +851,21 @@ int main(int argc, char** argv) {
             else
                 logf(2, "verify round sharing %s: opcode-2 requests %s", verify_rounds ? "on" : "off",
                      verify_rounds ? "with a byte-equal seed and bid list share one rounds call, the round sent once" : "each carry their seed and bid list to the device");
+        }
+        if (blinding_draw >= 0) {  // resolved only when asked for; an engine without the call draws as merlin does, which every verifier accepts just the same
+            const char* name = blinding_draw == BBP_BLINDING_DRAW_EXPANDED ? "expanded" : "merlin";
+            auto set_draw = (decltype(&bbp_set_blinding_draw))dlsym(g_eng.so, "bbp_set_blinding_draw");
+            if (set_draw && set_draw(g_eng.ctx, blinding_draw) != BBP_OK) {
+                logf(0, "--blinding-draw %s: the engine %s refused the setting (bbp_set_blinding_draw)", name, engine_path.c_str());
+                g_eng.free_(g_eng.ctx);
+                return 2;
+            }
+            if (!set_draw)
+                logf(1, "--blinding-draw %s: the engine %s has no such setting (bbp_set_blinding_draw); every proof's blinding scalars come from its TranscriptRng", name,
+                     engine_path.c_str());
+            else
+                logf(2, "blinding draw %s: opcode-1 proofs draw their blinding scalars %s", name,
+                     blinding_draw == BBP_BLINDING_DRAW_EXPANDED ? "from ChaCha20 blocks under a key of the proof's TranscriptRng" : "from the proof's TranscriptRng, one by one");
         }
         if (g_eng.describe) {  // what the engine runs on; its WARNING lines (hardware queues, memory) at warn level
             static char report[8192];

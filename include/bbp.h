@@ -862,6 +862,41 @@ int32_t bbp_draw_entropy_hedged_dev(bbp_ctx* ctx, uint32_t B, uint32_t N, const 
  * so that its records can be compared with an explicit-entropy call; consumed by that call.  A pool refuses it (take a member). */
 int32_t bbp_debug_next_entropy_key(bbp_ctx* ctx, const uint8_t key32[32]);
 
+/* ---- Expanded blinding draw -------------------------------------------------------------------------------------------------------
+ * Every proof draws 3 + 2 n1 blinding scalars after its commitments: i_blinding1, o_blinding1, s_blinding1, s_L[n1], s_R[n1] (n1 the
+ * circuit's multipliers, 1442 + 3 N: 2935 draws at N = 8, 4099 at N = 202).  merlin's TranscriptRng gives one Keccak-f[1600] per draw,
+ * each permutation feeding the next: the one stretch of a prove call that no batch parallelism shortens.  The protocol needs these
+ * scalars uniform and secret, not merlin's bytes, and the reference's bytes are not reproducible either (its rng is finalised with 32
+ * bytes of thread_rng).  This setting chooses how they are drawn, for every prove entry point of the context (bbp_prove[_async],
+ * bbp_prove_batch[_dev], bbp_prove_batch_checked_dev and checked proving's second attempt, bbp_prove_round[_dev], bbp_prove_round_select,
+ * the combiner's batches):
+ *   BBP_BLINDING_DRAW_MERLIN    (default) draw j = rng.fill_bytes(64) mod l, as the reference and the oracles draw
+ *   BBP_BLINDING_DRAW_EXPANDED  1. transcript and TranscriptRng exactly as under MERLIN: the rng is cloned from the transcript after the
+ *                                  "m" message, rekeyed with every v_blinding ("v_blinding", 32 canonical bytes each, in commit order)
+ *                                  and finalised ("rng") with the row's 32-byte seed
+ *                               2. key = rng.fill_bytes(32): merlin's ordinary draw, meta-AD of u32le(32), PRF of 32 bytes
+ *                               3. draw j, 0 <= j < 3 + 2 n1 = the 64-byte ChaCha20 block (RFC 8439 2.3) under key, block counter j,
+ *                                  nonce words ("BBPX" as a little-endian word, 0, 0), its 16 little-endian words read as one integer
+ *                                  mod l (from_bytes_mod_order_wide); j = 0 i_blinding1, 1 o_blinding1, 2 s_blinding1, 3 + i s_L[i],
+ *                                  3 + n1 + i s_R[i]: the order of the merlin draws
+ *                               4. every later draw (the five t blindings) comes from the same rng, continuing after step 2
+ *                               Commitments, challenges, the record layout and the entropy row layout stay as they are.
+ *   - What the key depends on: the transcript (every commitment), every v_blinding and the external 32 bytes, through merlin's own
+ *     construction.  merlin's hedge is kept: with a repeated or known seed the key still differs with the witness blindings, and with
+ *     repeated blindings it still differs with the seed.
+ *   - What is given up: under injected entropy an EXPANDED record is NOT the C oracle's or the reference's bytes (A_I1, A_O1, S1 and
+ *     everything after them differ; the 4 + N commitments are equal).
+ *   - What is kept: every verifier accepts the record (the verifier never sees how a blinding was drawn), and the record is deterministic
+ *     under injected entropy (tests/expanded_draw_model.py restates the draw; tests/golden/proofs_expanded_draw.json holds records).
+ *   - The default is MERLIN, with byte parity under injected entropy as before.
+ * The setter takes the context lock and holds for prove calls planned after it returns; on a pool it applies to every member.  Anything
+ * but the two modes: BBP_ERR_BAD_ARG, nothing changes.  bbp_blinding_draw reads the setting back (-1 for a NULL context); bbp_describe
+ * names it.  bbp_reserve covers both modes whichever is set: the expanded draw needs a subset of the merlin draw's scratch. */
+#define BBP_BLINDING_DRAW_MERLIN 0
+#define BBP_BLINDING_DRAW_EXPANDED 1
+int32_t bbp_set_blinding_draw(bbp_ctx* ctx, int32_t mode);
+int32_t bbp_blinding_draw(bbp_ctx* ctx);
+
 /* ---- Secret wiping ------------------------------------------------------------------------------------------------------------------
  * The engine proves with the bidder's secrets -- d, k, y, y^-1, the toggle, every commitment blinding, the TranscriptRng seed, a call's
  * entropy key and its hedged row keys -- and by default keeps what it computed in its batch buffers, MSM scratch, draw buffers,
